@@ -21,10 +21,15 @@ runs T x N pointers over the global table, each rank sweeps what falls in its re
 left out), ONE RCCL all-reduce of the per-round moment vectors serves the whole batch, and one launch replays the stop
 rules.  `value` is GLOBAL queries per second (a query over N regions counts once).
 
-Output: the LAST stdout line is one compact JSON object (< 3 KB: metric, value, roofline, roofline_hbm,
-cpu_baseline); everything else — per-configuration lines, cold staging, open loop, every CPU leg — goes to
-bench_report.json (repo root, and gpurun_out/ when present) and, one object per line, to stderr.
-`--headline-only` skips those.
+A plain run sets up, warms up, times the K steps and prints the result line; `--dump-outputs DIR` then also writes
+the results of the last timed step's launches to DIR/<field>.npy (float64, one row per launch, one column per query).
+
+Output: the LAST stdout line is one compact JSON object (< 3 KB: metric, value, unit, ms_per_step, ...).  `--full`
+adds everything else the bench measures: the launch's roofline, the single query, the packed layout, the open loop,
+the early-termination reading, the per-configuration lines, cold staging and the CPU baselines.  It puts `roofline`,
+`roofline_hbm` and `cpu_baseline` on the line and the rest into bench_report.json (repo root, and a second copy in an
+output folder when one is present) and, one object per line, on stderr.
+`--full --headline-only` keeps the roofline and the single query but skips the rest.
 """
 from __future__ import annotations
 
@@ -58,8 +63,10 @@ def parse():
     ap.add_argument("--rows-per-gpu", type=int, default=ROWS_PER_GPU)
     ap.add_argument("--error-percent", type=float, default=0.01, help="--e of the reference CLI, in percent")
     ap.add_argument("--batch", type=int, default=32, help="independent queries per step (one launch serves them all)")
+    ap.add_argument("--full", action="store_true", help="also measure everything besides the headline (roofline, configs, cold, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the results of the last timed step to DIR/<field>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="skip configs / cold / early-termination reading / cpu baseline")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: skip configs / cold / early-termination reading / cpu baseline")
     ap.add_argument("--no-configs", action="store_true", help="skip the per-configuration list (100 M and 1 B-row tables)")
     ap.add_argument("--max-config-rows", type=int, default=1_000_000_000)
     ap.add_argument("--cpu-sample-rows", type=int, default=2_000_000)
@@ -472,16 +479,18 @@ def _r(x, nd=4):
     return None if x is None else (round(x, nd) if isinstance(x, float) else x)
 
 
-def compact_line(rep: dict) -> dict:
-    """bench_report.json -> the one line on stdout: the contract's keys, `roofline`, `roofline_hbm`, `cpu_baseline`."""
-    cfg, rf = rep["config"], rep["roofline"]
+def compact_line(rep: dict, report: bool = True) -> dict:
+    """bench_report.json -> the one line on stdout: the contract's keys, `roofline`, `roofline_hbm`, `cpu_baseline`
+    (the last three only when the report has them: a plain run measures the headline alone and writes no report)."""
+    cfg, rf = rep["config"], rep.get("roofline")
     line = {k: rep[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                 "vs_baseline", "dtype", "data")}
     line["value"], line["ms_per_step"] = _r(line["value"], 1), _r(line["ms_per_step"], 4)
     line["config"] = {k: cfg[k] for k in ("workload", "rows_per_gpu", "global_rows", "queries_per_step", "launches_per_step", "queries_per_launch",
                                           "samples_per_query_per_gpu", "collectives_per_step", "collective") if k in cfg}
-    line["roofline"] = {k: _r(rf.get(k), 4 if k == "frac" else 1) for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "basis",
-                                                                            "algorithmic_bytes_per_launch", "unique_bytes_per_launch", "avg_launch_us", "l2_rate_GBps")}
+    if rf:
+        line["roofline"] = {k: _r(rf.get(k), 4 if k == "frac" else 1) for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "basis",
+                                                                                "algorithmic_bytes_per_launch", "unique_bytes_per_launch", "avg_launch_us", "l2_rate_GBps")}
     if rep.get("roofline_hbm"):
         line["roofline_hbm"] = [{k: _r(c.get(k), 4 if k == "frac" else 1) for k in ("case", "kernel", "avg_launch_us", "algorithmic_bytes", "achieved", "frac")}
                                 for c in rep["roofline_hbm"][:4]]
@@ -501,7 +510,8 @@ def compact_line(rep: dict) -> dict:
         line["scaling_detail"] = {"rows_swept_per_sec": _r(rep.get("rows_swept_per_sec"), 0), "region_aggregates_per_sec": _r(rep.get("region_aggregates_per_sec"), 1),
                                   "note": "weak: every rank holds rows_per_gpu rows (the table grows with N); value = completed queries over the GLOBAL table, "
                                           "each one sweep per rank + one collective per batch: ideal is value constant in N while rows_swept_per_sec grows N-fold"}
-    line["report"] = "bench_report.json"
+    if report:
+        line["report"] = "bench_report.json"
     if len(json.dumps(line)) > LINE_LIMIT:  # never let a long string cost the driver the whole line
         line["config"]["workload"] = line["config"]["workload"][:200]
         line.pop("single_query", None)
@@ -524,6 +534,23 @@ def write_report(rep: dict):
         elif isinstance(v, dict):
             print(json.dumps({k: v}), file=sys.stderr)
     sys.stderr.flush()
+
+
+# What a caller of the timed path receives per query (aqe_result), less kernel_ms (a timing, not a result)
+DUMP_FIELDS = ("value", "ci_lower", "ci_upper", "margin", "sum", "sumsq", "mean", "m2", "n", "visited", "topup", "converged", "rounds",
+               "bytes_algorithmic", "device_status", "topup_pending")
+DUMP_LIMIT = 64 << 20  # bytes, all files together
+
+
+def dump_outputs(out_dir, launches) -> None:
+    """The results of the timed loop's last step (its launches in order, each a list of the batch's results) as
+    out_dir/<field>.npy: float64 [launches, queries].  Past DUMP_LIMIT only the step's last launches are written."""
+    import numpy as np
+    per_launch = 8 * len(DUMP_FIELDS) * len(launches[0])
+    launches = launches[-max(1, DUMP_LIMIT // per_launch):]
+    os.makedirs(out_dir, exist_ok=True)
+    for f in DUMP_FIELDS:
+        np.save(os.path.join(out_dir, f + ".npy"), np.array([[getattr(r, f) for r in rs] for rs in launches], dtype=np.float64))
 
 
 def c_host_closed_loop(rows: int, reps: int = 300):
@@ -583,7 +610,9 @@ def main():
     e = args.error_percent
     pct = e_to_pct(e)
     B = max(1, args.batch)
-    extras = not args.headline_only
+    L = max(1, args.launches_per_step)
+    full = args.full
+    extras = full and not args.headline_only
 
     eng = Engine(local_rank)
     eng.generate_synthetic(hi - lo, shard_lo=lo, n_global=n_global, seed=SEED, keep_aos=False)
@@ -595,10 +624,11 @@ def main():
     st = side[0].cuda_stream
     q_one = make_query(nat.M_CLT_DUAL_POINTER, pct, agg=nat.AVG, confidence_level=0.95, check_interval=10,
                        num_threads=4 * world, max_error_percent=e, clt_round0=CLT_ROUND0, clt_growth=CLT_GROWTH)
-    plan_one = eng.plan(q_one)
+    plan_one = eng.plan(q_one) if full else None
     plan_sets = [[eng.plan(q) for q in batch_queries(e)] for _ in range(2)]
     natives = [Batch(ps) for ps in plan_sets]
     pipe = None
+    last_step = None  # a list during the timed loop's last step: what its launches return (--dump-outputs)
 
     with torch.cuda.stream(side[0]):
         if use_dist:
@@ -633,11 +663,15 @@ def main():
                 done = pipe.enqueue()
                 if done is not None:
                     k_state["results"] = done.fetch()
+                    if last_step is not None:
+                        last_step.append(k_state["results"])
 
             def drain():
                 done = pipe.flush()
                 if done is not None:
                     k_state["results"] = done.fetch()
+                    if last_step is not None:
+                        last_step.append(k_state["results"])
                 return k_state["results"]
 
             def one():            # one batch, start to end (profiling / latency)
@@ -651,12 +685,16 @@ def main():
                 natives[k % 2].enqueue_all(side[k % 2].cuda_stream)
                 if k > 0:
                     k_state["results"] = natives[(k - 1) % 2].fetch()
+                    if last_step is not None:
+                        last_step.append(k_state["results"])
                 k_state["k"] = k + 1
 
             def drain():
                 k = k_state["k"]
                 if k > 0:
                     k_state["results"] = natives[(k - 1) % 2].fetch()
+                    if last_step is not None:
+                        last_step.append(k_state["results"])
                 return k_state["results"]
 
             def one():
@@ -670,39 +708,40 @@ def main():
                 dist.barrier()
             torch.cuda.synchronize()
 
-        # ---- reference answers of the batch's queries, each as a launch of its own (single GPU) ----
-        for _ in range(3):
-            step()
-        firsts = drain()
-        fence()
+        if full:  # the checks and per-launch figures besides the headline
+            # ---- reference answers of the batch's queries, each as a launch of its own (single GPU) ----
+            for _ in range(3):
+                step()
+            firsts = drain()
+            fence()
 
-        # ---- roofline of the dominant kernel (k_sweep_lean_multi): ONE batch in flight, the launch's own begin/end
-        #      timestamps (event pair attached to the dispatch), before the throughput loop ----
-        prof_steps = 100
-        own_h = fresh_stream()
-        if not use_dist:
-            def one():  # (the timed launches on a stream of their own: see CASES)
-                natives[0].enqueue_all(own_h.cuda_stream)
-        natives[0].set_profiling(True)
-        ms_sum, ms_min, swept, wgs = 0.0, 1e9, 0, 0
-        for _ in range(prof_steps):
-            one()
-            if use_dist:
-                fence()
-            else:
-                natives[0].fetch()
-            ms, swept, wgs = natives[0].launch_info()
-            ms_sum += ms
-            ms_min = min(ms_min, ms)
-        natives[0].set_profiling(False)
-        avg_launch_ms = ms_sum / prof_steps
-        batch_kernel = nat.KERNEL_NAMES.get(plan_sets[0][0].last_kernel(), "?")  # k_sweep_lean_multi when every plan of the batch qualifies
-        bytes_per_launch = 8.0 * swept
-        torch.cuda.synchronize()
-        if not use_dist:
-            log_case(f"HEADLINE 10M: batch of {B} CLT e={e}% queries in ONE launch (executed bytes; see roofline for what is priced)", batch_kernel, prof_steps, prof_steps,
-                     bytes_per_launch, 1e3 * avg_launch_ms)
-        achieved = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9
+            # ---- roofline of the dominant kernel (k_sweep_lean_multi): ONE batch in flight, the launch's own begin/end
+            #      timestamps (event pair attached to the dispatch), before the throughput loop ----
+            prof_steps = 100
+            own_h = fresh_stream()
+            if not use_dist:
+                def one():  # (the timed launches on a stream of their own: see CASES)
+                    natives[0].enqueue_all(own_h.cuda_stream)
+            natives[0].set_profiling(True)
+            ms_sum, ms_min, swept, wgs = 0.0, 1e9, 0, 0
+            for _ in range(prof_steps):
+                one()
+                if use_dist:
+                    fence()
+                else:
+                    natives[0].fetch()
+                ms, swept, wgs = natives[0].launch_info()
+                ms_sum += ms
+                ms_min = min(ms_min, ms)
+            natives[0].set_profiling(False)
+            avg_launch_ms = ms_sum / prof_steps
+            batch_kernel = nat.KERNEL_NAMES.get(plan_sets[0][0].last_kernel(), "?")  # k_sweep_lean_multi when every plan of the batch qualifies
+            bytes_per_launch = 8.0 * swept
+            torch.cuda.synchronize()
+            if not use_dist:
+                log_case(f"HEADLINE 10M: batch of {B} CLT e={e}% queries in ONE launch (executed bytes; see roofline for what is priced)", batch_kernel, prof_steps, prof_steps,
+                         bytes_per_launch, 1e3 * avg_launch_ms)
+            achieved = bytes_per_launch / (avg_launch_ms * 1e-3) / 1e9
 
         # ---- the same batch with the XCD alignment of the groups turned off (AQE_MULTI_LAYOUT=packed): the layout in which
         #      the queries of a batch do not meet in a compute die's L2 and the fabric moves what the loads ask for ----
@@ -733,7 +772,7 @@ def main():
 
         # ---- a single query on the whole chip (k_sweep_lean), one in flight: launch time and closed loop ----
         single = None
-        if not use_dist:
+        if not use_dist and full:
             own_s = fresh_stream()
             torch.cuda.synchronize()
             plan_one.set_profiling(True)
@@ -833,33 +872,41 @@ def main():
                     p_.close()
 
         # ---- the timed region: K steps of L launches each, every result fetched ----
-        L = max(1, args.launches_per_step)
         for _ in range(max(args.warmup, 1) * L):
             step()
         drain()
         fence()
         k_state["k"] = 0
         t0 = time.perf_counter()
-        for _ in range(args.steps * L):
+        for _ in range((args.steps - 1) * L):
+            step()
+        # the last step keeps what its launches return; held only that long, the results add no work to the other steps
+        last_step = []
+        for _ in range(L):
             step()
         lasts = drain()
         fence()
         dt = time.perf_counter() - t0
+        last_step = last_step[-L:]  # (the step's first fetch returned the launch before it)
         if use_dist:
             t = torch.tensor([dt], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         last = lasts[0]
-        agree = all((a.n, a.visited, a.rounds, a.converged) == (b_.n, b_.visited, b_.rounds, b_.converged) and a.value == b_.value
-                    for a, b_ in zip(firsts[: len(lasts)], lasts)) if not use_dist else True
-        assert agree, "results of the timed loop differ from the first execution's"
+        agree = None
+        if full:
+            agree = all((a.n, a.visited, a.rounds, a.converged) == (b_.n, b_.visited, b_.rounds, b_.converged) and a.value == b_.value
+                        for a, b_ in zip(firsts[: len(lasts)], lasts)) if not use_dist else True
+            assert agree, "results of the timed loop differ from the first execution's"
+        else:
+            _, swept, wgs = natives[0].launch_info(False)  # rows swept per launch (the roofline loop reads them in a --full run)
 
     # HBM-side traffic of the sweep kernel: a PMC measurement (FETCH_SIZE + WRITE_SIZE in their own rocprofv3 passes,
     # gfx950 correction calibrated on a known 80 MB scan) cannot be taken inside this process; the committed value in
     # profiles/ is reported only when it was measured on these very sources and this workload.
     traffic, traffic_src, packed_traffic = None, None, None
     try:
-        if not use_dist and rows == ROWS_PER_GPU and e == 0.01:
+        if full and not use_dist and rows == ROWS_PER_GPU and e == 0.01:
             doc = json.loads(PMC_FILE.read_text())
             if doc.get("source_hash") == source_hash() and doc.get("batch") == B:
                 traffic = doc["batch_traffic_bytes_per_launch"]
@@ -871,24 +918,28 @@ def main():
         traffic = None
 
     if rank == 0:
-        qs0 = batch_queries(e)
-        # algorithmic bytes: 8 B per row the SUM / AVG queries sample (COUNT is metadata, SURVEY 8d: 0 B although the
-        # reference — and this launch — run the sampler for it); executed: every load of every query
-        per_q = [int(r.visited) for r in firsts[:B]] if not use_dist else [int(swept // B)] * B
-        alg_bytes = 8.0 * sum(v for q_, v in zip(qs0, per_q) if q_.agg != nat.COUNT)
-        try:
-            uniq_bytes = 8.0 * unique_sampled_rows(nat, qs0, n_global, lo, hi)
-        except Exception:
-            uniq_bytes = 8.0 * (hi - lo)  # every row of the shard at most once
-        roof = headline_roofline(batch_kernel, 1e3 * avg_launch_ms, alg_bytes, uniq_bytes, traffic, bytes_per_launch, traffic_src)
-        roof.update({"min_launch_us": 1e3 * ms_min, "queries_per_launch": B, "workgroups": int(wgs), "launches_timed": prof_steps,
-                     "executed_bytes_per_launch": bytes_per_launch, "packed_layout": packed,
-                     "l2_rate_guide_GBps": [16800, 18800],
-                     "note": "the queries of a batch sample the same 20 % of the rows (the reference's samplers are deterministic in (N, pct)) and the "
-                             "launch is XCD-aware (workgroup k of every group on compute die k mod 8, sweeping the k-th share of its query's tiles), so "
-                             "they read them out of that die's L2 together: `l2_rate_GBps` is the rate of all executed loads (the guide measures 16.8-18.8 "
-                             "TB/s for L2-served reads) and is NOT a roofline figure; `achieved` prices only the bytes that cross the fabric.  HBM proper: "
-                             "`roofline_hbm` (tables far larger than the 256 MiB Infinity Cache)"})
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_step)
+        roof = None
+        if full:
+            qs0 = batch_queries(e)
+            # algorithmic bytes: 8 B per row the SUM / AVG queries sample (COUNT is metadata, SURVEY 8d: 0 B although the
+            # reference — and this launch — run the sampler for it); executed: every load of every query
+            per_q = [int(r.visited) for r in firsts[:B]] if not use_dist else [int(swept // B)] * B
+            alg_bytes = 8.0 * sum(v for q_, v in zip(qs0, per_q) if q_.agg != nat.COUNT)
+            try:
+                uniq_bytes = 8.0 * unique_sampled_rows(nat, qs0, n_global, lo, hi)
+            except Exception:
+                uniq_bytes = 8.0 * (hi - lo)  # every row of the shard at most once
+            roof = headline_roofline(batch_kernel, 1e3 * avg_launch_ms, alg_bytes, uniq_bytes, traffic, bytes_per_launch, traffic_src)
+            roof.update({"min_launch_us": 1e3 * ms_min, "queries_per_launch": B, "workgroups": int(wgs), "launches_timed": prof_steps,
+                         "executed_bytes_per_launch": bytes_per_launch, "packed_layout": packed,
+                         "l2_rate_guide_GBps": [16800, 18800],
+                         "note": "the queries of a batch sample the same 20 % of the rows (the reference's samplers are deterministic in (N, pct)) and the "
+                                 "launch is XCD-aware (workgroup k of every group on compute die k mod 8, sweeping the k-th share of its query's tiles), so "
+                                 "they read them out of that die's L2 together: `l2_rate_GBps` is the rate of all executed loads (the guide measures 16.8-18.8 "
+                                 "TB/s for L2-served reads) and is NOT a roofline figure; `achieved` prices only the bytes that cross the fabric.  HBM proper: "
+                                 "`roofline_hbm` (tables far larger than the 256 MiB Infinity Cache)"})
         info = eng.info()
         Lps = max(1, args.launches_per_step)
         rep = {
@@ -915,15 +966,16 @@ def main():
             "rows_swept_per_sec": float(swept) * world * args.steps * Lps / dt,
             "timed_seconds": dt,
             "result": {"value": last.value, "ci": [last.ci_lower, last.ci_upper], "n": int(last.n), "converged": int(last.converged),
-                       "rounds": int(last.rounds), "same_as_first_execution": bool(agree)},
+                       "rounds": int(last.rounds), "same_as_first_execution": agree},
             "roofline": roof,
             "single_query": single,
             "open_loop_by_batch_size": open_loop,
             "early_termination_reading": other,
             "table": {"hbm_bytes": int(info.hbm_bytes), "view_bytes": int(info.view_bytes), "n_views": int(info.n_views),
                       "view_evictions": int(info.view_evictions), "view_fallbacks": int(info.view_fallbacks)},
-            "source_hash": source_hash(),
         }
+        if full:
+            rep["source_hash"] = source_hash()
         if packed is not None:
             packed["traffic"] = packed_traffic
             packed["note"] = ("AQE_MULTI_LAYOUT=packed: no XCD alignment of the groups, the queries of a batch do not meet in a die's L2; "
@@ -955,16 +1007,18 @@ def main():
                     rep["cpu_baseline_all"] = cb
                 except Exception as ex:  # the bench line must still print
                     rep["cpu_baseline"] = {"value": None, "unit": "aggregates/sec", "cores": 0, "kind": "port", "sample": f"failed: {ex!r}"}
-        rep["cases"] = CASES
-        write_report(rep)
-        print(json.dumps(compact_line(rep)), flush=True)
+        if full:
+            rep["cases"] = CASES
+            write_report(rep)
+        print(json.dumps(compact_line(rep, report=full)), flush=True)
 
     for nb in natives:
         nb.close()
     for ps in plan_sets:
         for p in ps:
             p.close()
-    plan_one.close()
+    if plan_one is not None:
+        plan_one.close()
     eng.close()
     if use_dist:
         dist.barrier()

@@ -1,8 +1,11 @@
-"""The bench's stdout contract (CPU only, canned numbers): the LAST line is one compact JSON object the driver's
-~8 KB window always holds whole, and its roofline fraction cannot exceed 1."""
+"""The bench's stdout contract (CPU, canned numbers): the LAST line is one compact JSON object the driver's
+~8 KB window always holds whole, and its roofline fraction cannot exceed 1; the files of --dump-outputs (CPU, and one
+plain run on the GPU)."""
 import json
 import sys
 from pathlib import Path
+
+import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
@@ -94,3 +97,57 @@ def test_unique_sampled_rows_matches_a_direct_count():
                         rows.add(f.row0_b + o * f.step)
     assert got == len(rows)
     assert 0.2 * n <= got <= n  # every query samples 20 % twice over (fast + slow pointers)
+
+
+def test_compact_line_of_a_plain_run_keeps_the_contract_without_the_full_measurements():
+    rep = canned_report()
+    for k in ("roofline", "roofline_hbm", "single_query", "configs", "cold", "cpu_baseline", "cpu_baseline_all"):
+        rep.pop(k)
+    line = bench.compact_line(rep, report=False)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in line, k
+    assert line["ms_per_step"] == 5.2261 and line["higher_is_better"] is True and line["dtype"] == "f64"
+    for k in ("roofline", "roofline_hbm", "cpu_baseline", "report"):
+        assert k not in line, k
+
+
+def test_dump_outputs_writes_every_result_field_per_launch_and_query(tmp_path, monkeypatch):
+    import numpy as np
+    from approximatequeryengine_amd import _native as nat
+
+    def results(k, B=5):
+        out = []
+        for i in range(B):
+            r = nat.Result()
+            r.value, r.ci_lower, r.ci_upper, r.n, r.rounds, r.kernel_ms = 100.0 * k + i, 99.0, 101.0, 4_000_000 + i, 5, 0.123
+            out.append(r)
+        return out
+
+    bench.dump_outputs(str(tmp_path / "d"), [results(k) for k in range(3)])
+    got = {p.stem: np.load(p) for p in (tmp_path / "d").glob("*.npy")}
+    assert set(got) == set(bench.DUMP_FIELDS) and "kernel_ms" not in got
+    for a in got.values():
+        assert a.dtype == np.float64 and a.shape == (3, 5)
+    assert got["value"][2, 4] == 204.0 and got["n"][1, 3] == 4_000_003 and (got["rounds"] == 5).all()
+    # past the size limit only the step's last launches are kept
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 2 * 8 * len(bench.DUMP_FIELDS) * 5)
+    bench.dump_outputs(str(tmp_path / "e"), [results(k) for k in range(3)])
+    v = np.load(tmp_path / "e" / "value.npy")
+    assert v.shape == (2, 5) and v[0, 0] == 100.0
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_steps_asked_for_and_dumps_its_last_step(tmp_path):
+    import subprocess
+    import numpy as np
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--launches-per-step", "4",
+                          "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert "roofline" not in line and not (tmp_path / "bench_report.json").exists()
+    value = np.load(tmp_path / "dump" / "value.npy")
+    n = np.load(tmp_path / "dump" / "n.npy")
+    assert value.shape == (4, line["config"]["queries_per_launch"]) and np.isfinite(value).all()
+    # every launch of the step runs the same batch of queries on the same table: the same answers, bit for bit
+    assert (value == value[0]).all() and (n == n[0]).all() and (n > 0).all()

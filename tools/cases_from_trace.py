@@ -1,7 +1,7 @@
 """Per-case kernel rows out of ONE `rocprofv3 --kernel-trace` of bench.py.
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof_r3/bench -o b -- python3 bench.py --steps 20 --warmup 5
-    python tools/cases_from_trace.py gpurun_out/prof_r3/bench gpurun_out/bench_report.json profiles/round3_configs_cases.csv
+    rocprofv3 --kernel-trace --output-format csv -d <trace dir> -o b -- python3 bench.py --full --steps 20 --warmup 5
+    python tools/cases_from_trace.py <trace dir> bench_report.json profiles/round3_configs_cases.csv
 
 bench.py runs the timed launches of every case on a stream of their own and records how many launches that were
 (bench_report.json: "cases").  Here the trace's sweep-kernel dispatches are grouped by Stream_Id; walking the groups in

@@ -2,7 +2,7 @@
 # Round-2 profiles: kernel stats of the bench, of the 100 M / 1 B-row configurations, of the grouped reductions; PMC passes.
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
-O=gpurun_out/prof_r2
+O=${1:?usage: tools/gpu_f.sh OUTDIR}/prof_r2
 rm -rf $O; mkdir -p $O
 echo "--- kernel trace + stats: bench headline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o b -- python3 bench.py --headline-only --steps 200 --warmup 20 > $O/bench_line.txt 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }

@@ -19,11 +19,11 @@ rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_disjoint
 python tools/pmc_summarize.py $O/pmc_fetch $O/pmc_write $O/round3_pmc_raw.json 32 $O/pmc_disjoint | tail -12
 cp $O/round3_pmc_raw.json profiles/round3_pmc_raw.json   # (measured a minute ago on these very sources: the bench reports it as roofline.traffic)
 echo "--- the bench, unprofiled (the driver's command)"
-( time python bench.py --steps 20 --warmup 5 ) > $O/bench_line.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+( time python bench.py --full --steps 20 --warmup 5 ) > $O/bench_line.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 cp gpurun_out/bench_report.json $O/bench_report.json
 tail -c 2600 $O/bench_line.json; grep real $O/bench.err
 echo "--- kernel trace + stats of the same command, split per case"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o b -- python3 bench.py --steps 20 --warmup 5 > $O/bench_profiled_line.json 2> $O/bench_profiled.err || { tail -5 $O/bench_profiled.err; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o b -- python3 bench.py --full --steps 20 --warmup 5 > $O/bench_profiled_line.json 2> $O/bench_profiled.err || { tail -5 $O/bench_profiled.err; exit 1; }
 cp gpurun_out/bench_report.json $O/bench_report_profiled.json
 python tools/cases_from_trace.py $O/bench $O/bench_report_profiled.json $O/round3_configs_cases.csv | cut -c1-200 | tail -40
 head -8 $O/bench/b_kernel_stats.csv | cut -c1-200
