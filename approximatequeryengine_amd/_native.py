@@ -38,6 +38,9 @@ MOMENT_VEC = 8
 COMM_ID_BYTES = 128
 MAILBOX_HANDLE_BYTES = 64
 MAILBOX_MAX_DOUBLES = 4096
+MAX_QUANTILES = 8
+QUANTILE_LINEAR, QUANTILE_INVERTED_CDF = 0, 1
+QUANTILE_VEC_SUM, QUANTILE_VEC_MAX = 8194, 64
 
 
 class Query(C.Structure):
@@ -74,6 +77,16 @@ class Family(C.Structure):
 class GroupResult(C.Structure):
     _fields_ = [("key", C.c_int64), ("n", C.c_uint64), ("visited", C.c_uint64), ("sum", C.c_double), ("sumsq", C.c_double),
                 ("mean", C.c_double), ("value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class QuantileResult(C.Structure):
+    _fields_ = [("p", C.c_double), ("value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double),
+                ("n", C.c_uint64), ("visited", C.c_uint64), ("rank_lo", C.c_uint64), ("rank_hi", C.c_uint64),
+                ("ci_rank_lo", C.c_uint64), ("ci_rank_hi", C.c_uint64), ("passes", C.c_int32), ("device_status", C.c_int32),
+                ("kernel_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -159,6 +172,14 @@ def lib() -> C.CDLL:
         "aqe_grouped_enqueue_bins": (C.c_int, [vp, P(Query), C.c_int, C.c_int32, u32, vp, vp]),
         "aqe_grouped_finish": (C.c_int, [vp, P(Query), C.c_int32, u32, vp, vp, P(GroupResult), u32, P(u32)]),
         "aqe_gather": (C.c_int, [vp, P(Query), vp, u64, P(u64)]),
+        "aqe_reduce_quantiles": (C.c_int, [vp, P(Query), P(dbl), u32, C.c_int, P(QuantileResult)]),
+        "aqe_quantile_amount_range": (C.c_int, [vp, P(dbl), P(dbl)]),
+        "aqe_quantile_begin": (C.c_int, [vp, P(Query), P(dbl), u32, C.c_int, dbl, dbl, vp, P(vp)]),
+        "aqe_quantile_enqueue_pass": (C.c_int, [vp, vp, vp]),
+        "aqe_quantile_enqueue_fold": (C.c_int, [vp, vp, vp]),
+        "aqe_quantile_done": (C.c_int, [vp, P(C.c_int)]),
+        "aqe_quantile_finish": (C.c_int, [vp, P(QuantileResult), vp]),
+        "aqe_quantile_destroy": (None, [vp]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),

@@ -33,7 +33,7 @@ from . import _native as nat
 from .engine import RECORD_DTYPE, Engine, make_query
 
 __all__ = ["Record", "CustomBPlusDB", "CustomApproximateScheduler", "CustomValidationResult",
-           "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate"]
+           "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate"]
 
 
 class Record:
@@ -121,6 +121,41 @@ class GroupEstimate:
 
     def __iter__(self):  # unpacks like the reference's (value, ci_lower, ci_upper)
         return iter((self.value, self.ci_lower, self.ci_upper))
+
+
+class QuantileEstimate:
+    """One probability of approx_quantile: numpy.quantile's value of the sampled amounts and the distribution-free interval
+    [x_(r_lo), x_(r_hi)] (include/aqe_hip.h, aqe_quantile_result)."""
+    __slots__ = ("p", "value", "ci_lower", "ci_upper", "n", "visited", "passes", "kernel_ms", "method", "rank_lo", "rank_hi",
+                 "ci_rank_lo", "ci_rank_hi")
+
+    def __init__(self, r, method: str):
+        for k in ("p", "value", "ci_lower", "ci_upper", "n", "visited", "passes", "kernel_ms", "rank_lo", "rank_hi", "ci_rank_lo", "ci_rank_hi"):
+            setattr(self, k, getattr(r, k))
+        self.method = method
+
+    def __repr__(self):
+        return (f"QuantileEstimate(p={self.p!r}, value={self.value!r}, ci=({self.ci_lower!r}, {self.ci_upper!r}), n={self.n}, "
+                f"passes={self.passes}, method={self.method!r})")
+
+    def __iter__(self):  # unpacks like a GroupEstimate: (value, ci_lower, ci_upper)
+        return iter((self.value, self.ci_lower, self.ci_upper))
+
+
+_QUANTILE_INTERP = {"linear": nat.QUANTILE_LINEAR, "inverted_cdf": nat.QUANTILE_INVERTED_CDF}
+
+
+def _quantile_call(fn):
+    """The errors of a quantile call as the Python API reports them: no sample -> RuntimeError("No samples collected"), as
+    approx() does; a sampler without a quantile form -> ValueError."""
+    try:
+        return fn()
+    except nat.AqeError as e:
+        if e.status == nat.ERR_UNSUPPORTED:
+            raise ValueError(str(e)) from None
+        if "No samples collected" in str(e):
+            raise RuntimeError("No samples collected") from None
+        raise
 
 
 def parse_where(query: str) -> Optional[Tuple[float, float]]:
@@ -526,6 +561,43 @@ class CustomBPlusDB:
         bs = 4096 if (method == "page" and block_size == 1000) else block_size
         q = make_query(m, sample_percent, agg=_AGG[agg.upper()], where=where, block_size=int(bs))
         return {str(r.key): GroupEstimate(r) for r in self._eng().reduce_grouped(q, col)}
+
+    def _quantile_query(self, method="stride", sample_percent=10.0, where=None, id_between=None, interpolation="linear",
+                        confidence_level=0.95, seed=42, num_threads=4, block_size=1000):
+        """(aqe_query, interpolation code) behind approx_quantile."""
+        if interpolation not in _QUANTILE_INTERP:
+            raise ValueError("interpolation must be 'linear' (PERCENTILE_CONT) or 'inverted_cdf' (PERCENTILE_DISC)")
+        if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
+            raise ValueError(f"quantiles do not take the {method} sampler (single-round family samplers and 'random' only)")
+        q = self._approx_query("SUM", method, sample_percent, None, where, seed, num_threads, block_size, confidence_level,
+                               id_between=id_between)
+        q.confidence_level = float(confidence_level)
+        return q, _QUANTILE_INTERP[interpolation]
+
+    def approx_quantile(self, p, method: str = "stride", sample_percent: float = 10.0, where: Optional[Tuple[float, float]] = None,
+                        id_between: Optional[Tuple[int, int]] = None, interpolation: str = "linear", confidence_level: float = 0.95,
+                        seed: int = 42, num_threads: int = 4, block_size: int = 1000):
+        """APPROX PERCENTILE(amount, p): numpy.quantile(X, p, method=interpolation) of the sampled amounts X (WHERE and the key
+        window applied, NaN rows left out) with a distribution-free interval from order statistics.  ``p`` is one probability
+        or a list of up to 8 (answered from the same sample in the same sweeps); the result is a QuantileEstimate or a list.
+        interpolation "linear" is PERCENTILE_CONT, "inverted_cdf" PERCENTILE_DISC.  method: "exact", "stride", "block", "page",
+        "parallel_block", "region", "random" ... (CLT, adaptive, stratified and random_device samplers raise ValueError)."""
+        single = not isinstance(p, (list, tuple, np.ndarray))
+        probs = [float(p)] if single else [float(v) for v in p]
+        if not probs or len(probs) > nat.MAX_QUANTILES or any(not (0.0 <= v <= 1.0) for v in probs):
+            raise ValueError(f"1 .. {nat.MAX_QUANTILES} probabilities, each in [0, 1]")
+        q, interp = self._quantile_query(method, sample_percent, where, id_between, interpolation, confidence_level, seed,
+                                         num_threads, block_size)
+        res = _quantile_call(lambda: self._quantiles(q, probs, interp))
+        out = [QuantileEstimate(r, method) for r in res]
+        return out[0] if single else out
+
+    def _quantiles(self, q, probs, interp):
+        return self._eng().reduce_quantiles(q, probs, interp)
+
+    def approx_median(self, **kw):
+        """APPROX MEDIAN(amount): approx_quantile(0.5, **kw)."""
+        return self.approx_quantile(0.5, **kw)
 
     def approx_sum(self, **kw) -> ApproxResult:
         return self.approx("SUM", **kw)

@@ -4,6 +4,8 @@
     python -m approximatequeryengine_amd.cli "SELECT SUM(amount) FROM sales" --db sales.db --s 10
     python -m approximatequeryengine_amd.cli "SELECT AVG(amount) FROM sales" --db sales.db --e 2 --ci
     python -m approximatequeryengine_amd.cli "SELECT APPROX(SUM(amount)) FROM sales" --db sales.db --compare
+    python -m approximatequeryengine_amd.cli "SELECT MEDIAN(amount) FROM sales" --db sales.db --s 10 --ci
+    python -m approximatequeryengine_amd.cli "SELECT PERCENTILE_DISC(amount, 0.99) FROM sales" --db sales.db --compare
     python -m approximatequeryengine_amd.cli --explain
 
 The reference's own CLI defines `-s/--sample` and `-e/--error` but tests `args.s` / `args.e`
@@ -49,6 +51,30 @@ def aggregate_of(query: str) -> str:
     return "AVG"  # enhanced_aqe_cli.py:198-200: default to average
 
 
+_QUANTILE_FUNCS = {"PERCENTILE_CONT": "linear", "PERCENTILE_DISC": "inverted_cdf", "PERCENTILE": "linear"}
+
+
+def quantile_of(query: str) -> Optional[Tuple[float, str, str]]:
+    """MEDIAN(amount) / PERCENTILE(amount, p) / PERCENTILE_CONT(amount, p) -> (p, "linear", name); PERCENTILE_DISC(amount, p)
+    -> (p, "inverted_cdf", name); None for any other query — and for every query that names SUM(, AVG( or COUNT(, whose
+    routing stays as it was.  A p that is not a number in [0, 1] raises ValueError."""
+    up = query.upper()
+    if any(a + "(" in up for a in ("SUM", "AVG", "COUNT")):
+        return None
+    if re.search(r"\bMEDIAN\s*\(\s*amount\s*\)", query, re.IGNORECASE):
+        return 0.5, "linear", "MEDIAN"
+    m = re.search(r"\b(PERCENTILE_CONT|PERCENTILE_DISC|PERCENTILE)\s*\(\s*amount\s*,\s*([^)]*?)\s*\)", query, re.IGNORECASE)
+    if not m:
+        return None
+    try:
+        p = float(m.group(2))
+    except ValueError:
+        raise ValueError(f"{m.group(1).upper()}: p must be a number in [0, 1], got {m.group(2)!r}") from None
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"{m.group(1).upper()}: p must lie in [0, 1], got {p:g}")
+    return p, _QUANTILE_FUNCS[m.group(1).upper()], m.group(1).upper()
+
+
 def determine_query_type(query: str, args) -> str:
     """enhanced_aqe_cli.py:97-114 with the attribute names fixed."""
     if parse_embedded_approx(query)[1]:
@@ -73,7 +99,7 @@ def get_optimal_method_for_query(query: str, dataset_size: Optional[int] = None)
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT on MI355X",
+    p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE on MI355X",
                                 allow_abbrev=False)
     p.add_argument("query", nargs="?", help="SQL query, e.g. \"SELECT SUM(amount) FROM sales\"")
     p.add_argument("--db", default="custom_demo.db", help="database file (reference format)")
@@ -101,11 +127,23 @@ def run(args, out=sys.stdout) -> int:
     if not args.query:
         print("error: a query is required unless --explain is given", file=out)
         return 2
+    clean, _ = parse_embedded_approx(args.query)
+    try:
+        quant = quantile_of(clean)
+    except ValueError as e:
+        print(f"error: {e}", file=out)
+        return 2
+    if quant is not None:
+        if args.e is not None:
+            print("error: quantiles have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
+            return 2
+        if re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
+            print("error: GROUP BY is not supported with MEDIAN / PERCENTILE", file=out)
+            return 2
     if not os.path.exists(args.db):
         print(f"error: database file '{args.db}' not found", file=out)
         return 1
     from . import aqe_backend
-    clean, _ = parse_embedded_approx(args.query)
     qtype = determine_query_type(args.query, args)
     agg = aggregate_of(clean)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -146,6 +184,9 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     n = db.get_total_records()
     print(f"query: {args.query}\ndatabase: {args.db} ({n:,} records{', ' + sharded_note if sharded_note else ''})\ntype: {qtype}", file=out)
     t0 = time.perf_counter()
+    quant = quantile_of(clean)
+    if quant is not None:
+        return _run_quantile(db, args, out, clean, qtype, quant, aqe_backend, t0)
     gb = re.search(r"GROUP\s+BY\s+(region|product_id)\b", clean, flags=re.IGNORECASE)
     if gb:  # one sweep, one (n, S, Q) bin per key, an interval per group (executor.cpp:202-321 semantics)
         pct = args.s if args.s is not None else (100.0 if qtype == QUERY_EXACT else 10.0)
@@ -192,6 +233,35 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us, {res.achieved_GBps:.0f} GB/s algorithmic)", file=out)
     if args.compare and qtype != QUERY_EXACT:
         exact = db.approx(agg, method="exact", where=where)
+        print(f"\ncomparison:\n   approximate: {res.value:,.4f}\n   exact:       {exact.value:,.4f}", file=out)
+        if exact.value != 0:
+            print(f"   actual error: {abs(res.value - exact.value) / abs(exact.value) * 100:.4f}%", file=out)
+    db.close_database()
+    return 0
+
+
+def _run_quantile(db, args, out, clean, qtype, quant, aqe_backend, t0) -> int:
+    """MEDIAN / PERCENTILE(_CONT, _DISC): exact without --s; with --s (or an APPROX(...) wrapper) a sample, --method block /
+    parallel / random honoured, stride otherwise."""
+    p, interp, fname = quant
+    where = aqe_backend.parse_where(clean)
+    if args.s is None and qtype != QUERY_EMBEDDED:
+        method, pct, name = "exact", 100.0, "exact"
+    else:
+        pct = args.s if args.s is not None else 10.0
+        method = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", "stride")
+        name = f"{method} sampling ({pct}%)"
+    res = db.approx_quantile(p, method=method, sample_percent=pct, where=where, interpolation=interp,
+                             confidence_level=args.confidence, seed=args.seed, num_threads=args.threads)
+    ms = (time.perf_counter() - t0) * 1e3
+    print(f"\n{name} {fname}(amount{'' if fname == 'MEDIAN' else f', {p:g}'}) result:\n   value: {res.value:,.4f}", file=out)
+    if args.ci and method != "exact":
+        print(f"   confidence interval ({args.confidence:g}, order statistics {res.ci_rank_lo:,} - {res.ci_rank_hi:,}): "
+              f"({res.ci_lower:,.4f} - {res.ci_upper:,.4f})", file=out)
+    print(f"   samples used: {res.n:,}   passes: {res.passes}", file=out)
+    print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
+    if args.compare and method != "exact":
+        exact = db.approx_quantile(p, method="exact", where=where, interpolation=interp)
         print(f"\ncomparison:\n   approximate: {res.value:,.4f}\n   exact:       {exact.value:,.4f}", file=out)
         if exact.value != 0:
             print(f"   actual error: {abs(res.value - exact.value) / abs(exact.value) * 100:.4f}%", file=out)

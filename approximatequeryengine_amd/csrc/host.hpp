@@ -145,6 +145,11 @@ struct aqe_ctx {
     unsigned long long epoch = 1;
     // prepared plans of aqe_reduce / aqe_gather, keyed by the query bytes
     std::vector<std::pair<aqe_query, aqe_plan*>> cache;
+    // quantiles (quantile.hip): the scratch of aqe_reduce_quantiles, and the shard's amount range, kept per table
+    aqe_quantile* qrun = nullptr;
+    bool qrange_valid = false;
+    uint64_t qrange_epoch = 0;
+    double qrange_lo = 0.0, qrange_hi = 0.0;
 };
 
 // One persistent-sweep form of a plan's rounds (persist.hip): the tile list of all slots, who owns tiles
@@ -270,6 +275,10 @@ inline double query_shift(const aqe_ctx* c, const aqe_query& q) {
     if (q.has_where && q.where_min <= q.where_max) s = std::min(std::max(s, q.where_min), q.where_max);
     return s;
 }
+
+// quantile.hip
+int quantile_amount_range(aqe_ctx* c, double* lo, double* hi);  // non-NaN amounts of the shard (+inf / -inf: none)
+void quantile_release(aqe_ctx* c);
 
 // plans.hip
 void destroy_plan(aqe_plan* p, bool device_idle = false);  // device_idle: the caller has just synchronised the device

@@ -567,6 +567,7 @@ void aqe_destroy(aqe_ctx* c) {
         (void)hipFree(sc.d_fams_small);
     }
     c->scratch_pool.clear();
+    quantile_release(c);
     free_table(c);
     free_ring(c);
     if (c->d_stamps) (void)hipFree(c->d_stamps);

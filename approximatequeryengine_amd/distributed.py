@@ -269,6 +269,43 @@ def _sharded_group_by(engine, query, group_column, bins, all_reduce_sum, all_red
     return engine.grouped_finish(query, kmin, nbins, b.data_ptr(), stream)
 
 
+def sharded_quantiles(engine, query, probs, interpolation: int, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0):
+    """Quantiles across the ranks of a process group (engine.Engine interface), collective: every rank gets the same answer.
+    The amount range is agreed first (one MAX all-reduce of [-min, max]); then per pass every rank counts the part of the
+    sample inside its shard into its pass vector, one all-reduce SUM merges the counts and one MAX the per-range extremes,
+    and every rank folds the same vector — so every rank narrows to the same ranks and stops after the same pass.
+
+    vec     float64 tensor on the engine's device with room for QUANTILE_VEC_SUM + QUANTILE_VEC_MAX doubles
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    stream = _stream_for(stream, vec)
+    with _torch_on(stream, vec):
+        return _sharded_quantiles(engine, query, probs, interpolation, vec, all_reduce_sum, all_reduce_max, stream)
+
+
+def _sharded_quantiles(engine, query, probs, interpolation, vec, all_reduce_sum, all_reduce_max, stream):
+    from ._native import QUANTILE_VEC_MAX, QUANTILE_VEC_SUM
+    lo, hi = engine.quantile_amount_range()
+    rng = vec.new_tensor([-float(lo), float(hi)])
+    all_reduce_max(rng)
+    amin, amax = -float(rng[0].item()), float(rng[1].item())
+    need = QUANTILE_VEC_SUM + QUANTILE_VEC_MAX
+    if vec.numel() < need:
+        raise ValueError(f"pass vector holds {vec.numel()} doubles, {need} needed")
+    v = vec[:need]
+    run = engine.quantile_begin(query, probs, interpolation, amin, amax, stream)
+    try:
+        while True:
+            run.enqueue_pass(v.data_ptr(), stream)
+            all_reduce_sum(v[:QUANTILE_VEC_SUM])
+            all_reduce_max(v[QUANTILE_VEC_SUM:])
+            run.enqueue_fold(v.data_ptr(), stream)
+            if run.done():  # (the same state on every rank: every rank leaves after the same pass)
+                break
+        return run.finish(stream)
+    finally:
+        run.close()
+
+
 # ---- the variance-aware samplers over a sharded table (SURVEY 8e "what does not shard") ---------------------------------
 # Both need one fact about the WHOLE table before a shard can plan (include/aqe_hip.h, the block above aqe_zone_moments).
 # The exchanges below are small host arrays, once per table and query shape — `host_all_reduce_sum(a) -> a summed over the

@@ -418,6 +418,26 @@ class Engine:
                                                C.c_void_p(stream), out, max_groups, C.byref(n)))
         return list(out[: n.value])
 
+    # -- quantiles (aqe_reduce_quantiles and its stepwise multi-GPU form) --
+    def reduce_quantiles(self, query: Query, probs: Sequence[float], interpolation: int = nat.QUANTILE_LINEAR):
+        """Order statistics of the sampled amounts: one QuantileResult per probability (numpy.quantile's value, the
+        distribution-free interval), all from the same sample in the same sweeps."""
+        ps = _probs(probs)
+        arr = (C.c_double * len(ps))(*ps)
+        out = (nat.QuantileResult * len(ps))()
+        self._chk(nat.lib().aqe_reduce_quantiles(self._h, C.byref(query), arr, len(ps), int(interpolation), out))
+        return list(out)
+
+    def quantile_amount_range(self) -> Tuple[float, float]:
+        """(smallest, largest) non-NaN amount of this shard; (inf, -inf) when it holds none."""
+        lo, hi = C.c_double(), C.c_double()
+        self._chk(nat.lib().aqe_quantile_amount_range(self._h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def quantile_begin(self, query: Query, probs: Sequence[float], interpolation: int, amount_min: float, amount_max: float,
+                       stream: int = 0) -> "QuantileRun":
+        return QuantileRun(self, query, probs, interpolation, amount_min, amount_max, stream)
+
     def gather(self, query: Query) -> np.ndarray:
         """Rows of the record-returning sampler, as a RECORD_DTYPE array."""
         n = C.c_uint64()
@@ -459,6 +479,54 @@ class Engine:
             self._chk(nat.lib().aqe_sorted_counts(self._h, v.ctypes.data_as(C.POINTER(C.c_double)), len(v),
                                                   lt.ctypes.data_as(C.POINTER(C.c_uint64)), le.ctypes.data_as(C.POINTER(C.c_uint64))))
         return lt, le
+
+
+def _probs(probs) -> list:
+    ps = [float(p) for p in probs]
+    if not 1 <= len(ps) <= nat.MAX_QUANTILES:
+        raise ValueError(f"1 .. {nat.MAX_QUANTILES} probabilities per call")
+    return ps
+
+
+class QuantileRun:
+    """One stepwise quantile computation (aqe_quantile_*): per pass ``enqueue_pass(vec)`` -> all-reduce SUM of the first
+    QUANTILE_VEC_SUM doubles and MAX of the next QUANTILE_VEC_MAX -> ``enqueue_fold(vec)``, until ``done()``; then ``finish()``."""
+
+    def __init__(self, engine: "Engine", query: Query, probs, interpolation: int, amount_min: float, amount_max: float, stream: int = 0):
+        self.engine, self.query = engine, query
+        self.probs = _probs(probs)
+        arr = (C.c_double * len(self.probs))(*self.probs)
+        self._h = C.c_void_p()
+        nat.check(nat.lib().aqe_quantile_begin(engine._h, C.byref(query), arr, len(self.probs), int(interpolation), float(amount_min),
+                                               float(amount_max), C.c_void_p(stream), C.byref(self._h)), engine._h)
+        engine._plans.add(self)
+
+    def enqueue_pass(self, dev_vec_ptr: int, stream: int = 0):
+        nat.check(nat.lib().aqe_quantile_enqueue_pass(self._h, C.c_void_p(dev_vec_ptr), C.c_void_p(stream)), self.engine._h)
+
+    def enqueue_fold(self, dev_vec_ptr: int, stream: int = 0):
+        nat.check(nat.lib().aqe_quantile_enqueue_fold(self._h, C.c_void_p(dev_vec_ptr), C.c_void_p(stream)), self.engine._h)
+
+    def done(self) -> bool:
+        d = C.c_int()
+        nat.check(nat.lib().aqe_quantile_done(self._h, C.byref(d)), self.engine._h)
+        return bool(d.value)
+
+    def finish(self, stream: int = 0):
+        out = (nat.QuantileResult * len(self.probs))()
+        nat.check(nat.lib().aqe_quantile_finish(self._h, out, C.c_void_p(stream)), self.engine._h)
+        return list(out)
+
+    def close(self):
+        if self._h:
+            nat.lib().aqe_quantile_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def make_query(method: int, sample_percent: float = 10.0, agg: int = nat.SUM, convention: int = nat.EST_CLI,

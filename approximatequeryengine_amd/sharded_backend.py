@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _native as nat
 from .aqe_backend import ApproxResult, CustomBPlusDB, GroupEstimate, _AGG
-from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, shard_bounds, sharded_adaptive_plan, sharded_group_by,
+from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, shard_bounds, sharded_adaptive_plan, sharded_group_by, sharded_quantiles,
                           sharded_stratified_plan, torch_all_reduce, torch_host_all_reduce)
 from .engine import RECORD_DTYPE, Batch, Engine, make_query
 
@@ -243,3 +243,12 @@ class ShardedBPlusDB(CustomBPlusDB):
                 self._bins = torch.zeros(4 * 4096, dtype=torch.float64, device=self._dev)
             groups = sharded_group_by(self._engine, q, col, self._bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream)
         return {str(r.key): GroupEstimate(r) for r in groups}
+
+    def _quantiles(self, q, probs, interp):
+        """approx_quantile over all ranks (collective): the amount range is agreed, then per pass one all-reduce SUM of the
+        counts and one MAX of the range extremes (distributed.sharded_quantiles).  Every rank gets the same answer."""
+        import torch
+        self._eng()
+        with torch.cuda.stream(self._side):
+            vec = self._buffer(nat.QUANTILE_VEC_SUM + nat.QUANTILE_VEC_MAX)
+            return sharded_quantiles(self._engine, q, probs, interp, vec, self._ar_sum, self._ar_max, stream=self._side.cuda_stream)

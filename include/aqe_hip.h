@@ -366,6 +366,65 @@ AQE_API int aqe_grouped_enqueue_bins(aqe_ctx* ctx, const aqe_query* q, int group
 AQE_API int aqe_grouped_finish(aqe_ctx* ctx, const aqe_query* q, int32_t key_min, uint32_t nbins, const double* dev_bins, void* stream,
                                aqe_group_result* out, uint32_t cap, uint32_t* n_groups);
 
+/* ---- quantiles: approximate MEDIAN / PERCENTILE with an order-statistic interval ----------------
+ * X = the sampled amounts: the rows of q's sampler inside its row window (row_lo/row_hi), passing the WHERE range
+ * (inclusive), NaN rows left out; n = |X|, visited = sampled rows before WHERE and NaN.  For each probability p:
+ *   value     numpy.quantile(X, p, method=M), the same double: AQE_QUANTILE_LINEAR (numpy's default, PERCENTILE_CONT;
+ *             h = (n-1)p, j = floor(h), g = h - j, a = x_(j), b = x_(j+1): b - (b-a)(1-g) if g >= 0.5, else a + (b-a)g)
+ *             or AQE_QUANTILE_INVERTED_CDF (PERCENTILE_DISC: always an element of X).  -0.0 == +0.0; +-inf are values.
+ *   interval  distribution-free, from order statistics: z from confidence_level as the CLT path (2.576 / 1.96 / 1.645),
+ *             r_lo = clamp(floor(np - z sqrt(np(1-p))), 1, n), r_hi = clamp(ceil(np + z sqrt(np(1-p))), 1, n),
+ *             [ci_lower, ci_upper] = [x_(r_lo), x_(r_hi)] (1-based); AQE_M_EXACT reports [value, value].
+ * Up to AQE_MAX_QUANTILES probabilities in [0, 1] per call, answered from the same sample in the same sweeps.  Samplers:
+ * the single-round family samplers (exact, stride, rowid-mod, block, page, parallel block, region, address arithmetic ...)
+ * and the seeded random sampler (RANDOM_POINTER, through its host index list; the one simple random sample, where the
+ * interval means what it says).  CLT, adaptive, stratified, RANDOM_DEVICE and pair-family samplers: AQE_ERR_UNSUPPORTED.
+ * n == 0: AQE_ERR_INVALID ("No samples collected").
+ * The selection (quantile.hip): passes over the sampled rows, each counting the order-preserving 64-bit keys of the amounts
+ * into narrowing histograms (the first digit starts at the top bit of key(max) - key(min) of the data), until every rank
+ * needed is pinned to one key.  Ranks below are 1-based. */
+#define AQE_MAX_QUANTILES 8
+#define AQE_QUANTILE_LINEAR 0
+#define AQE_QUANTILE_INVERTED_CDF 1
+typedef struct aqe_quantile_result {
+    double p;
+    double value;
+    double ci_lower, ci_upper;
+    uint64_t n;                    /* sampled rows that pass WHERE and are not NaN                    */
+    uint64_t visited;              /* sampled rows                                                    */
+    uint64_t rank_lo, rank_hi;     /* the order statistics `value` is made of (equal for inverted_cdf) */
+    uint64_t ci_rank_lo, ci_rank_hi;
+    int32_t passes;                /* sweeps over the sample that the selection took                  */
+    int32_t device_status;         /* 0 ok                                                            */
+    double kernel_ms;              /* aqe_reduce_quantiles: device time of the call (events around its launches) */
+} aqe_quantile_result;
+/* Single GPU, synchronous.  Runs on q's own (cached) plan, whatever else the context caches. */
+AQE_API int aqe_reduce_quantiles(aqe_ctx* ctx, const aqe_query* q, const double* probs, uint32_t n_probs, int interpolation,
+                                 aqe_quantile_result* out);
+/* Multi-GPU form.  Every rank holds the SAME state after every fold, so every rank takes the same decisions:
+ *     aqe_quantile_amount_range(ctx, &lo, &hi)      this shard's non-NaN amount range (+inf / -inf when it has none);
+ *                                                    all-reduce MAX of [-lo, hi] (kept per table)
+ *     aqe_quantile_begin(ctx, q, probs, n, interp, lo, hi, stream, &h)
+ *     repeat:
+ *       aqe_quantile_enqueue_pass(h, dev_vec, stream)   this shard's pass vector: AQE_QUANTILE_VEC_SUM counts (as doubles,
+ *                                                       exact below 2^53) then AQE_QUANTILE_VEC_MAX doubles
+ *       <all-reduce SUM of dev_vec[0 .. VEC_SUM), all-reduce MAX of dev_vec[VEC_SUM .. VEC_SUM + VEC_MAX), on `stream`>
+ *       aqe_quantile_enqueue_fold(h, dev_vec, stream)  narrows every rank on the device; no host round trip needed
+ *     until aqe_quantile_done(h, &done) reports 1 (it synchronises; a pass or fold enqueued after that is a device no-op)
+ *     aqe_quantile_finish(h, out, stream); aqe_quantile_destroy(h)
+ * aqe_reduce_quantiles is exactly this at a world of one (the last workgroup of each pass folds in the same launch). */
+#define AQE_QUANTILE_VEC_SUM 8194
+#define AQE_QUANTILE_VEC_MAX 64
+typedef struct aqe_quantile aqe_quantile;
+AQE_API int aqe_quantile_amount_range(aqe_ctx* ctx, double* amount_min, double* amount_max);
+AQE_API int aqe_quantile_begin(aqe_ctx* ctx, const aqe_query* q, const double* probs, uint32_t n_probs, int interpolation,
+                               double amount_min, double amount_max, void* stream, aqe_quantile** out);
+AQE_API int aqe_quantile_enqueue_pass(aqe_quantile* h, double* dev_vec, void* stream);
+AQE_API int aqe_quantile_enqueue_fold(aqe_quantile* h, const double* dev_vec, void* stream);
+AQE_API int aqe_quantile_done(aqe_quantile* h, int* done);
+AQE_API int aqe_quantile_finish(aqe_quantile* h, aqe_quantile_result* out, void* stream);
+AQE_API void aqe_quantile_destroy(aqe_quantile* h);
+
 /* ---- stepwise / multi-GPU form ----------------------------------------------------------------
  * One process per GPU; each rank plans the same query over its own shard.  Per round:
  *     aqe_plan_enqueue_round(plan, r, dev_vec, stream)     this shard's partial moment vector
