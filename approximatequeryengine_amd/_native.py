@@ -212,6 +212,7 @@ def lib() -> C.CDLL:
         "aqe_batch_enqueue_all": (C.c_int, [vp, vp]),
         "aqe_batch_set_profiling": (C.c_int, [vp, C.c_int]),
         "aqe_batch_launch_info": (C.c_int, [vp, P(C.c_float), P(u64), P(u32)]),
+        "aqe_batch_share_info": (C.c_int, [vp, P(u32), P(u64)]),
         "aqe_comm_unique_id": (C.c_int, [vp]),
         "aqe_comm_create": (C.c_int, [vp, vp, C.c_int, C.c_int, P(vp)]),
         "aqe_comm_create_all": (C.c_int, [P(vp), C.c_int, P(vp)]),

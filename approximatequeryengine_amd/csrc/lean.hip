@@ -254,9 +254,13 @@ __device__ __forceinline__ void lean_send_result(const LeanTail& T, const unsign
 
 // One query on the workgroups bid = 0 .. G-1 (a launch of its own, or one group of a batch's launch).  `a`: the fields
 // the sweep needs, in registers; K: the descriptor (the kernel arguments of a single launch, the batch's table in device
-// memory otherwise) — read twice: a lane's two runs, and the tail.
+// memory otherwise) — read twice: a lane's two runs, and the tail.  A batch's sweep class (plans.hip, build_multi):
+// members[0 .. nmem) are the descriptors of the queries that share this sweep, members[0] being K's; the sweep, the
+// partial list and the ticket are the first one's, and the folding workgroup judges every member (wave m: members m,
+// m + 16, ...) on the same round totals.  A launch of its own: nmem = 1.
 template <bool kNT, bool kWide>
-__device__ __forceinline__ void lean_query(const LeanLaunch& a, const LeanRuns* const runs, const LeanKarg K, const unsigned bid, const unsigned G, const unsigned long long epoch) {
+__device__ __forceinline__ void lean_query(const LeanLaunch& a, const LeanRuns* const runs, const LeanKarg K, const LeanLaunch* const members, const unsigned nmem,
+                                           const unsigned bid, const unsigned G, const unsigned long long epoch) {
     // a wave's sums of a round (zero where it swept none); in the folding workgroup, later, the launch's whole partial list
     __shared__ double lds_part[kMaxPersistRounds][kPersistWaves][kVec];
     static_assert(kMaxPersistRounds * kPersistWaves >= kLeanMaxSlots, "the partial list fits where the workgroup's own sums were");
@@ -264,7 +268,6 @@ __device__ __forceinline__ void lean_query(const LeanLaunch& a, const LeanRuns* 
     __shared__ unsigned lds_slot[kMaxPersistRounds];
     __shared__ unsigned lds_mask[kPersistWaves];  // rounds a wave swept tiles of
     __shared__ u64 lds_tail[64];
-    __shared__ unsigned long long lds_res[64];  // the finishing lane's result, word by word (lean_send_result)
     __shared__ int s_last;
     const int lane = threadIdx.x & 63;
     const unsigned wave = threadIdx.x >> 6;
@@ -435,6 +438,10 @@ __device__ __forceinline__ void lean_query(const LeanLaunch& a, const LeanRuns* 
     //      of coalesced loads (three words per thread at most) into the space the workgroup's own sums occupied ----
     const LeanTail& T = *reinterpret_cast<const LeanTail*>(lds_tail);
     const unsigned rounds = T.rounds;
+    // the other members' tails (wave m < 16 fetches member m's, one word per lane): in flight beside the partial list
+    constexpr unsigned kTailWords = sizeof(LeanTail) / 8u;
+    u64 mtail = 0;
+    if (wave != 0 && wave < nmem && static_cast<unsigned>(lane) < kTailWords) mtail = reinterpret_cast<const u64*>(&members[wave].tail)[lane];
     const unsigned long long t0 = T.want_ticks ? __hip_atomic_load(lean_t0_word(a.counter), AQE_RLX) : 0ull;  // (in flight beside the partials)
     // W waves per round (a power of two; one when the plan has more than eight rounds).  Thread (part, c) of a round's waves
     // sums component c of every (8 W)-th slot of the round straight out of the partial list — fewer than workgroups + rounds
@@ -478,11 +485,18 @@ __device__ __forceinline__ void lean_query(const LeanLaunch& a, const LeanRuns* 
 #endif
     __syncthreads();
     LEAN_STAMP_FOLD(1);
-    if (wave != 0) return;
+    if (wave >= nmem) return;
 #ifdef AQE_ABL_FOLD2  // (ablation: ... here — after the barrier, before the scan and the rules)
     if (rounds != 0x7fffffffu) return;
 #endif
-    // lane q: the moments through round q (a slot's own total in the totals form, and for the top-up slot)
+    // A judging wave's LDS: a member's tail (64 words) and the finishing lane's result, word by word (lean_send_result) —
+    // in lds_part, which nobody reads after the ticket.  Member 0's tail is T.
+    static_assert(kPersistWaves * 128 * sizeof(u64) <= sizeof(lds_part), "the judging waves' words fit in lds_part");
+    u64* const lds_mine = reinterpret_cast<u64*>(&lds_part[0][0][0]) + wave * 128u;
+    unsigned long long* const lds_res = lds_mine + 64;
+    if (wave != 0) { lds_mine[lane] = mtail; wave_lds_handoff(); }
+    // lane q: the moments through round q (a slot's own total in the totals form, and for the top-up slot).  The members of
+    // a class agree on rounds, top-up slot and form: every judging wave scans the same rows the same way.
     const bool tslot = T.topup_slot != 0;
     const bool own = T.totals_only != 0 || (tslot && static_cast<unsigned>(lane) == rounds - 1u);
     // Row L of lds_round (round-major, the W waves of a round in wave order; at most 32 rows) goes to lane L — ONE batch of
@@ -490,64 +504,76 @@ __device__ __forceinline__ void lean_query(const LeanLaunch& a, const LeanRuns* 
     // rules judge: the moments through round q) and, beside it, every round's own total (the totals form; the top-up slot).
     // The loop this replaces — every lane walking all rows, one LDS round trip after the other — was 1.4 us of a 10 us
     // launch (profiles/round3_lean_ablation.txt).  Fixed shift pattern: bit-reproducible.
-    double tot[7];
-    {
-        const unsigned nrow = rounds * W;
-        double own_t[7];
+    for (unsigned mi = wave;;) {  // (the scan is redone per member: nothing lives across the judges)
+        double tot[7];
+        {
+            const unsigned nrow = rounds * W;
+            double own_t[7];
 #pragma unroll
-        for (int cc = 0; cc < 7; ++cc) tot[cc] = static_cast<unsigned>(lane) < nrow ? lds_round[lane][cc] : 0.0;
+            for (int cc = 0; cc < 7; ++cc) tot[cc] = static_cast<unsigned>(lane) < nrow ? lds_round[lane][cc] : 0.0;
 #pragma unroll
-        for (int cc = 0; cc < 7; ++cc) {
-            double o = tot[cc];  // the W rows of a round: aligned groups of W lanes (W = 1, 2, 4, 8 or 16), butterfly
-            if (W >= 2u) o += dpp_f64<0xB1>(o);    // lane ^ 1
-            if (W >= 4u) o += dpp_f64<0x4E>(o);    // lane ^ 2
-            if (W >= 8u) o += dpp_f64<0x141>(o);   // the other quad of the eight (all four of its lanes agree)
-            if (W >= 16u) o += dpp_f64<0x128>(o);  // the other half of the row of sixteen
-            own_t[cc] = o;
-            double p = tot[cc];  // inclusive prefix within the row of sixteen: shifts by 1, 2, 4, 8 (lanes shifted in from outside add 0)
-            p += dpp_f64<0x111>(p);
-            p += dpp_f64<0x112>(p);
-            p += dpp_f64<0x114>(p);
-            p += dpp_f64<0x118>(p);
-            const double carry = read_lane_f64(p, 15);  // rows 16 .. 31 sit in the second row of lanes: plus the first row's total
-            tot[cc] = p + (lane >= 16 ? carry : 0.0);
+            for (int cc = 0; cc < 7; ++cc) {
+                double o = tot[cc];  // the W rows of a round: aligned groups of W lanes (W = 1, 2, 4, 8 or 16), butterfly
+                if (W >= 2u) o += dpp_f64<0xB1>(o);    // lane ^ 1
+                if (W >= 4u) o += dpp_f64<0x4E>(o);    // lane ^ 2
+                if (W >= 8u) o += dpp_f64<0x141>(o);   // the other quad of the eight (all four of its lanes agree)
+                if (W >= 16u) o += dpp_f64<0x128>(o);  // the other half of the row of sixteen
+                own_t[cc] = o;
+                double p = tot[cc];  // inclusive prefix within the row of sixteen: shifts by 1, 2, 4, 8 (lanes shifted in from outside add 0)
+                p += dpp_f64<0x111>(p);
+                p += dpp_f64<0x112>(p);
+                p += dpp_f64<0x114>(p);
+                p += dpp_f64<0x118>(p);
+                const double carry = read_lane_f64(p, 15);  // rows 16 .. 31 sit in the second row of lanes: plus the first row's total
+                tot[cc] = p + (lane >= 16 ? carry : 0.0);
+            }
+            if (W > 1u) {  // lane q takes what the last row of round q holds
+                const int src = static_cast<int>((static_cast<unsigned>(lane) + 1u) * W - 1u) & 63;
+#pragma unroll
+                for (int cc = 0; cc < 7; ++cc) { tot[cc] = __shfl(tot[cc], src, 64); own_t[cc] = __shfl(own_t[cc], src, 64); }
+            }
+#pragma unroll
+            for (int cc = 0; cc < 7; ++cc) tot[cc] = own ? own_t[cc] : tot[cc];
         }
-        if (W > 1u) {  // lane q takes what the last row of round q holds
-            const int src = static_cast<int>((static_cast<unsigned>(lane) + 1u) * W - 1u) & 63;
-#pragma unroll
-            for (int cc = 0; cc < 7; ++cc) { tot[cc] = __shfl(tot[cc], src, 64); own_t[cc] = __shfl(own_t[cc], src, 64); }
-        }
-#pragma unroll
-        for (int cc = 0; cc < 7; ++cc) tot[cc] = own ? own_t[cc] : tot[cc];
-    }
 #ifdef AQE_ABL_FOLD3  // (ablation: ... here — rounds scanned, nothing judged or stored)
-    if (tot[0] + tot[6] != -1.0) { if (lane == 0) T.state->n_a = tot[0] + tot[1] + tot[2] + tot[3] + tot[4] + tot[5] + tot[6]; return; }
+        if (tot[0] + tot[6] != -1.0) { if (lane == 0) T.state->n_a = tot[0] + tot[1] + tot[2] + tot[3] + tot[4] + tot[5] + tot[6]; return; }
 #endif
-    lean_judge(T, tot, static_cast<unsigned>(lane), t0, epoch, lds_res);
-    wave_lds_handoff();  // (the finishing lane's words, read by the whole wave)
-    lean_send_result(T, lds_res, static_cast<unsigned>(lane));
+        const LeanTail& Tm = mi == 0 ? T : *reinterpret_cast<const LeanTail*>(lds_mine);
+        lean_judge(Tm, tot, static_cast<unsigned>(lane), t0, epoch, lds_res);
+        wave_lds_handoff();  // (the finishing lane's words, read by the whole wave)
+        lean_send_result(Tm, lds_res, static_cast<unsigned>(lane));
+        mi += kPersistWaves;
+        if (mi >= nmem) break;
+        // a class of more than 16 members: this wave's next one (its tail is fetched now: one round trip)
+        const u64 w = static_cast<unsigned>(lane) < kTailWords ? reinterpret_cast<const u64*>(&members[mi].tail)[lane] : 0ull;
+        wave_lds_handoff();
+        lds_mine[lane] = w;
+        wave_lds_handoff();
+    }
 }
 
 template <bool kNT, bool kWide>
 __global__ __launch_bounds__(kPersistThreads) void k_sweep_lean(LeanLaunch a) {
     const LeanKarg K = (LeanKarg)__builtin_amdgcn_kernarg_segment_ptr();
     // (the run table is read out of the kernel-argument segment itself, per lane: ordinary global memory)
-    lean_query<kNT, kWide>(a, &((const LeanLaunch*)K)->runs, K, blockIdx.x, gridDim.x, a.epoch);
+    lean_query<kNT, kWide>(a, &((const LeanLaunch*)K)->runs, K, nullptr, 1u, blockIdx.x, gridDim.x, a.epoch);
 }
 
 // A BATCH of queries in one launch (as k_sweep_multi, persist.hip): the grid is cut into one group of workgroups per
-// query, wg_map[blockIdx.x] = query << 32 | group size << 16 | index in the group, group q runs table[q] exactly as a
-// launch of its own would on that many workgroups.  Nothing here waits for anything — the last workgroup of a group to
-// arrive finishes its query — so groups may be dispatched in any order and there may be more of them than compute units.
+// sweep class, wg_map[blockIdx.x] = members << 48 | first member << 32 | group size << 16 | index in the group; group q
+// runs table[q] exactly as a launch of its own would on that many workgroups, and judges table[q .. q + members) on its
+// totals.  Nothing here waits for anything — the last workgroup of a group to arrive finishes its queries — so groups
+// may be dispatched in any order and there may be more of them than compute units.
 template <bool kNT>
 __global__ __launch_bounds__(kPersistThreads) void k_sweep_lean_multi(const LeanLaunch* table, const unsigned long long* wg_map, unsigned long long epoch) {
     const u64 me = uniform64(wg_map[blockIdx.x]);
-    const LeanKarg K = (LeanKarg)(table + (me >> 32));
+    const unsigned q = static_cast<unsigned>(me >> 32) & 0xffffu, nmem = static_cast<unsigned>(me >> 48);
+    const LeanKarg K = (LeanKarg)(table + q);
     LeanLaunch a;  // what the sweep reads, out of the table once
     a.amount = K->amount; a.ntiles = K->ntiles; a.tiles_per_wg = K->tiles_per_wg;
     a.has_where = K->has_where; a.wmin = K->wmin; a.wmax = K->wmax; a.shift = K->shift;
     a.partials = K->partials; a.counter = K->counter; a.tail.want_ticks = 0; a.wide = nullptr; a.nruns = 0;
-    lean_query<kNT, false>(a, &(table + (me >> 32))->runs, K, static_cast<unsigned>(me) & 0xffffu, static_cast<unsigned>(me >> 16) & 0xffffu, epoch);
+    lean_query<kNT, false>(a, &(table + q)->runs, K, table + q, nmem, static_cast<unsigned>(me) & 0xffffu, static_cast<unsigned>(me >> 16) & 0xffffu, epoch);
 }
 
 }  // namespace

@@ -1117,6 +1117,8 @@ struct BatchMulti {
     unsigned long long* d_wgmap = nullptr; // [grid] workgroup -> (plan, group size, index in the group)
     unsigned grid = 0;
     uint64_t samples = 0;                  // rows one launch sweeps (all plans)
+    uint32_t classes = 0;                  // lean: sweep classes (groups of the launch); else one per plan
+    uint64_t rows_loaded = 0;              // rows the launch actually loads (each class's rows once)
     bool nt = false;                       // the launch's loads go past the caches (build_multi)
     const double* totals = nullptr;        // kind 1: the buffer the descriptors were written for
     uint64_t stride = 0;
@@ -1141,7 +1143,7 @@ namespace {
 
 void free_multi(BatchMulti& m) {
     for (SweepForm& f : m.forms)
-        if (f.d_ppart) (void)hipFree(f.d_ppart);
+        if (f.d_ppart) (void)hipFree(f.d_ppart);  // (a sweep class's members hold a copy of its form without the partial list)
     m.forms.clear();
     if (m.d_table) (void)hipFree(m.d_table);
     if (m.d_ltable) (void)hipFree(m.d_ltable);
@@ -1153,10 +1155,90 @@ void free_multi(BatchMulti& m) {
     m.built = false;
 }
 
+// What makes a plan's lean descriptor the plan's own rather than its sweep's: the judge's rules and estimator, where
+// the result, state and totals go, and the hand-off scratch.  Everything else — view, run table, WHERE bounds, shift,
+// rounds, slot layout, forms — decides the partials.
+void mask_member_fields(LeanLaunch& a) {
+    std::memset(&a.tail.fold, 0, sizeof(a.tail.fold));
+    std::memset(&a.tail.fin, 0, sizeof(a.tail.fin));
+    a.tail.out_totals = nullptr; a.tail.state = nullptr; a.tail.result = nullptr; a.tail.result_seq = nullptr;
+    a.partials = nullptr; a.counter = nullptr; a.epoch = 0;
+}
+
 uint64_t head_tiles(const aqe_plan* p) {
     uint64_t t = p->host.has_topup ? p->topup.ntiles : 0;
     for (size_t r = 0; r < p->r_head && r < p->rounds.size(); ++r) t += p->rounds[r].ntiles;
     return t;
+}
+
+// Sweep classes of a lean batch (kind 0).  Plans whose lean forms sweep the same thing produce bit-identical partials,
+// so ONE group of workgroups sweeps for all of them and its folding workgroup judges each (lean.hip, lean_query).  Two
+// plans are of one class when they take the same form (head or full) and their descriptors, built for one common grid
+// (a probe of one workgroup), agree byte for byte outside the fields that are a plan's own (mask_member_fields).  A class
+// gets the workgroups its members would have had: the sum of their group sizes, at most kMaxPersistGrid (a class that
+// would outgrow it is split), and one form built for that many, which every member's entry of `lf` then holds (the
+// partial list owned by the first member's).  Kind 1 (totals) and AQE_BATCH_SHARE=0: one class per plan.
+int sweep_classes(aqe_batch* b, int kind, const std::vector<char>& head, const std::vector<uint32_t>& gs, std::vector<SweepForm>& lf,
+                  std::vector<std::vector<size_t>>& classes) {
+    static const bool share_off = [] { const char* e = std::getenv("AQE_BATCH_SHARE"); return e && e[0] == '0'; }();  // diagnostics: A/B in one build
+    const size_t n = b->plans.size();
+    classes.clear();
+    if (kind != 0 || share_off) {
+        for (size_t i = 0; i < n; ++i) classes.push_back({i});
+        return AQE_OK;
+    }
+    auto rounds_of = [&](size_t i) { return head[i] ? b->plans[i]->r_head : b->plans[i]->rounds.size(); };
+    std::map<std::string, size_t> open;  // key -> the class that takes the next plan of that key
+    std::vector<uint64_t> cgrid;
+    auto d = std::make_unique<LeanLaunch>();
+    for (size_t i = 0; i < n; ++i) {
+        aqe_plan* p = b->plans[i];
+        std::string key;
+        SweepForm probe;
+        int rc = build_lean_form(p, head[i] != 0, probe, 1, rounds_of(i));
+        if (rc != AQE_OK) return rc;
+        if (probe.ok && !probe.wide) {
+            fill_lean(p, probe, false, nullptr, 0, *d);
+            d->tail.want_ticks = 0;  // (as build_multi writes them for every plan of a batch)
+            d->tail.keep_state = 0;
+            mask_member_fields(*d);
+            key.assign(reinterpret_cast<const char*>(d.get()), sizeof(LeanLaunch));
+            key.push_back(head[i]);
+        }
+        if (probe.d_ppart) (void)hipFree(probe.d_ppart);
+        size_t k = classes.size();
+        const auto it = key.empty() ? open.end() : open.find(key);
+        if (it != open.end() && cgrid[it->second] + gs[i] <= static_cast<uint64_t>(kMaxPersistGrid)) k = it->second;
+        if (k == classes.size()) {
+            classes.emplace_back();
+            cgrid.push_back(0);
+            if (!key.empty()) open[key] = k;
+        }
+        classes[k].push_back(i);
+        cgrid[k] += gs[i];
+    }
+    std::vector<std::vector<size_t>> alone;  // members of a class whose form did not come out: each on its own
+    for (size_t k = 0; k < classes.size(); ++k) {
+        std::vector<size_t>& cl = classes[k];
+        if (cl.size() < 2) continue;
+        SweepForm F;
+        int rc = build_lean_form(b->plans[cl[0]], head[cl[0]] != 0, F, static_cast<uint32_t>(cgrid[k]), rounds_of(cl[0]));
+        if (rc != AQE_OK) return rc;
+        if (!F.ok || F.wide) {
+            if (F.d_ppart) (void)hipFree(F.d_ppart);
+            for (size_t j = 1; j < cl.size(); ++j) alone.push_back({cl[j]});
+            cl.resize(1);
+            continue;
+        }
+        for (size_t j = 0; j < cl.size(); ++j) {
+            SweepForm& f = lf[cl[j]];
+            if (f.d_ppart) (void)hipFree(f.d_ppart);
+            f = F;
+            if (j) f.d_ppart = nullptr;
+        }
+    }
+    classes.insert(classes.end(), alone.begin(), alone.end());
+    return AQE_OK;
 }
 
 // Builds the one-launch form of a batch: group sizes in proportion to the plans' tiles (powers of two, the context's
@@ -1216,10 +1298,13 @@ int build_multi(aqe_batch* b, int kind, double* dev_totals, uint64_t row_stride)
     m.forms.resize(n);
     std::vector<PersistLaunch> table(n);
     std::vector<LeanLaunch> ltable;
+    std::vector<std::vector<size_t>> classes;  // lean: the sweep classes, plans in batch order
     std::vector<unsigned long long> wgmap, monitors;
     const char* layout_env = std::getenv("AQE_MULTI_LAYOUT");
     const bool packed_layout = layout_env && std::strcmp(layout_env, "packed") == 0;
     m.samples = 0;
+    m.rows_loaded = 0;
+    m.classes = static_cast<uint32_t>(n);
     {   // Lean groups (lean.hip, k_sweep_lean_multi) when every plan of the batch qualifies: no monitor waves, the last
         // workgroup of a group to arrive finishes its query.  (AQE_MULTI_LEAN=0: the groups of k_sweep_multi.)
         static const bool lean_off = [] { const char* e = std::getenv("AQE_MULTI_LEAN"); return e && e[0] == '0'; }();
@@ -1233,14 +1318,22 @@ int build_multi(aqe_batch* b, int kind, double* dev_totals, uint64_t row_stride)
             all = lf[i].ok && !lf[i].wide;  // (the groups of a batch read their run table out of the batch's descriptor table)
         }
         if (all) {
+            int rc = sweep_classes(b, kind, head, gs, lf, classes);
+            if (rc != AQE_OK) { for (SweepForm& f : lf) if (f.d_ppart) (void)hipFree(f.d_ppart); return rc; }
+            if (n > 0xffffu) { for (SweepForm& f : lf) if (f.d_ppart) (void)hipFree(f.d_ppart); return fail(c, AQE_ERR_UNSUPPORTED, "more than 65535 plans in one batch"); }
             m.lean = true;
-            ltable.resize(n);
-            for (size_t i = 0; i < n; ++i) {
-                fill_lean(b->plans[i], lf[i], kind == 1, kind == 1 ? dev_totals + i * row_stride : nullptr, 0, ltable[i]);
-                ltable[i].tail.want_ticks = 0;
-                ltable[i].tail.keep_state = 0;  // (a batch never enqueues a top-up launch up front: fetch() runs the due ones)
-                m.samples += lf[i].samples;
+            // the descriptor table in class order (a class's members consecutive, its first one's descriptor sweeps)
+            for (const std::vector<size_t>& cl : classes) {
+                for (size_t i : cl) {
+                    ltable.emplace_back();
+                    fill_lean(b->plans[i], lf[i], kind == 1, kind == 1 ? dev_totals + i * row_stride : nullptr, 0, ltable.back());
+                    ltable.back().tail.want_ticks = 0;
+                    ltable.back().tail.keep_state = 0;  // (a batch never enqueues a top-up launch up front: fetch() runs the due ones)
+                    m.samples += lf[i].samples;
+                }
+                m.rows_loaded += lf[cl[0]].samples;
             }
+            m.classes = static_cast<uint32_t>(classes.size());
             m.forms = std::move(lf);
         } else {
             for (SweepForm& f : lf) if (f.d_ppart) (void)hipFree(f.d_ppart);
@@ -1271,6 +1364,7 @@ int build_multi(aqe_batch* b, int kind, double* dev_totals, uint64_t row_stride)
         table[i].stamps = nullptr;  // (the stamp layout is per launch grid: single launches only)
         table[i].want_ticks = 0;
         m.samples += F.samples;
+        m.rows_loaded += F.samples;
     }
     // Workgroup order (wg_map): XCD-aware.  Workgroup p runs on compute die p mod 8, each die has its own L2, and
     // workgroup k of a group sweeps the k-th slice of its query's tiles.  A group's workgroups are therefore contiguous,
@@ -1283,11 +1377,26 @@ int build_multi(aqe_batch* b, int kind, double* dev_totals, uint64_t row_stride)
     // AQE_MULTI_LAYOUT=packed lists every group's sweeper-only workgroups first and all the monitors' workgroups last
     // instead: no alignment, the queries of a batch do not meet in a die's L2, and the measured bandwidth is the memory
     // system's alone (the bench reports that layout beside the default).
-    std::vector<size_t> order;
-    for (size_t i = 0; i < n; ++i) if (gs[i] >= 8) order.push_back(i);
-    for (size_t i = 0; i < n; ++i) if (gs[i] < 8) order.push_back(i);
-    for (size_t i : order) {
-        const unsigned long long g = gs[i], tag = (static_cast<unsigned long long>(i) << 32) | (g << 16);
+    // Lean: one group per sweep class (its size the sum of its members' — not always a power of two: groups whose size is
+    // a multiple of 8 first), tagged with its first member's place in the descriptor table and its member count.
+    std::vector<unsigned long long> tags;
+    if (m.lean) {
+        std::vector<unsigned long long> later;
+        unsigned long long first = 0;
+        for (const std::vector<size_t>& cl : classes) {
+            unsigned long long g = 0;
+            for (size_t i : cl) g += gs[i];
+            const unsigned long long tag = (static_cast<unsigned long long>(cl.size()) << 48) | (first << 32) | (g << 16);
+            (g % 8 == 0 ? tags : later).push_back(tag);
+            first += cl.size();
+        }
+        tags.insert(tags.end(), later.begin(), later.end());
+    } else {
+        for (size_t i = 0; i < n; ++i) if (gs[i] >= 8) tags.push_back((static_cast<unsigned long long>(i) << 32) | (static_cast<unsigned long long>(gs[i]) << 16));
+        for (size_t i = 0; i < n; ++i) if (gs[i] < 8) tags.push_back((static_cast<unsigned long long>(i) << 32) | (static_cast<unsigned long long>(gs[i]) << 16));
+    }
+    for (const unsigned long long tag : tags) {
+        const unsigned long long g = (tag >> 16) & 0xffffu;
         if (packed_layout) monitors.push_back(tag);
         else wgmap.push_back(tag);
         for (unsigned long long k = 1; k < g; ++k) wgmap.push_back(tag | k);
@@ -1295,7 +1404,7 @@ int build_multi(aqe_batch* b, int kind, double* dev_totals, uint64_t row_stride)
     wgmap.insert(wgmap.end(), monitors.begin(), monitors.end());
     m.grid = static_cast<unsigned>(wgmap.size());
     if (m.lean) {
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&m.d_ltable), n * sizeof(LeanLaunch)));
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&m.d_ltable), n * sizeof(LeanLaunch)));  // (n entries: every plan once, in class order)
         HIPCHK(c, hipMemcpy(m.d_ltable, ltable.data(), n * sizeof(LeanLaunch), hipMemcpyHostToDevice));
     } else {
         HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&m.d_table), n * sizeof(PersistLaunch)));
@@ -1582,6 +1691,15 @@ int aqe_batch_launch_info(aqe_batch* b, float* ms, uint64_t* samples, uint32_t* 
         HIPCHK(b->ctx, hipEventSynchronize(b->pev1));
         HIPCHK(b->ctx, hipEventElapsedTime(ms, b->pev0, b->pev1));
     }
+    return AQE_OK;
+}
+
+int aqe_batch_share_info(aqe_batch* b, uint32_t* classes, uint64_t* rows_loaded) {
+    if (!b) return AQE_ERR_INVALID;
+    if (b->last_kind < 0) return fail(b->ctx, AQE_ERR_INVALID, "no one-launch execution yet");
+    const BatchMulti& m = b->multi[b->last_kind];
+    if (classes) *classes = m.classes;
+    if (rows_loaded) *rows_loaded = m.rows_loaded;
     return AQE_OK;
 }
 

@@ -167,6 +167,13 @@ class Batch:
         nat.check(nat.lib().aqe_batch_launch_info(self._h, C.byref(ms) if timed else None, C.byref(n), C.byref(g)), self.engine._h)
         return (ms.value if timed else None), n.value, g.value
 
+    def share_info(self):
+        """(sweep classes, rows loaded) of the most recent one-launch execution: plans that sweep the same rows the same
+        way are swept once and judged each (aqe_batch_share_info)."""
+        k, r = C.c_uint32(), C.c_uint64()
+        nat.check(nat.lib().aqe_batch_share_info(self._h, C.byref(k), C.byref(r)), self.engine._h)
+        return k.value, r.value
+
 
 class Comm:
     """RCCL communicator behind the C ABI (aqe_comm): in-place f64 all-reduce on the engine's GPU.

@@ -504,6 +504,12 @@ AQE_API int aqe_batch_enqueue_all(aqe_batch* batch, void* stream);
  * launch, the rows it sweeps (all plans; 8 B each) and its workgroups.  Any of the outputs may be NULL. */
 AQE_API int aqe_batch_set_profiling(aqe_batch* batch, int enable);
 AQE_API int aqe_batch_launch_info(aqe_batch* batch, float* ms, uint64_t* samples, uint32_t* workgroups);
+/* How the most recent one-launch execution shared its sweeps: plans whose sweeps load the same rows the same way (the
+ * same sampler, WHERE bounds and rounds; they may differ in aggregate and error target) form one sweep class, swept
+ * once and judged per plan.  `classes`: groups of the launch; `rows_loaded`: rows it loads (each class's once) — beside
+ * aqe_batch_launch_info's `samples`, the rows its queries aggregate.  AQE_BATCH_SHARE=0 in the environment: one class
+ * per plan.  The totals form (aqe_batch_enqueue_sweeps) does not share.  Either output may be NULL. */
+AQE_API int aqe_batch_share_info(aqe_batch* batch, uint32_t* classes, uint64_t* rows_loaded);
 /* ---- the collective behind the C ABI: RCCL over xGMI ---------------------------------------------
  * One all-reduce SUM of the moment vectors replaces the reference's in-process merges (mutex-guarded vector, CAS on
  * atomic<double>, DB.cpp:948-951, 966-967, 2031-2036).  librccl is opened on first use (no link-time dependency; a
