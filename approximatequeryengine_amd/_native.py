@@ -160,6 +160,7 @@ def lib() -> C.CDLL:
         "aqe_device_write": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),
         "aqe_query_defaults": (None, [P(Query)]),
         "aqe_plan_families": (C.c_int, [P(Query), u64, u64, u64, u32, P(Family), u32, P(u32), P(u32), P(u64)]),
+        "aqe_union_cover": (C.c_int, [P(u64), P(u64), P(u32), u32, u32, P(u64), P(u64), u32, P(u32), P(u32), P(u32), u32, P(u32), P(u64), P(u64)]),
         "aqe_plan_random_indices": (C.c_int, [u64, dbl, u32, u64, u64, P(u64), u64, P(u64)]),
         "aqe_plan_row_list": (C.c_int, [P(Query), u64, u64, u64, P(u64), u64, P(u64)]),
         "aqe_plan_adaptive_families": (C.c_int, [P(Query), u64, P(dbl), P(Family), u32, P(u32), P(u64)]),
@@ -213,6 +214,7 @@ def lib() -> C.CDLL:
         "aqe_batch_set_profiling": (C.c_int, [vp, C.c_int]),
         "aqe_batch_launch_info": (C.c_int, [vp, P(C.c_float), P(u64), P(u32)]),
         "aqe_batch_share_info": (C.c_int, [vp, P(u32), P(u64)]),
+        "aqe_batch_union_info": (C.c_int, [vp, P(u32), P(u64)]),
         "aqe_comm_unique_id": (C.c_int, [vp]),
         "aqe_comm_create": (C.c_int, [vp, vp, C.c_int, C.c_int, P(vp)]),
         "aqe_comm_create_all": (C.c_int, [P(vp), C.c_int, P(vp)]),

@@ -102,6 +102,37 @@ int aqe_plan_families(const aqe_query* q, uint64_t n_global, uint64_t shard_lo, 
     return AQE_OK;
 }
 
+int aqe_union_cover(const uint64_t* run_lo, const uint64_t* run_len, const uint32_t* run_target, uint32_t n_runs, uint32_t n_targets,
+                    uint64_t* piece_lo, uint64_t* piece_hi, uint32_t cap_pieces, uint32_t* n_pieces,
+                    uint32_t* target_begin, uint32_t* target_piece, uint32_t cap_incidences, uint32_t* n_incidences,
+                    uint64_t* n_slots, uint64_t* n_tiles) {
+    if (n_runs && (!run_lo || !run_len || !run_target)) return AQE_ERR_INVALID;
+    std::vector<UnionRun> runs(n_runs);
+    for (uint32_t i = 0; i < n_runs; ++i) runs[i] = UnionRun{run_lo[i], run_len[i], run_target[i]};
+    UnionCover cv;
+    if (!build_union_cover(runs, n_targets, cv)) return fail(nullptr, AQE_ERR_INVALID, "a run's target is not below n_targets");
+    const size_t np = cv.piece_lo.size(), ni = cv.target_piece.size();
+    if (n_pieces) *n_pieces = static_cast<uint32_t>(np);
+    if (n_incidences) *n_incidences = static_cast<uint32_t>(ni);
+    if (n_slots) *n_slots = cv.slots;
+    if (n_tiles) {
+        std::vector<UnionTile> tiles;
+        union_tiles(cv, tiles);
+        *n_tiles = tiles.size();
+    }
+    if (piece_lo || piece_hi) {
+        if (cap_pieces < np) return fail(nullptr, AQE_ERR_CAPACITY, "piece buffer too small");
+        if (piece_lo) std::copy(cv.piece_lo.begin(), cv.piece_lo.end(), piece_lo);
+        if (piece_hi) std::copy(cv.piece_hi.begin(), cv.piece_hi.end(), piece_hi);
+    }
+    if (target_begin) std::copy(cv.target_begin.begin(), cv.target_begin.end(), target_begin);
+    if (target_piece) {
+        if (cap_incidences < ni) return fail(nullptr, AQE_ERR_CAPACITY, "incidence buffer too small");
+        std::copy(cv.target_piece.begin(), cv.target_piece.end(), target_piece);
+    }
+    return AQE_OK;
+}
+
 int aqe_plan_adaptive_families(const aqe_query* q, uint64_t n_global, const double* zone_var10, aqe_family* fams,
                                uint32_t cap, uint32_t* n_out, uint64_t* samples_out) {
     if (!q || !zone_var10) return AQE_ERR_INVALID;

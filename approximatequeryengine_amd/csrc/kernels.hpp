@@ -233,7 +233,7 @@ struct LeanTail {
     uint32_t rounds, finalize_here, topup_gate, more_rounds, topup_slot, want_ticks, totals_only;  // as in PersistLaunch
     uint32_t keep_state;       // 1: a launch that reads the query state is already enqueued behind this one (the top-up, device-gated)
     uint32_t slot_begin[kMaxPersistRounds + 1];  // round r owns the slots [slot_begin[r], slot_begin[r + 1]) of the flat list
-    uint32_t pad1;
+    uint32_t union_row;        // a member of a union group: its class's first row of round totals in the fold (lean.hip, lean_union)
     FoldParams fold;
     FinalizeParams fin;
     double* out_totals;        // totals_only: [rounds][kVec]
@@ -242,6 +242,7 @@ struct LeanTail {
     unsigned long long* result_seq;
 };
 static_assert(sizeof(LeanTail) % 8 == 0 && sizeof(LeanTail) <= 64 * 8, "one 8-byte load per lane of a wave stages the tail");
+struct LeanUnion;
 struct LeanLaunch {
     const double* amount;
     uint32_t ntiles;
@@ -253,13 +254,41 @@ struct LeanLaunch {
     double* partials;          // [slots][kVec]: doubles 0..6 = a workgroup's partial of one round
     unsigned* counter;         // arrival tickets (k_round's), zero between launches
     unsigned long long epoch;
-    const LeanWideRuns* wide;  // null: the run table below; else the plan's table of `nruns` > kLeanMaxRuns runs
+    union {
+        const LeanWideRuns* wide;  // null: the run table below; else the plan's table of `nruns` > kLeanMaxRuns runs
+        const LeanUnion* uni;      // a batch's descriptor table (never wide there): the first member of a union group
+    };                             // points at the union it sweeps instead of its own runs; null otherwise
     LeanTail tail;
     // The run table travels IN the descriptor — the kernel arguments of a single launch, the batch's table otherwise — so a
     // wave's very first loads (its lane's two runs) depend on nothing but the descriptor's address.
     LeanRuns runs;
 };
 static_assert(sizeof(LeanLaunch) <= 4096, "kernel arguments are limited to 4 KB");
+// A UNION GROUP of a batch (plans.hip, build_union; lean.hip, lean_union): sweep classes that read the same view with the
+// same shift and WHERE bounds, swept as ONE cover of the union of their runs.  Its group's first descriptor (`uni` set)
+// carries the union's tile count and share per workgroup in ntiles / tiles_per_wg, and its partial list in `partials`:
+// [entries][4] doubles (n, S, Q, rows visited) of one workgroup's rows of one piece, piece-major, workgroups ascending.
+// One device block: this header, then tile_row [ntiles] (u64), tile_meta [ntiles rounded up to even] (u32), then the
+// workgroups' records [group size][kUnionWgPieces + 1] (u32): its first piece, then the entry of each of its pieces.
+constexpr int kUnionMaxPieces = 512;        // so that entries < pieces + workgroups fit the fold's staging (768)
+constexpr int kUnionMaxEntries = 768;
+constexpr int kUnionMaxIncidences = 2048;   // (piece, target) pairs: two per thread of the fold
+constexpr int kUnionMaxRows = 256;          // (class, round) rows of totals; targets = 2 x rows (pointer groups a, b)
+constexpr int kUnionWgPieces = 32;          // pieces one workgroup's share may hold (a bit each in the waves' masks)
+constexpr int kUnionMaxTilesPerWg = 64 * kPersistWaves;  // lane j of wave w holds tile w + 16 j of the share
+// tile_meta: bits 0..15 the tile's first piece, 16..26 the end of its rows (vhi), 27 their start (vlo: 0 or 1) — see
+// planner.hpp, UnionTile — and this bit: 1024 rows of one piece, no masks
+constexpr uint32_t kUnionTileWhole = 1u << 31;
+struct LeanUnion {
+    const uint64_t* piece_lo;      // [pieces]
+    const uint64_t* piece_hi;      // [pieces]
+    const uint32_t* piece_entry;   // [pieces + 1]: piece p's partials are entries [piece_entry[p], piece_entry[p + 1])
+    const uint32_t* target_begin;  // [targets + 1]: target t (2 row + group) adds the pieces listed in
+    const uint32_t* target_entry;  //   target_entry[target_begin[t] .. target_begin[t + 1]) — each piece's first entry, ascending
+    uint32_t npieces, ntargets, nincidences, nentries;
+    uint32_t pad[2];
+};
+static_assert(sizeof(LeanUnion) == 64, "the union header is staged as 8 words");
 hipError_t launch_sweep_lean(const LeanLaunch& a, unsigned grid, bool nt, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // a batch of queries in one launch: table[q] describes query q (its epoch field is ignored), wg_map as for launch_sweep_multi
 hipError_t launch_sweep_lean_multi(const LeanLaunch* table, const unsigned long long* wg_map, unsigned long long epoch, unsigned grid, bool nt,

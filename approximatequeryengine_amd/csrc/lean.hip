@@ -252,6 +252,293 @@ __device__ __forceinline__ void lean_send_result(const LeanTail& T, const unsign
     else if (lane == kWords) __hip_atomic_store(T.result_seq, res_words[kWords], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// One lane of a workgroup that has published its partials: its ticket.  1 for the last of the G workgroups to arrive.
+// At most 256 arrivals: 16 shards of 16 (a same-address atomic serialises at ~16 ns), then the top counter.
+__device__ __forceinline__ int lean_ticket(unsigned* const counter, const unsigned bid, const unsigned G) {
+    int last = 0;
+    unsigned* const ct = counter + static_cast<size_t>(kShards) * kShardStride;
+    constexpr unsigned kLeanShards = 16;
+    if (G <= kLeanShards) {
+        if (__hip_atomic_fetch_add(ct, 1u, AQE_RLX) == G - 1u) { __hip_atomic_store(ct, 0u, AQE_RLX); last = 1; }
+    } else {
+        const unsigned sh = bid % kLeanShards;
+        const unsigned members = (G - sh + kLeanShards - 1u) / kLeanShards;
+        unsigned* const cs = counter + static_cast<size_t>(sh) * kShardStride;
+        if (__hip_atomic_fetch_add(cs, 1u, AQE_RLX) == members - 1u) {
+            __hip_atomic_store(cs, 0u, AQE_RLX);
+            if (__hip_atomic_fetch_add(ct, 1u, AQE_RLX) == kLeanShards - 1u) { __hip_atomic_store(ct, 0u, AQE_RLX); last = 1; }
+        }
+    }
+    return last;
+}
+
+// A UNION GROUP of a batch (plans.hip, build_union): sweep classes that read the same view with the same shift and WHERE
+// bounds, swept as one.  The union of their runs is cut into PIECES — slot ranges over which one multiset of (class,
+// round, pointer group) targets covers every slot — and tiled in 1024-slot tiles over the covered spans (from an even
+// slot: every 16-byte load aligned; the gaps between spans are skipped).  Workgroup b sweeps the contiguous share
+// [b K, (b + 1) K) of the tiles, as a multi-round query does, with ONE accumulator per piece (n, S, Q, rows: a piece feeds
+// the same moments to every target that covers it), flushed when the piece changes as a round's is when the round
+// changes.  A tile inside one piece takes lean_tile's unmasked path; a tile that crosses a piece boundary or a span's end
+// is loaded once and summed per piece under row masks (a pair may be split).  The workgroup publishes one partial per piece
+// it holds slots of and draws one ticket; the last one folds: the partials per piece in workgroup order, the pieces into
+// the targets in ascending piece order, the targets into each class's rows of round totals — and from there every member
+// is judged as lean_query judges a class's.  Fixed orders throughout: bit-reproducible.
+template <bool kNT>
+__device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion* const U, const LeanKarg K, const LeanLaunch* const members, const unsigned nmem,
+                                           const unsigned bid, const unsigned G, const unsigned long long epoch,
+                                           double (&lds_part)[kMaxPersistRounds][kPersistWaves][kVec], double (&lds_round)[kMaxPersistRounds][kVec],
+                                           unsigned (&lds_mask)[kPersistWaves], u64 (&lds_tail)[64], int& s_last) {
+    static_assert(kUnionWgPieces <= kMaxPersistRounds && kUnionWgPieces <= 32, "a share's pieces: a row of lds_part and a mask bit each");
+    static_assert(sizeof(LeanUnion) <= sizeof(lds_round), "the union's header is staged in lds_round");
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = threadIdx.x >> 6;
+    const unsigned t_lo = bid * a.tiles_per_wg;
+    const unsigned t_end = t_lo + a.tiles_per_wg < a.ntiles ? t_lo + a.tiles_per_wg : a.ntiles;
+    // the share's tiles: lane j of wave w holds tile t_lo + w + 16 j (one batch of loads, as the run table in lean_query)
+    const u64* const tile_row = reinterpret_cast<const u64*>(U + 1);
+    const unsigned* const tile_meta = reinterpret_cast<const unsigned*>(tile_row + a.ntiles);
+    const unsigned* const wg = tile_meta + ((a.ntiles + 1u) & ~1u) + static_cast<size_t>(bid) * (kUnionWgPieces + 1);
+    const unsigned my_t = t_lo + wave + kPersistWaves * static_cast<unsigned>(lane);
+    u64 my_row = 0;
+    unsigned my_meta = 0;
+    if (my_t < t_end) { my_row = tile_row[my_t]; my_meta = tile_meta[my_t]; }
+    const unsigned p0 = __builtin_amdgcn_readfirstlane(wg[0]);  // the share's first piece: its pieces are p0, p0 + 1, ...
+    unsigned my_entry = 0;  // (wave 0) lane j: where the share's partial of piece p0 + j goes
+    if (wave == 0 && lane < kUnionWgPieces) my_entry = wg[1 + lane];
+    // what only the folding workgroup reads, fetched now (lean_query): member 0's tail, and the union's header
+    const bool stager = wave == kPersistWaves - 1u, head_stager = wave == kPersistWaves - 2u;
+    u64 tail_word = 0, head_word = 0;
+    if (stager && static_cast<unsigned>(lane) < sizeof(LeanTail) / 8u) tail_word = reinterpret_cast<const AQE_KARG u64*>(&K->tail)[lane];
+    if (head_stager && static_cast<unsigned>(lane) < sizeof(LeanUnion) / 8u) head_word = reinterpret_cast<const u64*>(U)[lane];
+#pragma unroll
+    for (unsigned i = 0; i < kMaxPersistRounds * kVec / 64; ++i) {
+        const unsigned x = static_cast<unsigned>(lane) + 64u * i;
+        lds_part[x >> 3][wave][x & 7u] = 0.0;
+    }
+
+    double ps = 0.0, pq = 0.0;
+    unsigned pn = 0, pv = 0, cur = ~0u, touched = 0;  // the piece this wave is in; the share's pieces it has been in
+    auto take = [&](unsigned piece, const TileAcc& ta) {
+        if (piece != cur) {
+            if (cur != ~0u) {
+                const double v[7] = {static_cast<double>(pn), ps, pq, static_cast<double>(pv), 0.0, 0.0, 0.0};
+                const double mine = wave_sum7(v, lane);  // lane 8c holds component c
+                if ((lane & 7) == 0 && lane < 32) lds_part[cur - p0][wave][lane >> 3] = mine;
+                touched |= 1u << (cur - p0);
+                ps = 0.0; pq = 0.0; pn = 0; pv = 0;
+            }
+            cur = piece;
+        }
+        pn += ta.n; pv += ta.nv; ps += ta.s; pq += ta.q;
+    };
+    for (unsigned j = 0;; ++j) {
+        if (t_lo + wave + kPersistWaves * j >= t_end) break;
+        const u64 row = read_lane_u64(my_row, j);
+        const unsigned meta = __builtin_amdgcn_readlane(my_meta, j), piece = meta & 0xffffu;
+        const double* const base = a.amount + row;
+        if (meta & kUnionTileWhole) {
+            TileAcc ta;
+            lean_tile<kNT>(base, static_cast<unsigned>(kDenseTileOrdinals), a.amount, lane, a.has_where, a.wmin, a.wmax, a.shift, ta);
+            take(piece, ta);
+            continue;
+        }
+        // the tile owns the rows [vlo, vhi) and holds slots of one piece or of two adjacent ones: the same 16-byte loads, a
+        // pair that leaves the rows never addressed (such a lane reads rows 0 and 1 of the view), an odd last row on its
+        // own; both pieces' sums in one pass under row masks, then handed on (nothing of the tile is live across a flush)
+        const unsigned vhi = (meta >> 16) & 0x7ffu, vlo = (meta >> 27) & 1u;
+        Row2 v2[kTileUnroll];
+        bool ok[kTileUnroll];
+#pragma unroll
+        for (int k = 0; k < kTileUnroll; ++k) {
+            const unsigned oi = 2u * static_cast<unsigned>(lane) + 128u * static_cast<unsigned>(k);
+            ok[k] = oi + 1u < vhi;
+            const Row2* const p = reinterpret_cast<const Row2*>(ok[k] ? base + oi : a.amount);
+            if (kNT) {
+                v2[k].x = __builtin_nontemporal_load(&p->x);
+                v2[k].y = __builtin_nontemporal_load(&p->y);
+            } else {
+                v2[k] = *p;
+            }
+        }
+        const double xo = (vhi & 1u) ? base[vhi - 1u] : 0.0;  // (wave-uniform)
+        const u64 phi = U->piece_hi[piece];
+        const bool two = phi - row < vhi;  // (wave-uniform) the next piece starts inside the tile
+        const unsigned mid = two ? static_cast<unsigned>(phi - row) : vhi;
+        const unsigned hi = two ? (U->piece_hi[piece + 1u] - row < vhi ? static_cast<unsigned>(U->piece_hi[piece + 1u] - row) : vhi) : vhi;
+        TileAcc t0, t1;  // rows [vlo, mid) of the first piece, [mid, hi) of the second
+        auto add = [&](double x, unsigned r, bool ld) {
+            const bool i0 = ld && r >= vlo && r < mid, i1 = ld && r >= mid && r < hi;
+            const bool w = !a.has_where || (x >= a.wmin && x <= a.wmax);
+            const double d0 = i0 && w ? x - a.shift : 0.0, d1 = i1 && w ? x - a.shift : 0.0;
+            t0.nv += i0 ? 1u : 0u; t0.n += i0 && w ? 1u : 0u; t0.s += d0; t0.q += d0 * d0;
+            t1.nv += i1 ? 1u : 0u; t1.n += i1 && w ? 1u : 0u; t1.s += d1; t1.q += d1 * d1;
+        };
+#pragma unroll
+        for (int k = 0; k < kTileUnroll; ++k) {
+            const unsigned oi = 2u * static_cast<unsigned>(lane) + 128u * static_cast<unsigned>(k);
+            add(v2[k].x, oi, ok[k]);
+            add(v2[k].y, oi + 1u, ok[k]);
+        }
+        if (vhi & 1u) add(xo, vhi - 1u, lane == 0);  // the odd last row, folded by lane 0
+        take(piece, t0);
+        if (two) take(piece + 1u, t1);
+    }
+    if (cur != ~0u) take(~0u, TileAcc{});  // (flushes the last piece)
+    if (lane == 0) lds_mask[wave] = touched;
+    if (stager) lds_tail[lane] = tail_word;
+    if (head_stager && static_cast<unsigned>(lane) < sizeof(LeanUnion) / 8u) reinterpret_cast<u64*>(&lds_round[0][0])[lane] = head_word;
+    __syncthreads();
+
+    // ---- the share's partial of every piece it holds slots of: data, drain, ticket (as lean_query) ----
+    if (wave == 0) {
+        unsigned m = 0;
+#pragma unroll
+        for (unsigned j = 0; j < kPersistWaves; ++j) m |= lds_mask[j];
+        m = __builtin_amdgcn_readfirstlane(m);
+        while (m) {
+            const unsigned j = static_cast<unsigned>(__builtin_ctz(m));
+            m &= m - 1u;
+            const unsigned e = __builtin_amdgcn_readlane(my_entry, j);
+            if (lane < 4) {
+                double x[kPersistWaves];
+#pragma unroll
+                for (unsigned w = 0; w < kPersistWaves; ++w) x[w] = lds_part[j][w][lane];
+                double s = 0.0;
+#pragma unroll
+                for (unsigned w = 0; w < kPersistWaves; ++w) s += x[w];  // wave order
+                __hip_atomic_store(a.partials + static_cast<size_t>(e) * 4u + lane, s, AQE_RLX);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the partials are out before the ticket is drawn
+        if (lane == 0) s_last = lean_ticket(a.counter, bid, G);
+    }
+    __syncthreads();
+    if (!s_last) return;
+
+    // ---- the last workgroup folds.  ONE batch of loads: the partial list (an entry per thread), the pieces' and the
+    //      targets' ranges, the incidence list (two per thread) and the other members' tails; staged in lds_part ----
+    const LeanTail& T = *reinterpret_cast<const LeanTail*>(lds_tail);
+    const LeanUnion& H = *reinterpret_cast<const LeanUnion*>(&lds_round[0][0]);
+    constexpr unsigned kTailWords = sizeof(LeanTail) / 8u;
+    u64 mtail = 0;
+    if (wave != 0 && wave < nmem && static_cast<unsigned>(lane) < kTailWords) mtail = reinterpret_cast<const u64*>(&members[wave].tail)[lane];
+    const unsigned i = threadIdx.x;
+    const unsigned nent = H.nentries, npc = H.npieces, ntg = H.ntargets, ninc = H.nincidences;
+    double e4[4] = {0.0, 0.0, 0.0, 0.0};
+    if (i < nent) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e4[c] = __hip_atomic_load(a.partials + static_cast<size_t>(i) * 4u + c, AQE_RLX);
+    }
+    unsigned pb = 0, pe = 0, tb = 0, te = 0, inc0 = 0, inc1 = 0;
+    if (i < npc) { pb = H.piece_entry[i]; pe = H.piece_entry[i + 1u]; }
+    if (i < ntg) { tb = H.target_begin[i]; te = H.target_begin[i + 1u]; }
+    if (i < ninc) inc0 = H.target_entry[i];
+    if (i + kPersistThreads < ninc) inc1 = H.target_entry[i + kPersistThreads];
+    // lds_part as one flat list: [0, 4 kUnionMaxEntries) the entries, then the incidences; later [0, 2048) the judging
+    // waves' words (lean_query), [2048, 4096) the rows of round totals
+    double* const F = &lds_part[0][0][0];
+    unsigned* const Finc = reinterpret_cast<unsigned*>(F + 4 * kUnionMaxEntries);
+    double* const rows = F + 2048;
+    static_assert(4 * kUnionMaxEntries * sizeof(double) + kUnionMaxIncidences * sizeof(unsigned) <= sizeof(lds_part), "the fold's staging fits lds_part");
+    static_assert(kUnionMaxIncidences <= 2 * kPersistThreads && kUnionMaxEntries <= kPersistThreads && kUnionMaxPieces <= kPersistThreads, "one batch of loads");
+    static_assert(2048 + 8 * kUnionMaxRows <= kMaxPersistRounds * kPersistWaves * kVec && kPersistWaves * 128 <= 2048, "rows beside the judging waves' words");
+    static_assert(2 * kUnionMaxRows <= kPersistThreads, "a thread per target");
+    if (i < nent) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) F[4u * i + c] = e4[c];
+    }
+    if (i < ninc) Finc[i] = inc0;
+    if (i + kPersistThreads < ninc) Finc[i + kPersistThreads] = inc1;
+    __syncthreads();
+    // (both sums below read kFoldBatch LDS entries at a time before adding them in order: one LDS round trip per batch)
+    constexpr unsigned kFoldBatch = 4;
+    if (i < npc) {  // a piece's partials, in workgroup order, into its first entry
+        double s4[4] = {0.0, 0.0, 0.0, 0.0};
+        for (unsigned e0 = pb; e0 < pe; e0 += kFoldBatch) {
+            double x[kFoldBatch][4];
+#pragma unroll
+            for (unsigned u = 0; u < kFoldBatch; ++u) {
+                const unsigned e = e0 + u < pe ? e0 + u : pb;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) x[u][c] = F[4u * e + c];
+            }
+#pragma unroll
+            for (unsigned u = 0; u < kFoldBatch; ++u) {
+                if (e0 + u < pe) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) s4[c] += x[u][c];
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) F[4u * pb + c] = s4[c];
+    }
+    __syncthreads();
+    double r4[4] = {0.0, 0.0, 0.0, 0.0};
+    if (i < ntg) {  // a target's pieces, ascending
+        for (unsigned k0 = tb; k0 < te; k0 += kFoldBatch) {
+            unsigned e[kFoldBatch];
+#pragma unroll
+            for (unsigned u = 0; u < kFoldBatch; ++u) e[u] = Finc[k0 + u < te ? k0 + u : tb];
+            double x[kFoldBatch][4];
+#pragma unroll
+            for (unsigned u = 0; u < kFoldBatch; ++u) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) x[u][c] = F[4u * e[u] + c];
+            }
+#pragma unroll
+            for (unsigned u = 0; u < kFoldBatch; ++u) {
+                if (k0 + u < te) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) r4[c] += x[u][c];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (i < ntg) {  // target 2 L + g: group g of row L — (n, S, Q) at 3 g, its rows visited at 6 + g
+        const unsigned g = i & 1u;
+        double* const r = rows + static_cast<size_t>(i >> 1) * 8u;
+        r[3u * g] = r4[0]; r[3u * g + 1u] = r4[1]; r[3u * g + 2u] = r4[2];
+        r[6u + g] = r4[3];
+    }
+    __syncthreads();
+    if (wave >= nmem) return;
+    // the judges: wave m judges members m, m + 16, ... of every class of the group, each on its own class's rows
+    u64* const lds_mine = reinterpret_cast<u64*>(F) + wave * 128u;
+    unsigned long long* const lds_res = lds_mine + 64;
+    if (wave != 0) { lds_mine[lane] = mtail; wave_lds_handoff(); }
+    for (unsigned mi = wave;;) {
+        const LeanTail& Tm = mi == 0 ? T : *reinterpret_cast<const LeanTail*>(lds_mine);
+        const unsigned rounds = Tm.rounds;
+        const bool mine = static_cast<unsigned>(lane) < rounds;
+        const double* const r = rows + static_cast<size_t>(Tm.union_row + (mine ? static_cast<unsigned>(lane) : 0u)) * 8u;
+        double tot[7];
+#pragma unroll
+        for (int cc = 0; cc < 6; ++cc) tot[cc] = mine ? r[cc] : 0.0;
+        tot[6] = mine ? r[6] + r[7] : 0.0;
+#pragma unroll
+        for (int cc = 0; cc < 7; ++cc) {  // lane q: the moments through round q (lean_query's scan, one row per round)
+            double p = tot[cc];
+            p += dpp_f64<0x111>(p);
+            p += dpp_f64<0x112>(p);
+            p += dpp_f64<0x114>(p);
+            p += dpp_f64<0x118>(p);
+            const double carry = read_lane_f64(p, 15);
+            tot[cc] = p + (lane >= 16 ? carry : 0.0);
+        }
+        lean_judge(Tm, tot, static_cast<unsigned>(lane), 0ull, epoch, lds_res);
+        wave_lds_handoff();
+        lean_send_result(Tm, lds_res, static_cast<unsigned>(lane));
+        mi += kPersistWaves;
+        if (mi >= nmem) break;
+        const u64 w = static_cast<unsigned>(lane) < kTailWords ? reinterpret_cast<const u64*>(&members[mi].tail)[lane] : 0ull;
+        wave_lds_handoff();
+        lds_mine[lane] = w;
+        wave_lds_handoff();
+    }
+}
+
 // One query on the workgroups bid = 0 .. G-1 (a launch of its own, or one group of a batch's launch).  `a`: the fields
 // the sweep needs, in registers; K: the descriptor (the kernel arguments of a single launch, the batch's table in device
 // memory otherwise) — read twice: a lane's two runs, and the tail.  A batch's sweep class (plans.hip, build_multi):
@@ -260,7 +547,8 @@ __device__ __forceinline__ void lean_send_result(const LeanTail& T, const unsign
 // m + 16, ...) on the same round totals.  A launch of its own: nmem = 1.
 template <bool kNT, bool kWide>
 __device__ __forceinline__ void lean_query(const LeanLaunch& a, const LeanRuns* const runs, const LeanKarg K, const LeanLaunch* const members, const unsigned nmem,
-                                           const unsigned bid, const unsigned G, const unsigned long long epoch) {
+                                           const unsigned bid, const unsigned G, const unsigned long long epoch,
+                                           const LeanUnion* const uni = nullptr) {
     // a wave's sums of a round (zero where it swept none); in the folding workgroup, later, the launch's whole partial list
     __shared__ double lds_part[kMaxPersistRounds][kPersistWaves][kVec];
     static_assert(kMaxPersistRounds * kPersistWaves >= kLeanMaxSlots, "the partial list fits where the workgroup's own sums were");
@@ -269,6 +557,10 @@ __device__ __forceinline__ void lean_query(const LeanLaunch& a, const LeanRuns* 
     __shared__ unsigned lds_mask[kPersistWaves];  // rounds a wave swept tiles of
     __shared__ u64 lds_tail[64];
     __shared__ int s_last;
+    if (uni) {  // a union group of a batch: the same LDS, another sweep and fold
+        lean_union<kNT>(a, uni, K, members, nmem, bid, G, epoch, lds_part, lds_round, lds_mask, lds_tail, s_last);
+        return;
+    }
     const int lane = threadIdx.x & 63;
     const unsigned wave = threadIdx.x >> 6;
     LEAN_STAMP(0);
@@ -407,24 +699,7 @@ __device__ __forceinline__ void lean_query(const LeanLaunch& a, const LeanRuns* 
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the partials are out before the ticket is drawn
         LEAN_STAMP(5);
-        if (lane == 0) {
-            int last = 0;
-            unsigned* const ct = a.counter + static_cast<size_t>(kShards) * kShardStride;
-            // at most 256 arrivals: 16 shards of 16 (a same-address atomic serialises at ~16 ns), then the top counter
-            constexpr unsigned kLeanShards = 16;
-            if (G <= kLeanShards) {
-                if (__hip_atomic_fetch_add(ct, 1u, AQE_RLX) == G - 1u) { __hip_atomic_store(ct, 0u, AQE_RLX); last = 1; }
-            } else {
-                const unsigned sh = bid % kLeanShards;
-                const unsigned members = (G - sh + kLeanShards - 1u) / kLeanShards;
-                unsigned* const cs = a.counter + static_cast<size_t>(sh) * kShardStride;
-                if (__hip_atomic_fetch_add(cs, 1u, AQE_RLX) == members - 1u) {
-                    __hip_atomic_store(cs, 0u, AQE_RLX);
-                    if (__hip_atomic_fetch_add(ct, 1u, AQE_RLX) == kLeanShards - 1u) { __hip_atomic_store(ct, 0u, AQE_RLX); last = 1; }
-                }
-            }
-            s_last = last;
-        }
+        if (lane == 0) s_last = lean_ticket(a.counter, bid, G);
         LEAN_STAMP(6);
     }
     __syncthreads();
@@ -562,8 +837,9 @@ __global__ __launch_bounds__(kPersistThreads) void k_sweep_lean(LeanLaunch a) {
 // A BATCH of queries in one launch (as k_sweep_multi, persist.hip): the grid is cut into one group of workgroups per
 // sweep class, wg_map[blockIdx.x] = members << 48 | first member << 32 | group size << 16 | index in the group; group q
 // runs table[q] exactly as a launch of its own would on that many workgroups, and judges table[q .. q + members) on its
-// totals.  Nothing here waits for anything — the last workgroup of a group to arrive finishes its queries — so groups
-// may be dispatched in any order and there may be more of them than compute units.
+// totals.  A group whose first descriptor names a union (`uni`) sweeps the union of several classes' runs instead and
+// judges every member of them (lean_union).  Nothing here waits for anything — the last workgroup of a group to arrive
+// finishes its queries — so groups may be dispatched in any order and there may be more of them than compute units.
 template <bool kNT>
 __global__ __launch_bounds__(kPersistThreads) void k_sweep_lean_multi(const LeanLaunch* table, const unsigned long long* wg_map, unsigned long long epoch) {
     const u64 me = uniform64(wg_map[blockIdx.x]);
@@ -573,7 +849,8 @@ __global__ __launch_bounds__(kPersistThreads) void k_sweep_lean_multi(const Lean
     a.amount = K->amount; a.ntiles = K->ntiles; a.tiles_per_wg = K->tiles_per_wg;
     a.has_where = K->has_where; a.wmin = K->wmin; a.wmax = K->wmax; a.shift = K->shift;
     a.partials = K->partials; a.counter = K->counter; a.tail.want_ticks = 0; a.wide = nullptr; a.nruns = 0;
-    lean_query<kNT, false>(a, &(table + q)->runs, K, table + q, nmem, static_cast<unsigned>(me) & 0xffffu, static_cast<unsigned>(me >> 16) & 0xffffu, epoch);
+    lean_query<kNT, false>(a, &(table + q)->runs, K, table + q, nmem, static_cast<unsigned>(me) & 0xffffu, static_cast<unsigned>(me >> 16) & 0xffffu, epoch,
+                           K->uni);
 }
 
 }  // namespace

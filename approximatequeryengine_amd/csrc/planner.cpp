@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <regex>
 
 namespace aqe {
@@ -658,6 +659,79 @@ bool parse_where(const char* query, double* lo, double* hi) {
     *lo = -1;
     *hi = -1;
     return false;
+}
+
+bool build_union_cover(const std::vector<UnionRun>& runs, uint32_t ntargets, UnionCover& out) {
+    out = UnionCover{};
+    struct Ev { uint64_t pos; int delta; uint32_t target; };
+    std::vector<Ev> ev;
+    for (const UnionRun& r : runs) {
+        if (r.len == 0) continue;
+        if (r.target >= ntargets) return false;
+        ev.push_back({r.lo, +1, r.target});
+        ev.push_back({r.lo + r.len, -1, r.target});
+    }
+    std::sort(ev.begin(), ev.end(), [](const Ev& a, const Ev& b) { return a.pos < b.pos; });
+    std::map<uint32_t, uint32_t> active;  // target -> runs covering the current slot
+    std::vector<std::vector<uint32_t>> cov;  // piece -> its targets, ascending, with multiplicity
+    for (size_t i = 0; i < ev.size();) {
+        const uint64_t pos = ev[i].pos;
+        for (; i < ev.size() && ev[i].pos == pos; ++i) {
+            if (ev[i].delta > 0) ++active[ev[i].target];
+            else if (--active[ev[i].target] == 0) active.erase(ev[i].target);
+        }
+        if (active.empty() || i == ev.size()) continue;
+        const uint64_t next = ev[i].pos;
+        std::vector<uint32_t> key;
+        for (const auto& kv : active) key.insert(key.end(), kv.second, kv.first);
+        if (!out.piece_hi.empty() && out.piece_hi.back() == pos && cov.back() == key) {
+            out.piece_hi.back() = next;  // the same targets go on: one piece
+        } else {
+            out.piece_lo.push_back(pos);
+            out.piece_hi.push_back(next);
+            cov.push_back(std::move(key));
+        }
+    }
+    std::vector<std::vector<uint32_t>> per(ntargets);
+    for (size_t p = 0; p < cov.size(); ++p) {
+        const uint64_t len = out.piece_hi[p] - out.piece_lo[p];
+        out.slots += len;
+        out.incidence_slots += len * cov[p].size();
+        for (uint32_t t : cov[p]) per[t].push_back(static_cast<uint32_t>(p));
+    }
+    out.target_begin.assign(1, 0);
+    for (uint32_t t = 0; t < ntargets; ++t) {
+        out.target_piece.insert(out.target_piece.end(), per[t].begin(), per[t].end());
+        out.target_begin.push_back(static_cast<uint32_t>(out.target_piece.size()));
+    }
+    return true;
+}
+
+void union_tiles(const UnionCover& cv, std::vector<UnionTile>& out) {
+    out.clear();
+    const size_t np = cv.piece_lo.size();
+    for (size_t p = 0; p < np;) {
+        size_t q = p;  // the span: pieces p .. q
+        while (q + 1 < np && cv.piece_lo[q + 1] == cv.piece_hi[q]) ++q;
+        const uint64_t hi = cv.piece_hi[q];
+        size_t first = p;
+        for (uint64_t start = cv.piece_lo[p]; start < hi;) {  // the tile owns the slots [start, end)
+            const uint64_t row = start & ~1ull;
+            uint64_t end = std::min<uint64_t>(row + kUnionTileSlots, hi);
+            while (cv.piece_hi[first] <= start) ++first;
+            if (first + 1 <= q && end > cv.piece_hi[first + 1]) end = cv.piece_hi[first + 1];  // at most two pieces
+            UnionTile t;
+            t.row = row;
+            t.piece = static_cast<uint32_t>(first);
+            t.last_piece = static_cast<uint32_t>(end > cv.piece_hi[first] ? first + 1 : first);
+            t.vlo = static_cast<uint32_t>(start - row);
+            t.vhi = static_cast<uint32_t>(end - row);
+            t.whole = t.vlo == 0 && t.vhi == kUnionTileSlots && t.last_piece == first;
+            out.push_back(t);
+            start = end;
+        }
+        p = q + 1;
+    }
 }
 
 double confidence_heuristic(double pct, uint64_t total) {

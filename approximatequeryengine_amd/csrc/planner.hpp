@@ -93,6 +93,37 @@ inline uint64_t family_row(const aqe_family& f, uint64_t o) {
     return f.row0 + (o / f.seg_len) * f.pitch + (o % f.seg_len) * f.step;
 }
 
+// ---- union cover of a batch's runs (plans.hip, build_union; lean.hip, lean_union) ----
+// A RUN here is `len` consecutive slots of one column view from `lo` on, credited to one TARGET (a (class, round, group)
+// slot of the fold).  The cover cuts the union of the runs into PIECES: maximal slot ranges over which the multiset of
+// covering targets does not change.  Each piece is loaded once; its moments are credited to every target that covers it
+// (twice to a target that covers it twice, as two runs of it would have loaded it twice).
+struct UnionRun {
+    uint64_t lo, len;
+    uint32_t target;
+};
+struct UnionCover {
+    std::vector<uint64_t> piece_lo, piece_hi;  // ascending, disjoint
+    std::vector<uint32_t> target_begin;        // [targets + 1]: target t adds the pieces target_piece[target_begin[t] ..
+    std::vector<uint32_t> target_piece;        //   target_begin[t + 1]), ascending (the fold's summation order)
+    uint64_t slots = 0;                        // slots of the union
+    uint64_t incidence_slots = 0;              // sum over pieces of slots x covering targets: what the runs load
+};
+// Tiles of up to 1024 slots over the union: every covered span (a maximal run of adjacent pieces) is tiled from its
+// first slot on, each tile starting at an even slot (every 16-byte load aligned), the gaps between spans skipped.  A tile
+// owns the slots [row + vlo, row + vhi) (vlo is 0 or 1: an odd start; nothing past vhi is read) and holds slots of at
+// most two pieces, `piece` and `last_piece` = piece or piece + 1 (a tile that would reach a third ends where it starts).
+// `whole`: 1024 slots of one piece (no masks).
+struct UnionTile {
+    uint64_t row;
+    uint32_t piece, last_piece, vlo, vhi;
+    bool whole;
+};
+constexpr uint32_t kUnionTileSlots = 1024;
+// runs with len == 0 are ignored; targets must be < ntargets.  Returns false on a bad target.
+bool build_union_cover(const std::vector<UnionRun>& runs, uint32_t ntargets, UnionCover& out);
+void union_tiles(const UnionCover& cv, std::vector<UnionTile>& out);
+
 bool parse_where(const char* query, double* lo, double* hi);   // SCH.cpp:277-294
 double confidence_heuristic(double pct, uint64_t total);        // SCH.cpp:296-305
 double error_to_sample_percent(double e);                       // CLI:243-250

@@ -1118,7 +1118,9 @@ struct BatchMulti {
     unsigned grid = 0;
     uint64_t samples = 0;                  // rows one launch sweeps (all plans)
     uint32_t classes = 0;                  // lean: sweep classes (groups of the launch); else one per plan
-    uint64_t rows_loaded = 0;              // rows the launch actually loads (each class's rows once)
+    uint64_t rows_loaded = 0;              // rows the classes sweep (each class's rows once)
+    std::vector<void*> unions;             // lean: the union groups' device blocks (build_union)
+    uint64_t union_rows = 0;               // rows the launch loads (a union group's slots once, every other class's rows)
     bool nt = false;                       // the launch's loads go past the caches (build_multi)
     const double* totals = nullptr;        // kind 1: the buffer the descriptors were written for
     uint64_t stride = 0;
@@ -1148,6 +1150,8 @@ void free_multi(BatchMulti& m) {
     if (m.d_table) (void)hipFree(m.d_table);
     if (m.d_ltable) (void)hipFree(m.d_ltable);
     if (m.d_wgmap) (void)hipFree(m.d_wgmap);
+    for (void* u : m.unions) (void)hipFree(u);
+    m.unions.clear();
     m.d_ltable = nullptr;
     m.lean = false;
     m.d_table = nullptr;
@@ -1241,6 +1245,179 @@ int sweep_classes(aqe_batch* b, int kind, const std::vector<char>& head, const s
     return AQE_OK;
 }
 
+// A union group's device block (lean.hip, lean_union; kernels.hpp, LeanUnion): built once per batch.  `forms`: the first
+// form of each sweep class of the group (full forms of plain runs, one view, one shift and WHERE); `G`: the group's
+// workgroups.  Classes whose runs are the same (AQE_BATCH_SHARE=0 leaves one class per plan) share their rows of round
+// totals: `class_row` gets each class's first row.  Leaves `d_block` null (and returns AQE_OK) when the group exceeds a
+// bound of the kernel's fold — it then does not form, and its classes run as they are.
+struct UnionBuilt {
+    void* d_block = nullptr;
+    uint32_t ntiles = 0, tiles_per_wg = 0;
+    double* d_partials = nullptr;
+    uint64_t slots = 0;
+    std::vector<uint32_t> class_row;
+};
+
+int build_union(aqe_ctx* c, const std::vector<const SweepForm*>& forms, uint32_t G, UnionBuilt& out) {
+    out = UnionBuilt{};
+    std::vector<UnionRun> runs;
+    std::map<std::vector<uint64_t>, uint32_t> seen;  // a class's runs -> its first row
+    uint32_t nrows = 0;
+    for (const SweepForm* F : forms) {
+        std::vector<uint64_t> sig;
+        for (uint32_t i = 0; i < F->nruns; ++i) { sig.push_back(F->h_runs.row0[i]); sig.push_back(F->h_runs.rows[i]); sig.push_back(F->h_runs.meta[i]); }
+        sig.push_back(F->slots);
+        const auto it = seen.find(sig);
+        if (it != seen.end()) { out.class_row.push_back(it->second); continue; }
+        seen.emplace(sig, nrows);
+        out.class_row.push_back(nrows);
+        for (uint32_t i = 0; i < F->nruns; ++i) {
+            const uint32_t meta = F->h_runs.meta[i];
+            runs.push_back(UnionRun{F->h_runs.row0[i], F->h_runs.rows[i], 2u * (nrows + (meta & 0xffu)) + ((meta & kLeanMetaGroupB) ? 1u : 0u)});
+        }
+        nrows += F->slots;
+    }
+    if (nrows > static_cast<uint32_t>(kUnionMaxRows)) return AQE_OK;
+    UnionCover cv;
+    if (!build_union_cover(runs, 2u * nrows, cv)) return fail(c, AQE_ERR_INVALID, "internal: a union run names no row");
+    const size_t np = cv.piece_lo.size(), ninc = cv.target_piece.size();
+    if (np == 0 || np > static_cast<size_t>(kUnionMaxPieces) || ninc > static_cast<size_t>(kUnionMaxIncidences)) return AQE_OK;
+    std::vector<UnionTile> tl;
+    union_tiles(cv, tl);
+    const uint64_t T = tl.size(), K = (T + G - 1) / G;
+    if (K > static_cast<uint64_t>(kUnionMaxTilesPerWg) || T >= 0xffffffffull) return AQE_OK;
+    // every workgroup's share holds slots of the pieces pf .. pl (consecutive: the tiles of a share are); their partials
+    // go piece-major, the workgroups of a piece ascending
+    std::vector<std::vector<uint32_t>> piece_wgs(np);
+    std::vector<uint32_t> wg_first(G, 0), wg_count(G, 0);
+    for (uint32_t b = 0; b < G; ++b) {
+        const uint64_t t0 = b * K, t1 = std::min<uint64_t>(t0 + K, T);
+        if (t0 >= t1) continue;
+        const uint32_t pf = tl[t0].piece, pl = tl[t1 - 1].last_piece;
+        if (pl - pf + 1u > static_cast<uint32_t>(kUnionWgPieces)) return AQE_OK;
+        wg_first[b] = pf;
+        wg_count[b] = pl - pf + 1u;
+        for (uint32_t p = pf; p <= pl; ++p) piece_wgs[p].push_back(b);
+    }
+    std::vector<uint32_t> piece_entry(np + 1, 0);
+    for (size_t p = 0; p < np; ++p) piece_entry[p + 1] = piece_entry[p] + static_cast<uint32_t>(piece_wgs[p].size());
+    const uint32_t nent = piece_entry[np];
+    if (nent > static_cast<uint32_t>(kUnionMaxEntries)) return AQE_OK;
+    // the block: header, tile_row, tile_meta, workgroup records, piece_lo, piece_hi, piece_entry,
+    // target_begin, target_entry, then the partial list
+    auto up8 = [](size_t x) { return (x + 7) & ~static_cast<size_t>(7); };
+    const size_t o_row = sizeof(LeanUnion), o_meta = o_row + 8 * T, o_wg = o_meta + 4 * ((T + 1) & ~1ull);
+    const size_t o_plo = up8(o_wg + 4 * static_cast<size_t>(G) * (kUnionWgPieces + 1)), o_phi = o_plo + 8 * np, o_pent = o_phi + 8 * np;
+    const size_t o_tbeg = up8(o_pent + 4 * (np + 1)), o_tent = o_tbeg + 4 * static_cast<size_t>(2 * nrows + 1);
+    const size_t o_part = (o_tent + 4 * ninc + 255) & ~static_cast<size_t>(255), bytes = o_part + 4 * sizeof(double) * nent;
+    std::vector<uint8_t> img(bytes, 0);
+    auto at = [&](size_t off) { return img.data() + off; };
+    for (uint64_t t = 0; t < T; ++t) {
+        const UnionTile& u = tl[t];
+        const uint32_t meta = u.piece | (u.vhi << 16) | (u.vlo << 27) | (u.whole ? kUnionTileWhole : 0u);
+        std::memcpy(at(o_row + 8 * t), &u.row, 8);
+        std::memcpy(at(o_meta + 4 * t), &meta, 4);
+    }
+    for (uint32_t b = 0; b < G; ++b) {
+        uint32_t rec[kUnionWgPieces + 1] = {0};
+        rec[0] = wg_first[b];
+        for (uint32_t j = 0; j < wg_count[b]; ++j) {
+            const uint32_t p = wg_first[b] + j;
+            const auto& v = piece_wgs[p];
+            rec[1 + j] = piece_entry[p] + static_cast<uint32_t>(std::lower_bound(v.begin(), v.end(), b) - v.begin());
+        }
+        std::memcpy(at(o_wg + 4 * static_cast<size_t>(b) * (kUnionWgPieces + 1)), rec, sizeof(rec));
+    }
+    std::memcpy(at(o_plo), cv.piece_lo.data(), 8 * np);
+    std::memcpy(at(o_phi), cv.piece_hi.data(), 8 * np);
+    std::memcpy(at(o_pent), piece_entry.data(), 4 * (np + 1));
+    std::memcpy(at(o_tbeg), cv.target_begin.data(), 4 * cv.target_begin.size());
+    for (size_t k = 0; k < ninc; ++k) {
+        const uint32_t e = piece_entry[cv.target_piece[k]];
+        std::memcpy(at(o_tent + 4 * k), &e, 4);
+    }
+    char* d = nullptr;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&d), bytes));
+    LeanUnion h{};
+    h.piece_lo = reinterpret_cast<const uint64_t*>(d + o_plo);
+    h.piece_hi = reinterpret_cast<const uint64_t*>(d + o_phi);
+    h.piece_entry = reinterpret_cast<const uint32_t*>(d + o_pent);
+    h.target_begin = reinterpret_cast<const uint32_t*>(d + o_tbeg);
+    h.target_entry = reinterpret_cast<const uint32_t*>(d + o_tent);
+    h.npieces = static_cast<uint32_t>(np);
+    h.ntargets = 2 * nrows;
+    h.nincidences = static_cast<uint32_t>(ninc);
+    h.nentries = nent;
+    std::memcpy(img.data(), &h, sizeof(h));
+    if (hipMemcpy(d, img.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return fail(c, AQE_ERR_HIP, "hipMemcpy of a union block failed"); }
+    out.d_block = d;
+    out.ntiles = static_cast<uint32_t>(T);
+    out.tiles_per_wg = static_cast<uint32_t>(K);
+    out.d_partials = reinterpret_cast<double*>(d + o_part);
+    out.slots = cv.slots;
+    return AQE_OK;
+}
+
+// Union groups of a lean batch (kind 0): sweep classes whose first forms are full forms of plain runs (no head form, no
+// top-up slot) over one view with one shift and one WHERE are swept together when there are at least two of them (the
+// launch's load policy is one for all).  `groups` lists the launch's groups in order, each a list of class indices: a
+// union group where `blocks` holds one, a class of its own otherwise — without a union, exactly the classes in order.
+// AQE_BATCH_UNION=0: no union groups.
+int union_groups(aqe_batch* b, int kind, const std::vector<char>& head, const std::vector<uint32_t>& gs, const std::vector<SweepForm>& lf,
+                 const std::vector<std::vector<size_t>>& classes, std::vector<std::vector<size_t>>& groups, std::vector<UnionBuilt>& blocks) {
+    static const bool union_off = [] { const char* e = std::getenv("AQE_BATCH_UNION"); return e && e[0] == '0'; }();  // diagnostics: A/B in one build
+    groups.clear();
+    blocks.clear();
+    const size_t nc = classes.size();
+    std::vector<int> taken(nc, -1);  // class -> its union group
+    if (kind == 0 && !union_off) {
+        std::map<std::vector<uint64_t>, std::vector<size_t>> keyed;
+        std::vector<std::vector<uint64_t>> order;
+        for (size_t k = 0; k < nc; ++k) {
+            const size_t i = classes[k][0];
+            const SweepForm& F = lf[i];
+            bool ok = !head[i] && F.ok && !F.wide && F.topup_slot == 0 && F.more_rounds == 0 && F.slots > 0;
+            for (uint32_t r = 0; ok && r < F.nruns; ++r) ok = (F.h_runs.meta[r] & kLeanMetaSeg) == 0;
+            if (!ok) continue;
+            const SweepCommon sw = sweep_common(b->plans[i], nullptr, 0);
+            uint64_t wmin, wmax, shift;
+            std::memcpy(&wmin, &sw.wmin, 8); std::memcpy(&wmax, &sw.wmax, 8); std::memcpy(&shift, &sw.shift, 8);
+            std::vector<uint64_t> key = {reinterpret_cast<uintptr_t>(sw.amount), shift, static_cast<uint64_t>(sw.has_where), sw.has_where ? wmin : 0, sw.has_where ? wmax : 0};
+            if (!keyed.count(key)) order.push_back(key);
+            keyed[key].push_back(k);
+        }
+        for (const auto& key : order) {
+            const std::vector<size_t>& ks = keyed[key];
+            if (ks.size() < 2) continue;
+            std::vector<const SweepForm*> forms;
+            uint64_t g = 0;
+            for (size_t k : ks) {
+                forms.push_back(&lf[classes[k][0]]);
+                for (size_t i : classes[k]) g += gs[i];
+            }
+            UnionBuilt u;
+            int rc = build_union(b->ctx, forms, static_cast<uint32_t>(std::min<uint64_t>(g, kMaxPersistGrid)), u);
+            if (rc != AQE_OK) { for (UnionBuilt& x : blocks) (void)hipFree(x.d_block); blocks.clear(); return rc; }
+            if (!u.d_block) continue;
+            for (size_t k : ks) taken[k] = static_cast<int>(blocks.size());
+            blocks.push_back(std::move(u));
+        }
+    }
+    std::vector<int> placed(blocks.size(), 0);
+    std::vector<UnionBuilt> ordered;  // blocks in the order their groups take in the launch
+    for (size_t k = 0; k < nc; ++k) {
+        if (taken[k] < 0) { groups.push_back({k}); ordered.emplace_back(); continue; }
+        if (placed[taken[k]]) continue;
+        placed[taken[k]] = 1;
+        std::vector<size_t> g;
+        for (size_t j = k; j < nc; ++j) if (taken[j] == taken[k]) g.push_back(j);
+        groups.push_back(std::move(g));
+        ordered.push_back(std::move(blocks[taken[k]]));
+    }
+    blocks = std::move(ordered);  // blocks[g]: group g's union (d_block null: a class of its own)
+    return AQE_OK;
+}
+
 // Builds the one-launch form of a batch: group sizes in proportion to the plans' tiles (powers of two, the context's
 // persistent grid as the budget), one sweep form per plan for its group's size, the descriptor table, the workgroup map.
 int build_multi(aqe_batch* b, int kind, double* dev_totals, uint64_t row_stride) {
@@ -1299,11 +1476,14 @@ int build_multi(aqe_batch* b, int kind, double* dev_totals, uint64_t row_stride)
     std::vector<PersistLaunch> table(n);
     std::vector<LeanLaunch> ltable;
     std::vector<std::vector<size_t>> classes;  // lean: the sweep classes, plans in batch order
+    std::vector<std::vector<size_t>> groups;   // lean: the launch's groups, classes in order (union_groups)
+    std::vector<UnionBuilt> ublocks;           // ... and group g's union, if it is one
     std::vector<unsigned long long> wgmap, monitors;
     const char* layout_env = std::getenv("AQE_MULTI_LAYOUT");
     const bool packed_layout = layout_env && std::strcmp(layout_env, "packed") == 0;
     m.samples = 0;
     m.rows_loaded = 0;
+    m.union_rows = 0;
     m.classes = static_cast<uint32_t>(n);
     {   // Lean groups (lean.hip, k_sweep_lean_multi) when every plan of the batch qualifies: no monitor waves, the last
         // workgroup of a group to arrive finishes its query.  (AQE_MULTI_LEAN=0: the groups of k_sweep_multi.)
@@ -1321,17 +1501,36 @@ int build_multi(aqe_batch* b, int kind, double* dev_totals, uint64_t row_stride)
             int rc = sweep_classes(b, kind, head, gs, lf, classes);
             if (rc != AQE_OK) { for (SweepForm& f : lf) if (f.d_ppart) (void)hipFree(f.d_ppart); return rc; }
             if (n > 0xffffu) { for (SweepForm& f : lf) if (f.d_ppart) (void)hipFree(f.d_ppart); return fail(c, AQE_ERR_UNSUPPORTED, "more than 65535 plans in one batch"); }
+            rc = union_groups(b, kind, head, gs, lf, classes, groups, ublocks);
+            if (rc != AQE_OK) { for (SweepForm& f : lf) if (f.d_ppart) (void)hipFree(f.d_ppart); return rc; }
             m.lean = true;
-            // the descriptor table in class order (a class's members consecutive, its first one's descriptor sweeps)
-            for (const std::vector<size_t>& cl : classes) {
-                for (size_t i : cl) {
-                    ltable.emplace_back();
-                    fill_lean(b->plans[i], lf[i], kind == 1, kind == 1 ? dev_totals + i * row_stride : nullptr, 0, ltable.back());
-                    ltable.back().tail.want_ticks = 0;
-                    ltable.back().tail.keep_state = 0;  // (a batch never enqueues a top-up launch up front: fetch() runs the due ones)
-                    m.samples += lf[i].samples;
+            // the descriptor table in group order, a group's classes in order, a class's members consecutive: a class's first
+            // descriptor sweeps for it, a union group's first descriptor for the union (its tiles, share and partial list)
+            for (size_t gi = 0; gi < groups.size(); ++gi) {
+                const UnionBuilt& u = ublocks[gi];
+                const size_t first = ltable.size();
+                for (size_t ci = 0; ci < groups[gi].size(); ++ci) {
+                    const std::vector<size_t>& cl = classes[groups[gi][ci]];
+                    for (size_t i : cl) {
+                        ltable.emplace_back();
+                        fill_lean(b->plans[i], lf[i], kind == 1, kind == 1 ? dev_totals + i * row_stride : nullptr, 0, ltable.back());
+                        ltable.back().tail.want_ticks = 0;
+                        ltable.back().tail.keep_state = 0;  // (a batch never enqueues a top-up launch up front: fetch() runs the due ones)
+                        if (u.d_block) ltable.back().tail.union_row = u.class_row[ci];
+                        m.samples += lf[i].samples;
+                    }
+                    m.rows_loaded += lf[cl[0]].samples;
+                    if (!u.d_block) m.union_rows += lf[cl[0]].samples;
                 }
-                m.rows_loaded += lf[cl[0]].samples;
+                if (u.d_block) {
+                    LeanLaunch& f = ltable[first];
+                    f.uni = static_cast<const LeanUnion*>(u.d_block);
+                    f.ntiles = u.ntiles;
+                    f.tiles_per_wg = u.tiles_per_wg;
+                    f.partials = u.d_partials;
+                    m.unions.push_back(u.d_block);
+                    m.union_rows += u.slots;
+                }
             }
             m.classes = static_cast<uint32_t>(classes.size());
             m.forms = std::move(lf);
@@ -1380,15 +1579,20 @@ int build_multi(aqe_batch* b, int kind, double* dev_totals, uint64_t row_stride)
     // Lean: one group per sweep class (its size the sum of its members' — not always a power of two: groups whose size is
     // a multiple of 8 first), tagged with its first member's place in the descriptor table and its member count.
     std::vector<unsigned long long> tags;
+    // A union group: the sum of its classes' workgroups, at most kMaxPersistGrid, and all their members.
     if (m.lean) {
         std::vector<unsigned long long> later;
         unsigned long long first = 0;
-        for (const std::vector<size_t>& cl : classes) {
-            unsigned long long g = 0;
-            for (size_t i : cl) g += gs[i];
-            const unsigned long long tag = (static_cast<unsigned long long>(cl.size()) << 48) | (first << 32) | (g << 16);
+        for (size_t gi = 0; gi < groups.size(); ++gi) {
+            unsigned long long g = 0, nmem = 0;
+            for (size_t k : groups[gi]) {
+                for (size_t i : classes[k]) g += gs[i];
+                nmem += classes[k].size();
+            }
+            if (ublocks[gi].d_block) g = std::min<unsigned long long>(g, kMaxPersistGrid);
+            const unsigned long long tag = (nmem << 48) | (first << 32) | (g << 16);
             (g % 8 == 0 ? tags : later).push_back(tag);
-            first += cl.size();
+            first += nmem;
         }
         tags.insert(tags.end(), later.begin(), later.end());
     } else {
@@ -1700,6 +1904,15 @@ int aqe_batch_share_info(aqe_batch* b, uint32_t* classes, uint64_t* rows_loaded)
     const BatchMulti& m = b->multi[b->last_kind];
     if (classes) *classes = m.classes;
     if (rows_loaded) *rows_loaded = m.rows_loaded;
+    return AQE_OK;
+}
+
+int aqe_batch_union_info(aqe_batch* b, uint32_t* groups, uint64_t* rows_loaded) {
+    if (!b) return AQE_ERR_INVALID;
+    if (b->last_kind < 0) return fail(b->ctx, AQE_ERR_INVALID, "no one-launch execution yet");
+    const BatchMulti& m = b->multi[b->last_kind];
+    if (groups) *groups = static_cast<uint32_t>(m.unions.size());
+    if (rows_loaded) *rows_loaded = m.lean ? m.union_rows : m.rows_loaded;
     return AQE_OK;
 }
 

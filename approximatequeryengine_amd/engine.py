@@ -168,11 +168,18 @@ class Batch:
         return (ms.value if timed else None), n.value, g.value
 
     def share_info(self):
-        """(sweep classes, rows loaded) of the most recent one-launch execution: plans that sweep the same rows the same
+        """(sweep classes, rows the classes sweep) of the most recent one-launch execution: plans that sweep the same rows the same
         way are swept once and judged each (aqe_batch_share_info)."""
         k, r = C.c_uint32(), C.c_uint64()
         nat.check(nat.lib().aqe_batch_share_info(self._h, C.byref(k), C.byref(r)), self.engine._h)
         return k.value, r.value
+
+    def union_info(self):
+        """(union groups, rows loaded) of the most recent one-launch execution: sweep classes that read the same view the
+        same way are swept as one union, each slot loaded once (aqe_batch_union_info)."""
+        g, r = C.c_uint32(), C.c_uint64()
+        nat.check(nat.lib().aqe_batch_union_info(self._h, C.byref(g), C.byref(r)), self.engine._h)
+        return g.value, r.value
 
 
 class Comm:

@@ -302,6 +302,16 @@ AQE_API void aqe_query_defaults(aqe_query* q); /* reference defaults of BIND:56-
 AQE_API int aqe_plan_families(const aqe_query* q, uint64_t n_global, uint64_t shard_lo, uint64_t shard_hi,
                               uint32_t round, aqe_family* fams, uint32_t cap, uint32_t* n_out,
                               uint32_t* rounds_out, uint64_t* samples_out);
+/* The cover a lean batch's union group sweeps (plans.hip, build_union), for tests: runs of `run_len[i]` consecutive
+ * slots of one view from `run_lo[i]` on, each credited to target run_target[i] < n_targets.  Pieces: maximal slot
+ * ranges over which the multiset of covering targets is constant, ascending and disjoint.  target_begin
+ * [n_targets + 1] / target_piece: the pieces each target adds, ascending (with multiplicity).  *n_slots: slots of the
+ * union; *n_tiles: its 1024-slot tiles (spans tiled from an even slot, gaps skipped).  Any output may be NULL (call
+ * once with NULL buffers to size them). */
+AQE_API int aqe_union_cover(const uint64_t* run_lo, const uint64_t* run_len, const uint32_t* run_target, uint32_t n_runs, uint32_t n_targets,
+                            uint64_t* piece_lo, uint64_t* piece_hi, uint32_t cap_pieces, uint32_t* n_pieces,
+                            uint32_t* target_begin, uint32_t* target_piece, uint32_t cap_incidences, uint32_t* n_incidences,
+                            uint64_t* n_slots, uint64_t* n_tiles);
 /* adaptive_block_sample is data dependent: its families follow from the ten zone variances (population
  * variance of the amounts of rows [z*N/10, (z+1)*N/10)), which aqe_reduce obtains with a device pre-pass.
  * This host-side entry plans it from given variances (tests, external planners). */
@@ -506,10 +516,16 @@ AQE_API int aqe_batch_set_profiling(aqe_batch* batch, int enable);
 AQE_API int aqe_batch_launch_info(aqe_batch* batch, float* ms, uint64_t* samples, uint32_t* workgroups);
 /* How the most recent one-launch execution shared its sweeps: plans whose sweeps load the same rows the same way (the
  * same sampler, WHERE bounds and rounds; they may differ in aggregate and error target) form one sweep class, swept
- * once and judged per plan.  `classes`: groups of the launch; `rows_loaded`: rows it loads (each class's once) — beside
+ * once and judged per plan.  `classes`: sweep classes; `rows_loaded`: rows the classes sweep (each class's once) — beside
  * aqe_batch_launch_info's `samples`, the rows its queries aggregate.  AQE_BATCH_SHARE=0 in the environment: one class
  * per plan.  The totals form (aqe_batch_enqueue_sweeps) does not share.  Either output may be NULL. */
 AQE_API int aqe_batch_share_info(aqe_batch* batch, uint32_t* classes, uint64_t* rows_loaded);
+/* What the most recent one-launch execution actually loaded.  Sweep classes of one lean batch that read the same view
+ * with the same shift and WHERE bounds (full forms, decisions in the kernel) form a UNION GROUP: one group of workgroups
+ * loads every slot of the union of their runs once and credits it to every class, round and pointer group that covers
+ * it.  `groups`: union groups of the launch; `rows_loaded`: rows the launch loads (the union groups' slots once, every
+ * other class's rows once).  AQE_BATCH_UNION=0 in the environment: no union groups.  Either output may be NULL. */
+AQE_API int aqe_batch_union_info(aqe_batch* batch, uint32_t* groups, uint64_t* rows_loaded);
 /* ---- the collective behind the C ABI: RCCL over xGMI ---------------------------------------------
  * One all-reduce SUM of the moment vectors replaces the reference's in-process merges (mutex-guarded vector, CAS on
  * atomic<double>, DB.cpp:948-951, 966-967, 2031-2036).  librccl is opened on first use (no link-time dependency; a
