@@ -35,15 +35,20 @@ def is_stale() -> bool:
     return any(p.stat().st_mtime > t for p in SOURCES + HEADERS + [Path(__file__)])
 
 
+def compile_command(out, extra=()) -> list:
+    """The hipcc command line that builds the library into `out`, with `extra` flags (variant builds: tools/ab_libs.sh)."""
+    return [hipcc(), "-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-shared", "-fvisibility=hidden",
+            "-Wall", "-Wno-unused-function", "-fno-fast-math", "-ffp-contract=off", "-pthread", "-ldl",
+            *extra, "-I", str(ROOT / "include"), "-o", str(out)] + [str(s) for s in SOURCES]
+
+
 def build_native(force: bool = False, verbose: bool = False) -> Path:
     """Compile the HIP extension if missing or older than its sources; returns the .so path."""
     if not force and not is_stale():
         return LIB
     LIB.parent.mkdir(parents=True, exist_ok=True)
     tmp = LIB.with_suffix(".so.tmp%d" % os.getpid())
-    cmd = [hipcc(), "-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-shared", "-fvisibility=hidden",
-           "-Wall", "-Wno-unused-function", "-fno-fast-math", "-ffp-contract=off", "-pthread", "-ldl",
-           "-I", str(ROOT / "include"), "-o", str(tmp)] + [str(s) for s in SOURCES]
+    cmd = compile_command(tmp)
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)

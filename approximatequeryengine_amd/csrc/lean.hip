@@ -43,16 +43,22 @@ namespace {
 
 typedef const AQE_KARG LeanLaunch* LeanKarg;
 
-// Diagnostics (builds with -DAQE_LEAN_STAMPS only; tools/stamp_lean.py): s_memrealtime marks, 100 MHz.
-// [wave][8]: 0 entry, 1 table in registers, 2 first tile folded, 3 sweep done, 4 sums handed to the workgroup, 5 partial out
-// (wave 0), 6 ticket drawn (wave 0);  then [8] of the folding workgroup: 1 rounds summed, 2 judged
+// Diagnostics (builds with -DAQE_LEAN_STAMPS only; tools/stamp_lean.py, tools/stamp_union.py): s_memrealtime marks, 100 MHz.
+// [wave][8] of the first kMaxPersistGrid workgroups: 0 entry, 1 table in registers, 2 first tile folded, 3 sweep done, 4 sums
+// handed to the workgroup, 5 partial out (wave 0), 6 ticket drawn (wave 0);  then [8] of the folding workgroup: 1 rounds
+// summed, 2 judged.  A union group (lean_union) marks 0 entry, 1 tile list in registers, 2 first tile folded, 3 sweep done,
+// 5 partials out, 6 ticket drawn; its fold 3 partial list staged, 4 pieces summed, 5 targets summed, and then per judging
+// wave [wave][8]: 0 first judge done, 1 last result sent.
 #ifdef AQE_LEAN_STAMPS
-__device__ unsigned long long g_lean_stamps[(kMaxPersistGrid * kPersistWaves + 1) * 8];
-#define LEAN_STAMP(slot) do { if (lane == 0) g_lean_stamps[(static_cast<size_t>(blockIdx.x) * kPersistWaves + wave) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+constexpr size_t kLeanStampWords = (static_cast<size_t>(kMaxPersistGrid) * kPersistWaves + 1 + kPersistWaves) * 8;
+__device__ unsigned long long g_lean_stamps[kLeanStampWords];
+#define LEAN_STAMP(slot) do { if (lane == 0 && blockIdx.x < static_cast<unsigned>(kMaxPersistGrid)) g_lean_stamps[(static_cast<size_t>(blockIdx.x) * kPersistWaves + wave) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #define LEAN_STAMP_FOLD(slot) do { if (threadIdx.x == 0) g_lean_stamps[static_cast<size_t>(kMaxPersistGrid) * kPersistWaves * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define LEAN_STAMP_JUDGE(slot) do { if (lane == 0) g_lean_stamps[(static_cast<size_t>(kMaxPersistGrid) * kPersistWaves + 1 + wave) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 #define LEAN_STAMP(slot) do { } while (0)
 #define LEAN_STAMP_FOLD(slot) do { } while (0)
+#define LEAN_STAMP_JUDGE(slot) do { } while (0)
 #endif
 
 __device__ __forceinline__ void lean_state_store(QueryState* g, const QueryState& st) {
@@ -149,10 +155,15 @@ __device__ __forceinline__ void lean_tile(const double* base, unsigned rem, cons
 
 // Wave 0 of the folding workgroup, lane q holding the moments through round q (or a slot's own total where the form
 // asks for that): the decision and the result.  The rules and what follows them are the monitor's (persist.hip,
-// monitor_fold), evaluated once, for every round at the same time.  T: the launch's tail, in LDS.
-__device__ __forceinline__ void lean_judge(const LeanTail& T, const double (&tot)[7], unsigned lane, unsigned long long t0, unsigned long long epoch, unsigned long long* res_words) {
+// monitor_fold), evaluated once, for every round at the same time.  T: the launch's tail, in LDS.  kLanes = 32: each half
+// of the wave judges a member of its own (lean_union), lane q of the half holding round q, T the half's tail — such
+// members have no top-up slot (plans.hip, union_groups).
+template <unsigned kLanes = 64>
+__device__ __forceinline__ void lean_judge(const LeanTail& T, const double (&tot)[7], const unsigned wave_lane, unsigned long long t0, unsigned long long epoch, unsigned long long* res_words) {
+    static_assert(kLanes == 64 || kLanes == 32, "a whole wave or a half per member");
+    const unsigned lane = wave_lane & (kLanes - 1u), base = wave_lane & ~(kLanes - 1u) & 63u;  // lane in the member's lanes; their first
     const unsigned rounds = T.rounds;
-    const bool tslot = T.topup_slot != 0;  // the last slot is the top-up: summed on its own, never judged
+    const bool tslot = kLanes == 64 && T.topup_slot != 0;  // the last slot is the top-up: summed on its own, never judged
     const unsigned rounds_j = rounds - (tslot ? 1u : 0u);
     if (T.totals_only) {  // multi-GPU form: hand the slot totals out; the decision is taken after the all-reduce
         if (lane < rounds) {
@@ -189,7 +200,7 @@ __device__ __forceinline__ void lean_judge(const LeanTail& T, const double (&tot
 #else
     res.sum = st.sd_p; res.n = static_cast<uint64_t>(st.n_p);
 #endif
-    const unsigned long long stops = __ballot(code != 0);
+    const unsigned long long stops = kLanes == 64 ? __ballot(code != 0) : (__ballot(code != 0) >> base) & ((1ull << (kLanes & 63u)) - 1ull);
     const unsigned last_round = stops ? static_cast<unsigned>(__builtin_ctzll(stops)) : rounds_j - 1u;  // the rule holds after this round / samples exhausted
     if (lane != last_round) return;
     st.rounds = static_cast<int32_t>(last_round + 1u);
@@ -241,8 +252,11 @@ __device__ __forceinline__ void lean_judge(const LeanTail& T, const double (&tot
 #endif
 }
 
-// (all lanes of wave 0, after lean_judge: lane i sends word i of the result, lane sizeof/8 the check word)
-__device__ __forceinline__ void lean_send_result(const LeanTail& T, const unsigned long long* res_words, unsigned lane) {
+// (all lanes of wave 0, after lean_judge: lane i sends word i of the result, lane sizeof/8 the check word; kLanes = 32:
+// lane i of each half, for its member)
+template <unsigned kLanes = 64>
+__device__ __forceinline__ void lean_send_result(const LeanTail& T, const unsigned long long* res_words, const unsigned wave_lane) {
+    const unsigned lane = wave_lane & (kLanes - 1u);
 #if defined(AQE_ABL_NOSTORE) || defined(AQE_ABL_RESDEV)
     return;
 #endif
@@ -284,10 +298,10 @@ __device__ __forceinline__ int lean_ticket(unsigned* const counter, const unsign
 // the targets in ascending piece order, the targets into each class's rows of round totals — and from there every member
 // is judged as lean_query judges a class's.  Fixed orders throughout: bit-reproducible.
 template <bool kNT>
-__device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion* const U, const LeanKarg K, const LeanLaunch* const members, const unsigned nmem,
+__device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion* const U, const LeanLaunch* const members, const unsigned nmem,
                                            const unsigned bid, const unsigned G, const unsigned long long epoch,
                                            double (&lds_part)[kMaxPersistRounds][kPersistWaves][kVec], double (&lds_round)[kMaxPersistRounds][kVec],
-                                           unsigned (&lds_mask)[kPersistWaves], u64 (&lds_tail)[64], int& s_last) {
+                                           unsigned (&lds_mask)[kPersistWaves], int& s_last) {
     static_assert(kUnionWgPieces <= kMaxPersistRounds && kUnionWgPieces <= 32, "a share's pieces: a row of lds_part and a mask bit each");
     static_assert(sizeof(LeanUnion) <= sizeof(lds_round), "the union's header is staged in lds_round");
     const int lane = threadIdx.x & 63;
@@ -305,10 +319,14 @@ __device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion*
     const unsigned p0 = __builtin_amdgcn_readfirstlane(wg[0]);  // the share's first piece: its pieces are p0, p0 + 1, ...
     unsigned my_entry = 0;  // (wave 0) lane j: where the share's partial of piece p0 + j goes
     if (wave == 0 && lane < kUnionWgPieces) my_entry = wg[1 + lane];
-    // what only the folding workgroup reads, fetched now (lean_query): member 0's tail, and the union's header
-    const bool stager = wave == kPersistWaves - 1u, head_stager = wave == kPersistWaves - 2u;
-    u64 tail_word = 0, head_word = 0;
-    if (stager && static_cast<unsigned>(lane) < sizeof(LeanTail) / 8u) tail_word = reinterpret_cast<const AQE_KARG u64*>(&K->tail)[lane];
+#ifdef AQE_LEAN_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    LEAN_STAMP(1);
+#endif
+    // what only the folding workgroup reads, fetched now (lean_query): the union's header (the members' tails come with the
+    // fold's one batch of loads)
+    const bool head_stager = wave == kPersistWaves - 2u;
+    u64 head_word = 0;
     if (head_stager && static_cast<unsigned>(lane) < sizeof(LeanUnion) / 8u) head_word = reinterpret_cast<const u64*>(U)[lane];
 #pragma unroll
     for (unsigned i = 0; i < kMaxPersistRounds * kVec / 64; ++i) {
@@ -340,6 +358,9 @@ __device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion*
             TileAcc ta;
             lean_tile<kNT>(base, static_cast<unsigned>(kDenseTileOrdinals), a.amount, lane, a.has_where, a.wmin, a.wmax, a.shift, ta);
             take(piece, ta);
+#ifdef AQE_LEAN_STAMPS
+            if (j == 0) LEAN_STAMP(2);
+#endif
             continue;
         }
         // the tile owns the rows [vlo, vhi) and holds slots of one piece or of two adjacent ones: the same 16-byte loads, a
@@ -382,10 +403,13 @@ __device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion*
         if (vhi & 1u) add(xo, vhi - 1u, lane == 0);  // the odd last row, folded by lane 0
         take(piece, t0);
         if (two) take(piece + 1u, t1);
+#ifdef AQE_LEAN_STAMPS
+        if (j == 0) LEAN_STAMP(2);
+#endif
     }
+    LEAN_STAMP(3);
     if (cur != ~0u) take(~0u, TileAcc{});  // (flushes the last piece)
     if (lane == 0) lds_mask[wave] = touched;
-    if (stager) lds_tail[lane] = tail_word;
     if (head_stager && static_cast<unsigned>(lane) < sizeof(LeanUnion) / 8u) reinterpret_cast<u64*>(&lds_round[0][0])[lane] = head_word;
     __syncthreads();
 
@@ -395,33 +419,43 @@ __device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion*
 #pragma unroll
         for (unsigned j = 0; j < kPersistWaves; ++j) m |= lds_mask[j];
         m = __builtin_amdgcn_readfirstlane(m);
-        while (m) {
-            const unsigned j = static_cast<unsigned>(__builtin_ctz(m));
-            m &= m - 1u;
-            const unsigned e = __builtin_amdgcn_readlane(my_entry, j);
-            if (lane < 4) {
+        // lane 4 j + c sends component c of piece p0 + 16 g + j: sixteen pieces per store instruction
+        static_assert(kUnionWgPieces % 16 == 0, "pieces in sets of sixteen");
+#pragma unroll
+        for (unsigned g = 0; g < kUnionWgPieces / 16; ++g) {
+            if (((m >> (16u * g)) & 0xffffu) == 0u) continue;  // (wave-uniform)
+            const unsigned j = 16u * g + (static_cast<unsigned>(lane) >> 2), c = static_cast<unsigned>(lane) & 3u;
+            const unsigned e = static_cast<unsigned>(__shfl(static_cast<int>(my_entry), static_cast<int>(j), 64));
+            if ((m >> j) & 1u) {
                 double x[kPersistWaves];
 #pragma unroll
-                for (unsigned w = 0; w < kPersistWaves; ++w) x[w] = lds_part[j][w][lane];
+                for (unsigned w = 0; w < kPersistWaves; ++w) x[w] = lds_part[j][w][c];
                 double s = 0.0;
 #pragma unroll
                 for (unsigned w = 0; w < kPersistWaves; ++w) s += x[w];  // wave order
-                __hip_atomic_store(a.partials + static_cast<size_t>(e) * 4u + lane, s, AQE_RLX);
+                __hip_atomic_store(a.partials + static_cast<size_t>(e) * 4u + c, s, AQE_RLX);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the partials are out before the ticket is drawn
+        LEAN_STAMP(5);
         if (lane == 0) s_last = lean_ticket(a.counter, bid, G);
+        LEAN_STAMP(6);
     }
     __syncthreads();
     if (!s_last) return;
 
     // ---- the last workgroup folds.  ONE batch of loads: the partial list (an entry per thread), the pieces' and the
-    //      targets' ranges, the incidence list (two per thread) and the other members' tails; staged in lds_part ----
-    const LeanTail& T = *reinterpret_cast<const LeanTail*>(lds_tail);
+    //      targets' ranges, the incidence list (two per thread) and the tails of the members the first pass judges (two
+    //      words per lane); staged in lds_part, the tails in registers until the sums are done ----
     const LeanUnion& H = *reinterpret_cast<const LeanUnion*>(&lds_round[0][0]);
     constexpr unsigned kTailWords = sizeof(LeanTail) / 8u;
-    u64 mtail = 0;
-    if (wave != 0 && wave < nmem && static_cast<unsigned>(lane) < kTailWords) mtail = reinterpret_cast<const u64*>(&members[wave].tail)[lane];
+    static_assert(2 * kTailWords <= 128, "a wave's two members' tails, back to back: two words per lane");
+    // wave w judges members m0 = 32 k + 2 w (lanes 0 .. 31) and m0 + 1 (lanes 32 .. 63) in pass k: word j of the two tails
+    auto tail_word = [&](unsigned m0, unsigned j) -> u64 {
+        const unsigned m = m0 + (j >= kTailWords ? 1u : 0u), w = j >= kTailWords ? j - kTailWords : j;
+        return j < 2u * kTailWords && m < nmem ? reinterpret_cast<const u64*>(&members[m].tail)[w] : 0ull;
+    };
+    const u64 mt0 = tail_word(2u * wave, static_cast<unsigned>(lane)), mt1 = tail_word(2u * wave, static_cast<unsigned>(lane) + 64u);
     const unsigned i = threadIdx.x;
     const unsigned nent = H.nentries, npc = H.npieces, ntg = H.ntargets, ninc = H.nincidences;
     double e4[4] = {0.0, 0.0, 0.0, 0.0};
@@ -429,20 +463,24 @@ __device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion*
 #pragma unroll
         for (int c = 0; c < 4; ++c) e4[c] = __hip_atomic_load(a.partials + static_cast<size_t>(i) * 4u + c, AQE_RLX);
     }
-    unsigned pb = 0, pe = 0, tb = 0, te = 0, inc0 = 0, inc1 = 0;
+    // the target sums: thread i sums component i & 3 of target t0 + i / 4, in two turns of 256 targets (t0 = 0, 256)
+    constexpr unsigned kTurn = kPersistThreads / 4;
+    static_assert(2 * kUnionMaxRows <= 2 * kTurn, "two turns of targets");
+    const unsigned tt0 = i >> 2, tt1 = tt0 + kTurn, tc = i & 3u;
+    unsigned pb = 0, pe = 0, tb0 = 0, te0 = 0, tb1 = 0, te1 = 0, inc0 = 0, inc1 = 0;
     if (i < npc) { pb = H.piece_entry[i]; pe = H.piece_entry[i + 1u]; }
-    if (i < ntg) { tb = H.target_begin[i]; te = H.target_begin[i + 1u]; }
+    if (tt0 < ntg) { tb0 = H.target_begin[tt0]; te0 = H.target_begin[tt0 + 1u]; }
+    if (tt1 < ntg) { tb1 = H.target_begin[tt1]; te1 = H.target_begin[tt1 + 1u]; }
     if (i < ninc) inc0 = H.target_entry[i];
     if (i + kPersistThreads < ninc) inc1 = H.target_entry[i + kPersistThreads];
     // lds_part as one flat list: [0, 4 kUnionMaxEntries) the entries, then the incidences; later [0, 2048) the judging
-    // waves' words (lean_query), [2048, 4096) the rows of round totals
+    // waves' words, [2048, 4096) the rows of round totals
     double* const F = &lds_part[0][0][0];
     unsigned* const Finc = reinterpret_cast<unsigned*>(F + 4 * kUnionMaxEntries);
     double* const rows = F + 2048;
     static_assert(4 * kUnionMaxEntries * sizeof(double) + kUnionMaxIncidences * sizeof(unsigned) <= sizeof(lds_part), "the fold's staging fits lds_part");
     static_assert(kUnionMaxIncidences <= 2 * kPersistThreads && kUnionMaxEntries <= kPersistThreads && kUnionMaxPieces <= kPersistThreads, "one batch of loads");
     static_assert(2048 + 8 * kUnionMaxRows <= kMaxPersistRounds * kPersistWaves * kVec && kPersistWaves * 128 <= 2048, "rows beside the judging waves' words");
-    static_assert(2 * kUnionMaxRows <= kPersistThreads, "a thread per target");
     if (i < nent) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) F[4u * i + c] = e4[c];
@@ -450,7 +488,8 @@ __device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion*
     if (i < ninc) Finc[i] = inc0;
     if (i + kPersistThreads < ninc) Finc[i + kPersistThreads] = inc1;
     __syncthreads();
-    // (both sums below read kFoldBatch LDS entries at a time before adding them in order: one LDS round trip per batch)
+    LEAN_STAMP_FOLD(3);
+    // (the piece sums read kFoldBatch LDS entries at a time before adding them in order: one LDS round trip per batch)
     constexpr unsigned kFoldBatch = 4;
     if (i < npc) {  // a piece's partials, in workgroup order, into its first entry
         double s4[4] = {0.0, 0.0, 0.0, 0.0};
@@ -474,67 +513,85 @@ __device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion*
         for (int c = 0; c < 4; ++c) F[4u * pb + c] = s4[c];
     }
     __syncthreads();
-    double r4[4] = {0.0, 0.0, 0.0, 0.0};
-    if (i < ntg) {  // a target's pieces, ascending
-        for (unsigned k0 = tb; k0 < te; k0 += kFoldBatch) {
-            unsigned e[kFoldBatch];
+    LEAN_STAMP_FOLD(4);
+    // A target's pieces, ascending, one component per thread.  A target may add a few hundred pieces: its chain of adds
+    // is fixed (bit-reproducible), so what is cut is the LDS round trips around it — kTargetBatch values per trip, the
+    // next batch's incidences read beside them.
+    auto target_sum = [&](unsigned tb, unsigned te) {
+        constexpr unsigned kTargetBatch = 16;
+        double r = 0.0;
+        if (tb >= te) return r;
+        unsigned e[kTargetBatch];
 #pragma unroll
-            for (unsigned u = 0; u < kFoldBatch; ++u) e[u] = Finc[k0 + u < te ? k0 + u : tb];
-            double x[kFoldBatch][4];
+        for (unsigned u = 0; u < kTargetBatch; ++u) e[u] = Finc[tb + u < te ? tb + u : tb];
+        for (unsigned k0 = tb; k0 < te; k0 += kTargetBatch) {
+            double x[kTargetBatch];
 #pragma unroll
-            for (unsigned u = 0; u < kFoldBatch; ++u) {
+            for (unsigned u = 0; u < kTargetBatch; ++u) x[u] = F[4u * e[u] + tc];
+            const unsigned k1 = k0 + kTargetBatch;
 #pragma unroll
-                for (int c = 0; c < 4; ++c) x[u][c] = F[4u * e[u] + c];
-            }
+            for (unsigned u = 0; u < kTargetBatch; ++u) e[u] = Finc[k1 + u < te ? k1 + u : tb];
 #pragma unroll
-            for (unsigned u = 0; u < kFoldBatch; ++u) {
-                if (k0 + u < te) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) r4[c] += x[u][c];
-                }
+            for (unsigned u = 0; u < kTargetBatch; ++u) {
+                if (k0 + u < te) r += x[u];
             }
         }
-    }
+        return r;
+    };
+    const double r0 = tt0 < ntg ? target_sum(tb0, te0) : 0.0;
+    const double r1 = tt1 < ntg ? target_sum(tb1, te1) : 0.0;
     __syncthreads();
-    if (i < ntg) {  // target 2 L + g: group g of row L — (n, S, Q) at 3 g, its rows visited at 6 + g
-        const unsigned g = i & 1u;
-        double* const r = rows + static_cast<size_t>(i >> 1) * 8u;
-        r[3u * g] = r4[0]; r[3u * g + 1u] = r4[1]; r[3u * g + 2u] = r4[2];
-        r[6u + g] = r4[3];
-    }
+    // target 2 L + g: group g of row L — (n, S, Q) at 3 g, its rows visited at 6 + g
+    auto put = [&](unsigned t, double r) { rows[static_cast<size_t>(t >> 1) * 8u + (tc < 3u ? 3u * (t & 1u) + tc : 6u + (t & 1u))] = r; };
+    if (tt0 < ntg) put(tt0, r0);
+    if (tt1 < ntg) put(tt1, r1);
     __syncthreads();
-    if (wave >= nmem) return;
-    // the judges: wave m judges members m, m + 16, ... of every class of the group, each on its own class's rows
+    LEAN_STAMP_FOLD(5);
+    // The judges, two members per wave, one per half (a member has at most kMaxPersistRounds = 32 rounds): wave w judges
+    // members 2 w and 2 w + 1 — the bench's 32 members in ONE pass; a union of more members takes further passes, each
+    // fetching its tails first.  A wave's LDS: the two tails back to back, then each half's result words.
+    static_assert(kMaxPersistRounds <= 32, "a member's rounds fit a half wave");
+    if (2u * wave >= nmem) return;
     u64* const lds_mine = reinterpret_cast<u64*>(F) + wave * 128u;
-    unsigned long long* const lds_res = lds_mine + 64;
-    if (wave != 0) { lds_mine[lane] = mtail; wave_lds_handoff(); }
-    for (unsigned mi = wave;;) {
-        const LeanTail& Tm = mi == 0 ? T : *reinterpret_cast<const LeanTail*>(lds_mine);
+    const unsigned h = static_cast<unsigned>(lane) >> 5, q = static_cast<unsigned>(lane) & 31u;
+    unsigned long long* const lds_res = lds_mine + 80u + 16u * h;
+    static_assert(2 * kTailWords <= 80 && 80 + 2 * 16 <= 128, "a wave's words");
+    lds_mine[lane] = mt0;
+    if (static_cast<unsigned>(lane) + 64u < 2u * kTailWords) lds_mine[lane + 64] = mt1;
+    wave_lds_handoff();
+    for (unsigned m0 = 2u * wave;;) {
+        // (a half past the last member reads a tail of zeros: no rounds, nothing judged, nothing sent)
+        const LeanTail& Tm = *reinterpret_cast<const LeanTail*>(lds_mine + h * kTailWords);
         const unsigned rounds = Tm.rounds;
-        const bool mine = static_cast<unsigned>(lane) < rounds;
-        const double* const r = rows + static_cast<size_t>(Tm.union_row + (mine ? static_cast<unsigned>(lane) : 0u)) * 8u;
+        const bool mine = q < rounds;
+        const double* const r = rows + static_cast<size_t>(Tm.union_row + (mine ? q : 0u)) * 8u;
         double tot[7];
 #pragma unroll
         for (int cc = 0; cc < 6; ++cc) tot[cc] = mine ? r[cc] : 0.0;
         tot[6] = mine ? r[6] + r[7] : 0.0;
 #pragma unroll
-        for (int cc = 0; cc < 7; ++cc) {  // lane q: the moments through round q (lean_query's scan, one row per round)
+        for (int cc = 0; cc < 7; ++cc) {  // lane q of a half: the moments through round q (lean_query's scan, one row per round)
             double p = tot[cc];
             p += dpp_f64<0x111>(p);
             p += dpp_f64<0x112>(p);
             p += dpp_f64<0x114>(p);
             p += dpp_f64<0x118>(p);
-            const double carry = read_lane_f64(p, 15);
-            tot[cc] = p + (lane >= 16 ? carry : 0.0);
+            const double carry = __shfl(p, static_cast<int>((static_cast<unsigned>(lane) & 32u) | 15u), 64);  // the half's first row's total
+            tot[cc] = p + ((lane & 16) ? carry : 0.0);
         }
-        lean_judge(Tm, tot, static_cast<unsigned>(lane), 0ull, epoch, lds_res);
+        lean_judge<32>(Tm, tot, static_cast<unsigned>(lane), 0ull, epoch, lds_res);
         wave_lds_handoff();
-        lean_send_result(Tm, lds_res, static_cast<unsigned>(lane));
-        mi += kPersistWaves;
-        if (mi >= nmem) break;
-        const u64 w = static_cast<unsigned>(lane) < kTailWords ? reinterpret_cast<const u64*>(&members[mi].tail)[lane] : 0ull;
+#ifdef AQE_LEAN_STAMPS
+        if (m0 == 2u * wave) LEAN_STAMP_JUDGE(0);
+#endif
+        lean_send_result<32>(Tm, lds_res, static_cast<unsigned>(lane));
+        LEAN_STAMP_JUDGE(1);
+        m0 += 2u * kPersistWaves;
+        if (m0 >= nmem) break;
+        const u64 w0 = tail_word(m0, static_cast<unsigned>(lane)), w1 = tail_word(m0, static_cast<unsigned>(lane) + 64u);
         wave_lds_handoff();
-        lds_mine[lane] = w;
+        lds_mine[lane] = w0;
+        if (static_cast<unsigned>(lane) + 64u < 2u * kTailWords) lds_mine[lane + 64] = w1;
         wave_lds_handoff();
     }
 }
@@ -558,7 +615,7 @@ __device__ __forceinline__ void lean_query(const LeanLaunch& a, const LeanRuns* 
     __shared__ u64 lds_tail[64];
     __shared__ int s_last;
     if (uni) {  // a union group of a batch: the same LDS, another sweep and fold
-        lean_union<kNT>(a, uni, K, members, nmem, bid, G, epoch, lds_part, lds_round, lds_mask, lds_tail, s_last);
+        lean_union<kNT>(a, uni, members, nmem, bid, G, epoch, lds_part, lds_round, lds_mask, s_last);
         return;
     }
     const int lane = threadIdx.x & 63;
@@ -842,6 +899,13 @@ __global__ __launch_bounds__(kPersistThreads) void k_sweep_lean(LeanLaunch a) {
 // finishes its queries — so groups may be dispatched in any order and there may be more of them than compute units.
 template <bool kNT>
 __global__ __launch_bounds__(kPersistThreads) void k_sweep_lean_multi(const LeanLaunch* table, const unsigned long long* wg_map, unsigned long long epoch) {
+#ifdef AQE_LEAN_STAMPS
+    {
+        const int lane = threadIdx.x & 63;
+        const unsigned wave = threadIdx.x >> 6;
+        LEAN_STAMP(0);
+    }
+#endif
     const u64 me = uniform64(wg_map[blockIdx.x]);
     const unsigned q = static_cast<unsigned>(me >> 32) & 0xffffu, nmem = static_cast<unsigned>(me >> 48);
     const LeanKarg K = (LeanKarg)(table + q);
@@ -879,7 +943,7 @@ hipError_t launch_sweep_lean(const LeanLaunch& a, unsigned grid, bool nt, hipStr
 
 #ifdef AQE_LEAN_STAMPS
 extern "C" __attribute__((visibility("default"))) int aqe_debug_lean_stamps(unsigned long long* out, size_t words) {
-    const size_t all = (kMaxPersistGrid * kPersistWaves + 1) * 8;
+    const size_t all = kLeanStampWords;
     return static_cast<int>(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lean_stamps), 8 * (words < all ? words : all), 0, hipMemcpyDeviceToHost));
 }
 #endif
