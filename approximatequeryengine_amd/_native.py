@@ -41,6 +41,8 @@ MAILBOX_MAX_DOUBLES = 4096
 MAX_QUANTILES = 8
 QUANTILE_LINEAR, QUANTILE_INVERTED_CDF = 0, 1
 QUANTILE_VEC_SUM, QUANTILE_VEC_MAX = 8194, 64
+SPREAD_VAR_SAMP, SPREAD_VAR_POP, SPREAD_STDDEV_SAMP, SPREAD_STDDEV_POP = 0, 1, 2, 3
+SPREAD_VEC, SPREAD_BIN = 8, 6
 
 
 class Query(C.Structure):
@@ -90,6 +92,24 @@ class QuantileResult(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SpreadResult(C.Structure):
+    _fields_ = [("value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double), ("mean", C.c_double), ("m2", C.c_double),
+                ("m3", C.c_double), ("m4", C.c_double), ("n", C.c_uint64), ("visited", C.c_uint64), ("has_interval", C.c_int32),
+                ("device_status", C.c_int32), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SpreadGroupResult(C.Structure):
+    _fields_ = [("key", C.c_int64), ("value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double), ("mean", C.c_double),
+                ("m2", C.c_double), ("m3", C.c_double), ("m4", C.c_double), ("n", C.c_uint64), ("visited", C.c_uint64),
+                ("has_interval", C.c_int32), ("pad", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
 class TableInfo(C.Structure):
@@ -181,6 +201,13 @@ def lib() -> C.CDLL:
         "aqe_quantile_done": (C.c_int, [vp, P(C.c_int)]),
         "aqe_quantile_finish": (C.c_int, [vp, P(QuantileResult), vp]),
         "aqe_quantile_destroy": (None, [vp]),
+        "aqe_reduce_spread": (C.c_int, [vp, P(Query), C.c_int, P(SpreadResult)]),
+        "aqe_spread_enqueue": (C.c_int, [vp, P(Query), vp, vp]),
+        "aqe_spread_finish": (C.c_int, [vp, P(Query), C.c_int, vp, vp, P(SpreadResult)]),
+        "aqe_spread_from_sums": (C.c_int, [P(dbl), C.c_int, dbl, C.c_int, P(SpreadResult)]),
+        "aqe_reduce_grouped_spread": (C.c_int, [vp, P(Query), C.c_int, C.c_int, P(SpreadGroupResult), u32, P(u32)]),
+        "aqe_grouped_spread_enqueue_bins": (C.c_int, [vp, P(Query), C.c_int, C.c_int32, u32, vp, vp]),
+        "aqe_grouped_spread_finish": (C.c_int, [vp, P(Query), C.c_int, C.c_int32, u32, vp, vp, P(SpreadGroupResult), u32, P(u32)]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),

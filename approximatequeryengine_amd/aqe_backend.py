@@ -33,7 +33,7 @@ from . import _native as nat
 from .engine import RECORD_DTYPE, Engine, make_query
 
 __all__ = ["Record", "CustomBPlusDB", "CustomApproximateScheduler", "CustomValidationResult",
-           "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate"]
+           "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate", "SpreadEstimate"]
 
 
 class Record:
@@ -156,6 +156,32 @@ def _quantile_call(fn):
         if "No samples collected" in str(e):
             raise RuntimeError("No samples collected") from None
         raise
+
+
+class SpreadEstimate:
+    """Result of approx_spread: variance or standard deviation of the sampled amounts with the large-sample interval from the
+    fourth central moment (include/aqe_hip.h, aqe_spread_result).  ``has_interval`` is False when the sample is too small
+    (n < 4): the bounds are then NaN.  ``key`` is the group's key under GROUP BY, else None."""
+    __slots__ = ("kind", "value", "ci_lower", "ci_upper", "mean", "m2", "m3", "m4", "n", "visited", "has_interval", "kernel_ms", "method", "key")
+
+    def __init__(self, r, kind: str, method: str):
+        for k in ("value", "ci_lower", "ci_upper", "mean", "m2", "m3", "m4", "n", "visited"):
+            setattr(self, k, getattr(r, k))
+        self.has_interval = bool(r.has_interval)
+        self.kernel_ms = getattr(r, "kernel_ms", 0.0)
+        self.key = getattr(r, "key", None)
+        self.kind, self.method = kind, method
+
+    def __repr__(self):
+        return (f"SpreadEstimate(kind={self.kind!r}, value={self.value!r}, ci=({self.ci_lower!r}, {self.ci_upper!r}), n={self.n}, "
+                f"method={self.method!r})")
+
+    def __iter__(self):  # unpacks like a GroupEstimate: (value, ci_lower, ci_upper)
+        return iter((self.value, self.ci_lower, self.ci_upper))
+
+
+_SPREAD_KINDS = {"var_samp": nat.SPREAD_VAR_SAMP, "variance": nat.SPREAD_VAR_SAMP, "var_pop": nat.SPREAD_VAR_POP,
+                 "stddev_samp": nat.SPREAD_STDDEV_SAMP, "stddev": nat.SPREAD_STDDEV_SAMP, "stddev_pop": nat.SPREAD_STDDEV_POP}
 
 
 def parse_where(query: str) -> Optional[Tuple[float, float]]:
@@ -598,6 +624,54 @@ class CustomBPlusDB:
     def approx_median(self, **kw):
         """APPROX MEDIAN(amount): approx_quantile(0.5, **kw)."""
         return self.approx_quantile(0.5, **kw)
+
+    def approx_spread(self, kind: str = "var_samp", method: str = "stride", sample_percent: float = 10.0,
+                      where: Optional[Tuple[float, float]] = None, id_between: Optional[Tuple[int, int]] = None, seed: int = 42,
+                      confidence_level: float = 0.95, group_by: Optional[str] = None, num_threads: int = 4, block_size: int = 1000):
+        """APPROX VARIANCE / STDDEV(amount): ``kind`` is "var_samp" ("variance"), "var_pop", "stddev_samp" ("stddev") or
+        "stddev_pop" of the sampled amounts X (WHERE and the key window applied) — numpy.var(X, ddof=1) and its kin, not scaled
+        by the sampling fraction — with a large-sample normal interval from the fourth central moment; method "exact" reports
+        [value, value].  method as approx_quantile ("exact", "stride", "block", "page", "parallel_block", "region", "random" ...;
+        CLT, adaptive, stratified and random_device samplers raise ValueError), and "rowid" (approx_group_by's sample).  With
+        ``group_by`` ("region" | "product_id") the result is the key -> SpreadEstimate mapping approx_group_by returns."""
+        k = str(kind).strip().lower()
+        if k not in _SPREAD_KINDS:
+            raise ValueError(f"kind must be one of {sorted(_SPREAD_KINDS)}")
+        if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
+            raise ValueError(f"VARIANCE / STDDEV do not take the {method} sampler (single-round family samplers and 'random' only)")
+        col = None
+        if group_by is not None:
+            col = {"region": nat.GROUP_REGION, "product_id": nat.GROUP_PRODUCT}[group_by.strip().lower()]
+            if method == "random":
+                raise ValueError("GROUP BY takes a family sampler ('rowid', 'stride', 'block', 'page', 'exact' ...), not 'random'")
+            if self._n == 0:
+                return {}
+        if method == "rowid":
+            q = self._approx_query("SUM", "stride", sample_percent, None, where, seed, num_threads, block_size, confidence_level,
+                                   id_between=id_between)
+            q.method = nat.M_ROWID_MOD
+        else:
+            q = self._approx_query("SUM", method, sample_percent, None, where, seed, num_threads, block_size, confidence_level,
+                                   id_between=id_between)
+        q.confidence_level = float(confidence_level)
+        if col is not None:
+            groups = _quantile_call(lambda: self._spread_groups(q, _SPREAD_KINDS[k], col))
+            return {str(r.key): SpreadEstimate(r, k, method) for r in groups}
+        return SpreadEstimate(_quantile_call(lambda: self._spread(q, _SPREAD_KINDS[k])), k, method)
+
+    def _spread(self, q, kind):
+        return self._eng().reduce_spread(q, kind)
+
+    def _spread_groups(self, q, kind, col):
+        return self._eng().reduce_grouped_spread(q, kind, col)
+
+    def approx_variance(self, **kw):
+        """APPROX VARIANCE(amount): approx_spread("var_samp", **kw)."""
+        return self.approx_spread("var_samp", **kw)
+
+    def approx_stddev(self, **kw):
+        """APPROX STDDEV(amount): approx_spread("stddev_samp", **kw)."""
+        return self.approx_spread("stddev_samp", **kw)
 
     def approx_sum(self, **kw) -> ApproxResult:
         return self.approx("SUM", **kw)

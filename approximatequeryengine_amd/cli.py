@@ -6,6 +6,7 @@
     python -m approximatequeryengine_amd.cli "SELECT APPROX(SUM(amount)) FROM sales" --db sales.db --compare
     python -m approximatequeryengine_amd.cli "SELECT MEDIAN(amount) FROM sales" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli "SELECT PERCENTILE_DISC(amount, 0.99) FROM sales" --db sales.db --compare
+    python -m approximatequeryengine_amd.cli "SELECT STDDEV(amount) FROM sales GROUP BY region" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli --explain
 
 The reference's own CLI defines `-s/--sample` and `-e/--error` but tests `args.s` / `args.e`
@@ -75,6 +76,25 @@ def quantile_of(query: str) -> Optional[Tuple[float, str, str]]:
     return p, _QUANTILE_FUNCS[m.group(1).upper()], m.group(1).upper()
 
 
+_SPREAD_FUNCS = {"VARIANCE": "var_samp", "VAR_SAMP": "var_samp", "VAR_POP": "var_pop", "STDDEV": "stddev_samp",
+                 "STDDEV_SAMP": "stddev_samp", "STDDEV_POP": "stddev_pop"}
+
+
+def spread_of(query: str) -> Optional[Tuple[str, str]]:
+    """VARIANCE | VAR_SAMP | VAR_POP | STDDEV | STDDEV_SAMP | STDDEV_POP (amount) -> (kind of approx_spread, name as typed, in
+    upper case); None for any other query — and for every query that names SUM(, AVG(, COUNT( or a quantile function, whose
+    routing stays as it was."""
+    up = query.upper()
+    if any(a + "(" in up for a in ("SUM", "AVG", "COUNT")):
+        return None
+    if re.search(r"\b(MEDIAN|PERCENTILE(_CONT|_DISC)?)\s*\(", query, re.IGNORECASE):
+        return None
+    m = re.search(r"\b(VARIANCE|VAR_SAMP|VAR_POP|STDDEV_SAMP|STDDEV_POP|STDDEV)\s*\(\s*amount\s*\)", query, re.IGNORECASE)
+    if not m:
+        return None
+    return _SPREAD_FUNCS[m.group(1).upper()], m.group(1).upper()
+
+
 def determine_query_type(query: str, args) -> str:
     """enhanced_aqe_cli.py:97-114 with the attribute names fixed."""
     if parse_embedded_approx(query)[1]:
@@ -99,7 +119,7 @@ def get_optimal_method_for_query(query: str, dataset_size: Optional[int] = None)
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE on MI355X",
+    p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV on MI355X",
                                 allow_abbrev=False)
     p.add_argument("query", nargs="?", help="SQL query, e.g. \"SELECT SUM(amount) FROM sales\"")
     p.add_argument("--db", default="custom_demo.db", help="database file (reference format)")
@@ -140,6 +160,9 @@ def run(args, out=sys.stdout) -> int:
         if re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
             print("error: GROUP BY is not supported with MEDIAN / PERCENTILE", file=out)
             return 2
+    if spread_of(clean) is not None and args.e is not None:
+        print("error: VARIANCE / STDDEV have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
+        return 2
     if not os.path.exists(args.db):
         print(f"error: database file '{args.db}' not found", file=out)
         return 1
@@ -187,6 +210,9 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     quant = quantile_of(clean)
     if quant is not None:
         return _run_quantile(db, args, out, clean, qtype, quant, aqe_backend, t0)
+    spread = spread_of(clean)
+    if spread is not None:
+        return _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0)
     gb = re.search(r"GROUP\s+BY\s+(region|product_id)\b", clean, flags=re.IGNORECASE)
     if gb:  # one sweep, one (n, S, Q) bin per key, an interval per group (executor.cpp:202-321 semantics)
         pct = args.s if args.s is not None else (100.0 if qtype == QUERY_EXACT else 10.0)
@@ -263,6 +289,51 @@ def _run_quantile(db, args, out, clean, qtype, quant, aqe_backend, t0) -> int:
     if args.compare and method != "exact":
         exact = db.approx_quantile(p, method="exact", where=where, interpolation=interp)
         print(f"\ncomparison:\n   approximate: {res.value:,.4f}\n   exact:       {exact.value:,.4f}", file=out)
+        if exact.value != 0:
+            print(f"   actual error: {abs(res.value - exact.value) / abs(exact.value) * 100:.4f}%", file=out)
+    db.close_database()
+    return 0
+
+
+def _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0) -> int:
+    """VARIANCE / VAR_SAMP / VAR_POP / STDDEV / STDDEV_SAMP / STDDEV_POP: exact without --s; with --s (or an APPROX(...)
+    wrapper) a sample — --method block / parallel / random honoured, stride otherwise; GROUP BY region | product_id samples by
+    rowid, as the SUM / AVG / COUNT form does."""
+    kind, fname = spread
+    where = aqe_backend.parse_where(clean)
+    gb = re.search(r"GROUP\s+BY\s+(region|product_id)\b", clean, flags=re.IGNORECASE)
+    if args.s is None and qtype != QUERY_EMBEDDED:
+        method, pct, name = "exact", 100.0, "exact"
+    else:
+        pct = args.s if args.s is not None else 10.0
+        if gb:
+            method = "exact" if pct >= 100.0 else "rowid"
+        else:
+            method = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", "stride")
+        name = "exact" if method == "exact" else f"{method} sampling ({pct}%)"
+    fmt = lambda v: "n/a" if v != v else f"{v:,.4f}"
+    if gb:
+        groups = db.approx_spread(kind, method=method, sample_percent=pct, where=where, confidence_level=args.confidence,
+                                  group_by=gb.group(1))
+        ms = (time.perf_counter() - t0) * 1e3
+        print(f"\n{fname}(amount) GROUP BY {gb.group(1).lower()} ({name}):", file=out)
+        for key, g in groups.items():
+            ci = f"   ({fmt(g.ci_lower)} - {fmt(g.ci_upper)})" if (args.ci and method != "exact") else ""
+            print(f"   {key:>6}: {fmt(g.value)}{ci}   n={g.n:,}", file=out)
+        print(f"   execution time: {ms:.2f} ms", file=out)
+        db.close_database()
+        return 0
+    res = db.approx_spread(kind, method=method, sample_percent=pct, where=where, confidence_level=args.confidence, seed=args.seed,
+                           num_threads=args.threads)
+    ms = (time.perf_counter() - t0) * 1e3
+    print(f"\n{name} {fname}(amount) result:\n   value: {fmt(res.value)}", file=out)
+    if args.ci and method != "exact":
+        print(f"   confidence interval ({args.confidence:g}, fourth moment): ({fmt(res.ci_lower)} - {fmt(res.ci_upper)})", file=out)
+    print(f"   samples used: {res.n:,}   mean: {res.mean:,.4f}", file=out)
+    print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
+    if args.compare and method != "exact":
+        exact = db.approx_spread(kind, method="exact", where=where)
+        print(f"\ncomparison:\n   approximate: {fmt(res.value)}\n   exact:       {fmt(exact.value)}", file=out)
         if exact.value != 0:
             print(f"   actual error: {abs(res.value - exact.value) / abs(exact.value) * 100:.4f}%", file=out)
     db.close_database()

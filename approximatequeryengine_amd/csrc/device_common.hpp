@@ -455,5 +455,109 @@ __device__ __forceinline__ void sweep_tile(const SweepCommon& a, FamPtr fams, u6
     sweep_family<kNT>(a, fams[find_family(fams, a.nfam, t)], t, lane, ord_limit, acc);
 }
 
+// The row loop of sweep_family / k_grouped / the quantile passes as a VISITOR: one wave walks tile `t` of the launch's
+// family table (single-pointer families: dense 16-byte path with its interior form, page path, strided path and
+// stride-major views, window edges) and calls visit(x, key, ok) once per ordinal slot of the tile, in a fixed order — ok
+// says whether the slot is a sampled row (x and key are then that row's amount and, with kKeys, its key from `keys`, a
+// column in the amount's row or slot order; without kKeys key is 0).  Every load of the tile is issued before the first
+// visit; slots outside the window read row 0 of the shard.  kNT: non-temporal loads on the interior dense form.
+template <bool kNT, bool kKeys, typename FamPtr, typename Visit>
+__device__ __forceinline__ void visit_tile(const SweepCommon& sw, FamPtr fams, const int32_t* keys, u64 t, int lane, Visit& visit) {
+    const auto& F = fams[find_family(fams, sw.nfam, t)];
+    const u64 lt = t - F.tile_begin;
+    u64 seg, j;
+    if (F.tiles_per_seg == 0) { seg = F.seg_lo; j = F.j_lo + lt; }
+    else { seg = F.seg_lo + lt / F.tiles_per_seg; j = lt % F.tiles_per_seg; }
+    const u64 seg_len = F.seg_len, step = F.step, seg_ord0 = seg * seg_len;
+    const u64 ord_lo = F.ord_lo, ord_hi = F.ord_hi;
+    const u64 row_base = F.row0 + seg * F.pitch - sw.shard_lo;
+    const double* const base = sw.amount + row_base;
+    const int32_t* const kbase = kKeys ? keys + row_base : nullptr;
+    if (sw.dense16 && is_dense16(step, F.flags, seg_len)) {
+        struct __attribute__((packed, aligned(8))) Row2 { double x, y; };
+        struct __attribute__((packed, aligned(4))) Key2 { int x, y; };
+        Row2 x2[kTileUnroll];
+        Key2 k2[kTileUnroll];
+        // interior tile (sweep_family): every slot inside the segment and the window — no masks, no address selects
+        const u64 tile_lo = uniform64(j * kDenseTileOrdinals), o_lo = uniform64(seg_ord0 + tile_lo);
+        if (tile_lo + kDenseTileOrdinals <= uniform64(seg_len) && o_lo >= uniform64(ord_lo) && o_lo + kDenseTileOrdinals <= uniform64(ord_hi)) {
+            const Row2* const p = reinterpret_cast<const Row2*>(base + tile_lo) + lane;
+            const Key2* const pk = kKeys ? reinterpret_cast<const Key2*>(kbase + tile_lo) + lane : nullptr;
+#pragma unroll
+            for (int k = 0; k < kTileUnroll; ++k) {
+                if (kNT) {
+                    x2[k].x = __builtin_nontemporal_load(&p[k * 64].x);
+                    x2[k].y = __builtin_nontemporal_load(&p[k * 64].y);
+                } else {
+                    x2[k] = p[k * 64];
+                }
+                if (kKeys) k2[k] = pk[k * 64];
+                else k2[k].x = k2[k].y = 0;
+            }
+#pragma unroll
+            for (int k = 0; k < kTileUnroll; ++k) { visit(x2[k].x, k2[k].x, true); visit(x2[k].y, k2[k].y, true); }
+            return;
+        }
+        const u64 oi0 = j * kDenseTileOrdinals + 2 * static_cast<u64>(lane);
+        bool ok0[kTileUnroll], ok1[kTileUnroll];
+#pragma unroll
+        for (int k = 0; k < kTileUnroll; ++k) {
+            const u64 oi = oi0 + static_cast<u64>(k) * 128;
+            const u64 o = seg_ord0 + oi;
+            ok0[k] = oi < seg_len && o >= ord_lo && o < ord_hi;
+            ok1[k] = oi + 1 < seg_len && o + 1 >= ord_lo && o + 1 < ord_hi;
+            const bool both = ok0[k] && ok1[k];
+            x2[k] = *reinterpret_cast<const Row2*>(both ? base + oi : sw.amount);
+            if (kKeys) k2[k] = *reinterpret_cast<const Key2*>(both ? kbase + oi : keys);
+            else k2[k].x = k2[k].y = 0;
+            if (!both) {  // window edge: single reads
+                x2[k].x = ok0[k] ? base[oi] : 0.0;
+                x2[k].y = ok1[k] ? base[oi + 1] : 0.0;
+                if (kKeys) {
+                    k2[k].x = ok0[k] ? kbase[oi] : 0;
+                    k2[k].y = ok1[k] ? kbase[oi + 1] : 0;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kTileUnroll; ++k) { visit(x2[k].x, k2[k].x, ok0[k]); visit(x2[k].y, k2[k].y, ok1[k]); }
+        return;
+    }
+    const u64 oi0 = j * kTileOrdinals + lane;
+    double x[kTileUnroll];
+    int key[kTileUnroll];
+    bool ok[kTileUnroll];
+    if (F.flags & kFamLinear) {
+        // short segments (pages) tiled along the ordinal axis, a tile spanning several segments (sweep_family)
+        const u64 T0 = j * kTileOrdinals;
+        const u64 seg0 = T0 / seg_len;
+        const unsigned r0 = static_cast<unsigned>(T0 - seg0 * seg_len), sl = static_cast<unsigned>(seg_len);
+        const float inv = 1.0f / static_cast<float>(sl);
+        const u64 col0 = F.row0 - sw.shard_lo;
+#pragma unroll
+        for (int k = 0; k < kTileUnroll; ++k) {
+            const unsigned xx = r0 + static_cast<unsigned>(lane) + 64u * static_cast<unsigned>(k);
+            const unsigned qx = static_cast<unsigned>((static_cast<float>(xx) + 0.5f) * inv);
+            const u64 o = T0 + static_cast<unsigned>(lane) + 64u * static_cast<unsigned>(k);
+            ok[k] = o >= ord_lo && o < ord_hi;
+            const u64 off = ok[k] ? col0 + (seg0 + qx) * F.pitch + static_cast<u64>(xx - qx * sl) * step : 0;
+            x[k] = sw.amount[off];
+            key[k] = kKeys ? keys[off] : 0;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kTileUnroll; ++k) {
+            const u64 oi = oi0 + static_cast<u64>(k) * 64;
+            const u64 o = seg_ord0 + oi;
+            ok[k] = oi < seg_len && o >= ord_lo && o < ord_hi;
+            const u64 off = ok[k] ? oi * step : 0;
+            x[k] = ok[k] ? base[off] : sw.amount[0];
+            key[k] = kKeys ? (ok[k] ? kbase[off] : keys[0]) : 0;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kTileUnroll; ++k) visit(x[k], key[k], ok[k]);
+}
+
 }  // namespace
 }  // namespace aqe

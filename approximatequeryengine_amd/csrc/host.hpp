@@ -91,6 +91,8 @@ struct StageRing {
     size_t bytes_each = 0;
 };
 
+struct aqe_spread_scratch;  // spread.hip
+
 struct aqe_ctx {
     StageRing ring;
     aqe_stage_stats stage_stats{};  // of the most recent staging (aqe_last_stage_stats)
@@ -150,6 +152,8 @@ struct aqe_ctx {
     bool qrange_valid = false;
     uint64_t qrange_epoch = 0;
     double qrange_lo = 0.0, qrange_hi = 0.0;
+    // VARIANCE / STDDEV (spread.hip): partials, tickets, pinned results of the spread entries, made on first use
+    aqe_spread_scratch* spread = nullptr;
 };
 
 // One persistent-sweep form of a plan's rounds (persist.hip): the tile list of all slots, who owns tiles
@@ -279,6 +283,9 @@ inline double query_shift(const aqe_ctx* c, const aqe_query& q) {
 // quantile.hip
 int quantile_amount_range(aqe_ctx* c, double* lo, double* hi);  // non-NaN amounts of the shard (+inf / -inf: none)
 void quantile_release(aqe_ctx* c);
+
+// spread.hip
+void spread_release(aqe_ctx* c);
 
 // plans.hip
 void destroy_plan(aqe_plan* p, bool device_idle = false);  // device_idle: the caller has just synchronised the device

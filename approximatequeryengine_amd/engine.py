@@ -452,6 +452,40 @@ class Engine:
                        stream: int = 0) -> "QuantileRun":
         return QuantileRun(self, query, probs, interpolation, amount_min, amount_max, stream)
 
+    # -- spread: VARIANCE / STDDEV (aqe_reduce_spread, its additive multi-GPU split, the GROUP BY form) --
+    def reduce_spread(self, query: Query, kind: int = nat.SPREAD_VAR_SAMP) -> "nat.SpreadResult":
+        """Variance / standard deviation of the sampled amounts with the fourth-moment interval (include/aqe_hip.h)."""
+        out = nat.SpreadResult()
+        self._chk(nat.lib().aqe_reduce_spread(self._h, C.byref(query), int(kind), C.byref(out)))
+        return out
+
+    def spread_enqueue(self, query: Query, dev_vec_ptr: int, stream: int = 0):
+        """This shard's SPREAD_VEC power sums into device memory (to be all-reduced with SUM, then spread_finish)."""
+        self._chk(nat.lib().aqe_spread_enqueue(self._h, C.byref(query), C.c_void_p(dev_vec_ptr), C.c_void_p(stream)))
+
+    def spread_finish(self, query: Query, kind: int, dev_vec_ptr: int, stream: int = 0) -> "nat.SpreadResult":
+        out = nat.SpreadResult()
+        self._chk(nat.lib().aqe_spread_finish(self._h, C.byref(query), int(kind), C.c_void_p(dev_vec_ptr), C.c_void_p(stream), C.byref(out)))
+        return out
+
+    def reduce_grouped_spread(self, query: Query, kind: int, group_column: int, max_groups: int = 1024):
+        """GROUP BY region / product_id: list of SpreadGroupResult, ascending key, only keys with a sampled row."""
+        out = (nat.SpreadGroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_reduce_grouped_spread(self._h, C.byref(query), int(kind), int(group_column), out, max_groups, C.byref(n)))
+        return list(out[: n.value])
+
+    def grouped_spread_enqueue_bins(self, query: Query, group_column: int, key_min: int, nbins: int, dev_bins_ptr: int, stream: int = 0):
+        self._chk(nat.lib().aqe_grouped_spread_enqueue_bins(self._h, C.byref(query), int(group_column), int(key_min), int(nbins),
+                                                            C.c_void_p(dev_bins_ptr), C.c_void_p(stream)))
+
+    def grouped_spread_finish(self, query: Query, kind: int, key_min: int, nbins: int, dev_bins_ptr: int, stream: int = 0, max_groups: int = 1024):
+        out = (nat.SpreadGroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_grouped_spread_finish(self._h, C.byref(query), int(kind), int(key_min), int(nbins), C.c_void_p(dev_bins_ptr),
+                                                      C.c_void_p(stream), out, max_groups, C.byref(n)))
+        return list(out[: n.value])
+
     def gather(self, query: Query) -> np.ndarray:
         """Rows of the record-returning sampler, as a RECORD_DTYPE array."""
         n = C.c_uint64()
@@ -493,6 +527,19 @@ class Engine:
             self._chk(nat.lib().aqe_sorted_counts(self._h, v.ctypes.data_as(C.POINTER(C.c_double)), len(v),
                                                   lt.ctypes.data_as(C.POINTER(C.c_uint64)), le.ctypes.data_as(C.POINTER(C.c_uint64))))
         return lt, le
+
+
+def spread_from_sums(vec: Sequence[float], kind: int = nat.SPREAD_VAR_SAMP, confidence_level: float = 0.95, exact: bool = False) -> "nat.SpreadResult":
+    """aqe_spread_from_sums: the centring and the interval from SPREAD_VEC (summed) power sums, on the host — no GPU.  Raises
+    AqeError (ERR_INVALID, "No samples collected") when vec[0] == 0."""
+    v = [float(x) for x in vec]
+    if len(v) != nat.SPREAD_VEC:
+        raise ValueError(f"{nat.SPREAD_VEC} doubles expected: n, P1, P2, P3, P4, visited, n c, 0")
+    out = nat.SpreadResult()
+    rc = nat.lib().aqe_spread_from_sums((C.c_double * nat.SPREAD_VEC)(*v), int(kind), float(confidence_level), int(bool(exact)), C.byref(out))
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "No samples collected" if v[0] == 0 else "bad argument")
+    return out
 
 
 def _probs(probs) -> list:

@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _native as nat
 from .aqe_backend import ApproxResult, CustomBPlusDB, GroupEstimate, _AGG
-from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, shard_bounds, sharded_adaptive_plan, sharded_group_by, sharded_quantiles,
+from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, shard_bounds, sharded_adaptive_plan, sharded_group_by, sharded_group_by_spread, sharded_quantiles, sharded_spread,
                           sharded_stratified_plan, torch_all_reduce, torch_host_all_reduce)
 from .engine import RECORD_DTYPE, Batch, Engine, make_query
 
@@ -252,3 +252,18 @@ class ShardedBPlusDB(CustomBPlusDB):
         with torch.cuda.stream(self._side):
             vec = self._buffer(nat.QUANTILE_VEC_SUM + nat.QUANTILE_VEC_MAX)
             return sharded_quantiles(self._engine, q, probs, interp, vec, self._ar_sum, self._ar_max, stream=self._side.cuda_stream)
+
+    def _spread(self, q, kind):
+        """approx_spread over all ranks (collective): ONE all-reduce SUM of the 8 shifted power sums (distributed.sharded_spread)."""
+        import torch
+        self._eng()
+        with torch.cuda.stream(self._side):
+            return sharded_spread(self._engine, q, kind, self._buffer(nat.SPREAD_VEC), self._ar_sum, stream=self._side.cuda_stream)
+
+    def _spread_groups(self, q, kind, col):
+        """approx_spread(group_by=...) over all ranks: the key range is agreed, then ONE all-reduce SUM of nbins x 6 sums."""
+        import torch
+        self._eng()
+        with torch.cuda.stream(self._side):
+            bins = self._buffer(nat.SPREAD_BIN * 1024)
+            return sharded_group_by_spread(self._engine, q, kind, col, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream)

@@ -435,6 +435,73 @@ AQE_API int aqe_quantile_done(aqe_quantile* h, int* done);
 AQE_API int aqe_quantile_finish(aqe_quantile* h, aqe_quantile_result* out, void* stream);
 AQE_API void aqe_quantile_destroy(aqe_quantile* h);
 
+/* ---- spread: approximate VARIANCE / STDDEV with a fourth-moment interval --------------------------
+ * X = the sampled amounts: the rows of q's sampler inside its row window, passing the inclusive WHERE range.
+ * n = |X|, visited = sampled rows before WHERE.  With mean = sum(X)/n and M_k = sum (x - mean)^k:
+ *   AQE_SPREAD_VAR_SAMP     s^2 = M2/(n-1)        (VARIANCE, VAR_SAMP: numpy.var(X, ddof=1))
+ *   AQE_SPREAD_VAR_POP      M2/n
+ *   AQE_SPREAD_STDDEV_SAMP  sqrt(M2/(n-1))        (STDDEV, STDDEV_SAMP)
+ *   AQE_SPREAD_STDDEV_POP   sqrt(M2/n)
+ * The value is not scaled by the sampling fraction (like AVG).  Interval, large-sample normal, z from
+ * q.confidence_level as the CLT path picks it (>= 0.99: 2.576, >= 0.95: 1.96, else 1.645):
+ *   se(s^2) = sqrt(max(M4/n - (n-3)/(n-1) (s^2)^2, 0) / n); variance kinds report [max(value - z se, 0), value + z se]
+ *   (both with this se); standard deviations by the delta method, se(s) = se(s^2) / (2 s) with s = sqrt(s^2) for both
+ *   kinds, the same clamp at 0, and [0, 0] when s == 0.
+ *   AQE_M_EXACT reports [value, value].  n < 4 (n < 2 for a _SAMP value): the value as far as it is defined, NaN
+ *   bounds and has_interval = 0.  n == 0: AQE_ERR_INVALID ("No samples collected").  A non-finite amount in X gives
+ *   NaN, as numpy does.
+ * The sweep (spread.hip) accumulates the SHIFTED POWER SUMS P_k = sum (x - c)^k, k = 1..4, c the shift of
+ * AQE_MOMENT_VEC; they merge by addition, and the finish centres them: d = P1/n, M2 = P2 - n d^2,
+ * M3 = P3 - 3 d P2 + 2 n d^3, M4 = P4 - 4 d P3 + 6 d^2 P2 - 3 n d^4.  No floating-point atomics on this path: the
+ * answer of aqe_reduce_spread is bit-identical from run to run.
+ * Samplers: those the quantile path takes (single-round family samplers, row windows, the seeded AQE_M_RANDOM_POINTER);
+ * CLT, adaptive, stratified, AQE_M_RANDOM_DEVICE and pair-family samplers: AQE_ERR_UNSUPPORTED.  No error-threshold form. */
+#define AQE_SPREAD_VAR_SAMP 0
+#define AQE_SPREAD_VAR_POP 1
+#define AQE_SPREAD_STDDEV_SAMP 2
+#define AQE_SPREAD_STDDEV_POP 3
+#define AQE_SPREAD_VEC 8 /* {n, P1, P2, P3, P4, visited, n c, 0}: additive over shards (c is the same on every shard) */
+typedef struct aqe_spread_result {
+    double value, ci_lower, ci_upper;
+    double mean, m2, m3, m4;       /* mean and the centred sums M2, M3, M4 of X */
+    uint64_t n, visited;
+    int32_t has_interval;          /* 0: ci_lower / ci_upper are NaN (too few rows) */
+    int32_t device_status;
+    double kernel_ms;              /* aqe_reduce_spread: device time of the call (events around its launches) */
+} aqe_spread_result;
+AQE_API int aqe_reduce_spread(aqe_ctx* ctx, const aqe_query* q, int kind, aqe_spread_result* out);
+/* Multi-GPU form (the pattern of aqe_reduce_grouped): every rank sweeps the part of the sample in its shard,
+ *     aqe_spread_enqueue(ctx, q, dev_vec, stream)          this shard's AQE_SPREAD_VEC doubles
+ *     <all-reduce SUM of AQE_SPREAD_VEC doubles on `stream`>
+ *     aqe_spread_finish(ctx, q, kind, dev_vec, stream, &out)   synchronises `stream`
+ * aqe_reduce_spread is exactly this with a world of one (the sweep's last workgroup finishes in the same launch). */
+AQE_API int aqe_spread_enqueue(aqe_ctx* ctx, const aqe_query* q, double* dev_vec, void* stream);
+AQE_API int aqe_spread_finish(aqe_ctx* ctx, const aqe_query* q, int kind, const double* dev_vec, void* stream, aqe_spread_result* out);
+/* Host only, no GPU and no context: the centring and the interval from a (summed) vector.  AQE_ERR_INVALID when
+ * vec[0] == 0 (out is filled: NaN value and bounds). */
+AQE_API int aqe_spread_from_sums(const double vec[AQE_SPREAD_VEC], int kind, double confidence_level, int exact, aqe_spread_result* out);
+/* GROUP BY region | product_id: one bin {n, P1, P2, P3, P4, visited} per key, value and interval per group by the same
+ * finish.  Groups ascend by key; only keys with a sampled row are listed (a group with n == 0 has NaN value and bounds).
+ * Bins are summed in LDS in arrival order: reproducible to rounding, as aqe_reduce_grouped.  The seeded random sampler is
+ * not taken here (as aqe_reduce_grouped).  Multi-GPU: the key range as for aqe_grouped_enqueue_bins, then
+ *     aqe_grouped_spread_enqueue_bins(ctx, q, column, kmin, nbins, dev_bins, stream)     nbins x AQE_SPREAD_BIN doubles
+ *     <all-reduce SUM>
+ *     aqe_grouped_spread_finish(ctx, q, kind, kmin, nbins, dev_bins, stream, out, cap, &n_groups)   synchronises `stream` */
+#define AQE_SPREAD_BIN 6
+typedef struct aqe_spread_group_result {
+    int64_t key;
+    double value, ci_lower, ci_upper;
+    double mean, m2, m3, m4;
+    uint64_t n, visited;
+    int32_t has_interval, pad;
+} aqe_spread_group_result;
+AQE_API int aqe_reduce_grouped_spread(aqe_ctx* ctx, const aqe_query* q, int kind, int group_column, aqe_spread_group_result* out,
+                                      uint32_t cap, uint32_t* n_groups);
+AQE_API int aqe_grouped_spread_enqueue_bins(aqe_ctx* ctx, const aqe_query* q, int group_column, int32_t key_min, uint32_t nbins,
+                                            double* dev_bins, void* stream);
+AQE_API int aqe_grouped_spread_finish(aqe_ctx* ctx, const aqe_query* q, int kind, int32_t key_min, uint32_t nbins, const double* dev_bins,
+                                      void* stream, aqe_spread_group_result* out, uint32_t cap, uint32_t* n_groups);
+
 /* ---- stepwise / multi-GPU form ----------------------------------------------------------------
  * One process per GPU; each rank plans the same query over its own shard.  Per round:
  *     aqe_plan_enqueue_round(plan, r, dev_vec, stream)     this shard's partial moment vector
