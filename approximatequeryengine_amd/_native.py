@@ -43,6 +43,8 @@ QUANTILE_LINEAR, QUANTILE_INVERTED_CDF = 0, 1
 QUANTILE_VEC_SUM, QUANTILE_VEC_MAX = 8194, 64
 SPREAD_VAR_SAMP, SPREAD_VAR_POP, SPREAD_STDDEV_SAMP, SPREAD_STDDEV_POP = 0, 1, 2, 3
 SPREAD_VEC, SPREAD_BIN = 8, 6
+KEYTERM_NONE, KEYTERM_RANGE, KEYTERM_BITMAP = 0, 1, 2
+KEY_BITMAP_BITS = 1024
 
 
 class Query(C.Structure):
@@ -110,6 +112,15 @@ class SpreadGroupResult(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class KeyTerm(C.Structure):
+    _fields_ = [("form", C.c_int32), ("negate", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("bits", C.c_uint64 * (KEY_BITMAP_BITS // 64))]
+
+
+class KeyFilter(C.Structure):
+    """aqe_key_filter: term[0] judges region, term[1] product_id."""
+    _fields_ = [("term", KeyTerm * 2)]
 
 
 class TableInfo(C.Structure):
@@ -208,6 +219,20 @@ def lib() -> C.CDLL:
         "aqe_reduce_grouped_spread": (C.c_int, [vp, P(Query), C.c_int, C.c_int, P(SpreadGroupResult), u32, P(u32)]),
         "aqe_grouped_spread_enqueue_bins": (C.c_int, [vp, P(Query), C.c_int, C.c_int32, u32, vp, vp]),
         "aqe_grouped_spread_finish": (C.c_int, [vp, P(Query), C.c_int, C.c_int32, u32, vp, vp, P(SpreadGroupResult), u32, P(u32)]),
+        "aqe_key_term_in": (C.c_int, [P(KeyTerm), P(i32), u32, C.c_int]),
+        "aqe_key_term_range": (C.c_int, [P(KeyTerm), i32, i32, C.c_int]),
+        "aqe_parse_key_where": (C.c_int, [C.c_char_p, P(KeyFilter), C.c_char_p, C.c_size_t]),
+        "aqe_key_filter_test": (C.c_int, [P(KeyFilter), i32, i32]),
+        "aqe_reduce_filtered": (C.c_int, [vp, P(KeyFilter), P(Query), P(Result)]),
+        "aqe_reduce_filtered_spread": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, P(SpreadResult)]),
+        "aqe_reduce_filtered_grouped": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, P(GroupResult), u32, P(u32)]),
+        "aqe_reduce_filtered_grouped_spread": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, C.c_int, P(SpreadGroupResult), u32, P(u32)]),
+        "aqe_filtered_enqueue": (C.c_int, [vp, P(KeyFilter), P(Query), vp, vp]),
+        "aqe_filtered_finish": (C.c_int, [vp, P(Query), vp, vp, P(Result)]),
+        "aqe_filtered_spread_finish": (C.c_int, [vp, P(Query), C.c_int, vp, vp, P(SpreadResult)]),
+        "aqe_filtered_grouped_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, C.c_int32, u32, vp, vp]),
+        "aqe_filtered_grouped_finish": (C.c_int, [vp, P(Query), C.c_int32, u32, vp, vp, P(GroupResult), u32, P(u32)]),
+        "aqe_filtered_from_sums": (C.c_int, [P(dbl), P(Query), u64, P(Result)]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),

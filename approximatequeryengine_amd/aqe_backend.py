@@ -30,7 +30,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as nat
-from .engine import RECORD_DTYPE, Engine, make_query
+from .engine import RECORD_DTYPE, Engine, key_filter_terms, make_key_filter, make_query
 
 __all__ = ["Record", "CustomBPlusDB", "CustomApproximateScheduler", "CustomValidationResult",
            "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate", "SpreadEstimate"]
@@ -188,6 +188,33 @@ def parse_where(query: str) -> Optional[Tuple[float, float]]:
     """The amount range of a query's WHERE clause as the scheduler reads it (custom_scheduler.cpp:277-294), or None."""
     lo, hi = C.c_double(), C.c_double()
     return (lo.value, hi.value) if nat.lib().aqe_parse_where(query.encode(), C.byref(lo), C.byref(hi)) else None
+
+
+def parse_key_where(query: str) -> Optional[dict]:
+    """The key terms of a query's WHERE clause (aqe_parse_key_where; the reference's executor runs the clause as SQL,
+    executor.cpp:32-41, 68-92): ``{"region": ("in", [2]), "product_id": ("between", 10, 19)}`` — a term is ("in" | "not_in",
+    [values]) or ("between" | "not_between", lo, hi), comparisons as ranges to the int32 limits — or None when the clause names
+    neither region nor product_id.  ValueError for what is not a conjunction of at most one term per key column over int32
+    literals (OR, two terms on one column, a non-integer literal, a comparison between columns, an IN list too wide)."""
+    f = nat.KeyFilter()
+    err = C.create_string_buffer(512)
+    rc = nat.lib().aqe_parse_key_where(query.encode(), C.byref(f), err, len(err))
+    if rc == 0:
+        return None
+    if rc < 0:
+        raise ValueError(err.value.decode() or "unsupported key predicate")
+    return key_filter_terms(f)
+
+
+_NO_KEY_WHERE = ("clt", "adaptive_block", "stratified_block", "random_device")
+
+
+def _key_filter_for(key_where, method):
+    """The compiled filter of a ``key_where`` argument; the samplers without a filtered sweep are an error, not a no-op."""
+    if method in _NO_KEY_WHERE:
+        raise ValueError(f"method={method!r} has no WHERE form on region / product_id (key predicates take the single-round family "
+                         "samplers and 'random')")
+    return make_key_filter(key_where)
 
 
 def _records(arr: np.ndarray) -> List[Record]:
@@ -488,12 +515,21 @@ class CustomBPlusDB:
     def approx(self, agg: str, method: str = "stride", sample_percent: float = 10.0, error_percent: Optional[float] = None,
                where: Optional[Tuple[float, float]] = None, seed: int = 42, num_threads: int = 4, block_size: int = 1000,
                confidence_level: float = 0.95, check_interval: int = 10, round0: int = 4096, growth: int = 4,
-               convention: str = "cli", id_between: Optional[Tuple[int, int]] = None) -> ApproxResult:
+               convention: str = "cli", id_between: Optional[Tuple[int, int]] = None, key_where: Optional[dict] = None) -> ApproxResult:
         """APPROX <agg>(amount): method in {"stride","random","random_device","block","page","parallel_block","region","clt",
         "exact","adaptive_block","stratified_block"}.  "random" is random_pointer_sample(seed) bit for bit (host mt19937 +
         Lemire index list, DB.cpp:856-882); "random_device" draws a simple random sample on the device (no index list).
         ``error_percent`` (CLT) is in percent, as the reference CLI's --e (enhanced_aqe_cli.py:414-415); the
-        sample percentage then follows enhanced_aqe_cli.py:243-250."""
+        sample percentage then follows enhanced_aqe_cli.py:243-250.  ``key_where`` (parse_key_where's dictionary) keeps the
+        sampled rows whose region / product_id pass, exactly as ``where`` keeps an amount range."""
+        if key_where is not None:
+            f = _key_filter_for(key_where, method)
+            q = self._approx_query(agg, method, sample_percent, error_percent, where, seed, num_threads, block_size, confidence_level,
+                                   check_interval, round0, growth, convention, id_between)
+            res = _quantile_call(lambda: self._reduce_filtered(f, q))
+            if res.visited == 0:
+                raise RuntimeError("No samples collected")
+            return ApproxResult(res, method)
         q = self._approx_query(agg, method, sample_percent, error_percent, where, seed, num_threads, block_size, confidence_level,
                                check_interval, round0, growth, convention, id_between)
         res = self._reduce(q)
@@ -550,10 +586,13 @@ class CustomBPlusDB:
         from .engine import Batch
         eng = self._eng()
         specs = [dict(kw) for kw in queries]
-        qs = [self._approx_query(**kw) for kw in specs]
+        keyed = {i for i, kw in enumerate(specs) if kw.get("key_where") is not None}  # entries with a key predicate run on their own
+        qs = [None if i in keyed else self._approx_query(**kw) for i, kw in enumerate(specs)]
         out: "List[Optional[ApproxResult]]" = [None] * len(qs)
-        fused = [i for i, kw in enumerate(specs) if kw.get("method", "stride") not in ("random", "random_device", "direct_access", "sequential")]
-        for i in set(range(len(qs))) - set(fused):
+        for i in keyed:
+            out[i] = self.approx(**specs[i])
+        fused = [i for i, kw in enumerate(specs) if i not in keyed and kw.get("method", "stride") not in ("random", "random_device", "direct_access", "sequential")]
+        for i in set(range(len(qs))) - set(fused) - keyed:
             out[i] = ApproxResult(self._reduce(qs[i]), specs[i].get("method", "stride"))
         if fused:
             plans = [eng.plan(qs[i]) for i in fused]
@@ -574,7 +613,8 @@ class CustomBPlusDB:
         return out
 
     def approx_group_by(self, agg: str, group_by: str = "region", sample_percent: float = 10.0, method: str = "rowid",
-                        where: Optional[Tuple[float, float]] = None, block_size: int = 1000) -> "dict[str, GroupEstimate]":
+                        where: Optional[Tuple[float, float]] = None, block_size: int = 1000,
+                        key_where: Optional[dict] = None) -> "dict[str, GroupEstimate]":
         """APPROX <agg>(amount) ... GROUP BY region | product_id with a 95 % interval per group: the reference's
         execute_query_groupby_with_ci (executor.cpp:202-321; GroupResultWithCI = map<string, {value, ci_lower,
         ci_upper}>) in one sweep.  method "rowid" is that function's own sample (rowid % (100 / sample_percent) == 0);
@@ -586,7 +626,22 @@ class CustomBPlusDB:
             return {}
         bs = 4096 if (method == "page" and block_size == 1000) else block_size
         q = make_query(m, sample_percent, agg=_AGG[agg.upper()], where=where, block_size=int(bs))
+        if key_where is not None:  # a sampled group nothing of which passes is listed with n == 0
+            f = _key_filter_for(key_where, method)
+            return {str(r.key): GroupEstimate(r) for r in _quantile_call(lambda: self._grouped_filtered(f, q, col))}
         return {str(r.key): GroupEstimate(r) for r in self._eng().reduce_grouped(q, col)}
+
+    def _reduce_filtered(self, f, q):
+        return self._eng().reduce_filtered(f, q)
+
+    def _grouped_filtered(self, f, q, col):
+        return self._eng().reduce_filtered_grouped(f, q, col)
+
+    def _spread_filtered(self, f, q, kind):
+        return self._eng().reduce_filtered_spread(f, q, kind)
+
+    def _spread_groups_filtered(self, f, q, kind, col):
+        return self._eng().reduce_filtered_grouped_spread(f, q, kind, col)
 
     def _quantile_query(self, method="stride", sample_percent=10.0, where=None, id_between=None, interpolation="linear",
                         confidence_level=0.95, seed=42, num_threads=4, block_size=1000):
@@ -602,12 +657,14 @@ class CustomBPlusDB:
 
     def approx_quantile(self, p, method: str = "stride", sample_percent: float = 10.0, where: Optional[Tuple[float, float]] = None,
                         id_between: Optional[Tuple[int, int]] = None, interpolation: str = "linear", confidence_level: float = 0.95,
-                        seed: int = 42, num_threads: int = 4, block_size: int = 1000):
+                        seed: int = 42, num_threads: int = 4, block_size: int = 1000, key_where: Optional[dict] = None):
         """APPROX PERCENTILE(amount, p): numpy.quantile(X, p, method=interpolation) of the sampled amounts X (WHERE and the key
         window applied, NaN rows left out) with a distribution-free interval from order statistics.  ``p`` is one probability
         or a list of up to 8 (answered from the same sample in the same sweeps); the result is a QuantileEstimate or a list.
         interpolation "linear" is PERCENTILE_CONT, "inverted_cdf" PERCENTILE_DISC.  method: "exact", "stride", "block", "page",
         "parallel_block", "region", "random" ... (CLT, adaptive, stratified and random_device samplers raise ValueError)."""
+        if key_where is not None:
+            raise ValueError("quantiles under a key predicate (key_where) are not supported yet")
         single = not isinstance(p, (list, tuple, np.ndarray))
         probs = [float(p)] if single else [float(v) for v in p]
         if not probs or len(probs) > nat.MAX_QUANTILES or any(not (0.0 <= v <= 1.0) for v in probs):
@@ -627,7 +684,8 @@ class CustomBPlusDB:
 
     def approx_spread(self, kind: str = "var_samp", method: str = "stride", sample_percent: float = 10.0,
                       where: Optional[Tuple[float, float]] = None, id_between: Optional[Tuple[int, int]] = None, seed: int = 42,
-                      confidence_level: float = 0.95, group_by: Optional[str] = None, num_threads: int = 4, block_size: int = 1000):
+                      confidence_level: float = 0.95, group_by: Optional[str] = None, num_threads: int = 4, block_size: int = 1000,
+                      key_where: Optional[dict] = None):
         """APPROX VARIANCE / STDDEV(amount): ``kind`` is "var_samp" ("variance"), "var_pop", "stddev_samp" ("stddev") or
         "stddev_pop" of the sampled amounts X (WHERE and the key window applied) — numpy.var(X, ddof=1) and its kin, not scaled
         by the sampling fraction — with a large-sample normal interval from the fourth central moment; method "exact" reports
@@ -639,6 +697,7 @@ class CustomBPlusDB:
             raise ValueError(f"kind must be one of {sorted(_SPREAD_KINDS)}")
         if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
             raise ValueError(f"VARIANCE / STDDEV do not take the {method} sampler (single-round family samplers and 'random' only)")
+        f = None if key_where is None else _key_filter_for(key_where, method)
         col = None
         if group_by is not None:
             col = {"region": nat.GROUP_REGION, "product_id": nat.GROUP_PRODUCT}[group_by.strip().lower()]
@@ -654,6 +713,11 @@ class CustomBPlusDB:
             q = self._approx_query("SUM", method, sample_percent, None, where, seed, num_threads, block_size, confidence_level,
                                    id_between=id_between)
         q.confidence_level = float(confidence_level)
+        if f is not None:  # under a key predicate (a sample nothing of which passes: n == 0, NaN value, no interval)
+            if col is not None:
+                groups = _quantile_call(lambda: self._spread_groups_filtered(f, q, _SPREAD_KINDS[k], col))
+                return {str(r.key): SpreadEstimate(r, k, method) for r in groups}
+            return SpreadEstimate(_quantile_call(lambda: self._spread_filtered(f, q, _SPREAD_KINDS[k])), k, method)
         if col is not None:
             groups = _quantile_call(lambda: self._spread_groups(q, _SPREAD_KINDS[k], col))
             return {str(r.key): SpreadEstimate(r, k, method) for r in groups}

@@ -7,6 +7,7 @@
     python -m approximatequeryengine_amd.cli "SELECT MEDIAN(amount) FROM sales" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli "SELECT PERCENTILE_DISC(amount, 0.99) FROM sales" --db sales.db --compare
     python -m approximatequeryengine_amd.cli "SELECT STDDEV(amount) FROM sales GROUP BY region" --db sales.db --s 10 --ci
+    python -m approximatequeryengine_amd.cli "SELECT SUM(amount) FROM sales WHERE region = 2 AND product_id BETWEEN 10 AND 19" --db sales.db --s 10
     python -m approximatequeryengine_amd.cli --explain
 
 The reference's own CLI defines `-s/--sample` and `-e/--error` but tests `args.s` / `args.e`
@@ -95,6 +96,23 @@ def spread_of(query: str) -> Optional[Tuple[str, str]]:
     return _SPREAD_FUNCS[m.group(1).upper()], m.group(1).upper()
 
 
+def where_clause_of(query: str) -> Optional[str]:
+    """The text of the query's WHERE clause (up to GROUP BY / ORDER BY / LIMIT), or None."""
+    m = re.search(r"\bWHERE\b(.*?)(?=\bGROUP\s+BY\b|\bORDER\s+BY\b|\bLIMIT\b|\bHAVING\b|;|$)", query, re.IGNORECASE | re.DOTALL)
+    return m.group(1).strip() if m else None
+
+
+def key_where_of(query: str) -> Optional[dict]:
+    """The key predicate of the (unwrapped) query — aqe_backend.parse_key_where's dictionary — or None when its WHERE clause
+    names neither region nor product_id (such a query runs exactly as it did).  ValueError for a key term outside the supported
+    forms."""
+    clause = where_clause_of(query)
+    if clause is None or not re.search(r"\b(region|product_id)\b", clause, re.IGNORECASE):
+        return None
+    from . import aqe_backend
+    return aqe_backend.parse_key_where(query)
+
+
 def determine_query_type(query: str, args) -> str:
     """enhanced_aqe_cli.py:97-114 with the attribute names fixed."""
     if parse_embedded_approx(query)[1]:
@@ -163,6 +181,20 @@ def run(args, out=sys.stdout) -> int:
     if spread_of(clean) is not None and args.e is not None:
         print("error: VARIANCE / STDDEV have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
         return 2
+    try:
+        key_where = key_where_of(clean)
+    except ValueError as e:
+        print(f"error: {e}", file=out)
+        return 2
+    if key_where is not None:
+        clause = where_clause_of(clean)
+        if args.e is not None:
+            print(f"error: the CLT sampler (--e) samples the whole table and has no form for the key predicate 'WHERE {clause}': "
+                  "give a sample percentage (--s) or none (exact)", file=out)
+            return 2
+        if quant is not None:
+            print(f"error: MEDIAN / PERCENTILE under the key predicate 'WHERE {clause}' are not supported yet", file=out)
+            return 2
     if not os.path.exists(args.db):
         print(f"error: database file '{args.db}' not found", file=out)
         return 1
@@ -206,18 +238,22 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     db._path = ""  # a read-only session must not rewrite the file on close
     n = db.get_total_records()
     print(f"query: {args.query}\ndatabase: {args.db} ({n:,} records{', ' + sharded_note if sharded_note else ''})\ntype: {qtype}", file=out)
+    key_where = key_where_of(clean)
+    kw = {} if key_where is None else {"key_where": key_where}  # (passed only when there is a key predicate)
+    if key_where is not None:
+        print(f"predicate: WHERE {where_clause_of(clean)}", file=out)
     t0 = time.perf_counter()
     quant = quantile_of(clean)
     if quant is not None:
         return _run_quantile(db, args, out, clean, qtype, quant, aqe_backend, t0)
     spread = spread_of(clean)
     if spread is not None:
-        return _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0)
+        return _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0, kw)
     gb = re.search(r"GROUP\s+BY\s+(region|product_id)\b", clean, flags=re.IGNORECASE)
     if gb:  # one sweep, one (n, S, Q) bin per key, an interval per group (executor.cpp:202-321 semantics)
         pct = args.s if args.s is not None else (100.0 if qtype == QUERY_EXACT else 10.0)
         groups = db.approx_group_by(agg, group_by=gb.group(1), sample_percent=pct, method="exact" if pct >= 100.0 else "rowid",
-                                    where=aqe_backend.parse_where(clean))
+                                    where=aqe_backend.parse_where(clean), **kw)
         ms = (time.perf_counter() - t0) * 1e3
         print(f"\nGROUP BY {gb.group(1).lower()} ({'exact' if pct >= 100.0 else f'rowid sample {pct:g}%'}):", file=out)
         for key, g in groups.items():
@@ -230,6 +266,9 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
         method = args.method or get_optimal_method_for_query(clean, n)
         qtype = QUERY_CLT if method == "clt" else QUERY_RANDOM  # enhanced_aqe_cli.py:489-494
         e, s = 2.0, 10.0
+        if qtype == QUERY_CLT and key_where is not None:
+            print("note: the CLT sampler has no form for a key predicate (it samples the whole table): the query takes the sampled path (10%)", file=out)
+            qtype = QUERY_RANDOM
     else:
         e, s = args.e if args.e is not None else 5.0, args.s if args.s is not None else 10.0
     # `WHERE amount BETWEEN a AND b` / `>= a AND <= b` / `> a` (the façade's extraction, custom_scheduler.cpp:277-294) is
@@ -240,7 +279,7 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
         # above 50 k rows, direct access above 10 k, the sequential sampler below
         auto = "stride" if n > 50_000 else "direct_access" if n > 10_000 else "sequential"
         m = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", auto)
-        res = db.approx(agg, method=m, sample_percent=s, seed=args.seed, num_threads=args.threads, where=where)
+        res = db.approx(agg, method=m, sample_percent=s, seed=args.seed, num_threads=args.threads, where=where, **kw)
         name = f"{m} sampling ({s}%)"
     elif qtype == QUERY_CLT:
         if where is not None:
@@ -249,7 +288,7 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
         res = db.approx(agg, method="clt", error_percent=e, num_threads=args.threads, confidence_level=args.confidence)
         name = f"CLT (±{e}%)"
     else:
-        res = db.approx(agg, method="exact", where=where)
+        res = db.approx(agg, method="exact", where=where, **kw)
         name = "exact"
     ms = (time.perf_counter() - t0) * 1e3
     print(f"\n{name} result:\n   value: {res.value:,.4f}", file=out)
@@ -258,7 +297,7 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     print(f"   samples used: {res.n:,}   rounds: {res.rounds}   converged: {bool(res.converged)}", file=out)
     print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us, {res.achieved_GBps:.0f} GB/s algorithmic)", file=out)
     if args.compare and qtype != QUERY_EXACT:
-        exact = db.approx(agg, method="exact", where=where)
+        exact = db.approx(agg, method="exact", where=where, **kw)
         print(f"\ncomparison:\n   approximate: {res.value:,.4f}\n   exact:       {exact.value:,.4f}", file=out)
         if exact.value != 0:
             print(f"   actual error: {abs(res.value - exact.value) / abs(exact.value) * 100:.4f}%", file=out)
@@ -295,11 +334,12 @@ def _run_quantile(db, args, out, clean, qtype, quant, aqe_backend, t0) -> int:
     return 0
 
 
-def _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0) -> int:
+def _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0, kw=None) -> int:
     """VARIANCE / VAR_SAMP / VAR_POP / STDDEV / STDDEV_SAMP / STDDEV_POP: exact without --s; with --s (or an APPROX(...)
     wrapper) a sample — --method block / parallel / random honoured, stride otherwise; GROUP BY region | product_id samples by
     rowid, as the SUM / AVG / COUNT form does."""
     kind, fname = spread
+    kw = kw or {}  # {"key_where": ...} when the WHERE clause names region / product_id
     where = aqe_backend.parse_where(clean)
     gb = re.search(r"GROUP\s+BY\s+(region|product_id)\b", clean, flags=re.IGNORECASE)
     if args.s is None and qtype != QUERY_EMBEDDED:
@@ -314,7 +354,7 @@ def _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0) -> int:
     fmt = lambda v: "n/a" if v != v else f"{v:,.4f}"
     if gb:
         groups = db.approx_spread(kind, method=method, sample_percent=pct, where=where, confidence_level=args.confidence,
-                                  group_by=gb.group(1))
+                                  group_by=gb.group(1), **kw)
         ms = (time.perf_counter() - t0) * 1e3
         print(f"\n{fname}(amount) GROUP BY {gb.group(1).lower()} ({name}):", file=out)
         for key, g in groups.items():
@@ -324,7 +364,7 @@ def _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0) -> int:
         db.close_database()
         return 0
     res = db.approx_spread(kind, method=method, sample_percent=pct, where=where, confidence_level=args.confidence, seed=args.seed,
-                           num_threads=args.threads)
+                           num_threads=args.threads, **kw)
     ms = (time.perf_counter() - t0) * 1e3
     print(f"\n{name} {fname}(amount) result:\n   value: {fmt(res.value)}", file=out)
     if args.ci and method != "exact":
@@ -332,7 +372,7 @@ def _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0) -> int:
     print(f"   samples used: {res.n:,}   mean: {res.mean:,.4f}", file=out)
     print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
     if args.compare and method != "exact":
-        exact = db.approx_spread(kind, method="exact", where=where)
+        exact = db.approx_spread(kind, method="exact", where=where, **kw)
         print(f"\ncomparison:\n   approximate: {fmt(res.value)}\n   exact:       {fmt(exact.value)}", file=out)
         if exact.value != 0:
             print(f"   actual error: {abs(res.value - exact.value) / abs(exact.value) * 100:.4f}%", file=out)

@@ -99,7 +99,7 @@ struct Acc {
 // the shifted-data form of the running mean/variance (Chan, Golub & LeVeque 1983), and unlike Welford's
 // recurrence its partial states merge by plain addition — which is what lets workgroups, rounds and GPUs
 // (one all-reduce SUM) combine in any grouping.
-__device__ __forceinline__ void mean_m2(double n, double sd, double qd, double c, double& mean, double& m2) {
+__host__ __device__ __forceinline__ void mean_m2(double n, double sd, double qd, double c, double& mean, double& m2) {
     mean = c + sd / n;
     m2 = qd - sd * sd / n;
     if (m2 < 0.0) m2 = 0.0;
@@ -190,7 +190,7 @@ __device__ __forceinline__ void fold(QueryState& s, const double (&vec)[kVec], c
 }
 
 // Estimate + interval from the folded state (CLI:189-200, 277-291; DB.cpp:303-315).
-__device__ __forceinline__ aqe_result make_result(const QueryState& s, const FinalizeParams& p) {
+__host__ __device__ __forceinline__ aqe_result make_result(const QueryState& s, const FinalizeParams& p) {
     aqe_result r;
     const double n = s.n_p, visited = s.visited, c = p.shift;
     double mean = 0.0, m2 = 0.0;

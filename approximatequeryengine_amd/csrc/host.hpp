@@ -92,6 +92,7 @@ struct StageRing {
 };
 
 struct aqe_spread_scratch;  // spread.hip
+struct aqe_filter_scratch;  // filter.hip
 
 struct aqe_ctx {
     StageRing ring;
@@ -154,6 +155,8 @@ struct aqe_ctx {
     double qrange_lo = 0.0, qrange_hi = 0.0;
     // VARIANCE / STDDEV (spread.hip): partials, tickets, pinned results of the spread entries, made on first use
     aqe_spread_scratch* spread = nullptr;
+    // key predicates (filter.hip): partials, tickets, pinned results of the filtered entries, made on first use
+    aqe_filter_scratch* filter = nullptr;
 };
 
 // One persistent-sweep form of a plan's rounds (persist.hip): the tile list of all slots, who owns tiles
@@ -286,6 +289,9 @@ void quantile_release(aqe_ctx* c);
 
 // spread.hip
 void spread_release(aqe_ctx* c);
+
+// filter.hip
+void filter_release(aqe_ctx* c);
 
 // plans.hip
 void destroy_plan(aqe_plan* p, bool device_idle = false);  // device_idle: the caller has just synchronised the device

@@ -347,6 +347,53 @@ def sharded_group_by_spread(engine, query, kind: int, group_column: int, bins, a
         return engine.grouped_spread_finish(query, kind, kmin, nbins, b.data_ptr(), stream)
 
 
+def sharded_filtered(engine, key_filter, query, vec, all_reduce_sum: Callable, stream: int = 0, kind=None):
+    """SUM / AVG / COUNT (kind None) or VARIANCE / STDDEV (kind = SPREAD_*) under a key filter across the ranks of a process
+    group, collective: every rank sweeps the part of the sample inside its shard into SPREAD_VEC shifted power sums of the rows
+    that pass (aqe_filtered_enqueue), ONE all-reduce SUM merges them and every rank finishes the same vector.
+
+    vec     float64 tensor on the engine's device with room for SPREAD_VEC doubles
+    stream  raw handle of the stream the collective is issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    from ._native import SPREAD_VEC
+    stream = _stream_for(stream, vec)
+    if vec.numel() < SPREAD_VEC:
+        raise ValueError(f"vector holds {vec.numel()} doubles, {SPREAD_VEC} needed")
+    with _torch_on(stream, vec):
+        v = vec[:SPREAD_VEC]
+        engine.filtered_enqueue(key_filter, query, v.data_ptr(), stream)
+        all_reduce_sum(v)
+        if kind is None:
+            return engine.filtered_finish(query, v.data_ptr(), stream)
+        return engine.filtered_spread_finish(query, kind, v.data_ptr(), stream)
+
+
+def sharded_filtered_group_by(engine, key_filter, query, group_column: int, bins, all_reduce_sum: Callable, all_reduce_max: Callable,
+                              stream: int = 0, kind=None):
+    """GROUP BY under a key filter across ranks: the key range is agreed (one MAX all-reduce of [-min, max], as sharded_group_by),
+    every rank bins its part of the sample into nbins x SPREAD_BIN sums (aqe_filtered_grouped_enqueue_bins), ONE all-reduce SUM
+    merges them; kind None finishes SUM / AVG / COUNT per group, kind = SPREAD_* VARIANCE / STDDEV per group.
+
+    bins    float64 tensor on the engine's device with room for SPREAD_BIN * (number of distinct keys) doubles"""
+    from ._native import SPREAD_BIN
+    stream = _stream_for(stream, bins)
+    with _torch_on(stream, bins):
+        lo, hi = engine.group_key_range(group_column)
+        rng = bins.new_tensor([-float(lo), float(hi)])
+        all_reduce_max(rng)
+        kmin, kmax = -int(rng[0].item()), int(rng[1].item())
+        if kmax < kmin:
+            return []  # an empty table
+        nbins = kmax - kmin + 1
+        if bins.numel() < SPREAD_BIN * nbins:
+            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {SPREAD_BIN * nbins} needed")
+        b = bins[: SPREAD_BIN * nbins]
+        engine.filtered_grouped_enqueue_bins(key_filter, query, group_column, kmin, nbins, b.data_ptr(), stream)
+        all_reduce_sum(b)
+        if kind is None:
+            return engine.filtered_grouped_finish(query, kmin, nbins, b.data_ptr(), stream)
+        return engine.grouped_spread_finish(query, kind, kmin, nbins, b.data_ptr(), stream)
+
+
 # ---- the variance-aware samplers over a sharded table (SURVEY 8e "what does not shard") ---------------------------------
 # Both need one fact about the WHOLE table before a shard can plan (include/aqe_hip.h, the block above aqe_zone_moments).
 # The exchanges below are small host arrays, once per table and query shape — `host_all_reduce_sum(a) -> a summed over the

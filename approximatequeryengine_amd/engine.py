@@ -486,6 +486,58 @@ class Engine:
                                                       C.c_void_p(stream), out, max_groups, C.byref(n)))
         return list(out[: n.value])
 
+    # -- key predicates: WHERE on region / product_id (aqe_reduce_filtered and its kin; filter.hip) --
+    def reduce_filtered(self, key_filter: "nat.KeyFilter", query: Query) -> Result:
+        """SUM / AVG / COUNT over the sampled rows that pass the key filter (and the query's amount range)."""
+        res = Result()
+        self._chk(nat.lib().aqe_reduce_filtered(self._h, C.byref(key_filter), C.byref(query), C.byref(res)))
+        return res
+
+    def reduce_filtered_spread(self, key_filter: "nat.KeyFilter", query: Query, kind: int = nat.SPREAD_VAR_SAMP) -> "nat.SpreadResult":
+        out = nat.SpreadResult()
+        self._chk(nat.lib().aqe_reduce_filtered_spread(self._h, C.byref(key_filter), C.byref(query), int(kind), C.byref(out)))
+        return out
+
+    def reduce_filtered_grouped(self, key_filter: "nat.KeyFilter", query: Query, group_column: int, max_groups: int = 1024):
+        """GROUP BY under a key filter: list of GroupResult, ascending key; a sampled group nothing of which passes has n == 0."""
+        out = (nat.GroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_reduce_filtered_grouped(self._h, C.byref(key_filter), C.byref(query), int(group_column), out, max_groups, C.byref(n)))
+        return list(out[: n.value])
+
+    def reduce_filtered_grouped_spread(self, key_filter: "nat.KeyFilter", query: Query, kind: int, group_column: int, max_groups: int = 1024):
+        out = (nat.SpreadGroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_reduce_filtered_grouped_spread(self._h, C.byref(key_filter), C.byref(query), int(kind), int(group_column), out,
+                                                               max_groups, C.byref(n)))
+        return list(out[: n.value])
+
+    def filtered_enqueue(self, key_filter: "nat.KeyFilter", query: Query, dev_vec_ptr: int, stream: int = 0):
+        """This shard's SPREAD_VEC power sums of the rows that pass, into device memory (all-reduce SUM, then a finish)."""
+        self._chk(nat.lib().aqe_filtered_enqueue(self._h, C.byref(key_filter), C.byref(query), C.c_void_p(dev_vec_ptr), C.c_void_p(stream)))
+
+    def filtered_finish(self, query: Query, dev_vec_ptr: int, stream: int = 0) -> Result:
+        res = Result()
+        self._chk(nat.lib().aqe_filtered_finish(self._h, C.byref(query), C.c_void_p(dev_vec_ptr), C.c_void_p(stream), C.byref(res)))
+        return res
+
+    def filtered_spread_finish(self, query: Query, kind: int, dev_vec_ptr: int, stream: int = 0) -> "nat.SpreadResult":
+        out = nat.SpreadResult()
+        self._chk(nat.lib().aqe_filtered_spread_finish(self._h, C.byref(query), int(kind), C.c_void_p(dev_vec_ptr), C.c_void_p(stream), C.byref(out)))
+        return out
+
+    def filtered_grouped_enqueue_bins(self, key_filter: "nat.KeyFilter", query: Query, group_column: int, key_min: int, nbins: int,
+                                      dev_bins_ptr: int, stream: int = 0):
+        self._chk(nat.lib().aqe_filtered_grouped_enqueue_bins(self._h, C.byref(key_filter), C.byref(query), int(group_column), int(key_min),
+                                                              int(nbins), C.c_void_p(dev_bins_ptr), C.c_void_p(stream)))
+
+    def filtered_grouped_finish(self, query: Query, key_min: int, nbins: int, dev_bins_ptr: int, stream: int = 0, max_groups: int = 1024):
+        out = (nat.GroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_filtered_grouped_finish(self._h, C.byref(query), int(key_min), int(nbins), C.c_void_p(dev_bins_ptr),
+                                                        C.c_void_p(stream), out, max_groups, C.byref(n)))
+        return list(out[: n.value])
+
     def gather(self, query: Query) -> np.ndarray:
         """Rows of the record-returning sampler, as a RECORD_DTYPE array."""
         n = C.c_uint64()
@@ -539,6 +591,78 @@ def spread_from_sums(vec: Sequence[float], kind: int = nat.SPREAD_VAR_SAMP, conf
     rc = nat.lib().aqe_spread_from_sums((C.c_double * nat.SPREAD_VEC)(*v), int(kind), float(confidence_level), int(bool(exact)), C.byref(out))
     if rc != nat.OK:
         raise nat.AqeError(rc, "No samples collected" if v[0] == 0 else "bad argument")
+    return out
+
+
+_KEY_COLUMNS = ("region", "product_id")
+_INT32_MIN, _INT32_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def make_key_filter(key_where) -> "nat.KeyFilter":
+    """aqe_key_filter from ``{"region": term, "product_id": term}`` (either may be missing).  A term is ("in", [v, ...]),
+    ("not_in", [v, ...]), ("between", lo, hi), ("not_between", lo, hi) — what aqe_backend.parse_key_where returns — with
+    int32 values; a nat.KeyFilter is passed through.  ValueError for anything else, and for an IN list spanning more than
+    KEY_BITMAP_BITS keys."""
+    if isinstance(key_where, nat.KeyFilter):
+        return key_where
+    if not isinstance(key_where, dict) or not key_where:
+        raise ValueError("key_where is a dict with a term for 'region' and / or 'product_id'")
+    f = nat.KeyFilter()
+    for col, term in key_where.items():
+        name = str(col).strip().lower()
+        if name not in _KEY_COLUMNS:
+            raise ValueError(f"key_where: unknown key column {col!r} (region, product_id)")
+        t = f.term[_KEY_COLUMNS.index(name)]
+        form = str(term[0]).lower() if isinstance(term, (tuple, list)) and term else ""
+        if form in ("in", "not_in") and len(term) == 2 and len(term[1]) > 0:
+            vals = [int(v) for v in term[1]]
+            if any(v < _INT32_MIN or v > _INT32_MAX for v in vals):
+                raise ValueError(f"key_where[{name!r}]: values must fit int32")
+            rc = nat.lib().aqe_key_term_in(C.byref(t), (C.c_int32 * len(vals))(*vals), len(vals), int(form == "not_in"))
+            if rc == nat.ERR_UNSUPPORTED:
+                raise ValueError(f"key_where[{name!r}]: the IN list spans more than {nat.KEY_BITMAP_BITS} consecutive key values")
+            nat.check(rc)
+        elif form in ("between", "not_between") and len(term) == 3:
+            lo, hi = int(term[1]), int(term[2])
+            if lo < _INT32_MIN or lo > _INT32_MAX or hi < _INT32_MIN or hi > _INT32_MAX:
+                raise ValueError(f"key_where[{name!r}]: bounds must fit int32")
+            if lo > hi:
+                lo, hi = 1, 0  # no key
+            nat.check(nat.lib().aqe_key_term_range(C.byref(t), lo, hi, int(form == "not_between")))
+        else:
+            raise ValueError(f"key_where[{name!r}]: a term is ('in' | 'not_in', [values]) or ('between' | 'not_between', lo, hi), got {term!r}")
+    return f
+
+
+def key_filter_terms(f: "nat.KeyFilter") -> dict:
+    """The dictionary form of a compiled filter (the inverse of make_key_filter)."""
+    out = {}
+    for name, t in zip(_KEY_COLUMNS, f.term):
+        if t.form == nat.KEYTERM_RANGE:
+            if t.lo == t.hi:
+                out[name] = ("not_in" if t.negate else "in", [t.lo])
+            else:
+                out[name] = ("not_between" if t.negate else "between", t.lo, t.hi)
+        elif t.form == nat.KEYTERM_BITMAP:
+            vals = [t.lo + u for u in range(t.hi - t.lo + 1) if (t.bits[u >> 6] >> (u & 63)) & 1]
+            out[name] = ("not_in" if t.negate else "in", vals)
+    return out
+
+
+def key_filter_test(f: "nat.KeyFilter", region: int, product_id: int) -> bool:
+    """aqe_key_filter_test: whether a row with these keys passes — the test the kernels apply, on the host."""
+    return bool(nat.lib().aqe_key_filter_test(C.byref(f), int(region), int(product_id)))
+
+
+def filtered_from_sums(vec: Sequence[float], query: Query, n_global: int) -> Result:
+    """aqe_filtered_from_sums: SUM / AVG / COUNT with its interval from SPREAD_VEC (summed) power sums, on the host — no GPU."""
+    v = [float(x) for x in vec]
+    if len(v) != nat.SPREAD_VEC:
+        raise ValueError(f"{nat.SPREAD_VEC} doubles expected: n, P1, P2, P3, P4, visited, n c, 0")
+    out = Result()
+    rc = nat.lib().aqe_filtered_from_sums((C.c_double * nat.SPREAD_VEC)(*v), C.byref(query), int(n_global), C.byref(out))
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "No samples collected" if v[5] == 0 else "bad argument")
     return out
 
 

@@ -25,8 +25,8 @@ from typing import List, Optional
 import numpy as np
 
 from . import _native as nat
-from .aqe_backend import ApproxResult, CustomBPlusDB, GroupEstimate, _AGG
-from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, shard_bounds, sharded_adaptive_plan, sharded_group_by, sharded_group_by_spread, sharded_quantiles, sharded_spread,
+from .aqe_backend import ApproxResult, CustomBPlusDB, GroupEstimate, _AGG, _key_filter_for, _quantile_call
+from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, shard_bounds, sharded_adaptive_plan, sharded_group_by, sharded_filtered, sharded_filtered_group_by, sharded_group_by_spread, sharded_quantiles, sharded_spread,
                           sharded_stratified_plan, torch_all_reduce, torch_host_all_reduce)
 from .engine import RECORD_DTYPE, Batch, Engine, make_query
 
@@ -204,10 +204,13 @@ class ShardedBPlusDB(CustomBPlusDB):
         import torch
         self._eng()
         specs = [dict(kw) for kw in queries]
-        qs = [self._approx_query(**kw) for kw in specs]
-        plans = [self._plan_for(q) for q in qs]
+        keyed = {i for i, kw in enumerate(specs) if kw.get("key_where") is not None}  # entries with a key predicate run on their own
+        qs = [None if i in keyed else self._approx_query(**kw) for i, kw in enumerate(specs)]
+        plans = [None if q is None else self._plan_for(q) for q in qs]
         out: "List[Optional[ApproxResult]]" = [None] * len(qs)
-        fused = [i for i, p in enumerate(plans) if p.totals_len > 0]
+        for i in sorted(keyed):
+            out[i] = self.approx(**specs[i])
+        fused = [i for i, p in enumerate(plans) if p is not None and p.totals_len > 0]
         with torch.cuda.stream(self._side):
             if len(fused) >= 2:
                 ps = [plans[i] for i in fused]
@@ -229,7 +232,7 @@ class ShardedBPlusDB(CustomBPlusDB):
         return out
 
     def approx_group_by(self, agg: str, group_by: str = "region", sample_percent: float = 10.0, method: str = "rowid",
-                        where=None, block_size: int = 1000) -> "dict[str, GroupEstimate]":
+                        where=None, block_size: int = 1000, key_where=None) -> "dict[str, GroupEstimate]":
         """GROUP BY over all ranks: the key range is agreed (one MAX all-reduce), every rank bins the part of the sample inside
         its region, ONE all-reduce SUM merges the bins (distributed.sharded_group_by)."""
         import torch
@@ -238,6 +241,9 @@ class ShardedBPlusDB(CustomBPlusDB):
         self._eng()
         bs = 4096 if (method == "page" and block_size == 1000) else block_size
         q = make_query(m, sample_percent, agg=_AGG[agg.upper()], where=where, block_size=int(bs))
+        if key_where is not None:
+            f = _key_filter_for(key_where, method)
+            return {str(r.key): GroupEstimate(r) for r in _quantile_call(lambda: self._grouped_filtered(f, q, col))}
         with torch.cuda.stream(self._side):
             if self._bins is None:
                 self._bins = torch.zeros(4 * 4096, dtype=torch.float64, device=self._dev)
@@ -267,3 +273,30 @@ class ShardedBPlusDB(CustomBPlusDB):
         with torch.cuda.stream(self._side):
             bins = self._buffer(nat.SPREAD_BIN * 1024)
             return sharded_group_by_spread(self._engine, q, kind, col, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream)
+
+    # ---- key predicates (WHERE on region / product_id): the filtered sweeps over all ranks, one all-reduce SUM each ----
+    def _reduce_filtered(self, f, q):
+        import torch
+        self._eng()
+        with torch.cuda.stream(self._side):
+            return sharded_filtered(self._engine, f, q, self._buffer(nat.SPREAD_VEC), self._ar_sum, stream=self._side.cuda_stream)
+
+    def _spread_filtered(self, f, q, kind):
+        import torch
+        self._eng()
+        with torch.cuda.stream(self._side):
+            return sharded_filtered(self._engine, f, q, self._buffer(nat.SPREAD_VEC), self._ar_sum, stream=self._side.cuda_stream, kind=kind)
+
+    def _grouped_filtered(self, f, q, col):
+        import torch
+        self._eng()
+        with torch.cuda.stream(self._side):
+            bins = self._buffer(nat.SPREAD_BIN * 1024)
+            return sharded_filtered_group_by(self._engine, f, q, col, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream)
+
+    def _spread_groups_filtered(self, f, q, kind, col):
+        import torch
+        self._eng()
+        with torch.cuda.stream(self._side):
+            bins = self._buffer(nat.SPREAD_BIN * 1024)
+            return sharded_filtered_group_by(self._engine, f, q, col, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, kind=kind)

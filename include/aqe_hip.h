@@ -502,6 +502,87 @@ AQE_API int aqe_grouped_spread_enqueue_bins(aqe_ctx* ctx, const aqe_query* q, in
 AQE_API int aqe_grouped_spread_finish(aqe_ctx* ctx, const aqe_query* q, int kind, int32_t key_min, uint32_t nbins, const double* dev_bins,
                                       void* stream, aqe_spread_group_result* out, uint32_t cap, uint32_t* n_groups);
 
+/* ---- key predicates: WHERE on region and product_id ----------------------------------------------
+ * The reference's SQL executor pastes the whole WHERE clause into the statement it runs (EXE:32-41, 68-92), so
+ * `WHERE region = 2` filters there.  Here a key predicate is one more conjunct of the `pass` test the sweeps apply
+ * per sampled row: pass = sampled && amount range (aqe_query.has_where) && region term && product_id term.
+ * `visited` counts every sampled row, `n` the rows that pass — exactly as the amount range is treated — and the
+ * estimators are the ones of aqe_reduce / aqe_reduce_grouped / aqe_reduce_spread on those (n, visited).
+ * A filter is a conjunction of at most one term per key column; a term is
+ *     col = v | col <> v | col != v | col [NOT] IN (v1, ...) | col [NOT] BETWEEN a AND b | col >= a | col > a | col <= a | col < a
+ * with int32 literals, compiled by the host into a form the device tests in a few instructions per row:
+ *   AQE_KEYTERM_RANGE    lo <= key <= hi (lo > hi: no key), `negate` flips the outcome;
+ *   AQE_KEYTERM_BITMAP   bit (key - lo) of `bits`, keys outside [lo, hi] are not members; hi - lo < AQE_KEY_BITMAP_BITS
+ *                        (what GROUP BY accepts of a key column).  A span of 64 keys or fewer (region) is tested
+ *                        against one 64-bit scalar; wider maps are read from LDS.
+ * An IN list whose values span more than AQE_KEY_BITMAP_BITS keys is AQE_ERR_UNSUPPORTED, never truncated.
+ * aqe_query, aqe_result and the ABI version are unchanged: the filter travels beside the query. */
+#define AQE_KEYTERM_NONE 0
+#define AQE_KEYTERM_RANGE 1
+#define AQE_KEYTERM_BITMAP 2
+#define AQE_KEY_BITMAP_BITS 1024
+typedef struct aqe_key_term {
+    int32_t form;   /* AQE_KEYTERM_*                                        */
+    int32_t negate; /* 1: NOT IN / <> / NOT BETWEEN                         */
+    int32_t lo, hi; /* RANGE: inclusive bounds; BITMAP: base key and last key of the map */
+    uint64_t bits[AQE_KEY_BITMAP_BITS / 64];
+} aqe_key_term;
+typedef struct aqe_key_filter {
+    aqe_key_term term[2]; /* [AQE_GROUP_REGION - 1], [AQE_GROUP_PRODUCT - 1] */
+} aqe_key_filter;
+/* Host only, no GPU.  Compile one term: `col IN (values)` (n >= 1 values; one value is a RANGE) or lo <= col <= hi. */
+AQE_API int aqe_key_term_in(aqe_key_term* term, const int32_t* values, uint32_t n, int negate);
+AQE_API int aqe_key_term_range(aqe_key_term* term, int32_t lo, int32_t hi, int negate);
+/* Host only, no GPU: the key terms of a query's WHERE clause (the counterpart of aqe_parse_where, which keeps reading the
+ * amount range).  Returns 1 and fills *out when the clause names region or product_id, 0 when it names neither (*out is
+ * then empty: both forms NONE), AQE_ERR_INVALID for what is not a conjunction of the terms above (OR, two terms on one
+ * column, a non-integer literal, a comparison between columns ...) and AQE_ERR_UNSUPPORTED for an IN list too wide for
+ * the map; err (optional, err_cap bytes) then receives a message that quotes the term. */
+AQE_API int aqe_parse_key_where(const char* query, aqe_key_filter* out, char* err, size_t err_cap);
+/* Host only, no GPU: 1 when a row with these keys passes the filter, else 0 — the test the kernels apply. */
+AQE_API int aqe_key_filter_test(const aqe_key_filter* filter, int32_t region, int32_t product_id);
+/* One sweep of the sampled rows (filter.hip) reads the amount and the key column(s) the filter names — 8 + 4 bytes per
+ * sampled row and column referenced — and accumulates the shifted power sums {n, P1, P2, P3, P4, visited} of the spread
+ * section over the rows that pass.  P1, P2 are the (S - c n, Q shifted) of aqe_reduce, so the one vector answers SUM /
+ * AVG / COUNT (value and interval under q.convention, CLI:189-200, 277-291; DB.cpp:303-315) and, with all five sums,
+ * VARIANCE / STDDEV.  No floating-point atomics on the ungrouped path: bit-identical from run to run.
+ * Samplers: those of aqe_reduce_spread (single-round family samplers, AQE_M_ROWID_MOD, the seeded AQE_M_RANDOM_POINTER
+ * for the ungrouped form); CLT, adaptive, stratified, AQE_M_RANDOM_DEVICE and pair-family samplers: AQE_ERR_UNSUPPORTED.
+ * Needs the key columns (AQE_STAGE_KEEP_AOS or a synthetic table).  A sample none of whose rows pass is an answer, not an
+ * error: n == 0, SUM 0, AVG 0, VARIANCE NaN with has_interval == 0; only visited == 0 is "No samples collected". */
+AQE_API int aqe_reduce_filtered(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, aqe_result* out);
+AQE_API int aqe_reduce_filtered_spread(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, int kind, aqe_spread_result* out);
+/* GROUP BY `group_column` under the filter (a term may sit on the group column itself, on the other column, or both):
+ * one bin {n, P1, P2, P3, P4, visited} per key.  Per group SUM / AVG / COUNT as aqe_reduce_grouped (EXE:202-321),
+ * VARIANCE / STDDEV as aqe_reduce_grouped_spread.  A group none of whose rows pass is listed with n == 0 (visited is
+ * still its own).  Bins are summed in LDS in arrival order: reproducible to rounding. */
+AQE_API int aqe_reduce_filtered_grouped(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, int group_column,
+                                        aqe_group_result* out, uint32_t cap, uint32_t* n_groups);
+AQE_API int aqe_reduce_filtered_grouped_spread(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, int kind, int group_column,
+                                               aqe_spread_group_result* out, uint32_t cap, uint32_t* n_groups);
+/* Multi-GPU form (the pattern of aqe_spread_enqueue / aqe_grouped_spread_enqueue_bins): every rank sweeps its shard,
+ *     aqe_filtered_enqueue(ctx, filter, q, dev_vec, stream)        this shard's AQE_SPREAD_VEC doubles
+ *                                                                   {n, P1, P2, P3, P4, visited, n c, 0}
+ *     <all-reduce SUM of AQE_SPREAD_VEC doubles on `stream`>
+ *     aqe_filtered_finish(ctx, q, dev_vec, stream, &out)            SUM / AVG / COUNT; synchronises `stream`
+ *  or aqe_filtered_spread_finish(ctx, q, kind, dev_vec, stream, &out)
+ * and for GROUP BY, over the key range agreed as for aqe_grouped_enqueue_bins,
+ *     aqe_filtered_grouped_enqueue_bins(ctx, filter, q, column, kmin, nbins, dev_bins, stream)   nbins x AQE_SPREAD_BIN doubles
+ *     <all-reduce SUM>
+ *     aqe_filtered_grouped_finish(ctx, q, kmin, nbins, dev_bins, stream, out, cap, &n_groups)     SUM / AVG / COUNT per group
+ *  or aqe_grouped_spread_finish(...) as it is (the bins have its layout). */
+AQE_API int aqe_filtered_enqueue(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, double* dev_vec, void* stream);
+AQE_API int aqe_filtered_finish(aqe_ctx* ctx, const aqe_query* q, const double* dev_vec, void* stream, aqe_result* out);
+AQE_API int aqe_filtered_spread_finish(aqe_ctx* ctx, const aqe_query* q, int kind, const double* dev_vec, void* stream, aqe_spread_result* out);
+AQE_API int aqe_filtered_grouped_enqueue_bins(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, int group_column, int32_t key_min,
+                                              uint32_t nbins, double* dev_bins, void* stream);
+AQE_API int aqe_filtered_grouped_finish(aqe_ctx* ctx, const aqe_query* q, int32_t key_min, uint32_t nbins, const double* dev_bins, void* stream,
+                                        aqe_group_result* out, uint32_t cap, uint32_t* n_groups);
+/* Host only, no GPU and no context: SUM / AVG / COUNT with its interval from a (summed) vector — the twin of
+ * aqe_spread_from_sums.  q supplies agg, convention, sample_percent and method (AQE_M_EXACT reports the exact forms);
+ * n_global is N of the estimators (the row window's size when the query has one).  The shift is vec[6] / vec[0]. */
+AQE_API int aqe_filtered_from_sums(const double vec[AQE_SPREAD_VEC], const aqe_query* q, uint64_t n_global, aqe_result* out);
+
 /* ---- stepwise / multi-GPU form ----------------------------------------------------------------
  * One process per GPU; each rank plans the same query over its own shard.  Per round:
  *     aqe_plan_enqueue_round(plan, r, dev_vec, stream)     this shard's partial moment vector
