@@ -455,14 +455,16 @@ __device__ __forceinline__ void sweep_tile(const SweepCommon& a, FamPtr fams, u6
     sweep_family<kNT>(a, fams[find_family(fams, a.nfam, t)], t, lane, ord_limit, acc);
 }
 
-// The row loop of sweep_family / k_grouped / the quantile passes as a VISITOR: one wave walks tile `t` of the launch's
-// family table (single-pointer families: dense 16-byte path with its interior form, page path, strided path and
-// stride-major views, window edges) and calls visit(x, key, ok) once per ordinal slot of the tile, in a fixed order — ok
-// says whether the slot is a sampled row (x and key are then that row's amount and, with kKeys, its key from `keys`, a
-// column in the amount's row or slot order; without kKeys key is 0).  Every load of the tile is issued before the first
-// visit; slots outside the window read row 0 of the shard.  kNT: non-temporal loads on the interior dense form.
-template <bool kNT, bool kKeys, typename FamPtr, typename Visit>
-__device__ __forceinline__ void visit_tile(const SweepCommon& sw, FamPtr fams, const int32_t* keys, u64 t, int lane, Visit& visit) {
+// The row loop of sweep_family as a VISITOR, with NK = 0, 1 or 2 key columns beside the amount: one wave walks tile `t` of
+// the launch's family table (single-pointer families: dense 16-byte path with its interior form, page path, strided path
+// and stride-major views, window edges) and calls visit(x, key0, key1, ok) once per ordinal slot of the tile, in a fixed
+// order — ok says whether the slot is a sampled row (x is then that row's amount, key0 / key1 its keys from `keys0` /
+// `keys1`, columns in the amount's row or slot order).  Nothing of a column past NK is read: its key is 0 and its pointer
+// may be null.  Every load of the tile is issued before the first visit; slots outside the window read row 0 of the
+// shard.  kNT: non-temporal loads on the interior dense form; kInterior = false leaves that form out and masks every dense
+// tile (k_qpass, whose passes measured no faster with it).  (k_grouped of grouped.hip keeps a row loop of its own.)
+template <bool kNT, int NK, bool kInterior = true, typename FamPtr, typename Visit>
+__device__ __forceinline__ void visit_tile(const SweepCommon& sw, FamPtr fams, const int32_t* keys0, const int32_t* keys1, u64 t, int lane, Visit& visit) {
     const auto& F = fams[find_family(fams, sw.nfam, t)];
     const u64 lt = t - F.tile_begin;
     u64 seg, j;
@@ -472,17 +474,19 @@ __device__ __forceinline__ void visit_tile(const SweepCommon& sw, FamPtr fams, c
     const u64 ord_lo = F.ord_lo, ord_hi = F.ord_hi;
     const u64 row_base = F.row0 + seg * F.pitch - sw.shard_lo;
     const double* const base = sw.amount + row_base;
-    const int32_t* const kbase = kKeys ? keys + row_base : nullptr;
+    const int32_t* const kb0 = NK >= 1 ? keys0 + row_base : nullptr;
+    const int32_t* const kb1 = NK >= 2 ? keys1 + row_base : nullptr;
     if (sw.dense16 && is_dense16(step, F.flags, seg_len)) {
         struct __attribute__((packed, aligned(8))) Row2 { double x, y; };
         struct __attribute__((packed, aligned(4))) Key2 { int x, y; };
         Row2 x2[kTileUnroll];
-        Key2 k2[kTileUnroll];
+        Key2 a2[kTileUnroll], b2[kTileUnroll];
         // interior tile (sweep_family): every slot inside the segment and the window — no masks, no address selects
         const u64 tile_lo = uniform64(j * kDenseTileOrdinals), o_lo = uniform64(seg_ord0 + tile_lo);
-        if (tile_lo + kDenseTileOrdinals <= uniform64(seg_len) && o_lo >= uniform64(ord_lo) && o_lo + kDenseTileOrdinals <= uniform64(ord_hi)) {
+        if (kInterior && tile_lo + kDenseTileOrdinals <= uniform64(seg_len) && o_lo >= uniform64(ord_lo) && o_lo + kDenseTileOrdinals <= uniform64(ord_hi)) {
             const Row2* const p = reinterpret_cast<const Row2*>(base + tile_lo) + lane;
-            const Key2* const pk = kKeys ? reinterpret_cast<const Key2*>(kbase + tile_lo) + lane : nullptr;
+            const Key2* const pa = NK >= 1 ? reinterpret_cast<const Key2*>(kb0 + tile_lo) + lane : nullptr;
+            const Key2* const pb = NK >= 2 ? reinterpret_cast<const Key2*>(kb1 + tile_lo) + lane : nullptr;
 #pragma unroll
             for (int k = 0; k < kTileUnroll; ++k) {
                 if (kNT) {
@@ -491,11 +495,13 @@ __device__ __forceinline__ void visit_tile(const SweepCommon& sw, FamPtr fams, c
                 } else {
                     x2[k] = p[k * 64];
                 }
-                if (kKeys) k2[k] = pk[k * 64];
-                else k2[k].x = k2[k].y = 0;
+                if (NK >= 1) a2[k] = pa[k * 64];
+                else a2[k].x = a2[k].y = 0;
+                if (NK >= 2) b2[k] = pb[k * 64];
+                else b2[k].x = b2[k].y = 0;
             }
 #pragma unroll
-            for (int k = 0; k < kTileUnroll; ++k) { visit(x2[k].x, k2[k].x, true); visit(x2[k].y, k2[k].y, true); }
+            for (int k = 0; k < kTileUnroll; ++k) { visit(x2[k].x, a2[k].x, b2[k].x, true); visit(x2[k].y, a2[k].y, b2[k].y, true); }
             return;
         }
         const u64 oi0 = j * kDenseTileOrdinals + 2 * static_cast<u64>(lane);
@@ -508,24 +514,30 @@ __device__ __forceinline__ void visit_tile(const SweepCommon& sw, FamPtr fams, c
             ok1[k] = oi + 1 < seg_len && o + 1 >= ord_lo && o + 1 < ord_hi;
             const bool both = ok0[k] && ok1[k];
             x2[k] = *reinterpret_cast<const Row2*>(both ? base + oi : sw.amount);
-            if (kKeys) k2[k] = *reinterpret_cast<const Key2*>(both ? kbase + oi : keys);
-            else k2[k].x = k2[k].y = 0;
+            if (NK >= 1) a2[k] = *reinterpret_cast<const Key2*>(both ? kb0 + oi : keys0);
+            else a2[k].x = a2[k].y = 0;
+            if (NK >= 2) b2[k] = *reinterpret_cast<const Key2*>(both ? kb1 + oi : keys1);
+            else b2[k].x = b2[k].y = 0;
             if (!both) {  // window edge: single reads
                 x2[k].x = ok0[k] ? base[oi] : 0.0;
                 x2[k].y = ok1[k] ? base[oi + 1] : 0.0;
-                if (kKeys) {
-                    k2[k].x = ok0[k] ? kbase[oi] : 0;
-                    k2[k].y = ok1[k] ? kbase[oi + 1] : 0;
+                if (NK >= 1) {
+                    a2[k].x = ok0[k] ? kb0[oi] : 0;
+                    a2[k].y = ok1[k] ? kb0[oi + 1] : 0;
+                }
+                if (NK >= 2) {
+                    b2[k].x = ok0[k] ? kb1[oi] : 0;
+                    b2[k].y = ok1[k] ? kb1[oi + 1] : 0;
                 }
             }
         }
 #pragma unroll
-        for (int k = 0; k < kTileUnroll; ++k) { visit(x2[k].x, k2[k].x, ok0[k]); visit(x2[k].y, k2[k].y, ok1[k]); }
+        for (int k = 0; k < kTileUnroll; ++k) { visit(x2[k].x, a2[k].x, b2[k].x, ok0[k]); visit(x2[k].y, a2[k].y, b2[k].y, ok1[k]); }
         return;
     }
     const u64 oi0 = j * kTileOrdinals + lane;
     double x[kTileUnroll];
-    int key[kTileUnroll];
+    int ka[kTileUnroll], kb[kTileUnroll];
     bool ok[kTileUnroll];
     if (F.flags & kFamLinear) {
         // short segments (pages) tiled along the ordinal axis, a tile spanning several segments (sweep_family)
@@ -542,7 +554,8 @@ __device__ __forceinline__ void visit_tile(const SweepCommon& sw, FamPtr fams, c
             ok[k] = o >= ord_lo && o < ord_hi;
             const u64 off = ok[k] ? col0 + (seg0 + qx) * F.pitch + static_cast<u64>(xx - qx * sl) * step : 0;
             x[k] = sw.amount[off];
-            key[k] = kKeys ? keys[off] : 0;
+            ka[k] = NK >= 1 ? keys0[off] : 0;
+            kb[k] = NK >= 2 ? keys1[off] : 0;
         }
     } else {
 #pragma unroll
@@ -552,11 +565,12 @@ __device__ __forceinline__ void visit_tile(const SweepCommon& sw, FamPtr fams, c
             ok[k] = oi < seg_len && o >= ord_lo && o < ord_hi;
             const u64 off = ok[k] ? oi * step : 0;
             x[k] = ok[k] ? base[off] : sw.amount[0];
-            key[k] = kKeys ? (ok[k] ? kbase[off] : keys[0]) : 0;
+            ka[k] = NK >= 1 ? (ok[k] ? kb0[off] : keys0[0]) : 0;
+            kb[k] = NK >= 2 ? (ok[k] ? kb1[off] : keys1[0]) : 0;
         }
     }
 #pragma unroll
-    for (int k = 0; k < kTileUnroll; ++k) visit(x[k], key[k], ok[k]);
+    for (int k = 0; k < kTileUnroll; ++k) visit(x[k], ka[k], kb[k], ok[k]);
 }
 
 }  // namespace

@@ -91,8 +91,7 @@ struct StageRing {
     size_t bytes_each = 0;
 };
 
-struct aqe_spread_scratch;  // spread.hip
-struct aqe_filter_scratch;  // filter.hip
+struct aqe_moment_scratch;  // moments.hip
 
 struct aqe_ctx {
     StageRing ring;
@@ -153,10 +152,9 @@ struct aqe_ctx {
     bool qrange_valid = false;
     uint64_t qrange_epoch = 0;
     double qrange_lo = 0.0, qrange_hi = 0.0;
-    // VARIANCE / STDDEV (spread.hip): partials, tickets, pinned results of the spread entries, made on first use
-    aqe_spread_scratch* spread = nullptr;
-    // key predicates (filter.hip): partials, tickets, pinned results of the filtered entries, made on first use
-    aqe_filter_scratch* filter = nullptr;
+    // VARIANCE / STDDEV and key predicates (moments.hip): partials, tickets, pinned results of the power-sum sweep's entries,
+    // made on first use
+    aqe_moment_scratch* moments = nullptr;
 };
 
 // One persistent-sweep form of a plan's rounds (persist.hip): the tile list of all slots, who owns tiles
@@ -287,11 +285,8 @@ inline double query_shift(const aqe_ctx* c, const aqe_query& q) {
 int quantile_amount_range(aqe_ctx* c, double* lo, double* hi);  // non-NaN amounts of the shard (+inf / -inf: none)
 void quantile_release(aqe_ctx* c);
 
-// spread.hip
-void spread_release(aqe_ctx* c);
-
-// filter.hip
-void filter_release(aqe_ctx* c);
+// moments.hip
+void moments_release(aqe_ctx* c);
 
 // plans.hip
 void destroy_plan(aqe_plan* p, bool device_idle = false);  // device_idle: the caller has just synchronised the device

@@ -1,0 +1,1019 @@
+// moments.hip — the sweep of the SHIFTED POWER SUMS, and the two sets of entry points it answers: approximate VARIANCE /
+// STDDEV with a fourth-moment interval (aqe_reduce_spread and its kin) and the aggregates under a WHERE predicate on region /
+// product_id (aqe_reduce_filtered and its kin); contracts in include/aqe_hip.h.
+//
+// The sampling error of a variance depends on the fourth central moment, which the (n, S, Q) sweeps do not carry.  ONE
+// sweep of the sampled rows (visit_tile of device_common.hpp with NK = 0, 1 or 2 key columns beside the amount; the seeded
+// random sampler through its host-built index list) accumulates over the rows that pass
+//     {n, P1, P2, P3, P4, visited},   Pk = sum (x - c)^k,   c = query_shift (the same on every shard),
+// which merge by plain addition across lanes, waves, workgroups and GPUs.  A key predicate (key_term.hpp) is one more
+// conjunct of `pass`; NK counts the key columns it names, and a column without a term is not read.  P1, P2 are the (sd, qd)
+// make_result turns into SUM / AVG / COUNT; all five feed spread_core, which centres them
+//     d = P1/n,  M2 = P2 - n d^2,  M3 = P3 - 3 d P2 + 2 n d^3,  M4 = P4 - 4 d P3 + 6 d^2 P2 - 3 n d^4
+// and works out the value and the interval (one function for the device and for aqe_spread_from_sums).
+//
+// Ungrouped (k_moments): no floating-point atomics.  A lane keeps its sums in registers, the wave adds them with
+// cross-lane moves (wave_sum7), the workgroup in wave order through LDS; a workgroup stores its [8] partial and draws a
+// ticket (the counter form of k_round's finish_block), and the workgroup that draws the last one adds the partials in a
+// fixed order and finishes into pinned memory — nothing, an aqe_result or an aqe_spread_result.  The answer is therefore
+// bit-identical from run to run.
+//
+// GROUP BY (k_moments_grouped): one bin of the six sums per key, binned the way grouped.hip does — lane-private LDS bins
+// for few keys, replicated shared bins (ds_add_f64) above — then [workgroup][bin][6] partials, summed per word in
+// workgroup order (k_bins_sum: what ranks all-reduce), and one thread per bin finishes.  A row the predicate fails still
+// counts into its group's `visited`.  Six components instead of three make a lane-private bin 40 bytes per thread: 4 keys
+// (region) take 40 KB of LDS, so the private form is used up to kPrivBins = 4 keys where grouped.hip goes to 8.  Shared
+// bins are added in arrival order: reproducible to rounding, not bit for bit, as the grouped sums are.
+#include <cstddef>
+
+#include "device_common.hpp"
+#include "host.hpp"
+#include "key_term.hpp"
+#include "spread_core.hpp"
+
+namespace aqe {
+namespace {
+
+constexpr unsigned kGridCap = 1024;  // workgroups of the ungrouped sweep at most: 4 per CU, as k_round (kRoundGridCap)
+constexpr unsigned kPrivBins = 4;
+constexpr unsigned kMaxReplicas = 8;
+constexpr unsigned kSharedLdsBytes = 50u << 10;  // 1024 keys x 6 sums in one replica: 49 200 bytes
+static_assert(kSpVec == 8 && kSpBin == 6, "vector layout of include/aqe_hip.h");
+static_assert((kMaxGroupBins | 1) * kSpBin * 8 <= kSharedLdsBytes, "one replica of the widest key range fits");
+static_assert(kMapWords == 16, "two maps are staged by 32 threads");
+
+__host__ __device__ inline unsigned replica_stride(unsigned nbins) { return nbins | 1u; }  // odd: replicas start on different banks
+__host__ __device__ inline unsigned replicas_for(unsigned nbins) {
+    unsigned r = kSharedLdsBytes / (replica_stride(nbins) * 8u * kSpBin);
+    r = r > kMaxReplicas ? kMaxReplicas : r;
+    unsigned p = 1;
+    while (2 * p <= r) p *= 2;  // a power of two (lane & (p - 1)), at least one
+    return p;
+}
+
+constexpr int kFuseNone = 0, kFuseResult = 1, kFuseSpread = 2;
+
+struct MomentLaunch {
+    SweepCommon sw;
+    u64 ntiles;
+    const uint64_t* idx;  // the seeded random sampler: global rows (else null)
+    u64 n_idx;
+    const int32_t* keys[2];  // the key columns (or their stride-major views) the filter's terms judge
+    double* partials;     // [gridDim.x][kSpVec]
+    unsigned* ticket;     // kCounterWords, zero between launches
+    double* vec;          // this launch's kSpVec sums
+    aqe_result* out;              // kFuseResult: the finished SUM / AVG / COUNT (pinned, mapped)
+    aqe_spread_result* out_spread;  // kFuseSpread
+    FinalizeParams fin;
+    SpreadFin sfin;
+    int32_t fused;
+    uint32_t row_bytes;   // bytes read per sampled row: 8 + 4 per key column
+    DevFilter flt;
+};
+static_assert(sizeof(MomentLaunch) <= 4096, "kernel arguments are limited to 4 KB");
+
+// The two columns' maps from the kernel-argument segment into LDS (32 threads, one word each).
+template <typename Launch>
+__device__ __forceinline__ void stage_maps(u64 (*s_map)[kMapWords]) {
+    if (threadIdx.x < 2 * kMapWords) {
+        typedef const AQE_KARG char* KargBytes;
+        typedef const AQE_KARG u64* KargWords;
+        const KargBytes K = (KargBytes)__builtin_amdgcn_kernarg_segment_ptr();
+        const KargWords m = (KargWords)(K + offsetof(Launch, flt) + offsetof(DevFilter, map));
+        s_map[threadIdx.x / kMapWords][threadIdx.x % kMapWords] = m[threadIdx.x];
+    }
+    __syncthreads();
+}
+
+// SUM / AVG / COUNT from the power sums: the state make_result reads (device_common.hpp), one round folded.
+__host__ __device__ inline aqe_result result_from_vec(const double* vec, const FinalizeParams& fin, uint32_t row_bytes) {
+    QueryState s{};
+    s.n_a = s.n_p = vec[0];
+    s.sd_a = s.sd_p = vec[1];
+    s.qd_a = s.qd_p = vec[2];
+    s.visited = vec[5];
+    s.rounds = 1;
+    aqe_result r = make_result(s, fin);
+    r.bytes_algorithmic = r.visited * static_cast<uint64_t>(row_bytes);
+    return r;
+}
+
+template <bool kNT, int NK>
+__global__ __launch_bounds__(kBlockThreads) void k_moments(MomentLaunch a) {
+    __shared__ DevFamily lds_fams[kMaxLdsFams];
+    __shared__ double red[kWavesPerBlock][kSpVec];
+    __shared__ double s_vec[kSpVec];
+    __shared__ u64 s_map[2][kMapWords];
+    __shared__ int s_last;
+    const unsigned tid = threadIdx.x;
+    const int lane = tid & 63;
+    if (NK >= 1) stage_maps<MomentLaunch>(s_map);
+    const bool has_where = a.sw.has_where != 0;
+    const double c = a.sw.shift, wmin = a.sw.wmin, wmax = a.sw.wmax;
+    const DevTerm T0 = a.flt.t[0], T1 = a.flt.t[1];
+    double p1 = 0.0, p2 = 0.0, p3 = 0.0, p4 = 0.0;
+    unsigned n = 0, nv = 0;
+    auto visit = [&](double x, int k0, int k1, bool ok) {
+        bool pass = ok && (!has_where || (x >= wmin && x <= wmax));  // inclusive both ends, as the sums
+        if (NK >= 1) pass = pass && term_pass(T0, s_map[0], k0);
+        if (NK >= 2) pass = pass && term_pass(T1, s_map[1], k1);
+        const double d = pass ? x - c : 0.0;
+        const double d2 = d * d;
+        nv += ok ? 1u : 0u;
+        n += pass ? 1u : 0u;
+        p1 += d;
+        p2 += d2;
+        p3 = fma(d2, d, p3);
+        p4 = fma(d2, d2, p4);
+    };
+    if (a.idx) {
+        constexpr u64 kChunk = static_cast<u64>(kBlockThreads) * kTileUnroll;
+        for (u64 c0 = static_cast<u64>(blockIdx.x) * kChunk; c0 < a.n_idx; c0 += static_cast<u64>(gridDim.x) * kChunk) {
+            u64 off[kTileUnroll];
+            bool ok[kTileUnroll];
+#pragma unroll
+            for (int k = 0; k < kTileUnroll; ++k) {
+                const u64 i = c0 + tid + static_cast<u64>(k) * kBlockThreads;
+                ok[k] = i < a.n_idx;
+                const u64 row = a.idx[ok[k] ? i : 0];
+                off[k] = ok[k] ? row - a.sw.shard_lo : 0;
+            }
+            double v[kTileUnroll];
+            int ka[kTileUnroll], kb[kTileUnroll];
+#pragma unroll
+            for (int k = 0; k < kTileUnroll; ++k) {
+                v[k] = a.sw.amount[off[k]];
+                ka[k] = NK >= 1 ? a.keys[0][off[k]] : 0;
+                kb[k] = NK >= 2 ? a.keys[1][off[k]] : 0;
+            }
+#pragma unroll
+            for (int k = 0; k < kTileUnroll; ++k) visit(v[k], ka[k], kb[k], ok[k]);
+        }
+    } else {
+        const DevFamily* fams = stage_families(a.sw, lds_fams);
+        const u64 wave_id = uniform64(static_cast<u64>(blockIdx.x) * kWavesPerBlock + (tid >> 6));
+        const u64 wave_stride = static_cast<u64>(gridDim.x) * kWavesPerBlock;
+        for (u64 t = wave_id; t < a.ntiles; t += wave_stride) visit_tile<kNT, NK>(a.sw, fams, a.keys[0], a.keys[1], t, lane, visit);
+    }
+    // lanes -> wave (cross-lane moves) -> workgroup (LDS, wave order): components {n, P1, P2, P3, P4, visited}
+    const double v7[7] = {static_cast<double>(n), p1, p2, p3, p4, static_cast<double>(nv), 0.0};
+    const double mine = wave_sum7(v7, lane);
+    if ((lane & 7) == 0) red[tid >> 6][lane >> 3] = mine;  // (component 7 is wave_sum7's zero pad)
+    __syncthreads();
+    double tot = 0.0;
+    if (tid < 8) {
+        const unsigned k = tid == 6 ? 0u : tid;
+        tot = red[0][k];
+#pragma unroll
+        for (int w = 1; w < kWavesPerBlock; ++w) tot += red[w][k];
+        if (tid == 6) tot *= c;  // n c: the shift travels with the sums (additive: c is the same on every shard)
+    }
+    if (gridDim.x > 1) {
+        if (tid < 8) __hip_atomic_store(a.partials + static_cast<size_t>(blockIdx.x) * kSpVec + tid, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid < 64) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the partial is out before the ticket is drawn (same wave)
+        if (tid == 0) {  // sharded arrival tickets, as finish_block (kernels.hip)
+            const unsigned G = gridDim.x, shards = G < static_cast<unsigned>(kShards) ? G : static_cast<unsigned>(kShards);
+            unsigned* const ct = a.ticket + static_cast<size_t>(kShards) * kShardStride;
+            int last = 0;
+            if (G <= static_cast<unsigned>(kShards)) {
+                if (__hip_atomic_fetch_add(ct, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1u) { __hip_atomic_store(ct, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); last = 1; }
+            } else {
+                const unsigned sh = blockIdx.x % shards, members = (G - sh + shards - 1u) / shards;
+                unsigned* const cs = a.ticket + static_cast<size_t>(sh) * kShardStride;
+                if (__hip_atomic_fetch_add(cs, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == members - 1u) {
+                    __hip_atomic_store(cs, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (__hip_atomic_fetch_add(ct, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == shards - 1u) { __hip_atomic_store(ct, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); last = 1; }
+                }
+            }
+            s_last = last;
+        }
+        __syncthreads();
+        if (!s_last) return;
+        tot = sum_partials(a.partials, gridDim.x * static_cast<unsigned>(kSpVec), red);
+    }
+    if (tid < 8) {
+        a.vec[tid] = tot;
+        s_vec[tid] = tot;
+    }
+    if (a.fused == kFuseNone) return;
+    __syncthreads();
+    if (tid == 0) {
+        if (a.fused == kFuseResult) *a.out = result_from_vec(s_vec, a.fin, a.row_bytes);
+        else *a.out_spread = spread_result(s_vec, c, a.sfin);
+    }
+}
+
+// The multi-GPU finishes: one thread works the result out of the (all-reduced) vector.
+__global__ __launch_bounds__(64) void k_result_finish(const double* __restrict__ vec, FinalizeParams fin, aqe_result* out) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        double v[kSpVec];
+        for (int k = 0; k < kSpVec; ++k) v[k] = vec[k];
+        *out = result_from_vec(v, fin, 8u);
+    }
+}
+__global__ __launch_bounds__(64) void k_spread_finish(const double* __restrict__ vec, double c, SpreadFin fin, aqe_spread_result* out) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        double v[kSpVec];
+        for (int k = 0; k < kSpVec; ++k) v[k] = vec[k];
+        *out = spread_result(v, c, fin);
+    }
+}
+
+// ---- GROUP BY ---------------------------------------------------------------------------------------------------------------
+
+struct MomentGroupLaunch {
+    SweepCommon sw;
+    u64 ntiles;
+    const int32_t* keys[2];  // [0]: the group column, [1]: the other column when the filter has a term on it
+    int32_t key_min;
+    uint32_t nbins;
+    double* partial;         // [gridDim.x][nbins][kSpBin]: n, P1, P2, P3, P4, visited
+    DevFilter flt;           // kFiltered: t[0] judges the group column (pass-all when it has no term), t[1] the other
+};
+
+// kFiltered = false is the unfiltered grouped spread (NK = 1): no map is staged and no term is tested.
+template <bool kPrivate, bool kNT, int NK, bool kFiltered>
+__global__ __launch_bounds__(kBlockThreads) void k_moments_grouped(MomentGroupLaunch a) {
+    static_assert(NK == 1 || (NK == 2 && kFiltered), "the group column, and the other one only under a term on it");
+    extern __shared__ double lds[];
+    __shared__ DevFamily lds_fams[kMaxLdsFams];
+    __shared__ u64 s_map[2][kMapWords];
+    const unsigned nb = a.nbins, tid = threadIdx.x;
+    const unsigned reps = replicas_for(nb), rstride = replica_stride(nb), comp_len = reps * rstride;
+    const unsigned plane = nb * kBlockThreads;  // private: words of one component
+    const unsigned words = kPrivate ? plane * 5 : comp_len * kSpBin;  // in doubles (private: P1..P4, and n + visited as 2 x u32)
+    for (unsigned i = tid; i < words; i += kBlockThreads) lds[i] = 0.0;
+    double* const P1 = kPrivate ? lds : lds + comp_len;
+    double* const P2 = kPrivate ? lds + plane : lds + 2 * comp_len;
+    double* const P3 = kPrivate ? lds + 2 * plane : lds + 3 * comp_len;
+    double* const P4 = kPrivate ? lds + 3 * plane : lds + 4 * comp_len;
+    unsigned* const Nu = reinterpret_cast<unsigned*>(lds + 4 * plane);  // private: u32 counters
+    unsigned* const Vu = Nu + plane;
+    double* const Nd = lds;                                             // shared: counts as f64 (one LDS atomic type)
+    double* const Vd = lds + 5 * comp_len;
+    const unsigned rep_off = (tid & (reps - 1u)) * rstride;
+    if constexpr (kFiltered) stage_maps<MomentGroupLaunch>(s_map);
+    const DevFamily* fams = stage_families(a.sw, lds_fams);
+    __syncthreads();
+    const int lane = tid & 63;
+    const u64 wave_id = uniform64(static_cast<u64>(blockIdx.x) * kWavesPerBlock + (tid >> 6));
+    const u64 wave_stride = static_cast<u64>(gridDim.x) * kWavesPerBlock;
+    const double c = a.sw.shift, wmin = a.sw.wmin, wmax = a.sw.wmax;
+    const bool has_where = a.sw.has_where != 0;
+    const int kmin = a.key_min;
+    const DevTerm T0 = a.flt.t[0], T1 = a.flt.t[1];
+    auto visit = [&](double x, int key, int other, bool ok) {
+        const unsigned b = static_cast<unsigned>(key - kmin);
+        if (!ok || b >= nb) return;  // (the host checked the shard's key range: b >= nb does not occur)
+        bool pass = !has_where || (x >= wmin && x <= wmax);
+        if constexpr (kFiltered) pass = pass && term_pass(T0, s_map[0], key);
+        if constexpr (NK >= 2) pass = pass && term_pass(T1, s_map[1], other);
+        const double d = x - c, d2 = d * d;
+        if (kPrivate) {  // a word of its own per lane and bin: the add never conflicts
+            const unsigned i = b * kBlockThreads + tid;
+            __hip_atomic_fetch_add(Vu + i, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (pass) {
+                __hip_atomic_fetch_add(Nu + i, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(P1 + i, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(P2 + i, d2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(P3 + i, d2 * d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(P4 + i, d2 * d2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        } else {
+            const unsigned i = rep_off + b;
+            __hip_atomic_fetch_add(Vd + i, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (pass) {
+                __hip_atomic_fetch_add(Nd + i, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(P1 + i, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(P2 + i, d2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(P3 + i, d2 * d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(P4 + i, d2 * d2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+    };
+    for (u64 t = wave_id; t < a.ntiles; t += wave_stride) visit_tile<kNT, NK>(a.sw, fams, a.keys[0], a.keys[1], t, lane, visit);
+    __syncthreads();
+    double* const out = a.partial + static_cast<size_t>(blockIdx.x) * nb * kSpBin;  // [nbins][6]
+    if (kPrivate) {
+        // the workgroup's 256 private words per (bin, component), summed by a fixed binary tree over the threads
+        for (unsigned stride = kBlockThreads / 2; stride > 0; stride >>= 1) {
+            if (tid < stride) {
+                for (unsigned b = 0; b < nb; ++b) {
+                    const unsigned i = b * kBlockThreads + tid;
+                    P1[i] += P1[i + stride];
+                    P2[i] += P2[i + stride];
+                    P3[i] += P3[i + stride];
+                    P4[i] += P4[i + stride];
+                    Nu[i] += Nu[i + stride];
+                    Vu[i] += Vu[i + stride];
+                }
+            }
+            __syncthreads();
+        }
+        if (tid < nb * kSpBin) {
+            const unsigned b = tid / kSpBin, comp = tid % kSpBin, w = b * kBlockThreads;
+            out[tid] = comp == 0 ? static_cast<double>(Nu[w]) : comp == 1 ? P1[w] : comp == 2 ? P2[w] : comp == 3 ? P3[w] : comp == 4 ? P4[w]
+                                                                                                                          : static_cast<double>(Vu[w]);
+        }
+    } else {
+        for (unsigned i = tid; i < nb * kSpBin; i += kBlockThreads) {  // the replicas in order
+            const unsigned comp = i % kSpBin, b = i / kSpBin;
+            double t = 0.0;
+            for (unsigned r = 0; r < reps; ++r) t += lds[comp * comp_len + r * rstride + b];
+            out[i] = t;
+        }
+    }
+}
+
+// One wave per word (bin, component): lane l adds the workgroups l, l + 64, ... in order, then a fixed xor butterfly adds
+// the lanes -> bins[nbins][6] (k_grouped_sum of grouped.hip).
+__global__ __launch_bounds__(64) void k_bins_sum(const double* __restrict__ partial, unsigned nblocks, unsigned nwords, double* __restrict__ bins) {
+    const unsigned i = blockIdx.x, lane = threadIdx.x;
+    double t = 0.0;
+    for (unsigned w = lane; w < nblocks; w += 64) t += partial[static_cast<size_t>(w) * nwords + i];
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+    if (lane == 0) bins[i] = t;
+}
+
+// One thread per bin: SUM / AVG / COUNT of the group and its interval from the (all-reduced) sums — the arithmetic of
+// k_grouped_finish (grouped.hip, group_result; executor.cpp:280-296) on the bin's n, P1, P2, visited.
+__global__ __launch_bounds__(64) void k_groups_finish(const double* __restrict__ bins, unsigned nbins, int32_t key_min, double c, double pct, int agg,
+                                                      aqe_group_result* __restrict__ out) {
+    const unsigned b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= nbins) return;
+    const double* v = bins + static_cast<size_t>(b) * kSpBin;
+    const double n = v[0], sd = v[1], qd = v[2];
+    aqe_group_result r;
+    r.key = static_cast<int64_t>(key_min) + b;
+    r.n = static_cast<uint64_t>(n);
+    r.visited = static_cast<uint64_t>(v[5]);
+    r.sum = sd + n * c;
+    r.sumsq = qd + 2.0 * c * sd + n * c * c;
+    double mean = 0.0, m2 = 0.0;
+    if (n > 0.0) mean_m2(n, sd, qd, c, mean, m2);
+    r.mean = mean;
+    const double scale = 100.0 / pct;
+    double margin = 0.0;
+    if (n >= 2.0) margin = 1.96 * sqrt((m2 / (n - 1.0)) / n);
+    double value;
+    if (agg == AQE_SUM) { value = r.sum * scale; margin *= scale; }
+    else if (agg == AQE_AVG) { value = mean; }
+    else { value = n * scale; margin = 0.0; }
+    r.value = value;
+    r.ci_lower = value - margin;
+    r.ci_upper = value + margin;
+    out[b] = r;
+}
+
+// One thread per bin: VARIANCE / STDDEV of the group and its interval from the (all-reduced) sums.
+__global__ __launch_bounds__(64) void k_spread_groups_finish(const double* __restrict__ bins, unsigned nbins, int32_t key_min, double c, SpreadFin fin,
+                                                             aqe_spread_group_result* __restrict__ out) {
+    const unsigned b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= nbins) return;
+    const double* v = bins + static_cast<size_t>(b) * kSpBin;
+    const SpreadCore k = spread_core(v[0], v[1], v[2], v[3], v[4], c, fin);
+    aqe_spread_group_result r;
+    r.key = static_cast<int64_t>(key_min) + b;
+    r.value = k.value; r.ci_lower = k.lo; r.ci_upper = k.hi;
+    r.mean = k.mean; r.m2 = k.m2; r.m3 = k.m3; r.m4 = k.m4;
+    r.n = static_cast<uint64_t>(v[0]);
+    r.visited = static_cast<uint64_t>(v[5]);
+    r.has_interval = k.has_interval;
+    r.pad = 0;
+    out[b] = r;
+}
+
+inline unsigned grid_for(uint64_t work, uint64_t per_block) {
+    const uint64_t g = (work + per_block - 1) / per_block;
+    return static_cast<unsigned>(g < 1 ? 1 : g > kGridCap ? kGridCap : g);
+}
+
+}  // namespace
+}  // namespace aqe
+
+// What the spread and the filtered entries keep with the context: partials and tickets of the ungrouped sweep, the pinned
+// results, the grouped form's partials, bins and pinned groups.  Allocated on first use.
+struct aqe_moment_scratch {
+    double* d_partials = nullptr;   // [kGridCap][kSpVec]
+    unsigned* d_ticket = nullptr;   // kCounterWords, zeroed once: every launch leaves them at zero
+    double* d_vec = nullptr;        // [kSpVec]
+    aqe_result* h_out = nullptr;    // pinned, mapped
+    aqe_result* d_out = nullptr;
+    aqe_spread_result* h_sout = nullptr;
+    aqe_spread_result* d_sout = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    double* d_gpartial = nullptr;   // grown on demand
+    size_t gpartial_bytes = 0;
+    double* d_bins = nullptr;       // [kMaxGroupBins][kSpBin]
+    aqe_group_result* h_groups = nullptr;  // pinned, mapped: [kMaxGroupBins]
+    aqe_group_result* d_groups = nullptr;
+    aqe_spread_group_result* h_sgroups = nullptr;
+    aqe_spread_group_result* d_sgroups = nullptr;
+};
+
+namespace aqe {
+namespace {
+
+template <typename T>
+int pinned(aqe_ctx* c, T** host, T** dev, size_t count) {
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(host), sizeof(T) * count, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(dev), *host, 0));
+    return AQE_OK;
+}
+
+int ensure_scratch(aqe_ctx* c) {
+    if (c->moments) return AQE_OK;
+    aqe_moment_scratch* s = new aqe_moment_scratch;
+    c->moments = s;  // (moments_release frees whatever part of it exists)
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_partials), sizeof(double) * kGridCap * kSpVec));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_ticket), sizeof(unsigned) * kCounterWords));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_vec), sizeof(double) * kSpVec));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_bins), sizeof(double) * kMaxGroupBins * kSpBin));
+    int rc = pinned(c, &s->h_out, &s->d_out, 1);
+    if (rc == AQE_OK) rc = pinned(c, &s->h_sout, &s->d_sout, 1);
+    if (rc == AQE_OK) rc = pinned(c, &s->h_groups, &s->d_groups, kMaxGroupBins);
+    if (rc == AQE_OK) rc = pinned(c, &s->h_sgroups, &s->d_sgroups, kMaxGroupBins);
+    if (rc != AQE_OK) return rc;
+    HIPCHK(c, hipEventCreate(&s->ev0));
+    HIPCHK(c, hipEventCreate(&s->ev1));
+    HIPCHK(c, hipMemset(s->d_ticket, 0, sizeof(unsigned) * kCounterWords));
+    HIPCHK(c, hipDeviceSynchronize());  // (the memset runs on the null stream, which the context's stream does not wait for)
+    return AQE_OK;
+}
+
+int check_kind(aqe_ctx* c, int kind) {
+    if (kind < AQE_SPREAD_VAR_SAMP || kind > AQE_SPREAD_STDDEV_POP) return fail(c, AQE_ERR_INVALID, "kind must be one of AQE_SPREAD_VAR_SAMP .. AQE_SPREAD_STDDEV_POP");
+    return AQE_OK;
+}
+
+int group_column_ok(aqe_ctx* c, int group_column) {
+    if (group_column != AQE_GROUP_REGION && group_column != AQE_GROUP_PRODUCT) return fail(c, AQE_ERR_INVALID, "group_column must be AQE_GROUP_REGION or AQE_GROUP_PRODUCT");
+    return AQE_OK;
+}
+
+int check_filter(aqe_ctx* c, const aqe_key_filter* f) {
+    if (!f) return fail(c, AQE_ERR_INVALID, "null filter");
+    for (int k = 0; k < 2; ++k)
+        if (const char* why = term_defect(f->term[k])) return fail(c, AQE_ERR_INVALID, why);
+    return AQE_OK;
+}
+
+// The two sets of entries refuse a sampler in their own words.
+struct Wording {
+    const char* subject;  // "... do not take the <method> sampler"
+    const char* grouped;  // the grouped forms under the seeded random sampler
+};
+constexpr Wording kSpreadWords{"VARIANCE / STDDEV do not take the ",
+                               "grouped VARIANCE / STDDEV takes a single-round family sampler (exact, stride, rowid-mod, block, page, pointer, region ...)"};
+constexpr Wording kFilterWords{"key predicates do not take the ",
+                               "GROUP BY under a key predicate takes a single-round family sampler (exact, stride, rowid-mod, block, page, pointer, region ...)"};
+inline const Wording& words_for(const aqe_key_filter* f) { return f ? kFilterWords : kSpreadWords; }
+
+int unsupported(aqe_ctx* c, const Wording& w, int method) {
+    return fail(c, AQE_ERR_UNSUPPORTED, std::string(w.subject) + method_name(method) + " sampler (single-round family samplers and the seeded random sampler only)");
+}
+
+// Checks the query and takes its cached plan; refuses samplers out of scope before anything reaches a kernel.
+int moment_plan(aqe_ctx* c, const aqe_query* q, bool grouped, const Wording& w, aqe_plan** out) {
+    if (!q) return fail(c, AQE_ERR_INVALID, "null query");
+    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
+    if (!(q->sample_percent > 0.0)) return fail(c, AQE_ERR_INVALID, "sample_percent must be positive");
+    switch (q->method) {
+        case AQE_M_OPTIMIZED_CLT: case AQE_M_CLT_DUAL_POINTER: case AQE_M_ADAPTIVE_BLOCK: case AQE_M_STRATIFIED_BLOCK: case AQE_M_RANDOM_DEVICE:
+            return unsupported(c, w, q->method);
+        default: break;
+    }
+    aqe_plan* p = nullptr;
+    int rc = cached_plan(c, q, &p);
+    if (rc != AQE_OK) return rc;
+    rc = plan_is_current(p);
+    if (rc != AQE_OK) return rc;
+    bool pair = false;
+    for (const DevFamily& f : p->h_fams) pair = pair || (f.flags & AQE_F_PAIR);
+    if (p->host.is_perm || p->host.is_clt || p->host.on_sorted || p->rounds.size() > 1 || pair) return unsupported(c, w, q->method);
+    if (grouped && p->host.is_random) return fail(c, AQE_ERR_UNSUPPORTED, w.grouped);
+    *out = p;
+    return AQE_OK;
+}
+
+SpreadFin fin_for(const aqe_query* q, int kind) {
+    SpreadFin f;
+    f.z = z_for(q->confidence_level);
+    f.kind = kind;
+    f.exact = q->method == AQE_M_EXACT ? 1 : 0;
+    return f;
+}
+
+FinalizeParams finalize_for(const aqe_ctx* c, const aqe_query& q) {
+    FinalizeParams f{};
+    f.n_global = q.row_hi > q.row_lo ? q.row_hi - q.row_lo : c->n_global;  // a row window is the table (finalize_params, plans.hip)
+    f.pct = q.sample_percent;
+    f.shift = query_shift(c, q);
+    f.agg = q.agg;
+    f.convention = q.convention;
+    f.is_exact = q.method == AQE_M_EXACT;
+    f.is_clt = 0;
+    return f;
+}
+
+inline hipStream_t stream_of(aqe_ctx* c, void* stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
+
+// The key column `column` as the plan's rows index it: the column itself, or its stride-major view.
+int key_pointer(aqe_ctx* c, aqe_plan* p, int column, const int32_t** out) {
+    int rc = ensure_keys(c, column);
+    if (rc != AQE_OK) return rc;
+    *out = c->keycol[column - 1];
+    if (p->view_rounds) rc = ensure_key_view(c, column, p->view_step_rounds, out);
+    return rc;
+}
+
+// One launch: this shard's kSpVec sums into `vec`, under the filter `f` (null: none); fused: the last workgroup also
+// finishes into a pinned result.
+int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, double* vec, int fused, const SpreadFin* sfin, hipStream_t s) {
+    aqe_moment_scratch* sc = c->moments;
+    MomentLaunch a{};
+    a.partials = sc->d_partials;
+    a.ticket = sc->d_ticket;
+    a.vec = vec;
+    a.out = sc->d_out;
+    a.out_spread = sc->d_sout;
+    a.fused = fused;
+    a.fin = finalize_for(c, p->q);
+    if (sfin) a.sfin = *sfin;
+    unsigned grid = 1;
+    a.sw = SweepCommon{};
+    a.sw.shift = query_shift(c, p->q);
+    if (p->host.is_random) {
+        a.sw.amount = c->amount;
+        a.sw.shard_lo = c->shard_lo;
+        a.sw.has_where = p->q.has_where ? 1 : 0;
+        a.sw.wmin = p->q.where_min;
+        a.sw.wmax = p->q.where_max;
+        a.idx = p->d_idx;
+        a.n_idx = a.idx ? p->host.random_idx.size() : 0;
+        grid = grid_for(a.n_idx, static_cast<uint64_t>(kBlockThreads) * kTileUnroll);
+    } else if (!p->rounds.empty() && c->n_local) {
+        const LaunchDesc& L = p->rounds[0];
+        a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
+        a.ntiles = L.nfam ? L.ntiles : 0;
+        grid = grid_for(a.ntiles, kWavesPerBlock);
+    }
+    // the columns the filter names, in column order: a column without a term is not read
+    int nk = 0;
+    a.flt.t[0] = a.flt.t[1] = pass_all();
+    const bool work = a.ntiles > 0 || a.n_idx > 0;
+    for (int col = AQE_GROUP_REGION; f && col <= AQE_GROUP_PRODUCT; ++col) {
+        const aqe_key_term& t = f->term[col - 1];
+        if (t.form == AQE_KEYTERM_NONE) continue;
+        compile_term(t, &a.flt.t[nk], a.flt.map[nk]);
+        if (work) {
+            int rc = p->host.is_random ? ensure_keys(c, col) : key_pointer(c, p, col, &a.keys[nk]);
+            if (rc != AQE_OK) return rc;
+            if (p->host.is_random) a.keys[nk] = c->keycol[col - 1];
+        }
+        ++nk;
+    }
+    a.row_bytes = 8u + 4u * static_cast<unsigned>(nk);
+    const bool nt = a.sw.nt != 0;
+    const dim3 g(grid), b(kBlockThreads);
+    if (nk == 0) {
+        if (nt) hipLaunchKernelGGL((k_moments<true, 0>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((k_moments<false, 0>), g, b, 0, s, a);
+    } else if (nk == 1) {
+        if (nt) hipLaunchKernelGGL((k_moments<true, 1>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((k_moments<false, 1>), g, b, 0, s, a);
+    } else {
+        if (nt) hipLaunchKernelGGL((k_moments<true, 2>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((k_moments<false, 2>), g, b, 0, s, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return AQE_OK;
+}
+
+// The ungrouped entries up to the launch, behind their argument checks: the device, the plan, the scratch.
+int sweep_prologue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, aqe_plan** p) {
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = moment_plan(c, q, false, words_for(f), p);
+    if (rc == AQE_OK) rc = ensure_scratch(c);
+    return rc;
+}
+
+// The single-GPU ungrouped entries: one fused launch on the context's stream, timed by events; the result is then in
+// the scratch's pinned h_out (kFuseResult) or h_sout (kFuseSpread, of `kind`; kFuseResult reads no kind).
+int reduce_fused(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int fused, int kind, double* kernel_ms) {
+    aqe_plan* p = nullptr;
+    int rc = sweep_prologue(c, f, q, &p);
+    if (rc != AQE_OK) return rc;
+    const SpreadFin fin = fin_for(q, kind);
+    aqe_moment_scratch* sc = c->moments;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipEventRecord(sc->ev0, s));
+    rc = enqueue_sweep(c, p, f, sc->d_vec, fused, &fin, s);
+    if (rc != AQE_OK) return rc;
+    HIPCHK(c, hipEventRecord(sc->ev1, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, sc->ev0, sc->ev1));
+    *kernel_ms = static_cast<double>(ms);
+    return AQE_OK;
+}
+
+// The multi-GPU spread finishes, from their argument checks to the copy out of pinned memory.
+int spread_finish(aqe_ctx* c, const aqe_query* q, int kind, const double* dev_vec, void* stream, aqe_spread_result* out) {
+    if (!q || !dev_vec || !out) return fail(c, AQE_ERR_INVALID, "null argument");
+    int rc = check_kind(c, kind);
+    if (rc != AQE_OK) return rc;
+    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    aqe_moment_scratch* sc = c->moments;
+    hipStream_t s = stream_of(c, stream);
+    hipLaunchKernelGGL(k_spread_finish, dim3(1), dim3(64), 0, s, dev_vec, query_shift(c, *q), fin_for(q, kind), sc->d_sout);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    std::memcpy(out, sc->h_sout, sizeof *out);
+    return AQE_OK;
+}
+
+// This shard's bins [nbins][kSpBin] into dev_bins (zeros when nothing of the sample lies in this shard), under the filter
+// `f` (null: none; the caller has checked it).
+int enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int group_column, int32_t key_min, uint32_t nbins, double* dev_bins, hipStream_t s) {
+    aqe_plan* p = nullptr;
+    int rc = moment_plan(c, q, true, words_for(f), &p);
+    if (rc != AQE_OK) return rc;
+    rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    const size_t bins_bytes = static_cast<size_t>(nbins) * kSpBin * sizeof(double);
+    if (p->rounds.empty() || c->n_local == 0 || p->rounds[0].ntiles == 0 || p->rounds[0].nfam == 0) {
+        HIPCHK(c, hipMemsetAsync(dev_bins, 0, bins_bytes, s));
+        return AQE_OK;
+    }
+    const LaunchDesc& L = p->rounds[0];
+    MomentGroupLaunch a{};
+    a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
+    a.ntiles = L.ntiles;
+    a.key_min = key_min;
+    a.nbins = nbins;
+    rc = key_pointer(c, p, group_column, &a.keys[0]);
+    if (rc != AQE_OK) return rc;
+    const int k = group_column - 1;
+    if (c->key_min[k] < key_min || static_cast<int64_t>(c->key_max[k]) - key_min >= static_cast<int64_t>(nbins))
+        return fail(c, AQE_ERR_INVALID, "this shard has keys outside [key_min, key_min + nbins)");
+    a.flt.t[0] = a.flt.t[1] = pass_all();
+    int nk = 1;
+    if (f) {
+        compile_term(f->term[k], &a.flt.t[0], a.flt.map[0]);
+        const int other = group_column == AQE_GROUP_REGION ? AQE_GROUP_PRODUCT : AQE_GROUP_REGION;
+        if (f->term[other - 1].form != AQE_KEYTERM_NONE) {
+            compile_term(f->term[other - 1], &a.flt.t[1], a.flt.map[1]);
+            rc = key_pointer(c, p, other, &a.keys[1]);
+            if (rc != AQE_OK) return rc;
+            nk = 2;
+        }
+    }
+    const unsigned grid = grouped_grid(L.ntiles);
+    aqe_moment_scratch* sc = c->moments;
+    const size_t need = static_cast<size_t>(grid) * bins_bytes;
+    if (sc->gpartial_bytes < need) {
+        if (sc->d_gpartial) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier sweep may still be reading the buffer
+            (void)hipFree(sc->d_gpartial);
+        }
+        sc->d_gpartial = nullptr;
+        sc->gpartial_bytes = 0;
+        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_gpartial), need));
+        sc->gpartial_bytes = need;
+    }
+    a.partial = sc->d_gpartial;
+    const bool priv = nbins <= kPrivBins;
+    const size_t lds_bytes = priv ? static_cast<size_t>(nbins) * kBlockThreads * 5 * sizeof(double)
+                                  : static_cast<size_t>(replicas_for(nbins)) * replica_stride(nbins) * kSpBin * sizeof(double);
+    const bool nt = a.sw.nt != 0;
+    const dim3 g(grid), b(kBlockThreads);
+#define AQE_MG_LAUNCH(PRIV, NT)                                                                               \
+    do {                                                                                                      \
+        if (!f) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 1, false>), g, b, lds_bytes, s, a);           \
+        else if (nk == 1) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 1, true>), g, b, lds_bytes, s, a);  \
+        else hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 2, true>), g, b, lds_bytes, s, a);               \
+    } while (0)
+    if (priv) {
+        if (nt) AQE_MG_LAUNCH(true, true);
+        else AQE_MG_LAUNCH(true, false);
+    } else {
+        if (nt) AQE_MG_LAUNCH(false, true);
+        else AQE_MG_LAUNCH(false, false);
+    }
+#undef AQE_MG_LAUNCH
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_bins_sum, dim3(nbins * kSpBin), dim3(64), 0, s, sc->d_gpartial, grid, nbins * static_cast<unsigned>(kSpBin), dev_bins);
+    HIPCHK(c, hipGetLastError());
+    return AQE_OK;
+}
+
+// The finishing kernel has been enqueued on `s` and writes pinned `groups`: wait, and hand out the keys somebody sampled.
+template <typename Group>
+int collect_groups(aqe_ctx* c, hipStream_t s, const Group* groups, uint32_t nbins, Group* out, uint32_t cap, uint32_t* n_groups) {
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    uint32_t g = 0;
+    for (uint32_t b = 0; b < nbins; ++b) {
+        const Group& r = groups[b];
+        if (r.visited == 0) continue;  // a key nobody sampled
+        if (g < cap) out[g] = r;
+        ++g;
+    }
+    *n_groups = g;
+    if (g > cap) return fail(c, AQE_ERR_CAPACITY, "more groups than the caller's buffer holds (n_groups has the count)");
+    return AQE_OK;
+}
+
+int finish_groups(aqe_ctx* c, const aqe_query* q, int32_t key_min, uint32_t nbins, const double* dev_bins, hipStream_t s, aqe_group_result* out,
+                  uint32_t cap, uint32_t* n_groups) {
+    aqe_moment_scratch* sc = c->moments;
+    hipLaunchKernelGGL(k_groups_finish, dim3((nbins + 63) / 64), dim3(64), 0, s, dev_bins, nbins, key_min, query_shift(c, *q), q->sample_percent, q->agg,
+                       sc->d_groups);
+    return collect_groups(c, s, sc->h_groups, nbins, out, cap, n_groups);
+}
+
+int finish_spread_groups(aqe_ctx* c, const aqe_query* q, int kind, int32_t key_min, uint32_t nbins, const double* dev_bins, hipStream_t s,
+                         aqe_spread_group_result* out, uint32_t cap, uint32_t* n_groups) {
+    aqe_moment_scratch* sc = c->moments;
+    hipLaunchKernelGGL(k_spread_groups_finish, dim3((nbins + 63) / 64), dim3(64), 0, s, dev_bins, nbins, key_min, query_shift(c, *q), fin_for(q, kind),
+                       sc->d_sgroups);
+    return collect_groups(c, s, sc->h_sgroups, nbins, out, cap, n_groups);
+}
+
+// The key range of the group column and the sweep into the context's own bins (the single-GPU grouped entries).
+// nbins_out stays 0 for an empty table: no groups.
+int grouped_prologue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int group_column, uint32_t* n_groups, int32_t* kmin_out, uint32_t* nbins_out) {
+    *n_groups = 0;
+    *nbins_out = 0;
+    int32_t kmin = 0, kmax = -1;
+    int rc = aqe_group_key_range(c, group_column, &kmin, &kmax);
+    if (rc != AQE_OK) return rc;
+    if (kmax < kmin) return AQE_OK;
+    const int64_t span = static_cast<int64_t>(kmax) - kmin + 1;
+    if (span > kMaxGroupBins) return fail(c, AQE_ERR_UNSUPPORTED, "group column spans more than 1024 distinct values");
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    rc = enqueue_bins(c, f, q, group_column, kmin, static_cast<uint32_t>(span), c->moments->d_bins, c->stream);
+    if (rc != AQE_OK) return rc;
+    *kmin_out = kmin;
+    *nbins_out = static_cast<uint32_t>(span);
+    return AQE_OK;
+}
+
+// The single-GPU grouped spread entries behind their argument checks.
+int grouped_spread(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int kind, int group_column, aqe_spread_group_result* out, uint32_t cap,
+                   uint32_t* n_groups) {
+    int32_t kmin = 0;
+    uint32_t nbins = 0;
+    const int rc = grouped_prologue(c, f, q, group_column, n_groups, &kmin, &nbins);
+    if (rc != AQE_OK || nbins == 0) return rc;
+    return finish_spread_groups(c, q, kind, kmin, nbins, c->moments->d_bins, c->stream, out, cap, n_groups);
+}
+
+// What the multi-GPU grouped enqueues check of their arguments, and the device.
+int bins_arguments(aqe_ctx* c, int group_column, const double* dev_bins, uint32_t nbins) {
+    int rc = group_column_ok(c, group_column);
+    if (rc != AQE_OK) return rc;
+    if (!dev_bins || nbins == 0 || nbins > static_cast<uint32_t>(kMaxGroupBins)) return fail(c, AQE_ERR_INVALID, "dev_bins null or nbins outside 1..1024");
+    HIPCHK(c, hipSetDevice(c->device));
+    return AQE_OK;
+}
+
+}  // namespace
+
+void moments_release(aqe_ctx* c) {
+    aqe_moment_scratch* s = c->moments;
+    if (!s) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(s->d_partials);
+    (void)hipFree(s->d_ticket);
+    (void)hipFree(s->d_vec);
+    (void)hipFree(s->d_bins);
+    (void)hipFree(s->d_gpartial);
+    if (s->h_out) (void)hipHostFree(s->h_out);
+    if (s->h_sout) (void)hipHostFree(s->h_sout);
+    if (s->h_groups) (void)hipHostFree(s->h_groups);
+    if (s->h_sgroups) (void)hipHostFree(s->h_sgroups);
+    if (s->ev0) (void)hipEventDestroy(s->ev0);
+    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    delete s;
+    c->moments = nullptr;
+}
+
+}  // namespace aqe
+
+using namespace aqe;
+
+extern "C" {
+
+// ---- VARIANCE / STDDEV ------------------------------------------------------------------------------------------------------
+
+int aqe_reduce_spread(aqe_ctx* c, const aqe_query* q, int kind, aqe_spread_result* out) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!out) return fail(c, AQE_ERR_INVALID, "null argument");
+    int rc = check_kind(c, kind);
+    if (rc != AQE_OK) return rc;
+    double ms = 0.0;
+    rc = reduce_fused(c, nullptr, q, kFuseSpread, kind, &ms);
+    if (rc != AQE_OK) return rc;
+    std::memcpy(out, c->moments->h_sout, sizeof *out);
+    out->kernel_ms = ms;
+    if (out->n == 0) return fail(c, AQE_ERR_INVALID, "No samples collected");
+    return AQE_OK;
+}
+
+int aqe_spread_enqueue(aqe_ctx* c, const aqe_query* q, double* dev_vec, void* stream) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!dev_vec) return fail(c, AQE_ERR_INVALID, "null dev_vec");
+    aqe_plan* p = nullptr;
+    int rc = sweep_prologue(c, nullptr, q, &p);
+    if (rc != AQE_OK) return rc;
+    return enqueue_sweep(c, p, nullptr, dev_vec, kFuseNone, nullptr, stream_of(c, stream));
+}
+
+int aqe_spread_finish(aqe_ctx* c, const aqe_query* q, int kind, const double* dev_vec, void* stream, aqe_spread_result* out) {
+    if (!c) return AQE_ERR_INVALID;
+    int rc = spread_finish(c, q, kind, dev_vec, stream, out);
+    if (rc != AQE_OK) return rc;
+    if (out->n == 0) return fail(c, AQE_ERR_INVALID, "No samples collected");
+    return AQE_OK;
+}
+
+int aqe_spread_from_sums(const double* vec, int kind, double confidence_level, int exact, aqe_spread_result* out) {
+    if (!vec || !out || kind < AQE_SPREAD_VAR_SAMP || kind > AQE_SPREAD_STDDEV_POP) return AQE_ERR_INVALID;
+    SpreadFin f;
+    f.z = z_for(confidence_level);
+    f.kind = kind;
+    f.exact = exact ? 1 : 0;
+    const double n = vec[0];
+    *out = spread_result(vec, n > 0.0 ? vec[6] / n : 0.0, f);
+    return n > 0.0 ? AQE_OK : AQE_ERR_INVALID;
+}
+
+int aqe_reduce_grouped_spread(aqe_ctx* c, const aqe_query* q, int kind, int group_column, aqe_spread_group_result* out, uint32_t cap,
+                              uint32_t* n_groups) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_groups || (cap && !out)) return fail(c, AQE_ERR_INVALID, "null argument");
+    int rc = check_kind(c, kind);
+    if (rc == AQE_OK) rc = group_column_ok(c, group_column);
+    if (rc != AQE_OK) return rc;
+    return grouped_spread(c, nullptr, q, kind, group_column, out, cap, n_groups);
+}
+
+int aqe_grouped_spread_enqueue_bins(aqe_ctx* c, const aqe_query* q, int group_column, int32_t key_min, uint32_t nbins, double* dev_bins,
+                                    void* stream) {
+    if (!c) return AQE_ERR_INVALID;
+    const int rc = bins_arguments(c, group_column, dev_bins, nbins);
+    if (rc != AQE_OK) return rc;
+    return enqueue_bins(c, nullptr, q, group_column, key_min, nbins, dev_bins, stream_of(c, stream));
+}
+
+int aqe_grouped_spread_finish(aqe_ctx* c, const aqe_query* q, int kind, int32_t key_min, uint32_t nbins, const double* dev_bins, void* stream,
+                              aqe_spread_group_result* out, uint32_t cap, uint32_t* n_groups) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_groups || (cap && !out) || !dev_bins || nbins == 0 || nbins > static_cast<uint32_t>(kMaxGroupBins)) return fail(c, AQE_ERR_INVALID, "bad argument");
+    int rc = check_kind(c, kind);
+    if (rc != AQE_OK) return rc;
+    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
+    HIPCHK(c, hipSetDevice(c->device));
+    *n_groups = 0;
+    rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    return finish_spread_groups(c, q, kind, key_min, nbins, dev_bins, stream_of(c, stream), out, cap, n_groups);
+}
+
+// ---- key predicates ---------------------------------------------------------------------------------------------------------
+
+int aqe_filtered_from_sums(const double* vec, const aqe_query* q, uint64_t n_global, aqe_result* out) {
+    if (!vec || !q || !out) return AQE_ERR_INVALID;
+    FinalizeParams f{};
+    f.n_global = n_global;
+    f.pct = q->sample_percent;
+    f.shift = vec[0] > 0.0 ? vec[6] / vec[0] : 0.0;
+    f.agg = q->agg;
+    f.convention = q->convention;
+    f.is_exact = q->method == AQE_M_EXACT;
+    f.is_clt = 0;
+    *out = result_from_vec(vec, f, 8u);
+    return vec[5] > 0.0 ? AQE_OK : AQE_ERR_INVALID;
+}
+
+int aqe_reduce_filtered(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, aqe_result* out) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!out) return fail(c, AQE_ERR_INVALID, "null argument");
+    int rc = check_filter(c, f);
+    if (rc != AQE_OK) return rc;
+    double ms = 0.0;
+    rc = reduce_fused(c, f, q, kFuseResult, 0, &ms);
+    if (rc != AQE_OK) return rc;
+    std::memcpy(out, c->moments->h_out, sizeof *out);
+    out->kernel_ms = ms;
+    if (out->visited == 0) return fail(c, AQE_ERR_INVALID, "No samples collected");
+    return AQE_OK;
+}
+
+int aqe_reduce_filtered_spread(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int kind, aqe_spread_result* out) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!out) return fail(c, AQE_ERR_INVALID, "null argument");
+    int rc = check_kind(c, kind);
+    if (rc == AQE_OK) rc = check_filter(c, f);
+    if (rc != AQE_OK) return rc;
+    double ms = 0.0;
+    rc = reduce_fused(c, f, q, kFuseSpread, kind, &ms);
+    if (rc != AQE_OK) return rc;
+    std::memcpy(out, c->moments->h_sout, sizeof *out);
+    out->kernel_ms = ms;
+    if (out->visited == 0) return fail(c, AQE_ERR_INVALID, "No samples collected");
+    return AQE_OK;
+}
+
+int aqe_filtered_enqueue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, double* dev_vec, void* stream) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!dev_vec) return fail(c, AQE_ERR_INVALID, "null dev_vec");
+    int rc = check_filter(c, f);
+    if (rc != AQE_OK) return rc;
+    aqe_plan* p = nullptr;
+    rc = sweep_prologue(c, f, q, &p);
+    if (rc != AQE_OK) return rc;
+    return enqueue_sweep(c, p, f, dev_vec, kFuseNone, nullptr, stream_of(c, stream));
+}
+
+int aqe_filtered_finish(aqe_ctx* c, const aqe_query* q, const double* dev_vec, void* stream, aqe_result* out) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !dev_vec || !out) return fail(c, AQE_ERR_INVALID, "null argument");
+    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    aqe_moment_scratch* sc = c->moments;
+    hipStream_t s = stream_of(c, stream);
+    hipLaunchKernelGGL(k_result_finish, dim3(1), dim3(64), 0, s, dev_vec, finalize_for(c, *q), sc->d_out);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    std::memcpy(out, sc->h_out, sizeof *out);
+    if (out->visited == 0) return fail(c, AQE_ERR_INVALID, "No samples collected");
+    return AQE_OK;
+}
+
+int aqe_filtered_spread_finish(aqe_ctx* c, const aqe_query* q, int kind, const double* dev_vec, void* stream, aqe_spread_result* out) {
+    if (!c) return AQE_ERR_INVALID;
+    int rc = spread_finish(c, q, kind, dev_vec, stream, out);
+    if (rc != AQE_OK) return rc;
+    if (out->visited == 0) return fail(c, AQE_ERR_INVALID, "No samples collected");
+    return AQE_OK;
+}
+
+int aqe_reduce_filtered_grouped(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int group_column, aqe_group_result* out, uint32_t cap,
+                                uint32_t* n_groups) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_groups || (cap && !out)) return fail(c, AQE_ERR_INVALID, "null argument");
+    int rc = group_column_ok(c, group_column);
+    if (rc == AQE_OK) rc = check_filter(c, f);
+    if (rc != AQE_OK) return rc;
+    int32_t kmin = 0;
+    uint32_t nbins = 0;
+    rc = grouped_prologue(c, f, q, group_column, n_groups, &kmin, &nbins);
+    if (rc != AQE_OK || nbins == 0) return rc;
+    return finish_groups(c, q, kmin, nbins, c->moments->d_bins, c->stream, out, cap, n_groups);
+}
+
+int aqe_reduce_filtered_grouped_spread(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int kind, int group_column,
+                                       aqe_spread_group_result* out, uint32_t cap, uint32_t* n_groups) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_groups || (cap && !out)) return fail(c, AQE_ERR_INVALID, "null argument");
+    int rc = check_kind(c, kind);
+    if (rc == AQE_OK) rc = group_column_ok(c, group_column);
+    if (rc == AQE_OK) rc = check_filter(c, f);
+    if (rc != AQE_OK) return rc;
+    return grouped_spread(c, f, q, kind, group_column, out, cap, n_groups);
+}
+
+int aqe_filtered_grouped_enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int group_column, int32_t key_min, uint32_t nbins,
+                                      double* dev_bins, void* stream) {
+    if (!c) return AQE_ERR_INVALID;
+    int rc = bins_arguments(c, group_column, dev_bins, nbins);
+    if (rc == AQE_OK) rc = check_filter(c, f);
+    if (rc != AQE_OK) return rc;
+    return enqueue_bins(c, f, q, group_column, key_min, nbins, dev_bins, stream_of(c, stream));
+}
+
+int aqe_filtered_grouped_finish(aqe_ctx* c, const aqe_query* q, int32_t key_min, uint32_t nbins, const double* dev_bins, void* stream,
+                                aqe_group_result* out, uint32_t cap, uint32_t* n_groups) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_groups || (cap && !out) || !dev_bins || nbins == 0 || nbins > static_cast<uint32_t>(kMaxGroupBins)) return fail(c, AQE_ERR_INVALID, "bad argument");
+    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
+    if (!(q->sample_percent > 0.0)) return fail(c, AQE_ERR_INVALID, "sample_percent must be positive");
+    HIPCHK(c, hipSetDevice(c->device));
+    *n_groups = 0;
+    int rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    return finish_groups(c, q, key_min, nbins, dev_bins, stream_of(c, stream), out, cap, n_groups);
+}
+
+}  // extern "C"

@@ -305,71 +305,6 @@ __device__ void q_fold(const double* vec, QState* st, const QSpec& spec, QOut* o
     }
 }
 
-// Count the sampled keys of one tile of the family table into the workgroup's histograms (k_grouped's sweep of
-// grouped.hip:204-343 without the key column: dense 16-byte path, page path, strided path, window edges).
-template <typename Visit>
-__device__ __forceinline__ void q_sweep_tile(const SweepCommon& sw, const DevFamily* fams, u64 t, int lane, Visit& visit) {
-    const DevFamily& F = fams[find_family(fams, sw.nfam, t)];
-    const u64 lt = t - F.tile_begin;
-    u64 seg, j;
-    if (F.tiles_per_seg == 0) { seg = F.seg_lo; j = F.j_lo + lt; }
-    else { seg = F.seg_lo + lt / F.tiles_per_seg; j = lt % F.tiles_per_seg; }
-    const u64 seg_len = F.seg_len, step = F.step, seg_ord0 = seg * seg_len;
-    const u64 ord_lo = F.ord_lo, ord_hi = F.ord_hi;
-    const double* const base = sw.amount + (F.row0 + seg * F.pitch - sw.shard_lo);
-    if (sw.dense16 && is_dense16(step, F.flags, seg_len)) {
-        struct __attribute__((packed, aligned(8))) Row2 { double x, y; };
-        const u64 oi0 = j * kDenseTileOrdinals + 2 * static_cast<u64>(lane);
-        Row2 x2[kTileUnroll];
-        bool ok0[kTileUnroll], ok1[kTileUnroll];
-#pragma unroll
-        for (int k = 0; k < kTileUnroll; ++k) {
-            const u64 oi = oi0 + static_cast<u64>(k) * 128;
-            const u64 o = seg_ord0 + oi;
-            ok0[k] = oi < seg_len && o >= ord_lo && o < ord_hi;
-            ok1[k] = oi + 1 < seg_len && o + 1 >= ord_lo && o + 1 < ord_hi;
-            const bool both = ok0[k] && ok1[k];
-            x2[k] = *reinterpret_cast<const Row2*>(both ? base + oi : sw.amount);
-            if (!both) {
-                x2[k].x = ok0[k] ? base[oi] : 0.0;
-                x2[k].y = ok1[k] ? base[oi + 1] : 0.0;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < kTileUnroll; ++k) { visit(x2[k].x, ok0[k]); visit(x2[k].y, ok1[k]); }
-        return;
-    }
-    const u64 oi0 = j * kTileOrdinals + lane;
-    double x[kTileUnroll];
-    bool ok[kTileUnroll];
-    if (F.flags & kFamLinear) {
-        const u64 T0 = j * kTileOrdinals;
-        const u64 seg0 = T0 / seg_len;
-        const unsigned r0 = static_cast<unsigned>(T0 - seg0 * seg_len), sl = static_cast<unsigned>(seg_len);
-        const float inv = 1.0f / static_cast<float>(sl);
-        const u64 col0 = F.row0 - sw.shard_lo;
-#pragma unroll
-        for (int k = 0; k < kTileUnroll; ++k) {
-            const unsigned xx = r0 + static_cast<unsigned>(lane) + 64u * static_cast<unsigned>(k);
-            const unsigned qx = static_cast<unsigned>((static_cast<float>(xx) + 0.5f) * inv);
-            const u64 o = T0 + static_cast<unsigned>(lane) + 64u * static_cast<unsigned>(k);
-            ok[k] = o >= ord_lo && o < ord_hi;
-            const u64 off = ok[k] ? col0 + (seg0 + qx) * F.pitch + static_cast<u64>(xx - qx * sl) * step : 0;
-            x[k] = sw.amount[off];
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kTileUnroll; ++k) {
-            const u64 oi = oi0 + static_cast<u64>(k) * 64;
-            const u64 o = seg_ord0 + oi;
-            ok[k] = oi < seg_len && o >= ord_lo && o < ord_hi;
-            x[k] = ok[k] ? base[oi * step] : sw.amount[0];
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < kTileUnroll; ++k) visit(x[k], ok[k]);
-}
-
 __global__ __launch_bounds__(kBlockThreads) void k_qpass(QPassArgs a) {
     __shared__ unsigned hist[kQBins];
     __shared__ u64 s_lo[kQMaxGroups], s_hi[kQMaxGroups], s_mn[kQMaxGroups], s_mx[kQMaxGroups];
@@ -393,7 +328,7 @@ __global__ __launch_bounds__(kBlockThreads) void k_qpass(QPassArgs a) {
     const unsigned sh0 = s_shift[0];
     unsigned vis = 0, cnt = 0;
     u64 rmn = ~0ull, rmx = 0ull;  // one group: its min / max key in registers
-    auto visit = [&](double x, bool ok) {
+    auto visit = [&](double x, int, int, bool ok) {  // (visit_tile's visitor: the pass reads no key column)
         vis += ok ? 1u : 0u;
         const bool pass = ok && x == x && (!has_where || (x >= wmin && x <= wmax));  // inclusive both ends, as the sums
         if (!pass) return;
@@ -431,13 +366,13 @@ __global__ __launch_bounds__(kBlockThreads) void k_qpass(QPassArgs a) {
 #pragma unroll
             for (int k = 0; k < kTileUnroll; ++k) v[k] = a.sw.amount[ok[k] ? row[k] - a.sw.shard_lo : 0];
 #pragma unroll
-            for (int k = 0; k < kTileUnroll; ++k) visit(v[k], ok[k]);
+            for (int k = 0; k < kTileUnroll; ++k) visit(v[k], 0, 0, ok[k]);
         }
     } else {
         const int lane = tid & 63;
         const u64 wave_id = uniform64(static_cast<u64>(blockIdx.x) * kWavesPerBlock + (tid >> 6));
         const u64 wave_stride = static_cast<u64>(gridDim.x) * kWavesPerBlock;
-        for (u64 t = wave_id; t < a.ntiles; t += wave_stride) q_sweep_tile(a.sw, fams, t, lane, visit);
+        for (u64 t = wave_id; t < a.ntiles; t += wave_stride) visit_tile<false, 0, false>(a.sw, fams, nullptr, nullptr, t, lane, visit);
     }
     if (G == 1 && rmn <= rmx) {
         __hip_atomic_fetch_min(&s_mn[0], rmn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);

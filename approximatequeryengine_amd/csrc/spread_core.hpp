@@ -1,6 +1,5 @@
-// spread_core.hpp — what the spread sweeps (spread.hip) and the filtered sweeps (filter.hip) share: the centring, value and
-// interval from the shifted power sums (one function for the device and for the host), and the fixed-order sum of the
-// workgroups' partial vectors.
+// spread_core.hpp — the arithmetic of the power-sum sweep (moments.hip): the centring, value and interval from the shifted
+// power sums (one function for the device and for the host), and the fixed-order sum of the workgroups' partial vectors.
 #pragma once
 
 #include "device_common.hpp"

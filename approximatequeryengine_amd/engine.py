@@ -486,7 +486,7 @@ class Engine:
                                                       C.c_void_p(stream), out, max_groups, C.byref(n)))
         return list(out[: n.value])
 
-    # -- key predicates: WHERE on region / product_id (aqe_reduce_filtered and its kin; filter.hip) --
+    # -- key predicates: WHERE on region / product_id (aqe_reduce_filtered and its kin; moments.hip) --
     def reduce_filtered(self, key_filter: "nat.KeyFilter", query: Query) -> Result:
         """SUM / AVG / COUNT over the sampled rows that pass the key filter (and the query's amount range)."""
         res = Result()

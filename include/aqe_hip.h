@@ -450,7 +450,7 @@ AQE_API void aqe_quantile_destroy(aqe_quantile* h);
  *   AQE_M_EXACT reports [value, value].  n < 4 (n < 2 for a _SAMP value): the value as far as it is defined, NaN
  *   bounds and has_interval = 0.  n == 0: AQE_ERR_INVALID ("No samples collected").  A non-finite amount in X gives
  *   NaN, as numpy does.
- * The sweep (spread.hip) accumulates the SHIFTED POWER SUMS P_k = sum (x - c)^k, k = 1..4, c the shift of
+ * The sweep (moments.hip) accumulates the SHIFTED POWER SUMS P_k = sum (x - c)^k, k = 1..4, c the shift of
  * AQE_MOMENT_VEC; they merge by addition, and the finish centres them: d = P1/n, M2 = P2 - n d^2,
  * M3 = P3 - 3 d P2 + 2 n d^3, M4 = P4 - 4 d P3 + 6 d^2 P2 - 3 n d^4.  No floating-point atomics on this path: the
  * answer of aqe_reduce_spread is bit-identical from run to run.
@@ -474,7 +474,9 @@ AQE_API int aqe_reduce_spread(aqe_ctx* ctx, const aqe_query* q, int kind, aqe_sp
  *     aqe_spread_enqueue(ctx, q, dev_vec, stream)          this shard's AQE_SPREAD_VEC doubles
  *     <all-reduce SUM of AQE_SPREAD_VEC doubles on `stream`>
  *     aqe_spread_finish(ctx, q, kind, dev_vec, stream, &out)   synchronises `stream`
- * aqe_reduce_spread is exactly this with a world of one (the sweep's last workgroup finishes in the same launch). */
+ * aqe_reduce_spread is exactly this with a world of one (the sweep's last workgroup finishes in the same launch).
+ * The spread and the filtered enqueues of one context share its tickets and partials: issue them one after the other, not
+ * concurrently on two streams. */
 AQE_API int aqe_spread_enqueue(aqe_ctx* ctx, const aqe_query* q, double* dev_vec, void* stream);
 AQE_API int aqe_spread_finish(aqe_ctx* ctx, const aqe_query* q, int kind, const double* dev_vec, void* stream, aqe_spread_result* out);
 /* Host only, no GPU and no context: the centring and the interval from a (summed) vector.  AQE_ERR_INVALID when
@@ -541,7 +543,7 @@ AQE_API int aqe_key_term_range(aqe_key_term* term, int32_t lo, int32_t hi, int n
 AQE_API int aqe_parse_key_where(const char* query, aqe_key_filter* out, char* err, size_t err_cap);
 /* Host only, no GPU: 1 when a row with these keys passes the filter, else 0 — the test the kernels apply. */
 AQE_API int aqe_key_filter_test(const aqe_key_filter* filter, int32_t region, int32_t product_id);
-/* One sweep of the sampled rows (filter.hip) reads the amount and the key column(s) the filter names — 8 + 4 bytes per
+/* One sweep of the sampled rows (moments.hip) reads the amount and the key column(s) the filter names — 8 + 4 bytes per
  * sampled row and column referenced — and accumulates the shifted power sums {n, P1, P2, P3, P4, visited} of the spread
  * section over the rows that pass.  P1, P2 are the (S - c n, Q shifted) of aqe_reduce, so the one vector answers SUM /
  * AVG / COUNT (value and interval under q.convention, CLI:189-200, 277-291; DB.cpp:303-315) and, with all five sums,

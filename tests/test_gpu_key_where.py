@@ -1,4 +1,4 @@
-"""WHERE predicates on region / product_id on the GPU (aqe_reduce_filtered and its kin; filter.hip) against numpy.
+"""WHERE predicates on region / product_id on the GPU (aqe_reduce_filtered and its kin; moments.hip under the terms of filter.hip) against numpy.
 
 Expectations come from the host copy of the rows, the oracle's index sets (SAMPLERS of tests/test_gpu_spread.py) and numpy
 boolean masks written here — never from the engine's own sums.  Tolerances are the project's: n and visited exact; values and

@@ -1,4 +1,4 @@
-"""Approximate VARIANCE / STDDEV on the GPU (aqe_reduce_spread, aqe_reduce_grouped_spread; spread.hip) against numpy on the
+"""Approximate VARIANCE / STDDEV on the GPU (aqe_reduce_spread, aqe_reduce_grouped_spread; moments.hip) against numpy on the
 sampled rows.
 
 For every case the index set comes from the oracle's samplers (the helpers the parity tests use), X from the host rows with

@@ -19,7 +19,7 @@ for n in (10_000_000, 100_000_000):
         eng.generate_synthetic(n)
         for name, q in (("exact", make_query(nat.M_EXACT, 100.0)), ("stride 20%", make_query(nat.M_MEMORY_STRIDE, 20.0))):
             base = med(lambda: eng.reduce_spread(q, nat.SPREAD_VAR_SAMP))
-            row = [f"{n:>11,} {name:<10} k_spread {base:9.1f} us"]
+            row = [f"{n:>11,} {name:<10} unfiltered {base:9.1f} us"]
             for tag, f in (("1 col range/word", F1), ("1 col LDS map", F1W), ("2 cols", F2), ("2 cols LDS map", F2W)):
                 t = med(lambda: eng.reduce_filtered_spread(f, q, nat.SPREAD_VAR_SAMP))
                 row.append(f"{tag} {t:9.1f} us (x{t / base:.2f})")
