@@ -20,6 +20,19 @@ M_DIRECT_ACCESS = 19
 M_OPTIMIZED_SEQUENTIAL = 20
 GROUP_REGION, GROUP_PRODUCT = 1, 2
 
+
+def group_key_pack(a: int, b: int) -> int:
+    """AQE_GROUP_KEY_PACK: the int64 key of a pair's result, a in the upper and b in the lower half."""
+    v = ((int(a) & 0xFFFFFFFF) << 32) | (int(b) & 0xFFFFFFFF)
+    return v - (1 << 64) if v >= 1 << 63 else v
+
+
+def group_key_unpack(k: int):
+    """(AQE_GROUP_KEY_MAJOR(k), AQE_GROUP_KEY_MINOR(k)): both int32 keys of a pair's result."""
+    s32 = lambda v: v - (1 << 32) if v >= 1 << 31 else v
+    k = int(k) & 0xFFFFFFFFFFFFFFFF
+    return s32(k >> 32), s32(k & 0xFFFFFFFF)
+
 SUM, AVG, COUNT = 0, 1, 2
 EST_CLI, EST_CPP, EST_RAW = 0, 1, 2
 Q_NO_TOPUP = 1
@@ -233,6 +246,11 @@ def lib() -> C.CDLL:
         "aqe_filtered_grouped_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, C.c_int32, u32, vp, vp]),
         "aqe_filtered_grouped_finish": (C.c_int, [vp, P(Query), C.c_int32, u32, vp, vp, P(GroupResult), u32, P(u32)]),
         "aqe_filtered_from_sums": (C.c_int, [P(dbl), P(Query), u64, P(Result)]),
+        "aqe_reduce_grouped_pair": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), P(GroupResult), u32, P(u32)]),
+        "aqe_reduce_grouped_pair_spread": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, P(C.c_int), P(SpreadGroupResult), u32, P(u32)]),
+        "aqe_grouped_pair_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), P(i32), P(u32), vp, vp]),
+        "aqe_grouped_pair_finish": (C.c_int, [vp, P(Query), P(i32), P(u32), vp, vp, P(GroupResult), u32, P(u32)]),
+        "aqe_grouped_pair_spread_finish": (C.c_int, [vp, P(Query), C.c_int, P(i32), P(u32), vp, vp, P(SpreadGroupResult), u32, P(u32)]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),

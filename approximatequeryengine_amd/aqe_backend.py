@@ -217,6 +217,31 @@ def _key_filter_for(key_where, method):
     return make_key_filter(key_where)
 
 
+_GROUP_COLUMNS = {"region": nat.GROUP_REGION, "product_id": nat.GROUP_PRODUCT}
+
+
+def group_columns(group_by) -> Tuple[int, ...]:
+    """The column codes of a ``group_by`` argument, in the order named: one column ("region"), or both ("region, product_id",
+    or a 2-tuple / list of names); case and whitespace are tolerated.  ValueError names the offender: an unknown column or a
+    repeated one (which every third column is), no column at all."""
+    names = group_by.split(",") if isinstance(group_by, str) else list(group_by)
+    shown = group_by if isinstance(group_by, str) else ", ".join(str(n) for n in names)
+    cols = []
+    for name in names:
+        key = str(name).strip().lower()
+        if key not in _GROUP_COLUMNS:
+            raise ValueError(f"GROUP BY {shown}: unknown column {str(name).strip()!r} (region and product_id are the key columns)")
+        if _GROUP_COLUMNS[key] in cols:
+            raise ValueError(f"GROUP BY {shown}: column {key!r} is named twice")
+        cols.append(_GROUP_COLUMNS[key])
+    return tuple(cols)  # (a third column is an unknown or a repeated one: there are two key columns)
+
+
+def _pair_groups(results, make):
+    """The mapping of a pair's results: "a,b" in the order the columns were named -> estimate, ascending by (a, b)."""
+    return {"%d,%d" % nat.group_key_unpack(r.key): make(r) for r in results}
+
+
 def _records(arr: np.ndarray) -> List[Record]:
     """numpy rows -> list[Record], what pybind11's list_caster gives the reference's callers."""
     return [Record(int(i), float(a), int(r), int(p), int(t))
@@ -619,13 +644,19 @@ class CustomBPlusDB:
         execute_query_groupby_with_ci (executor.cpp:202-321; GroupResultWithCI = map<string, {value, ci_lower,
         ci_upper}>) in one sweep.  method "rowid" is that function's own sample (rowid % (100 / sample_percent) == 0);
         "stride", "block", "page" and "exact" group the CustomBPlusDB samplers the same way.
-        SUM is sum * 100/pct (the reference reports mean * 100/pct under that name; GroupEstimate.mean has the mean)."""
-        col = {"region": nat.GROUP_REGION, "product_id": nat.GROUP_PRODUCT}[group_by.strip().lower()]
+        SUM is sum * 100/pct (the reference reports mean * 100/pct under that name; GroupEstimate.mean has the mean).
+        ``group_by`` may name both columns ("region, product_id", or a 2-tuple / list): one group per pair that occurs in the
+        sample, keyed "a,b" in the order the columns were named (the power-sum sweep with both keys, aqe_reduce_grouped_pair)."""
+        cols = group_columns(group_by)
+        col = cols[0]
         m = {"rowid": nat.M_ROWID_MOD, "stride": nat.M_MEMORY_STRIDE, "block": nat.M_BLOCK, "page": nat.M_PAGE, "exact": nat.M_EXACT}[method]
         if self._n == 0:
             return {}
         bs = 4096 if (method == "page" and block_size == 1000) else block_size
         q = make_query(m, sample_percent, agg=_AGG[agg.upper()], where=where, block_size=int(bs))
+        if len(cols) == 2:
+            f = None if key_where is None else _key_filter_for(key_where, method)
+            return _pair_groups(_quantile_call(lambda: self._grouped_pair(f, q, cols)), GroupEstimate)
         if key_where is not None:  # a sampled group nothing of which passes is listed with n == 0
             f = _key_filter_for(key_where, method)
             return {str(r.key): GroupEstimate(r) for r in _quantile_call(lambda: self._grouped_filtered(f, q, col))}
@@ -639,6 +670,12 @@ class CustomBPlusDB:
 
     def _spread_filtered(self, f, q, kind):
         return self._eng().reduce_filtered_spread(f, q, kind)
+
+    def _grouped_pair(self, f, q, cols):
+        return self._eng().reduce_grouped_pair(q, cols, f)
+
+    def _spread_groups_pair(self, f, q, kind, cols):
+        return self._eng().reduce_grouped_pair_spread(q, kind, cols, f)
 
     def _spread_groups_filtered(self, f, q, kind, col):
         return self._eng().reduce_filtered_grouped_spread(f, q, kind, col)
@@ -691,16 +728,18 @@ class CustomBPlusDB:
         by the sampling fraction — with a large-sample normal interval from the fourth central moment; method "exact" reports
         [value, value].  method as approx_quantile ("exact", "stride", "block", "page", "parallel_block", "region", "random" ...;
         CLT, adaptive, stratified and random_device samplers raise ValueError), and "rowid" (approx_group_by's sample).  With
-        ``group_by`` ("region" | "product_id") the result is the key -> SpreadEstimate mapping approx_group_by returns."""
+        ``group_by`` ("region" | "product_id", or both as approx_group_by takes them) the result is the key -> SpreadEstimate
+        mapping approx_group_by returns."""
         k = str(kind).strip().lower()
         if k not in _SPREAD_KINDS:
             raise ValueError(f"kind must be one of {sorted(_SPREAD_KINDS)}")
         if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
             raise ValueError(f"VARIANCE / STDDEV do not take the {method} sampler (single-round family samplers and 'random' only)")
         f = None if key_where is None else _key_filter_for(key_where, method)
-        col = None
+        col = cols = None
         if group_by is not None:
-            col = {"region": nat.GROUP_REGION, "product_id": nat.GROUP_PRODUCT}[group_by.strip().lower()]
+            cols = group_columns(group_by)
+            col = cols[0]
             if method == "random":
                 raise ValueError("GROUP BY takes a family sampler ('rowid', 'stride', 'block', 'page', 'exact' ...), not 'random'")
             if self._n == 0:
@@ -713,6 +752,9 @@ class CustomBPlusDB:
             q = self._approx_query("SUM", method, sample_percent, None, where, seed, num_threads, block_size, confidence_level,
                                    id_between=id_between)
         q.confidence_level = float(confidence_level)
+        if cols is not None and len(cols) == 2:
+            groups = _quantile_call(lambda: self._spread_groups_pair(f, q, _SPREAD_KINDS[k], cols))
+            return _pair_groups(groups, lambda r: SpreadEstimate(r, k, method))
         if f is not None:  # under a key predicate (a sample nothing of which passes: n == 0, NaN value, no interval)
             if col is not None:
                 groups = _quantile_call(lambda: self._spread_groups_filtered(f, q, _SPREAD_KINDS[k], col))

@@ -24,6 +24,10 @@
 // counts into its group's `visited`.  Six components instead of three make a lane-private bin 40 bytes per thread: 4 keys
 // (region) take 40 KB of LDS, so the private form is used up to kPrivBins = 4 keys where grouped.hip goes to 8.  Shared
 // bins are added in arrival order: reproducible to rounding, not bit for bit, as the grouped sums are.
+//
+// GROUP BY both key columns (kPair): the same kernel with NK = 2 — key 0 is column A, key 1 column B of the ordered pair —
+// and the bin (a - minA) * spanB + (b - minB), spanA * spanB <= kMaxGroupBins; a term may sit on either column.  Partials,
+// k_bins_sum and the finishes' arithmetic are the single-column ones; the pair finishes only decode the bin into (a, b).
 #include <cstddef>
 
 #include "device_common.hpp"
@@ -224,17 +228,21 @@ __global__ __launch_bounds__(64) void k_spread_finish(const double* __restrict__
 struct MomentGroupLaunch {
     SweepCommon sw;
     u64 ntiles;
-    const int32_t* keys[2];  // [0]: the group column, [1]: the other column when the filter has a term on it
+    const int32_t* keys[2];  // [0]: the group column, [1]: the other column when the filter has a term on it (kPair: columns A, B)
     int32_t key_min;
     uint32_t nbins;
+    int32_t key_min_b;       // kPair: column B's smallest key and span; nbins = span_a * span_b
+    uint32_t span_b;
     double* partial;         // [gridDim.x][nbins][kSpBin]: n, P1, P2, P3, P4, visited
     DevFilter flt;           // kFiltered: t[0] judges the group column (pass-all when it has no term), t[1] the other
 };
+static_assert(sizeof(MomentGroupLaunch) <= 4096, "kernel arguments are limited to 4 KB");
 
 // kFiltered = false is the unfiltered grouped spread (NK = 1): no map is staged and no term is tested.
-template <bool kPrivate, bool kNT, int NK, bool kFiltered>
+// kPair bins on both keys (NK = 2); kFiltered then tests t[0] on column A and t[1] on column B (pass-all without a term).
+template <bool kPrivate, bool kNT, int NK, bool kFiltered, bool kPair = false>
 __global__ __launch_bounds__(kBlockThreads) void k_moments_grouped(MomentGroupLaunch a) {
-    static_assert(NK == 1 || (NK == 2 && kFiltered), "the group column, and the other one only under a term on it");
+    static_assert(kPair ? NK == 2 : (NK == 1 || (NK == 2 && kFiltered)), "the group column, and the other one only under a term on it or as column B");
     extern __shared__ double lds[];
     __shared__ DevFamily lds_fams[kMaxLdsFams];
     __shared__ u64 s_map[2][kMapWords];
@@ -261,13 +269,20 @@ __global__ __launch_bounds__(kBlockThreads) void k_moments_grouped(MomentGroupLa
     const double c = a.sw.shift, wmin = a.sw.wmin, wmax = a.sw.wmax;
     const bool has_where = a.sw.has_where != 0;
     const int kmin = a.key_min;
+    const int kmin_b = kPair ? a.key_min_b : 0;
+    const unsigned span_b = kPair ? a.span_b : 1u, span_a = kPair ? nb / span_b : nb;
     const DevTerm T0 = a.flt.t[0], T1 = a.flt.t[1];
     auto visit = [&](double x, int key, int other, bool ok) {
-        const unsigned b = static_cast<unsigned>(key - kmin);
+        unsigned b = static_cast<unsigned>(key - kmin);
+        if constexpr (kPair) {
+            const unsigned bb = static_cast<unsigned>(other - kmin_b);
+            if (b >= span_a || bb >= span_b) return;  // (does not occur either: no bin outside [0, nb) is ever formed)
+            b = b * span_b + bb;
+        }
         if (!ok || b >= nb) return;  // (the host checked the shard's key range: b >= nb does not occur)
         bool pass = !has_where || (x >= wmin && x <= wmax);
         if constexpr (kFiltered) pass = pass && term_pass(T0, s_map[0], key);
-        if constexpr (NK >= 2) pass = pass && term_pass(T1, s_map[1], other);
+        if constexpr (NK >= 2 && kFiltered) pass = pass && term_pass(T1, s_map[1], other);
         const double d = x - c, d2 = d * d;
         if (kPrivate) {  // a word of its own per lane and bin: the add never conflicts
             const unsigned i = b * kBlockThreads + tid;
@@ -337,14 +352,10 @@ __global__ __launch_bounds__(64) void k_bins_sum(const double* __restrict__ part
 
 // One thread per bin: SUM / AVG / COUNT of the group and its interval from the (all-reduced) sums — the arithmetic of
 // k_grouped_finish (grouped.hip, group_result; executor.cpp:280-296) on the bin's n, P1, P2, visited.
-__global__ __launch_bounds__(64) void k_groups_finish(const double* __restrict__ bins, unsigned nbins, int32_t key_min, double c, double pct, int agg,
-                                                      aqe_group_result* __restrict__ out) {
-    const unsigned b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= nbins) return;
-    const double* v = bins + static_cast<size_t>(b) * kSpBin;
+__device__ __forceinline__ aqe_group_result group_result(const double* v, int64_t key, double c, double pct, int agg) {
     const double n = v[0], sd = v[1], qd = v[2];
     aqe_group_result r;
-    r.key = static_cast<int64_t>(key_min) + b;
+    r.key = key;
     r.n = static_cast<uint64_t>(n);
     r.visited = static_cast<uint64_t>(v[5]);
     r.sum = sd + n * c;
@@ -362,25 +373,56 @@ __global__ __launch_bounds__(64) void k_groups_finish(const double* __restrict__
     r.value = value;
     r.ci_lower = value - margin;
     r.ci_upper = value + margin;
-    out[b] = r;
+    return r;
+}
+__global__ __launch_bounds__(64) void k_groups_finish(const double* __restrict__ bins, unsigned nbins, int32_t key_min, double c, double pct, int agg,
+                                                      aqe_group_result* __restrict__ out) {
+    const unsigned b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= nbins) return;
+    out[b] = group_result(bins + static_cast<size_t>(b) * kSpBin, static_cast<int64_t>(key_min) + b, c, pct, agg);
+}
+
+// The two columns' ranges of a pair, and bin -> (a, b) as the results carry it (AQE_GROUP_KEY_PACK of include/aqe_hip.h).
+struct PairRange {
+    int32_t kmin_a, kmin_b;
+    uint32_t span_a, span_b;
+};
+__host__ __device__ inline int64_t pair_key(const PairRange& g, unsigned bin) {
+    const int32_t ka = static_cast<int32_t>(static_cast<int64_t>(g.kmin_a) + bin / g.span_b);
+    const int32_t kb = static_cast<int32_t>(static_cast<int64_t>(g.kmin_b) + bin % g.span_b);
+    return AQE_GROUP_KEY_PACK(ka, kb);
+}
+__global__ __launch_bounds__(64) void k_groups_finish_pair(const double* __restrict__ bins, PairRange g, double c, double pct, int agg,
+                                                           aqe_group_result* __restrict__ out) {
+    const unsigned b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= g.span_a * g.span_b) return;
+    out[b] = group_result(bins + static_cast<size_t>(b) * kSpBin, pair_key(g, b), c, pct, agg);
 }
 
 // One thread per bin: VARIANCE / STDDEV of the group and its interval from the (all-reduced) sums.
-__global__ __launch_bounds__(64) void k_spread_groups_finish(const double* __restrict__ bins, unsigned nbins, int32_t key_min, double c, SpreadFin fin,
-                                                             aqe_spread_group_result* __restrict__ out) {
-    const unsigned b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= nbins) return;
-    const double* v = bins + static_cast<size_t>(b) * kSpBin;
+__device__ __forceinline__ aqe_spread_group_result spread_group_result(const double* v, int64_t key, double c, const SpreadFin& fin) {
     const SpreadCore k = spread_core(v[0], v[1], v[2], v[3], v[4], c, fin);
     aqe_spread_group_result r;
-    r.key = static_cast<int64_t>(key_min) + b;
+    r.key = key;
     r.value = k.value; r.ci_lower = k.lo; r.ci_upper = k.hi;
     r.mean = k.mean; r.m2 = k.m2; r.m3 = k.m3; r.m4 = k.m4;
     r.n = static_cast<uint64_t>(v[0]);
     r.visited = static_cast<uint64_t>(v[5]);
     r.has_interval = k.has_interval;
     r.pad = 0;
-    out[b] = r;
+    return r;
+}
+__global__ __launch_bounds__(64) void k_spread_groups_finish(const double* __restrict__ bins, unsigned nbins, int32_t key_min, double c, SpreadFin fin,
+                                                             aqe_spread_group_result* __restrict__ out) {
+    const unsigned b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= nbins) return;
+    out[b] = spread_group_result(bins + static_cast<size_t>(b) * kSpBin, static_cast<int64_t>(key_min) + b, c, fin);
+}
+__global__ __launch_bounds__(64) void k_spread_groups_finish_pair(const double* __restrict__ bins, PairRange g, double c, SpreadFin fin,
+                                                                  aqe_spread_group_result* __restrict__ out) {
+    const unsigned b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= g.span_a * g.span_b) return;
+    out[b] = spread_group_result(bins + static_cast<size_t>(b) * kSpBin, pair_key(g, b), c, fin);
 }
 
 inline unsigned grid_for(uint64_t work, uint64_t per_block) {
@@ -636,9 +678,21 @@ int spread_finish(aqe_ctx* c, const aqe_query* q, int kind, const double* dev_ve
     return AQE_OK;
 }
 
+// What a grouped sweep bins on: one key column (col[1] == 0, span[1] == 1) or the ordered pair (A, B) of both.
+struct GroupCols {
+    int col[2];
+    int32_t kmin[2];
+    uint32_t span[2];
+    bool pair() const { return col[1] != 0; }
+    uint32_t nbins() const { return span[0] * span[1]; }
+    PairRange range() const { return PairRange{kmin[0], kmin[1], span[0], span[1]}; }
+};
+inline GroupCols one_column(int column, int32_t key_min, uint32_t nbins) { return GroupCols{{column, 0}, {key_min, 0}, {nbins, 1u}}; }
+
 // This shard's bins [nbins][kSpBin] into dev_bins (zeros when nothing of the sample lies in this shard), under the filter
 // `f` (null: none; the caller has checked it).
-int enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int group_column, int32_t key_min, uint32_t nbins, double* dev_bins, hipStream_t s) {
+int enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const GroupCols& g, double* dev_bins, hipStream_t s) {
+    const uint32_t nbins = g.nbins();
     aqe_plan* p = nullptr;
     int rc = moment_plan(c, q, true, words_for(f), &p);
     if (rc != AQE_OK) return rc;
@@ -653,19 +707,27 @@ int enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int gr
     MomentGroupLaunch a{};
     a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
     a.ntiles = L.ntiles;
-    a.key_min = key_min;
+    a.key_min = g.kmin[0];
     a.nbins = nbins;
-    rc = key_pointer(c, p, group_column, &a.keys[0]);
-    if (rc != AQE_OK) return rc;
-    const int k = group_column - 1;
-    if (c->key_min[k] < key_min || static_cast<int64_t>(c->key_max[k]) - key_min >= static_cast<int64_t>(nbins))
-        return fail(c, AQE_ERR_INVALID, "this shard has keys outside [key_min, key_min + nbins)");
+    a.key_min_b = g.kmin[1];
+    a.span_b = g.span[1];
+    const bool pair = g.pair();
+    for (int i = 0; i < (pair ? 2 : 1); ++i) {
+        rc = key_pointer(c, p, g.col[i], &a.keys[i]);
+        if (rc != AQE_OK) return rc;
+        const int k = g.col[i] - 1;
+        if (c->key_min[k] < g.kmin[i] || static_cast<int64_t>(c->key_max[k]) - g.kmin[i] >= static_cast<int64_t>(g.span[i]))
+            return fail(c, AQE_ERR_INVALID, pair ? "this shard has keys outside [key_min, key_min + span) of a column of the pair"
+                                                 : "this shard has keys outside [key_min, key_min + nbins)");
+    }
     a.flt.t[0] = a.flt.t[1] = pass_all();
-    int nk = 1;
+    int nk = pair ? 2 : 1;
     if (f) {
-        compile_term(f->term[k], &a.flt.t[0], a.flt.map[0]);
-        const int other = group_column == AQE_GROUP_REGION ? AQE_GROUP_PRODUCT : AQE_GROUP_REGION;
-        if (f->term[other - 1].form != AQE_KEYTERM_NONE) {
+        compile_term(f->term[g.col[0] - 1], &a.flt.t[0], a.flt.map[0]);
+        const int other = g.col[0] == AQE_GROUP_REGION ? AQE_GROUP_PRODUCT : AQE_GROUP_REGION;  // (column B of a pair)
+        if (pair) {
+            compile_term(f->term[other - 1], &a.flt.t[1], a.flt.map[1]);
+        } else if (f->term[other - 1].form != AQE_KEYTERM_NONE) {
             compile_term(f->term[other - 1], &a.flt.t[1], a.flt.map[1]);
             rc = key_pointer(c, p, other, &a.keys[1]);
             if (rc != AQE_OK) return rc;
@@ -690,12 +752,14 @@ int enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int gr
     const size_t lds_bytes = priv ? static_cast<size_t>(nbins) * kBlockThreads * 5 * sizeof(double)
                                   : static_cast<size_t>(replicas_for(nbins)) * replica_stride(nbins) * kSpBin * sizeof(double);
     const bool nt = a.sw.nt != 0;
-    const dim3 g(grid), b(kBlockThreads);
+    const dim3 gd(grid), bd(kBlockThreads);
 #define AQE_MG_LAUNCH(PRIV, NT)                                                                               \
-    do {                                                                                                      \
-        if (!f) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 1, false>), g, b, lds_bytes, s, a);           \
-        else if (nk == 1) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 1, true>), g, b, lds_bytes, s, a);  \
-        else hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 2, true>), g, b, lds_bytes, s, a);               \
+    do {                                                                                                             \
+        if (pair && !f) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 2, false, true>), gd, bd, lds_bytes, s, a);  \
+        else if (pair) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 2, true, true>), gd, bd, lds_bytes, s, a);    \
+        else if (!f) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 1, false>), gd, bd, lds_bytes, s, a);           \
+        else if (nk == 1) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 1, true>), gd, bd, lds_bytes, s, a);       \
+        else hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 2, true>), gd, bd, lds_bytes, s, a);                    \
     } while (0)
     if (priv) {
         if (nt) AQE_MG_LAUNCH(true, true);
@@ -728,51 +792,96 @@ int collect_groups(aqe_ctx* c, hipStream_t s, const Group* groups, uint32_t nbin
     return AQE_OK;
 }
 
-int finish_groups(aqe_ctx* c, const aqe_query* q, int32_t key_min, uint32_t nbins, const double* dev_bins, hipStream_t s, aqe_group_result* out,
-                  uint32_t cap, uint32_t* n_groups) {
+int finish_groups(aqe_ctx* c, const aqe_query* q, const GroupCols& g, const double* dev_bins, hipStream_t s, aqe_group_result* out, uint32_t cap,
+                  uint32_t* n_groups) {
     aqe_moment_scratch* sc = c->moments;
-    hipLaunchKernelGGL(k_groups_finish, dim3((nbins + 63) / 64), dim3(64), 0, s, dev_bins, nbins, key_min, query_shift(c, *q), q->sample_percent, q->agg,
-                       sc->d_groups);
+    const uint32_t nbins = g.nbins();
+    const dim3 grid((nbins + 63) / 64), block(64);
+    if (g.pair()) hipLaunchKernelGGL(k_groups_finish_pair, grid, block, 0, s, dev_bins, g.range(), query_shift(c, *q), q->sample_percent, q->agg, sc->d_groups);
+    else hipLaunchKernelGGL(k_groups_finish, grid, block, 0, s, dev_bins, nbins, g.kmin[0], query_shift(c, *q), q->sample_percent, q->agg, sc->d_groups);
     return collect_groups(c, s, sc->h_groups, nbins, out, cap, n_groups);
 }
 
-int finish_spread_groups(aqe_ctx* c, const aqe_query* q, int kind, int32_t key_min, uint32_t nbins, const double* dev_bins, hipStream_t s,
+int finish_spread_groups(aqe_ctx* c, const aqe_query* q, int kind, const GroupCols& g, const double* dev_bins, hipStream_t s,
                          aqe_spread_group_result* out, uint32_t cap, uint32_t* n_groups) {
     aqe_moment_scratch* sc = c->moments;
-    hipLaunchKernelGGL(k_spread_groups_finish, dim3((nbins + 63) / 64), dim3(64), 0, s, dev_bins, nbins, key_min, query_shift(c, *q), fin_for(q, kind),
-                       sc->d_sgroups);
+    const uint32_t nbins = g.nbins();
+    const dim3 grid((nbins + 63) / 64), block(64);
+    if (g.pair()) hipLaunchKernelGGL(k_spread_groups_finish_pair, grid, block, 0, s, dev_bins, g.range(), query_shift(c, *q), fin_for(q, kind), sc->d_sgroups);
+    else hipLaunchKernelGGL(k_spread_groups_finish, grid, block, 0, s, dev_bins, nbins, g.kmin[0], query_shift(c, *q), fin_for(q, kind), sc->d_sgroups);
     return collect_groups(c, s, sc->h_sgroups, nbins, out, cap, n_groups);
 }
 
-// The key range of the group column and the sweep into the context's own bins (the single-GPU grouped entries).
-// nbins_out stays 0 for an empty table: no groups.
-int grouped_prologue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int group_column, uint32_t* n_groups, int32_t* kmin_out, uint32_t* nbins_out) {
+const char* column_name(int column) { return column == AQE_GROUP_REGION ? "region" : "product_id"; }
+
+// The key range of the group column(s) — cols[1] == 0: one column — and the sweep into the context's own bins (the
+// single-GPU grouped entries).  out->span[0] stays 0 for an empty table: no groups.
+int grouped_prologue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int cols[2], uint32_t* n_groups, GroupCols* out) {
     *n_groups = 0;
-    *nbins_out = 0;
-    int32_t kmin = 0, kmax = -1;
-    int rc = aqe_group_key_range(c, group_column, &kmin, &kmax);
-    if (rc != AQE_OK) return rc;
-    if (kmax < kmin) return AQE_OK;
-    const int64_t span = static_cast<int64_t>(kmax) - kmin + 1;
-    if (span > kMaxGroupBins) return fail(c, AQE_ERR_UNSUPPORTED, "group column spans more than 1024 distinct values");
+    GroupCols g{{cols[0], cols[1]}, {0, 0}, {0u, 1u}};
+    *out = g;
+    int64_t span[2] = {0, 1};
+    for (int i = 0; i < (g.pair() ? 2 : 1); ++i) {
+        int32_t kmin = 0, kmax = -1;
+        const int rc = aqe_group_key_range(c, g.col[i], &kmin, &kmax);
+        if (rc != AQE_OK) return rc;
+        if (kmax < kmin) return AQE_OK;
+        g.kmin[i] = kmin;
+        span[i] = static_cast<int64_t>(kmax) - kmin + 1;
+    }
+    if (!g.pair() && span[0] > kMaxGroupBins) return fail(c, AQE_ERR_UNSUPPORTED, "group column spans more than 1024 distinct values");
+    if (g.pair() && (span[0] > kMaxGroupBins || span[1] > kMaxGroupBins || span[0] * span[1] > kMaxGroupBins))
+        return fail(c, AQE_ERR_UNSUPPORTED, std::string("GROUP BY ") + column_name(g.col[0]) + ", " + column_name(g.col[1]) + ": the columns span " +
+                                                std::to_string(span[0]) + " x " + std::to_string(span[1]) + " keys, more than 1024 bins");
+    g.span[0] = static_cast<uint32_t>(span[0]);
+    g.span[1] = static_cast<uint32_t>(span[1]);
     HIPCHK(c, hipSetDevice(c->device));
-    rc = ensure_scratch(c);
+    int rc = ensure_scratch(c);
     if (rc != AQE_OK) return rc;
-    rc = enqueue_bins(c, f, q, group_column, kmin, static_cast<uint32_t>(span), c->moments->d_bins, c->stream);
+    rc = enqueue_bins(c, f, q, g, c->moments->d_bins, c->stream);
     if (rc != AQE_OK) return rc;
-    *kmin_out = kmin;
-    *nbins_out = static_cast<uint32_t>(span);
+    *out = g;
     return AQE_OK;
 }
 
 // The single-GPU grouped spread entries behind their argument checks.
-int grouped_spread(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int kind, int group_column, aqe_spread_group_result* out, uint32_t cap,
+int grouped_spread(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int kind, const int cols[2], aqe_spread_group_result* out, uint32_t cap,
                    uint32_t* n_groups) {
-    int32_t kmin = 0;
-    uint32_t nbins = 0;
-    const int rc = grouped_prologue(c, f, q, group_column, n_groups, &kmin, &nbins);
-    if (rc != AQE_OK || nbins == 0) return rc;
-    return finish_spread_groups(c, q, kind, kmin, nbins, c->moments->d_bins, c->stream, out, cap, n_groups);
+    GroupCols g;
+    const int rc = grouped_prologue(c, f, q, cols, n_groups, &g);
+    if (rc != AQE_OK || g.span[0] == 0) return rc;
+    return finish_spread_groups(c, q, kind, g, c->moments->d_bins, c->stream, out, cap, n_groups);
+}
+
+// SUM / AVG / COUNT per group, likewise.
+int grouped_result(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int cols[2], aqe_group_result* out, uint32_t cap, uint32_t* n_groups) {
+    GroupCols g;
+    const int rc = grouped_prologue(c, f, q, cols, n_groups, &g);
+    if (rc != AQE_OK || g.span[0] == 0) return rc;
+    return finish_groups(c, q, g, c->moments->d_bins, c->stream, out, cap, n_groups);
+}
+
+// The columns of a pair entry: {REGION, PRODUCT} in either order.
+int pair_columns_ok(aqe_ctx* c, const int* cols) {
+    if (!cols) return fail(c, AQE_ERR_INVALID, "null argument");
+    for (int i = 0; i < 2; ++i)
+        if (cols[i] != AQE_GROUP_REGION && cols[i] != AQE_GROUP_PRODUCT) return fail(c, AQE_ERR_INVALID, "a column of the pair is neither AQE_GROUP_REGION nor AQE_GROUP_PRODUCT");
+    if (cols[0] == cols[1]) return fail(c, AQE_ERR_INVALID, "the pair names one column twice");
+    return AQE_OK;
+}
+
+// The agreed ranges of the multi-GPU pair entries.
+int pair_range_ok(aqe_ctx* c, const int* cols, const int32_t* key_min, const uint32_t* span, GroupCols* out) {
+    int rc = pair_columns_ok(c, cols);
+    if (rc != AQE_OK) return rc;
+    if (!key_min || !span) return fail(c, AQE_ERR_INVALID, "null argument");
+    const uint64_t bins = static_cast<uint64_t>(span[0]) * span[1];
+    if (span[0] == 0 || span[1] == 0) return fail(c, AQE_ERR_INVALID, "a span of the pair is zero");
+    if (bins > static_cast<uint64_t>(kMaxGroupBins))
+        return fail(c, AQE_ERR_UNSUPPORTED, std::string("GROUP BY ") + column_name(cols[0]) + ", " + column_name(cols[1]) + ": the columns span " +
+                                                std::to_string(span[0]) + " x " + std::to_string(span[1]) + " keys, more than 1024 bins");
+    *out = GroupCols{{cols[0], cols[1]}, {key_min[0], key_min[1]}, {span[0], span[1]}};
+    return AQE_OK;
 }
 
 // What the multi-GPU grouped enqueues check of their arguments, and the device.
@@ -863,7 +972,8 @@ int aqe_reduce_grouped_spread(aqe_ctx* c, const aqe_query* q, int kind, int grou
     int rc = check_kind(c, kind);
     if (rc == AQE_OK) rc = group_column_ok(c, group_column);
     if (rc != AQE_OK) return rc;
-    return grouped_spread(c, nullptr, q, kind, group_column, out, cap, n_groups);
+    const int cols[2] = {group_column, 0};
+    return grouped_spread(c, nullptr, q, kind, cols, out, cap, n_groups);
 }
 
 int aqe_grouped_spread_enqueue_bins(aqe_ctx* c, const aqe_query* q, int group_column, int32_t key_min, uint32_t nbins, double* dev_bins,
@@ -871,7 +981,7 @@ int aqe_grouped_spread_enqueue_bins(aqe_ctx* c, const aqe_query* q, int group_co
     if (!c) return AQE_ERR_INVALID;
     const int rc = bins_arguments(c, group_column, dev_bins, nbins);
     if (rc != AQE_OK) return rc;
-    return enqueue_bins(c, nullptr, q, group_column, key_min, nbins, dev_bins, stream_of(c, stream));
+    return enqueue_bins(c, nullptr, q, one_column(group_column, key_min, nbins), dev_bins, stream_of(c, stream));
 }
 
 int aqe_grouped_spread_finish(aqe_ctx* c, const aqe_query* q, int kind, int32_t key_min, uint32_t nbins, const double* dev_bins, void* stream,
@@ -885,7 +995,7 @@ int aqe_grouped_spread_finish(aqe_ctx* c, const aqe_query* q, int kind, int32_t 
     *n_groups = 0;
     rc = ensure_scratch(c);
     if (rc != AQE_OK) return rc;
-    return finish_spread_groups(c, q, kind, key_min, nbins, dev_bins, stream_of(c, stream), out, cap, n_groups);
+    return finish_spread_groups(c, q, kind, one_column(AQE_GROUP_REGION, key_min, nbins), dev_bins, stream_of(c, stream), out, cap, n_groups);
 }
 
 // ---- key predicates ---------------------------------------------------------------------------------------------------------
@@ -976,11 +1086,8 @@ int aqe_reduce_filtered_grouped(aqe_ctx* c, const aqe_key_filter* f, const aqe_q
     int rc = group_column_ok(c, group_column);
     if (rc == AQE_OK) rc = check_filter(c, f);
     if (rc != AQE_OK) return rc;
-    int32_t kmin = 0;
-    uint32_t nbins = 0;
-    rc = grouped_prologue(c, f, q, group_column, n_groups, &kmin, &nbins);
-    if (rc != AQE_OK || nbins == 0) return rc;
-    return finish_groups(c, q, kmin, nbins, c->moments->d_bins, c->stream, out, cap, n_groups);
+    const int cols[2] = {group_column, 0};
+    return grouped_result(c, f, q, cols, out, cap, n_groups);
 }
 
 int aqe_reduce_filtered_grouped_spread(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int kind, int group_column,
@@ -991,7 +1098,8 @@ int aqe_reduce_filtered_grouped_spread(aqe_ctx* c, const aqe_key_filter* f, cons
     if (rc == AQE_OK) rc = group_column_ok(c, group_column);
     if (rc == AQE_OK) rc = check_filter(c, f);
     if (rc != AQE_OK) return rc;
-    return grouped_spread(c, f, q, kind, group_column, out, cap, n_groups);
+    const int cols[2] = {group_column, 0};
+    return grouped_spread(c, f, q, kind, cols, out, cap, n_groups);
 }
 
 int aqe_filtered_grouped_enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int group_column, int32_t key_min, uint32_t nbins,
@@ -1000,7 +1108,7 @@ int aqe_filtered_grouped_enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const
     int rc = bins_arguments(c, group_column, dev_bins, nbins);
     if (rc == AQE_OK) rc = check_filter(c, f);
     if (rc != AQE_OK) return rc;
-    return enqueue_bins(c, f, q, group_column, key_min, nbins, dev_bins, stream_of(c, stream));
+    return enqueue_bins(c, f, q, one_column(group_column, key_min, nbins), dev_bins, stream_of(c, stream));
 }
 
 int aqe_filtered_grouped_finish(aqe_ctx* c, const aqe_query* q, int32_t key_min, uint32_t nbins, const double* dev_bins, void* stream,
@@ -1013,7 +1121,76 @@ int aqe_filtered_grouped_finish(aqe_ctx* c, const aqe_query* q, int32_t key_min,
     *n_groups = 0;
     int rc = ensure_scratch(c);
     if (rc != AQE_OK) return rc;
-    return finish_groups(c, q, key_min, nbins, dev_bins, stream_of(c, stream), out, cap, n_groups);
+    return finish_groups(c, q, one_column(AQE_GROUP_REGION, key_min, nbins), dev_bins, stream_of(c, stream), out, cap, n_groups);
+}
+
+// ---- GROUP BY both key columns ----------------------------------------------------------------------------------------------
+
+int aqe_reduce_grouped_pair(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int* columns, aqe_group_result* out, uint32_t cap,
+                            uint32_t* n_groups) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_groups || (cap && !out)) return fail(c, AQE_ERR_INVALID, "null argument");
+    int rc = pair_columns_ok(c, columns);
+    if (rc == AQE_OK && f) rc = check_filter(c, f);
+    if (rc != AQE_OK) return rc;
+    return grouped_result(c, f, q, columns, out, cap, n_groups);
+}
+
+int aqe_reduce_grouped_pair_spread(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int kind, const int* columns,
+                                   aqe_spread_group_result* out, uint32_t cap, uint32_t* n_groups) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_groups || (cap && !out)) return fail(c, AQE_ERR_INVALID, "null argument");
+    int rc = check_kind(c, kind);
+    if (rc == AQE_OK) rc = pair_columns_ok(c, columns);
+    if (rc == AQE_OK && f) rc = check_filter(c, f);
+    if (rc != AQE_OK) return rc;
+    return grouped_spread(c, f, q, kind, columns, out, cap, n_groups);
+}
+
+int aqe_grouped_pair_enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int* columns, const int32_t* key_min,
+                                  const uint32_t* span, double* dev_bins, void* stream) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!dev_bins) return fail(c, AQE_ERR_INVALID, "null dev_bins");
+    GroupCols g;
+    int rc = pair_range_ok(c, columns, key_min, span, &g);
+    if (rc == AQE_OK && f) rc = check_filter(c, f);
+    if (rc != AQE_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return enqueue_bins(c, f, q, g, dev_bins, stream_of(c, stream));
+}
+
+int aqe_grouped_pair_finish(aqe_ctx* c, const aqe_query* q, const int32_t* key_min, const uint32_t* span, const double* dev_bins, void* stream,
+                            aqe_group_result* out, uint32_t cap, uint32_t* n_groups) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_groups || (cap && !out) || !dev_bins) return fail(c, AQE_ERR_INVALID, "bad argument");
+    const int cols[2] = {AQE_GROUP_REGION, AQE_GROUP_PRODUCT};  // (the finish reads the ranges, not the columns)
+    GroupCols g;
+    int rc = pair_range_ok(c, cols, key_min, span, &g);
+    if (rc != AQE_OK) return rc;
+    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
+    if (!(q->sample_percent > 0.0)) return fail(c, AQE_ERR_INVALID, "sample_percent must be positive");
+    HIPCHK(c, hipSetDevice(c->device));
+    *n_groups = 0;
+    rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    return finish_groups(c, q, g, dev_bins, stream_of(c, stream), out, cap, n_groups);
+}
+
+int aqe_grouped_pair_spread_finish(aqe_ctx* c, const aqe_query* q, int kind, const int32_t* key_min, const uint32_t* span, const double* dev_bins,
+                                   void* stream, aqe_spread_group_result* out, uint32_t cap, uint32_t* n_groups) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_groups || (cap && !out) || !dev_bins) return fail(c, AQE_ERR_INVALID, "bad argument");
+    int rc = check_kind(c, kind);
+    const int cols[2] = {AQE_GROUP_REGION, AQE_GROUP_PRODUCT};
+    GroupCols g;
+    if (rc == AQE_OK) rc = pair_range_ok(c, cols, key_min, span, &g);
+    if (rc != AQE_OK) return rc;
+    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
+    HIPCHK(c, hipSetDevice(c->device));
+    *n_groups = 0;
+    rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    return finish_spread_groups(c, q, kind, g, dev_bins, stream_of(c, stream), out, cap, n_groups);
 }
 
 }  // extern "C"

@@ -394,6 +394,40 @@ def sharded_filtered_group_by(engine, key_filter, query, group_column: int, bins
         return engine.grouped_spread_finish(query, kind, kmin, nbins, b.data_ptr(), stream)
 
 
+def sharded_group_by_pair(engine, query, columns, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None,
+                          kind=None):
+    """GROUP BY both key columns across ranks, collective: ``columns`` is the ordered pair (A, B).  Both key ranges are agreed
+    in ONE MAX all-reduce of [-minA, maxA, -minB, maxB]; every rank bins its part of the sample into spanA x spanB x SPREAD_BIN
+    sums (aqe_grouped_pair_enqueue_bins, under ``key_filter`` when there is one), ONE all-reduce SUM merges them and every rank
+    finishes the same bins — kind None: SUM / AVG / COUNT per pair, kind = SPREAD_*: VARIANCE / STDDEV per pair — so every rank
+    returns the same bits.  More than 1024 bins is refused on every rank alike, before the sweep.
+
+    bins    float64 tensor on the engine's device with room for SPREAD_BIN * spanA * spanB doubles (at most SPREAD_BIN * 1024)"""
+    from ._native import ERR_UNSUPPORTED, SPREAD_BIN, AqeError
+    stream = _stream_for(stream, bins)
+    cols = [int(c) for c in columns]
+    with _torch_on(stream, bins):
+        (lo_a, hi_a), (lo_b, hi_b) = engine.group_key_range(cols[0]), engine.group_key_range(cols[1])
+        rng = bins.new_tensor([-float(lo_a), float(hi_a), -float(lo_b), float(hi_b)])
+        all_reduce_max(rng)
+        r = [int(v) for v in rng.tolist()]
+        kmin, kmax = (-r[0], -r[2]), (r[1], r[3])
+        if kmax[0] < kmin[0] or kmax[1] < kmin[1]:
+            return []  # an empty table
+        span = (kmax[0] - kmin[0] + 1, kmax[1] - kmin[1] + 1)
+        nbins = span[0] * span[1]
+        if nbins > 1024:
+            raise AqeError(ERR_UNSUPPORTED, f"GROUP BY over both key columns: the columns span {span[0]} x {span[1]} keys, more than 1024 bins")
+        if bins.numel() < SPREAD_BIN * nbins:
+            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {SPREAD_BIN * nbins} needed")
+        b = bins[: SPREAD_BIN * nbins]
+        engine.grouped_pair_enqueue_bins(query, cols, kmin, span, b.data_ptr(), stream, key_filter)
+        all_reduce_sum(b)
+        if kind is None:
+            return engine.grouped_pair_finish(query, kmin, span, b.data_ptr(), stream)
+        return engine.grouped_pair_spread_finish(query, kind, kmin, span, b.data_ptr(), stream)
+
+
 # ---- the variance-aware samplers over a sharded table (SURVEY 8e "what does not shard") ---------------------------------
 # Both need one fact about the WHOLE table before a shard can plan (include/aqe_hip.h, the block above aqe_zone_moments).
 # The exchanges below are small host arrays, once per table and query shape — `host_all_reduce_sum(a) -> a summed over the

@@ -538,6 +538,43 @@ class Engine:
                                                         C.c_void_p(stream), out, max_groups, C.byref(n)))
         return list(out[: n.value])
 
+    # -- GROUP BY both key columns (aqe_reduce_grouped_pair and its kin): `columns` is the ordered pair (A, B), key_filter may be None --
+    def reduce_grouped_pair(self, query: Query, columns: Sequence[int], key_filter: "Optional[nat.KeyFilter]" = None, max_groups: int = 1024):
+        """SUM / AVG / COUNT per (a, b): list of GroupResult ascending by (a, b); ``key`` packs both (nat.group_key_unpack)."""
+        out = (nat.GroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_reduce_grouped_pair(self._h, _filter_ref(key_filter), C.byref(query), _pair(C.c_int, columns), out, max_groups, C.byref(n)))
+        return list(out[: n.value])
+
+    def reduce_grouped_pair_spread(self, query: Query, kind: int, columns: Sequence[int], key_filter: "Optional[nat.KeyFilter]" = None,
+                                   max_groups: int = 1024):
+        out = (nat.SpreadGroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_reduce_grouped_pair_spread(self._h, _filter_ref(key_filter), C.byref(query), int(kind), _pair(C.c_int, columns), out,
+                                                           max_groups, C.byref(n)))
+        return list(out[: n.value])
+
+    def grouped_pair_enqueue_bins(self, query: Query, columns: Sequence[int], key_min: Sequence[int], span: Sequence[int], dev_bins_ptr: int,
+                                  stream: int = 0, key_filter: "Optional[nat.KeyFilter]" = None):
+        """This shard's span[0] * span[1] x SPREAD_BIN sums into device memory (all-reduce SUM, then a pair finish)."""
+        self._chk(nat.lib().aqe_grouped_pair_enqueue_bins(self._h, _filter_ref(key_filter), C.byref(query), _pair(C.c_int, columns),
+                                                          _pair(C.c_int32, key_min), _pair(C.c_uint32, span), C.c_void_p(dev_bins_ptr), C.c_void_p(stream)))
+
+    def grouped_pair_finish(self, query: Query, key_min: Sequence[int], span: Sequence[int], dev_bins_ptr: int, stream: int = 0, max_groups: int = 1024):
+        out = (nat.GroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_grouped_pair_finish(self._h, C.byref(query), _pair(C.c_int32, key_min), _pair(C.c_uint32, span), C.c_void_p(dev_bins_ptr),
+                                                    C.c_void_p(stream), out, max_groups, C.byref(n)))
+        return list(out[: n.value])
+
+    def grouped_pair_spread_finish(self, query: Query, kind: int, key_min: Sequence[int], span: Sequence[int], dev_bins_ptr: int, stream: int = 0,
+                                   max_groups: int = 1024):
+        out = (nat.SpreadGroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_grouped_pair_spread_finish(self._h, C.byref(query), int(kind), _pair(C.c_int32, key_min), _pair(C.c_uint32, span),
+                                                           C.c_void_p(dev_bins_ptr), C.c_void_p(stream), out, max_groups, C.byref(n)))
+        return list(out[: n.value])
+
     def gather(self, query: Query) -> np.ndarray:
         """Rows of the record-returning sampler, as a RECORD_DTYPE array."""
         n = C.c_uint64()
@@ -712,6 +749,18 @@ class QuantileRun:
             self.close()
         except Exception:
             pass
+
+
+def _pair(ctype, values):
+    """Two values as the C array a pair entry takes (ValueError for any other count)."""
+    vals = [int(v) for v in values]
+    if len(vals) != 2:
+        raise ValueError(f"a pair takes two values, got {len(vals)}")
+    return (ctype * 2)(*vals)
+
+
+def _filter_ref(key_filter):
+    return None if key_filter is None else C.byref(key_filter)
 
 
 def make_query(method: int, sample_percent: float = 10.0, agg: int = nat.SUM, convention: int = nat.EST_CLI,

@@ -25,8 +25,8 @@ from typing import List, Optional
 import numpy as np
 
 from . import _native as nat
-from .aqe_backend import ApproxResult, CustomBPlusDB, GroupEstimate, _AGG, _key_filter_for, _quantile_call
-from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, shard_bounds, sharded_adaptive_plan, sharded_group_by, sharded_filtered, sharded_filtered_group_by, sharded_group_by_spread, sharded_quantiles, sharded_spread,
+from .aqe_backend import ApproxResult, CustomBPlusDB, GroupEstimate, _AGG, _key_filter_for, _pair_groups, _quantile_call, group_columns
+from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, shard_bounds, sharded_adaptive_plan, sharded_group_by, sharded_filtered, sharded_filtered_group_by, sharded_group_by_pair, sharded_group_by_spread, sharded_quantiles, sharded_spread,
                           sharded_stratified_plan, torch_all_reduce, torch_host_all_reduce)
 from .engine import RECORD_DTYPE, Batch, Engine, make_query
 
@@ -234,13 +234,17 @@ class ShardedBPlusDB(CustomBPlusDB):
     def approx_group_by(self, agg: str, group_by: str = "region", sample_percent: float = 10.0, method: str = "rowid",
                         where=None, block_size: int = 1000, key_where=None) -> "dict[str, GroupEstimate]":
         """GROUP BY over all ranks: the key range is agreed (one MAX all-reduce), every rank bins the part of the sample inside
-        its region, ONE all-reduce SUM merges the bins (distributed.sharded_group_by)."""
+        its region, ONE all-reduce SUM merges the bins (distributed.sharded_group_by; both columns: sharded_group_by_pair)."""
         import torch
-        col = {"region": nat.GROUP_REGION, "product_id": nat.GROUP_PRODUCT}[group_by.strip().lower()]
+        cols = group_columns(group_by)
+        col = cols[0]
         m = {"rowid": nat.M_ROWID_MOD, "stride": nat.M_MEMORY_STRIDE, "block": nat.M_BLOCK, "page": nat.M_PAGE, "exact": nat.M_EXACT}[method]
         self._eng()
         bs = 4096 if (method == "page" and block_size == 1000) else block_size
         q = make_query(m, sample_percent, agg=_AGG[agg.upper()], where=where, block_size=int(bs))
+        if len(cols) == 2:
+            f = None if key_where is None else _key_filter_for(key_where, method)
+            return _pair_groups(_quantile_call(lambda: self._grouped_pair(f, q, cols)), GroupEstimate)
         if key_where is not None:
             f = _key_filter_for(key_where, method)
             return {str(r.key): GroupEstimate(r) for r in _quantile_call(lambda: self._grouped_filtered(f, q, col))}
@@ -300,3 +304,18 @@ class ShardedBPlusDB(CustomBPlusDB):
         with torch.cuda.stream(self._side):
             bins = self._buffer(nat.SPREAD_BIN * 1024)
             return sharded_filtered_group_by(self._engine, f, q, col, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, kind=kind)
+
+    # ---- GROUP BY both key columns: one MAX all-reduce of both key ranges, one all-reduce SUM of the bins ----
+    def _grouped_pair(self, f, q, cols):
+        import torch
+        self._eng()
+        with torch.cuda.stream(self._side):
+            bins = self._buffer(nat.SPREAD_BIN * 1024)
+            return sharded_group_by_pair(self._engine, q, cols, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)
+
+    def _spread_groups_pair(self, f, q, kind, cols):
+        import torch
+        self._eng()
+        with torch.cuda.stream(self._side):
+            bins = self._buffer(nat.SPREAD_BIN * 1024)
+            return sharded_group_by_pair(self._engine, q, cols, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f, kind=kind)

@@ -585,6 +585,37 @@ AQE_API int aqe_filtered_grouped_finish(aqe_ctx* ctx, const aqe_query* q, int32_
  * n_global is N of the estimators (the row window's size when the query has one).  The shift is vec[6] / vec[0]. */
 AQE_API int aqe_filtered_from_sums(const double vec[AQE_SPREAD_VEC], const aqe_query* q, uint64_t n_global, aqe_result* out);
 
+/* ---- GROUP BY both key columns: GROUP BY region, product_id | product_id, region ------------------
+ * The reference's executor pastes the GROUP BY clause into the statement it runs (EXE:202-321), so it answers a GROUP BY
+ * over both columns.  Here `columns` is the ordered pair (A, B): {AQE_GROUP_REGION, AQE_GROUP_PRODUCT} in either order (a
+ * repeated or unknown column: AQE_ERR_INVALID).  With spanX = maxX - minX + 1 over the table (agreed over all shards), a
+ * sampled row falls into bin (a - minA) * spanB + (b - minB): ONE sweep of the power sums (moments.hip) with both key columns
+ * beside the amount — 16 bytes per sampled row — and one bin {n, P1, P2, P3, P4, visited} per pair.  spanA * spanB <= 1024 is
+ * required; anything larger is AQE_ERR_UNSUPPORTED with both spans in the message, never truncated.  `filter` may be NULL;
+ * with one, a term may sit on either column or both, and a sampled pair none of whose rows pass is listed with n == 0.
+ * Per group SUM / AVG / COUNT as aqe_reduce_filtered_grouped, VARIANCE / STDDEV as aqe_reduce_grouped_spread; samplers and
+ * refusals as there.  Groups ascend by (a, b), signed; only pairs with a sampled row are listed.  The result structs are the
+ * single-column ones: `key` carries both int32 keys, a in the upper and b in the lower half. */
+#define AQE_GROUP_KEY_PACK(a, b) ((int64_t)(((uint64_t)(uint32_t)(int32_t)(a) << 32) | (uint64_t)(uint32_t)(int32_t)(b)))
+#define AQE_GROUP_KEY_MAJOR(k) ((int32_t)(uint32_t)((uint64_t)(int64_t)(k) >> 32))
+#define AQE_GROUP_KEY_MINOR(k) ((int32_t)(uint32_t)((uint64_t)(int64_t)(k) & 0xffffffffu))
+AQE_API int aqe_reduce_grouped_pair(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const int columns[2], aqe_group_result* out,
+                                    uint32_t cap, uint32_t* n_groups);
+AQE_API int aqe_reduce_grouped_pair_spread(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, int kind, const int columns[2],
+                                           aqe_spread_group_result* out, uint32_t cap, uint32_t* n_groups);
+/* Multi-GPU form: aqe_group_key_range per column, all-reduce MIN / MAX, key_min[i] and span[i] = max - min + 1 of column i
+ * of the pair (a shard with keys outside them: AQE_ERR_INVALID), then
+ *     aqe_grouped_pair_enqueue_bins(ctx, filter, q, columns, key_min, span, dev_bins, stream)   span[0] * span[1] x AQE_SPREAD_BIN doubles
+ *     <all-reduce SUM>
+ *     aqe_grouped_pair_finish(ctx, q, key_min, span, dev_bins, stream, out, cap, &n_groups)      SUM / AVG / COUNT per pair
+ *  or aqe_grouped_pair_spread_finish(ctx, q, kind, key_min, span, dev_bins, stream, out, cap, &n_groups); both synchronise `stream`. */
+AQE_API int aqe_grouped_pair_enqueue_bins(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const int columns[2],
+                                          const int32_t key_min[2], const uint32_t span[2], double* dev_bins, void* stream);
+AQE_API int aqe_grouped_pair_finish(aqe_ctx* ctx, const aqe_query* q, const int32_t key_min[2], const uint32_t span[2], const double* dev_bins,
+                                    void* stream, aqe_group_result* out, uint32_t cap, uint32_t* n_groups);
+AQE_API int aqe_grouped_pair_spread_finish(aqe_ctx* ctx, const aqe_query* q, int kind, const int32_t key_min[2], const uint32_t span[2],
+                                           const double* dev_bins, void* stream, aqe_spread_group_result* out, uint32_t cap, uint32_t* n_groups);
+
 /* ---- stepwise / multi-GPU form ----------------------------------------------------------------
  * One process per GPU; each rank plans the same query over its own shard.  Per round:
  *     aqe_plan_enqueue_round(plan, r, dev_vec, stream)     this shard's partial moment vector
