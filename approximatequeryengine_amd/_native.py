@@ -127,6 +127,16 @@ class SpreadGroupResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class GroupErrorInfo(C.Structure):
+    """aqe_group_error_info: where a GROUP BY to an error threshold stopped."""
+    _fields_ = [("level", C.c_uint32), ("levels", C.c_uint32), ("sample_percent", C.c_double), ("visited", C.c_uint64),
+                ("converged", C.c_int32), ("unsettled", C.c_uint32), ("worst_key", C.c_int64), ("worst_rel", C.c_double),
+                ("launches", C.c_uint32), ("reserved", C.c_uint32), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 class KeyTerm(C.Structure):
     _fields_ = [("form", C.c_int32), ("negate", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("bits", C.c_uint64 * (KEY_BITMAP_BITS // 64))]
 
@@ -251,6 +261,13 @@ def lib() -> C.CDLL:
         "aqe_grouped_pair_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), P(i32), P(u32), vp, vp]),
         "aqe_grouped_pair_finish": (C.c_int, [vp, P(Query), P(i32), P(u32), vp, vp, P(GroupResult), u32, P(u32)]),
         "aqe_grouped_pair_spread_finish": (C.c_int, [vp, P(Query), C.c_int, P(i32), P(u32), vp, vp, P(SpreadGroupResult), u32, P(u32)]),
+        "aqe_plan_group_error_round": (C.c_int, [u64, u64, u64, dbl, u64, u64, u32, P(Family), u32, P(u32), P(u32), P(u64)]),
+        "aqe_reduce_grouped_error": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), dbl, dbl, P(GroupResult), u32, P(u32), P(GroupErrorInfo)]),
+        "aqe_grouped_error_begin": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), P(i32), P(u32), dbl, dbl, vp, P(u32)]),
+        "aqe_grouped_error_enqueue_round": (C.c_int, [vp, u32, vp, vp]),
+        "aqe_grouped_error_enqueue_judge": (C.c_int, [vp, u32, vp, vp]),
+        "aqe_grouped_error_stopped": (C.c_int, [vp, vp, P(C.c_int)]),
+        "aqe_grouped_error_finish": (C.c_int, [vp, vp, P(GroupResult), u32, P(u32), P(GroupErrorInfo)]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),
@@ -340,6 +357,17 @@ def plan_families(q: Query, n_global: int, lo: int = 0, hi: int | None = None, r
     fams = (Family * max(n.value, 1))()
     check(L.aqe_plan_families(C.byref(q), n_global, lo, hi, round, fams, n.value, C.byref(n), C.byref(rounds), C.byref(samples)))
     return list(fams[: n.value]), rounds.value, samples.value
+
+
+def plan_group_error_round(n_rows: int, block_size: int, start_percent: float, round: int, lo: int = 0, hi: int | None = None, row_base: int = 0):
+    """Host-side plan (no GPU) of round `round` of a GROUP BY to an error threshold over n_rows rows from row_base on, clipped
+    to the shard [lo, hi): (families, levels, P_0)."""
+    L = lib()
+    hi = row_base + n_rows if hi is None else hi
+    n, levels, p0 = C.c_uint32(), C.c_uint32(), C.c_uint64()
+    fams = (Family * 4)()
+    check(L.aqe_plan_group_error_round(n_rows, row_base, block_size, start_percent, lo, hi, round, fams, 4, C.byref(n), C.byref(levels), C.byref(p0)))
+    return list(fams[: n.value]), levels.value, p0.value
 
 
 def plan_adaptive_families(q: Query, n_global: int, zone_var):

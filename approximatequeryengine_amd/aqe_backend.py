@@ -637,18 +637,31 @@ class CustomBPlusDB:
                 raise RuntimeError("No samples collected")
         return out
 
-    def approx_group_by(self, agg: str, group_by: str = "region", sample_percent: float = 10.0, method: str = "rowid",
+    def approx_group_by(self, agg: str, group_by: str = "region", sample_percent: Optional[float] = None, method: Optional[str] = None,
                         where: Optional[Tuple[float, float]] = None, block_size: int = 1000,
-                        key_where: Optional[dict] = None) -> "dict[str, GroupEstimate]":
+                        key_where: Optional[dict] = None, error_percent: Optional[float] = None,
+                        max_percent: float = 100.0) -> "dict[str, GroupEstimate]":
         """APPROX <agg>(amount) ... GROUP BY region | product_id with a 95 % interval per group: the reference's
         execute_query_groupby_with_ci (executor.cpp:202-321; GroupResultWithCI = map<string, {value, ci_lower,
         ci_upper}>) in one sweep.  method "rowid" is that function's own sample (rowid % (100 / sample_percent) == 0);
         "stride", "block", "page" and "exact" group the CustomBPlusDB samplers the same way.
         SUM is sum * 100/pct (the reference reports mean * 100/pct under that name; GroupEstimate.mean has the mean).
         ``group_by`` may name both columns ("region, product_id", or a 2-tuple / list): one group per pair that occurs in the
-        sample, keyed "a,b" in the order the columns were named (the power-sum sweep with both keys, aqe_reduce_grouped_pair)."""
+        sample, keyed "a,b" in the order the columns were named (the power-sum sweep with both keys, aqe_reduce_grouped_pair).
+        sample_percent defaults to 10, method to "rowid".
+
+        ``error_percent``: the error-threshold form (aqe_reduce_grouped_error) — SUM / AVG only: nested block levels are sampled,
+        from ``sample_percent`` (here the START percentage, default 1) on, each level doubling the sample, until every group has
+        n >= 30 and a half-width within error_percent % of its value, or the level of ``max_percent`` (default 100: the exact
+        scan) is reached.  ``method`` must be left out or be "block".  Same mapping; where the query stopped — level, levels,
+        sample_percent reached, visited rows, converged, unsettled groups, the widest group's key ("a,b" for a pair) and ratio —
+        is kept as the dictionary ``last_group_error_info``."""
         cols = group_columns(group_by)
         col = cols[0]
+        if error_percent is not None:
+            return self._group_by_error(agg, cols, sample_percent, method, where, block_size, key_where, error_percent, max_percent)
+        sample_percent = 10.0 if sample_percent is None else sample_percent
+        method = "rowid" if method is None else method
         m = {"rowid": nat.M_ROWID_MOD, "stride": nat.M_MEMORY_STRIDE, "block": nat.M_BLOCK, "page": nat.M_PAGE, "exact": nat.M_EXACT}[method]
         if self._n == 0:
             return {}
@@ -661,6 +674,41 @@ class CustomBPlusDB:
             f = _key_filter_for(key_where, method)
             return {str(r.key): GroupEstimate(r) for r in _quantile_call(lambda: self._grouped_filtered(f, q, col))}
         return {str(r.key): GroupEstimate(r) for r in self._eng().reduce_grouped(q, col)}
+
+    last_group_error_info: Optional[dict] = None  # of the most recent approx_group_by(error_percent=...)
+
+    def _group_by_error(self, agg, cols, sample_percent, method, where, block_size, key_where, error_percent, max_percent):
+        """approx_group_by(error_percent=...): the argument checks (before any table is needed), the call, the info."""
+        a = agg.upper()
+        if a == "COUNT":
+            raise ValueError("GROUP BY with error_percent takes SUM or AVG: a grouped COUNT has no interval to judge")
+        if a not in ("SUM", "AVG"):
+            raise ValueError(f"GROUP BY with error_percent takes SUM or AVG, not {agg!r}")
+        if method not in (None, "block"):
+            raise ValueError(f"method={method!r} has no error-threshold form: GROUP BY with error_percent samples nested blocks "
+                             "(leave method out, or give 'block')")
+        e, mp = float(error_percent), float(max_percent)
+        if not (e > 0.0 and e != float("inf")):
+            raise ValueError(f"error_percent must be a positive number, got {error_percent!r}")
+        if not mp > 0.0:
+            raise ValueError(f"max_percent must be positive, got {max_percent!r}")
+        start = 1.0 if sample_percent is None else float(sample_percent)
+        f = None if key_where is None else _key_filter_for(key_where, "block")
+        self.last_group_error_info = None
+        if self._n == 0:
+            return {}
+        q = make_query(nat.M_BLOCK, start, agg=_AGG[a], where=where, block_size=int(block_size))
+        groups, info = _quantile_call(lambda: self._grouped_error(f, q, cols, e, mp))
+        pair = len(cols) == 2
+        d = info.as_dict()
+        d["worst_key"] = "%d,%d" % nat.group_key_unpack(info.worst_key) if pair else str(info.worst_key)
+        d["converged"] = bool(info.converged)
+        d["error_percent"], d["max_percent"] = e, mp
+        self.last_group_error_info = d
+        return _pair_groups(groups, GroupEstimate) if pair else {str(r.key): GroupEstimate(r) for r in groups}
+
+    def _grouped_error(self, f, q, cols, error_percent, max_percent):
+        return self._eng().reduce_grouped_error(q, cols, error_percent, max_percent, f)
 
     def _reduce_filtered(self, f, q):
         return self._eng().reduce_filtered(f, q)

@@ -135,6 +135,16 @@ def group_by_of(query: str) -> Optional[Tuple[str, ...]]:
     return tuple(names)
 
 
+def group_error_form(clean: str, args) -> bool:
+    """SUM / AVG / COUNT ... GROUP BY ... --e E without --s (--s wins, as in determine_query_type) and outside an APPROX(...)
+    wrapper: the query the error-threshold form of GROUP BY answers."""
+    if args.e is None or args.s is not None or parse_embedded_approx(args.query)[1]:
+        return False
+    if quantile_of(clean) is not None or spread_of(clean) is not None:
+        return False
+    return bool(group_by_of(clean))
+
+
 def determine_query_type(query: str, args) -> str:
     """enhanced_aqe_cli.py:97-114 with the attribute names fixed."""
     if parse_embedded_approx(query)[1]:
@@ -222,6 +232,10 @@ def run(args, out=sys.stdout) -> int:
         if quant is not None:
             print(f"error: MEDIAN / PERCENTILE under the key predicate 'WHERE {clause}' are not supported yet", file=out)
             return 2
+    if group_error_form(clean, args) and aggregate_of(clean) == "COUNT":
+        print("error: COUNT ... GROUP BY has no error-threshold (--e) form (a grouped COUNT has no interval to judge): "
+              "give a sample percentage (--s) or none (exact)", file=out)
+        return 2
     if not os.path.exists(args.db):
         print(f"error: database file '{args.db}' not found", file=out)
         return 1
@@ -277,6 +291,21 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     if spread is not None:
         return _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0, kw)
     gb = group_by_of(clean)
+    if gb and group_error_form(clean, args):
+        # --e with GROUP BY: nested block levels until every group's interval is within the threshold (aqe_reduce_grouped_error)
+        groups = db.approx_group_by(agg, group_by=", ".join(gb), where=aqe_backend.parse_where(clean), error_percent=float(args.e), **kw)
+        ms = (time.perf_counter() - t0) * 1e3
+        info = db.last_group_error_info or {}
+        print(f"\nGROUP BY {', '.join(gb).lower()} (every group within ±{args.e:g}%, nested block sample):", file=out)
+        for key, g in groups.items():
+            print(f"   {key:>6}: {g.value:,.4f}   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})   n={g.n:,}", file=out)
+        if info:
+            how = "yes" if info["converged"] else f"no ({info['unsettled']} groups unsettled)"
+            print(f"   stopped at level {info['level']} of {info['levels'] - 1} ({info['sample_percent']:g}% of rows), converged: {how}, "
+                  f"widest: key {info['worst_key']} ±{info['worst_rel'] * 100.0:.4g}%", file=out)
+        print(f"   execution time: {ms:.2f} ms", file=out)
+        db.close_database()
+        return 0
     if gb:  # one sweep, one bin per key (or per pair of keys), an interval per group (executor.cpp:202-321 semantics)
         pct = args.s if args.s is not None else (100.0 if qtype == QUERY_EXACT else 10.0)
         groups = db.approx_group_by(agg, group_by=", ".join(gb), sample_percent=pct, method="exact" if pct >= 100.0 else "rowid",

@@ -102,6 +102,23 @@ int aqe_plan_families(const aqe_query* q, uint64_t n_global, uint64_t shard_lo, 
     return AQE_OK;
 }
 
+int aqe_plan_group_error_round(uint64_t n_rows, uint64_t row_base, uint64_t block_size, double start_percent, uint64_t shard_lo, uint64_t shard_hi,
+                               uint32_t round, aqe_family* fams, uint32_t cap, uint32_t* n_out, uint32_t* levels_out, uint64_t* period0_out) {
+    ErrorLevels L;
+    if (!error_levels(n_rows, row_base, block_size, start_percent, L)) return fail(nullptr, AQE_ERR_INVALID, "block_size and start_percent must be positive");
+    if (levels_out) *levels_out = L.R + 1;
+    if (period0_out) *period0_out = L.P0;
+    if (round > L.R) return fail(nullptr, AQE_ERR_INVALID, "round beyond the last level");
+    std::vector<aqe_family> out;
+    error_round_families(L, round, ClipWindow{shard_lo, shard_hi}, out);
+    if (n_out) *n_out = static_cast<uint32_t>(out.size());
+    if (fams) {
+        if (cap < out.size()) return fail(nullptr, AQE_ERR_CAPACITY, "family buffer too small");
+        std::copy(out.begin(), out.end(), fams);
+    }
+    return AQE_OK;
+}
+
 int aqe_union_cover(const uint64_t* run_lo, const uint64_t* run_len, const uint32_t* run_target, uint32_t n_runs, uint32_t n_targets,
                     uint64_t* piece_lo, uint64_t* piece_hi, uint32_t cap_pieces, uint32_t* n_pieces,
                     uint32_t* target_begin, uint32_t* target_piece, uint32_t cap_incidences, uint32_t* n_incidences,

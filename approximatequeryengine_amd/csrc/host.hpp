@@ -291,6 +291,9 @@ void moments_release(aqe_ctx* c);
 // plans.hip
 void destroy_plan(aqe_plan* p, bool device_idle = false);  // device_idle: the caller has just synchronised the device
 void drop_cache(aqe_ctx* c);
+// One more family of a sweep launch that is not a plan's (moments.hip, the rounds of aqe_reduce_grouped_error): the tile
+// decomposition every planned family gets, appended to `out`, its tiles and samples counted into L.
+void add_sweep_family(std::vector<DevFamily>& out, LaunchDesc& L, const aqe_family& f, bool dense16);
 SweepCommon sweep_common(const aqe_plan* p, const DevFamily* fams, uint32_t nfam, bool topup = false);
 FoldParams fold_params(const aqe_plan* p, bool topup);
 FinalizeParams finalize_params(const aqe_plan* p);

@@ -28,6 +28,11 @@
 // GROUP BY both key columns (kPair): the same kernel with NK = 2 — key 0 is column A, key 1 column B of the ordered pair —
 // and the bin (a - minA) * spanB + (b - minB), spanA * spanB <= kMaxGroupBins; a term may sit on either column.  Partials,
 // k_bins_sum and the finishes' arithmetic are the single-column ones; the pair finishes only decode the bin into (a, b).
+//
+// GROUP BY to an error threshold (aqe_reduce_grouped_error): the grouped sweep run level by level over nested block samples
+// (planner.cpp, error_round_families) — k_level_init sets up cumulative bins, tickets and state per call, each round's sweep
+// (kStop) leaves at once when the query has stopped, and k_level_judge adds the round's partials onto the cumulative bins in
+// a fixed order and has the last workgroup to arrive judge every group with group_result; DESIGN 10f.
 #include <cstddef>
 
 #include "device_common.hpp"
@@ -235,14 +240,21 @@ struct MomentGroupLaunch {
     uint32_t span_b;
     double* partial;         // [gridDim.x][nbins][kSpBin]: n, P1, P2, P3, P4, visited
     DevFilter flt;           // kFiltered: t[0] judges the group column (pass-all when it has no term), t[1] the other
+    const unsigned* stop;    // kStop: the stop word of a query swept level by level (LevelState::stop); null in every other launch
 };
 static_assert(sizeof(MomentGroupLaunch) <= 4096, "kernel arguments are limited to 4 KB");
 
 // kFiltered = false is the unfiltered grouped spread (NK = 1): no map is staged and no term is tested.
 // kPair bins on both keys (NK = 2); kFiltered then tests t[0] on column A and t[1] on column B (pass-all without a term).
-template <bool kPrivate, bool kNT, int NK, bool kFiltered, bool kPair = false>
+// kStop: a round of a query swept level by level (aqe_reduce_grouped_error) — the workgroup reads the query's stop word
+// once, one uniform load, and when it is set returns without touching a row or its partial (k_level_judge and
+// k_level_bins test the same word and read no partial of such a launch).  kStop = false compiles to what it was.
+template <bool kPrivate, bool kNT, int NK, bool kFiltered, bool kPair = false, bool kStop = false>
 __global__ __launch_bounds__(kBlockThreads) void k_moments_grouped(MomentGroupLaunch a) {
     static_assert(kPair ? NK == 2 : (NK == 1 || (NK == 2 && kFiltered)), "the group column, and the other one only under a term on it or as column B");
+    if constexpr (kStop) {
+        if (__builtin_amdgcn_readfirstlane(static_cast<int>(__hip_atomic_load(a.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))) return;
+    }
     extern __shared__ double lds[];
     __shared__ DevFamily lds_fams[kMaxLdsFams];
     __shared__ u64 s_map[2][kMapWords];
@@ -399,6 +411,173 @@ __global__ __launch_bounds__(64) void k_groups_finish_pair(const double* __restr
     out[b] = group_result(bins + static_cast<size_t>(b) * kSpBin, pair_key(g, b), c, pct, agg);
 }
 
+// ---- GROUP BY to an error threshold (aqe_reduce_grouped_error): the kernels of a level ----------------------------------------
+// What the device knows of a query swept level by level: written by k_level_init and by the judging workgroup of
+// k_level_judge, in device memory (the sweeps' stop word) and in its pinned mirror (what the host reads).
+struct LevelState {
+    unsigned stop;       // 1: the query has stopped at `level`; every later launch of the query returns at once
+    unsigned level;      // the level judged last
+    unsigned unsettled;  // groups not settled at that level
+    unsigned worst_bin;  // the bin with the largest half-width / |value| there (lowest bin among equals) ...
+    unsigned converged;  // with stop: every group settled (or level R)
+    unsigned judged;     // levels judged so far
+    unsigned groups;     // bins with a sampled row
+    unsigned pad;
+    double worst_rel;    // ... and that ratio
+    double visited;      // rows read so far, all bins
+};
+static_assert(sizeof(LevelState) == 48, "state block");
+
+// Per call: zero cumulative bins, zero tickets, a fresh state — nothing an earlier launch left is relied on.
+__global__ __launch_bounds__(kBlockThreads) void k_level_init(double* __restrict__ cum, unsigned nwords, unsigned* __restrict__ ticket,
+                                                             LevelState* state, LevelState* h_state) {
+    for (unsigned i = threadIdx.x; i < nwords; i += kBlockThreads) cum[i] = 0.0;
+    for (unsigned i = threadIdx.x; i < static_cast<unsigned>(kCounterWords); i += kBlockThreads) ticket[i] = 0u;
+    if (threadIdx.x == 0) {
+        const LevelState z{};
+        *state = z;
+        *h_state = z;
+    }
+}
+
+// The multi-GPU form's k_bins_sum: this shard's bins of a round, zeros once the query has stopped (the sweep then wrote no
+// partial).
+__global__ __launch_bounds__(64) void k_level_bins(const double* __restrict__ partial, unsigned nblocks, unsigned nwords, const unsigned* stop,
+                                                   double* __restrict__ bins) {
+    const unsigned i = blockIdx.x, lane = threadIdx.x;
+    const bool stopped = __builtin_amdgcn_readfirstlane(static_cast<int>(__hip_atomic_load(stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) != 0;
+    double t = 0.0;
+    if (!stopped)
+        for (unsigned w = lane; w < nblocks; w += 64) t += partial[static_cast<size_t>(w) * nwords + i];
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+    if (lane == 0) bins[i] = t;
+}
+
+constexpr unsigned kJudgeGrid = 128;  // workgroups of k_level_judge at most: 1024 bins are 12 words per wave
+
+struct LevelJudge {
+    const double* src;    // [nblocks][nbins][kSpBin]: the round's workgroup partials (one GPU), or its all-reduced bins (nblocks = 1)
+    unsigned nblocks, nbins;
+    double* cum;          // [nbins][kSpBin], cumulative over the rounds
+    unsigned* ticket;     // kCounterWords
+    LevelState* state;    // device
+    LevelState* h_state;  // its pinned mirror
+    aqe_group_result* groups;  // pinned [nbins]: written at the stop
+    PairRange g;          // key ranges (one column: span_b = 1)
+    int32_t pair, agg;
+    double c, err;        // the shift; error_percent / 100
+    unsigned level, period, final_level, cap_level;  // this level r, P_r, R, the last level max_percent allows
+};
+
+// Accumulate and judge.  At most kJudgeGrid workgroups (one fence and one ticket each); a wave owns the words (bin,
+// component) w, w + waves of the grid, ...: lane l adds the workgroups l, l + 64, ... of the round's
+// partials in order, a fixed butterfly adds the lanes (k_bins_sum), and the sum goes onto the cumulative word — no
+// floating-point atomics: given the same round partials every rank holds the same cumulative bins, bit for bit.  Workgroups
+// draw sharded arrival tickets (k_moments); the last to arrive judges: thread t finishes the bins t, t + 256, ... with
+// group_result at scale P_r, the lanes' counts and maxima meet by cross-lane moves, the four waves through LDS, and thread 0
+// writes the state.  At the stop every thread writes its bins' groups to pinned memory.
+__global__ __launch_bounds__(kBlockThreads) void k_level_judge(LevelJudge a) {
+    __shared__ int s_last, s_stop;
+    __shared__ double s_rel[kWavesPerBlock], s_vis[kWavesPerBlock];
+    __shared__ unsigned s_bin[kWavesPerBlock], s_uns[kWavesPerBlock], s_grp[kWavesPerBlock];
+    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (__builtin_amdgcn_readfirstlane(static_cast<int>(__hip_atomic_load(&a.state->stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))) return;
+    const unsigned nwords = a.nbins * static_cast<unsigned>(kSpBin);
+    for (unsigned i = blockIdx.x * kWavesPerBlock + wave; i < nwords; i += gridDim.x * kWavesPerBlock) {  // (a word has one owner)
+        double t = 0.0;
+        for (unsigned w = lane; w < a.nblocks; w += 64) t += a.src[static_cast<size_t>(w) * nwords + i];
+        for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+        if (lane == 0) a.cum[i] += t;
+    }
+    __threadfence();  // the cumulative word is out before the ticket is drawn
+    __syncthreads();
+    if (tid == 0) {  // sharded arrival tickets, as k_moments
+        const unsigned G = gridDim.x, shards = G < static_cast<unsigned>(kShards) ? G : static_cast<unsigned>(kShards);
+        unsigned* const ct = a.ticket + static_cast<size_t>(kShards) * kShardStride;
+        int last = 0;
+        if (G <= static_cast<unsigned>(kShards)) {
+            if (__hip_atomic_fetch_add(ct, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1u) { __hip_atomic_store(ct, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); last = 1; }
+        } else {
+            const unsigned sh = blockIdx.x % shards, members = (G - sh + shards - 1u) / shards;
+            unsigned* const cs = a.ticket + static_cast<size_t>(sh) * kShardStride;
+            if (__hip_atomic_fetch_add(cs, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == members - 1u) {
+                __hip_atomic_store(cs, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (__hip_atomic_fetch_add(ct, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == shards - 1u) { __hip_atomic_store(ct, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); last = 1; }
+            }
+        }
+        s_last = last;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();
+    const double pct = 100.0 / static_cast<double>(a.period);
+    const bool final_level = a.level == a.final_level;
+    auto finish = [&](unsigned b, bool* sampled) {
+        double v[kSpBin];
+#pragma unroll
+        for (int k = 0; k < kSpBin; ++k) v[k] = __hip_atomic_load(a.cum + static_cast<size_t>(b) * kSpBin + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *sampled = v[5] > 0.0;
+        const int64_t key = a.pair ? pair_key(a.g, b) : static_cast<int64_t>(a.g.kmin_a) + b;
+        return group_result(v, key, a.c, pct, a.agg);
+    };
+    unsigned uns = 0, grp = 0, wbin = 0xffffffffu;
+    double wrel = -1.0, vis = 0.0;
+    for (unsigned b = tid; b < a.nbins; b += kBlockThreads) {
+        bool sampled;
+        const aqe_group_result r = finish(b, &sampled);
+        if (!sampled) continue;  // a bin nobody sampled is not a group
+        const double half = (r.ci_upper - r.ci_lower) / 2.0, av = fabs(r.value);
+        const bool settled = final_level || (r.n >= 30u && half <= a.err * av);
+        const double rel = av > 0.0 ? half / av : (half > 0.0 ? __builtin_inf() : 0.0);
+        ++grp;
+        uns += settled ? 0u : 1u;
+        vis += static_cast<double>(r.visited);
+        if (rel > wrel) { wrel = rel; wbin = b; }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double orel = __shfl_xor(wrel, off, 64);
+        const unsigned obin = __shfl_xor(wbin, off, 64);
+        if (orel > wrel || (orel == wrel && obin < wbin)) { wrel = orel; wbin = obin; }
+        uns += __shfl_xor(uns, off, 64);
+        grp += __shfl_xor(grp, off, 64);
+        vis += __shfl_xor(vis, off, 64);  // (row counts: whole numbers below 2^53, their sum is exact in any order)
+    }
+    if (lane == 0) { s_rel[wave] = wrel; s_bin[wave] = wbin; s_uns[wave] = uns; s_grp[wave] = grp; s_vis[wave] = vis; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < kWavesPerBlock; ++w) {
+            if (s_rel[w] > wrel || (s_rel[w] == wrel && s_bin[w] < wbin)) { wrel = s_rel[w]; wbin = s_bin[w]; }
+            uns += s_uns[w]; grp += s_grp[w]; vis += s_vis[w];
+        }
+        s_stop = (uns == 0u || a.level >= a.cap_level || final_level) ? 1 : 0;
+    }
+    __syncthreads();
+    const bool stop = s_stop != 0;
+    if (stop) {
+        for (unsigned b = tid; b < a.nbins; b += kBlockThreads) {
+            bool sampled;
+            a.groups[b] = finish(b, &sampled);
+        }
+        __threadfence_system();  // the groups are in host memory before the state says so
+        __syncthreads();
+    }
+    if (tid == 0) {
+        LevelState st{};
+        st.stop = stop ? 1u : 0u;
+        st.level = a.level;
+        st.unsettled = uns;
+        st.worst_bin = wbin == 0xffffffffu ? 0u : wbin;
+        st.converged = uns == 0u ? 1u : 0u;
+        st.judged = a.level + 1u;
+        st.groups = grp;
+        st.worst_rel = wrel < 0.0 ? 0.0 : wrel;
+        st.visited = vis;
+        *a.h_state = st;
+        __threadfence_system();
+        *a.state = st;
+    }
+}
+
 // One thread per bin: VARIANCE / STDDEV of the group and its interval from the (all-reduced) sums.
 __device__ __forceinline__ aqe_spread_group_result spread_group_result(const double* v, int64_t key, double c, const SpreadFin& fin) {
     const SpreadCore k = spread_core(v[0], v[1], v[2], v[3], v[4], c, fin);
@@ -431,6 +610,26 @@ inline unsigned grid_for(uint64_t work, uint64_t per_block) {
 }
 
 }  // namespace
+
+// What the host keeps of the level-by-level query in progress on a context (one at a time).
+constexpr unsigned kLevelFams = 3 * kMaxErrorLevels;  // a round's family clipped to a shard is one family
+struct LevelRun {
+    bool active = false;
+    aqe_query q{};
+    aqe_key_filter filter{};
+    bool has_filter = false;
+    int col[2] = {0, 0};
+    int32_t kmin[2] = {0, 0};
+    uint32_t span[2] = {0, 1};
+    ErrorLevels levels;
+    double err = 0.0;
+    uint32_t cap_level = 0;
+    uint32_t next_round = 0, next_judge = 0;
+    uint32_t launches = 0;
+    unsigned last_grid = 0;  // workgroups of the sweep of the round enqueued last (0: it had no tile here)
+    std::vector<LaunchDesc> rounds;
+};
+
 }  // namespace aqe
 
 // What the spread and the filtered entries keep with the context: partials and tickets of the ungrouped sweep, the pinned
@@ -451,6 +650,16 @@ struct aqe_moment_scratch {
     aqe_group_result* d_groups = nullptr;
     aqe_spread_group_result* h_sgroups = nullptr;
     aqe_spread_group_result* d_sgroups = nullptr;
+    // GROUP BY to an error threshold (made on first use): cumulative bins, the judge's tickets, the state and its pinned
+    // mirror, the rounds' family tables (pinned staging + device), and the query in progress
+    double* d_cum = nullptr;          // [kMaxGroupBins][kSpBin]
+    unsigned* d_lticket = nullptr;    // kCounterWords
+    aqe::LevelState* d_lstate = nullptr;
+    aqe::LevelState* h_lstate = nullptr;   // pinned, mapped
+    aqe::LevelState* hd_lstate = nullptr;  // the device's address of h_lstate
+    aqe::DevFamily* d_lfams = nullptr;     // [kLevelFams]
+    aqe::DevFamily* h_lfams = nullptr;     // pinned
+    aqe::LevelRun* run = nullptr;
 };
 
 namespace aqe {
@@ -689,31 +898,54 @@ struct GroupCols {
 };
 inline GroupCols one_column(int column, int32_t key_min, uint32_t nbins) { return GroupCols{{column, 0}, {key_min, 0}, {nbins, 1u}}; }
 
-// This shard's bins [nbins][kSpBin] into dev_bins (zeros when nothing of the sample lies in this shard), under the filter
-// `f` (null: none; the caller has checked it).
-int enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const GroupCols& g, double* dev_bins, hipStream_t s) {
-    const uint32_t nbins = g.nbins();
-    aqe_plan* p = nullptr;
-    int rc = moment_plan(c, q, true, words_for(f), &p);
-    if (rc != AQE_OK) return rc;
-    rc = ensure_scratch(c);
-    if (rc != AQE_OK) return rc;
-    const size_t bins_bytes = static_cast<size_t>(nbins) * kSpBin * sizeof(double);
-    if (p->rounds.empty() || c->n_local == 0 || p->rounds[0].ntiles == 0 || p->rounds[0].nfam == 0) {
-        HIPCHK(c, hipMemsetAsync(dev_bins, 0, bins_bytes, s));
-        return AQE_OK;
+// The grouped sweep's partial buffer, grown on demand.
+int ensure_gpartial(aqe_ctx* c, size_t need) {
+    aqe_moment_scratch* sc = c->moments;
+    if (sc->gpartial_bytes >= need) return AQE_OK;
+    if (sc->d_gpartial) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier sweep may still be reading the buffer
+        (void)hipFree(sc->d_gpartial);
     }
-    const LaunchDesc& L = p->rounds[0];
+    sc->d_gpartial = nullptr;
+    sc->gpartial_bytes = 0;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_gpartial), need));
+    sc->gpartial_bytes = need;
+    return AQE_OK;
+}
+
+template <bool PRIV, bool NT, bool STOP>
+void launch_grouped_as(bool pair, bool filtered, int nk, dim3 gd, dim3 bd, size_t lds_bytes, hipStream_t s, const MomentGroupLaunch& a) {
+    if (pair && !filtered) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 2, false, true, STOP>), gd, bd, lds_bytes, s, a);
+    else if (pair) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 2, true, true, STOP>), gd, bd, lds_bytes, s, a);
+    else if (!filtered) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 1, false, false, STOP>), gd, bd, lds_bytes, s, a);
+    else if (nk == 1) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 1, true, false, STOP>), gd, bd, lds_bytes, s, a);
+    else hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 2, true, false, STOP>), gd, bd, lds_bytes, s, a);
+}
+
+// The grouped sweep of the `ntiles` tiles of sw's families into the scratch's partials [*grid_out][nbins][kSpBin], under the
+// filter `f` (null: none; the caller has checked it).  view_plan: the plan whose families the tiles are (its rows may index a
+// stride-major view); null: rows of the column itself.  stop: the stop word of a query swept level by level, or null.
+int launch_grouped(aqe_ctx* c, const aqe_key_filter* f, const GroupCols& g, const SweepCommon& sw, uint64_t ntiles, aqe_plan* view_plan,
+                   const unsigned* stop, unsigned* grid_out, hipStream_t s) {
+    const uint32_t nbins = g.nbins();
+    auto key_of = [&](int col, const int32_t** out) {
+        if (view_plan) return key_pointer(c, view_plan, col, out);
+        const int rc = ensure_keys(c, col);
+        if (rc == AQE_OK) *out = c->keycol[col - 1];
+        return rc;
+    };
     MomentGroupLaunch a{};
-    a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
-    a.ntiles = L.ntiles;
+    a.sw = sw;
+    a.ntiles = ntiles;
     a.key_min = g.kmin[0];
     a.nbins = nbins;
     a.key_min_b = g.kmin[1];
     a.span_b = g.span[1];
+    a.stop = stop;
     const bool pair = g.pair();
+    int rc = AQE_OK;
     for (int i = 0; i < (pair ? 2 : 1); ++i) {
-        rc = key_pointer(c, p, g.col[i], &a.keys[i]);
+        rc = key_of(g.col[i], &a.keys[i]);
         if (rc != AQE_OK) return rc;
         const int k = g.col[i] - 1;
         if (c->key_min[k] < g.kmin[i] || static_cast<int64_t>(c->key_max[k]) - g.kmin[i] >= static_cast<int64_t>(g.span[i]))
@@ -729,37 +961,25 @@ int enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const 
             compile_term(f->term[other - 1], &a.flt.t[1], a.flt.map[1]);
         } else if (f->term[other - 1].form != AQE_KEYTERM_NONE) {
             compile_term(f->term[other - 1], &a.flt.t[1], a.flt.map[1]);
-            rc = key_pointer(c, p, other, &a.keys[1]);
+            rc = key_of(other, &a.keys[1]);
             if (rc != AQE_OK) return rc;
             nk = 2;
         }
     }
-    const unsigned grid = grouped_grid(L.ntiles);
-    aqe_moment_scratch* sc = c->moments;
-    const size_t need = static_cast<size_t>(grid) * bins_bytes;
-    if (sc->gpartial_bytes < need) {
-        if (sc->d_gpartial) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier sweep may still be reading the buffer
-            (void)hipFree(sc->d_gpartial);
-        }
-        sc->d_gpartial = nullptr;
-        sc->gpartial_bytes = 0;
-        HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_gpartial), need));
-        sc->gpartial_bytes = need;
-    }
-    a.partial = sc->d_gpartial;
+    const unsigned grid = grouped_grid(ntiles);
+    const size_t bins_bytes = static_cast<size_t>(nbins) * kSpBin * sizeof(double);
+    rc = ensure_gpartial(c, static_cast<size_t>(grid) * bins_bytes);
+    if (rc != AQE_OK) return rc;
+    a.partial = c->moments->d_gpartial;
     const bool priv = nbins <= kPrivBins;
     const size_t lds_bytes = priv ? static_cast<size_t>(nbins) * kBlockThreads * 5 * sizeof(double)
                                   : static_cast<size_t>(replicas_for(nbins)) * replica_stride(nbins) * kSpBin * sizeof(double);
     const bool nt = a.sw.nt != 0;
     const dim3 gd(grid), bd(kBlockThreads);
-#define AQE_MG_LAUNCH(PRIV, NT)                                                                               \
-    do {                                                                                                             \
-        if (pair && !f) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 2, false, true>), gd, bd, lds_bytes, s, a);  \
-        else if (pair) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 2, true, true>), gd, bd, lds_bytes, s, a);    \
-        else if (!f) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 1, false>), gd, bd, lds_bytes, s, a);           \
-        else if (nk == 1) hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 1, true>), gd, bd, lds_bytes, s, a);       \
-        else hipLaunchKernelGGL((k_moments_grouped<PRIV, NT, 2, true>), gd, bd, lds_bytes, s, a);                    \
+#define AQE_MG_LAUNCH(PRIV, NT)                                                                        \
+    do {                                                                                               \
+        if (stop) launch_grouped_as<PRIV, NT, true>(pair, f != nullptr, nk, gd, bd, lds_bytes, s, a);  \
+        else launch_grouped_as<PRIV, NT, false>(pair, f != nullptr, nk, gd, bd, lds_bytes, s, a);      \
     } while (0)
     if (priv) {
         if (nt) AQE_MG_LAUNCH(true, true);
@@ -770,7 +990,28 @@ int enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const 
     }
 #undef AQE_MG_LAUNCH
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(k_bins_sum, dim3(nbins * kSpBin), dim3(64), 0, s, sc->d_gpartial, grid, nbins * static_cast<unsigned>(kSpBin), dev_bins);
+    *grid_out = grid;
+    return AQE_OK;
+}
+
+// This shard's bins [nbins][kSpBin] into dev_bins (zeros when nothing of the sample lies in this shard), under the filter
+// `f` (null: none; the caller has checked it).
+int enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const GroupCols& g, double* dev_bins, hipStream_t s) {
+    const uint32_t nbins = g.nbins();
+    aqe_plan* p = nullptr;
+    int rc = moment_plan(c, q, true, words_for(f), &p);
+    if (rc != AQE_OK) return rc;
+    rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    if (p->rounds.empty() || c->n_local == 0 || p->rounds[0].ntiles == 0 || p->rounds[0].nfam == 0) {
+        HIPCHK(c, hipMemsetAsync(dev_bins, 0, static_cast<size_t>(nbins) * kSpBin * sizeof(double), s));
+        return AQE_OK;
+    }
+    const LaunchDesc& L = p->rounds[0];
+    unsigned grid = 0;
+    rc = launch_grouped(c, f, g, sweep_common(p, p->d_fams + L.fam_offset, L.nfam), L.ntiles, p, nullptr, &grid, s);
+    if (rc != AQE_OK) return rc;
+    hipLaunchKernelGGL(k_bins_sum, dim3(nbins * kSpBin), dim3(64), 0, s, c->moments->d_gpartial, grid, nbins * static_cast<unsigned>(kSpBin), dev_bins);
     HIPCHK(c, hipGetLastError());
     return AQE_OK;
 }
@@ -814,9 +1055,9 @@ int finish_spread_groups(aqe_ctx* c, const aqe_query* q, int kind, const GroupCo
 
 const char* column_name(int column) { return column == AQE_GROUP_REGION ? "region" : "product_id"; }
 
-// The key range of the group column(s) — cols[1] == 0: one column — and the sweep into the context's own bins (the
-// single-GPU grouped entries).  out->span[0] stays 0 for an empty table: no groups.
-int grouped_prologue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int cols[2], uint32_t* n_groups, GroupCols* out) {
+// The key range of the group column(s) — cols[1] == 0: one column — of the single-GPU grouped entries, with their refusals.
+// out->span[0] stays 0 for an empty table: no groups.
+int grouped_ranges(aqe_ctx* c, const int cols[2], uint32_t* n_groups, GroupCols* out) {
     *n_groups = 0;
     GroupCols g{{cols[0], cols[1]}, {0, 0}, {0u, 1u}};
     *out = g;
@@ -836,12 +1077,24 @@ int grouped_prologue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, co
     g.span[0] = static_cast<uint32_t>(span[0]);
     g.span[1] = static_cast<uint32_t>(span[1]);
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensure_scratch(c);
-    if (rc != AQE_OK) return rc;
-    rc = enqueue_bins(c, f, q, g, c->moments->d_bins, c->stream);
+    const int rc = ensure_scratch(c);
     if (rc != AQE_OK) return rc;
     *out = g;
     return AQE_OK;
+}
+
+// ... and the sweep into the context's own bins.
+int grouped_prologue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int cols[2], uint32_t* n_groups, GroupCols* out) {
+    GroupCols g;
+    int rc = grouped_ranges(c, cols, n_groups, &g);
+    if (rc != AQE_OK || g.span[0] == 0) {
+        *out = g;
+        return rc;
+    }
+    rc = enqueue_bins(c, f, q, g, c->moments->d_bins, c->stream);
+    *out = g;
+    if (rc != AQE_OK) out->span[0] = 0;
+    return rc;
 }
 
 // The single-GPU grouped spread entries behind their argument checks.
@@ -893,6 +1146,196 @@ int bins_arguments(aqe_ctx* c, int group_column, const double* dev_bins, uint32_
     return AQE_OK;
 }
 
+// ---- GROUP BY to an error threshold: the host side ---------------------------------------------------------------------------
+
+int ensure_level_scratch(aqe_ctx* c) {
+    int rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    aqe_moment_scratch* sc = c->moments;
+    // (each buffer on its own test: a call that failed part way is taken up where it stopped, nothing is allocated twice)
+    if (!sc->d_cum) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_cum), sizeof(double) * kMaxGroupBins * kSpBin));
+    if (!sc->d_lticket) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_lticket), sizeof(unsigned) * kCounterWords));
+    if (!sc->d_lstate) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_lstate), sizeof(LevelState)));
+    if (!sc->d_lfams) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_lfams), sizeof(DevFamily) * kLevelFams));
+    if (!sc->hd_lstate) {
+        if (sc->h_lstate) (void)hipHostFree(sc->h_lstate);  // (pinned, but its device address was refused)
+        sc->h_lstate = nullptr;
+        rc = pinned(c, &sc->h_lstate, &sc->hd_lstate, 1);
+        if (rc != AQE_OK) return rc;
+    }
+    if (!sc->h_lfams) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&sc->h_lfams), sizeof(DevFamily) * kLevelFams, hipHostMallocDefault));
+    if (!sc->run) sc->run = new LevelRun;
+    return AQE_OK;
+}
+
+// What every entry of the form checks of the query before anything is launched.
+int level_query_ok(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, double error_percent, double max_percent) {
+    if (!q) return fail(c, AQE_ERR_INVALID, "null query");
+    if (q->agg == AQE_COUNT) return fail(c, AQE_ERR_UNSUPPORTED, "GROUP BY to an error threshold takes SUM or AVG: a grouped COUNT has no interval to judge");
+    if (q->agg != AQE_SUM && q->agg != AQE_AVG) return fail(c, AQE_ERR_INVALID, "agg must be AQE_SUM or AQE_AVG");
+    if (q->method != AQE_M_BLOCK) return fail(c, AQE_ERR_UNSUPPORTED, "GROUP BY to an error threshold samples nested blocks: q->method must be AQE_M_BLOCK");
+    if (!(error_percent > 0.0) || !(error_percent < std::numeric_limits<double>::infinity())) return fail(c, AQE_ERR_INVALID, "error_percent must be positive and finite");
+    if (!(max_percent > 0.0)) return fail(c, AQE_ERR_INVALID, "max_percent must be positive");
+    if (!(q->sample_percent > 0.0)) return fail(c, AQE_ERR_INVALID, "sample_percent (the start percentage) must be positive");
+    if (q->block_size == 0) return fail(c, AQE_ERR_INVALID, "block_size must be positive");
+    if (q->has_where && (q->where_min != q->where_min || q->where_max != q->where_max)) return fail(c, AQE_ERR_INVALID, "WHERE bound is NaN");
+    if (f) return check_filter(c, f);
+    return AQE_OK;
+}
+
+// Plans the levels, uploads the rounds' family tables and enqueues the init launch.
+int level_begin(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const GroupCols& g, double error_percent, double max_percent, hipStream_t s) {
+    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
+    int rc = ensure_level_scratch(c);
+    if (rc != AQE_OK) return rc;
+    aqe_moment_scratch* sc = c->moments;
+    LevelRun& run = *sc->run;
+    if (run.active) HIPCHK(c, hipStreamSynchronize(s));  // an abandoned query's launches may still read the family tables
+    run = LevelRun{};
+    uint64_t base = 0, n = c->n_global;
+    if (q->row_hi > q->row_lo) {
+        if (q->row_hi > c->n_global) return fail(c, AQE_ERR_INVALID, "row window leaves the table");
+        base = q->row_lo;
+        n = q->row_hi - q->row_lo;
+    }
+    if (!error_levels(n, base, q->block_size, q->sample_percent, run.levels)) return fail(c, AQE_ERR_INVALID, "block_size and sample_percent must be positive");
+    const ErrorLevels& L = run.levels;
+    std::vector<DevFamily> fams;
+    std::vector<aqe_family> rf;
+    uint64_t max_tiles = 0;
+    for (uint32_t r = 0; r <= L.R; ++r) {
+        rf.clear();
+        error_round_families(L, r, ClipWindow{c->shard_lo, c->shard_lo + c->n_local}, rf);
+        LaunchDesc d;
+        d.fam_offset = fams.size();
+        for (const aqe_family& fam : rf) add_sweep_family(fams, d, fam, c->dense16);
+        max_tiles = std::max(max_tiles, d.ntiles);
+        run.rounds.push_back(d);
+    }
+    if (fams.size() > kLevelFams) return fail(c, AQE_ERR_INVALID, "more families than the level tables hold");
+    run.q = *q;
+    run.has_filter = f != nullptr;
+    if (f) run.filter = *f;
+    for (int i = 0; i < 2; ++i) { run.col[i] = g.col[i]; run.kmin[i] = g.kmin[i]; run.span[i] = g.span[i]; }
+    run.err = error_percent / 100.0;
+    run.cap_level = 0;  // the last level whose fraction 100 / P_r does not exceed max_percent (level 0 when none does)
+    for (uint32_t r = 0; r <= L.R; ++r)
+        if (100.0 / static_cast<double>(L.P0 >> r) <= max_percent) run.cap_level = r;
+    const uint32_t nbins = g.nbins();
+    if (max_tiles) {
+        rc = ensure_gpartial(c, static_cast<size_t>(grouped_grid(max_tiles)) * nbins * kSpBin * sizeof(double));  // (no growth between the rounds)
+        if (rc != AQE_OK) return rc;
+    }
+    if (!fams.empty()) {
+        std::memcpy(sc->h_lfams, fams.data(), fams.size() * sizeof(DevFamily));
+        HIPCHK(c, hipMemcpyAsync(sc->d_lfams, sc->h_lfams, fams.size() * sizeof(DevFamily), hipMemcpyHostToDevice, s));
+    }
+    hipLaunchKernelGGL(k_level_init, dim3(1), dim3(kBlockThreads), 0, s, sc->d_cum, nbins * static_cast<unsigned>(kSpBin), sc->d_lticket, sc->d_lstate, sc->hd_lstate);
+    HIPCHK(c, hipGetLastError());
+    run.launches = 1;
+    run.active = true;
+    return AQE_OK;
+}
+
+GroupCols run_cols(const LevelRun& run) { return GroupCols{{run.col[0], run.col[1]}, {run.kmin[0], run.kmin[1]}, {run.span[0], run.span[1]}}; }
+
+// Round r's sweep of this shard into the scratch's partials (run.last_grid workgroups; 0: no tile of the round lies here).
+int level_sweep(aqe_ctx* c, uint32_t r, hipStream_t s) {
+    aqe_moment_scratch* sc = c->moments;
+    LevelRun& run = *sc->run;
+    if (!run.active || r != run.next_round || r > run.levels.R) return fail(c, AQE_ERR_INVALID, "rounds of a GROUP BY to an error threshold are enqueued in order, after its begin");
+    run.next_round = r + 1;
+    run.last_grid = 0;
+    const LaunchDesc& d = run.rounds[r];
+    if (d.ntiles == 0 || d.nfam == 0 || c->n_local == 0) return AQE_OK;
+    SweepCommon sw{};
+    sw.amount = c->amount;
+    sw.shard_lo = c->shard_lo;
+    sw.fams = sc->d_lfams + d.fam_offset;
+    sw.nfam = d.nfam;
+    sw.has_where = run.q.has_where ? 1 : 0;
+    sw.wmin = run.q.where_min;
+    sw.wmax = run.q.where_max;
+    sw.shift = query_shift(c, run.q);
+    sw.dense16 = c->dense16 ? 1 : 0;
+    sw.nt = d.samples * sizeof(double) > kInfinityCacheBytes ? 1 : 0;
+    const int rc = launch_grouped(c, run.has_filter ? &run.filter : nullptr, run_cols(run), sw, d.ntiles, nullptr, &sc->d_lstate->stop, &run.last_grid, s);
+    if (rc == AQE_OK) ++run.launches;
+    return rc;
+}
+
+// Accumulate-and-judge of round r from `src` ([nblocks][nbins][kSpBin]).
+int level_judge(aqe_ctx* c, uint32_t r, const double* src, unsigned nblocks, hipStream_t s) {
+    aqe_moment_scratch* sc = c->moments;
+    LevelRun& run = *sc->run;
+    if (!run.active || r != run.next_judge || r >= run.next_round) return fail(c, AQE_ERR_INVALID, "a level is judged once, after its round was enqueued");
+    run.next_judge = r + 1;
+    const GroupCols g = run_cols(run);
+    LevelJudge a{};
+    a.src = src;
+    a.nblocks = nblocks;
+    a.nbins = g.nbins();
+    a.cum = sc->d_cum;
+    a.ticket = sc->d_lticket;
+    a.state = sc->d_lstate;
+    a.h_state = sc->hd_lstate;
+    a.groups = sc->d_groups;
+    a.g = g.range();
+    a.pair = g.pair() ? 1 : 0;
+    a.agg = run.q.agg;
+    a.c = query_shift(c, run.q);
+    a.err = run.err;
+    a.level = r;
+    a.period = static_cast<unsigned>(run.levels.P0 >> r);
+    a.final_level = run.levels.R;
+    a.cap_level = run.cap_level;
+    const unsigned nwords = a.nbins * static_cast<unsigned>(kSpBin);
+    const unsigned grid = std::min((nwords + kWavesPerBlock - 1) / kWavesPerBlock, kJudgeGrid);
+    hipLaunchKernelGGL(k_level_judge, dim3(grid), dim3(kBlockThreads), 0, s, a);
+    HIPCHK(c, hipGetLastError());
+    ++run.launches;
+    return AQE_OK;
+}
+
+// `s` has been synchronised: the groups and the info of the query that stopped.
+int level_collect(aqe_ctx* c, aqe_group_result* out, uint32_t cap, uint32_t* n_groups, aqe_group_error_info* info) {
+    aqe_moment_scratch* sc = c->moments;
+    LevelRun& run = *sc->run;
+    const LevelState st = *sc->h_lstate;
+    run.active = false;
+    if (!st.stop) return fail(c, AQE_ERR_INVALID, "the query has not stopped: levels remain to be enqueued and judged");
+    const GroupCols g = run_cols(run);
+    if (info) {
+        std::memset(info, 0, sizeof *info);
+        info->level = st.level;
+        info->levels = run.levels.R + 1;
+        info->sample_percent = 100.0 / static_cast<double>(run.levels.P0 >> st.level);
+        info->visited = static_cast<uint64_t>(st.visited);
+        info->converged = static_cast<int32_t>(st.converged);
+        info->unsettled = st.unsettled;
+        info->worst_key = g.pair() ? pair_key(g.range(), st.worst_bin) : static_cast<int64_t>(g.kmin[0]) + st.worst_bin;
+        info->worst_rel = st.worst_rel;
+        info->launches = run.launches;
+    }
+    uint32_t k = 0;
+    for (uint32_t b = 0; b < g.nbins(); ++b) {
+        const aqe_group_result& r = sc->h_groups[b];
+        if (r.visited == 0) continue;  // a key nobody sampled
+        if (k < cap) out[k] = r;
+        ++k;
+    }
+    *n_groups = k;
+    if (k > cap) return fail(c, AQE_ERR_CAPACITY, "more groups than the caller's buffer holds (n_groups has the count)");
+    return AQE_OK;
+}
+
+// The columns of the form's entries: one column (cols[1] == 0) or the ordered pair.
+int level_columns_ok(aqe_ctx* c, const int* cols) {
+    if (!cols) return fail(c, AQE_ERR_INVALID, "null argument");
+    if (cols[1] == 0) return group_column_ok(c, cols[0]);
+    return pair_columns_ok(c, cols);
+}
+
 }  // namespace
 
 void moments_release(aqe_ctx* c) {
@@ -911,6 +1354,13 @@ void moments_release(aqe_ctx* c) {
     if (s->h_sgroups) (void)hipHostFree(s->h_sgroups);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
+    (void)hipFree(s->d_cum);
+    (void)hipFree(s->d_lticket);
+    (void)hipFree(s->d_lstate);
+    (void)hipFree(s->d_lfams);
+    if (s->h_lstate) (void)hipHostFree(s->h_lstate);
+    if (s->h_lfams) (void)hipHostFree(s->h_lfams);
+    delete s->run;
     delete s;
     c->moments = nullptr;
 }
@@ -1191,6 +1641,119 @@ int aqe_grouped_pair_spread_finish(aqe_ctx* c, const aqe_query* q, int kind, con
     rc = ensure_scratch(c);
     if (rc != AQE_OK) return rc;
     return finish_spread_groups(c, q, kind, g, dev_bins, stream_of(c, stream), out, cap, n_groups);
+}
+
+// ---- GROUP BY to an error threshold ------------------------------------------------------------------------------------------
+
+int aqe_reduce_grouped_error(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int* columns, double error_percent, double max_percent,
+                             aqe_group_result* out, uint32_t cap, uint32_t* n_groups, aqe_group_error_info* info) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!n_groups || (cap && !out)) return fail(c, AQE_ERR_INVALID, "null argument");
+    int rc = level_query_ok(c, f, q, error_percent, max_percent);
+    if (rc == AQE_OK) rc = level_columns_ok(c, columns);
+    if (rc != AQE_OK) return rc;
+    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
+    if (c->shard_lo != 0 || c->n_local != c->n_global) return fail(c, AQE_ERR_UNSUPPORTED, "aqe_reduce_grouped_error needs the whole table in this context: a shard takes the aqe_grouped_error_* calls");
+    if (info) std::memset(info, 0, sizeof *info);
+    GroupCols g;
+    rc = grouped_ranges(c, columns, n_groups, &g);
+    if (rc != AQE_OK || g.span[0] == 0) return rc;
+    hipStream_t s = c->stream;
+    rc = ensure_level_scratch(c);
+    if (rc != AQE_OK) return rc;
+    aqe_moment_scratch* sc = c->moments;
+    HIPCHK(c, hipEventRecord(sc->ev0, s));
+    rc = level_begin(c, f, q, g, error_percent, max_percent, s);
+    if (rc != AQE_OK) return rc;
+    LevelRun& run = *sc->run;
+    const uint32_t levels = run.levels.R + 1;
+    if (run.levels.nb == 0) { run.active = false; return AQE_OK; }
+    // every round back to back, no host round trip in between: the launches after the stop find the stop word set
+    for (uint32_t r = 0; r < levels; ++r) {
+        rc = level_sweep(c, r, s);
+        if (rc == AQE_OK) rc = level_judge(c, r, sc->d_gpartial, run.last_grid, s);
+        if (rc != AQE_OK) { run.active = false; return rc; }
+    }
+    HIPCHK(c, hipEventRecord(sc->ev1, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    rc = level_collect(c, out, cap, n_groups, info);
+    if (info) {
+        float ms = 0.0f;
+        HIPCHK(c, hipEventElapsedTime(&ms, sc->ev0, sc->ev1));
+        info->kernel_ms = static_cast<double>(ms);
+    }
+    return rc;
+}
+
+int aqe_grouped_error_begin(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int* columns, const int32_t* key_min, const uint32_t* span,
+                            double error_percent, double max_percent, void* stream, uint32_t* levels) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!key_min || !span || !levels) return fail(c, AQE_ERR_INVALID, "null argument");
+    int rc = level_query_ok(c, f, q, error_percent, max_percent);
+    if (rc == AQE_OK) rc = level_columns_ok(c, columns);
+    if (rc != AQE_OK) return rc;
+    GroupCols g;
+    if (columns[1] == 0) {
+        if (span[0] == 0 || span[0] > static_cast<uint32_t>(kMaxGroupBins)) return fail(c, AQE_ERR_INVALID, "nbins outside 1..1024");
+        g = one_column(columns[0], key_min[0], span[0]);
+    } else {
+        rc = pair_range_ok(c, columns, key_min, span, &g);
+        if (rc != AQE_OK) return rc;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = level_begin(c, f, q, g, error_percent, max_percent, stream_of(c, stream));
+    if (rc != AQE_OK) return rc;
+    *levels = c->moments->run->levels.nb ? c->moments->run->levels.R + 1 : 0;
+    return AQE_OK;
+}
+
+int aqe_grouped_error_enqueue_round(aqe_ctx* c, uint32_t round, double* dev_bins, void* stream) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!dev_bins) return fail(c, AQE_ERR_INVALID, "null dev_bins");
+    if (!c->moments || !c->moments->run || !c->moments->run->active) return fail(c, AQE_ERR_INVALID, "no GROUP BY to an error threshold in progress: call aqe_grouped_error_begin");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream_of(c, stream);
+    aqe_moment_scratch* sc = c->moments;
+    const int rc = level_sweep(c, round, s);
+    if (rc != AQE_OK) return rc;
+    const unsigned nwords = run_cols(*sc->run).nbins() * static_cast<unsigned>(kSpBin);
+    hipLaunchKernelGGL(k_level_bins, dim3(nwords), dim3(64), 0, s, sc->d_gpartial, sc->run->last_grid, nwords, &sc->d_lstate->stop, dev_bins);
+    HIPCHK(c, hipGetLastError());
+    ++sc->run->launches;
+    return AQE_OK;
+}
+
+int aqe_grouped_error_enqueue_judge(aqe_ctx* c, uint32_t round, const double* dev_bins, void* stream) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!dev_bins) return fail(c, AQE_ERR_INVALID, "null dev_bins");
+    if (!c->moments || !c->moments->run || !c->moments->run->active) return fail(c, AQE_ERR_INVALID, "no GROUP BY to an error threshold in progress: call aqe_grouped_error_begin");
+    HIPCHK(c, hipSetDevice(c->device));
+    return level_judge(c, round, dev_bins, 1u, stream_of(c, stream));
+}
+
+int aqe_grouped_error_stopped(aqe_ctx* c, void* stream, int* stopped) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!stopped) return fail(c, AQE_ERR_INVALID, "null argument");
+    if (!c->moments || !c->moments->run || !c->moments->run->active) return fail(c, AQE_ERR_INVALID, "no GROUP BY to an error threshold in progress: call aqe_grouped_error_begin");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(stream_of(c, stream)));
+    *stopped = c->moments->h_lstate->stop ? 1 : 0;
+    return AQE_OK;
+}
+
+int aqe_grouped_error_finish(aqe_ctx* c, void* stream, aqe_group_result* out, uint32_t cap, uint32_t* n_groups, aqe_group_error_info* info) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!n_groups || (cap && !out)) return fail(c, AQE_ERR_INVALID, "null argument");
+    if (!c->moments || !c->moments->run || !c->moments->run->active) return fail(c, AQE_ERR_INVALID, "no GROUP BY to an error threshold in progress: call aqe_grouped_error_begin");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(stream_of(c, stream)));
+    *n_groups = 0;
+    if (c->moments->run->levels.nb == 0) {  // an empty table: no groups
+        c->moments->run->active = false;
+        if (info) std::memset(info, 0, sizeof *info);
+        return AQE_OK;
+    }
+    return level_collect(c, out, cap, n_groups, info);
 }
 
 }  // extern "C"

@@ -734,6 +734,39 @@ void union_tiles(const UnionCover& cv, std::vector<UnionTile>& out) {
     }
 }
 
+// ---- GROUP BY to an error threshold: the nested block levels (contract: include/aqe_hip.h, aqe_reduce_grouped_error) ----
+bool error_levels(uint64_t n_rows, uint64_t row_base, uint64_t block_size, double start_percent, ErrorLevels& out) {
+    out = ErrorLevels{};
+    if (block_size == 0 || !(start_percent > 0.0)) return false;
+    out.n = n_rows;
+    out.base = row_base;
+    out.B = block_size;
+    out.nb = n_rows / block_size + (n_rows % block_size ? 1 : 0);
+    out.P0 = 1;
+    out.R = 0;
+    const double limit = 100.0 / start_percent;  // P_0 <= 100 / start_percent and P_0 <= nb
+    while (out.R < kMaxErrorLevels - 1 && static_cast<double>(2 * out.P0) <= limit && 2 * out.P0 <= out.nb) {
+        out.P0 *= 2;
+        ++out.R;
+    }
+    return true;
+}
+
+void error_round_families(const ErrorLevels& L, uint32_t r, ClipWindow shard, std::vector<aqe_family>& out) {
+    if (L.nb == 0 || r > L.R) return;
+    const u64 B = L.B, P = L.P0 >> r;         // this level's period
+    const u64 first = r == 0 ? 0 : P;         // first block of the round; the next ones follow every `every` blocks
+    const u64 every = r == 0 ? P : 2 * P;     // (round r >= 1 takes the blocks j % P_{r-1} == P_r)
+    if (first >= L.nb) return;
+    const u64 nseg = (L.nb - first + every - 1) / every;
+    const u64 last_block = first + (nseg - 1) * every;
+    const u64 last_rows = std::min((last_block + 1) * B, L.n) - last_block * B;  // the table's last block may be short
+    aqe_family f;
+    if (every == 1) f = blocks(L.base, L.n, L.n, L.n);  // every block: one run of rows (the exact scan)
+    else f = blocks(L.base + first * B, every * B, B, (nseg - 1) * B + last_rows);
+    clip_push(out, f, shard);
+}
+
 double confidence_heuristic(double pct, uint64_t total) {
     double sample = static_cast<double>(total) * pct / 100.0;
     if (sample >= 1000) return 0.95;

@@ -124,6 +124,19 @@ constexpr uint32_t kUnionTileSlots = 1024;
 bool build_union_cover(const std::vector<UnionRun>& runs, uint32_t ntargets, UnionCover& out);
 void union_tiles(const UnionCover& cv, std::vector<UnionTile>& out);
 
+// ---- GROUP BY to an error threshold (moments.hip): a progressive block sample whose levels are nested ----
+// Blocks of B rows over the n rows from `base` on (the table, or the query's row window); nb = ceil(n / B) of them; P0 the
+// largest power of two <= 100 / start_percent and <= nb (at least 1), R = log2 P0.  After level r the sample is every block
+// j with j % (P0 >> r) == 0; round 0 sweeps those of level 0, round r >= 1 the blocks level r adds (j % P_{r-1} == P_r):
+// one family each, the last block clipped to the table, clipped to the shard like every planned family.
+constexpr uint32_t kMaxErrorLevels = 32;
+struct ErrorLevels {
+    uint64_t n = 0, base = 0, B = 0, nb = 0, P0 = 1;
+    uint32_t R = 0;  // levels 0 .. R
+};
+bool error_levels(uint64_t n_rows, uint64_t row_base, uint64_t block_size, double start_percent, ErrorLevels& out);  // false: B == 0 or start_percent <= 0
+void error_round_families(const ErrorLevels& L, uint32_t round, ClipWindow shard, std::vector<aqe_family>& out);   // appends
+
 bool parse_where(const char* query, double* lo, double* hi);   // SCH.cpp:277-294
 double confidence_heuristic(double pct, uint64_t total);        // SCH.cpp:296-305
 double error_to_sample_percent(double e);                       // CLI:243-250

@@ -94,6 +94,11 @@ void add_family(std::vector<DevFamily>& out, LaunchDesc& L, const aqe_family& f,
 
 }  // namespace
 
+void add_sweep_family(std::vector<DevFamily>& out, LaunchDesc& L, const aqe_family& f, bool dense16) {
+    uint64_t out_pos = 0;  // (a gather's output position: a sweep has none)
+    add_family(out, L, f, out_pos, dense16, true);
+}
+
 FoldParams fold_params(const aqe_plan* p, bool topup) {
     FoldParams f{};
     f.shift = query_shift(p->ctx, p->q);

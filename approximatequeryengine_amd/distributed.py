@@ -428,6 +428,48 @@ def sharded_group_by_pair(engine, query, columns, bins, all_reduce_sum: Callable
         return engine.grouped_pair_spread_finish(query, kind, kmin, span, b.data_ptr(), stream)
 
 
+def sharded_group_by_error(engine, query, columns, error_percent: float, max_percent: float, bins, all_reduce_sum: Callable,
+                           all_reduce_max: Callable, stream: int = 0, key_filter=None):
+    """GROUP BY to an error threshold across ranks, collective (aqe_grouped_error_*): ``columns`` is one column or the ordered
+    pair.  The key ranges are agreed in ONE MAX all-reduce; then, level by level, every rank bins the blocks of the round that lie
+    in its region, ONE all-reduce SUM of nbins x SPREAD_BIN doubles merges them, and every rank adds the same sums to its
+    cumulative bins and judges them on its device — so every rank stops at the same level with the same groups.  The pinned
+    stop word is read once per level.  Returns (groups, GroupErrorInfo).
+
+    bins    float64 tensor on the engine's device with room for SPREAD_BIN * (number of bins) doubles (at most SPREAD_BIN * 1024)"""
+    from ._native import ERR_UNSUPPORTED, SPREAD_BIN, AqeError, GroupErrorInfo
+    stream = _stream_for(stream, bins)
+    cols = [int(c) for c in columns]
+    with _torch_on(stream, bins):
+        flat = []
+        for col in cols:
+            lo, hi = engine.group_key_range(col)
+            flat += [-float(lo), float(hi)]
+        rng = bins.new_tensor(flat)
+        all_reduce_max(rng)
+        r = [int(v) for v in rng.tolist()]
+        kmin, kmax = [-r[2 * i] for i in range(len(cols))], [r[2 * i + 1] for i in range(len(cols))]
+        if any(hi < lo for lo, hi in zip(kmin, kmax)):
+            return [], GroupErrorInfo()  # an empty table
+        span = [hi - lo + 1 for lo, hi in zip(kmin, kmax)]
+        nbins = span[0] * (span[1] if len(cols) == 2 else 1)
+        if nbins > 1024:
+            if len(cols) == 2:
+                raise AqeError(ERR_UNSUPPORTED, f"GROUP BY over both key columns: the columns span {span[0]} x {span[1]} keys, more than 1024 bins")
+            raise AqeError(ERR_UNSUPPORTED, "group column spans more than 1024 distinct values")
+        if bins.numel() < SPREAD_BIN * nbins:
+            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {SPREAD_BIN * nbins} needed")
+        b = bins[: SPREAD_BIN * nbins]
+        levels = engine.grouped_error_begin(query, cols, kmin, span, error_percent, max_percent, stream, key_filter)
+        for level in range(levels):
+            engine.grouped_error_enqueue_round(level, b.data_ptr(), stream)
+            all_reduce_sum(b)
+            engine.grouped_error_enqueue_judge(level, b.data_ptr(), stream)
+            if engine.grouped_error_stopped(stream):
+                break
+        return engine.grouped_error_finish(stream)
+
+
 # ---- the variance-aware samplers over a sharded table (SURVEY 8e "what does not shard") ---------------------------------
 # Both need one fact about the WHOLE table before a shard can plan (include/aqe_hip.h, the block above aqe_zone_moments).
 # The exchanges below are small host arrays, once per table and query shape — `host_all_reduce_sum(a) -> a summed over the

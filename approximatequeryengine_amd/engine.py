@@ -575,6 +575,45 @@ class Engine:
                                                            C.c_void_p(dev_bins_ptr), C.c_void_p(stream), out, max_groups, C.byref(n)))
         return list(out[: n.value])
 
+    # -- GROUP BY to an error threshold (aqe_reduce_grouped_error and its stepwise multi-GPU form) --
+    def reduce_grouped_error(self, query: Query, columns: Sequence[int], error_percent: float, max_percent: float = 100.0,
+                             key_filter: "Optional[nat.KeyFilter]" = None, max_groups: int = 1024):
+        """Sample nested block levels until every group's 95 % half-width is within error_percent of its value (SUM / AVG; one
+        column or the ordered pair): (list of GroupResult of the stop level, GroupErrorInfo)."""
+        out = (nat.GroupResult * max_groups)()
+        n, info = C.c_uint32(), nat.GroupErrorInfo()
+        cols = [int(c) for c in columns] + [0] * (2 - len(columns))
+        self._chk(nat.lib().aqe_reduce_grouped_error(self._h, _filter_ref(key_filter), C.byref(query), _pair(C.c_int, cols), float(error_percent),
+                                                     float(max_percent), out, max_groups, C.byref(n), C.byref(info)))
+        return list(out[: n.value]), info
+
+    def grouped_error_begin(self, query: Query, columns: Sequence[int], key_min: Sequence[int], span: Sequence[int], error_percent: float,
+                            max_percent: float = 100.0, stream: int = 0, key_filter: "Optional[nat.KeyFilter]" = None) -> int:
+        """Starts the stepwise form over the agreed key ranges; returns the number of levels."""
+        levels = C.c_uint32()
+        cols = [int(c) for c in columns] + [0] * (2 - len(columns))
+        kmin, sp = list(key_min) + [0] * (2 - len(key_min)), list(span) + [1] * (2 - len(span))
+        self._chk(nat.lib().aqe_grouped_error_begin(self._h, _filter_ref(key_filter), C.byref(query), _pair(C.c_int, cols), _pair(C.c_int32, kmin),
+                                                    _pair(C.c_uint32, sp), float(error_percent), float(max_percent), C.c_void_p(stream), C.byref(levels)))
+        return levels.value
+
+    def grouped_error_enqueue_round(self, round: int, dev_bins_ptr: int, stream: int = 0):
+        self._chk(nat.lib().aqe_grouped_error_enqueue_round(self._h, int(round), C.c_void_p(dev_bins_ptr), C.c_void_p(stream)))
+
+    def grouped_error_enqueue_judge(self, round: int, dev_bins_ptr: int, stream: int = 0):
+        self._chk(nat.lib().aqe_grouped_error_enqueue_judge(self._h, int(round), C.c_void_p(dev_bins_ptr), C.c_void_p(stream)))
+
+    def grouped_error_stopped(self, stream: int = 0) -> bool:
+        stopped = C.c_int()
+        self._chk(nat.lib().aqe_grouped_error_stopped(self._h, C.c_void_p(stream), C.byref(stopped)))
+        return bool(stopped.value)
+
+    def grouped_error_finish(self, stream: int = 0, max_groups: int = 1024):
+        out = (nat.GroupResult * max_groups)()
+        n, info = C.c_uint32(), nat.GroupErrorInfo()
+        self._chk(nat.lib().aqe_grouped_error_finish(self._h, C.c_void_p(stream), out, max_groups, C.byref(n), C.byref(info)))
+        return list(out[: n.value]), info
+
     def gather(self, query: Query) -> np.ndarray:
         """Rows of the record-returning sampler, as a RECORD_DTYPE array."""
         n = C.c_uint64()

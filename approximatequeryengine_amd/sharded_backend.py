@@ -231,13 +231,19 @@ class ShardedBPlusDB(CustomBPlusDB):
                 raise RuntimeError("No samples collected")
         return out
 
-    def approx_group_by(self, agg: str, group_by: str = "region", sample_percent: float = 10.0, method: str = "rowid",
-                        where=None, block_size: int = 1000, key_where=None) -> "dict[str, GroupEstimate]":
+    def approx_group_by(self, agg: str, group_by: str = "region", sample_percent=None, method=None,
+                        where=None, block_size: int = 1000, key_where=None, error_percent=None, max_percent: float = 100.0) -> "dict[str, GroupEstimate]":
         """GROUP BY over all ranks: the key range is agreed (one MAX all-reduce), every rank bins the part of the sample inside
-        its region, ONE all-reduce SUM merges the bins (distributed.sharded_group_by; both columns: sharded_group_by_pair)."""
+        its region, ONE all-reduce SUM merges the bins (distributed.sharded_group_by; both columns: sharded_group_by_pair).
+        With ``error_percent``: level by level, one all-reduce SUM of the bins per level, every rank judging the same sums
+        (distributed.sharded_group_by_error)."""
         import torch
         cols = group_columns(group_by)
         col = cols[0]
+        if error_percent is not None:
+            return self._group_by_error(agg, cols, sample_percent, method, where, block_size, key_where, error_percent, max_percent)
+        sample_percent = 10.0 if sample_percent is None else sample_percent
+        method = "rowid" if method is None else method
         m = {"rowid": nat.M_ROWID_MOD, "stride": nat.M_MEMORY_STRIDE, "block": nat.M_BLOCK, "page": nat.M_PAGE, "exact": nat.M_EXACT}[method]
         self._eng()
         bs = 4096 if (method == "page" and block_size == 1000) else block_size
@@ -304,6 +310,15 @@ class ShardedBPlusDB(CustomBPlusDB):
         with torch.cuda.stream(self._side):
             bins = self._buffer(nat.SPREAD_BIN * 1024)
             return sharded_filtered_group_by(self._engine, f, q, col, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, kind=kind)
+
+    def _grouped_error(self, f, q, cols, error_percent, max_percent):
+        import torch
+        from .distributed import sharded_group_by_error
+        self._eng()
+        with torch.cuda.stream(self._side):
+            bins = self._buffer(nat.SPREAD_BIN * 1024)
+            return sharded_group_by_error(self._engine, q, cols, error_percent, max_percent, bins, self._ar_sum, self._ar_max,
+                                          stream=self._side.cuda_stream, key_filter=f)
 
     # ---- GROUP BY both key columns: one MAX all-reduce of both key ranges, one all-reduce SUM of the bins ----
     def _grouped_pair(self, f, q, cols):

@@ -616,6 +616,73 @@ AQE_API int aqe_grouped_pair_finish(aqe_ctx* ctx, const aqe_query* q, const int3
 AQE_API int aqe_grouped_pair_spread_finish(aqe_ctx* ctx, const aqe_query* q, int kind, const int32_t key_min[2], const uint32_t span[2],
                                            const double* dev_bins, void* stream, aqe_spread_group_result* out, uint32_t cap, uint32_t* n_groups);
 
+/* ---- GROUP BY to an error threshold: sample until every group's interval is within e % ---------------------------------
+ * The reference's execute_query_groupby_with_ci (EXE:202-321) has no error-threshold form; this contract is the project's.
+ * Sample levels: a progressive BLOCK sample whose levels are nested.  B = q->block_size rows per block, block j = rows
+ * [jB, min((j+1)B, N)) of the N rows of the table (of q's row window when it has one), nb = ceil(N / B) blocks.  P_0 is the
+ * largest power of two with P_0 <= 100 / q->sample_percent (the START percentage of this form) and P_0 <= nb (P_0 = 1, one
+ * level, is legal; at most 32 levels).  Level r = 0 .. R, R = log2 P_0, has period P_r = P_0 >> r: the cumulative sample after
+ * level r is every block with j % P_r == 0.  Round 0 sweeps those; round r >= 1 only the blocks the level adds
+ * (j % P_{r-1} == P_r: the family row0 = P_r B, pitch = P_{r-1} B, seg_len = B, step 1), the last, short block clipped, each
+ * family clipped to the shard.  Level R is every block: the loop always ends.  (Blocks, not strides: a power-of-two row
+ * stride would alias with keys that follow from the row number, and contiguous rows take the 16-byte loads.)
+ * Bins: per bin, cumulatively over the rounds, {n, P1, P2, P3, P4, visited} (AQE_SPREAD_BIN) from the grouped power-sum sweep
+ * for one column or the ordered pair, under q's amount WHERE and an optional key filter; refusals as aqe_reduce_grouped_pair.
+ * Stop rule, on the device after each level, on the cumulative bins: every group is finished as aqe_reduce_filtered_grouped
+ * would at sample_percent = 100 / P_r (1.96 half-width).  A bin with visited == 0 is not a group.  A group is SETTLED when
+ * n >= 30 and (ci_upper - ci_lower) / 2 <= error_percent / 100 * |value|; every other group (n < 30, value == 0, n == 0 under a
+ * filter) is unsettled.  The query stops at the first level at which every group is settled (converged = 1), else at the last
+ * level whose fraction 100 / P_r does not exceed max_percent (level 0 when none does; converged = 0), else at level R, whose
+ * groups are those of the exact scan (what AQE_M_EXACT reports for the same grouping) and count as converged.
+ * Aggregates: AQE_SUM and AQE_AVG.  Grouped COUNT has no interval: AQE_COUNT is AQE_ERR_UNSUPPORTED before anything is
+ * launched.  q->method must be AQE_M_BLOCK.  Groups: as the one-shot entries (ascending keys, AQE_GROUP_KEY_PACK for a pair). */
+typedef struct aqe_group_error_info {
+    uint32_t level;        /* the level the query stopped at                                              */
+    uint32_t levels;       /* R + 1                                                                       */
+    double sample_percent; /* 100 / P_level                                                               */
+    uint64_t visited;      /* rows read, all groups, all rounds (later rounds read nothing)              */
+    int32_t converged;     /* 0: stopped by max_percent with groups unsettled                             */
+    uint32_t unsettled;    /* groups not settled at the stop level (0 at level R)                         */
+    int64_t worst_key;     /* the group with the largest half-width / |value| at the stop level (lowest key among equals;
+                              a group of value 0 counts as +inf when its half-width is positive, 0 otherwise) ...         */
+    double worst_rel;      /* ... and that ratio                                                          */
+    /* bookkeeping beside the contract's fields; launches counts what THIS context enqueued, kernel_ms is filled by
+     * aqe_reduce_grouped_error only and stays 0 in the multi-GPU form (whose time includes the caller's collectives) */
+    uint32_t launches;     /* kernel launches of the query on this context                                */
+    uint32_t reserved;
+    double kernel_ms;      /* one-call form: device time, first launch to last (HIP events)               */
+} aqe_group_error_info;
+/* Host only, no GPU: the families of round `round` over n_rows rows from row_base on, clipped to rows [shard_lo, shard_hi);
+ * *levels_out = R + 1, *period0_out = P_0.  fams may be NULL to count (at most 3 per round). */
+AQE_API int aqe_plan_group_error_round(uint64_t n_rows, uint64_t row_base, uint64_t block_size, double start_percent, uint64_t shard_lo,
+                                       uint64_t shard_hi, uint32_t round, aqe_family* fams, uint32_t cap, uint32_t* n_out, uint32_t* levels_out,
+                                       uint64_t* period0_out);
+/* One call, the whole table in this context.  columns[1] == 0: GROUP BY columns[0]; else the ordered pair.  filter may be
+ * NULL.  Every round (a sweep and an accumulate-and-judge launch) is enqueued back to back on the context's stream with no
+ * host round trip in between; rounds after the stop return at once without reading a row. */
+AQE_API int aqe_reduce_grouped_error(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const int columns[2], double error_percent,
+                                     double max_percent, aqe_group_result* out, uint32_t cap, uint32_t* n_groups, aqe_group_error_info* info);
+/* Multi-GPU form (the pattern of aqe_grouped_pair_enqueue_bins): the key ranges are agreed as there — key_min[i], span[i] of
+ * column i; one column: columns[1] == 0, span[1] == 1 — then, on every rank,
+ *     aqe_grouped_error_begin(ctx, filter, q, columns, key_min, span, error_percent, max_percent, stream, &levels)
+ *     for r = 0 .. levels - 1:
+ *         aqe_grouped_error_enqueue_round(ctx, r, dev_bins, stream)     this shard's round-r bins, span[0] * span[1] x AQE_SPREAD_BIN
+ *                                                                        doubles (zeros once the query has stopped)
+ *         <all-reduce SUM of dev_bins on `stream`>
+ *         aqe_grouped_error_enqueue_judge(ctx, r, dev_bins, stream)     adds them to the cumulative bins and judges, on the device
+ *         aqe_grouped_error_stopped(ctx, stream, &stopped)              optional: synchronises `stream` and reads the pinned stop
+ *                                                                        word — ONCE per round at most; leave the loop when set
+ *     aqe_grouped_error_finish(ctx, stream, out, cap, &n_groups, &info)  synchronises `stream`
+ * Every rank judges the same sums, so every rank stops at the same level with the same groups.  One such query per context
+ * at a time: begin starts a new one (an init launch sets up state, cumulative bins and tickets; nothing of an earlier query is
+ * relied on).  Rounds must be enqueued in order. */
+AQE_API int aqe_grouped_error_begin(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const int columns[2], const int32_t key_min[2],
+                                    const uint32_t span[2], double error_percent, double max_percent, void* stream, uint32_t* levels);
+AQE_API int aqe_grouped_error_enqueue_round(aqe_ctx* ctx, uint32_t round, double* dev_bins, void* stream);
+AQE_API int aqe_grouped_error_enqueue_judge(aqe_ctx* ctx, uint32_t round, const double* dev_bins, void* stream);
+AQE_API int aqe_grouped_error_stopped(aqe_ctx* ctx, void* stream, int* stopped);
+AQE_API int aqe_grouped_error_finish(aqe_ctx* ctx, void* stream, aqe_group_result* out, uint32_t cap, uint32_t* n_groups, aqe_group_error_info* info);
+
 /* ---- stepwise / multi-GPU form ----------------------------------------------------------------
  * One process per GPU; each rank plans the same query over its own shard.  Per round:
  *     aqe_plan_enqueue_round(plan, r, dev_vec, stream)     this shard's partial moment vector
