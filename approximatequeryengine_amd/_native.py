@@ -56,6 +56,7 @@ QUANTILE_LINEAR, QUANTILE_INVERTED_CDF = 0, 1
 QUANTILE_VEC_SUM, QUANTILE_VEC_MAX = 8194, 64
 SPREAD_VAR_SAMP, SPREAD_VAR_POP, SPREAD_STDDEV_SAMP, SPREAD_STDDEV_POP = 0, 1, 2, 3
 SPREAD_VEC, SPREAD_BIN = 8, 6
+EXTREME_VEC = 4  # {n, visited} for a SUM all-reduce, then {-min, max} for a MAX all-reduce
 KEYTERM_NONE, KEYTERM_RANGE, KEYTERM_BITMAP = 0, 1, 2
 KEY_BITMAP_BITS = 1024
 
@@ -125,6 +126,23 @@ class SpreadGroupResult(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class ExtremeResult(C.Structure):
+    """aqe_extreme_result: MIN and MAX of the sampled rows that pass, from one sweep."""
+    _fields_ = [("min", C.c_double), ("max", C.c_double), ("tail_fraction", C.c_double), ("n", C.c_uint64), ("visited", C.c_uint64),
+                ("device_status", C.c_int32), ("pad", C.c_int32), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class ExtremeGroupResult(C.Structure):
+    _fields_ = [("key", C.c_int64), ("min", C.c_double), ("max", C.c_double), ("tail_fraction", C.c_double), ("n", C.c_uint64),
+                ("visited", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class GroupErrorInfo(C.Structure):
@@ -268,6 +286,13 @@ def lib() -> C.CDLL:
         "aqe_grouped_error_enqueue_judge": (C.c_int, [vp, u32, vp, vp]),
         "aqe_grouped_error_stopped": (C.c_int, [vp, vp, P(C.c_int)]),
         "aqe_grouped_error_finish": (C.c_int, [vp, vp, P(GroupResult), u32, P(u32), P(GroupErrorInfo)]),
+        "aqe_reduce_extremes": (C.c_int, [vp, P(KeyFilter), P(Query), P(ExtremeResult)]),
+        "aqe_reduce_grouped_extremes": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), P(ExtremeGroupResult), u32, P(u32)]),
+        "aqe_extremes_enqueue": (C.c_int, [vp, P(KeyFilter), P(Query), vp, vp]),
+        "aqe_extremes_finish": (C.c_int, [vp, P(Query), vp, vp, P(ExtremeResult)]),
+        "aqe_grouped_extremes_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), P(i32), P(u32), vp, vp]),
+        "aqe_grouped_extremes_finish": (C.c_int, [vp, P(Query), P(C.c_int), P(i32), P(u32), vp, vp, P(ExtremeGroupResult), u32, P(u32)]),
+        "aqe_extremes_from_vec": (C.c_int, [P(dbl), dbl, C.c_int, P(ExtremeResult)]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),

@@ -180,6 +180,32 @@ class SpreadEstimate:
         return iter((self.value, self.ci_lower, self.ci_upper))
 
 
+class ExtremeEstimate:
+    """Result of approx_extremes / approx_min / approx_max: the smallest and the largest of the sampled amounts that pass (NaN
+    when none does, n == 0).  ``tail_fraction``: with the confidence asked for, at most that fraction of the qualifying rows lie
+    above ``max``, and at most that fraction below ``min`` (include/aqe_hip.h, aqe_extreme_result; 0 for method "exact").
+    ``value`` is the extreme approx_min / approx_max was asked for, else None; ``key`` the group's key under GROUP BY."""
+    __slots__ = ("min", "max", "n", "visited", "tail_fraction", "kernel_ms", "method", "key", "value")
+
+    def __init__(self, r, method: str):
+        for k in ("min", "max", "n", "visited", "tail_fraction"):
+            setattr(self, k, getattr(r, k))
+        self.kernel_ms = getattr(r, "kernel_ms", 0.0)
+        self.key = getattr(r, "key", None)
+        self.method = method
+        self.value = None
+
+    def __repr__(self):
+        return f"ExtremeEstimate(min={self.min!r}, max={self.max!r}, n={self.n}, tail_fraction={self.tail_fraction!r}, method={self.method!r})"
+
+
+def _named_extreme(res, which):
+    """approx_extremes' estimate, or mapping of them, with ``value`` set to the extreme named."""
+    for e in (res.values() if isinstance(res, dict) else (res,)):
+        e.value = getattr(e, which)
+    return res
+
+
 _SPREAD_KINDS = {"var_samp": nat.SPREAD_VAR_SAMP, "variance": nat.SPREAD_VAR_SAMP, "var_pop": nat.SPREAD_VAR_POP,
                  "stddev_samp": nat.SPREAD_STDDEV_SAMP, "stddev": nat.SPREAD_STDDEV_SAMP, "stddev_pop": nat.SPREAD_STDDEV_POP}
 
@@ -826,6 +852,54 @@ class CustomBPlusDB:
     def approx_stddev(self, **kw):
         """APPROX STDDEV(amount): approx_spread("stddev_samp", **kw)."""
         return self.approx_spread("stddev_samp", **kw)
+
+    def approx_extremes(self, method: str = "stride", sample_percent: float = 10.0, where: Optional[Tuple[float, float]] = None,
+                        id_between: Optional[Tuple[int, int]] = None, seed: int = 42, confidence_level: float = 0.95,
+                        group_by: Optional[str] = None, num_threads: int = 4, block_size: int = 1000, key_where: Optional[dict] = None):
+        """APPROX MIN / MAX(amount): numpy.min(X) and numpy.max(X) of the sampled amounts X (WHERE, the key window and
+        ``key_where`` applied, NaN rows left out) from ONE sweep, as an ExtremeEstimate.  A sample's extreme bounds the table's
+        from one side only: ``tail_fraction`` says how much of the qualifying rows may lie beyond it at ``confidence_level``
+        (strictly between 0 and 1).  method as approx_spread ("exact", "stride", "block", "page", "parallel_block", "region",
+        "random", "rowid" ...; CLT, adaptive, stratified and random_device samplers raise ValueError).  With ``group_by``
+        ("region" | "product_id", or both as approx_group_by takes them) the result is the key -> ExtremeEstimate mapping
+        approx_group_by returns.  There is no error-threshold form."""
+        if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
+            raise ValueError(f"MIN / MAX do not take the {method} sampler (single-round family samplers and 'random' only)")
+        if not 0.0 < float(confidence_level) < 1.0:
+            raise ValueError("MIN / MAX: confidence_level must lie strictly between 0 and 1")
+        f = None if key_where is None else _key_filter_for(key_where, method)
+        cols = None
+        if group_by is not None:
+            cols = group_columns(group_by)
+            if method == "random":
+                raise ValueError("GROUP BY takes a family sampler ('rowid', 'stride', 'block', 'page', 'exact' ...), not 'random'")
+            if self._n == 0:
+                return {}
+        q = self._approx_query("SUM", "stride" if method == "rowid" else method, sample_percent, None, where, seed, num_threads, block_size,
+                               confidence_level, id_between=id_between)
+        if method == "rowid":
+            q.method = nat.M_ROWID_MOD
+        q.confidence_level = float(confidence_level)
+        if cols is not None:
+            groups = _quantile_call(lambda: self._extremes_groups(f, q, cols))
+            if len(cols) == 2:
+                return _pair_groups(groups, lambda r: ExtremeEstimate(r, method))
+            return {str(r.key): ExtremeEstimate(r, method) for r in groups}
+        return ExtremeEstimate(_quantile_call(lambda: self._extremes(f, q)), method)
+
+    def _extremes(self, f, q):
+        return self._eng().reduce_extremes(q, f)
+
+    def _extremes_groups(self, f, q, cols):
+        return self._eng().reduce_grouped_extremes(q, cols, f)
+
+    def approx_min(self, **kw):
+        """APPROX MIN(amount): approx_extremes(**kw) with ``value`` set to the minimum."""
+        return _named_extreme(self.approx_extremes(**kw), "min")
+
+    def approx_max(self, **kw):
+        """APPROX MAX(amount): approx_extremes(**kw) with ``value`` set to the maximum."""
+        return _named_extreme(self.approx_extremes(**kw), "max")
 
     def approx_sum(self, **kw) -> ApproxResult:
         return self.approx("SUM", **kw)

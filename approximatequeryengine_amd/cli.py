@@ -9,6 +9,8 @@
     python -m approximatequeryengine_amd.cli "SELECT STDDEV(amount) FROM sales GROUP BY region" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli "SELECT SUM(amount) FROM sales WHERE region = 2 AND product_id BETWEEN 10 AND 19" --db sales.db --s 10
     python -m approximatequeryengine_amd.cli "SELECT region, product_id, AVG(amount) FROM sales GROUP BY region, product_id" --db sales.db --s 10 --ci
+    python -m approximatequeryengine_amd.cli "SELECT MIN(amount), MAX(amount) FROM sales" --db sales.db --s 10 --ci
+    python -m approximatequeryengine_amd.cli "SELECT region, MAX(amount) FROM sales WHERE product_id < 50 GROUP BY region" --db sales.db --s 10
     python -m approximatequeryengine_amd.cli --explain
 
 The reference's own CLI defines `-s/--sample` and `-e/--error` but tests `args.s` / `args.e`
@@ -97,6 +99,22 @@ def spread_of(query: str) -> Optional[Tuple[str, str]]:
     return _SPREAD_FUNCS[m.group(1).upper()], m.group(1).upper()
 
 
+def extreme_of(query: str) -> Optional[Tuple[str, ...]]:
+    """MIN(amount) and / or MAX(amount) -> the names typed, in upper case and in the order typed (each once); None for any
+    other query — and for every query that names SUM(, AVG(, COUNT(, a quantile function or a spread function, whose routing
+    stays as it was."""
+    up = query.upper()
+    if any(a + "(" in up for a in ("SUM", "AVG", "COUNT")):
+        return None
+    if re.search(r"\b(MEDIAN|PERCENTILE(_CONT|_DISC)?|VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?)\s*\(", query, re.IGNORECASE):
+        return None
+    names = []
+    for m in re.finditer(r"\b(MIN|MAX)\s*\(\s*amount\s*\)", query, re.IGNORECASE):
+        if m.group(1).upper() not in names:
+            names.append(m.group(1).upper())
+    return tuple(names) or None
+
+
 def where_clause_of(query: str) -> Optional[str]:
     """The text of the query's WHERE clause (up to GROUP BY / ORDER BY / LIMIT), or None."""
     m = re.search(r"\bWHERE\b(.*?)(?=\bGROUP\s+BY\b|\bORDER\s+BY\b|\bLIMIT\b|\bHAVING\b|;|$)", query, re.IGNORECASE | re.DOTALL)
@@ -140,7 +158,7 @@ def group_error_form(clean: str, args) -> bool:
     wrapper: the query the error-threshold form of GROUP BY answers."""
     if args.e is None or args.s is not None or parse_embedded_approx(args.query)[1]:
         return False
-    if quantile_of(clean) is not None or spread_of(clean) is not None:
+    if quantile_of(clean) is not None or spread_of(clean) is not None or extreme_of(clean) is not None:
         return False
     return bool(group_by_of(clean))
 
@@ -169,7 +187,7 @@ def get_optimal_method_for_query(query: str, dataset_size: Optional[int] = None)
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV on MI355X",
+    p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV, MIN/MAX on MI355X",
                                 allow_abbrev=False)
     p.add_argument("query", nargs="?", help="SQL query, e.g. \"SELECT SUM(amount) FROM sales\"")
     p.add_argument("--db", default="custom_demo.db", help="database file (reference format)")
@@ -212,6 +230,9 @@ def run(args, out=sys.stdout) -> int:
             return 2
     if spread_of(clean) is not None and args.e is not None:
         print("error: VARIANCE / STDDEV have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
+        return 2
+    if extreme_of(clean) is not None and args.e is not None:
+        print("error: MIN / MAX have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
         return 2
     try:
         group_by_of(clean)
@@ -290,6 +311,9 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     spread = spread_of(clean)
     if spread is not None:
         return _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0, kw)
+    extreme = extreme_of(clean)
+    if extreme is not None:
+        return _run_extremes(db, args, out, clean, qtype, extreme, aqe_backend, t0, kw)
     gb = group_by_of(clean)
     if gb and group_error_form(clean, args):
         # --e with GROUP BY: nested block levels until every group's interval is within the threshold (aqe_reduce_grouped_error)
@@ -432,6 +456,55 @@ def _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0, kw=None) -
         print(f"\ncomparison:\n   approximate: {fmt(res.value)}\n   exact:       {fmt(exact.value)}", file=out)
         if exact.value != 0:
             print(f"   actual error: {abs(res.value - exact.value) / abs(exact.value) * 100:.4f}%", file=out)
+    db.close_database()
+    return 0
+
+
+def _run_extremes(db, args, out, clean, qtype, names, aqe_backend, t0, kw=None) -> int:
+    """MIN / MAX (either or both, from one call): exact without --s; with --s (or an APPROX(...) wrapper) a sample — --method
+    block / parallel / random honoured, stride otherwise; GROUP BY region | product_id | both samples by rowid, as the other
+    grouped forms do."""
+    kw = kw or {}  # {"key_where": ...} when the WHERE clause names region / product_id
+    where = aqe_backend.parse_where(clean)
+    gb = group_by_of(clean)
+    if args.s is None and qtype != QUERY_EMBEDDED:
+        method, pct, name = "exact", 100.0, "exact"
+    else:
+        pct = args.s if args.s is not None else 10.0
+        if gb:
+            method = "exact" if pct >= 100.0 else "rowid"
+        else:
+            method = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", "stride")
+        name = "exact" if method == "exact" else f"{method} sampling ({pct}%)"
+    fmt = lambda v: "n/a" if v != v else f"{v:,.4f}"
+    if gb:
+        groups = db.approx_extremes(method=method, sample_percent=pct, where=where, confidence_level=args.confidence, group_by=", ".join(gb), **kw)
+        ms = (time.perf_counter() - t0) * 1e3
+        print(f"\n{', '.join(f'{fn}(amount)' for fn in names)} GROUP BY {', '.join(gb).lower()} ({name}):", file=out)
+        for key, g in groups.items():
+            vals = "   ".join(f"{fn.lower()} {fmt(getattr(g, fn.lower()))}" for fn in names) if len(names) > 1 else fmt(getattr(g, names[0].lower()))
+            tail = f"   (beyond: at most {g.tail_fraction * 100:.4g}%)" if (args.ci and method != "exact" and g.n) else ""
+            print(f"   {key:>6}: {vals}{tail}   n={g.n:,}", file=out)
+        print(f"   execution time: {ms:.2f} ms", file=out)
+        db.close_database()
+        return 0
+    res = db.approx_extremes(method=method, sample_percent=pct, where=where, confidence_level=args.confidence, seed=args.seed,
+                             num_threads=args.threads, **kw)
+    ms = (time.perf_counter() - t0) * 1e3
+    for fn in names:
+        print(f"\n{name} {fn}(amount) result:\n   value: {fmt(getattr(res, fn.lower()))}", file=out)
+        if args.ci and method != "exact" and res.n:
+            print(f"   with confidence {args.confidence:g}, at most {res.tail_fraction * 100:.4g}% of qualifying rows lie "
+                  f"{'below' if fn == 'MIN' else 'above'} it", file=out)
+    print(f"   samples used: {res.n:,}", file=out)
+    print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
+    if args.compare and method != "exact":
+        exact = db.approx_extremes(method="exact", where=where, **kw)
+        for fn in names:
+            a, x = getattr(res, fn.lower()), getattr(exact, fn.lower())
+            print(f"\ncomparison ({fn}):\n   approximate: {fmt(a)}\n   exact:       {fmt(x)}", file=out)
+            if x == x and a == a and x != 0 and abs(x) != float("inf"):
+                print(f"   actual error: {abs(a - x) / abs(x) * 100:.4f}%", file=out)
     db.close_database()
     return 0
 

@@ -573,5 +573,18 @@ __device__ __forceinline__ void visit_tile(const SweepCommon& sw, FamPtr fams, c
     for (int k = 0; k < kTileUnroll; ++k) visit(x[k], ka[k], kb[k], ok[k]);
 }
 
+
+// The order-preserving 64-bit key of an amount: a < b as doubles <=> okey(a) < okey(b) as integers, NaN aside (the
+// callers leave NaN out).  What the quantile passes count and what the extremes sweep feeds integer min / max atomics.
+__device__ __forceinline__ u64 okey(double x) {
+    if (x == 0.0) x = 0.0;  // -0.0 and +0.0 are one value
+    const u64 b = static_cast<u64>(__double_as_longlong(x));
+    return (b >> 63) ? ~b : (b | (1ull << 63));
+}
+__device__ __forceinline__ double okey_inv(u64 k) {
+    const u64 b = (k >> 63) ? (k & ~(1ull << 63)) : ~k;
+    return __longlong_as_double(static_cast<long long>(b));
+}
+
 }  // namespace
 }  // namespace aqe

@@ -92,6 +92,7 @@ struct StageRing {
 };
 
 struct aqe_moment_scratch;  // moments.hip
+struct aqe_extreme_scratch;  // extremes.hip
 
 struct aqe_ctx {
     StageRing ring;
@@ -155,6 +156,8 @@ struct aqe_ctx {
     // VARIANCE / STDDEV and key predicates (moments.hip): partials, tickets, pinned results of the power-sum sweep's entries,
     // made on first use
     aqe_moment_scratch* moments = nullptr;
+    // MIN / MAX (extremes.hip): partials, tickets, bins and pinned results of the extremes sweep, made on first use
+    aqe_extreme_scratch* extremes = nullptr;
 };
 
 // One persistent-sweep form of a plan's rounds (persist.hip): the tile list of all slots, who owns tiles
@@ -287,6 +290,45 @@ void quantile_release(aqe_ctx* c);
 
 // moments.hip
 void moments_release(aqe_ctx* c);
+// The two columns' ranges of a pair, and bin -> (a, b) as the results carry it (AQE_GROUP_KEY_PACK of include/aqe_hip.h).
+struct PairRange {
+    int32_t kmin_a, kmin_b;
+    uint32_t span_a, span_b;
+};
+__host__ __device__ inline int64_t pair_key(const PairRange& g, unsigned bin) {
+    const int32_t ka = static_cast<int32_t>(static_cast<int64_t>(g.kmin_a) + bin / g.span_b);
+    const int32_t kb = static_cast<int32_t>(static_cast<int64_t>(g.kmin_b) + bin % g.span_b);
+    return AQE_GROUP_KEY_PACK(ka, kb);
+}
+// The two sets of entries refuse a sampler in their own words.
+struct Wording {
+    const char* subject;  // "... do not take the <method> sampler"
+    const char* grouped;  // the grouped forms under the seeded random sampler
+};
+// What a grouped sweep bins on: one key column (col[1] == 0, span[1] == 1) or the ordered pair (A, B) of both.
+struct GroupCols {
+    int col[2];
+    int32_t kmin[2];
+    uint32_t span[2];
+    bool pair() const { return col[1] != 0; }
+    uint32_t nbins() const { return span[0] * span[1]; }
+    PairRange range() const { return PairRange{kmin[0], kmin[1], span[0], span[1]}; }
+};
+// What the sweeps over sampled rows outside moments.hip (extremes.hip) share with it.
+int check_filter(aqe_ctx* c, const aqe_key_filter* f);
+// Checks the query and takes its cached plan; refuses samplers out of scope, in the caller's words, before anything reaches a kernel.
+int moment_plan(aqe_ctx* c, const aqe_query* q, bool grouped, const Wording& w, aqe_plan** out);
+// The key column `column` as the plan's rows index it: the column itself, or its stride-major view.
+int key_pointer(aqe_ctx* c, aqe_plan* p, int column, const int32_t** out);
+// The key range of the group column(s) of a single-GPU grouped entry, with the refusals; out->span[0] stays 0 for an empty table.
+int grouped_ranges(aqe_ctx* c, const int cols[2], uint32_t* n_groups, GroupCols* out);
+// The agreed ranges of a multi-GPU pair entry.
+int pair_range_ok(aqe_ctx* c, const int* cols, const int32_t* key_min, const uint32_t* span, GroupCols* out);
+// One column (cols[1] == 0) or the ordered pair {REGION, PRODUCT} in either order.
+int level_columns_ok(aqe_ctx* c, const int* cols);
+
+// extremes.hip
+void extremes_release(aqe_ctx* c);
 
 // plans.hip
 void destroy_plan(aqe_plan* p, bool device_idle = false);  // device_idle: the caller has just synchronised the device

@@ -2,6 +2,7 @@
 // the power-sum sweep (moments.hip) applies per sampled row.
 #pragma once
 
+#include <cstddef>
 #include <limits>
 
 #include "kernels.hpp"
@@ -29,6 +30,22 @@ __host__ __device__ __forceinline__ bool term_pass(const DevTerm& t, const unsig
     const bool in = inside && ((w >> (u & 63u)) & 1ull) != 0;
     return in != (t.negate != 0);
 }
+
+#ifdef __HIPCC__
+// The two columns' maps from the kernel-argument segment of a launch whose descriptor carries a DevFilter `flt` into LDS
+// (32 threads, one word each).
+template <typename Launch>
+__device__ __forceinline__ void stage_maps(unsigned long long (*s_map)[kMapWords]) {
+    if (threadIdx.x < 2 * kMapWords) {
+        typedef const __attribute__((address_space(4))) char* KargBytes;
+        typedef const __attribute__((address_space(4))) unsigned long long* KargWords;
+        const KargBytes K = (KargBytes)__builtin_amdgcn_kernarg_segment_ptr();
+        const KargWords m = (KargWords)(K + offsetof(Launch, flt) + offsetof(DevFilter, map));
+        s_map[threadIdx.x / kMapWords][threadIdx.x % kMapWords] = m[threadIdx.x];
+    }
+    __syncthreads();
+}
+#endif
 
 inline DevTerm pass_all() { return DevTerm{std::numeric_limits<int32_t>::min(), std::numeric_limits<int32_t>::max(), 0u, 0u, ~0ull}; }
 

@@ -81,19 +81,6 @@ struct MomentLaunch {
 };
 static_assert(sizeof(MomentLaunch) <= 4096, "kernel arguments are limited to 4 KB");
 
-// The two columns' maps from the kernel-argument segment into LDS (32 threads, one word each).
-template <typename Launch>
-__device__ __forceinline__ void stage_maps(u64 (*s_map)[kMapWords]) {
-    if (threadIdx.x < 2 * kMapWords) {
-        typedef const AQE_KARG char* KargBytes;
-        typedef const AQE_KARG u64* KargWords;
-        const KargBytes K = (KargBytes)__builtin_amdgcn_kernarg_segment_ptr();
-        const KargWords m = (KargWords)(K + offsetof(Launch, flt) + offsetof(DevFilter, map));
-        s_map[threadIdx.x / kMapWords][threadIdx.x % kMapWords] = m[threadIdx.x];
-    }
-    __syncthreads();
-}
-
 // SUM / AVG / COUNT from the power sums: the state make_result reads (device_common.hpp), one round folded.
 __host__ __device__ inline aqe_result result_from_vec(const double* vec, const FinalizeParams& fin, uint32_t row_bytes) {
     QueryState s{};
@@ -394,16 +381,6 @@ __global__ __launch_bounds__(64) void k_groups_finish(const double* __restrict__
     out[b] = group_result(bins + static_cast<size_t>(b) * kSpBin, static_cast<int64_t>(key_min) + b, c, pct, agg);
 }
 
-// The two columns' ranges of a pair, and bin -> (a, b) as the results carry it (AQE_GROUP_KEY_PACK of include/aqe_hip.h).
-struct PairRange {
-    int32_t kmin_a, kmin_b;
-    uint32_t span_a, span_b;
-};
-__host__ __device__ inline int64_t pair_key(const PairRange& g, unsigned bin) {
-    const int32_t ka = static_cast<int32_t>(static_cast<int64_t>(g.kmin_a) + bin / g.span_b);
-    const int32_t kb = static_cast<int32_t>(static_cast<int64_t>(g.kmin_b) + bin % g.span_b);
-    return AQE_GROUP_KEY_PACK(ka, kb);
-}
 __global__ __launch_bounds__(64) void k_groups_finish_pair(const double* __restrict__ bins, PairRange g, double c, double pct, int agg,
                                                            aqe_group_result* __restrict__ out) {
     const unsigned b = blockIdx.x * 64 + threadIdx.x;
@@ -702,18 +679,7 @@ int group_column_ok(aqe_ctx* c, int group_column) {
     return AQE_OK;
 }
 
-int check_filter(aqe_ctx* c, const aqe_key_filter* f) {
-    if (!f) return fail(c, AQE_ERR_INVALID, "null filter");
-    for (int k = 0; k < 2; ++k)
-        if (const char* why = term_defect(f->term[k])) return fail(c, AQE_ERR_INVALID, why);
-    return AQE_OK;
-}
 
-// The two sets of entries refuse a sampler in their own words.
-struct Wording {
-    const char* subject;  // "... do not take the <method> sampler"
-    const char* grouped;  // the grouped forms under the seeded random sampler
-};
 constexpr Wording kSpreadWords{"VARIANCE / STDDEV do not take the ",
                                "grouped VARIANCE / STDDEV takes a single-round family sampler (exact, stride, rowid-mod, block, page, pointer, region ...)"};
 constexpr Wording kFilterWords{"key predicates do not take the ",
@@ -724,28 +690,6 @@ int unsupported(aqe_ctx* c, const Wording& w, int method) {
     return fail(c, AQE_ERR_UNSUPPORTED, std::string(w.subject) + method_name(method) + " sampler (single-round family samplers and the seeded random sampler only)");
 }
 
-// Checks the query and takes its cached plan; refuses samplers out of scope before anything reaches a kernel.
-int moment_plan(aqe_ctx* c, const aqe_query* q, bool grouped, const Wording& w, aqe_plan** out) {
-    if (!q) return fail(c, AQE_ERR_INVALID, "null query");
-    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
-    if (!(q->sample_percent > 0.0)) return fail(c, AQE_ERR_INVALID, "sample_percent must be positive");
-    switch (q->method) {
-        case AQE_M_OPTIMIZED_CLT: case AQE_M_CLT_DUAL_POINTER: case AQE_M_ADAPTIVE_BLOCK: case AQE_M_STRATIFIED_BLOCK: case AQE_M_RANDOM_DEVICE:
-            return unsupported(c, w, q->method);
-        default: break;
-    }
-    aqe_plan* p = nullptr;
-    int rc = cached_plan(c, q, &p);
-    if (rc != AQE_OK) return rc;
-    rc = plan_is_current(p);
-    if (rc != AQE_OK) return rc;
-    bool pair = false;
-    for (const DevFamily& f : p->h_fams) pair = pair || (f.flags & AQE_F_PAIR);
-    if (p->host.is_perm || p->host.is_clt || p->host.on_sorted || p->rounds.size() > 1 || pair) return unsupported(c, w, q->method);
-    if (grouped && p->host.is_random) return fail(c, AQE_ERR_UNSUPPORTED, w.grouped);
-    *out = p;
-    return AQE_OK;
-}
 
 SpreadFin fin_for(const aqe_query* q, int kind) {
     SpreadFin f;
@@ -769,14 +713,6 @@ FinalizeParams finalize_for(const aqe_ctx* c, const aqe_query& q) {
 
 inline hipStream_t stream_of(aqe_ctx* c, void* stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
 
-// The key column `column` as the plan's rows index it: the column itself, or its stride-major view.
-int key_pointer(aqe_ctx* c, aqe_plan* p, int column, const int32_t** out) {
-    int rc = ensure_keys(c, column);
-    if (rc != AQE_OK) return rc;
-    *out = c->keycol[column - 1];
-    if (p->view_rounds) rc = ensure_key_view(c, column, p->view_step_rounds, out);
-    return rc;
-}
 
 // One launch: this shard's kSpVec sums into `vec`, under the filter `f` (null: none); fused: the last workgroup also
 // finishes into a pinned result.
@@ -887,15 +823,6 @@ int spread_finish(aqe_ctx* c, const aqe_query* q, int kind, const double* dev_ve
     return AQE_OK;
 }
 
-// What a grouped sweep bins on: one key column (col[1] == 0, span[1] == 1) or the ordered pair (A, B) of both.
-struct GroupCols {
-    int col[2];
-    int32_t kmin[2];
-    uint32_t span[2];
-    bool pair() const { return col[1] != 0; }
-    uint32_t nbins() const { return span[0] * span[1]; }
-    PairRange range() const { return PairRange{kmin[0], kmin[1], span[0], span[1]}; }
-};
 inline GroupCols one_column(int column, int32_t key_min, uint32_t nbins) { return GroupCols{{column, 0}, {key_min, 0}, {nbins, 1u}}; }
 
 // The grouped sweep's partial buffer, grown on demand.
@@ -1055,33 +982,6 @@ int finish_spread_groups(aqe_ctx* c, const aqe_query* q, int kind, const GroupCo
 
 const char* column_name(int column) { return column == AQE_GROUP_REGION ? "region" : "product_id"; }
 
-// The key range of the group column(s) — cols[1] == 0: one column — of the single-GPU grouped entries, with their refusals.
-// out->span[0] stays 0 for an empty table: no groups.
-int grouped_ranges(aqe_ctx* c, const int cols[2], uint32_t* n_groups, GroupCols* out) {
-    *n_groups = 0;
-    GroupCols g{{cols[0], cols[1]}, {0, 0}, {0u, 1u}};
-    *out = g;
-    int64_t span[2] = {0, 1};
-    for (int i = 0; i < (g.pair() ? 2 : 1); ++i) {
-        int32_t kmin = 0, kmax = -1;
-        const int rc = aqe_group_key_range(c, g.col[i], &kmin, &kmax);
-        if (rc != AQE_OK) return rc;
-        if (kmax < kmin) return AQE_OK;
-        g.kmin[i] = kmin;
-        span[i] = static_cast<int64_t>(kmax) - kmin + 1;
-    }
-    if (!g.pair() && span[0] > kMaxGroupBins) return fail(c, AQE_ERR_UNSUPPORTED, "group column spans more than 1024 distinct values");
-    if (g.pair() && (span[0] > kMaxGroupBins || span[1] > kMaxGroupBins || span[0] * span[1] > kMaxGroupBins))
-        return fail(c, AQE_ERR_UNSUPPORTED, std::string("GROUP BY ") + column_name(g.col[0]) + ", " + column_name(g.col[1]) + ": the columns span " +
-                                                std::to_string(span[0]) + " x " + std::to_string(span[1]) + " keys, more than 1024 bins");
-    g.span[0] = static_cast<uint32_t>(span[0]);
-    g.span[1] = static_cast<uint32_t>(span[1]);
-    HIPCHK(c, hipSetDevice(c->device));
-    const int rc = ensure_scratch(c);
-    if (rc != AQE_OK) return rc;
-    *out = g;
-    return AQE_OK;
-}
 
 // ... and the sweep into the context's own bins.
 int grouped_prologue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int cols[2], uint32_t* n_groups, GroupCols* out) {
@@ -1123,19 +1023,6 @@ int pair_columns_ok(aqe_ctx* c, const int* cols) {
     return AQE_OK;
 }
 
-// The agreed ranges of the multi-GPU pair entries.
-int pair_range_ok(aqe_ctx* c, const int* cols, const int32_t* key_min, const uint32_t* span, GroupCols* out) {
-    int rc = pair_columns_ok(c, cols);
-    if (rc != AQE_OK) return rc;
-    if (!key_min || !span) return fail(c, AQE_ERR_INVALID, "null argument");
-    const uint64_t bins = static_cast<uint64_t>(span[0]) * span[1];
-    if (span[0] == 0 || span[1] == 0) return fail(c, AQE_ERR_INVALID, "a span of the pair is zero");
-    if (bins > static_cast<uint64_t>(kMaxGroupBins))
-        return fail(c, AQE_ERR_UNSUPPORTED, std::string("GROUP BY ") + column_name(cols[0]) + ", " + column_name(cols[1]) + ": the columns span " +
-                                                std::to_string(span[0]) + " x " + std::to_string(span[1]) + " keys, more than 1024 bins");
-    *out = GroupCols{{cols[0], cols[1]}, {key_min[0], key_min[1]}, {span[0], span[1]}};
-    return AQE_OK;
-}
 
 // What the multi-GPU grouped enqueues check of their arguments, and the device.
 int bins_arguments(aqe_ctx* c, int group_column, const double* dev_bins, uint32_t nbins) {
@@ -1329,14 +1216,97 @@ int level_collect(aqe_ctx* c, aqe_group_result* out, uint32_t cap, uint32_t* n_g
     return AQE_OK;
 }
 
+}  // namespace
+
+// ---- what the sweeps of other translation units share with this one (declared in host.hpp; extremes.hip) --------------------------
+
+int check_filter(aqe_ctx* c, const aqe_key_filter* f) {
+    if (!f) return fail(c, AQE_ERR_INVALID, "null filter");
+    for (int k = 0; k < 2; ++k)
+        if (const char* why = term_defect(f->term[k])) return fail(c, AQE_ERR_INVALID, why);
+    return AQE_OK;
+}
+
+// Checks the query and takes its cached plan; refuses samplers out of scope before anything reaches a kernel.
+int moment_plan(aqe_ctx* c, const aqe_query* q, bool grouped, const Wording& w, aqe_plan** out) {
+    if (!q) return fail(c, AQE_ERR_INVALID, "null query");
+    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
+    if (!(q->sample_percent > 0.0)) return fail(c, AQE_ERR_INVALID, "sample_percent must be positive");
+    switch (q->method) {
+        case AQE_M_OPTIMIZED_CLT: case AQE_M_CLT_DUAL_POINTER: case AQE_M_ADAPTIVE_BLOCK: case AQE_M_STRATIFIED_BLOCK: case AQE_M_RANDOM_DEVICE:
+            return unsupported(c, w, q->method);
+        default: break;
+    }
+    aqe_plan* p = nullptr;
+    int rc = cached_plan(c, q, &p);
+    if (rc != AQE_OK) return rc;
+    rc = plan_is_current(p);
+    if (rc != AQE_OK) return rc;
+    bool pair = false;
+    for (const DevFamily& f : p->h_fams) pair = pair || (f.flags & AQE_F_PAIR);
+    if (p->host.is_perm || p->host.is_clt || p->host.on_sorted || p->rounds.size() > 1 || pair) return unsupported(c, w, q->method);
+    if (grouped && p->host.is_random) return fail(c, AQE_ERR_UNSUPPORTED, w.grouped);
+    *out = p;
+    return AQE_OK;
+}
+
+// The key column `column` as the plan's rows index it: the column itself, or its stride-major view.
+int key_pointer(aqe_ctx* c, aqe_plan* p, int column, const int32_t** out) {
+    int rc = ensure_keys(c, column);
+    if (rc != AQE_OK) return rc;
+    *out = c->keycol[column - 1];
+    if (p->view_rounds) rc = ensure_key_view(c, column, p->view_step_rounds, out);
+    return rc;
+}
+
+// The key range of the group column(s) — cols[1] == 0: one column — of the single-GPU grouped entries, with their refusals.
+// out->span[0] stays 0 for an empty table: no groups.
+int grouped_ranges(aqe_ctx* c, const int cols[2], uint32_t* n_groups, GroupCols* out) {
+    *n_groups = 0;
+    GroupCols g{{cols[0], cols[1]}, {0, 0}, {0u, 1u}};
+    *out = g;
+    int64_t span[2] = {0, 1};
+    for (int i = 0; i < (g.pair() ? 2 : 1); ++i) {
+        int32_t kmin = 0, kmax = -1;
+        const int rc = aqe_group_key_range(c, g.col[i], &kmin, &kmax);
+        if (rc != AQE_OK) return rc;
+        if (kmax < kmin) return AQE_OK;
+        g.kmin[i] = kmin;
+        span[i] = static_cast<int64_t>(kmax) - kmin + 1;
+    }
+    if (!g.pair() && span[0] > kMaxGroupBins) return fail(c, AQE_ERR_UNSUPPORTED, "group column spans more than 1024 distinct values");
+    if (g.pair() && (span[0] > kMaxGroupBins || span[1] > kMaxGroupBins || span[0] * span[1] > kMaxGroupBins))
+        return fail(c, AQE_ERR_UNSUPPORTED, std::string("GROUP BY ") + column_name(g.col[0]) + ", " + column_name(g.col[1]) + ": the columns span " +
+                                                std::to_string(span[0]) + " x " + std::to_string(span[1]) + " keys, more than 1024 bins");
+    g.span[0] = static_cast<uint32_t>(span[0]);
+    g.span[1] = static_cast<uint32_t>(span[1]);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    *out = g;
+    return AQE_OK;
+}
+
+// The agreed ranges of the multi-GPU pair entries.
+int pair_range_ok(aqe_ctx* c, const int* cols, const int32_t* key_min, const uint32_t* span, GroupCols* out) {
+    int rc = pair_columns_ok(c, cols);
+    if (rc != AQE_OK) return rc;
+    if (!key_min || !span) return fail(c, AQE_ERR_INVALID, "null argument");
+    const uint64_t bins = static_cast<uint64_t>(span[0]) * span[1];
+    if (span[0] == 0 || span[1] == 0) return fail(c, AQE_ERR_INVALID, "a span of the pair is zero");
+    if (bins > static_cast<uint64_t>(kMaxGroupBins))
+        return fail(c, AQE_ERR_UNSUPPORTED, std::string("GROUP BY ") + column_name(cols[0]) + ", " + column_name(cols[1]) + ": the columns span " +
+                                                std::to_string(span[0]) + " x " + std::to_string(span[1]) + " keys, more than 1024 bins");
+    *out = GroupCols{{cols[0], cols[1]}, {key_min[0], key_min[1]}, {span[0], span[1]}};
+    return AQE_OK;
+}
+
 // The columns of the form's entries: one column (cols[1] == 0) or the ordered pair.
 int level_columns_ok(aqe_ctx* c, const int* cols) {
     if (!cols) return fail(c, AQE_ERR_INVALID, "null argument");
     if (cols[1] == 0) return group_column_ok(c, cols[0]);
     return pair_columns_ok(c, cols);
 }
-
-}  // namespace
 
 void moments_release(aqe_ctx* c) {
     aqe_moment_scratch* s = c->moments;

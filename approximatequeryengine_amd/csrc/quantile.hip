@@ -88,15 +88,6 @@ struct QPassArgs {
     int32_t fused, pad;
 };
 
-__device__ __forceinline__ u64 okey(double x) {
-    if (x == 0.0) x = 0.0;  // -0.0 and +0.0 are one value
-    const u64 b = static_cast<u64>(__double_as_longlong(x));
-    return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-__device__ __forceinline__ double okey_inv(u64 k) {
-    const u64 b = (k >> 63) ? (k & ~(1ull << 63)) : ~k;
-    return __longlong_as_double(static_cast<long long>(b));
-}
 __host__ __device__ inline unsigned bins_log2_for(unsigned groups) {  // groups x bins <= kQBins, at most 4096 bins
     unsigned l = 12;
     while ((static_cast<unsigned>(groups) << l) > kQBins) --l;

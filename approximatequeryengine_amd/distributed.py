@@ -428,6 +428,63 @@ def sharded_group_by_pair(engine, query, columns, bins, all_reduce_sum: Callable
         return engine.grouped_pair_spread_finish(query, kind, kmin, span, b.data_ptr(), stream)
 
 
+def sharded_extremes(engine, query, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
+    """MIN / MAX across the ranks of a process group (engine.Engine interface), collective: every rank sweeps the part of the
+    sample inside its shard into EXTREME_VEC doubles (aqe_extremes_enqueue, under ``key_filter`` when there is one), ONE
+    all-reduce SUM merges {n, visited}, ONE all-reduce MAX merges {-min, max} (an empty shard contributes 0 and -inf), and
+    every rank finishes the same vector — so every rank returns the same bits.
+
+    vec     float64 tensor on the engine's device with room for EXTREME_VEC doubles
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    from ._native import EXTREME_VEC
+    stream = _stream_for(stream, vec)
+    if vec.numel() < EXTREME_VEC:
+        raise ValueError(f"vector holds {vec.numel()} doubles, {EXTREME_VEC} needed")
+    with _torch_on(stream, vec):
+        v = vec[:EXTREME_VEC]
+        engine.extremes_enqueue(query, v.data_ptr(), stream, key_filter)
+        all_reduce_sum(v[:2])
+        all_reduce_max(v[2:])
+        return engine.extremes_finish(query, v.data_ptr(), stream)
+
+
+def sharded_group_extremes(engine, query, columns, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
+    """GROUP BY MIN / MAX across ranks, collective: ``columns`` is one column or the ordered pair (A, B).  The key ranges are
+    agreed in ONE MAX all-reduce (as sharded_group_by_pair); every rank bins its part of the sample into
+    [nbins x {n, visited}] + [nbins x {-min, max}] (aqe_grouped_extremes_enqueue_bins), ONE all-reduce SUM merges the first
+    half, ONE all-reduce MAX the second, and every rank finishes the same bins.  More than 1024 bins is refused on every rank
+    alike, before the sweep.
+
+    bins    float64 tensor on the engine's device with room for 4 * (number of bins) doubles (at most 4 * 1024)"""
+    from ._native import ERR_UNSUPPORTED, AqeError
+    stream = _stream_for(stream, bins)
+    cols = [int(c) for c in columns]
+    with _torch_on(stream, bins):
+        flat = []
+        for col in cols:
+            lo, hi = engine.group_key_range(col)
+            flat += [-float(lo), float(hi)]
+        rng = bins.new_tensor(flat)
+        all_reduce_max(rng)
+        r = [int(v) for v in rng.tolist()]
+        kmin, kmax = [-r[2 * i] for i in range(len(cols))], [r[2 * i + 1] for i in range(len(cols))]
+        if any(hi < lo for lo, hi in zip(kmin, kmax)):
+            return []  # an empty table
+        span = [hi - lo + 1 for lo, hi in zip(kmin, kmax)]
+        nbins = span[0] * (span[1] if len(cols) == 2 else 1)
+        if nbins > 1024:
+            if len(cols) == 2:
+                raise AqeError(ERR_UNSUPPORTED, f"GROUP BY over both key columns: the columns span {span[0]} x {span[1]} keys, more than 1024 bins")
+            raise AqeError(ERR_UNSUPPORTED, "group column spans more than 1024 distinct values")
+        if bins.numel() < 4 * nbins:
+            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {4 * nbins} needed")
+        b = bins[: 4 * nbins]
+        engine.grouped_extremes_enqueue_bins(query, cols, kmin, span, b.data_ptr(), stream, key_filter)
+        all_reduce_sum(b[: 2 * nbins])
+        all_reduce_max(b[2 * nbins:])
+        return engine.grouped_extremes_finish(query, cols, kmin, span, b.data_ptr(), stream)
+
+
 def sharded_group_by_error(engine, query, columns, error_percent: float, max_percent: float, bins, all_reduce_sum: Callable,
                            all_reduce_max: Callable, stream: int = 0, key_filter=None):
     """GROUP BY to an error threshold across ranks, collective (aqe_grouped_error_*): ``columns`` is one column or the ordered

@@ -614,6 +614,45 @@ class Engine:
         self._chk(nat.lib().aqe_grouped_error_finish(self._h, C.c_void_p(stream), out, max_groups, C.byref(n), C.byref(info)))
         return list(out[: n.value]), info
 
+    # -- MIN / MAX (aqe_reduce_extremes and its kin): one sweep answers both; key_filter may be None everywhere --
+    def reduce_extremes(self, query: Query, key_filter: "Optional[nat.KeyFilter]" = None) -> "nat.ExtremeResult":
+        out = nat.ExtremeResult()
+        self._chk(nat.lib().aqe_reduce_extremes(self._h, _filter_ref(key_filter), C.byref(query), C.byref(out)))
+        return out
+
+    def reduce_grouped_extremes(self, query: Query, columns: Sequence[int], key_filter: "Optional[nat.KeyFilter]" = None, max_groups: int = 1024):
+        """MIN / MAX per group of one column or the ordered pair: list of ExtremeGroupResult ascending by key."""
+        out = (nat.ExtremeGroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_reduce_grouped_extremes(self._h, _filter_ref(key_filter), C.byref(query), _pair(C.c_int, _two(columns, 0)), out, max_groups,
+                                                        C.byref(n)))
+        return list(out[: n.value])
+
+    def extremes_enqueue(self, query: Query, dev_vec_ptr: int, stream: int = 0, key_filter: "Optional[nat.KeyFilter]" = None):
+        """This shard's EXTREME_VEC doubles into device memory: all-reduce SUM of [0, 2), MAX of [2, 4), then extremes_finish."""
+        self._chk(nat.lib().aqe_extremes_enqueue(self._h, _filter_ref(key_filter), C.byref(query), C.c_void_p(dev_vec_ptr), C.c_void_p(stream)))
+
+    def extremes_finish(self, query: Query, dev_vec_ptr: int, stream: int = 0) -> "nat.ExtremeResult":
+        out = nat.ExtremeResult()
+        self._chk(nat.lib().aqe_extremes_finish(self._h, C.byref(query), C.c_void_p(dev_vec_ptr), C.c_void_p(stream), C.byref(out)))
+        return out
+
+    def grouped_extremes_enqueue_bins(self, query: Query, columns: Sequence[int], key_min: Sequence[int], span: Sequence[int], dev_bins_ptr: int,
+                                      stream: int = 0, key_filter: "Optional[nat.KeyFilter]" = None):
+        """This shard's 4 x nbins doubles: [nbins x {n, visited}] (all-reduce SUM), then [nbins x {-min, max}] (all-reduce MAX)."""
+        self._chk(nat.lib().aqe_grouped_extremes_enqueue_bins(self._h, _filter_ref(key_filter), C.byref(query), _pair(C.c_int, _two(columns, 0)),
+                                                              _pair(C.c_int32, _two(key_min, 0)), _pair(C.c_uint32, _two(span, 1)),
+                                                              C.c_void_p(dev_bins_ptr), C.c_void_p(stream)))
+
+    def grouped_extremes_finish(self, query: Query, columns: Sequence[int], key_min: Sequence[int], span: Sequence[int], dev_bins_ptr: int,
+                                stream: int = 0, max_groups: int = 1024):
+        out = (nat.ExtremeGroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_grouped_extremes_finish(self._h, C.byref(query), _pair(C.c_int, _two(columns, 0)), _pair(C.c_int32, _two(key_min, 0)),
+                                                        _pair(C.c_uint32, _two(span, 1)), C.c_void_p(dev_bins_ptr), C.c_void_p(stream), out, max_groups,
+                                                        C.byref(n)))
+        return list(out[: n.value])
+
     def gather(self, query: Query) -> np.ndarray:
         """Rows of the record-returning sampler, as a RECORD_DTYPE array."""
         n = C.c_uint64()
@@ -667,6 +706,20 @@ def spread_from_sums(vec: Sequence[float], kind: int = nat.SPREAD_VAR_SAMP, conf
     rc = nat.lib().aqe_spread_from_sums((C.c_double * nat.SPREAD_VEC)(*v), int(kind), float(confidence_level), int(bool(exact)), C.byref(out))
     if rc != nat.OK:
         raise nat.AqeError(rc, "No samples collected" if v[0] == 0 else "bad argument")
+    return out
+
+
+def extremes_from_vec(vec: Sequence[float], confidence_level: float = 0.95, exact: bool = False) -> "nat.ExtremeResult":
+    """aqe_extremes_from_vec: MIN / MAX and the tail fraction from EXTREME_VEC (all-reduced) doubles {n, visited, -min, max}, on
+    the host — no GPU.  Raises AqeError (ERR_INVALID) when visited == 0 ("No samples collected") or confidence_level is outside
+    (0, 1)."""
+    v = [float(x) for x in vec]
+    if len(v) != nat.EXTREME_VEC:
+        raise ValueError(f"{nat.EXTREME_VEC} doubles expected: n, visited, -min, max")
+    out = nat.ExtremeResult()
+    rc = nat.lib().aqe_extremes_from_vec((C.c_double * nat.EXTREME_VEC)(*v), float(confidence_level), int(bool(exact)), C.byref(out))
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "confidence_level must lie inside (0, 1)" if not 0.0 < confidence_level < 1.0 else "No samples collected")
     return out
 
 
@@ -796,6 +849,12 @@ def _pair(ctype, values):
     if len(vals) != 2:
         raise ValueError(f"a pair takes two values, got {len(vals)}")
     return (ctype * 2)(*vals)
+
+
+def _two(values, fill):
+    """One value or two as the two a C entry takes (a single group column: the second is `fill`)."""
+    vals = [int(v) for v in values]
+    return vals + [fill] * (2 - len(vals))
 
 
 def _filter_ref(key_filter):

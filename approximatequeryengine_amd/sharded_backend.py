@@ -334,3 +334,21 @@ class ShardedBPlusDB(CustomBPlusDB):
         with torch.cuda.stream(self._side):
             bins = self._buffer(nat.SPREAD_BIN * 1024)
             return sharded_group_by_pair(self._engine, q, cols, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f, kind=kind)
+
+    # ---- MIN / MAX: one all-reduce SUM of the counts, one all-reduce MAX of {-min, max}; approx_extremes / approx_min /
+    # approx_max are CustomBPlusDB's own, over these ----
+    def _extremes(self, f, q):
+        import torch
+        from .distributed import sharded_extremes
+        self._eng()
+        with torch.cuda.stream(self._side):
+            return sharded_extremes(self._engine, q, self._buffer(nat.EXTREME_VEC), self._ar_sum, self._ar_max, stream=self._side.cuda_stream,
+                                    key_filter=f)
+
+    def _extremes_groups(self, f, q, cols):
+        import torch
+        from .distributed import sharded_group_extremes
+        self._eng()
+        with torch.cuda.stream(self._side):
+            bins = self._buffer(4 * 1024)
+            return sharded_group_extremes(self._engine, q, cols, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)

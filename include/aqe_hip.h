@@ -871,6 +871,65 @@ AQE_API int aqe_plan_last_kernel(const aqe_plan* plan, int* kernel);
  * its upper bound */
 AQE_API int aqe_plan_launch_samples(const aqe_plan* plan, uint64_t* samples, uint32_t cap, uint32_t* n_out);
 
+/* ---- extremes: approximate MIN / MAX from ONE sweep (extremes.hip) -------------------------------------------------------
+ * X = the sampled amounts: rows of q's sampler inside its row window that pass the inclusive amount WHERE range and the
+ * key filter (`filter`, NULL: none — in every entry), NaN rows left out.  n = |X|; visited = sampled rows before WHERE,
+ * filter and NaN.  min / max are the same doubles as numpy.min(X) / numpy.max(X): +-inf are values, -0.0 == +0.0.
+ *
+ * tail_fraction.  A sample's MAX only bounds the population's MAX from below, so there is no two-sided interval.  What holds
+ * without assuming a distribution: with confidence c = q->confidence_level (used as is; outside (0, 1) the entries return
+ * AQE_ERR_INVALID), at most eps = 1 - (1 - c)^(1/n) of the qualifying rows lie above the reported MAX, and the same
+ * below the reported MIN; computed in double as -expm1(log1p(-c) / n).  eps means what it says for a SIMPLE RANDOM
+ * sample (the seeded AQE_M_RANDOM_POINTER); for the systematic samplers it is reported by the same formula, as the
+ * quantile interval is.  0 for AQE_M_EXACT, NaN when n == 0.
+ *
+ * Samplers: those of the VARIANCE / STDDEV entries — single-round family samplers, row windows, and the seeded
+ * AQE_M_RANDOM_POINTER for the ungrouped form only.  CLT, adaptive, stratified, random_device and pair-family samplers:
+ * AQE_ERR_UNSUPPORTED naming the sampler; the grouped form under the seeded random sampler: AQE_ERR_UNSUPPORTED.  Key
+ * columns are needed only when a filter or GROUP BY names them.  Ungrouped entries: visited == 0 is AQE_ERR_INVALID "No
+ * samples collected"; n == 0 with visited > 0 is AQE_OK with NaN values (the rule of the filtered family).  Grouped entries
+ * list the keys somebody sampled: when no row was sampled they return AQE_OK with *n_groups == 0 (as the other grouped
+ * entries do), and a listed group nothing of which passes has n == 0 and NaN values.  Min and max do not depend on the
+ * order of the rows: the answer is bit-identical from run to run. */
+typedef struct aqe_extreme_result {
+    double min, max;          /* NaN when n == 0 */
+    double tail_fraction;     /* see above; 0 for AQE_M_EXACT, NaN when n == 0 */
+    uint64_t n, visited;
+    int32_t device_status, pad;
+    double kernel_ms;
+} aqe_extreme_result;
+typedef struct aqe_extreme_group_result {
+    int64_t key;              /* pair form: packed as AQE_GROUP_KEY_* */
+    double min, max, tail_fraction;
+    uint64_t n, visited;
+} aqe_extreme_group_result;
+/* Single GPU, synchronous: one launch; the last workgroup to arrive finishes into pinned memory. */
+AQE_API int aqe_reduce_extremes(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, aqe_extreme_result* out);
+/* GROUP BY one column (columns[1] == 0) or the ordered pair; key ranges and the 1024-bin limit are those of
+ * aqe_reduce_grouped_pair.  Groups ascend by key; only keys with visited > 0 are listed; a listed group with n == 0 has NaN
+ * min / max. */
+AQE_API int aqe_reduce_grouped_extremes(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const int* columns,
+                                        aqe_extreme_group_result* out, uint32_t cap, uint32_t* n_groups);
+/* Multi-GPU, ungrouped.  dev_vec: AQE_EXTREME_VEC doubles — {n, visited} for a SUM all-reduce, then {-min, max} for a MAX
+ * all-reduce (the two-part layout of aqe_quantile_enqueue_pass; neutral: -inf):
+ *     aqe_extremes_enqueue(ctx, filter, q, dev_vec, stream)
+ *     all-reduce SUM of dev_vec[0..2), all-reduce MAX of dev_vec[2..4)
+ *     aqe_extremes_finish(ctx, q, dev_vec, stream, &out) */
+#define AQE_EXTREME_VEC 4
+AQE_API int aqe_extremes_enqueue(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, double* dev_vec, void* stream);
+AQE_API int aqe_extremes_finish(aqe_ctx* ctx, const aqe_query* q, const double* dev_vec, void* stream, aqe_extreme_result* out);
+/* Multi-GPU, grouped: the agreed key range as aqe_grouped_pair_enqueue_bins takes it (one column: columns[1] == 0,
+ * span[1] == 1).  dev_bins: 4 * nbins doubles, nbins = span[0] * span[1] — [nbins x {n, visited}] for the SUM all-reduce,
+ * then [nbins x {-min, max}] for the MAX all-reduce.  A sampled row whose key is outside the agreed range is not binned. */
+AQE_API int aqe_grouped_extremes_enqueue_bins(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const int* columns,
+                                              const int32_t* key_min, const uint32_t* span, double* dev_bins, void* stream);
+AQE_API int aqe_grouped_extremes_finish(aqe_ctx* ctx, const aqe_query* q, const int* columns, const int32_t* key_min, const uint32_t* span,
+                                        const double* dev_bins, void* stream, aqe_extreme_group_result* out, uint32_t cap,
+                                        uint32_t* n_groups);
+/* Host only, no GPU: the result from an (all-reduced) vector.  exact != 0: tail_fraction 0.  AQE_ERR_INVALID when
+ * visited == 0 or confidence_level is outside (0, 1). */
+AQE_API int aqe_extremes_from_vec(const double* vec, double confidence_level, int exact, aqe_extreme_result* out);
+
 #ifdef __cplusplus
 }
 #endif
