@@ -57,6 +57,8 @@ QUANTILE_VEC_SUM, QUANTILE_VEC_MAX = 8194, 64
 SPREAD_VAR_SAMP, SPREAD_VAR_POP, SPREAD_STDDEV_SAMP, SPREAD_STDDEV_POP = 0, 1, 2, 3
 SPREAD_VEC, SPREAD_BIN = 8, 6
 EXTREME_VEC = 4  # {n, visited} for a SUM all-reduce, then {-min, max} for a MAX all-reduce
+HISTOGRAM_MAX_BINS = 4096
+HISTOGRAM_VEC_HEAD = 4  # [visited, n, below, above], then count[0 .. bins): one SUM all-reduce
 KEYTERM_NONE, KEYTERM_RANGE, KEYTERM_BITMAP = 0, 1, 2
 KEY_BITMAP_BITS = 1024
 
@@ -140,6 +142,30 @@ class ExtremeResult(C.Structure):
 class ExtremeGroupResult(C.Structure):
     _fields_ = [("key", C.c_int64), ("min", C.c_double), ("max", C.c_double), ("tail_fraction", C.c_double), ("n", C.c_uint64),
                 ("visited", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class HistogramSpec(C.Structure):
+    """aqe_histogram_spec: the bucket count and, with has_range, the range counted over."""
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("bins", C.c_uint32), ("has_range", C.c_uint32)]
+
+
+class HistogramHeader(C.Structure):
+    """aqe_histogram_header: what a histogram carries beside its buckets."""
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("visited", C.c_uint64), ("n", C.c_uint64), ("below", C.c_uint64), ("above", C.c_uint64),
+                ("bins", C.c_uint32), ("device_status", C.c_int32), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class HistogramBin(C.Structure):
+    """aqe_histogram_bin: one bucket [lo, hi) with its count, shares and Wilson intervals."""
+    _fields_ = [("lo", C.c_double), ("hi", C.c_double), ("count", C.c_uint64), ("fraction", C.c_double), ("fraction_ci_lower", C.c_double),
+                ("fraction_ci_upper", C.c_double), ("cumulative", C.c_double), ("estimate", C.c_double), ("estimate_ci_lower", C.c_double),
+                ("estimate_ci_upper", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -293,6 +319,13 @@ def lib() -> C.CDLL:
         "aqe_grouped_extremes_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), P(i32), P(u32), vp, vp]),
         "aqe_grouped_extremes_finish": (C.c_int, [vp, P(Query), P(C.c_int), P(i32), P(u32), vp, vp, P(ExtremeGroupResult), u32, P(u32)]),
         "aqe_extremes_from_vec": (C.c_int, [P(dbl), dbl, C.c_int, P(ExtremeResult)]),
+        "aqe_reduce_histogram": (C.c_int, [vp, P(KeyFilter), P(Query), P(HistogramSpec), P(HistogramHeader), P(HistogramBin), u32]),
+        "aqe_histogram_enqueue": (C.c_int, [vp, P(KeyFilter), P(Query), P(HistogramSpec), vp, vp]),
+        "aqe_histogram_finish": (C.c_int, [vp, P(Query), P(HistogramSpec), vp, vp, P(HistogramHeader), P(HistogramBin), u32]),
+        "aqe_histogram_edges": (C.c_int, [dbl, dbl, u32, P(dbl)]),
+        "aqe_histogram_bucket": (C.c_int, [dbl, dbl, u32, dbl]),
+        "aqe_histogram_buckets": (C.c_int, [dbl, dbl, u32, P(dbl), u64, P(i32)]),
+        "aqe_histogram_from_vec": (C.c_int, [P(dbl), u32, P(HistogramSpec), u64, dbl, C.c_int, P(HistogramHeader), P(HistogramBin), u32]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),

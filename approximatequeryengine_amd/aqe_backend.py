@@ -30,7 +30,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as nat
-from .engine import RECORD_DTYPE, Engine, key_filter_terms, make_key_filter, make_query
+from .engine import RECORD_DTYPE, Engine, histogram_spec, key_filter_terms, make_key_filter, make_query
 
 __all__ = ["Record", "CustomBPlusDB", "CustomApproximateScheduler", "CustomValidationResult",
            "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate", "SpreadEstimate"]
@@ -204,6 +204,51 @@ def _named_extreme(res, which):
     for e in (res.values() if isinstance(res, dict) else (res,)):
         e.value = getattr(e, which)
     return res
+
+
+class HistogramEstimate:
+    """Result of approx_histogram: ``bins`` equal-width buckets over [lo, hi].  numpy arrays, one entry per bucket: ``edges``
+    (bins + 1: numpy.linspace(lo, hi, bins + 1)), ``counts`` (numpy.histogram of the sampled amounts that pass, the same
+    integers), ``fraction`` (count / n), ``cumulative``, ``estimate`` (count x N / visited: rows of the table in the bucket) and
+    the Wilson score intervals ``fraction_ci_lower`` / ``fraction_ci_upper`` / ``estimate_ci_lower`` / ``estimate_ci_upper``
+    (include/aqe_hip.h, aqe_histogram_bin).  ``below`` / ``above`` count the passing amounts outside the range, ``n`` all passing
+    amounts, ``visited`` the sampled rows."""
+    __slots__ = ("edges", "counts", "fraction", "cumulative", "estimate", "fraction_ci_lower", "fraction_ci_upper", "estimate_ci_lower",
+                 "estimate_ci_upper", "below", "above", "n", "visited", "lo", "hi", "bins", "kernel_ms", "method")
+
+    def __init__(self, head, buckets, method: str):
+        b = np.frombuffer(buckets, dtype=_HISTOGRAM_BIN_DTYPE, count=head.bins)
+        self.edges = np.append(b["lo"], b["hi"][-1:])
+        self.counts = b["count"].astype(np.int64)
+        for k in ("fraction", "cumulative", "estimate", "fraction_ci_lower", "fraction_ci_upper", "estimate_ci_lower", "estimate_ci_upper"):
+            setattr(self, k, b[k].copy())
+        for k in ("below", "above", "n", "visited", "lo", "hi", "bins", "kernel_ms"):
+            setattr(self, k, getattr(head, k))
+        self.method = method
+
+    def __repr__(self):
+        return f"HistogramEstimate(bins={self.bins}, range=({self.lo!r}, {self.hi!r}), n={self.n}, below={self.below}, above={self.above}, method={self.method!r})"
+
+
+_HISTOGRAM_BIN_DTYPE = np.dtype([(name, "<u8" if name == "count" else "<f8") for name, _ in nat.HistogramBin._fields_])
+
+
+def histogram_spec_for(bins, range) -> "nat.HistogramSpec":
+    """The checked aqe_histogram_spec of approx_histogram's ``bins`` / ``range`` arguments: ValueError naming what is wrong with
+    them (a bucket count outside 1 .. 4096, a range that is not two finite numbers with lo < hi)."""
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= int(bins) <= nat.HISTOGRAM_MAX_BINS:
+        raise ValueError(f"HISTOGRAM: bins={bins!r} — the number of buckets is an integer in 1 .. {nat.HISTOGRAM_MAX_BINS}")
+    if range is None:
+        return histogram_spec(int(bins))
+    try:
+        lo, hi = (float(v) for v in range)
+    except (TypeError, ValueError):
+        raise ValueError(f"HISTOGRAM: range={range!r} — a range is (lo, hi)") from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and np.isfinite(hi - lo)):
+        raise ValueError(f"HISTOGRAM: range={range!r} — the range must be finite")
+    if not lo < hi:
+        raise ValueError(f"HISTOGRAM: range={range!r} — the range is empty (lo >= hi)")
+    return histogram_spec(int(bins), (lo, hi))
 
 
 _SPREAD_KINDS = {"var_samp": nat.SPREAD_VAR_SAMP, "variance": nat.SPREAD_VAR_SAMP, "var_pop": nat.SPREAD_VAR_POP,
@@ -900,6 +945,32 @@ class CustomBPlusDB:
     def approx_max(self, **kw):
         """APPROX MAX(amount): approx_extremes(**kw) with ``value`` set to the maximum."""
         return _named_extreme(self.approx_extremes(**kw), "max")
+
+    def approx_histogram(self, bins: int = 20, range: Optional[Tuple[float, float]] = None, method: str = "stride", sample_percent: float = 10.0,
+                         where: Optional[Tuple[float, float]] = None, id_between: Optional[Tuple[int, int]] = None, key_where: Optional[dict] = None,
+                         confidence_level: float = 0.95, seed: int = 42, num_threads: int = 4, block_size: int = 1000) -> HistogramEstimate:
+        """APPROX HISTOGRAM(amount, bins): numpy.histogram(X, bins=bins, range=range) of the sampled amounts X (WHERE, the key
+        window and ``key_where`` applied, NaN rows left out) from ONE counting sweep, as a HistogramEstimate — per bucket the
+        count, its share of the sample, the estimated number of table rows and Wilson score intervals at ``confidence_level``.
+        ``range`` None: the table's own amount range, clipped to ``where`` (a constant column has none: ValueError asking for a
+        range).  method as approx_extremes ("exact", "stride", "block", "page", "parallel_block", "region", "random" ...; CLT,
+        adaptive, stratified and random_device samplers raise ValueError).  There is no GROUP BY and no error-threshold form."""
+        if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
+            raise ValueError(f"HISTOGRAM does not take the {method} sampler (single-round family samplers and 'random' only)")
+        spec = histogram_spec_for(bins, range)
+        f = None if key_where is None else _key_filter_for(key_where, method)
+        q = self._approx_query("SUM", method, sample_percent, None, where, seed, num_threads, block_size, confidence_level, id_between=id_between)
+        q.confidence_level = float(confidence_level)
+        try:
+            head, buckets = _quantile_call(lambda: self._histogram(f, q, spec))
+        except nat.AqeError as e:
+            if e.status == nat.ERR_INVALID and "give a range" in str(e):
+                raise ValueError(str(e)) from None
+            raise
+        return HistogramEstimate(head, buckets, method)
+
+    def _histogram(self, f, q, spec):
+        return self._eng().reduce_histogram(q, spec, f)
 
     def approx_sum(self, **kw) -> ApproxResult:
         return self.approx("SUM", **kw)

@@ -11,6 +11,8 @@
     python -m approximatequeryengine_amd.cli "SELECT region, product_id, AVG(amount) FROM sales GROUP BY region, product_id" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli "SELECT MIN(amount), MAX(amount) FROM sales" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli "SELECT region, MAX(amount) FROM sales WHERE product_id < 50 GROUP BY region" --db sales.db --s 10
+    python -m approximatequeryengine_amd.cli "SELECT HISTOGRAM(amount, 20) FROM sales WHERE region = 2" --db sales.db --s 10 --ci
+    python -m approximatequeryengine_amd.cli "SELECT HISTOGRAM(amount, 10, 0, 1000) FROM sales" --db sales.db --s 10 --compare
     python -m approximatequeryengine_amd.cli --explain
 
 The reference's own CLI defines `-s/--sample` and `-e/--error` but tests `args.s` / `args.e`
@@ -115,6 +117,38 @@ def extreme_of(query: str) -> Optional[Tuple[str, ...]]:
     return tuple(names) or None
 
 
+def histogram_of(query: str) -> Optional[Tuple[int, Optional[Tuple[float, float]]]]:
+    """HISTOGRAM(amount, B) -> (B, None); HISTOGRAM(amount, B, lo, hi) -> (B, (lo, hi)); None for any other query — and for
+    every query that also names SUM(, AVG(, COUNT(, a quantile, spread or extreme function, whose routing stays as it was.
+    ValueError, quoting the offending text, for a B that is not an integer in 1 .. 4096, a range that is not two finite numbers
+    with lo < hi, or another number of arguments."""
+    up = query.upper()
+    if any(a + "(" in up for a in ("SUM", "AVG", "COUNT")):
+        return None
+    if re.search(r"\b(MEDIAN|PERCENTILE(_CONT|_DISC)?|VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?|MIN|MAX)\s*\(", query, re.IGNORECASE):
+        return None
+    m = re.search(r"\bHISTOGRAM\s*\(\s*amount\s*(?:,([^)]*))?\)", query, re.IGNORECASE)
+    if not m:
+        return None
+    shown = " ".join(m.group(0).split())
+    parts = [a.strip() for a in (m.group(1) or "").split(",")] if m.group(1) is not None else []
+    if len(parts) not in (1, 3):
+        raise ValueError(f"'{shown}': HISTOGRAM takes (amount, B) or (amount, B, lo, hi)")
+    if not re.fullmatch(r"\+?\d+", parts[0]) or not 1 <= int(parts[0]) <= 4096:
+        raise ValueError(f"'{shown}': the number of buckets {parts[0]!r} is not an integer in 1 .. 4096")
+    if len(parts) == 1:
+        return int(parts[0]), None
+    try:
+        lo, hi = float(parts[1]), float(parts[2])
+    except ValueError:
+        raise ValueError(f"'{shown}': the range '{parts[1]}, {parts[2]}' is not two numbers") from None
+    if not (abs(lo) < float("inf") and abs(hi) < float("inf") and hi - lo < float("inf")):
+        raise ValueError(f"'{shown}': the range '{parts[1]}, {parts[2]}' is not finite")
+    if not lo < hi:
+        raise ValueError(f"'{shown}': the range '{parts[1]}, {parts[2]}' is empty (lo must be below hi)")
+    return int(parts[0]), (lo, hi)
+
+
 def where_clause_of(query: str) -> Optional[str]:
     """The text of the query's WHERE clause (up to GROUP BY / ORDER BY / LIMIT), or None."""
     m = re.search(r"\bWHERE\b(.*?)(?=\bGROUP\s+BY\b|\bORDER\s+BY\b|\bLIMIT\b|\bHAVING\b|;|$)", query, re.IGNORECASE | re.DOTALL)
@@ -187,7 +221,8 @@ def get_optimal_method_for_query(query: str, dataset_size: Optional[int] = None)
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV, MIN/MAX on MI355X",
+    p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV, MIN/MAX, HISTOGRAM on MI355X "
+                                "(e.g. \"SELECT HISTOGRAM(amount, 20) FROM sales\" --s 10 --ci)",
                                 allow_abbrev=False)
     p.add_argument("query", nargs="?", help="SQL query, e.g. \"SELECT SUM(amount) FROM sales\"")
     p.add_argument("--db", default="custom_demo.db", help="database file (reference format)")
@@ -234,6 +269,18 @@ def run(args, out=sys.stdout) -> int:
     if extreme_of(clean) is not None and args.e is not None:
         print("error: MIN / MAX have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
         return 2
+    try:
+        hist = histogram_of(clean)
+    except ValueError as e:
+        print(f"error: {e}", file=out)
+        return 2
+    if hist is not None:
+        if args.e is not None:
+            print("error: HISTOGRAM has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
+            return 2
+        if re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
+            print("error: GROUP BY is not supported with HISTOGRAM", file=out)
+            return 2
     try:
         group_by_of(clean)
     except ValueError as e:
@@ -314,6 +361,9 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     extreme = extreme_of(clean)
     if extreme is not None:
         return _run_extremes(db, args, out, clean, qtype, extreme, aqe_backend, t0, kw)
+    hist = histogram_of(clean)
+    if hist is not None:
+        return _run_histogram(db, args, out, clean, qtype, hist, aqe_backend, t0, kw)
     gb = group_by_of(clean)
     if gb and group_error_form(clean, args):
         # --e with GROUP BY: nested block levels until every group's interval is within the threshold (aqe_reduce_grouped_error)
@@ -505,6 +555,44 @@ def _run_extremes(db, args, out, clean, qtype, names, aqe_backend, t0, kw=None) 
             print(f"\ncomparison ({fn}):\n   approximate: {fmt(a)}\n   exact:       {fmt(x)}", file=out)
             if x == x and a == a and x != 0 and abs(x) != float("inf"):
                 print(f"   actual error: {abs(a - x) / abs(x) * 100:.4f}%", file=out)
+    db.close_database()
+    return 0
+
+
+def _run_histogram(db, args, out, clean, qtype, hist, aqe_backend, t0, kw=None) -> int:
+    """HISTOGRAM(amount, B [, lo, hi]): exact without --s; with --s (or an APPROX(...) wrapper) a sample — --method block /
+    parallel / random honoured, stride otherwise.  One line per bucket: [e_i, e_{i+1})  estimate  (interval with --ci)  count."""
+    kw = kw or {}  # {"key_where": ...} when the WHERE clause names region / product_id
+    bins, rng = hist
+    where = aqe_backend.parse_where(clean)
+    if args.s is None and qtype != QUERY_EMBEDDED:
+        method, pct, name = "exact", 100.0, "exact"
+    else:
+        pct = args.s if args.s is not None else 10.0
+        method = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", "stride")
+        name = f"{method} sampling ({pct}%)"
+    try:
+        res = db.approx_histogram(bins=bins, range=rng, method=method, sample_percent=pct, where=where, confidence_level=args.confidence,
+                                  seed=args.seed, num_threads=args.threads, **kw)
+    except ValueError as e:  # (a constant column without a range)
+        print(f"error: {e}", file=out)
+        db.close_database()
+        return 2
+    ms = (time.perf_counter() - t0) * 1e3
+    exact = None
+    if args.compare and method != "exact":
+        exact = db.approx_histogram(bins=bins, range=(res.lo, res.hi), method="exact", where=where, **kw)
+    print(f"\n{name} HISTOGRAM(amount, {bins}) over [{res.lo:,.4f}, {res.hi:,.4f}] result:", file=out)
+    for i in range(res.bins):
+        ci = f"   ({res.estimate_ci_lower[i]:,.1f} - {res.estimate_ci_upper[i]:,.1f})" if (args.ci and method != "exact") else ""
+        cmp_ = f"   exact {int(exact.counts[i]):,}" if exact is not None else ""
+        close = "]" if i == res.bins - 1 else ")"
+        print(f"   [{res.edges[i]:,.4f}, {res.edges[i + 1]:,.4f}{close}   {res.estimate[i]:,.1f}{ci}   count={int(res.counts[i]):,}{cmp_}", file=out)
+    print(f"   below: {res.below:,}   above: {res.above:,}", file=out)
+    if exact is not None:
+        print(f"   exact below: {exact.below:,}   exact above: {exact.above:,}", file=out)
+    print(f"   samples used: {res.n:,}", file=out)
+    print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
     db.close_database()
     return 0
 

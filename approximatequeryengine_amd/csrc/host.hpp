@@ -93,6 +93,7 @@ struct StageRing {
 
 struct aqe_moment_scratch;  // moments.hip
 struct aqe_extreme_scratch;  // extremes.hip
+struct aqe_histogram_scratch;  // histogram.hip
 
 struct aqe_ctx {
     StageRing ring;
@@ -158,6 +159,8 @@ struct aqe_ctx {
     aqe_moment_scratch* moments = nullptr;
     // MIN / MAX (extremes.hip): partials, tickets, bins and pinned results of the extremes sweep, made on first use
     aqe_extreme_scratch* extremes = nullptr;
+    // HISTOGRAM (histogram.hip): accumulator, tickets and the pinned vector of the counting sweep, made on first use
+    aqe_histogram_scratch* histogram = nullptr;
 };
 
 // One persistent-sweep form of a plan's rounds (persist.hip): the tile list of all slots, who owns tiles
@@ -329,6 +332,9 @@ int level_columns_ok(aqe_ctx* c, const int* cols);
 
 // extremes.hip
 void extremes_release(aqe_ctx* c);
+
+// histogram.hip
+void histogram_release(aqe_ctx* c);
 
 // plans.hip
 void destroy_plan(aqe_plan* p, bool device_idle = false);  // device_idle: the caller has just synchronised the device

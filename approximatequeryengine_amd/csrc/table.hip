@@ -570,6 +570,7 @@ void aqe_destroy(aqe_ctx* c) {
     quantile_release(c);
     moments_release(c);
     extremes_release(c);
+    histogram_release(c);
     free_table(c);
     free_ring(c);
     if (c->d_stamps) (void)hipFree(c->d_stamps);

@@ -448,6 +448,40 @@ def sharded_extremes(engine, query, vec, all_reduce_sum: Callable, all_reduce_ma
         return engine.extremes_finish(query, v.data_ptr(), stream)
 
 
+def sharded_histogram(engine, query, spec, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
+    """HISTOGRAM(amount, B) across the ranks of a process group (engine.Engine interface), collective.  When ``spec`` carries no
+    range the ranks agree on the table's amount range first — ONE all-reduce MAX of [-min, max] (engine.quantile_amount_range),
+    clipped to the query's amount WHERE bounds — and never otherwise.  Then every rank counts the part of the sample inside
+    its shard into HISTOGRAM_VEC_HEAD + B doubles (aqe_histogram_enqueue), ONE all-reduce SUM merges the whole numbers, and
+    every rank finishes the same vector: the same (header, buckets) on every rank.
+
+    vec     float64 tensor on the engine's device with room for HISTOGRAM_VEC_HEAD + spec.bins doubles
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    from ._native import ERR_INVALID, HISTOGRAM_MAX_BINS, HISTOGRAM_VEC_HEAD, AqeError, HistogramSpec
+    stream = _stream_for(stream, vec)
+    bins = int(spec.bins)
+    if not 1 <= bins <= HISTOGRAM_MAX_BINS:
+        raise AqeError(ERR_INVALID, "HISTOGRAM: the number of buckets must lie in 1 .. 4096")
+    need = HISTOGRAM_VEC_HEAD + bins
+    if vec.numel() < need:
+        raise ValueError(f"vector holds {vec.numel()} doubles, {need} needed")
+    with _torch_on(stream, vec):
+        if not spec.has_range:
+            lo, hi = engine.quantile_amount_range()
+            rng = vec.new_tensor([-float(lo), float(hi)])
+            all_reduce_max(rng)
+            lo, hi = -float(rng[0].item()), float(rng[1].item())
+            if query.has_where:
+                lo, hi = max(lo, float(query.where_min)), min(hi, float(query.where_max))
+            if not (lo < hi and hi - lo < float("inf") and lo > float("-inf")):
+                raise AqeError(ERR_INVALID, "HISTOGRAM: the table's amounts leave no finite range with lo < hi (a constant or empty column): give a range")
+            spec = HistogramSpec(lo, hi, bins, 1)
+        v = vec[:need]
+        engine.histogram_enqueue(query, spec, v.data_ptr(), stream, key_filter)
+        all_reduce_sum(v)
+        return engine.histogram_finish(query, spec, v.data_ptr(), stream)
+
+
 def sharded_group_extremes(engine, query, columns, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
     """GROUP BY MIN / MAX across ranks, collective: ``columns`` is one column or the ordered pair (A, B).  The key ranges are
     agreed in ONE MAX all-reduce (as sharded_group_by_pair); every rank bins its part of the sample into

@@ -653,6 +653,24 @@ class Engine:
                                                         C.byref(n)))
         return list(out[: n.value])
 
+    # -- HISTOGRAM (aqe_reduce_histogram and its kin): one counting sweep; key_filter may be None everywhere --
+    def reduce_histogram(self, query: Query, spec: "nat.HistogramSpec", key_filter: "Optional[nat.KeyFilter]" = None):
+        """(HistogramHeader, HistogramBin array of spec.bins entries) of the sampled rows that pass."""
+        head, bins = nat.HistogramHeader(), (nat.HistogramBin * max(int(spec.bins), 1))()
+        self._chk(nat.lib().aqe_reduce_histogram(self._h, _filter_ref(key_filter), C.byref(query), C.byref(spec), C.byref(head), bins, len(bins)))
+        return head, bins
+
+    def histogram_enqueue(self, query: Query, spec: "nat.HistogramSpec", dev_vec_ptr: int, stream: int = 0, key_filter: "Optional[nat.KeyFilter]" = None):
+        """This shard's HISTOGRAM_VEC_HEAD + spec.bins doubles into device memory: all-reduce SUM, then histogram_finish.  The
+        spec carries the agreed range (has_range)."""
+        self._chk(nat.lib().aqe_histogram_enqueue(self._h, _filter_ref(key_filter), C.byref(query), C.byref(spec), C.c_void_p(dev_vec_ptr), C.c_void_p(stream)))
+
+    def histogram_finish(self, query: Query, spec: "nat.HistogramSpec", dev_vec_ptr: int, stream: int = 0):
+        head, bins = nat.HistogramHeader(), (nat.HistogramBin * max(int(spec.bins), 1))()
+        self._chk(nat.lib().aqe_histogram_finish(self._h, C.byref(query), C.byref(spec), C.c_void_p(dev_vec_ptr), C.c_void_p(stream), C.byref(head), bins,
+                                                 len(bins)))
+        return head, bins
+
     def gather(self, query: Query) -> np.ndarray:
         """Rows of the record-returning sampler, as a RECORD_DTYPE array."""
         n = C.c_uint64()
@@ -721,6 +739,55 @@ def extremes_from_vec(vec: Sequence[float], confidence_level: float = 0.95, exac
     if rc != nat.OK:
         raise nat.AqeError(rc, "confidence_level must lie inside (0, 1)" if not 0.0 < confidence_level < 1.0 else "No samples collected")
     return out
+
+
+def histogram_spec(bins: int, range=None) -> "nat.HistogramSpec":
+    """aqe_histogram_spec of ``bins`` buckets over ``range`` = (lo, hi), or over the table's own amount range (None)."""
+    if range is None:
+        return nat.HistogramSpec(0.0, 0.0, int(bins), 0)
+    return nat.HistogramSpec(float(range[0]), float(range[1]), int(bins), 1)
+
+
+def histogram_edges(lo: float, hi: float, bins: int) -> np.ndarray:
+    """aqe_histogram_edges: the bins + 1 bucket edges, numpy.linspace(lo, hi, bins + 1) to the bit — no GPU."""
+    out = np.empty(int(bins) + 1 if 0 < int(bins) <= nat.HISTOGRAM_MAX_BINS else 1, dtype=np.float64)
+    rc = nat.lib().aqe_histogram_edges(float(lo), float(hi), max(int(bins), 0), out.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "HISTOGRAM: 1 .. 4096 buckets over a finite range with lo < hi")
+    return out
+
+
+def histogram_bucket(lo: float, hi: float, bins: int, x):
+    """aqe_histogram_bucket(s): the bucket the sweep counts ``x`` into — -1 below lo, bins above hi, -2 for NaN — no GPU.  A
+    scalar gives an int, an array an int32 array."""
+    if np.ndim(x) == 0:
+        b = nat.lib().aqe_histogram_bucket(float(lo), float(hi), max(int(bins), 0), float(x))
+        if b == -3:
+            raise nat.AqeError(nat.ERR_INVALID, "HISTOGRAM: 1 .. 4096 buckets over a finite range with lo < hi")
+        return b
+    xs = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    out = np.empty(len(xs), dtype=np.int32)
+    rc = nat.lib().aqe_histogram_buckets(float(lo), float(hi), max(int(bins), 0), xs.ctypes.data_as(C.POINTER(C.c_double)), len(xs),
+                                         out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "HISTOGRAM: 1 .. 4096 buckets over a finite range with lo < hi")
+    return out
+
+
+def histogram_from_vec(vec: Sequence[float], bins: int, spec: "nat.HistogramSpec", n_global: int, confidence_level: float = 0.95, exact: bool = False):
+    """aqe_histogram_from_vec: (HistogramHeader, HistogramBin array) from the HISTOGRAM_VEC_HEAD + bins (all-reduced) doubles
+    [visited, n, below, above, count...], on the host — no GPU.  Raises AqeError (ERR_INVALID) when visited == 0 ("No samples
+    collected") or the spec is not a range of ``bins`` buckets."""
+    v = np.ascontiguousarray(vec, dtype=np.float64)
+    if len(v) != nat.HISTOGRAM_VEC_HEAD + int(bins):
+        raise ValueError(f"{nat.HISTOGRAM_VEC_HEAD} + {int(bins)} doubles expected: visited, n, below, above, then the counts")
+    head, out = nat.HistogramHeader(), (nat.HistogramBin * max(int(bins), 1))()
+    rc = nat.lib().aqe_histogram_from_vec(v.ctypes.data_as(C.POINTER(C.c_double)), int(bins), C.byref(spec), int(n_global), float(confidence_level),
+                                          int(bool(exact)), C.byref(head), out, len(out))
+    if rc != nat.OK:
+        bad = int(spec.bins) != int(bins) or not spec.has_range
+        raise nat.AqeError(rc, "the spec must carry a finite range lo < hi of as many buckets as the vector" if bad or v[0] > 0 else "No samples collected")
+    return head, out
 
 
 _KEY_COLUMNS = ("region", "product_id")

@@ -352,3 +352,13 @@ class ShardedBPlusDB(CustomBPlusDB):
         with torch.cuda.stream(self._side):
             bins = self._buffer(4 * 1024)
             return sharded_group_extremes(self._engine, q, cols, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)
+
+    # ---- HISTOGRAM: one all-reduce MAX for the range when the caller gives none, one all-reduce SUM of the counts;
+    # approx_histogram is CustomBPlusDB's own, over this ----
+    def _histogram(self, f, q, spec):
+        import torch
+        from .distributed import sharded_histogram
+        self._eng()
+        with torch.cuda.stream(self._side):
+            vec = self._buffer(nat.HISTOGRAM_VEC_HEAD + nat.HISTOGRAM_MAX_BINS)
+            return sharded_histogram(self._engine, q, spec, vec, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)

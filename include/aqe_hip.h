@@ -930,6 +930,79 @@ AQE_API int aqe_grouped_extremes_finish(aqe_ctx* ctx, const aqe_query* q, const 
  * visited == 0 or confidence_level is outside (0, 1). */
 AQE_API int aqe_extremes_from_vec(const double* vec, double confidence_level, int exact, aqe_extreme_result* out);
 
+/* ---- histogram: approximate HISTOGRAM(amount, B) from ONE counting sweep (histogram.hip) ----------------------------------
+ * X = the sampled amounts: rows of q's sampler inside its row window that pass the inclusive amount WHERE range and the
+ * key filter (`filter`, NULL: none — in every entry), NaN rows left out: the set aqe_reduce_extremes sees.  n = |X|;
+ * visited = sampled rows before WHERE, filter and NaN.
+ *
+ * Edges.  With B = spec->bins buckets (1 .. AQE_HISTOGRAM_MAX_BINS) over a finite range lo < hi (hi - lo finite too):
+ * e = numpy.linspace(lo, hi, B + 1), the same doubles — e_i = i * ((hi - lo) / B) + lo with the multiply and the add
+ * rounded separately (never fused), e_B = hi.
+ * Counts.  count[i] = numpy.histogram(X, bins=B, range=(lo, hi))[0][i], the same integers: bucket i holds
+ * e_i <= x < e_{i+1}, the last bucket also x == hi.  below = |{x < lo}| (-inf included), above = |{x > hi}| (+inf
+ * included); below + sum(count) + above == n.  A value's bucket is the scaled guess (x - lo) / (hi - lo) * B truncated,
+ * moved at most one step down or up against the edges: the edges decide (aqe_histogram_bucket is that function).
+ * Range.  spec->has_range == 0: the table's non-NaN amount range (aqe_quantile_amount_range) clipped to the amount WHERE
+ * bounds when q has some; when that leaves lo >= hi (a constant column, an empty table) the call returns AQE_ERR_INVALID
+ * asking for a range.  Over shards the ranks agree on the range first and every rank passes it (has_range = 1).
+ *
+ * Per bucket, z from q->confidence_level as the quantile path picks it (>= 0.99: 2.576, >= 0.95: 1.96, else 1.645):
+ *   fraction = count / n, cumulative = (below + count[0] + ... + count[i]) / n, estimate = count * N / visited (N: the global
+ *   row count); intervals are WILSON SCORE intervals — for k of m: centre (p + z^2 / 2m) / (1 + z^2 / m), half-width
+ *   z sqrt(p (1 - p) / m + z^2 / 4m^2) / (1 + z^2 / m), p = k / m — which keep their width at count 0, the bucket a sample
+ *   misses: fraction_ci_* takes k = count, m = n; estimate_ci_* is N times the interval of k = count, m = visited.  The lower
+ *   end at k == 0 is 0 and the upper end at k == m is 1 (fraction) or N (estimate), exactly.  AQE_M_EXACT: estimate =
+ *   count and zero-width intervals.
+ * Status: visited == 0 is AQE_ERR_INVALID "No samples collected"; n == 0 with visited > 0 is AQE_OK with all counts 0 and
+ * NaN fraction / cumulative / fraction_ci_*.  Samplers: those of aqe_reduce_extremes' ungrouped form; CLT, adaptive,
+ * stratified, random_device and pair-family samplers: AQE_ERR_UNSUPPORTED naming the sampler, before any launch.  A bucket
+ * count outside 1 .. 4096, a range that is not finite or is empty: AQE_ERR_INVALID before any launch.  Every count is an
+ * integer merged with integer atomics: the answer is bit-identical from run to run. */
+#define AQE_HISTOGRAM_MAX_BINS 4096
+#define AQE_HISTOGRAM_VEC_HEAD 4
+typedef struct aqe_histogram_spec {
+    double lo, hi;            /* read when has_range != 0 */
+    uint32_t bins;
+    uint32_t has_range;
+} aqe_histogram_spec;
+typedef struct aqe_histogram_header {
+    double lo, hi;            /* the range counted over */
+    uint64_t visited, n, below, above;
+    uint32_t bins;
+    int32_t device_status;
+    double kernel_ms;
+} aqe_histogram_header;
+typedef struct aqe_histogram_bin {
+    double lo, hi;            /* e_i, e_{i+1} */
+    uint64_t count;
+    double fraction, fraction_ci_lower, fraction_ci_upper;
+    double cumulative;
+    double estimate, estimate_ci_lower, estimate_ci_upper;
+} aqe_histogram_bin;
+/* Single GPU, synchronous: one launch; the last workgroup to arrive writes the counts into pinned memory.  buckets_out has
+ * room for max_buckets >= spec->bins entries (AQE_ERR_CAPACITY otherwise). */
+AQE_API int aqe_reduce_histogram(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const aqe_histogram_spec* spec,
+                                 aqe_histogram_header* header_out, aqe_histogram_bin* buckets_out, uint32_t max_buckets);
+/* Multi-GPU, additive.  dev_vec: AQE_HISTOGRAM_VEC_HEAD + bins doubles — [visited, n, below, above, count[0 .. bins)],
+ * whole numbers below 2^53 — for ONE SUM all-reduce; every rank passes the same spec, with has_range != 0:
+ *     aqe_histogram_enqueue(ctx, filter, q, spec, dev_vec, stream)
+ *     all-reduce SUM of dev_vec[0 .. 4 + bins)
+ *     aqe_histogram_finish(ctx, q, spec, dev_vec, stream, &header, buckets, max_buckets) */
+AQE_API int aqe_histogram_enqueue(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const aqe_histogram_spec* spec, double* dev_vec,
+                                  void* stream);
+AQE_API int aqe_histogram_finish(aqe_ctx* ctx, const aqe_query* q, const aqe_histogram_spec* spec, const double* dev_vec, void* stream,
+                                 aqe_histogram_header* header_out, aqe_histogram_bin* buckets_out, uint32_t max_buckets);
+/* Host only, no GPU.  aqe_histogram_edges: the bins + 1 edges.  aqe_histogram_bucket: the bucket the sweep counts x into —
+ * the twin of the device function: -1 below lo, bins above hi, -2 for NaN (-3: bad range or bucket count);
+ * aqe_histogram_buckets: the same for `count` values at once.  aqe_histogram_from_vec: all the estimate and interval
+ * arithmetic from an (all-reduced) vector; spec->has_range != 0 and spec->bins == bins; n_global: N; exact != 0 as
+ * AQE_M_EXACT.  The header is filled even when visited == 0 (AQE_ERR_INVALID). */
+AQE_API int aqe_histogram_edges(double lo, double hi, uint32_t bins, double* out);
+AQE_API int aqe_histogram_bucket(double lo, double hi, uint32_t bins, double x);
+AQE_API int aqe_histogram_buckets(double lo, double hi, uint32_t bins, const double* x, uint64_t count, int32_t* out);
+AQE_API int aqe_histogram_from_vec(const double* vec, uint32_t bins, const aqe_histogram_spec* spec, uint64_t n_global, double confidence_level,
+                                   int exact, aqe_histogram_header* header_out, aqe_histogram_bin* buckets_out, uint32_t max_buckets);
+
 #ifdef __cplusplus
 }
 #endif
