@@ -59,6 +59,9 @@ SPREAD_VEC, SPREAD_BIN = 8, 6
 EXTREME_VEC = 4  # {n, visited} for a SUM all-reduce, then {-min, max} for a MAX all-reduce
 HISTOGRAM_MAX_BINS = 4096
 HISTOGRAM_VEC_HEAD = 4  # [visited, n, below, above], then count[0 .. bins): one SUM all-reduce
+DISTINCT_AMOUNT = 0  # the column of a distinct count: this, GROUP_REGION or GROUP_PRODUCT
+DISTINCT_SKETCH, DISTINCT_EXACT_KEYS = 0, 1
+DISTINCT_VEC_HEAD, DISTINCT_SLOTS = 2, 8192  # [visited, n] for a SUM all-reduce, then slot[0 .. 8192) for a MAX all-reduce
 KEYTERM_NONE, KEYTERM_RANGE, KEYTERM_BITMAP = 0, 1, 2
 KEY_BITMAP_BITS = 1024
 
@@ -169,6 +172,16 @@ class HistogramBin(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class DistinctResult(C.Structure):
+    """aqe_distinct_result: COUNT(DISTINCT column) of the sampled rows that qualify."""
+    _fields_ = [("value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double), ("n", C.c_uint64), ("visited", C.c_uint64),
+                ("column", C.c_int32), ("mode", C.c_int32), ("lower_bound", C.c_int32), ("key_min", C.c_int32), ("empty_slots", C.c_uint32),
+                ("reserved", C.c_uint32), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 class GroupErrorInfo(C.Structure):
@@ -326,6 +339,13 @@ def lib() -> C.CDLL:
         "aqe_histogram_bucket": (C.c_int, [dbl, dbl, u32, dbl]),
         "aqe_histogram_buckets": (C.c_int, [dbl, dbl, u32, P(dbl), u64, P(i32)]),
         "aqe_histogram_from_vec": (C.c_int, [P(dbl), u32, P(HistogramSpec), u64, dbl, C.c_int, P(HistogramHeader), P(HistogramBin), u32]),
+        "aqe_reduce_distinct": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, P(DistinctResult)]),
+        "aqe_distinct_enqueue": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, C.c_int, i32, vp, vp]),
+        "aqe_distinct_finish": (C.c_int, [vp, P(Query), C.c_int, C.c_int, i32, vp, vp, P(DistinctResult)]),
+        "aqe_distinct_hash": (u64, [u64]),
+        "aqe_distinct_mode": (C.c_int, [C.c_int, i32, i32, P(C.c_int), P(i32)]),
+        "aqe_distinct_slot": (C.c_int, [C.c_int, C.c_int, i32, u64, P(u32), P(u32)]),
+        "aqe_distinct_from_vec": (C.c_int, [P(dbl), C.c_int, C.c_int, i32, dbl, C.c_int, P(DistinctResult)]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),

@@ -13,6 +13,8 @@
     python -m approximatequeryengine_amd.cli "SELECT region, MAX(amount) FROM sales WHERE product_id < 50 GROUP BY region" --db sales.db --s 10
     python -m approximatequeryengine_amd.cli "SELECT HISTOGRAM(amount, 20) FROM sales WHERE region = 2" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli "SELECT HISTOGRAM(amount, 10, 0, 1000) FROM sales" --db sales.db --s 10 --compare
+    python -m approximatequeryengine_amd.cli "SELECT COUNT(DISTINCT product_id) FROM sales WHERE region = 2" --db sales.db --s 10 --ci
+    python -m approximatequeryengine_amd.cli "SELECT APPROX_COUNT_DISTINCT(amount) FROM sales" --db sales.db --compare
     python -m approximatequeryengine_amd.cli --explain
 
 The reference's own CLI defines `-s/--sample` and `-e/--error` but tests `args.s` / `args.e`
@@ -149,6 +151,31 @@ def histogram_of(query: str) -> Optional[Tuple[int, Optional[Tuple[float, float]
     return int(parts[0]), (lo, hi)
 
 
+_DISTINCT_COLUMNS = ("amount", "region", "product_id")
+
+
+def distinct_of(query: str) -> Optional[str]:
+    """COUNT(DISTINCT col) / APPROX_COUNT_DISTINCT(col), in any letter case -> col in lower case (amount, region or product_id);
+    None for any other query — and for every query that names another aggregate beside it (SUM(, AVG(, a COUNT( not followed by
+    DISTINCT, a quantile, spread, extreme or histogram function), whose routing stays as it was.  ValueError, quoting the
+    offending text, for a column that cannot be counted and for more than one distinct count in a query."""
+    found = list(re.finditer(r"\b(?:COUNT\s*\(\s*DISTINCT\b|APPROX_COUNT_DISTINCT\s*\()([^)]*)\)", query, re.IGNORECASE))
+    if not found:
+        return None
+    up = query.upper()
+    if "SUM(" in up or "AVG(" in up or re.search(r"COUNT\((?!\s*DISTINCT\b)", up):
+        return None
+    if re.search(r"\b(MEDIAN|PERCENTILE(_CONT|_DISC)?|VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?|MIN|MAX|HISTOGRAM)\s*\(", query, re.IGNORECASE):
+        return None
+    shown = " ".join(found[0].group(0).split())
+    if len(found) > 1:
+        raise ValueError(f"'{shown}', '{' '.join(found[1].group(0).split())}': one COUNT(DISTINCT) per query")
+    col = found[0].group(1).strip()
+    if col.lower() not in _DISTINCT_COLUMNS:
+        raise ValueError(f"'{shown}': unknown column {col!r} (COUNT(DISTINCT) takes amount, region or product_id)")
+    return col.lower()
+
+
 def where_clause_of(query: str) -> Optional[str]:
     """The text of the query's WHERE clause (up to GROUP BY / ORDER BY / LIMIT), or None."""
     m = re.search(r"\bWHERE\b(.*?)(?=\bGROUP\s+BY\b|\bORDER\s+BY\b|\bLIMIT\b|\bHAVING\b|;|$)", query, re.IGNORECASE | re.DOTALL)
@@ -221,7 +248,7 @@ def get_optimal_method_for_query(query: str, dataset_size: Optional[int] = None)
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV, MIN/MAX, HISTOGRAM on MI355X "
+    p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV, MIN/MAX, HISTOGRAM, COUNT(DISTINCT) on MI355X "
                                 "(e.g. \"SELECT HISTOGRAM(amount, 20) FROM sales\" --s 10 --ci)",
                                 allow_abbrev=False)
     p.add_argument("query", nargs="?", help="SQL query, e.g. \"SELECT SUM(amount) FROM sales\"")
@@ -280,6 +307,18 @@ def run(args, out=sys.stdout) -> int:
             return 2
         if re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
             print("error: GROUP BY is not supported with HISTOGRAM", file=out)
+            return 2
+    try:
+        distinct = distinct_of(clean)
+    except ValueError as e:
+        print(f"error: {e}", file=out)
+        return 2
+    if distinct is not None:
+        if args.e is not None:
+            print("error: COUNT(DISTINCT) has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
+            return 2
+        if re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
+            print("error: GROUP BY is not supported with COUNT(DISTINCT)", file=out)
             return 2
     try:
         group_by_of(clean)
@@ -364,6 +403,9 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     hist = histogram_of(clean)
     if hist is not None:
         return _run_histogram(db, args, out, clean, qtype, hist, aqe_backend, t0, kw)
+    distinct = distinct_of(clean)
+    if distinct is not None:
+        return _run_distinct(db, args, out, clean, qtype, distinct, aqe_backend, t0, kw)
     gb = group_by_of(clean)
     if gb and group_error_form(clean, args):
         # --e with GROUP BY: nested block levels until every group's interval is within the threshold (aqe_reduce_grouped_error)
@@ -593,6 +635,39 @@ def _run_histogram(db, args, out, clean, qtype, hist, aqe_backend, t0, kw=None) 
         print(f"   exact below: {exact.below:,}   exact above: {exact.above:,}", file=out)
     print(f"   samples used: {res.n:,}", file=out)
     print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
+    db.close_database()
+    return 0
+
+
+def _run_distinct(db, args, out, clean, qtype, column, aqe_backend, t0, kw=None) -> int:
+    """COUNT(DISTINCT col) / APPROX_COUNT_DISTINCT(col): exact without --s; with --s (or an APPROX(...) wrapper) a sample —
+    --method block / parallel / random honoured, stride otherwise.  A sample's figure counts the sampled rows' values."""
+    kw = kw or {}  # {"key_where": ...} when the WHERE clause names region / product_id
+    where = aqe_backend.parse_where(clean)
+    if args.s is None and qtype != QUERY_EMBEDDED:
+        method, pct, name = "exact", 100.0, "exact"
+    else:
+        pct = args.s if args.s is not None else 10.0
+        method = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", "stride")
+        name = f"{method} sampling ({pct}%)"
+    res = db.approx_distinct(column=column, method=method, sample_percent=pct, where=where, confidence_level=args.confidence, seed=args.seed,
+                             num_threads=args.threads, **kw)
+    ms = (time.perf_counter() - t0) * 1e3
+    sketch = res.mode == "sketch"
+    fmt = (lambda v: f"{v:,.1f}") if sketch else (lambda v: f"{int(v):,}")
+    how = "sketch: HyperLogLog over 8,192 slots, standard error 1.15%" if sketch else "exact keys: one slot per key"
+    print(f"\n{name} COUNT(DISTINCT {column}) result:\n   value: {fmt(res.value)}   ({how})", file=out)
+    if args.ci:
+        print(f"   confidence interval ({args.confidence:g}, the sketch's error over the rows swept): ({fmt(res.ci_lower)} - {fmt(res.ci_upper)})", file=out)
+    if method != "exact":
+        print("   note: the figure counts the distinct values among the sampled rows: a lower bound for the table", file=out)
+    print(f"   samples used: {res.n:,}", file=out)
+    print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
+    if args.compare and method != "exact":
+        exact = db.approx_distinct(column=column, method="exact", where=where, **kw)
+        print(f"\ncomparison:\n   approximate: {fmt(res.value)}\n   exact:       {fmt(exact.value)}", file=out)
+        if exact.value != 0:
+            print(f"   actual error: {abs(res.value - exact.value) / abs(exact.value) * 100:.4f}%", file=out)
     db.close_database()
     return 0
 

@@ -94,6 +94,7 @@ struct StageRing {
 struct aqe_moment_scratch;  // moments.hip
 struct aqe_extreme_scratch;  // extremes.hip
 struct aqe_histogram_scratch;  // histogram.hip
+struct aqe_distinct_scratch;  // distinct.hip
 
 struct aqe_ctx {
     StageRing ring;
@@ -161,6 +162,8 @@ struct aqe_ctx {
     aqe_extreme_scratch* extremes = nullptr;
     // HISTOGRAM (histogram.hip): accumulator, tickets and the pinned vector of the counting sweep, made on first use
     aqe_histogram_scratch* histogram = nullptr;
+    // COUNT(DISTINCT) (distinct.hip): accumulator, tickets and the pinned vector of the sketch sweep, made on first use
+    aqe_distinct_scratch* distinct = nullptr;
 };
 
 // One persistent-sweep form of a plan's rounds (persist.hip): the tile list of all slots, who owns tiles
@@ -335,6 +338,9 @@ void extremes_release(aqe_ctx* c);
 
 // histogram.hip
 void histogram_release(aqe_ctx* c);
+
+// distinct.hip
+void distinct_release(aqe_ctx* c);
 
 // plans.hip
 void destroy_plan(aqe_plan* p, bool device_idle = false);  // device_idle: the caller has just synchronised the device

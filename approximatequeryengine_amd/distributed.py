@@ -482,6 +482,37 @@ def sharded_histogram(engine, query, spec, vec, all_reduce_sum: Callable, all_re
         return engine.histogram_finish(query, spec, v.data_ptr(), stream)
 
 
+def sharded_distinct(engine, query, column: int, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
+    """COUNT(DISTINCT column) across the ranks of a process group (engine.Engine interface), collective.  For a key column the
+    ranks agree on its range first — ONE all-reduce MAX of [-min, max] (engine.group_key_range, as sharded_group_by_pair) — and
+    derive mode and key_min from it (engine.distinct_mode): exact keys up to a span of DISTINCT_SLOTS, the sketch beyond it; the
+    amount column takes the sketch and needs no range.  Then every rank sweeps the part of the sample inside its shard into
+    DISTINCT_VEC_HEAD + DISTINCT_SLOTS doubles (aqe_distinct_enqueue), ONE all-reduce SUM merges [visited, n], ONE all-reduce
+    MAX the slots (an empty shard contributes zeros), and every rank finishes the same vector: the same bits on every rank.
+
+    vec     float64 tensor on the engine's device with room for DISTINCT_VEC_HEAD + DISTINCT_SLOTS doubles
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    from ._native import DISTINCT_AMOUNT, DISTINCT_SKETCH, DISTINCT_SLOTS, DISTINCT_VEC_HEAD
+    from .engine import distinct_mode
+    stream = _stream_for(stream, vec)
+    need = DISTINCT_VEC_HEAD + DISTINCT_SLOTS
+    if vec.numel() < need:
+        raise ValueError(f"vector holds {vec.numel()} doubles, {need} needed")
+    column = int(column)
+    with _torch_on(stream, vec):
+        mode, kmin = DISTINCT_SKETCH, 0
+        if column != DISTINCT_AMOUNT:
+            lo, hi = engine.group_key_range(column)
+            rng = vec.new_tensor([-float(lo), float(hi)])
+            all_reduce_max(rng)
+            mode, kmin = distinct_mode(column, -int(rng[0].item()), int(rng[1].item()))
+        v = vec[:need]
+        engine.distinct_enqueue(query, column, mode, kmin, v.data_ptr(), stream, key_filter)
+        all_reduce_sum(v[:DISTINCT_VEC_HEAD])
+        all_reduce_max(v[DISTINCT_VEC_HEAD:])
+        return engine.distinct_finish(query, column, mode, kmin, v.data_ptr(), stream)
+
+
 def sharded_group_extremes(engine, query, columns, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
     """GROUP BY MIN / MAX across ranks, collective: ``columns`` is one column or the ordered pair (A, B).  The key ranges are
     agreed in ONE MAX all-reduce (as sharded_group_by_pair); every rank bins its part of the sample into

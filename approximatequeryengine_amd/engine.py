@@ -671,6 +671,26 @@ class Engine:
                                                  len(bins)))
         return head, bins
 
+    # -- COUNT(DISTINCT column) (aqe_reduce_distinct and its kin): one sketch sweep; key_filter may be None everywhere --
+    def distinct(self, query: Query, column: int = nat.DISTINCT_AMOUNT, key_filter: "Optional[nat.KeyFilter]" = None) -> "nat.DistinctResult":
+        """The distinct values of ``column`` (DISTINCT_AMOUNT, GROUP_REGION, GROUP_PRODUCT) among the sampled rows that qualify."""
+        out = nat.DistinctResult()
+        self._chk(nat.lib().aqe_reduce_distinct(self._h, _filter_ref(key_filter), C.byref(query), int(column), C.byref(out)))
+        return out
+
+    def distinct_enqueue(self, query: Query, column: int, mode: int, key_min: int, dev_vec_ptr: int, stream: int = 0,
+                         key_filter: "Optional[nat.KeyFilter]" = None):
+        """This shard's DISTINCT_VEC_HEAD + DISTINCT_SLOTS doubles into device memory: all-reduce SUM of [0, 2), MAX of the rest,
+        then distinct_finish.  ``mode`` and ``key_min`` follow from the agreed key range (distinct_mode)."""
+        self._chk(nat.lib().aqe_distinct_enqueue(self._h, _filter_ref(key_filter), C.byref(query), int(column), int(mode), int(key_min),
+                                                 C.c_void_p(dev_vec_ptr), C.c_void_p(stream)))
+
+    def distinct_finish(self, query: Query, column: int, mode: int, key_min: int, dev_vec_ptr: int, stream: int = 0) -> "nat.DistinctResult":
+        out = nat.DistinctResult()
+        self._chk(nat.lib().aqe_distinct_finish(self._h, C.byref(query), int(column), int(mode), int(key_min), C.c_void_p(dev_vec_ptr), C.c_void_p(stream),
+                                                C.byref(out)))
+        return out
+
     def gather(self, query: Query) -> np.ndarray:
         """Rows of the record-returning sampler, as a RECORD_DTYPE array."""
         n = C.c_uint64()
@@ -788,6 +808,45 @@ def histogram_from_vec(vec: Sequence[float], bins: int, spec: "nat.HistogramSpec
         bad = int(spec.bins) != int(bins) or not spec.has_range
         raise nat.AqeError(rc, "the spec must carry a finite range lo < hi of as many buckets as the vector" if bad or v[0] > 0 else "No samples collected")
     return head, out
+
+
+def distinct_hash(u: int) -> int:
+    """aqe_distinct_hash: splitmix64's finaliser of the 64 value bits ``u`` — no GPU."""
+    return int(nat.lib().aqe_distinct_hash(int(u) & 0xFFFFFFFFFFFFFFFF))
+
+
+def distinct_mode(column: int, key_lo: int, key_hi: int):
+    """aqe_distinct_mode: (mode, key_min) of a distinct count of ``column`` whose keys span [key_lo, key_hi] — exact keys up to a
+    span of DISTINCT_SLOTS (and for an empty range), the sketch beyond it and for the amount column — no GPU."""
+    mode, kmin = C.c_int(), C.c_int32()
+    rc = nat.lib().aqe_distinct_mode(int(column), int(key_lo), int(key_hi), C.byref(mode), C.byref(kmin))
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "COUNT(DISTINCT): column must be DISTINCT_AMOUNT, GROUP_REGION or GROUP_PRODUCT")
+    return mode.value, kmin.value
+
+
+def distinct_slot(column: int, mode: int, key_min: int, value_bits: int):
+    """aqe_distinct_slot: (slot, rank) the sweep writes for the 64 value bits — an amount's bit pattern, or a key as int64 — no
+    GPU.  AqeError (ERR_INVALID) for a NaN amount and for a key outside the exact-keys window."""
+    slot, rank = C.c_uint32(), C.c_uint32()
+    rc = nat.lib().aqe_distinct_slot(int(column), int(mode), int(key_min), int(value_bits) & 0xFFFFFFFFFFFFFFFF, C.byref(slot), C.byref(rank))
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "COUNT(DISTINCT): no slot for this column, mode and value (a NaN amount, a key outside the window, a bad column or mode)")
+    return slot.value, rank.value
+
+
+def distinct_from_vec(vec: Sequence[float], column: int, mode: int, key_min: int = 0, confidence_level: float = 0.95, exact: bool = False) -> "nat.DistinctResult":
+    """aqe_distinct_from_vec: value and interval from the DISTINCT_VEC_HEAD + DISTINCT_SLOTS (all-reduced) doubles [visited, n,
+    slot...], on the host — no GPU.  An empty vector gives 0."""
+    v = np.ascontiguousarray(vec, dtype=np.float64)
+    if len(v) != nat.DISTINCT_VEC_HEAD + nat.DISTINCT_SLOTS:
+        raise ValueError(f"{nat.DISTINCT_VEC_HEAD} + {nat.DISTINCT_SLOTS} doubles expected: visited, n, then the slots")
+    out = nat.DistinctResult()
+    rc = nat.lib().aqe_distinct_from_vec(v.ctypes.data_as(C.POINTER(C.c_double)), int(column), int(mode), int(key_min), float(confidence_level),
+                                         int(bool(exact)), C.byref(out))
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "COUNT(DISTINCT): bad column or mode (the amount column takes the sketch only)")
+    return out
 
 
 _KEY_COLUMNS = ("region", "product_id")

@@ -362,3 +362,13 @@ class ShardedBPlusDB(CustomBPlusDB):
         with torch.cuda.stream(self._side):
             vec = self._buffer(nat.HISTOGRAM_VEC_HEAD + nat.HISTOGRAM_MAX_BINS)
             return sharded_histogram(self._engine, q, spec, vec, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)
+
+    # ---- COUNT(DISTINCT): one all-reduce MAX for a key column's range, one all-reduce SUM of the counts, one all-reduce MAX of
+    # the slots; approx_distinct is CustomBPlusDB's own, over this ----
+    def _distinct(self, f, q, col):
+        import torch
+        from .distributed import sharded_distinct
+        self._eng()
+        with torch.cuda.stream(self._side):
+            vec = self._buffer(nat.DISTINCT_VEC_HEAD + nat.DISTINCT_SLOTS)
+            return sharded_distinct(self._engine, q, col, vec, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)

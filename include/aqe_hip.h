@@ -1003,6 +1003,80 @@ AQE_API int aqe_histogram_buckets(double lo, double hi, uint32_t bins, const dou
 AQE_API int aqe_histogram_from_vec(const double* vec, uint32_t bins, const aqe_histogram_spec* spec, uint64_t n_global, double confidence_level,
                                    int exact, aqe_histogram_header* header_out, aqe_histogram_bin* buckets_out, uint32_t max_buckets);
 
+/* ---- distinct: approximate COUNT(DISTINCT column) from ONE sketch sweep (distinct.hip) --------------------------------------
+ * `column` is AQE_DISTINCT_AMOUNT, AQE_GROUP_REGION or AQE_GROUP_PRODUCT.  A row QUALIFIES when it is sampled (q's sampler
+ * inside its row window), passes the amount WHERE range if q has one (inclusive at both ends; a NaN fails it) and passes the key
+ * filter (`filter`, NULL: none — in every entry).  For AQE_DISTINCT_AMOUNT a NaN amount never qualifies; for a key column
+ * without an amount range a NaN-amount row does qualify: SQL counts the key, not the amount.  visited = rows sampled,
+ * n = rows qualifying, as for the histogram.
+ *
+ * Value bits u (64-bit).  Amount: the double's bit pattern with -0.0 read as +0.0 (+inf and -inf are two values).  Key:
+ * (uint64_t)(int64_t)key.
+ * Hash.  splitmix64's finaliser: z = u + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ (z >> 27)) * 0x94D049BB133111EB; h = z ^ (z >> 31)   (aqe_distinct_hash).
+ *
+ * Two modes, one vector: [visited, n, slot[0 .. AQE_DISTINCT_SLOTS)] as doubles.
+ *   AQE_DISTINCT_SKETCH      the amount column, and a key column whose span max - min + 1 (in 64 bits) exceeds 8192:
+ *                            HyperLogLog with p = 13.  Slot h >> 51; with w = h << 13 the rank is w ? clz(w) + 1 : 52; a slot
+ *                            holds the largest rank seen, 0 = empty.
+ *   AQE_DISTINCT_EXACT_KEYS  a key column whose span is at most 8192: slot key - key_min holds 1 when that key was seen, and
+ *                            the value is the number of non-zero slots — the exact distinct count of the qualifying sampled rows.
+ *                            (A key outside [key_min, key_min + 8192) sets no slot; the table's, or the ranks' agreed, range
+ *                            leaves none.)
+ * Both modes merge by MAX over the slots and SUM over the head: inside a launch, between launches and between shards.  Every
+ * merge is an integer one: the answer is bit-identical from run to run.
+ *
+ * Value in sketch mode.  Ertl's improved estimator from the slot histogram C[0 .. 52], m = 8192, q = 51:
+ *   z = m tau(1 - C[52] / m);  for k = 51 down to 1: z = (z + C[k]) / 2;  z += m sigma(C[0] / m);  value = m m / (2 ln 2) / z
+ *   sigma(x): +inf at x == 1; else y = 1, z = x, repeat { x *= x; z += x y; y += y } until z stops changing; z.
+ *   tau(x):   0 at x == 0 or x == 1; else y = 1, z = 1 - x, repeat { x = sqrt(x); y *= 0.5; z -= (1 - x)^2 y } until z stops
+ *             changing; z / 3.
+ * Interval.  Sketch mode: value (1 -+ z s) with s = 1.04 / sqrt(8192) and z from confidence_level as every other path picks it
+ * (>= 0.99: 2.576, >= 0.95: 1.96, else 1.645), the lower end never below 0.  Exact-keys mode: [value, value].
+ * THE INTERVAL COVERS THE SKETCH'S ERROR OVER THE ROWS SWEPT, NOT THE SAMPLING: a sampled query reports the distinct values
+ * among the sampled rows, which can only be fewer than the table's.  lower_bound = 1 says so: it is set whenever the method is
+ * not AQE_M_EXACT.
+ * Status.  n == 0 (visited == 0 included): value 0, interval [0, 0], AQE_OK — a COUNT of nothing is 0.  Samplers: those of
+ * aqe_reduce_histogram; CLT, adaptive, stratified, random_device and pair-family samplers: AQE_ERR_UNSUPPORTED naming the
+ * sampler, before any launch.  A key column needs the key columns (AQE_STAGE_KEEP_AOS, or a synthetic table). */
+#define AQE_DISTINCT_AMOUNT 0
+#define AQE_DISTINCT_SKETCH 0
+#define AQE_DISTINCT_EXACT_KEYS 1
+#define AQE_DISTINCT_VEC_HEAD 2
+#define AQE_DISTINCT_SLOTS 8192
+typedef struct aqe_distinct_result {
+    double value, ci_lower, ci_upper;
+    uint64_t n, visited;
+    int32_t column, mode;
+    int32_t lower_bound;      /* 1: the rows swept are a sample — value bounds the table's distinct count from below */
+    int32_t key_min;          /* exact-keys mode: the key of slot 0 (else 0) */
+    uint32_t empty_slots;     /* slots still 0, of AQE_DISTINCT_SLOTS */
+    uint32_t reserved;
+    double kernel_ms;
+} aqe_distinct_result;
+/* Single GPU, synchronous: one launch; the last workgroup to arrive writes the vector into pinned memory.  Mode and key_min
+ * follow from the table's own key range (aqe_group_key_range, aqe_distinct_mode). */
+AQE_API int aqe_reduce_distinct(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, int column, aqe_distinct_result* out);
+/* Multi-GPU.  For a key column the ranks first agree on the key range (aqe_group_key_range, all-reduce MIN / MAX) and derive
+ * mode and key_min from it (aqe_distinct_mode); dev_vec: AQE_DISTINCT_VEC_HEAD + AQE_DISTINCT_SLOTS doubles:
+ *     aqe_distinct_enqueue(ctx, filter, q, column, mode, key_min, dev_vec, stream)
+ *     all-reduce SUM of dev_vec[0 .. 2), all-reduce MAX of dev_vec[2 .. 2 + 8192)
+ *     aqe_distinct_finish(ctx, q, column, mode, key_min, dev_vec, stream, &out)        synchronises `stream` */
+AQE_API int aqe_distinct_enqueue(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, int column, int mode, int32_t key_min, double* dev_vec,
+                                 void* stream);
+AQE_API int aqe_distinct_finish(aqe_ctx* ctx, const aqe_query* q, int column, int mode, int32_t key_min, const double* dev_vec, void* stream,
+                                aqe_distinct_result* out);
+/* Host only, no GPU.  aqe_distinct_hash: the hash of value bits u.  aqe_distinct_mode: mode and key_min of `column` over the key
+ * range [key_lo, key_hi] (an empty range, key_hi < key_lo: exact keys from 0; the amount column: the sketch).
+ * aqe_distinct_slot: the slot and the rank the sweep writes for `value_bits` (amount: the double's bits, -0.0 folded here; a
+ * NaN is AQE_ERR_INVALID, as is a key outside the exact-keys window).  aqe_distinct_from_vec: value and interval from an
+ * (all-reduced) vector; exact != 0 as AQE_M_EXACT. */
+AQE_API uint64_t aqe_distinct_hash(uint64_t u);
+AQE_API int aqe_distinct_mode(int column, int32_t key_lo, int32_t key_hi, int* mode, int32_t* key_min);
+AQE_API int aqe_distinct_slot(int column, int mode, int32_t key_min, uint64_t value_bits, uint32_t* slot, uint32_t* rank);
+AQE_API int aqe_distinct_from_vec(const double* vec, int column, int mode, int32_t key_min, double confidence_level, int exact,
+                                  aqe_distinct_result* out);
+
 #ifdef __cplusplus
 }
 #endif
