@@ -62,6 +62,7 @@ HISTOGRAM_VEC_HEAD = 4  # [visited, n, below, above], then count[0 .. bins): one
 DISTINCT_AMOUNT = 0  # the column of a distinct count: this, GROUP_REGION or GROUP_PRODUCT
 DISTINCT_SKETCH, DISTINCT_EXACT_KEYS = 0, 1
 DISTINCT_VEC_HEAD, DISTINCT_SLOTS = 2, 8192  # [visited, n] for a SUM all-reduce, then slot[0 .. 8192) for a MAX all-reduce
+SUMMARY_VEC, SUMMARY_VEC_SUM = 12, 10  # the SPREAD_VEC layout + {0, 0} for a SUM all-reduce, then {-min, max} for a MAX all-reduce
 KEYTERM_NONE, KEYTERM_RANGE, KEYTERM_BITMAP = 0, 1, 2
 KEY_BITMAP_BITS = 1024
 
@@ -148,6 +149,12 @@ class ExtremeGroupResult(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SummaryResult(C.Structure):
+    """aqe_summary_result: SUM / AVG / COUNT, VAR_SAMP / STDDEV_SAMP and MIN / MAX of the sampled rows that pass, from one sweep."""
+    _fields_ = [("sum", Result), ("avg", Result), ("count", Result), ("var_samp", SpreadResult), ("stddev_samp", SpreadResult),
+                ("extremes", ExtremeResult), ("kernel_ms", C.c_double)]
 
 
 class HistogramSpec(C.Structure):
@@ -346,6 +353,10 @@ def lib() -> C.CDLL:
         "aqe_distinct_mode": (C.c_int, [C.c_int, i32, i32, P(C.c_int), P(i32)]),
         "aqe_distinct_slot": (C.c_int, [C.c_int, C.c_int, i32, u64, P(u32), P(u32)]),
         "aqe_distinct_from_vec": (C.c_int, [P(dbl), C.c_int, C.c_int, i32, dbl, C.c_int, P(DistinctResult)]),
+        "aqe_reduce_summary": (C.c_int, [vp, P(KeyFilter), P(Query), P(SummaryResult)]),
+        "aqe_summary_enqueue": (C.c_int, [vp, P(KeyFilter), P(Query), vp, vp]),
+        "aqe_summary_finish": (C.c_int, [vp, P(Query), vp, vp, P(SummaryResult)]),
+        "aqe_summary_from_vec": (C.c_int, [P(dbl), P(Query), u64, C.c_int, P(SummaryResult)]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),

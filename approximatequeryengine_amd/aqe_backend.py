@@ -33,7 +33,7 @@ from . import _native as nat
 from .engine import RECORD_DTYPE, Engine, histogram_spec, key_filter_terms, make_key_filter, make_query
 
 __all__ = ["Record", "CustomBPlusDB", "CustomApproximateScheduler", "CustomValidationResult",
-           "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate", "SpreadEstimate"]
+           "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate", "SpreadEstimate", "SummaryEstimate"]
 
 
 class Record:
@@ -204,6 +204,49 @@ def _named_extreme(res, which):
     for e in (res.values() if isinstance(res, dict) else (res,)):
         e.value = getattr(e, which)
     return res
+
+
+def shape_moments(n, m2, m3, m4):
+    """(skewness, excess_kurtosis) from the centred sums of n values: (m3/n) / (m2/n)**1.5 and (m4/n) / (m2/n)**2 - 3; NaN
+    when m2 == 0 or n == 0 (a constant or an empty sample has no shape)."""
+    n, m2 = float(n), float(m2)
+    if not n > 0.0 or not m2 > 0.0:
+        return float("nan"), float("nan")
+    var = m2 / n
+    return (float(m3) / n) / var ** 1.5, (float(m4) / n) / var ** 2 - 3.0
+
+
+class SummaryEstimate:
+    """Result of approx_summary: the descriptive statistics of the sampled amounts that pass (NaN rows left out), from ONE
+    fused sweep (include/aqe_hip.h, aqe_summary_result).  ``count``, ``sum``, ``mean`` are the ApproxResults approx("COUNT" |
+    "SUM" | "AVG") gives on these rows; ``variance`` and ``stddev`` the SpreadEstimates of approx_variance / approx_stddev;
+    ``min``, ``max`` and ``tail_fraction`` those of approx_extremes.  ``skewness`` and ``excess_kurtosis`` follow on the host
+    from the spread result's n, m2, m3, m4 (shape_moments)."""
+    __slots__ = ("count", "sum", "mean", "variance", "stddev", "min", "max", "tail_fraction", "n", "visited", "kernel_ms", "method")
+
+    def __init__(self, r, method: str):
+        self.count, self.sum, self.mean = ApproxResult(r.count, method), ApproxResult(r.sum, method), ApproxResult(r.avg, method)
+        self.variance = SpreadEstimate(r.var_samp, "var_samp", method)
+        self.stddev = SpreadEstimate(r.stddev_samp, "stddev_samp", method)
+        x = r.extremes
+        self.min, self.max, self.tail_fraction = x.min, x.max, x.tail_fraction
+        self.n, self.visited = int(x.n), int(x.visited)
+        self.kernel_ms = r.kernel_ms
+        self.method = method
+
+    @property
+    def skewness(self):
+        v = self.variance
+        return shape_moments(v.n, v.m2, v.m3, v.m4)[0]
+
+    @property
+    def excess_kurtosis(self):
+        v = self.variance
+        return shape_moments(v.n, v.m2, v.m3, v.m4)[1]
+
+    def __repr__(self):
+        return (f"SummaryEstimate(count={self.count.value!r}, sum={self.sum.value!r}, mean={self.mean.value!r}, stddev={self.stddev.value!r}, "
+                f"min={self.min!r}, max={self.max!r}, n={self.n}, method={self.method!r})")
 
 
 class HistogramEstimate:
@@ -978,6 +1021,30 @@ class CustomBPlusDB:
     def approx_max(self, **kw):
         """APPROX MAX(amount): approx_extremes(**kw) with ``value`` set to the maximum."""
         return _named_extreme(self.approx_extremes(**kw), "max")
+
+    def approx_summary(self, method: str = "stride", sample_percent: float = 10.0, where: Optional[Tuple[float, float]] = None,
+                       id_between: Optional[Tuple[int, int]] = None, seed: int = 42, confidence_level: float = 0.95, num_threads: int = 4,
+                       block_size: int = 1000, key_where: Optional[dict] = None) -> SummaryEstimate:
+        """APPROX SUMMARY(amount): count, sum, mean, variance, standard deviation, smallest and largest of the sampled amounts X
+        (WHERE, the key window and ``key_where`` applied, NaN rows left out) from ONE fused sweep, as a SummaryEstimate —
+        what approx("COUNT" | "SUM" | "AVG"), approx_variance, approx_stddev and approx_extremes report for these rows, for
+        one reading of them instead of two or more.  method and ``confidence_level`` as approx_extremes ("exact", "stride",
+        "block", "page", "parallel_block", "region", "random", "rowid" ...; CLT, adaptive, stratified and random_device
+        samplers raise ValueError).  There is no GROUP BY and no error-threshold form."""
+        if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
+            raise ValueError(f"SUMMARY does not take the {method} sampler (single-round family samplers and 'random' only)")
+        if not 0.0 < float(confidence_level) < 1.0:
+            raise ValueError("SUMMARY: confidence_level must lie strictly between 0 and 1")
+        f = None if key_where is None else _key_filter_for(key_where, method)
+        q = self._approx_query("SUM", "stride" if method == "rowid" else method, sample_percent, None, where, seed, num_threads, block_size,
+                               confidence_level, id_between=id_between)
+        if method == "rowid":
+            q.method = nat.M_ROWID_MOD
+        q.confidence_level = float(confidence_level)
+        return SummaryEstimate(_quantile_call(lambda: self._summary(f, q)), method)
+
+    def _summary(self, f, q):
+        return self._eng().reduce_summary(q, f)
 
     def approx_histogram(self, bins: int = 20, range: Optional[Tuple[float, float]] = None, method: str = "stride", sample_percent: float = 10.0,
                          where: Optional[Tuple[float, float]] = None, id_between: Optional[Tuple[int, int]] = None, key_where: Optional[dict] = None,

@@ -15,6 +15,8 @@
     python -m approximatequeryengine_amd.cli "SELECT HISTOGRAM(amount, 10, 0, 1000) FROM sales" --db sales.db --s 10 --compare
     python -m approximatequeryengine_amd.cli "SELECT COUNT(DISTINCT product_id) FROM sales WHERE region = 2" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli "SELECT APPROX_COUNT_DISTINCT(amount) FROM sales" --db sales.db --compare
+    python -m approximatequeryengine_amd.cli "SELECT SUMMARY(amount) FROM sales WHERE region = 2" --db sales.db --s 10 --ci
+    python -m approximatequeryengine_amd.cli "SELECT DESCRIBE(amount) FROM sales" --db sales.db --compare
     python -m approximatequeryengine_amd.cli --explain
 
 The reference's own CLI defines `-s/--sample` and `-e/--error` but tests `args.s` / `args.e`
@@ -176,6 +178,25 @@ def distinct_of(query: str) -> Optional[str]:
     return col.lower()
 
 
+def summary_of(query: str) -> Optional[bool]:
+    """SUMMARY(amount) / DESCRIBE(amount), in any letter case -> True; None for any other query — and for every query that
+    names another aggregate beside it (SUM(, AVG(, COUNT(, a distinct count, a quantile, spread, extreme or histogram
+    function), whose routing stays as it was.  ValueError, quoting the offending text, for a column other than amount."""
+    m = re.search(r"\b(SUMMARY|DESCRIBE)\s*\(([^)]*)\)", query, re.IGNORECASE)
+    if not m:
+        return None
+    up = query.upper()
+    if any(a + "(" in up for a in ("SUM", "AVG", "COUNT")):
+        return None
+    if re.search(r"\b(MEDIAN|PERCENTILE(_CONT|_DISC)?|VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?|MIN|MAX|HISTOGRAM|COUNT|APPROX_COUNT_DISTINCT)\s*\(",
+                 query, re.IGNORECASE):
+        return None
+    col = m.group(2).strip()
+    if col.lower() != "amount":
+        raise ValueError(f"'{' '.join(m.group(0).split())}': unknown column {col!r} ({m.group(1).upper()} takes amount)")
+    return True
+
+
 def where_clause_of(query: str) -> Optional[str]:
     """The text of the query's WHERE clause (up to GROUP BY / ORDER BY / LIMIT), or None."""
     m = re.search(r"\bWHERE\b(.*?)(?=\bGROUP\s+BY\b|\bORDER\s+BY\b|\bLIMIT\b|\bHAVING\b|;|$)", query, re.IGNORECASE | re.DOTALL)
@@ -248,8 +269,8 @@ def get_optimal_method_for_query(query: str, dataset_size: Optional[int] = None)
 
 
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV, MIN/MAX, HISTOGRAM, COUNT(DISTINCT) on MI355X "
-                                "(e.g. \"SELECT HISTOGRAM(amount, 20) FROM sales\" --s 10 --ci)",
+    p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV, MIN/MAX, HISTOGRAM, COUNT(DISTINCT), SUMMARY on MI355X "
+                                "(e.g. \"SELECT HISTOGRAM(amount, 20) FROM sales\" --s 10 --ci; \"SELECT SUMMARY(amount) FROM sales\" --s 10 --ci)",
                                 allow_abbrev=False)
     p.add_argument("query", nargs="?", help="SQL query, e.g. \"SELECT SUM(amount) FROM sales\"")
     p.add_argument("--db", default="custom_demo.db", help="database file (reference format)")
@@ -319,6 +340,18 @@ def run(args, out=sys.stdout) -> int:
             return 2
         if re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
             print("error: GROUP BY is not supported with COUNT(DISTINCT)", file=out)
+            return 2
+    try:
+        summary = summary_of(clean)
+    except ValueError as e:
+        print(f"error: {e}", file=out)
+        return 2
+    if summary is not None:
+        if args.e is not None:
+            print("error: SUMMARY has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
+            return 2
+        if re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
+            print("error: GROUP BY is not supported with SUMMARY", file=out)
             return 2
     try:
         group_by_of(clean)
@@ -406,6 +439,8 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     distinct = distinct_of(clean)
     if distinct is not None:
         return _run_distinct(db, args, out, clean, qtype, distinct, aqe_backend, t0, kw)
+    if summary_of(clean) is not None:
+        return _run_summary(db, args, out, clean, qtype, aqe_backend, t0, kw)
     gb = group_by_of(clean)
     if gb and group_error_form(clean, args):
         # --e with GROUP BY: nested block levels until every group's interval is within the threshold (aqe_reduce_grouped_error)
@@ -668,6 +703,48 @@ def _run_distinct(db, args, out, clean, qtype, column, aqe_backend, t0, kw=None)
         print(f"\ncomparison:\n   approximate: {fmt(res.value)}\n   exact:       {fmt(exact.value)}", file=out)
         if exact.value != 0:
             print(f"   actual error: {abs(res.value - exact.value) / abs(exact.value) * 100:.4f}%", file=out)
+    db.close_database()
+    return 0
+
+
+def _run_summary(db, args, out, clean, qtype, aqe_backend, t0, kw=None) -> int:
+    """SUMMARY(amount) / DESCRIBE(amount): exact without --s; with --s (or an APPROX(...) wrapper) a sample — --method block /
+    parallel / random honoured, stride otherwise.  One fused sweep; one line per figure, in a fixed order: count, sum, mean,
+    stddev, min, max, skewness, kurtosis."""
+    kw = kw or {}  # {"key_where": ...} when the WHERE clause names region / product_id
+    where = aqe_backend.parse_where(clean)
+    if args.s is None and qtype != QUERY_EMBEDDED:
+        method, pct, name = "exact", 100.0, "exact"
+    else:
+        pct = args.s if args.s is not None else 10.0
+        method = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", "stride")
+        name = f"{method} sampling ({pct}%)"
+    res = db.approx_summary(method=method, sample_percent=pct, where=where, confidence_level=args.confidence, seed=args.seed,
+                            num_threads=args.threads, **kw)
+    ms = (time.perf_counter() - t0) * 1e3
+    fmt = lambda v: "n/a" if v != v else f"{v:,.4f}"
+    ci = args.ci and method != "exact"
+    between = lambda r: f"   ({fmt(r.ci_lower)} - {fmt(r.ci_upper)})" if ci else ""
+    tail = lambda side: f"   (with confidence {args.confidence:g}, at most {res.tail_fraction * 100:.4g}% of qualifying rows lie {side} it)" if (ci and res.n) else ""
+    print(f"\n{name} SUMMARY(amount) result:", file=out)
+    print(f"   count:    {fmt(res.count.value)}", file=out)
+    print(f"   sum:      {fmt(res.sum.value)}{between(res.sum)}", file=out)
+    print(f"   mean:     {fmt(res.mean.value)}{between(res.mean)}", file=out)
+    print(f"   stddev:   {fmt(res.stddev.value)}{between(res.stddev)}", file=out)
+    print(f"   min:      {fmt(res.min)}{tail('below')}", file=out)
+    print(f"   max:      {fmt(res.max)}{tail('above')}", file=out)
+    print(f"   skewness: {fmt(res.skewness)}", file=out)
+    print(f"   kurtosis: {fmt(res.excess_kurtosis)}   (excess)", file=out)
+    print(f"   samples used: {res.n:,}", file=out)
+    print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
+    if args.compare and method != "exact":
+        exact = db.approx_summary(method="exact", where=where, **kw)
+        print("\ncomparison (approximate / exact):", file=out)
+        for label, a, x in (("count", res.count.value, exact.count.value), ("sum", res.sum.value, exact.sum.value),
+                            ("mean", res.mean.value, exact.mean.value), ("stddev", res.stddev.value, exact.stddev.value),
+                            ("min", res.min, exact.min), ("max", res.max, exact.max)):
+            err = f"   actual error: {abs(a - x) / abs(x) * 100:.4f}%" if (x == x and a == a and x != 0 and abs(x) != float("inf")) else ""
+            print(f"   {label + ':':<8} {fmt(a)} / {fmt(x)}{err}", file=out)
     db.close_database()
     return 0
 

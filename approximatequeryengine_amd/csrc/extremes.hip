@@ -21,6 +21,7 @@
 #include <cstddef>
 
 #include "device_common.hpp"
+#include "extreme_core.hpp"
 #include "host.hpp"
 #include "key_term.hpp"
 #include "spread_core.hpp"
@@ -28,38 +29,10 @@
 namespace aqe {
 namespace {
 
-constexpr unsigned kGridCap = 1024;  // workgroups of the ungrouped sweep at most, as k_moments
 constexpr int kExVec = AQE_EXTREME_VEC;
 static_assert(kExVec == 4, "vector layout of include/aqe_hip.h");
 static_assert(kMapWords == 16, "two maps are staged by 32 threads");
 static_assert(sizeof(aqe_extreme_result) == 56 && sizeof(aqe_extreme_group_result) == 48, "layouts of include/aqe_hip.h");
-
-// What the finishes need besides the vector.
-struct ExtremeFin {
-    double confidence;
-    int32_t exact, pad;
-};
-
-// min, max and the tail fraction from {n, -min, max}: eps = 1 - (1 - c)^(1/n), in the form that keeps its digits.
-__host__ __device__ inline void extreme_values(double n, double neg_min, double mx, const ExtremeFin& f, double* mn_out, double* mx_out, double* tail) {
-    if (n > 0.0) {
-        *mn_out = 0.0 - neg_min;  // (0 - 0 is +0.0: a zero extreme is reported as +0.0)
-        *mx_out = mx + 0.0;
-        *tail = f.exact ? 0.0 : -expm1(log1p(-f.confidence) / n);
-    } else {
-        *mn_out = *mx_out = *tail = __builtin_nan("");
-    }
-}
-__host__ __device__ inline aqe_extreme_result extreme_result(const double* vec, const ExtremeFin& f) {
-    aqe_extreme_result r;
-    extreme_values(vec[0], vec[2], vec[3], f, &r.min, &r.max, &r.tail_fraction);
-    r.n = static_cast<uint64_t>(vec[0]);
-    r.visited = static_cast<uint64_t>(vec[1]);
-    r.device_status = 0;
-    r.pad = 0;
-    r.kernel_ms = 0.0;
-    return r;
-}
 
 struct ExtremeLaunch {
     SweepCommon sw;
@@ -76,23 +49,6 @@ struct ExtremeLaunch {
     DevFilter flt;
 };
 static_assert(sizeof(ExtremeLaunch) <= 4096, "kernel arguments are limited to 4 KB");
-
-// Sharded arrival tickets (k_moments, finish_block of kernels.hip): true in the one thread that draws the last.
-__device__ __forceinline__ int draw_ticket(unsigned* ticket) {
-    const unsigned G = gridDim.x, shards = G < static_cast<unsigned>(kShards) ? G : static_cast<unsigned>(kShards);
-    unsigned* const ct = ticket + static_cast<size_t>(kShards) * kShardStride;
-    if (G <= static_cast<unsigned>(kShards)) {
-        if (__hip_atomic_fetch_add(ct, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1u) { __hip_atomic_store(ct, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return 1; }
-        return 0;
-    }
-    const unsigned sh = blockIdx.x % shards, members = (G - sh + shards - 1u) / shards;
-    unsigned* const cs = ticket + static_cast<size_t>(sh) * kShardStride;
-    if (__hip_atomic_fetch_add(cs, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == members - 1u) {
-        __hip_atomic_store(cs, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__hip_atomic_fetch_add(ct, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == shards - 1u) { __hip_atomic_store(ct, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return 1; }
-    }
-    return 0;
-}
 
 // {n, visited, -min, max} of the workgroup's threads: lanes -> wave by cross-lane moves, waves -> workgroup through LDS.
 // Thread k < 4 returns component k (as k_moments' threads 0..7 hold its sums).  Counts are whole numbers below 2^53 (their
@@ -344,17 +300,12 @@ __global__ __launch_bounds__(64) void k_extremes_groups_finish(const double* __r
     out[b] = r;
 }
 
-inline unsigned grid_for(uint64_t work, uint64_t per_block) {
-    const uint64_t g = (work + per_block - 1) / per_block;
-    return static_cast<unsigned>(g < 1 ? 1 : g > kGridCap ? kGridCap : g);
-}
-
 }  // namespace
 }  // namespace aqe
 
 // What the extremes entries keep with the context, apart from every other path's scratch.  Allocated on first use.
 struct aqe_extreme_scratch {
-    double* d_partials = nullptr;          // [kGridCap][kExVec]
+    double* d_partials = nullptr;          // [kSweepGridCap][kExVec]
     unsigned* d_ticket = nullptr;          // kCounterWords: the ungrouped sweep's; every launch leaves them at zero
     unsigned* d_gticket = nullptr;         // ... the grouped sweep's
     double* d_vec = nullptr;               // [kExVec]
@@ -386,7 +337,7 @@ int ensure_scratch(aqe_ctx* c) {
     if (c->extremes) extremes_release(c);  // an allocation that failed part way: start over
     aqe_extreme_scratch* s = new aqe_extreme_scratch;
     c->extremes = s;  // (extremes_release frees whatever part of it exists)
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_partials), sizeof(double) * kGridCap * kExVec));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_partials), sizeof(double) * kSweepGridCap * kExVec));
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_ticket), sizeof(unsigned) * kCounterWords));
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_gticket), sizeof(unsigned) * kCounterWords));
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_vec), sizeof(double) * kExVec));
@@ -448,12 +399,12 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, double* vec,
         a.sw.wmax = p->q.where_max;
         a.idx = p->d_idx;
         a.n_idx = a.idx ? p->host.random_idx.size() : 0;
-        grid = grid_for(a.n_idx, static_cast<uint64_t>(kBlockThreads) * kTileUnroll);
+        grid = sweep_grid(a.n_idx, static_cast<uint64_t>(kBlockThreads) * kTileUnroll);
     } else if (!p->rounds.empty() && c->n_local) {
         const LaunchDesc& L = p->rounds[0];
         a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
         a.ntiles = L.nfam ? L.ntiles : 0;
-        grid = grid_for(a.ntiles, kWavesPerBlock);
+        grid = sweep_grid(a.ntiles, kWavesPerBlock);
     }
     // the columns the filter names, in column order: a column without a term is not read
     int nk = 0;

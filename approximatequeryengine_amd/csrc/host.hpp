@@ -95,6 +95,7 @@ struct aqe_moment_scratch;  // moments.hip
 struct aqe_extreme_scratch;  // extremes.hip
 struct aqe_histogram_scratch;  // histogram.hip
 struct aqe_distinct_scratch;  // distinct.hip
+struct aqe_summary_scratch;  // summary.hip
 
 struct aqe_ctx {
     StageRing ring;
@@ -164,6 +165,8 @@ struct aqe_ctx {
     aqe_histogram_scratch* histogram = nullptr;
     // COUNT(DISTINCT) (distinct.hip): accumulator, tickets and the pinned vector of the sketch sweep, made on first use
     aqe_distinct_scratch* distinct = nullptr;
+    // SUMMARY (summary.hip): partials, tickets and the pinned result of the fused moments-and-extremes sweep, made on first use
+    aqe_summary_scratch* summary = nullptr;
 };
 
 // One persistent-sweep form of a plan's rounds (persist.hip): the tile list of all slots, who owns tiles
@@ -341,6 +344,9 @@ void histogram_release(aqe_ctx* c);
 
 // distinct.hip
 void distinct_release(aqe_ctx* c);
+
+// summary.hip
+void summary_release(aqe_ctx* c);
 
 // plans.hip
 void destroy_plan(aqe_plan* p, bool device_idle = false);  // device_idle: the caller has just synchronised the device

@@ -39,11 +39,11 @@
 #include "host.hpp"
 #include "key_term.hpp"
 #include "spread_core.hpp"
+#include "sweep_host.hpp"
 
 namespace aqe {
 namespace {
 
-constexpr unsigned kGridCap = 1024;  // workgroups of the ungrouped sweep at most: 4 per CU, as k_round (kRoundGridCap)
 constexpr unsigned kPrivBins = 4;
 constexpr unsigned kMaxReplicas = 8;
 constexpr unsigned kSharedLdsBytes = 50u << 10;  // 1024 keys x 6 sums in one replica: 49 200 bytes
@@ -80,19 +80,6 @@ struct MomentLaunch {
     DevFilter flt;
 };
 static_assert(sizeof(MomentLaunch) <= 4096, "kernel arguments are limited to 4 KB");
-
-// SUM / AVG / COUNT from the power sums: the state make_result reads (device_common.hpp), one round folded.
-__host__ __device__ inline aqe_result result_from_vec(const double* vec, const FinalizeParams& fin, uint32_t row_bytes) {
-    QueryState s{};
-    s.n_a = s.n_p = vec[0];
-    s.sd_a = s.sd_p = vec[1];
-    s.qd_a = s.qd_p = vec[2];
-    s.visited = vec[5];
-    s.rounds = 1;
-    aqe_result r = make_result(s, fin);
-    r.bytes_algorithmic = r.visited * static_cast<uint64_t>(row_bytes);
-    return r;
-}
 
 template <bool kNT, int NK>
 __global__ __launch_bounds__(kBlockThreads) void k_moments(MomentLaunch a) {
@@ -581,11 +568,6 @@ __global__ __launch_bounds__(64) void k_spread_groups_finish_pair(const double* 
     out[b] = spread_group_result(bins + static_cast<size_t>(b) * kSpBin, pair_key(g, b), c, fin);
 }
 
-inline unsigned grid_for(uint64_t work, uint64_t per_block) {
-    const uint64_t g = (work + per_block - 1) / per_block;
-    return static_cast<unsigned>(g < 1 ? 1 : g > kGridCap ? kGridCap : g);
-}
-
 }  // namespace
 
 // What the host keeps of the level-by-level query in progress on a context (one at a time).
@@ -612,7 +594,7 @@ struct LevelRun {
 // What the spread and the filtered entries keep with the context: partials and tickets of the ungrouped sweep, the pinned
 // results, the grouped form's partials, bins and pinned groups.  Allocated on first use.
 struct aqe_moment_scratch {
-    double* d_partials = nullptr;   // [kGridCap][kSpVec]
+    double* d_partials = nullptr;   // [kSweepGridCap][kSpVec]
     unsigned* d_ticket = nullptr;   // kCounterWords, zeroed once: every launch leaves them at zero
     double* d_vec = nullptr;        // [kSpVec]
     aqe_result* h_out = nullptr;    // pinned, mapped
@@ -642,18 +624,11 @@ struct aqe_moment_scratch {
 namespace aqe {
 namespace {
 
-template <typename T>
-int pinned(aqe_ctx* c, T** host, T** dev, size_t count) {
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(host), sizeof(T) * count, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(dev), *host, 0));
-    return AQE_OK;
-}
-
 int ensure_scratch(aqe_ctx* c) {
     if (c->moments) return AQE_OK;
     aqe_moment_scratch* s = new aqe_moment_scratch;
     c->moments = s;  // (moments_release frees whatever part of it exists)
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_partials), sizeof(double) * kGridCap * kSpVec));
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_partials), sizeof(double) * kSweepGridCap * kSpVec));
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_ticket), sizeof(unsigned) * kCounterWords));
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_vec), sizeof(double) * kSpVec));
     HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_bins), sizeof(double) * kMaxGroupBins * kSpBin));
@@ -691,29 +666,6 @@ int unsupported(aqe_ctx* c, const Wording& w, int method) {
 }
 
 
-SpreadFin fin_for(const aqe_query* q, int kind) {
-    SpreadFin f;
-    f.z = z_for(q->confidence_level);
-    f.kind = kind;
-    f.exact = q->method == AQE_M_EXACT ? 1 : 0;
-    return f;
-}
-
-FinalizeParams finalize_for(const aqe_ctx* c, const aqe_query& q) {
-    FinalizeParams f{};
-    f.n_global = q.row_hi > q.row_lo ? q.row_hi - q.row_lo : c->n_global;  // a row window is the table (finalize_params, plans.hip)
-    f.pct = q.sample_percent;
-    f.shift = query_shift(c, q);
-    f.agg = q.agg;
-    f.convention = q.convention;
-    f.is_exact = q.method == AQE_M_EXACT;
-    f.is_clt = 0;
-    return f;
-}
-
-inline hipStream_t stream_of(aqe_ctx* c, void* stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
-
-
 // One launch: this shard's kSpVec sums into `vec`, under the filter `f` (null: none); fused: the last workgroup also
 // finishes into a pinned result.
 int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, double* vec, int fused, const SpreadFin* sfin, hipStream_t s) {
@@ -738,12 +690,12 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, double* vec,
         a.sw.wmax = p->q.where_max;
         a.idx = p->d_idx;
         a.n_idx = a.idx ? p->host.random_idx.size() : 0;
-        grid = grid_for(a.n_idx, static_cast<uint64_t>(kBlockThreads) * kTileUnroll);
+        grid = sweep_grid(a.n_idx, static_cast<uint64_t>(kBlockThreads) * kTileUnroll);
     } else if (!p->rounds.empty() && c->n_local) {
         const LaunchDesc& L = p->rounds[0];
         a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
         a.ntiles = L.nfam ? L.ntiles : 0;
-        grid = grid_for(a.ntiles, kWavesPerBlock);
+        grid = sweep_grid(a.ntiles, kWavesPerBlock);
     }
     // the columns the filter names, in column order: a column without a term is not read
     int nk = 0;

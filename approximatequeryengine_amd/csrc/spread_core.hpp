@@ -15,6 +15,27 @@ struct SpreadFin {
     int32_t kind, exact;
 };
 
+// The grid of an ungrouped sweep over sampled rows (k_moments, k_extremes, k_summary): one workgroup per `per_block` units
+// of work, at most kSweepGridCap — 4 per CU, as k_round (kRoundGridCap).
+constexpr unsigned kSweepGridCap = 1024;
+inline unsigned sweep_grid(uint64_t work, uint64_t per_block) {
+    const uint64_t g = (work + per_block - 1) / per_block;
+    return static_cast<unsigned>(g < 1 ? 1 : g > kSweepGridCap ? kSweepGridCap : g);
+}
+
+// SUM / AVG / COUNT from the power sums: the state make_result reads (device_common.hpp), one round folded.
+__host__ __device__ inline aqe_result result_from_vec(const double* vec, const FinalizeParams& fin, uint32_t row_bytes) {
+    QueryState s{};
+    s.n_a = s.n_p = vec[0];
+    s.sd_a = s.sd_p = vec[1];
+    s.qd_a = s.qd_p = vec[2];
+    s.visited = vec[5];
+    s.rounds = 1;
+    aqe_result r = make_result(s, fin);
+    r.bytes_algorithmic = r.visited * static_cast<uint64_t>(row_bytes);
+    return r;
+}
+
 struct SpreadCore {
     double value, lo, hi, mean, m2, m3, m4;
     int has_interval;

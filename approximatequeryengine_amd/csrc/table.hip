@@ -572,6 +572,7 @@ void aqe_destroy(aqe_ctx* c) {
     extremes_release(c);
     histogram_release(c);
     distinct_release(c);
+    summary_release(c);
     free_table(c);
     free_ring(c);
     if (c->d_stamps) (void)hipFree(c->d_stamps);

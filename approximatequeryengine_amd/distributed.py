@@ -448,6 +448,27 @@ def sharded_extremes(engine, query, vec, all_reduce_sum: Callable, all_reduce_ma
         return engine.extremes_finish(query, v.data_ptr(), stream)
 
 
+def sharded_summary(engine, query, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
+    """SUMMARY(amount) across the ranks of a process group (engine.Engine interface), collective: every rank sweeps the part of
+    the sample inside its shard ONCE into SUMMARY_VEC doubles (aqe_summary_enqueue, under ``key_filter`` when there is one),
+    ONE all-reduce SUM merges the first SUMMARY_VEC_SUM words (the power sums, the counts and the pad), ONE all-reduce MAX the
+    last two, {-min, max} (an empty shard contributes 0 and -inf), and every rank finishes the same vector — so every rank
+    returns the same bits.
+
+    vec     float64 tensor on the engine's device with room for SUMMARY_VEC doubles
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    from ._native import SUMMARY_VEC, SUMMARY_VEC_SUM
+    stream = _stream_for(stream, vec)
+    if vec.numel() < SUMMARY_VEC:
+        raise ValueError(f"vector holds {vec.numel()} doubles, {SUMMARY_VEC} needed")
+    with _torch_on(stream, vec):
+        v = vec[:SUMMARY_VEC]
+        engine.summary_enqueue(query, v.data_ptr(), stream, key_filter)
+        all_reduce_sum(v[:SUMMARY_VEC_SUM])
+        all_reduce_max(v[SUMMARY_VEC_SUM:])
+        return engine.summary_finish(query, v.data_ptr(), stream)
+
+
 def sharded_histogram(engine, query, spec, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
     """HISTOGRAM(amount, B) across the ranks of a process group (engine.Engine interface), collective.  When ``spec`` carries no
     range the ranks agree on the table's amount range first — ONE all-reduce MAX of [-min, max] (engine.quantile_amount_range),

@@ -614,6 +614,21 @@ class Engine:
         self._chk(nat.lib().aqe_grouped_error_finish(self._h, C.c_void_p(stream), out, max_groups, C.byref(n), C.byref(info)))
         return list(out[: n.value]), info
 
+    # -- SUMMARY (aqe_reduce_summary and its kin): one fused sweep answers SUM / AVG / COUNT, VARIANCE / STDDEV, MIN / MAX --
+    def reduce_summary(self, query: Query, key_filter: "Optional[nat.KeyFilter]" = None) -> "nat.SummaryResult":
+        out = nat.SummaryResult()
+        self._chk(nat.lib().aqe_reduce_summary(self._h, _filter_ref(key_filter), C.byref(query), C.byref(out)))
+        return out
+
+    def summary_enqueue(self, query: Query, dev_vec_ptr: int, stream: int = 0, key_filter: "Optional[nat.KeyFilter]" = None):
+        """This shard's SUMMARY_VEC doubles into device memory: all-reduce SUM of [0, 10), MAX of [10, 12), then summary_finish."""
+        self._chk(nat.lib().aqe_summary_enqueue(self._h, _filter_ref(key_filter), C.byref(query), C.c_void_p(dev_vec_ptr), C.c_void_p(stream)))
+
+    def summary_finish(self, query: Query, dev_vec_ptr: int, stream: int = 0) -> "nat.SummaryResult":
+        out = nat.SummaryResult()
+        self._chk(nat.lib().aqe_summary_finish(self._h, C.byref(query), C.c_void_p(dev_vec_ptr), C.c_void_p(stream), C.byref(out)))
+        return out
+
     # -- MIN / MAX (aqe_reduce_extremes and its kin): one sweep answers both; key_filter may be None everywhere --
     def reduce_extremes(self, query: Query, key_filter: "Optional[nat.KeyFilter]" = None) -> "nat.ExtremeResult":
         out = nat.ExtremeResult()
@@ -758,6 +773,20 @@ def extremes_from_vec(vec: Sequence[float], confidence_level: float = 0.95, exac
     rc = nat.lib().aqe_extremes_from_vec((C.c_double * nat.EXTREME_VEC)(*v), float(confidence_level), int(bool(exact)), C.byref(out))
     if rc != nat.OK:
         raise nat.AqeError(rc, "confidence_level must lie inside (0, 1)" if not 0.0 < confidence_level < 1.0 else "No samples collected")
+    return out
+
+
+def summary_from_vec(vec: Sequence[float], query: Query, n_global: int, exact: bool = False) -> "nat.SummaryResult":
+    """aqe_summary_from_vec: every figure of a SUMMARY from SUMMARY_VEC (all-reduced) doubles — the SPREAD_VEC layout, {0, 0},
+    {-min, max} — on the host, no GPU.  ``n_global`` is the N of the estimators.  Raises AqeError (ERR_INVALID) when visited
+    == 0 ("No samples collected") or the query's confidence_level is outside (0, 1)."""
+    v = [float(x) for x in vec]
+    if len(v) != nat.SUMMARY_VEC:
+        raise ValueError(f"{nat.SUMMARY_VEC} doubles expected: n, P1, P2, P3, P4, visited, n c, 0, 0, 0, -min, max")
+    out = nat.SummaryResult()
+    rc = nat.lib().aqe_summary_from_vec((C.c_double * nat.SUMMARY_VEC)(*v), C.byref(query), int(n_global), int(bool(exact)), C.byref(out))
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "confidence_level must lie inside (0, 1)" if not 0.0 < query.confidence_level < 1.0 else "No samples collected")
     return out
 
 

@@ -353,6 +353,16 @@ class ShardedBPlusDB(CustomBPlusDB):
             bins = self._buffer(4 * 1024)
             return sharded_group_extremes(self._engine, q, cols, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)
 
+    # ---- SUMMARY: one all-reduce SUM of the power sums and counts, one all-reduce MAX of {-min, max}; approx_summary is
+    # CustomBPlusDB's own, over this ----
+    def _summary(self, f, q):
+        import torch
+        from .distributed import sharded_summary
+        self._eng()
+        with torch.cuda.stream(self._side):
+            return sharded_summary(self._engine, q, self._buffer(nat.SUMMARY_VEC), self._ar_sum, self._ar_max, stream=self._side.cuda_stream,
+                                   key_filter=f)
+
     # ---- HISTOGRAM: one all-reduce MAX for the range when the caller gives none, one all-reduce SUM of the counts;
     # approx_histogram is CustomBPlusDB's own, over this ----
     def _histogram(self, f, q, spec):

@@ -1077,6 +1077,53 @@ AQE_API int aqe_distinct_slot(int column, int mode, int32_t key_min, uint64_t va
 AQE_API int aqe_distinct_from_vec(const double* vec, int column, int mode, int32_t key_min, double confidence_level, int exact,
                                   aqe_distinct_result* out);
 
+/* ---- summary: SUMMARY(amount) — count, sum, mean, spread, smallest and largest from ONE fused sweep (summary.hip) ----------
+ * X = the sampled amounts: rows of q's sampler inside its row window that pass the inclusive amount WHERE range and the
+ * key filter (`filter`, NULL: none — in every entry), NaN rows left out: the set aqe_reduce_extremes sees.  n = |X|;
+ * visited = sampled rows before WHERE, filter and NaN.  One kernel (k_summary) reads each sampled row once and carries both
+ * the shifted power sums of the VARIANCE / STDDEV sweep and the two extremes of the MIN / MAX sweep; q->agg is ignored.
+ *
+ * Vector, AQE_SUMMARY_VEC doubles:
+ *   [0 .. 8)    the AQE_SPREAD_VEC layout {n, P1, P2, P3, P4, visited, n c, 0}         merged over shards by SUM
+ *   [8 .. 10)   {0, 0} (pad)                                                           SUM
+ *   [10 .. 12)  {-min, max}, neutral -inf                                              MAX
+ * so ranks issue one SUM all-reduce over the first AQE_SUMMARY_VEC_SUM words and one MAX all-reduce over the last two.
+ * On a table without NaN amounts words [0 .. 8) equal, to the bit, what aqe_spread_enqueue (no filter) or
+ * aqe_filtered_enqueue (with one) writes for the same query: the same grid, the same tile-to-wave assignment and the same
+ * order of additions.  Words {0, 5, 10, 11} equal aqe_extremes_enqueue's {n, visited, -min, max} on any table.  A NaN
+ * amount is left out of every figure here, where aqe_reduce_spread lets it poison the sums as numpy does.  No floating-
+ * point atomics: the answer is bit-identical from run to run.
+ *
+ * The sub-results are those of the existing finishes on these rows: sum / avg / count what aqe_reduce_filtered gives for
+ * AQE_SUM / AQE_AVG / AQE_COUNT, var_samp / stddev_samp what aqe_reduce_filtered_spread gives for AQE_SPREAD_VAR_SAMP /
+ * AQE_SPREAD_STDDEV_SAMP, extremes what aqe_reduce_extremes gives (their kernel_ms fields are 0; the call's time is
+ * kernel_ms of the summary).  Samplers, row windows and refusals are those of aqe_reduce_extremes' ungrouped form
+ * (AQE_ERR_UNSUPPORTED naming the sampler); confidence_level outside (0, 1) is AQE_ERR_INVALID; visited == 0 is
+ * AQE_ERR_INVALID "No samples collected"; n == 0 with visited > 0 is AQE_OK with NaN values.  No GROUP BY and no
+ * error-threshold form.  The summary entries of one context share its tickets and partials: issue them one after the
+ * other, not concurrently on two streams. */
+#define AQE_SUMMARY_VEC 12
+#define AQE_SUMMARY_VEC_SUM 10
+typedef struct aqe_summary_result {
+    aqe_result sum, avg, count;           /* what aqe_reduce_filtered gives for AQE_SUM / AQE_AVG / AQE_COUNT on these rows */
+    aqe_spread_result var_samp, stddev_samp;
+    aqe_extreme_result extremes;
+    double kernel_ms;
+} aqe_summary_result;
+/* Single GPU, synchronous: one launch; the last workgroup to arrive finishes into pinned memory. */
+AQE_API int aqe_reduce_summary(aqe_ctx* ctx, const aqe_key_filter* filter /* NULL: none */, const aqe_query* q, aqe_summary_result* out);
+/* Multi-GPU:
+ *     aqe_summary_enqueue(ctx, filter, q, dev_vec, stream)
+ *     all-reduce SUM of dev_vec[0 .. 10), all-reduce MAX of dev_vec[10 .. 12)
+ *     aqe_summary_finish(ctx, q, dev_vec, stream, &out)                                 synchronises `stream`
+ * (the finish sees the vector, not the filter: bytes_algorithmic counts 8 bytes per visited row, as aqe_filtered_finish does) */
+AQE_API int aqe_summary_enqueue(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, double* dev_vec, void* stream);
+AQE_API int aqe_summary_finish(aqe_ctx* ctx, const aqe_query* q, const double* dev_vec, void* stream, aqe_summary_result* out);
+/* Host only, no GPU: the result from an (all-reduced) vector; the shift is vec[6] / vec[0], n_global the N of the
+ * estimators, exact != 0 as AQE_M_EXACT.  AQE_ERR_INVALID when visited == 0 (out is filled) or q->confidence_level is
+ * outside (0, 1). */
+AQE_API int aqe_summary_from_vec(const double vec[AQE_SUMMARY_VEC], const aqe_query* q, uint64_t n_global, int exact, aqe_summary_result* out);
+
 #ifdef __cplusplus
 }
 #endif
