@@ -409,6 +409,7 @@ def lib() -> C.CDLL:
         "aqe_plan_launch_ms": (C.c_int, [vp, P(C.c_float), u32, P(u32)]),
         "aqe_plan_launch_samples": (C.c_int, [vp, P(u64), u32, P(u32)]),
         "aqe_plan_last_kernel": (C.c_int, [vp, P(C.c_int)]),
+        "aqe_last_load_policy": (C.c_int, [vp, P(C.c_int)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

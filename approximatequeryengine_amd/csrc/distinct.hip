@@ -416,6 +416,7 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, int column, 
     const bool key = column != AQE_DISTINCT_AMOUNT && work;
     if (!work) nk = 0;  // nothing is read: the kernel only writes the zero vector
     const bool nt = a.sw.nt != 0;
+    c->last_nt = nt ? 1 : 0;
     const dim3 g(grid);
     if (key) {
         if (nk == 1) {

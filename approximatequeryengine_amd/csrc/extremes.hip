@@ -423,6 +423,7 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, double* vec,
     }
     if (!work) nk = 0;  // nothing is read: the kernel only writes the neutral vector
     const bool nt = a.sw.nt != 0;
+    c->last_nt = nt ? 1 : 0;
     const dim3 g(grid), b(kBlockThreads);
     if (nk == 0) {
         if (nt) hipLaunchKernelGGL((k_extremes<true, 0>), g, b, 0, s, a);
@@ -489,6 +490,7 @@ int enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, aqe_plan* p, const GroupCo
     }
     const dim3 gd(grouped_grid(L.ntiles)), bd(kBlockThreads);
     const size_t lds_bytes = static_cast<size_t>(nbins) * kLdsBinBytes;
+    c->last_nt = a.sw.nt ? 1 : 0;
     if (a.sw.nt) launch_grouped_as<true>(pair, f != nullptr, nk, gd, bd, lds_bytes, s, a);
     else launch_grouped_as<false>(pair, f != nullptr, nk, gd, bd, lds_bytes, s, a);
     HIPCHK(c, hipGetLastError());

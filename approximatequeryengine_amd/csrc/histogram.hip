@@ -393,6 +393,7 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, const HistRa
     }
     if (!work) nk = 0;  // nothing is read: the kernel only writes the zero vector
     const bool nt = a.sw.nt != 0;
+    c->last_nt = nt ? 1 : 0;
     const dim3 g(grid);
     const size_t lds = hist_lds_bytes(rg.bins, a.copies);
     if (nk == 0) {

@@ -50,6 +50,12 @@ constexpr size_t kBatchLanes = 3;  // side streams of the batched multi-GPU form
 // warmed up on, non-temporal loads are up to 11 % faster from 48 MB; on a stream the plan has not run on before they cost
 // 1.5-2 us per launch at every size) — so the switch stays where both agree.  AQE_NT=0/1 forces it per plan (diagnostics).
 constexpr size_t kInfinityCacheBytes = 256ull << 20;
+// The one place of that rule: the load policy of an execution that sweeps `rows` sampled rows of this shard.  What a plan
+// (plans.hip, create_plan) and a level of a GROUP BY to an error threshold (moments.hip, level_sweep) both ask.
+inline bool sweeps_non_temporal(uint64_t rows) {
+    if (const char* e = std::getenv("AQE_NT")) return e[0] == '1';  // diagnostics (tools/ab_nt.py): force the load policy
+    return rows * sizeof(double) > kInfinityCacheBytes;
+}
 constexpr size_t kGraphMinRounds = 4, kGraphMaxRounds = 8192;  // one-launch-per-round plans replayed as a HIP graph
 
 }  // namespace aqe
@@ -167,6 +173,9 @@ struct aqe_ctx {
     aqe_distinct_scratch* distinct = nullptr;
     // SUMMARY (summary.hip): partials, tickets and the pinned result of the fused moments-and-extremes sweep, made on first use
     aqe_summary_scratch* summary = nullptr;
+    // diagnostics (aqe_last_load_policy): the instantiation the most recent launch of a visit_tile kernel was — 1 non-temporal,
+    // 0 plain loads, -1 no such launch yet.  Index-list sweeps and the quantile pass have the plain one only.
+    int last_nt = -1;
 };
 
 // One persistent-sweep form of a plan's rounds (persist.hip): the tile list of all slots, who owns tiles

@@ -714,6 +714,7 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, double* vec,
     }
     a.row_bytes = 8u + 4u * static_cast<unsigned>(nk);
     const bool nt = a.sw.nt != 0;
+    c->last_nt = nt ? 1 : 0;
     const dim3 g(grid), b(kBlockThreads);
     if (nk == 0) {
         if (nt) hipLaunchKernelGGL((k_moments<true, 0>), g, b, 0, s, a);
@@ -854,6 +855,7 @@ int launch_grouped(aqe_ctx* c, const aqe_key_filter* f, const GroupCols& g, cons
     const size_t lds_bytes = priv ? static_cast<size_t>(nbins) * kBlockThreads * 5 * sizeof(double)
                                   : static_cast<size_t>(replicas_for(nbins)) * replica_stride(nbins) * kSpBin * sizeof(double);
     const bool nt = a.sw.nt != 0;
+    c->last_nt = nt ? 1 : 0;
     const dim3 gd(grid), bd(kBlockThreads);
 #define AQE_MG_LAUNCH(PRIV, NT)                                                                        \
     do {                                                                                               \
@@ -1097,7 +1099,7 @@ int level_sweep(aqe_ctx* c, uint32_t r, hipStream_t s) {
     sw.wmax = run.q.where_max;
     sw.shift = query_shift(c, run.q);
     sw.dense16 = c->dense16 ? 1 : 0;
-    sw.nt = d.samples * sizeof(double) > kInfinityCacheBytes ? 1 : 0;
+    sw.nt = sweeps_non_temporal(d.samples) ? 1 : 0;  // (per level: each is a launch of its own size)
     const int rc = launch_grouped(c, run.has_filter ? &run.filter : nullptr, run_cols(run), sw, d.ntiles, nullptr, &sc->d_lstate->stop, &run.last_grid, s);
     if (rc == AQE_OK) ++run.launches;
     return rc;

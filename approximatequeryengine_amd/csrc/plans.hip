@@ -634,8 +634,7 @@ int create_plan(aqe_ctx* c, const aqe_query* q, aqe_plan** out, const GivenFamil
     {   // (what one execution sweeps, in bytes of this shard: decides the load policy, sweep_common)
         uint64_t swept = p->host.has_topup ? p->topup.samples : 0;
         for (const LaunchDesc& L : p->rounds) swept += L.samples;
-        p->nt = swept * sizeof(double) > kInfinityCacheBytes;
-        if (const char* e = std::getenv("AQE_NT")) p->nt = e[0] == '1';  // diagnostics (tools/ab_nt.py): force the load policy, read per plan
+        p->nt = sweeps_non_temporal(swept);  // (AQE_NT is read here: per plan)
     }
     {   // persistent single-launch forms of the rounds
         const size_t R = p->rounds.size();
@@ -2023,6 +2022,12 @@ int aqe_plan_launch_ms(aqe_plan* p, float* ms, uint32_t cap, uint32_t* n_out) {
 int aqe_plan_last_kernel(const aqe_plan* p, int* kernel) {
     if (!p || !kernel) return AQE_ERR_INVALID;
     *kernel = p->last_kernel;
+    return AQE_OK;
+}
+
+int aqe_last_load_policy(const aqe_ctx* c, int* policy) {
+    if (!c || !policy) return AQE_ERR_INVALID;
+    *policy = c->last_nt;
     return AQE_OK;
 }
 

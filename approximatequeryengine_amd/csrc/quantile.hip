@@ -668,6 +668,7 @@ int enqueue_pass(aqe_quantile* r, double* vec, bool fused, hipStream_t s) {
         a.sw = SweepCommon{};
         a.ntiles = 0;
     }
+    c->last_nt = 0;  // (the pass masks every dense tile and has the plain instantiation only, whatever a.sw.nt says)
     hipLaunchKernelGGL(k_qpass, dim3(grid), dim3(kBlockThreads), 0, s, a);
     HIPCHK(c, hipGetLastError());
     r->passes++;

@@ -358,6 +358,7 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, double* vec,
     a.fin = fin;
     if (!work) nk = 0;  // nothing is read: the kernel only writes the neutral vector
     const bool nt = a.sw.nt != 0;
+    c->last_nt = nt ? 1 : 0;
     const dim3 g(grid), b(kBlockThreads);
     if (nk == 0) {
         if (nt) hipLaunchKernelGGL((k_summary<true, 0>), g, b, 0, s, a);

@@ -383,6 +383,13 @@ class Engine:
         self._chk(nat.lib().aqe_table_info_get(self._h, C.byref(t)))
         return t
 
+    def last_load_policy(self) -> int:
+        """Diagnostics: 1 when the most recent sweep over sampled rows ran the non-temporal instantiation, 0 the plain one, -1
+        before any such sweep (aqe_last_load_policy)."""
+        k = C.c_int()
+        self._chk(nat.lib().aqe_last_load_policy(self._h, C.byref(k)))
+        return k.value
+
     def key_range_rows(self, id_min: int, id_max: int) -> Tuple[int, int]:
         """Row window [lo, hi) of `id BETWEEN id_min AND id_max` (rows are in ascending-id leaf order)."""
         lo, hi = C.c_uint64(), C.c_uint64()

@@ -867,6 +867,12 @@ AQE_API int aqe_plan_launch_ms(aqe_plan* plan, float* ms, uint32_t cap, uint32_t
 #define AQE_KERNEL_INDEXED 5       /* k_indexed: the seeded-random sampler over its host-built index list (one launch)  */
 #define AQE_KERNEL_PERMUTED 6      /* k_permuted: AQE_M_RANDOM_DEVICE, rows drawn in the kernel (one launch)            */
 AQE_API int aqe_plan_last_kernel(const aqe_plan* plan, int* kernel);
+/* Diagnostics, read-only: which load policy the most recent sweep of the entries over sampled rows on this context (SPREAD and
+ * key predicates, GROUP BY forms, SUMMARY, MIN / MAX, HISTOGRAM, COUNT(DISTINCT), quantiles) was launched with — 1: the
+ * instantiation with non-temporal loads on interior dense tiles (one execution sweeps more than the Infinity Cache holds, or
+ * AQE_NT=1 in the environment when the plan — or the level of a GROUP BY to an error threshold — was made), 0: plain loads
+ * (the index list of the seeded random sampler and the quantile pass always are), -1: no such sweep yet. */
+AQE_API int aqe_last_load_policy(const aqe_ctx* ctx, int* policy);
 /* samples (sampled rows) each sweep launch of this shard folds, in launch order; the top-up entry is
  * its upper bound */
 AQE_API int aqe_plan_launch_samples(const aqe_plan* plan, uint64_t* samples, uint32_t cap, uint32_t* n_out);

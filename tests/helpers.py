@@ -1,4 +1,5 @@
 """Test helpers: map a golden "call" (reference method + positional args) onto the oracle."""
+import math
 import zlib
 
 import numpy as np
@@ -63,6 +64,57 @@ def oracle_indices(o, rows, call, cache_rows=None):
 
 def rel(a, b):
     return abs(a - b) / max(abs(a), abs(b), 1e-300)
+
+
+# ---- the checker of the sweeps over sampled rows (VARIANCE / STDDEV, key predicates, GROUP BY, the load-policy tests): two-pass
+#      moments in numpy.longdouble and include/aqe_hip.h's definition of the spread results from them — never the engine's sums
+LD = np.longdouble
+EST_TOL = 1e-9  # an estimate or an interval end against the longdouble checker, relative
+
+
+def moments(x):
+    """(n, mean, M2, M4) of X by the two-pass definition in longdouble (in chunks: 100 M rows)."""
+    x = np.asarray(x, dtype=np.float64)
+    n = len(x)
+    if n == 0:
+        return 0, LD(0), LD(0), LD(0)
+    step = 1 << 22
+    mean = sum((x[i:i + step].astype(LD).sum() for i in range(0, n, step)), LD(0)) / n
+    m2 = m4 = LD(0)
+    for i in range(0, n, step):
+        d = x[i:i + step].astype(LD) - mean
+        d2 = d * d
+        m2 += d2.sum()
+        m4 += (d2 * d2).sum()
+    return n, mean, m2, m4
+
+
+def expect(mom, kind, conf=0.95, exact=False):
+    """(value, ci_lower, ci_upper, has_interval) of include/aqe_hip.h's definition from longdouble moments."""
+    n, mean, m2, m4 = mom
+    nan = float("nan")
+    samp, sd = kind in ("var_samp", "stddev_samp"), kind.startswith("stddev")
+    if n == 0 or (samp and n < 2):
+        return nan, nan, nan, 0
+    var = m2 / (n - 1) if samp else m2 / n
+    value = np.sqrt(var) if sd else var
+    if exact:
+        return float(value), float(value), float(value), 1
+    if n < 4:
+        return float(value), nan, nan, 0
+    z = LD(2.576 if conf >= 0.99 else 1.96 if conf >= 0.95 else 1.645)
+    s2 = m2 / (n - 1)
+    se = np.sqrt(max(m4 / n - LD(n - 3) / LD(n - 1) * s2 * s2, LD(0)) / n)
+    if sd:
+        s = np.sqrt(s2)
+        if s == 0:
+            return float(value), 0.0, 0.0, 1
+        se = se / (2 * s)
+    return float(value), float(max(value - z * se, LD(0))), float(value + z * se), 1
+
+
+def close(got, want, tol=EST_TOL):
+    return (math.isnan(got) and math.isnan(want)) or rel(got, want) <= tol
 
 
 # ---- AQE_M_RANDOM_DEVICE: the keyed bijection of [0, N), restated in numpy from its definition in include/aqe_hip.h /
