@@ -63,6 +63,7 @@ DISTINCT_AMOUNT = 0  # the column of a distinct count: this, GROUP_REGION or GRO
 DISTINCT_SKETCH, DISTINCT_EXACT_KEYS = 0, 1
 DISTINCT_VEC_HEAD, DISTINCT_SLOTS = 2, 8192  # [visited, n] for a SUM all-reduce, then slot[0 .. 8192) for a MAX all-reduce
 SUMMARY_VEC, SUMMARY_VEC_SUM = 12, 10  # the SPREAD_VEC layout + {0, 0} for a SUM all-reduce, then {-min, max} for a MAX all-reduce
+TIME_BIN, TIME_MAX_BUCKETS, TIME_MAX_SPAN = 4, 1024, 2 ** 31 - 1  # {n, P1, P2, visited} per time bucket; the limits of aqe_time_plan
 KEYTERM_NONE, KEYTERM_RANGE, KEYTERM_BITMAP = 0, 1, 2
 KEY_BITMAP_BITS = 1024
 
@@ -155,6 +156,12 @@ class SummaryResult(C.Structure):
     """aqe_summary_result: SUM / AVG / COUNT, VAR_SAMP / STDDEV_SAMP and MIN / MAX of the sampled rows that pass, from one sweep."""
     _fields_ = [("sum", Result), ("avg", Result), ("count", Result), ("var_samp", SpreadResult), ("stddev_samp", SpreadResult),
                 ("extremes", ExtremeResult), ("kernel_ms", C.c_double)]
+
+
+class TimeSpec(C.Structure):
+    """aqe_time_spec: bucket(ts) = floor((ts - origin) / width); with has_window the inclusive timestamp window [t_lo, t_hi]."""
+    _fields_ = [("width", C.c_int64), ("origin", C.c_int64), ("t_lo", C.c_int64), ("t_hi", C.c_int64), ("has_window", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class HistogramSpec(C.Structure):
@@ -357,6 +364,13 @@ def lib() -> C.CDLL:
         "aqe_summary_enqueue": (C.c_int, [vp, P(KeyFilter), P(Query), vp, vp]),
         "aqe_summary_finish": (C.c_int, [vp, P(Query), vp, vp, P(SummaryResult)]),
         "aqe_summary_from_vec": (C.c_int, [P(dbl), P(Query), u64, C.c_int, P(SummaryResult)]),
+        "aqe_time_range": (C.c_int, [vp, P(C.c_int64), P(C.c_int64)]),
+        "aqe_time_bucket": (C.c_int64, [C.c_int64, P(TimeSpec)]),
+        "aqe_time_plan": (C.c_int, [P(TimeSpec), C.c_int64, C.c_int64, P(C.c_int64), P(u32)]),
+        "aqe_parse_time_where": (C.c_int, [C.c_char_p, P(TimeSpec), C.c_char_p, C.c_size_t]),
+        "aqe_reduce_time_buckets": (C.c_int, [vp, P(KeyFilter), P(Query), P(TimeSpec), P(GroupResult), u32, P(u32)]),
+        "aqe_time_buckets_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), P(TimeSpec), C.c_int64, C.c_int64, vp, vp]),
+        "aqe_time_buckets_finish": (C.c_int, [vp, P(Query), P(TimeSpec), C.c_int64, C.c_int64, vp, vp, P(GroupResult), u32, P(u32)]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),

@@ -30,10 +30,10 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as nat
-from .engine import RECORD_DTYPE, Engine, histogram_spec, key_filter_terms, make_key_filter, make_query
+from .engine import RECORD_DTYPE, Engine, histogram_spec, key_filter_terms, make_key_filter, make_query, time_spec
 
 __all__ = ["Record", "CustomBPlusDB", "CustomApproximateScheduler", "CustomValidationResult",
-           "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate", "SpreadEstimate", "SummaryEstimate"]
+           "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate", "SpreadEstimate", "SummaryEstimate", "BucketEstimate"]
 
 
 class Record:
@@ -121,6 +121,19 @@ class GroupEstimate:
 
     def __iter__(self):  # unpacks like the reference's (value, ci_lower, ci_upper)
         return iter((self.value, self.ci_lower, self.ci_upper))
+
+
+class BucketEstimate(GroupEstimate):
+    """One time bucket of approx_time_series: a GroupEstimate plus the bucket's ``start`` (origin + b * width) and ``visited``, the
+    sampled rows of the bucket inside the timestamp window (``n`` of them also pass the amount range and the key term)."""
+    __slots__ = ("start", "visited")
+
+    def __init__(self, r):
+        super().__init__(r)
+        self.start, self.visited = int(r.key), int(r.visited)
+
+    def __repr__(self):
+        return f"BucketEstimate(start={self.start}, value={self.value:.6g}, ci=[{self.ci_lower:.6g}, {self.ci_upper:.6g}], n={self.n})"
 
 
 class QuantileEstimate:
@@ -1045,6 +1058,39 @@ class CustomBPlusDB:
 
     def _summary(self, f, q):
         return self._eng().reduce_summary(q, f)
+
+    def approx_time_series(self, agg: str, width: int, origin: int = 0, time_between: Optional[Tuple[int, int]] = None,
+                           sample_percent: float = 10.0, method: str = "rowid", where: Optional[Tuple[float, float]] = None,
+                           id_between: Optional[Tuple[int, int]] = None, key_where: Optional[dict] = None, seed: int = 42, num_threads: int = 4,
+                           block_size: int = 1000) -> "dict[int, BucketEstimate]":
+        """APPROX <agg>(amount) ... GROUP BY BUCKET(timestamp, width[, origin]): SUM / AVG / COUNT per time bucket with a 95 %
+        interval, from ONE sweep of the sampled rows (aqe_reduce_time_buckets).  bucket(ts) = floor((ts - origin) / width); the
+        result is an ordered ``dict`` keyed by the bucket's start, origin + b * width, ascending — only buckets with a sampled row;
+        one nothing of which passes ``where`` / ``key_where`` is listed with n == 0.  ``time_between`` = (t_lo, t_hi) keeps the
+        rows with t_lo <= timestamp <= t_hi, both inclusive: a row outside counts into no bucket.  ``key_where`` may carry a term
+        on ONE key column.  Estimates as approx_group_by.  method: "rowid" (default), "exact", "stride", "block", "page",
+        "parallel_block", "region", "random" ...; CLT, adaptive, stratified and random_device samplers raise ValueError.  More
+        than 1024 buckets, or a table whose timestamps span 2^31 or more, raise ValueError (nothing is truncated); a window
+        that holds no sampled row raises RuntimeError("No samples collected")."""
+        a = str(agg).upper()
+        if a not in _AGG:
+            raise ValueError(f"time buckets take SUM, AVG or COUNT, not {agg!r}")
+        spec = time_spec(width, origin, time_between)
+        if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
+            raise ValueError(f"time buckets do not take the {method} sampler (single-round family samplers and 'random' only)")
+        if not float(sample_percent) > 0.0:
+            raise ValueError(f"sample_percent must be positive, got {sample_percent!r}")
+        f = None if key_where is None else _key_filter_for(key_where, method)
+        if f is not None and f.term[0].form != nat.KEYTERM_NONE and f.term[1].form != nat.KEYTERM_NONE:
+            raise ValueError("time buckets take a key predicate on ONE key column (region or product_id), not on both")
+        q = self._approx_query(a, "stride" if method == "rowid" else method, sample_percent, None, where, seed, num_threads, block_size,
+                               id_between=id_between)
+        if method == "rowid":
+            q.method = nat.M_ROWID_MOD
+        return {int(r.key): BucketEstimate(r) for r in _quantile_call(lambda: self._time_series(f, q, spec))}
+
+    def _time_series(self, f, q, spec):
+        return self._eng().time_buckets(q, spec, f)
 
     def approx_histogram(self, bins: int = 20, range: Optional[Tuple[float, float]] = None, method: str = "stride", sample_percent: float = 10.0,
                          where: Optional[Tuple[float, float]] = None, id_between: Optional[Tuple[int, int]] = None, key_where: Optional[dict] = None,

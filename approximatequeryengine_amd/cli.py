@@ -17,6 +17,7 @@
     python -m approximatequeryengine_amd.cli "SELECT APPROX_COUNT_DISTINCT(amount) FROM sales" --db sales.db --compare
     python -m approximatequeryengine_amd.cli "SELECT SUMMARY(amount) FROM sales WHERE region = 2" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli "SELECT DESCRIBE(amount) FROM sales" --db sales.db --compare
+    python -m approximatequeryengine_amd.cli "SELECT SUM(amount) FROM sales WHERE timestamp BETWEEN 0 AND 86399 GROUP BY BUCKET(timestamp, 3600)" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli --explain
 
 The reference's own CLI defines `-s/--sample` and `-e/--error` but tests `args.s` / `args.e`
@@ -235,6 +236,60 @@ def group_by_of(query: str) -> Optional[Tuple[str, ...]]:
     return tuple(names)
 
 
+def time_bucket_of(query: str) -> Optional[Tuple[int, int]]:
+    """GROUP BY BUCKET(timestamp, W[, origin]) / GROUP BY TIME_BUCKET(W, timestamp[, origin]), in any letter case -> (W, origin);
+    None for a query whose GROUP BY clause has no ``BUCKET(`` — whose routing stays as it was.  ValueError, quoting the clause, for a
+    column other than timestamp, a W that is not an integer of at least 1, an origin that is not an integer, another number of
+    arguments, or a second GROUP BY column beside the bucket."""
+    m = re.search(r"\bGROUP\s+BY\b(.*?)(?=\bHAVING\b|\bORDER\s+BY\b|\bLIMIT\b|;|$)", query, re.IGNORECASE | re.DOTALL)
+    if not m or not re.search(r"BUCKET\s*\(", m.group(1), re.IGNORECASE):
+        return None
+    clause = " ".join(m.group(1).split())
+    shown = f"'GROUP BY {clause}'"
+    b = re.fullmatch(r"(TIME_BUCKET|BUCKET)\s*\(([^()]*)\)\s*(.*)", clause, re.IGNORECASE)
+    if not b:
+        raise ValueError(f"{shown}: time buckets are written GROUP BY BUCKET(timestamp, W[, origin]) or GROUP BY TIME_BUCKET(W, timestamp[, origin])")
+    if b.group(3):
+        raise ValueError(f"{shown}: a second GROUP BY column beside the time bucket is not supported (filter with WHERE region ... or WHERE product_id ...)")
+    parts = [a.strip() for a in b.group(2).split(",")]
+    if len(parts) not in (2, 3):
+        raise ValueError(f"{shown}: {b.group(1).upper()} takes the column, the width and an optional origin")
+    if b.group(1).upper() == "TIME_BUCKET":
+        parts[0], parts[1] = parts[1], parts[0]
+    if re.sub(r"^\w+\.", "", parts[0]).lower() != "timestamp":
+        raise ValueError(f"{shown}: unknown column {parts[0]!r} (time buckets take timestamp)")
+    if not re.fullmatch(r"\+?\d+", parts[1]) or int(parts[1]) < 1 or int(parts[1]) > 2 ** 63 - 1:
+        raise ValueError(f"{shown}: the width {parts[1]!r} is not an integer of at least 1")
+    origin = 0
+    if len(parts) == 3:
+        if not re.fullmatch(r"[+-]?\d+", parts[2]) or not -2 ** 63 <= int(parts[2]) <= 2 ** 63 - 1:
+            raise ValueError(f"{shown}: the origin {parts[2]!r} is not an int64 integer")
+        origin = int(parts[2])
+    return int(parts[1]), origin
+
+
+_NO_BUCKET_FORM = r"\b(MEDIAN|PERCENTILE(_CONT|_DISC)?|VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?|MIN|MAX|HISTOGRAM|APPROX_COUNT_DISTINCT|SUMMARY|DESCRIBE)\s*\("
+
+
+def time_bucket_defect(clean: str, args) -> Optional[str]:
+    """What keeps a GROUP BY BUCKET(...) query from running, found before the table is opened (None: nothing): --e, an aggregate
+    without a bucketed form, a timestamp or key predicate outside the supported forms, key terms on both columns."""
+    if args.e is not None:
+        return "GROUP BY BUCKET(...) has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"
+    m = re.search(_NO_BUCKET_FORM, clean, re.IGNORECASE) or re.search(r"\bCOUNT\s*\(\s*DISTINCT\b", clean, re.IGNORECASE)
+    if m:
+        return f"{' '.join(m.group(0).split()).rstrip('(').strip().upper()} has no GROUP BY BUCKET(...) form: time buckets take SUM, AVG or COUNT"
+    from . import aqe_backend, engine
+    try:
+        engine.parse_time_where(clean)
+        kw = aqe_backend.parse_key_where(clean)
+    except ValueError as e:
+        return str(e)
+    if kw is not None and len(kw) > 1:
+        return f"the key predicate 'WHERE {where_clause_of(clean)}' names both key columns: time buckets take a term on ONE of region / product_id"
+    return None
+
+
 def group_error_form(clean: str, args) -> bool:
     """SUM / AVG / COUNT ... GROUP BY ... --e E without --s (--s wins, as in determine_query_type) and outside an APPROX(...)
     wrapper: the query the error-threshold form of GROUP BY answers."""
@@ -299,6 +354,17 @@ def run(args, out=sys.stdout) -> int:
         print("error: a query is required unless --explain is given", file=out)
         return 2
     clean, _ = parse_embedded_approx(args.query)
+    try:
+        bucket = time_bucket_of(clean)  # before group_by_of: the comma inside the parentheses never reaches that function's split
+    except ValueError as e:
+        print(f"error: {e}", file=out)
+        return 2
+    if bucket is not None:
+        why = time_bucket_defect(clean, args)
+        if why is not None:
+            print(f"error: {why}", file=out)
+            return 2
+        return _open_and_run(args, out, clean)
     try:
         quant = quantile_of(clean)
     except ValueError as e:
@@ -376,6 +442,11 @@ def run(args, out=sys.stdout) -> int:
         print("error: COUNT ... GROUP BY has no error-threshold (--e) form (a grouped COUNT has no interval to judge): "
               "give a sample percentage (--s) or none (exact)", file=out)
         return 2
+    return _open_and_run(args, out, clean)
+
+
+def _open_and_run(args, out, clean) -> int:
+    """The query has passed the checks that need no table: open it — sharded over the ranks under torchrun — and run."""
     if not os.path.exists(args.db):
         print(f"error: database file '{args.db}' not found", file=out)
         return 1
@@ -424,6 +495,9 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     if key_where is not None:
         print(f"predicate: WHERE {where_clause_of(clean)}", file=out)
     t0 = time.perf_counter()
+    bucket = time_bucket_of(clean)
+    if bucket is not None:
+        return _run_time_series(db, args, out, clean, qtype, agg, bucket, aqe_backend, t0, kw)
     quant = quantile_of(clean)
     if quant is not None:
         return _run_quantile(db, args, out, clean, qtype, quant, aqe_backend, t0)
@@ -745,6 +819,35 @@ def _run_summary(db, args, out, clean, qtype, aqe_backend, t0, kw=None) -> int:
                             ("min", res.min, exact.min), ("max", res.max, exact.max)):
             err = f"   actual error: {abs(a - x) / abs(x) * 100:.4f}%" if (x == x and a == a and x != 0 and abs(x) != float("inf")) else ""
             print(f"   {label + ':':<8} {fmt(a)} / {fmt(x)}{err}", file=out)
+    db.close_database()
+    return 0
+
+
+def _run_time_series(db, args, out, clean, qtype, agg, bucket, aqe_backend, t0, kw=None) -> int:
+    """SUM / AVG / COUNT ... GROUP BY BUCKET(timestamp, W[, origin]): exact without --s; with --s (or an APPROX(...) wrapper) the
+    rowid sample the other grouped forms take.  The query's WHERE timestamp terms are the window, its amount and key terms keep
+    their meaning.  One line per bucket: start, value, interval (with --ci), n."""
+    from .engine import parse_time_where
+    kw = kw or {}  # {"key_where": ...} when the WHERE clause names region / product_id
+    width, origin = bucket
+    window = parse_time_where(clean)
+    pct = args.s if args.s is not None else (10.0 if qtype == QUERY_EMBEDDED else 100.0)
+    method = "exact" if pct >= 100.0 else "rowid"
+    try:
+        series = db.approx_time_series(agg, width, origin=origin, time_between=window, sample_percent=pct, method=method,
+                                       where=aqe_backend.parse_where(clean), **kw)
+    except ValueError as e:  # (more than 1024 buckets, a timestamp range of 2^31 or more)
+        print(f"error: {e}", file=out)
+        db.close_database()
+        return 2
+    ms = (time.perf_counter() - t0) * 1e3
+    if window is not None:
+        print(f"window: timestamp {window[0]} .. {window[1]}", file=out)
+    print(f"\n{agg}(amount) GROUP BY BUCKET(timestamp, {width}{f', {origin}' if origin else ''}) ({'exact' if method == 'exact' else f'rowid sample {pct:g}%'}):", file=out)
+    for start, g in series.items():
+        ci = f"   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})" if (args.ci and method != "exact") else ""
+        print(f"   {start:>12}: {g.value:,.4f}{ci}   n={g.n:,}", file=out)
+    print(f"   execution time: {ms:.2f} ms", file=out)
     db.close_database()
     return 0
 

@@ -81,7 +81,7 @@ struct PlanScratch {
 // One stride-major copy of the column (and, for GROUP BY, of the key columns in the same slot order).
 struct StrideView {
     double* amount = nullptr;
-    int32_t* keys[2] = {nullptr, nullptr};  // [AQE_GROUP_REGION - 1], [AQE_GROUP_PRODUCT - 1], built on first use
+    int32_t* keys[3] = {nullptr, nullptr, nullptr};  // [AQE_GROUP_REGION - 1], [AQE_GROUP_PRODUCT - 1], [kTimeColumn - 1], built on first use
     uint64_t M = 0, q0 = 0;   // slot(r) = (r % step) * M + (r / step - q0)
     uint64_t bytes = 0;       // HBM this view holds (amount + key views)
     uint32_t refs = 0;        // plans laid out over it
@@ -102,6 +102,7 @@ struct aqe_extreme_scratch;  // extremes.hip
 struct aqe_histogram_scratch;  // histogram.hip
 struct aqe_distinct_scratch;  // distinct.hip
 struct aqe_summary_scratch;  // summary.hip
+struct aqe_time_scratch;  // timeseries.hip
 
 struct aqe_ctx {
     StageRing ring;
@@ -129,8 +130,10 @@ struct aqe_ctx {
     uint64_t view_evictions = 0;   // views dropped to make room, since the table was staged
     uint64_t view_fallbacks = 0;   // plans that wanted a view and were laid out in place instead
     // GROUP BY: key columns (SoA int32), extracted from the AoS rows or generated for a synthetic table on first use
-    int32_t* keycol[2] = {nullptr, nullptr};  // [AQE_GROUP_REGION - 1], [AQE_GROUP_PRODUCT - 1]
+    // ... and, for time buckets, the time OFFSET of each row as a third such column: timestamp - time_min (timeseries.hip)
+    int32_t* keycol[3] = {nullptr, nullptr, nullptr};  // [AQE_GROUP_REGION - 1], [AQE_GROUP_PRODUCT - 1], [kTimeColumn - 1]
     int32_t key_min[2] = {0, 0}, key_max[2] = {-1, -1};
+    int64_t time_min = std::numeric_limits<int64_t>::max(), time_max = std::numeric_limits<int64_t>::min();  // this shard's timestamps, found with the column
     bool synthetic = false;  // made by aqe_generate_synthetic: keys follow from the row number
     std::vector<hipStream_t> lanes;         // side streams of the batched multi-GPU form (aqe_batch), made on first use
     double* grp_partial = nullptr;          // GROUP BY scratch, grown on demand and kept with the context
@@ -173,6 +176,8 @@ struct aqe_ctx {
     aqe_distinct_scratch* distinct = nullptr;
     // SUMMARY (summary.hip): partials, tickets and the pinned result of the fused moments-and-extremes sweep, made on first use
     aqe_summary_scratch* summary = nullptr;
+    // time buckets (timeseries.hip): the workgroups' bins, the summed bins and the pinned groups, made on first use
+    aqe_time_scratch* timeseries = nullptr;
     // diagnostics (aqe_last_load_policy): the instantiation the most recent launch of a visit_tile kernel was — 1 non-temporal,
     // 0 plain loads, -1 no such launch yet.  Index-list sweeps and the quantile pass have the plain one only.
     int last_nt = -1;
@@ -356,6 +361,12 @@ void distinct_release(aqe_ctx* c);
 
 // summary.hip
 void summary_release(aqe_ctx* c);
+
+// timeseries.hip
+// The "column" number of the time-offset column where a key column's is taken (ensure_keys, ensure_key_view, key_pointer).
+constexpr int kTimeColumn = 3;
+int ensure_time(aqe_ctx* c);  // builds keycol[kTimeColumn - 1] and the shard's [time_min, time_max] on first use
+void timeseries_release(aqe_ctx* c);
 
 // plans.hip
 void destroy_plan(aqe_plan* p, bool device_idle = false);  // device_idle: the caller has just synchronised the device

@@ -48,10 +48,12 @@ void free_table(aqe_ctx* c) {
     }
     if (c->sorted_amount) (void)hipFree(c->sorted_amount);
     if (c->sorted_row) (void)hipFree(c->sorted_row);
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < 3; ++k) {
         if (c->keycol[k]) (void)hipFree(c->keycol[k]);
         c->keycol[k] = nullptr;
     }
+    c->time_min = std::numeric_limits<int64_t>::max();
+    c->time_max = std::numeric_limits<int64_t>::min();
     for (auto& kv : c->stride_views) {
         (void)hipFree(kv.second.amount);
         for (int32_t* k : kv.second.keys)
@@ -94,6 +96,7 @@ int alloc_table(aqe_ctx* c, uint64_t n_local, bool keep_aos) {
 // GROUP BY needs the key column as SoA int32 on the device: from the resident 32-byte rows, or — for a table made
 // by aqe_generate_synthetic — from the row number.  Built on first use, kept until the table changes.
 int ensure_keys(aqe_ctx* c, int column) {
+    if (column == kTimeColumn) return ensure_time(c);  // the time offsets ride where a key column does (timeseries.hip)
     const int k = column - 1;
     if (c->keycol[k] || c->n_local == 0) return AQE_OK;
     if (!c->aos && !c->synthetic)
@@ -573,6 +576,7 @@ void aqe_destroy(aqe_ctx* c) {
     histogram_release(c);
     distinct_release(c);
     summary_release(c);
+    timeseries_release(c);
     free_table(c);
     free_ring(c);
     if (c->d_stamps) (void)hipFree(c->d_stamps);

@@ -469,6 +469,37 @@ def sharded_summary(engine, query, vec, all_reduce_sum: Callable, all_reduce_max
         return engine.summary_finish(query, v.data_ptr(), stream)
 
 
+def sharded_time_series(engine, query, spec, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
+    """SUM / AVG / COUNT per time bucket across the ranks of a process group (engine.Engine interface), collective.  The table's
+    timestamp range is agreed in ONE all-reduce MAX of the int64 pair [~tmin, tmax] (engine.time_range; ~t = -t - 1 reverses the
+    order without overflowing; an empty shard contributes the neutral elements), every rank derives the same buckets from it on
+    the host (engine.time_plan: more than 1024 buckets, or a range of 2^31 or more, is refused on every rank alike, before the
+    sweep), bins the part of the sample inside its shard into nbuckets x TIME_BIN sums (aqe_time_buckets_enqueue_bins, under
+    ``key_filter`` when there is one), ONE all-reduce SUM merges them and every rank finishes the same bins — so every rank
+    returns the same list of GroupResult, ``key`` the bucket's start, ascending.
+
+    bins    float64 tensor on the engine's device with room for TIME_BIN * nbuckets doubles (at most TIME_BIN * 1024)
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    import torch
+    from ._native import ERR_INVALID, TIME_BIN, AqeError
+    from .engine import time_plan
+    stream = _stream_for(stream, bins)
+    with _torch_on(stream, bins):
+        lo, hi = engine.time_range()
+        rng = torch.tensor([~int(lo), int(hi)], dtype=torch.int64, device=bins.device)
+        all_reduce_max(rng)
+        tmin, tmax = ~int(rng[0].item()), int(rng[1].item())
+        nbuckets = time_plan(spec, tmin, tmax)[1]
+        if nbuckets == 0:  # an empty table, or a window that holds none of its timestamps
+            raise AqeError(ERR_INVALID, "No samples collected")
+        if bins.numel() < TIME_BIN * nbuckets:
+            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {TIME_BIN * nbuckets} needed")
+        b = bins[: TIME_BIN * nbuckets]
+        engine.time_buckets_enqueue_bins(query, spec, tmin, tmax, b.data_ptr(), stream, key_filter)
+        all_reduce_sum(b)
+        return engine.time_buckets_finish(query, spec, tmin, tmax, b.data_ptr(), stream)
+
+
 def sharded_histogram(engine, query, spec, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
     """HISTOGRAM(amount, B) across the ranks of a process group (engine.Engine interface), collective.  When ``spec`` carries no
     range the ranks agree on the table's amount range first — ONE all-reduce MAX of [-min, max] (engine.quantile_amount_range),

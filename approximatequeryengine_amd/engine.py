@@ -636,6 +636,35 @@ class Engine:
         self._chk(nat.lib().aqe_summary_finish(self._h, C.byref(query), C.c_void_p(dev_vec_ptr), C.c_void_p(stream), C.byref(out)))
         return out
 
+    # -- time buckets (aqe_reduce_time_buckets and its kin): GROUP BY BUCKET(timestamp, W) in one sweep; key_filter may be None --
+    def time_range(self) -> Tuple[int, int]:
+        """(smallest, largest) timestamp of this shard; (INT64_MAX, INT64_MIN) when it holds no row."""
+        lo, hi = C.c_int64(), C.c_int64()
+        self._chk(nat.lib().aqe_time_range(self._h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def time_buckets(self, query: Query, spec: "nat.TimeSpec", key_filter: "Optional[nat.KeyFilter]" = None, max_groups: int = 1024):
+        """SUM / AVG / COUNT per time bucket: list of GroupResult whose ``key`` is the bucket's start, ascending; only buckets with a
+        sampled row inside the window, one nothing of which passes with n == 0."""
+        out = (nat.GroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_reduce_time_buckets(self._h, _filter_ref(key_filter), C.byref(query), C.byref(spec), out, max_groups, C.byref(n)))
+        return list(out[: n.value])
+
+    def time_buckets_enqueue_bins(self, query: Query, spec: "nat.TimeSpec", tmin: int, tmax: int, dev_bins_ptr: int, stream: int = 0,
+                                  key_filter: "Optional[nat.KeyFilter]" = None):
+        """This shard's nbuckets x TIME_BIN doubles over the agreed range [tmin, tmax] into device memory (all-reduce SUM, then
+        time_buckets_finish); nbuckets is time_plan(spec, tmin, tmax)[1]."""
+        self._chk(nat.lib().aqe_time_buckets_enqueue_bins(self._h, _filter_ref(key_filter), C.byref(query), C.byref(spec), int(tmin), int(tmax),
+                                                          C.c_void_p(dev_bins_ptr), C.c_void_p(stream)))
+
+    def time_buckets_finish(self, query: Query, spec: "nat.TimeSpec", tmin: int, tmax: int, dev_bins_ptr: int, stream: int = 0, max_groups: int = 1024):
+        out = (nat.GroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_time_buckets_finish(self._h, C.byref(query), C.byref(spec), int(tmin), int(tmax), C.c_void_p(dev_bins_ptr),
+                                                    C.c_void_p(stream), out, max_groups, C.byref(n)))
+        return list(out[: n.value])
+
     # -- MIN / MAX (aqe_reduce_extremes and its kin): one sweep answers both; key_filter may be None everywhere --
     def reduce_extremes(self, query: Query, key_filter: "Optional[nat.KeyFilter]" = None) -> "nat.ExtremeResult":
         out = nat.ExtremeResult()
@@ -795,6 +824,64 @@ def summary_from_vec(vec: Sequence[float], query: Query, n_global: int, exact: b
     if rc != nat.OK:
         raise nat.AqeError(rc, "confidence_level must lie inside (0, 1)" if not 0.0 < query.confidence_level < 1.0 else "No samples collected")
     return out
+
+
+_I64_MIN, _I64_MAX = -2 ** 63, 2 ** 63 - 1
+
+
+def time_spec(width: int, origin: int = 0, time_between=None) -> "nat.TimeSpec":
+    """aqe_time_spec of buckets ``width`` wide from ``origin``, over the inclusive timestamp window ``time_between`` = (t_lo, t_hi)
+    when given.  ValueError for a width below 1, values that are not int64 integers, or a window with t_lo > t_hi."""
+    def i64(v, what):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"BUCKET: {what} must be an integer, got {v!r}")
+        if not _I64_MIN <= int(v) <= _I64_MAX:
+            raise ValueError(f"BUCKET: {what} {v!r} does not fit int64")
+        return int(v)
+    w = i64(width, "the width")
+    if w < 1:
+        raise ValueError(f"BUCKET: the width must be at least 1, got {width!r}")
+    spec = nat.TimeSpec(w, i64(origin, "the origin"), _I64_MIN, _I64_MAX, 0, 0)
+    if time_between is not None:
+        if len(time_between) != 2:
+            raise ValueError(f"BUCKET: time_between takes (t_lo, t_hi), got {time_between!r}")
+        lo, hi = i64(time_between[0], "t_lo"), i64(time_between[1], "t_hi")
+        if lo > hi:
+            raise ValueError(f"BUCKET: the timestamp window is empty (t_lo {lo} > t_hi {hi})")
+        spec.t_lo, spec.t_hi, spec.has_window = lo, hi, 1
+    return spec
+
+
+def time_bucket(ts: int, spec: "nat.TimeSpec") -> int:
+    """aqe_time_bucket: floor((ts - origin) / width), host only."""
+    return int(nat.lib().aqe_time_bucket(int(ts), C.byref(spec)))
+
+
+def time_plan(spec: "nat.TimeSpec", tmin: int, tmax: int) -> Tuple[int, int]:
+    """aqe_time_plan: (first_bucket, nbuckets) of the timestamp range [tmin, tmax] under ``spec`` (nbuckets == 0: an empty table, or
+    a window that leaves nothing), host only.  Raises AqeError: ERR_UNSUPPORTED for more than 1024 buckets (the message names the
+    count) and for a range of 2^31 or more (it names the span), ERR_INVALID for a malformed spec."""
+    first, n = C.c_int64(), C.c_uint32()
+    rc = nat.lib().aqe_time_plan(C.byref(spec), int(tmin), int(tmax), C.byref(first), C.byref(n))
+    if rc == nat.ERR_UNSUPPORTED and n.value:
+        raise nat.AqeError(rc, f"BUCKET: {n.value} buckets of width {spec.width}, more than {nat.TIME_MAX_BUCKETS}: take a wider bucket or a narrower window")
+    if rc == nat.ERR_UNSUPPORTED:
+        raise nat.AqeError(rc, f"BUCKET: the table's timestamps span {int(tmax) - int(tmin)} (tmax - tmin), 2^31 or more: the time column is kept as int32 offsets")
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "BUCKET: the width must be at least 1 and the window must have t_lo <= t_hi")
+    return first.value, n.value
+
+
+def parse_time_where(query: str, spec: "Optional[nat.TimeSpec]" = None):
+    """aqe_parse_time_where: the ``timestamp`` terms of the query's WHERE clause as the inclusive window (t_lo, t_hi) — a side
+    without a bound is INT64_MIN / INT64_MAX — or None when the clause does not name timestamp; with ``spec`` the window is also
+    written into it.  ValueError, quoting the term, for OR, another form, or a second bound on one side."""
+    sp = spec if spec is not None else nat.TimeSpec(1, 0, 0, 0, 0, 0)
+    err = C.create_string_buffer(512)
+    rc = nat.lib().aqe_parse_time_where(query.encode(), C.byref(sp), err, len(err))
+    if rc < 0:
+        raise ValueError(err.value.decode() or "unsupported timestamp predicate")
+    return (sp.t_lo, sp.t_hi) if rc else None
 
 
 def histogram_spec(bins: int, range=None) -> "nat.HistogramSpec":

@@ -363,6 +363,16 @@ class ShardedBPlusDB(CustomBPlusDB):
             return sharded_summary(self._engine, q, self._buffer(nat.SUMMARY_VEC), self._ar_sum, self._ar_max, stream=self._side.cuda_stream,
                                    key_filter=f)
 
+    # ---- time buckets: one all-reduce MAX of the timestamp range, one all-reduce SUM of nbuckets x 4 sums; approx_time_series is
+    # CustomBPlusDB's own, over this ----
+    def _time_series(self, f, q, spec):
+        import torch
+        from .distributed import sharded_time_series
+        self._eng()
+        with torch.cuda.stream(self._side):
+            bins = self._buffer(nat.TIME_BIN * nat.TIME_MAX_BUCKETS)
+            return sharded_time_series(self._engine, q, spec, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)
+
     # ---- HISTOGRAM: one all-reduce MAX for the range when the caller gives none, one all-reduce SUM of the counts;
     # approx_histogram is CustomBPlusDB's own, over this ----
     def _histogram(self, f, q, spec):

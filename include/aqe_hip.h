@@ -1130,6 +1130,70 @@ AQE_API int aqe_summary_finish(aqe_ctx* ctx, const aqe_query* q, const double* d
  * outside (0, 1). */
 AQE_API int aqe_summary_from_vec(const double vec[AQE_SUMMARY_VEC], const aqe_query* q, uint64_t n_global, int exact, aqe_summary_result* out);
 
+/* ---- time buckets: SUM / AVG / COUNT ... GROUP BY BUCKET(timestamp, W) in one sweep (timeseries.hip) ------------------------
+ * A time spec is {width >= 1, origin, optional inclusive window [t_lo, t_hi]}, all int64.  bucket(ts) = floor((ts - origin) /
+ * width) — floor division, also for negative values — and a bucket is reported by its start, origin + b * width.  With
+ * [tmin, tmax] the table's timestamp range (agreed over shards) intersected with the window, the buckets are bucket(tmin) ..
+ * bucket(tmax): more than 1024 of them is AQE_ERR_UNSUPPORTED with the count in the message, and so is a table whose range
+ * tmax - tmin is 2^31 or more, with the span in the message (the sweep reads each row's time as an int32 offset from the
+ * shard's smallest timestamp); nothing is truncated.
+ *
+ * Rows.  A sampled row outside the window counts into no bucket: it is in neither n nor visited.  A row inside counts into
+ * its bucket's `visited`, and into `n` and the sums when it also passes the inclusive amount range (aqe_query.has_where) and
+ * the key term.  `filter` (NULL: none, in every entry) may carry a term on ONE key column; terms on both are
+ * AQE_ERR_UNSUPPORTED.  Per bucket SUM / AVG / COUNT and the interval are those of aqe_reduce_grouped on {n, P1 = sum(x - c),
+ * P2 = sum (x - c)^2, visited} (c the shift of the query): value and half-width scaled by 100 / pct for SUM, no interval for
+ * COUNT or when n < 2.  Results are aqe_group_result with `key` the bucket's start, ascending; only buckets with visited > 0
+ * are listed, a bucket none of whose rows pass with n == 0; visited == 0 over all buckets is AQE_ERR_INVALID "No samples
+ * collected".  Samplers, row windows and refusals are those of aqe_reduce_extremes' ungrouped form: the single-round family
+ * samplers and the seeded AQE_M_RANDOM_POINTER (through its index list); CLT, adaptive, stratified, AQE_M_RANDOM_DEVICE and
+ * pair-family samplers are AQE_ERR_UNSUPPORTED by name.  Needs the rows' timestamps (AQE_STAGE_KEEP_AOS, or a synthetic
+ * table, whose timestamp is the row number).
+ *
+ * The sweep (k_time_buckets) reads 8 + 4 bytes per sampled row (+ 4 under a key term).  Each lane keeps the sums of its
+ * current bucket in registers and adds them to the workgroup's LDS bins only when the bucket changes; the workgroups' bins
+ * are summed per word in a fixed order.  Counts are exact; the floating-point sums of a bucket are reproducible to rounding,
+ * as those of aqe_reduce_grouped.  No floating-point atomics on device memory. */
+typedef struct aqe_time_spec {
+    int64_t width;      /* bucket width, >= 1                                 */
+    int64_t origin;     /* bucket b starts at origin + b * width              */
+    int64_t t_lo, t_hi; /* the inclusive window, read when has_window != 0    */
+    int32_t has_window;
+    int32_t reserved;
+} aqe_time_spec;
+/* This shard's timestamp range (built with the time column on first use, kept until the table changes); an empty shard gives
+ * INT64_MAX / INT64_MIN, the neutral elements of MIN / MAX. */
+AQE_API int aqe_time_range(aqe_ctx* ctx, int64_t* tmin, int64_t* tmax);
+/* Host only, no GPU.  aqe_time_bucket: floor((ts - origin) / width), saturated to int64 (0 for a null spec or width < 1).
+ * aqe_time_plan: the buckets of the range [tmin, tmax] under the spec — *first_bucket and *nbuckets (0 when tmin > tmax or the
+ * window leaves nothing).  AQE_ERR_INVALID: width < 1 or t_lo > t_hi.  AQE_ERR_UNSUPPORTED: tmax - tmin >= 2^31 (*nbuckets
+ * is then 0), or more than 1024 buckets (*nbuckets then holds the count, so that a caller can name it). */
+AQE_API int64_t aqe_time_bucket(int64_t ts, const aqe_time_spec* spec);
+AQE_API int aqe_time_plan(const aqe_time_spec* spec, int64_t tmin, int64_t tmax, int64_t* first_bucket, uint32_t* nbuckets);
+/* Host only, no GPU: the `timestamp` terms of a query's WHERE clause into spec->has_window / t_lo / t_hi (width and origin are
+ * left as they are).  Terms: timestamp BETWEEN a AND b | = a | >= a | > a | <= a | < a with int64 literals, joined by AND with
+ * each other and with terms on other columns (which are skipped); at most one lower and one upper bound.  Returns 1 when the
+ * clause names timestamp, 0 when it does not (has_window = 0), AQE_ERR_INVALID for OR, any other form, or a second bound on one
+ * side; err (optional, err_cap bytes) then receives a message that quotes the term.  A side without a bound is INT64_MIN /
+ * INT64_MAX. */
+AQE_API int aqe_parse_time_where(const char* query, aqe_time_spec* spec, char* err, size_t err_cap);
+/* Single GPU, synchronous: the sweep, then one launch that sums the workgroups' bins and writes every bucket's result into
+ * pinned memory. */
+AQE_API int aqe_reduce_time_buckets(aqe_ctx* ctx, const aqe_key_filter* filter /* NULL: none */, const aqe_query* q, const aqe_time_spec* spec,
+                                    aqe_group_result* out, uint32_t cap, uint32_t* n_groups);
+/* Multi-GPU:
+ *     aqe_time_range(ctx, &tmin, &tmax)                          all-reduce MIN / MAX them
+ *     aqe_time_plan(spec, tmin, tmax, &first, &nbuckets)         host only: the same buckets on every rank
+ *     aqe_time_buckets_enqueue_bins(ctx, filter, q, spec, tmin, tmax, dev_bins, stream)   nbuckets x 4 doubles:
+ *                                                                {n, P1, P2, visited} per bucket (zeros from an empty shard)
+ *     <ONE all-reduce SUM of nbuckets * 4 doubles on `stream`>
+ *     aqe_time_buckets_finish(ctx, q, spec, tmin, tmax, dev_bins, stream, out, cap, &n_groups)     synchronises `stream`
+ * Every rank finishes the same bins.  A shard with timestamps outside [tmin, tmax] is AQE_ERR_INVALID. */
+AQE_API int aqe_time_buckets_enqueue_bins(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const aqe_time_spec* spec, int64_t tmin,
+                                          int64_t tmax, double* dev_bins, void* stream);
+AQE_API int aqe_time_buckets_finish(aqe_ctx* ctx, const aqe_query* q, const aqe_time_spec* spec, int64_t tmin, int64_t tmax, const double* dev_bins,
+                                    void* stream, aqe_group_result* out, uint32_t cap, uint32_t* n_groups);
+
 #ifdef __cplusplus
 }
 #endif
