@@ -10,6 +10,7 @@ from .build import LIB, build_native
 
 # ---- enums of include/aqe_hip.h ------------------------------------------------------------------
 OK, ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_NO_TABLE, ERR_IO, ERR_CAPACITY, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6, -7
+ERR_INTERNAL = -8
 
 M_EXACT, M_MEMORY_STRIDE, M_ADDRESS_ARITHMETIC, M_RANDOM_POINTER, M_BLOCK, M_PAGE, M_PARALLEL_BLOCK = range(7)
 M_OPTIMIZED_CLT, M_CLT_DUAL_POINTER, M_FAST_POINTER, M_SLOW_POINTER, M_DUAL_POINTER = 7, 8, 9, 10, 11
@@ -64,6 +65,7 @@ DISTINCT_SKETCH, DISTINCT_EXACT_KEYS = 0, 1
 DISTINCT_VEC_HEAD, DISTINCT_SLOTS = 2, 8192  # [visited, n] for a SUM all-reduce, then slot[0 .. 8192) for a MAX all-reduce
 SUMMARY_VEC, SUMMARY_VEC_SUM = 12, 10  # the SPREAD_VEC layout + {0, 0} for a SUM all-reduce, then {-min, max} for a MAX all-reduce
 TIME_BIN, TIME_MAX_BUCKETS, TIME_MAX_SPAN = 4, 1024, 2 ** 31 - 1  # {n, P1, P2, visited} per time bucket; the limits of aqe_time_plan
+WIDE_BIN, WIDE_MAX_BINS, WIDE_SLICE_DEFAULT = 4, 65536, 2048  # {n, P1, P2, visited} per bin of the wide GROUP BY; the bound and default slice of aqe_wide_plan
 KEYTERM_NONE, KEYTERM_RANGE, KEYTERM_BITMAP = 0, 1, 2
 KEY_BITMAP_BITS = 1024
 
@@ -371,6 +373,10 @@ def lib() -> C.CDLL:
         "aqe_reduce_time_buckets": (C.c_int, [vp, P(KeyFilter), P(Query), P(TimeSpec), P(GroupResult), u32, P(u32)]),
         "aqe_time_buckets_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), P(TimeSpec), C.c_int64, C.c_int64, vp, vp]),
         "aqe_time_buckets_finish": (C.c_int, [vp, P(Query), P(TimeSpec), C.c_int64, C.c_int64, vp, vp, P(GroupResult), u32, P(u32)]),
+        "aqe_wide_plan": (C.c_int, [P(u32), C.c_int, u32, P(u32), P(u32)]),
+        "aqe_reduce_grouped_wide": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), C.c_int, P(GroupResult), u32, P(u32)]),
+        "aqe_grouped_wide_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), C.c_int, P(i32), P(u32), vp, vp]),
+        "aqe_grouped_wide_finish": (C.c_int, [vp, P(Query), C.c_int, P(i32), P(u32), vp, vp, P(GroupResult), u32, P(u32)]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),

@@ -30,7 +30,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as nat
-from .engine import RECORD_DTYPE, Engine, histogram_spec, key_filter_terms, make_key_filter, make_query, time_spec
+from .engine import RECORD_DTYPE, Engine, histogram_spec, key_filter_terms, make_key_filter, make_query, time_spec, wide_plan
 
 __all__ = ["Record", "CustomBPlusDB", "CustomApproximateScheduler", "CustomValidationResult",
            "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate", "SpreadEstimate", "SummaryEstimate", "BucketEstimate"]
@@ -400,6 +400,19 @@ def group_columns(group_by) -> Tuple[int, ...]:
 def _pair_groups(results, make):
     """The mapping of a pair's results: "a,b" in the order the columns were named -> estimate, ascending by (a, b)."""
     return {"%d,%d" % nat.group_key_unpack(r.key): make(r) for r in results}
+
+
+def _wide_groups_arg(max_groups, combined_with=None) -> bool:
+    """The ``max_groups`` argument of the grouped methods, checked before anything is launched: True when it asks for the wide
+    GROUP BY (above 1024, at most 65 536).  ``combined_with`` names what the wide form does not combine with."""
+    if isinstance(max_groups, bool) or not isinstance(max_groups, (int, np.integer)) or max_groups < 1:
+        raise ValueError(f"max_groups must be a positive integer, got {max_groups!r}")
+    if max_groups > nat.WIDE_MAX_BINS:
+        raise ValueError(f"max_groups={max_groups} is more than the {nat.WIDE_MAX_BINS} groups a GROUP BY can hold")
+    if max_groups > 1024 and combined_with is not None:
+        raise ValueError(f"max_groups={max_groups} with {combined_with}: GROUP BY over more than 1024 groups answers SUM, AVG and COUNT "
+                         f"at one sample percentage only ({combined_with} stops at 1024 groups)")
+    return max_groups > 1024
 
 
 def _records(arr: np.ndarray) -> List[Record]:
@@ -800,7 +813,7 @@ class CustomBPlusDB:
     def approx_group_by(self, agg: str, group_by: str = "region", sample_percent: Optional[float] = None, method: Optional[str] = None,
                         where: Optional[Tuple[float, float]] = None, block_size: int = 1000,
                         key_where: Optional[dict] = None, error_percent: Optional[float] = None,
-                        max_percent: float = 100.0) -> "dict[str, GroupEstimate]":
+                        max_percent: float = 100.0, max_groups: int = 1024) -> "dict[str, GroupEstimate]":
         """APPROX <agg>(amount) ... GROUP BY region | product_id with a 95 % interval per group: the reference's
         execute_query_groupby_with_ci (executor.cpp:202-321; GroupResultWithCI = map<string, {value, ci_lower,
         ci_upper}>) in one sweep.  method "rowid" is that function's own sample (rowid % (100 / sample_percent) == 0);
@@ -815,9 +828,14 @@ class CustomBPlusDB:
         n >= 30 and a half-width within error_percent % of its value, or the level of ``max_percent`` (default 100: the exact
         scan) is reached.  ``method`` must be left out or be "block".  Same mapping; where the query stopped — level, levels,
         sample_percent reached, visited rows, converged, unsettled groups, the widest group's key ("a,b" for a pair) and ratio —
-        is kept as the dictionary ``last_group_error_info``."""
+        is kept as the dictionary ``last_group_error_info``.
+
+        ``max_groups`` (default 1024: today's routing and refusals): above 1024, at most 65 536, SUM / AVG / COUNT over key ranges
+        that span more than 1024 bins go through the sliced sweep (aqe_reduce_grouped_wide) instead of being refused; it does
+        not combine with ``error_percent``."""
         cols = group_columns(group_by)
         col = cols[0]
+        wide = _wide_groups_arg(max_groups, "error_percent" if error_percent is not None else None)
         if error_percent is not None:
             return self._group_by_error(agg, cols, sample_percent, method, where, block_size, key_where, error_percent, max_percent)
         sample_percent = 10.0 if sample_percent is None else sample_percent
@@ -827,6 +845,11 @@ class CustomBPlusDB:
             return {}
         bs = 4096 if (method == "page" and block_size == 1000) else block_size
         q = make_query(m, sample_percent, agg=_AGG[agg.upper()], where=where, block_size=int(bs))
+        if wide:
+            f = None if key_where is None else _key_filter_for(key_where, method)
+            groups = _quantile_call(lambda: self._grouped_wide(f, q, cols, int(max_groups)))
+            if groups is not None:  # (None: the spans fit 1024 bins — today's routing)
+                return _pair_groups(groups, GroupEstimate) if len(cols) == 2 else {str(r.key): GroupEstimate(r) for r in groups}
         if len(cols) == 2:
             f = None if key_where is None else _key_filter_for(key_where, method)
             return _pair_groups(_quantile_call(lambda: self._grouped_pair(f, q, cols)), GroupEstimate)
@@ -882,6 +905,19 @@ class CustomBPlusDB:
     def _grouped_pair(self, f, q, cols):
         return self._eng().reduce_grouped_pair(q, cols, f)
 
+    def _grouped_wide(self, f, q, cols, max_groups):
+        """The groups through the sliced sweep when the key ranges span more than 1024 bins; None when they do not."""
+        eng = self._eng()
+        span = []
+        for c in cols:
+            lo, hi = eng.group_key_range(c)
+            if hi < lo:
+                return None
+            span.append(hi - lo + 1)
+        if wide_plan(span)[0] <= 1024:
+            return None
+        return eng.reduce_grouped_wide(q, cols, f, max_groups)
+
     def _spread_groups_pair(self, f, q, kind, cols):
         return self._eng().reduce_grouped_pair_spread(q, kind, cols, f)
 
@@ -930,7 +966,7 @@ class CustomBPlusDB:
     def approx_spread(self, kind: str = "var_samp", method: str = "stride", sample_percent: float = 10.0,
                       where: Optional[Tuple[float, float]] = None, id_between: Optional[Tuple[int, int]] = None, seed: int = 42,
                       confidence_level: float = 0.95, group_by: Optional[str] = None, num_threads: int = 4, block_size: int = 1000,
-                      key_where: Optional[dict] = None):
+                      key_where: Optional[dict] = None, max_groups: int = 1024):
         """APPROX VARIANCE / STDDEV(amount): ``kind`` is "var_samp" ("variance"), "var_pop", "stddev_samp" ("stddev") or
         "stddev_pop" of the sampled amounts X (WHERE and the key window applied) — numpy.var(X, ddof=1) and its kin, not scaled
         by the sampling fraction — with a large-sample normal interval from the fourth central moment; method "exact" reports
@@ -941,6 +977,7 @@ class CustomBPlusDB:
         k = str(kind).strip().lower()
         if k not in _SPREAD_KINDS:
             raise ValueError(f"kind must be one of {sorted(_SPREAD_KINDS)}")
+        _wide_groups_arg(max_groups, "VARIANCE / STDDEV")
         if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
             raise ValueError(f"VARIANCE / STDDEV do not take the {method} sampler (single-round family samplers and 'random' only)")
         f = None if key_where is None else _key_filter_for(key_where, method)
@@ -989,7 +1026,8 @@ class CustomBPlusDB:
 
     def approx_extremes(self, method: str = "stride", sample_percent: float = 10.0, where: Optional[Tuple[float, float]] = None,
                         id_between: Optional[Tuple[int, int]] = None, seed: int = 42, confidence_level: float = 0.95,
-                        group_by: Optional[str] = None, num_threads: int = 4, block_size: int = 1000, key_where: Optional[dict] = None):
+                        group_by: Optional[str] = None, num_threads: int = 4, block_size: int = 1000, key_where: Optional[dict] = None,
+                        max_groups: int = 1024):
         """APPROX MIN / MAX(amount): numpy.min(X) and numpy.max(X) of the sampled amounts X (WHERE, the key window and
         ``key_where`` applied, NaN rows left out) from ONE sweep, as an ExtremeEstimate.  A sample's extreme bounds the table's
         from one side only: ``tail_fraction`` says how much of the qualifying rows may lie beyond it at ``confidence_level``
@@ -997,6 +1035,7 @@ class CustomBPlusDB:
         "random", "rowid" ...; CLT, adaptive, stratified and random_device samplers raise ValueError).  With ``group_by``
         ("region" | "product_id", or both as approx_group_by takes them) the result is the key -> ExtremeEstimate mapping
         approx_group_by returns.  There is no error-threshold form."""
+        _wide_groups_arg(max_groups, "MIN / MAX")
         if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
             raise ValueError(f"MIN / MAX do not take the {method} sampler (single-round family samplers and 'random' only)")
         if not 0.0 < float(confidence_level) < 1.0:

@@ -11,6 +11,7 @@
     python -m approximatequeryengine_amd.cli "SELECT region, product_id, AVG(amount) FROM sales GROUP BY region, product_id" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli "SELECT MIN(amount), MAX(amount) FROM sales" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli "SELECT region, MAX(amount) FROM sales WHERE product_id < 50 GROUP BY region" --db sales.db --s 10
+    python -m approximatequeryengine_amd.cli "SELECT product_id, SUM(amount) FROM sales GROUP BY product_id" --db sales.db --s 10 --max-groups 65536
     python -m approximatequeryengine_amd.cli "SELECT HISTOGRAM(amount, 20) FROM sales WHERE region = 2" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli "SELECT HISTOGRAM(amount, 10, 0, 1000) FROM sales" --db sales.db --s 10 --compare
     python -m approximatequeryengine_amd.cli "SELECT COUNT(DISTINCT product_id) FROM sales WHERE region = 2" --db sales.db --s 10 --ci
@@ -323,6 +324,28 @@ def get_optimal_method_for_query(query: str, dataset_size: Optional[int] = None)
     return "adaptive"
 
 
+MAX_GROUPS_SHOWN = 50  # groups printed under --max-groups unless --all-groups is given
+
+
+def max_groups_defect(clean: str, args):
+    """What keeps a query given --max-groups from running, found before the table is opened (None: nothing, or no --max-groups):
+    a value outside 1 .. 65536, --e, VARIANCE / STDDEV, MIN / MAX or a time bucket — the forms that stop at 1024 groups."""
+    mg = getattr(args, "max_groups", None)
+    if mg is None:
+        return None
+    if not 1 <= mg <= 65536:
+        return f"--max-groups {mg}: a GROUP BY holds 1 .. 65536 groups"
+    if args.e is not None:
+        return "--max-groups has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"
+    if spread_of(clean) is not None:
+        return "--max-groups has no VARIANCE / STDDEV form: GROUP BY over more than 1024 groups takes SUM, AVG or COUNT"
+    if extreme_of(clean) is not None:
+        return "--max-groups has no MIN / MAX form: GROUP BY over more than 1024 groups takes SUM, AVG or COUNT"
+    if re.search(r"BUCKET\s*\(", clean, flags=re.IGNORECASE):
+        return "--max-groups has no GROUP BY BUCKET(...) form: time buckets stop at 1024 buckets"
+    return None
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV, MIN/MAX, HISTOGRAM, COUNT(DISTINCT), SUMMARY on MI355X "
                                 "(e.g. \"SELECT HISTOGRAM(amount, 20) FROM sales\" --s 10 --ci; \"SELECT SUMMARY(amount) FROM sales\" --s 10 --ci)",
@@ -338,6 +361,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--confidence", type=float, default=0.95)
     p.add_argument("--ci", action="store_true", help="print the confidence interval")
     p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--max-groups", dest="max_groups", type=int, metavar="N", help="SUM / AVG / COUNT ... GROUP BY over key ranges of up to N groups "
+                   "(above 1024, at most 65536: the sliced sweep); without it GROUP BY stops at 1024 groups")
+    p.add_argument("--all-groups", dest="all_groups", action="store_true", help="with --max-groups: print every group (default: the first 50 and a count of the rest)")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="under torchrun (one process per GPU): the torch.distributed backend (nccl = RCCL)")
     p.add_argument("--collective", choices=["torch", "mailbox"], default="torch", help="under torchrun: the all-reduce of the moment vectors "
@@ -354,6 +380,10 @@ def run(args, out=sys.stdout) -> int:
         print("error: a query is required unless --explain is given", file=out)
         return 2
     clean, _ = parse_embedded_approx(args.query)
+    why = max_groups_defect(clean, args)
+    if why is not None:
+        print(f"error: {why}", file=out)
+        return 2
     try:
         bucket = time_bucket_of(clean)  # before group_by_of: the comma inside the parentheses never reaches that function's split
     except ValueError as e:
@@ -533,11 +563,17 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
         return 0
     if gb:  # one sweep, one bin per key (or per pair of keys), an interval per group (executor.cpp:202-321 semantics)
         pct = args.s if args.s is not None else (100.0 if qtype == QUERY_EXACT else 10.0)
+        mg = getattr(args, "max_groups", None)
+        gkw = dict(kw) if mg is None else dict(kw, max_groups=mg)  # (passed only when the option is given)
         groups = db.approx_group_by(agg, group_by=", ".join(gb), sample_percent=pct, method="exact" if pct >= 100.0 else "rowid",
-                                    where=aqe_backend.parse_where(clean), **kw)
+                                    where=aqe_backend.parse_where(clean), **gkw)
         ms = (time.perf_counter() - t0) * 1e3
         print(f"\nGROUP BY {', '.join(gb).lower()} ({'exact' if pct >= 100.0 else f'rowid sample {pct:g}%'}):", file=out)
-        for key, g in groups.items():
+        shown = len(groups) if (mg is None or getattr(args, "all_groups", False)) else MAX_GROUPS_SHOWN
+        for i, (key, g) in enumerate(groups.items()):
+            if i >= shown:
+                print(f"   ... and {len(groups) - shown:,} more groups ({len(groups):,} in all; --all-groups prints every one)", file=out)
+                break
             ci = f"   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})" if (args.ci and pct < 100.0) else ""
             print(f"   {key:>6}: {g.value:,.4f}{ci}   n={g.n:,}", file=out)
         print(f"   execution time: {ms:.2f} ms", file=out)

@@ -19,6 +19,7 @@ const char* aqe_status_string(int s) {
         case AQE_ERR_IO: return "I/O error";
         case AQE_ERR_CAPACITY: return "output buffer too small";
         case AQE_ERR_UNSUPPORTED: return "unsupported";
+        case AQE_ERR_INTERNAL: return "internal error";
         default: return "unknown status";
     }
 }

@@ -103,6 +103,7 @@ struct aqe_histogram_scratch;  // histogram.hip
 struct aqe_distinct_scratch;  // distinct.hip
 struct aqe_summary_scratch;  // summary.hip
 struct aqe_time_scratch;  // timeseries.hip
+struct aqe_wide_scratch;  // wide_group.hip
 
 struct aqe_ctx {
     StageRing ring;
@@ -178,6 +179,8 @@ struct aqe_ctx {
     aqe_summary_scratch* summary = nullptr;
     // time buckets (timeseries.hip): the workgroups' bins, the summed bins and the pinned groups, made on first use
     aqe_time_scratch* timeseries = nullptr;
+    // GROUP BY over wide key ranges (wide_group.hip): the slices' partials, the summed bins and the result list, made on first use
+    aqe_wide_scratch* wide = nullptr;
     // diagnostics (aqe_last_load_policy): the instantiation the most recent launch of a visit_tile kernel was — 1 non-temporal,
     // 0 plain loads, -1 no such launch yet.  Index-list sweeps and the quantile pass have the plain one only.
     int last_nt = -1;
@@ -367,6 +370,9 @@ void summary_release(aqe_ctx* c);
 constexpr int kTimeColumn = 3;
 int ensure_time(aqe_ctx* c);  // builds keycol[kTimeColumn - 1] and the shard's [time_min, time_max] on first use
 void timeseries_release(aqe_ctx* c);
+
+// wide_group.hip
+void wide_release(aqe_ctx* c);
 
 // plans.hip
 void destroy_plan(aqe_plan* p, bool device_idle = false);  // device_idle: the caller has just synchronised the device

@@ -1,0 +1,612 @@
+// wide_group.hip — GROUP BY over wide key ranges: SUM / AVG / COUNT per group for up to kMaxWideBins = 65 536 bins, and the
+// entry points it answers (aqe_reduce_grouped_wide and its kin; contract in include/aqe_hip.h).
+//
+// Every other grouped sweep bins a sampled row into one workgroup's LDS, which holds at most kMaxGroupBins = 1024 bins.  Here
+// the bin range is cut into SLICES that fit LDS, and each slice's workgroups sweep the sampled rows again: the grid is
+// two-dimensional, blockIdx.y the slice and blockIdx.x the workgroup's share of the tiles.  A sampled sweep is small (10 % of
+// 10 M rows is 12 MB), so the repeats are served by the L2 and the Infinity Cache.  A row of another slice costs its loads and
+// one compare.
+//
+// The row loop is the one the other sweeps share: visit_tile of device_common.hpp with NK = 1 or 2 key columns beside the
+// amount (the seeded random sampler through its host-built index list).  A bin is four doubles {n, P1, P2, visited}, the layout
+// of timeseries.hip's bins, counts as whole doubles; a row adds to its bin with LDS atomics (ds_add_f64).  Workgroups write
+// [slice][blockIdx.x][slice_bins][4] partials with 16-byte stores; k_wide_bins_sum adds the gridDim.x partials of every word
+// in workgroup order (k_time_bins_sum's walk) into dev_bins[nbins][4] — what ranks all-reduce — and k_wide_finish works every
+// group out and compacts the groups with visited > 0 in ascending key order (a block-wide prefix over flags behind
+// per-workgroup offsets from a counting pass: no atomics, which would reorder the list).  Counts are exact; the floating-point
+// sums of a group are reproducible to rounding, as those of aqe_reduce_grouped.  No floating-point atomics on device memory.
+#include <cstddef>
+#include <string>
+
+#include "device_common.hpp"
+#include "host.hpp"
+#include "key_term.hpp"
+#include "sweep_host.hpp"
+
+namespace aqe {
+namespace {
+
+constexpr unsigned kMaxWideBins = 65536;
+constexpr unsigned kWideBin = 4;           // {n, P1, P2, visited}: aqe_grouped_enqueue_bins' layout
+constexpr unsigned kWideMinSlice = 64, kWideMaxSlice = 4096;
+// The slice a call takes unless AQE_WIDE_SLICE forces one: 2048 bins are 64 KiB of LDS, two workgroups per CU.  Measured
+// (profiles/wide_group_time.txt, 10 M rows): at 65 536 keys the exact scan takes 811 / 525 / 551 us with 1024 / 2048 / 4096 bins
+// per slice, rowid 10 % 109 / 81 / 103 us; 2048 is the fastest or within its min - max span of the fastest from 4 096 keys on.
+constexpr unsigned kWideSliceDefault = 2048;
+// Workgroups of a launch over all slices, which sets gridDim.x per slice (same file): ceil(1024 / nslices) is at or near the best
+// forced value from 8 slices on; at 2 slices the exact scan would gain 14 % from 128 workgroups per slice (fewer partial stores).
+constexpr unsigned kWideTargetBlocks = 1024;
+constexpr unsigned kFinishThreads = 256;
+static_assert(kWideMaxSlice * kWideBin * 8 == 128 * 1024, "the largest slice is 128 KiB of LDS");
+static_assert(kWideMinSlice % 16 == 0, "64 consecutive words of the bins lie in one slice");
+
+struct WideLaunch {
+    SweepCommon sw;
+    u64 ntiles;
+    const uint64_t* idx;     // the seeded random sampler: global rows (else null)
+    u64 n_idx;
+    const int32_t* keys[2];  // [0]: the group column (a pair: column A), [1]: column B, or the other column under a term
+    double* partial;         // [gridDim.y][gridDim.x][slice_bins][4]
+    int32_t key_min;         // column A
+    uint32_t span_a;
+    int32_t key_min_b;       // a pair: column B's smallest key and span; else 0 and 1
+    uint32_t span_b;
+    uint32_t slice_bins;
+    uint32_t pair;
+    DevFilter flt;           // t[0] judges keys[0], t[1] keys[1] (pass-all without a term)
+};
+static_assert(sizeof(WideLaunch) <= 4096, "kernel arguments are limited to 4 KB");
+
+// Estimate and interval of one group from its sums: group_result of grouped.hip (executor.cpp:277-296), restated here because
+// that one lives in its translation unit.
+__device__ __forceinline__ aqe_group_result wide_result(double n, double sd, double qd, double visited, int64_t key, double c, double pct, int agg) {
+    aqe_group_result r;
+    r.key = key;
+    r.n = static_cast<uint64_t>(n);
+    r.visited = static_cast<uint64_t>(visited);
+    r.sum = sd + n * c;
+    r.sumsq = qd + 2.0 * c * sd + n * c * c;
+    double mean = 0.0, m2 = 0.0;
+    if (n > 0.0) mean_m2(n, sd, qd, c, mean, m2);
+    r.mean = mean;
+    const double scale = 100.0 / pct;
+    double margin = 0.0;
+    if (n >= 2.0) margin = 1.96 * sqrt((m2 / (n - 1.0)) / n);
+    double value;
+    if (agg == AQE_SUM) { value = r.sum * scale; margin *= scale; }
+    else if (agg == AQE_AVG) { value = mean; }
+    else { value = n * scale; margin = 0.0; }
+    r.value = value;
+    r.ci_lower = value - margin;
+    r.ci_upper = value + margin;
+    return r;
+}
+
+template <bool kNT, int NK>
+__global__ __launch_bounds__(kBlockThreads) void k_group_wide(WideLaunch a) {
+    static_assert(NK == 1 || NK == 2, "the group column, and the second column of a pair or under a term");
+    extern __shared__ __attribute__((aligned(16))) double wbins[];  // [slice_bins][4]
+    __shared__ DevFamily lds_fams[kMaxLdsFams];
+    __shared__ u64 s_map[2][kMapWords];
+    const unsigned sb = a.slice_bins, tid = threadIdx.x;
+    const int lane = tid & 63;
+    for (unsigned i = tid; i < sb * kWideBin; i += kBlockThreads) wbins[i] = 0.0;
+    stage_maps<WideLaunch>(s_map);  // (ends with a barrier)
+    const bool has_where = a.sw.has_where != 0;
+    const double c = a.sw.shift, wmin = a.sw.wmin, wmax = a.sw.wmax;
+    const int kmin = a.key_min, kmin_b = a.key_min_b;
+    const unsigned span_a = a.span_a, span_b = a.span_b;
+    const bool pair = NK >= 2 && a.pair != 0;
+    const unsigned slice_lo = blockIdx.y * sb;
+    const DevTerm T0 = a.flt.t[0], T1 = a.flt.t[1];
+    auto visit = [&](double x, int key, int other, bool ok) {
+        const unsigned ba = static_cast<unsigned>(key - kmin);
+        const unsigned bb = pair ? static_cast<unsigned>(other - kmin_b) : 0u;
+        const bool in = ok && ba < span_a && bb < span_b;  // (the host checked the shard's key ranges: a sampled row is inside)
+        const unsigned rel = ba * span_b + bb - slice_lo;  // in: the bin is below 65 536, no wrap
+        if (!in || rel >= sb) return;                      // a row of another slice
+        bool pass = !has_where || (x >= wmin && x <= wmax);  // inclusive both ends, as the sums
+        pass = pass && term_pass(T0, s_map[0], key);
+        if (NK >= 2) pass = pass && term_pass(T1, s_map[1], other);
+        double* const w = wbins + rel * kWideBin;
+        __hip_atomic_fetch_add(w + 3, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (pass) {
+            const double d = x - c;
+            __hip_atomic_fetch_add(w + 0, 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(w + 1, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(w + 2, d * d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    };
+    if (a.idx) {
+        constexpr u64 kChunk = static_cast<u64>(kBlockThreads) * kTileUnroll;
+        for (u64 c0 = static_cast<u64>(blockIdx.x) * kChunk; c0 < a.n_idx; c0 += static_cast<u64>(gridDim.x) * kChunk) {
+            u64 off[kTileUnroll];
+            bool ok[kTileUnroll];
+#pragma unroll
+            for (int k = 0; k < kTileUnroll; ++k) {
+                const u64 i = c0 + tid + static_cast<u64>(k) * kBlockThreads;
+                ok[k] = i < a.n_idx;
+                const u64 row = a.idx[ok[k] ? i : 0];
+                off[k] = ok[k] ? row - a.sw.shard_lo : 0;
+            }
+            double v[kTileUnroll];
+            int ka[kTileUnroll], kb[kTileUnroll];
+#pragma unroll
+            for (int k = 0; k < kTileUnroll; ++k) {
+                v[k] = a.sw.amount[off[k]];
+                ka[k] = a.keys[0][off[k]];
+                kb[k] = NK >= 2 ? a.keys[1][off[k]] : 0;
+            }
+#pragma unroll
+            for (int k = 0; k < kTileUnroll; ++k) visit(v[k], ka[k], kb[k], ok[k]);
+        }
+    } else {
+        const DevFamily* fams = stage_families(a.sw, lds_fams);
+        __syncthreads();
+        const u64 wave_id = uniform64(static_cast<u64>(blockIdx.x) * kWavesPerBlock + (tid >> 6));
+        const u64 wave_stride = static_cast<u64>(gridDim.x) * kWavesPerBlock;
+        for (u64 t = wave_id; t < a.ntiles; t += wave_stride) visit_tile<kNT, NK>(a.sw, fams, a.keys[0], a.keys[1], t, lane, visit);
+    }
+    __syncthreads();
+    // the workgroup's bins, whole slice (a short last slice: zeros behind its bins), two words per store
+    double2* const out = reinterpret_cast<double2*>(a.partial + (static_cast<size_t>(blockIdx.y) * gridDim.x + blockIdx.x) * sb * kWideBin);
+    const double2* const mine = reinterpret_cast<const double2*>(wbins);
+    for (unsigned i = tid; i < sb * (kWideBin / 2); i += kBlockThreads) out[i] = mine[i];
+}
+
+// The workgroups' bins summed per word, in a fixed order (k_time_bins_sum's walk): a workgroup takes 64 consecutive words (16
+// bins, which lie in one slice: slice_bins is a multiple of 16, or there is one slice); wave r adds the partials of the
+// workgroups r, r + 4, ... of that slice in that order (64 lanes on 64 consecutive words: one 512-byte line per load), and
+// the four sums are added in wave order.
+__global__ __launch_bounds__(kBlockThreads) void k_wide_bins_sum(const double* __restrict__ partial, unsigned nblocks, unsigned slice_bins, unsigned nwords,
+                                                                 double* __restrict__ out) {
+    __shared__ double part[kWavesPerBlock][64];
+    const unsigned j = threadIdx.x & 63u, r = threadIdx.x >> 6, word = blockIdx.x * 64u + j;
+    const unsigned slice_words = slice_bins * kWideBin;
+    const unsigned slice = (blockIdx.x * 64u) / slice_words, within = word - slice * slice_words;
+    double t = 0.0;
+    if (word < nwords) {
+        const double* const p = partial + static_cast<size_t>(slice) * nblocks * slice_words + within;
+        for (unsigned w = r; w < nblocks; w += kWavesPerBlock) t += p[static_cast<size_t>(w) * slice_words];
+    }
+    part[r][j] = t;
+    __syncthreads();
+    if (r == 0 && word < nwords) {
+        for (unsigned k = 1; k < kWavesPerBlock; ++k) t += part[k][j];
+        out[word] = t;
+    }
+}
+
+// How many of a workgroup's kFinishThreads bins somebody sampled: counts[blockIdx.x].
+__global__ __launch_bounds__(kFinishThreads) void k_wide_count(const double* __restrict__ bins, unsigned nbins, unsigned* __restrict__ counts) {
+    __shared__ unsigned wsum[kFinishThreads / 64];
+    const unsigned b = blockIdx.x * kFinishThreads + threadIdx.x;
+    const bool flag = b < nbins && bins[static_cast<size_t>(b) * kWideBin + 3] > 0.0;
+    const u64 m = __ballot(flag);
+    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = static_cast<unsigned>(__popcll(m));
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0;
+        for (unsigned w = 0; w < kFinishThreads / 64; ++w) t += wsum[w];
+        counts[blockIdx.x] = t;
+    }
+}
+
+struct WideFinish {
+    PairRange g;
+    double shift, pct;
+    int32_t agg, pair;
+};
+
+// One thread per bin: the group's result from its (all-reduced) sums, written at its rank among the bins with visited > 0 —
+// the counts of the workgroups before this one (at most 256 of them: one per thread), then a prefix over this workgroup's
+// flags by ballots.  The last workgroup also writes the number of groups behind the counts.  cap: nothing past it is written.
+__global__ __launch_bounds__(kFinishThreads) void k_wide_finish(const double* __restrict__ bins, unsigned nbins, unsigned* __restrict__ counts, WideFinish fin,
+                                                                aqe_group_result* __restrict__ out, unsigned cap) {
+    __shared__ unsigned wsum[kFinishThreads / 64];
+    __shared__ unsigned before[kFinishThreads / 64];
+    const unsigned tid = threadIdx.x, b = blockIdx.x * kFinishThreads + tid;
+    // integer sums: any order gives the same offset
+    unsigned mine = tid < blockIdx.x ? counts[tid] : 0u;
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+    if ((tid & 63u) == 0) before[tid >> 6] = mine;
+    const double* const v = bins + static_cast<size_t>(b < nbins ? b : 0) * kWideBin;
+    const double n = v[0], sd = v[1], qd = v[2], visited = v[3];
+    const bool flag = b < nbins && visited > 0.0;
+    const u64 m = __ballot(flag);
+    if ((tid & 63u) == 0) wsum[tid >> 6] = static_cast<unsigned>(__popcll(m));
+    __syncthreads();
+    unsigned pos = 0;
+    for (unsigned w = 0; w < kFinishThreads / 64; ++w) pos += before[w];
+    for (unsigned w = 0; w < (tid >> 6); ++w) pos += wsum[w];
+    pos += static_cast<unsigned>(__popcll(m & ((1ull << (tid & 63u)) - 1ull)));
+    if (flag && pos < cap) {
+        const int64_t key = fin.pair ? pair_key(fin.g, b) : static_cast<int64_t>(fin.g.kmin_a) + b;
+        out[pos] = wide_result(n, sd, qd, visited, key, fin.shift, fin.pct, fin.agg);
+    }
+    if (blockIdx.x == gridDim.x - 1 && tid == kFinishThreads - 1) counts[gridDim.x] = pos + (flag ? 1u : 0u);
+}
+
+static_assert(kMaxWideBins / kFinishThreads <= kFinishThreads, "one thread per earlier workgroup's count");
+
+const char* column_name(int column) { return column == AQE_GROUP_REGION ? "region" : "product_id"; }
+
+// The bound and its refusal, in one place: nbins of one column's span (ncols == 1) or of the pair's, and the slices of `slice`
+// bins each.  why: the message of a refusal.
+int wide_plan(const uint32_t* span, int ncols, uint32_t slice, uint32_t* nbins, uint32_t* nslices, std::string* why) {
+    *nbins = *nslices = 0;
+    if (!span || (ncols != 1 && ncols != 2)) { *why = "GROUP BY (wide): one group column or a pair of them"; return AQE_ERR_INVALID; }
+    if (slice == 0) slice = kWideSliceDefault;
+    if (slice < kWideMinSlice || slice > kWideMaxSlice || (slice & (slice - 1)) != 0) {
+        *why = "GROUP BY (wide): slice_bins " + std::to_string(slice) + " is not a power of two in 64 .. 4096";
+        return AQE_ERR_INVALID;
+    }
+    if (span[0] == 0 || (ncols == 2 && span[1] == 0)) { *why = "GROUP BY (wide): a span is zero"; return AQE_ERR_INVALID; }
+    const uint64_t bins = ncols == 2 ? static_cast<uint64_t>(span[0]) * span[1] : span[0];
+    if (bins > kMaxWideBins) {
+        *why = ncols == 2 ? "GROUP BY (wide): the columns span " + std::to_string(span[0]) + " x " + std::to_string(span[1]) + " keys, more than 65536 bins"
+                          : "GROUP BY (wide): the group column spans " + std::to_string(span[0]) + " distinct values, more than 65536 bins";
+        return AQE_ERR_UNSUPPORTED;
+    }
+    *nbins = static_cast<uint32_t>(bins);
+    *nslices = static_cast<uint32_t>((bins + slice - 1) / slice);
+    return AQE_OK;
+}
+
+// The slice of this call: AQE_WIDE_SLICE (diagnostics: a power of two, 64 .. 4096; anything else is ignored), or the default.
+uint32_t call_slice() {
+    if (const char* e = std::getenv("AQE_WIDE_SLICE")) {
+        char* end = nullptr;
+        const long v = std::strtol(e, &end, 10);
+        if (end != e && *end == '\0' && v >= static_cast<long>(kWideMinSlice) && v <= static_cast<long>(kWideMaxSlice) && (v & (v - 1)) == 0) return static_cast<uint32_t>(v);
+    }
+    return kWideSliceDefault;
+}
+
+}  // namespace
+}  // namespace aqe
+
+// What the wide grouped entries keep with the context.  Allocated on first use at the size the call needs, grown when a later
+// call needs more, freed with the context.
+struct aqe_wide_scratch {
+    double* d_partial = nullptr;  // [nslices][grid][slice_bins][4]
+    size_t partial_bytes = 0;
+    double* d_bins = nullptr;     // [nbins][4]
+    size_t bins_bytes = 0;
+    aqe_group_result* d_groups = nullptr;  // the compacted list
+    aqe_group_result* h_groups = nullptr;  // its host mirror (pinned)
+    size_t groups_cap = 0;
+    unsigned* d_counts = nullptr;  // [kMaxWideBins / kFinishThreads + 1]: per finishing workgroup, then the number of groups
+    unsigned* h_count = nullptr;   // pinned
+    bool lds_opted = false;        // every instantiation of k_group_wide may take kWideMaxSlice bins of dynamic LDS
+};
+
+namespace aqe {
+namespace {
+
+constexpr Wording kWideWords{"GROUP BY (wide) does not take the ", "GROUP BY (wide) has no grouped refusal of its own"};
+
+template <typename T>
+int grow(aqe_ctx* c, T** p, size_t* have, size_t need) {
+    if (*have >= need) return AQE_OK;
+    if (*p) {
+        HIPCHK(c, hipDeviceSynchronize());  // an earlier sweep (on any stream) may still be using the buffer
+        (void)hipFree(*p);
+    }
+    *p = nullptr;
+    *have = 0;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(p), need));
+    *have = need;
+    return AQE_OK;
+}
+
+int ensure_scratch(aqe_ctx* c) {
+    if (!c->wide) c->wide = new aqe_wide_scratch;  // (wide_release frees whatever part of it exists)
+    aqe_wide_scratch* s = c->wide;
+    if (!s->d_counts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_counts), sizeof(unsigned) * (kMaxWideBins / kFinishThreads + 1)));
+    if (!s->h_count) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_count), sizeof(unsigned), hipHostMallocDefault));
+    return AQE_OK;
+}
+
+int ensure_groups(aqe_ctx* c, size_t count) {
+    aqe_wide_scratch* s = c->wide;
+    if (s->groups_cap >= count) return AQE_OK;
+    if (s->d_groups) {
+        HIPCHK(c, hipDeviceSynchronize());
+        (void)hipFree(s->d_groups);
+    }
+    if (s->h_groups) (void)hipHostFree(s->h_groups);
+    s->d_groups = s->h_groups = nullptr;
+    s->groups_cap = 0;
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_groups), sizeof(aqe_group_result) * count));
+    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_groups), sizeof(aqe_group_result) * count, hipHostMallocDefault));
+    s->groups_cap = count;
+    return AQE_OK;
+}
+
+// More than 64 KiB of dynamic LDS needs opting in, once per instantiation; a failure never reaches a launch.
+template <bool NT, int NK>
+int opt_in(aqe_ctx* c) {
+    const int bytes = static_cast<int>(kWideMaxSlice * kWideBin * sizeof(double));
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_group_wide<NT, NK>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess)
+        return fail(c, AQE_ERR_INTERNAL, "GROUP BY (wide): " + std::to_string(bytes) + " bytes of dynamic LDS per workgroup were refused (hipFuncSetAttribute: " +
+                                             hipGetErrorString(e) + ")");
+    return AQE_OK;
+}
+int ensure_lds(aqe_ctx* c) {
+    if (c->wide->lds_opted) return AQE_OK;
+    int rc = opt_in<false, 1>(c);
+    if (rc == AQE_OK) rc = opt_in<false, 2>(c);
+    if (rc == AQE_OK) rc = opt_in<true, 1>(c);
+    if (rc == AQE_OK) rc = opt_in<true, 2>(c);
+    if (rc == AQE_OK) c->wide->lds_opted = true;
+    return rc;
+}
+
+inline unsigned blocks_for(u64 work, u64 per_block, unsigned cap) {
+    u64 g = (work + per_block - 1) / per_block;
+    if (g < 1) g = 1;
+    return static_cast<unsigned>(g > cap ? cap : g);
+}
+
+// columns[1] is read only with ncols == 2.
+int columns_ok(aqe_ctx* c, const int* columns, int ncols, int cols[2]) {
+    if (!columns || (ncols != 1 && ncols != 2) || (ncols == 2 && columns[1] == 0)) return fail(c, AQE_ERR_INVALID, "GROUP BY (wide): one group column or a pair of them");
+    cols[0] = columns[0];
+    cols[1] = ncols == 2 ? columns[1] : 0;
+    return level_columns_ok(c, cols);
+}
+
+// The agreed ranges as the sweep and the finish take them, behind wide_plan's bound.
+int range_ok(aqe_ctx* c, const int cols[2], const int32_t* key_min, const uint32_t* span, GroupCols* g, uint32_t* nslices, uint32_t slice) {
+    if (!key_min || !span) return fail(c, AQE_ERR_INVALID, "null argument");
+    const int ncols = cols[1] ? 2 : 1;
+    uint32_t nbins = 0;
+    std::string why;
+    const int rc = wide_plan(span, ncols, slice, &nbins, nslices, &why);
+    if (rc != AQE_OK) return fail(c, rc, why);
+    *g = GroupCols{{cols[0], cols[1]}, {key_min[0], ncols == 2 ? key_min[1] : 0}, {span[0], ncols == 2 ? span[1] : 1u}};
+    return AQE_OK;
+}
+
+WideFinish finish_for(const aqe_ctx* c, const aqe_query* q, const GroupCols& g) {
+    return WideFinish{g.range(), query_shift(c, *q), q->sample_percent, q->agg, g.pair() ? 1 : 0};
+}
+
+// This shard's bins [nbins][4] into dev_bins (zeros when nothing of the sample lies in this shard), under the filter `f`
+// (null: none; the caller has checked it).
+int enqueue_bins(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, const GroupCols& g, uint32_t slice, double* dev_bins, hipStream_t s) {
+    const uint32_t nbins = g.nbins();
+    const size_t bins_bytes = static_cast<size_t>(nbins) * kWideBin * sizeof(double);
+    WideLaunch a{};
+    a.sw = SweepCommon{};
+    unsigned cap_x = 1;
+    if (p->host.is_random) {
+        a.sw.amount = c->amount;
+        a.sw.shard_lo = c->shard_lo;
+        a.sw.has_where = p->q.has_where ? 1 : 0;
+        a.sw.wmin = p->q.where_min;
+        a.sw.wmax = p->q.where_max;
+        a.idx = p->d_idx;
+        a.n_idx = a.idx ? p->host.random_idx.size() : 0;
+        cap_x = blocks_for(a.n_idx, static_cast<u64>(kBlockThreads) * kTileUnroll, kGroupedMaxBlocks);
+    } else if (!p->rounds.empty() && c->n_local) {
+        const LaunchDesc& L = p->rounds[0];
+        a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
+        a.ntiles = L.nfam ? L.ntiles : 0;
+        cap_x = grouped_grid(a.ntiles);
+    }
+    a.sw.shift = query_shift(c, p->q);
+    if (!((a.ntiles > 0 || a.n_idx > 0) && c->n_local > 0)) {
+        HIPCHK(c, hipMemsetAsync(dev_bins, 0, bins_bytes, s));
+        return AQE_OK;
+    }
+    // the columns: the group column (a pair: both) and, under a term on it, the other one
+    const bool pair = g.pair();
+    auto key_of = [&](int col, const int32_t** out) {
+        if (!p->host.is_random) return key_pointer(c, p, col, out);
+        const int rc = ensure_keys(c, col);
+        if (rc == AQE_OK) *out = c->keycol[col - 1];
+        return rc;
+    };
+    int rc = AQE_OK;
+    for (int i = 0; i < (pair ? 2 : 1); ++i) {
+        rc = key_of(g.col[i], &a.keys[i]);
+        if (rc != AQE_OK) return rc;
+        const int k = g.col[i] - 1;
+        if (c->key_min[k] < g.kmin[i] || static_cast<int64_t>(c->key_max[k]) - g.kmin[i] >= static_cast<int64_t>(g.span[i]))
+            return fail(c, AQE_ERR_INVALID, pair ? "this shard has keys outside [key_min, key_min + span) of a column of the pair"
+                                                 : "this shard has keys outside [key_min, key_min + span)");
+    }
+    a.flt.t[0] = a.flt.t[1] = pass_all();
+    int nk = pair ? 2 : 1;
+    if (f) {
+        compile_term(f->term[g.col[0] - 1], &a.flt.t[0], a.flt.map[0]);
+        const int other = g.col[0] == AQE_GROUP_REGION ? AQE_GROUP_PRODUCT : AQE_GROUP_REGION;  // (column B of a pair)
+        if (pair) {
+            compile_term(f->term[other - 1], &a.flt.t[1], a.flt.map[1]);
+        } else if (f->term[other - 1].form != AQE_KEYTERM_NONE) {
+            compile_term(f->term[other - 1], &a.flt.t[1], a.flt.map[1]);
+            rc = key_of(other, &a.keys[1]);
+            if (rc != AQE_OK) return rc;
+            nk = 2;
+        }
+    }
+    a.key_min = g.kmin[0];
+    a.span_a = g.span[0];
+    a.key_min_b = pair ? g.kmin[1] : 0;
+    a.span_b = pair ? g.span[1] : 1u;
+    a.pair = pair ? 1u : 0u;
+    const uint32_t nslices = (nbins + slice - 1) / slice;
+    const uint32_t sb = nslices == 1 ? ((nbins + 15u) & ~15u) : slice;  // one slice: as many bins as there are (whole 512-byte lines)
+    a.slice_bins = sb;
+    unsigned want_x = (kWideTargetBlocks + nslices - 1) / nslices;
+    if (const char* e = std::getenv("AQE_WIDE_GRID")) {  // diagnostics (tools/wide_group_time.py): workgroups per slice
+        const long v = std::atol(e);
+        if (v >= 1 && v <= static_cast<long>(kGroupedMaxBlocks)) want_x = static_cast<unsigned>(v);
+    }
+    const unsigned grid_x = std::max(1u, std::min(cap_x, want_x));
+    const size_t lds_bytes = static_cast<size_t>(sb) * kWideBin * sizeof(double);
+    aqe_wide_scratch* sc = c->wide;
+    rc = grow(c, &sc->d_partial, &sc->partial_bytes, static_cast<size_t>(nslices) * grid_x * lds_bytes);
+    if (rc == AQE_OK) rc = ensure_lds(c);
+    if (rc != AQE_OK) return rc;
+    a.partial = sc->d_partial;
+    const bool nt = a.sw.nt != 0;
+    c->last_nt = nt ? 1 : 0;
+    const dim3 gd(grid_x, nslices), bd(kBlockThreads);
+    if (nt) {
+        if (nk == 1) hipLaunchKernelGGL((k_group_wide<true, 1>), gd, bd, lds_bytes, s, a);
+        else hipLaunchKernelGGL((k_group_wide<true, 2>), gd, bd, lds_bytes, s, a);
+    } else {
+        if (nk == 1) hipLaunchKernelGGL((k_group_wide<false, 1>), gd, bd, lds_bytes, s, a);
+        else hipLaunchKernelGGL((k_group_wide<false, 2>), gd, bd, lds_bytes, s, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    const unsigned nwords = nbins * kWideBin;
+    hipLaunchKernelGGL(k_wide_bins_sum, dim3((nwords + 63) / 64), dim3(kBlockThreads), 0, s, sc->d_partial, grid_x, sb, nwords, dev_bins);
+    HIPCHK(c, hipGetLastError());
+    return AQE_OK;
+}
+
+// The counting pass and the finishing kernel over dev_bins on `s`, then the list: the groups somebody sampled, ascending.
+int finish_groups(aqe_ctx* c, const aqe_query* q, const GroupCols& g, const double* dev_bins, hipStream_t s, aqe_group_result* out, uint32_t cap, uint32_t* n_groups) {
+    aqe_wide_scratch* sc = c->wide;
+    const uint32_t nbins = g.nbins();
+    const uint32_t room = std::min(cap, nbins);
+    int rc = ensure_groups(c, std::max<size_t>(room, 1));
+    if (rc != AQE_OK) return rc;
+    const unsigned blocks = (nbins + kFinishThreads - 1) / kFinishThreads;
+    hipLaunchKernelGGL(k_wide_count, dim3(blocks), dim3(kFinishThreads), 0, s, dev_bins, nbins, sc->d_counts);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_wide_finish, dim3(blocks), dim3(kFinishThreads), 0, s, dev_bins, nbins, sc->d_counts, finish_for(c, q, g), sc->d_groups, room);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(sc->h_count, sc->d_counts + blocks, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const uint32_t count = *sc->h_count;
+    *n_groups = count;
+    if (count > cap)  // no partial list
+        return fail(c, AQE_ERR_INVALID, "GROUP BY (wide): " + std::to_string(count) + " groups, more than the caller's buffer holds (cap " + std::to_string(cap) + ")");
+    if (count == 0) return AQE_OK;
+    HIPCHK(c, hipMemcpyAsync(sc->h_groups, sc->d_groups, sizeof(aqe_group_result) * count, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    std::memcpy(out, sc->h_groups, sizeof(aqe_group_result) * count);
+    return AQE_OK;
+}
+
+// What the sweeping entries check before the ranges: the query's sampler (moment_plan's refusals, as for aqe_reduce_extremes'
+// ungrouped form: the seeded random sampler is taken, through its index list) and the filter.
+int sweep_prologue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, aqe_plan** p) {
+    if (!q) return fail(c, AQE_ERR_INVALID, "null query");
+    if (q->agg != AQE_SUM && q->agg != AQE_AVG && q->agg != AQE_COUNT) return fail(c, AQE_ERR_INVALID, "GROUP BY (wide) takes SUM, AVG or COUNT");
+    int rc = f ? check_filter(c, f) : AQE_OK;
+    if (rc != AQE_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = moment_plan(c, q, false, kWideWords, p);
+    if (rc == AQE_OK) rc = ensure_scratch(c);
+    return rc;
+}
+
+}  // namespace
+
+void wide_release(aqe_ctx* c) {
+    aqe_wide_scratch* s = c->wide;
+    if (!s) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    (void)hipFree(s->d_partial);
+    (void)hipFree(s->d_bins);
+    (void)hipFree(s->d_groups);
+    (void)hipFree(s->d_counts);
+    if (s->h_groups) (void)hipHostFree(s->h_groups);
+    if (s->h_count) (void)hipHostFree(s->h_count);
+    delete s;
+    c->wide = nullptr;
+}
+
+}  // namespace aqe
+
+using namespace aqe;
+
+extern "C" {
+
+int aqe_wide_plan(const uint32_t* span, int ncols, uint32_t slice_bins, uint32_t* nbins, uint32_t* nslices) {
+    if (!nbins || !nslices) return fail(nullptr, AQE_ERR_INVALID, "null argument");
+    std::string why;
+    const int rc = wide_plan(span, ncols, slice_bins, nbins, nslices, &why);
+    return rc == AQE_OK ? rc : fail(nullptr, rc, why);  // (no context: aqe_last_error(NULL) has the text)
+}
+
+int aqe_reduce_grouped_wide(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int* columns, int ncols, aqe_group_result* out, uint32_t cap,
+                            uint32_t* n_groups) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_groups || (cap && !out)) return fail(c, AQE_ERR_INVALID, "null argument");
+    *n_groups = 0;
+    int cols[2];
+    int rc = columns_ok(c, columns, ncols, cols);
+    if (rc != AQE_OK) return rc;
+    aqe_plan* p = nullptr;
+    rc = sweep_prologue(c, f, q, &p);
+    if (rc != AQE_OK) return rc;
+    // the table's key ranges (this context holds all of it)
+    int32_t kmin[2] = {0, 0};
+    uint32_t span[2] = {0, 1};
+    for (int i = 0; i < ncols; ++i) {
+        int32_t lo = 0, hi = -1;
+        rc = aqe_group_key_range(c, cols[i], &lo, &hi);
+        if (rc != AQE_OK) return rc;
+        if (hi < lo) return AQE_OK;  // an empty table: no groups
+        kmin[i] = lo;
+        span[i] = static_cast<uint32_t>(std::min<int64_t>(static_cast<int64_t>(hi) - lo + 1, 0xffffffffll));  // (2^32 keys: refused as 2^32 - 1 would be)
+    }
+    const uint32_t slice = call_slice();
+    GroupCols g;
+    uint32_t nslices = 0;
+    rc = range_ok(c, cols, kmin, span, &g, &nslices, slice);
+    if (rc != AQE_OK) return rc;
+    aqe_wide_scratch* sc = c->wide;
+    rc = grow(c, &sc->d_bins, &sc->bins_bytes, static_cast<size_t>(g.nbins()) * kWideBin * sizeof(double));
+    if (rc == AQE_OK) rc = enqueue_bins(c, p, f, g, slice, sc->d_bins, c->stream);
+    if (rc != AQE_OK) return rc;
+    return finish_groups(c, q, g, sc->d_bins, c->stream, out, cap, n_groups);
+}
+
+int aqe_grouped_wide_enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int* columns, int ncols, const int32_t* key_min,
+                                  const uint32_t* span, double* dev_bins, void* stream) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!dev_bins) return fail(c, AQE_ERR_INVALID, "null dev_bins");
+    int cols[2];
+    int rc = columns_ok(c, columns, ncols, cols);
+    if (rc != AQE_OK) return rc;
+    const uint32_t slice = call_slice();
+    GroupCols g;
+    uint32_t nslices = 0;
+    rc = range_ok(c, cols, key_min, span, &g, &nslices, slice);
+    if (rc != AQE_OK) return rc;
+    aqe_plan* p = nullptr;
+    rc = sweep_prologue(c, f, q, &p);
+    if (rc != AQE_OK) return rc;
+    return enqueue_bins(c, p, f, g, slice, dev_bins, stream_of(c, stream));
+}
+
+int aqe_grouped_wide_finish(aqe_ctx* c, const aqe_query* q, int ncols, const int32_t* key_min, const uint32_t* span, const double* dev_bins, void* stream,
+                            aqe_group_result* out, uint32_t cap, uint32_t* n_groups) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_groups || (cap && !out) || !dev_bins) return fail(c, AQE_ERR_INVALID, "bad argument");
+    *n_groups = 0;
+    if (ncols != 1 && ncols != 2) return fail(c, AQE_ERR_INVALID, "GROUP BY (wide): one group column or a pair of them");
+    const int cols[2] = {AQE_GROUP_REGION, ncols == 2 ? AQE_GROUP_PRODUCT : 0};  // (the finish reads the ranges, not the columns)
+    GroupCols g;
+    uint32_t nslices = 0;
+    int rc = range_ok(c, cols, key_min, span, &g, &nslices, 0);
+    if (rc != AQE_OK) return rc;
+    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
+    if (!(q->sample_percent > 0.0)) return fail(c, AQE_ERR_INVALID, "sample_percent must be positive");
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    return finish_groups(c, q, g, dev_bins, stream_of(c, stream), out, cap, n_groups);
+}
+
+}  // extern "C"

@@ -428,6 +428,39 @@ def sharded_group_by_pair(engine, query, columns, bins, all_reduce_sum: Callable
         return engine.grouped_pair_spread_finish(query, kind, kmin, span, b.data_ptr(), stream)
 
 
+def sharded_group_by_wide(engine, query, columns, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None,
+                          max_groups: int = 65536):
+    """GROUP BY over wide key ranges across ranks, collective: ``columns`` is one key column or the ordered pair (A, B).  The
+    key ranges are agreed in ONE MAX all-reduce of [-minA, maxA(, -minB, maxB)] as sharded_group_by_pair does; every rank derives
+    the same bins from them on the host (engine.wide_plan: more than 65 536 bins is refused on every rank alike, before the
+    sweep), bins its part of the sample into nbins x WIDE_BIN sums (aqe_grouped_wide_enqueue_bins, under ``key_filter`` when
+    there is one), ONE all-reduce SUM merges them and every rank finishes the same bins — so every rank returns the same list
+    of GroupResult.
+
+    bins    float64 tensor on the engine's device with room for WIDE_BIN * nbins doubles (at most WIDE_BIN * 65 536)
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    from ._native import WIDE_BIN
+    from .engine import wide_plan
+    stream = _stream_for(stream, bins)
+    cols = [int(c) for c in columns]
+    with _torch_on(stream, bins):
+        ranges = [engine.group_key_range(c) for c in cols]
+        rng = bins.new_tensor([v for lo, hi in ranges for v in (-float(lo), float(hi))])
+        all_reduce_max(rng)
+        r = [int(v) for v in rng.tolist()]
+        kmin, kmax = [-v for v in r[0::2]], r[1::2]
+        if any(hi < lo for lo, hi in zip(kmin, kmax)):
+            return []  # an empty table
+        span = [hi - lo + 1 for lo, hi in zip(kmin, kmax)]
+        nbins = wide_plan(span)[0]
+        if bins.numel() < WIDE_BIN * nbins:
+            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {WIDE_BIN * nbins} needed")
+        b = bins[: WIDE_BIN * nbins]
+        engine.grouped_wide_enqueue_bins(query, cols, kmin, span, b.data_ptr(), stream, key_filter)
+        all_reduce_sum(b)
+        return engine.grouped_wide_finish(query, kmin, span, b.data_ptr(), stream, max_groups)
+
+
 def sharded_extremes(engine, query, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
     """MIN / MAX across the ranks of a process group (engine.Engine interface), collective: every rank sweeps the part of the
     sample inside its shard into EXTREME_VEC doubles (aqe_extremes_enqueue, under ``key_filter`` when there is one), ONE

@@ -582,6 +582,36 @@ class Engine:
                                                            C.c_void_p(dev_bins_ptr), C.c_void_p(stream), out, max_groups, C.byref(n)))
         return list(out[: n.value])
 
+    # -- GROUP BY over wide key ranges (aqe_reduce_grouped_wide and its kin): one column or the ordered pair, up to 65 536 bins --
+    def reduce_grouped_wide(self, query: Query, columns: Sequence[int], key_filter: "Optional[nat.KeyFilter]" = None, max_groups: int = nat.WIDE_MAX_BINS):
+        """SUM / AVG / COUNT per group of ``columns`` (one column, or the ordered pair) through the sliced sweep: list of
+        GroupResult ascending by key (a pair: ``key`` packs both, nat.group_key_unpack), only groups with a sampled row.  More
+        groups than ``max_groups`` is AqeError(ERR_INVALID) with the count; no partial list."""
+        cols = [int(c) for c in columns]
+        out = self._group_buf(max_groups)
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_reduce_grouped_wide(self._h, _filter_ref(key_filter), C.byref(query), _pair(C.c_int, _two(cols, 0)), len(cols), out,
+                                                    max_groups, C.byref(n)))
+        return list((nat.GroupResult * n.value).from_buffer_copy(out)) if n.value else []
+
+    def grouped_wide_enqueue_bins(self, query: Query, columns: Sequence[int], key_min: Sequence[int], span: Sequence[int], dev_bins_ptr: int,
+                                  stream: int = 0, key_filter: "Optional[nat.KeyFilter]" = None):
+        """This shard's nbins x WIDE_BIN sums over the agreed key ranges into device memory (all-reduce SUM, then
+        grouped_wide_finish); nbins is wide_plan(span)[0]."""
+        cols = [int(c) for c in columns]
+        self._chk(nat.lib().aqe_grouped_wide_enqueue_bins(self._h, _filter_ref(key_filter), C.byref(query), _pair(C.c_int, _two(cols, 0)), len(cols),
+                                                          _pair(C.c_int32, _two(key_min, 0)), _pair(C.c_uint32, _two(span, 1)), C.c_void_p(dev_bins_ptr),
+                                                          C.c_void_p(stream)))
+
+    def grouped_wide_finish(self, query: Query, key_min: Sequence[int], span: Sequence[int], dev_bins_ptr: int, stream: int = 0,
+                            max_groups: int = nat.WIDE_MAX_BINS):
+        ncols = len(list(span))
+        out = self._group_buf(max_groups)
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_grouped_wide_finish(self._h, C.byref(query), ncols, _pair(C.c_int32, _two(key_min, 0)), _pair(C.c_uint32, _two(span, 1)),
+                                                    C.c_void_p(dev_bins_ptr), C.c_void_p(stream), out, max_groups, C.byref(n)))
+        return list((nat.GroupResult * n.value).from_buffer_copy(out)) if n.value else []
+
     # -- GROUP BY to an error threshold (aqe_reduce_grouped_error and its stepwise multi-GPU form) --
     def reduce_grouped_error(self, query: Query, columns: Sequence[int], error_percent: float, max_percent: float = 100.0,
                              key_filter: "Optional[nat.KeyFilter]" = None, max_groups: int = 1024):
@@ -870,6 +900,18 @@ def time_plan(spec: "nat.TimeSpec", tmin: int, tmax: int) -> Tuple[int, int]:
     if rc != nat.OK:
         raise nat.AqeError(rc, "BUCKET: the width must be at least 1 and the window must have t_lo <= t_hi")
     return first.value, n.value
+
+
+def wide_plan(span: Sequence[int], slice_bins: int = 0) -> Tuple[int, int]:
+    """aqe_wide_plan: (nbins, nslices) of the wide GROUP BY over one column's span or the pair's two, in slices of ``slice_bins``
+    bins (0: the default), host only.  Raises AqeError with the library's text: ERR_UNSUPPORTED past 65 536 bins (the message
+    names the span, or both), ERR_INVALID for a zero span or a slice that is no power of two in 64 .. 4096."""
+    vals = [int(v) for v in span]
+    if len(vals) not in (1, 2) or any(not 0 <= v <= 0xFFFFFFFF for v in vals):
+        raise ValueError(f"one span or two, each an unsigned 32-bit number, got {list(span)!r}")
+    nbins, nslices = C.c_uint32(), C.c_uint32()
+    nat.check(nat.lib().aqe_wide_plan(_pair(C.c_uint32, _two(vals, 1)), len(vals), int(slice_bins), C.byref(nbins), C.byref(nslices)))
+    return nbins.value, nslices.value
 
 
 def parse_time_where(query: str, spec: "Optional[nat.TimeSpec]" = None):

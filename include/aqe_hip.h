@@ -45,7 +45,8 @@ typedef enum aqe_status {
     AQE_ERR_NO_TABLE = -4,  /* nothing staged                                                     */
     AQE_ERR_IO = -5,        /* file missing / malformed                                           */
     AQE_ERR_CAPACITY = -6,  /* caller buffer too small                                            */
-    AQE_ERR_UNSUPPORTED = -7
+    AQE_ERR_UNSUPPORTED = -7,
+    AQE_ERR_INTERNAL = -8   /* the device refused a resource a kernel of the library needs (the message names it) */
 } aqe_status;
 
 /* DB.hpp:17-27 — the reference's 32-byte row, amount at byte 8. */
@@ -1192,6 +1193,51 @@ AQE_API int aqe_reduce_time_buckets(aqe_ctx* ctx, const aqe_key_filter* filter /
 AQE_API int aqe_time_buckets_enqueue_bins(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const aqe_time_spec* spec, int64_t tmin,
                                           int64_t tmax, double* dev_bins, void* stream);
 AQE_API int aqe_time_buckets_finish(aqe_ctx* ctx, const aqe_query* q, const aqe_time_spec* spec, int64_t tmin, int64_t tmax, const double* dev_bins,
+                                    void* stream, aqe_group_result* out, uint32_t cap, uint32_t* n_groups);
+
+/* ---- GROUP BY over wide key ranges: up to 65 536 groups, sliced sweep (wide_group.hip) --------------------------------------
+ * aqe_reduce_grouped and aqe_reduce_grouped_pair bin into one workgroup's LDS and stop at 1024 bins; they keep that bound and
+ * their refusals.  These entries answer SUM / AVG / COUNT per group — per group the estimate and interval of
+ * aqe_reduce_grouped: value and half-width scaled by 100 / pct for SUM, no interval for COUNT or when n < 2 — for one key
+ * column (ncols == 1: columns[0]) or the ordered pair (ncols == 2: columns as aqe_reduce_grouped_pair takes them) with
+ * nbins = span, or spanA * spanB, up to 65 536.  More is AQE_ERR_UNSUPPORTED with the span (or both spans) in the message;
+ * nothing is truncated.  The bin of a row is key - key_min, or (a - minA) * spanB + (b - minB).
+ *
+ * Rows.  `filter` (NULL: none) takes terms as aqe_reduce_grouped_pair does, on either key column or both; q carries the amount
+ * range and the row window.  A sampled row counts into its group's `visited`; it counts into `n` and the sums when it also
+ * passes the amount range and the filter, so a sampled group none of whose rows pass is listed with n == 0.  Samplers and
+ * refusals are those of aqe_reduce_extremes' ungrouped form: the single-round family samplers and the seeded
+ * AQE_M_RANDOM_POINTER (through its index list); CLT, adaptive, stratified, AQE_M_RANDOM_DEVICE and pair-family samplers are
+ * AQE_ERR_UNSUPPORTED by name.  VARIANCE / STDDEV, MIN / MAX, the error-threshold form and time buckets have no wide form.
+ *
+ * Results.  aqe_group_result ascending by key (a pair: AQE_GROUP_KEY_PACK, ascending by (a, b)), only groups with
+ * visited > 0.  cap smaller than their number is AQE_ERR_INVALID with the count in the message and in *n_groups; no partial
+ * list is written.
+ *
+ * The sweep (k_group_wide).  The bins {n, P1, P2, visited} are cut into slices of slice_bins bins that fit a workgroup's LDS
+ * (1024 / 2048 / 4096 bins: 32 / 64 / 128 KiB; the default is 2048), the grid is (workgroups, slices), and every slice's
+ * workgroups sweep the sampled rows — 8 + 4 (+ 4) bytes per row and slice, from cache for a sample below the Infinity Cache.
+ * Workgroups store their slice; the stores are summed per word in workgroup order and one thread per bin finishes and
+ * compacts the list.  Counts are exact; sums are reproducible to rounding.  No floating-point atomics on device memory.
+ * Diagnostics: the environment variable AQE_WIDE_SLICE (a power of two, 64 .. 4096; anything else is ignored) is read per call
+ * and forces the slice; AQE_NT=0/1 picks the load flavour, which aqe_last_load_policy reports.  A device that refuses the
+ * dynamic LDS is AQE_ERR_INTERNAL with the byte count; nothing is launched. */
+/* Host only, no GPU and no context (extends aqe_time_plan's role for the buckets): nbins and the number of slices of
+ * slice_bins bins (0: the default) for one span (ncols == 1) or two.  AQE_ERR_UNSUPPORTED past 65 536 bins, AQE_ERR_INVALID
+ * for a zero span, ncols outside 1..2 or a slice_bins that is no power of two in 64 .. 4096; aqe_last_error(NULL) has the text. */
+AQE_API int aqe_wide_plan(const uint32_t span[2], int ncols, uint32_t slice_bins, uint32_t* nbins, uint32_t* nslices);
+/* Single GPU, synchronous (extends aqe_reduce_grouped / aqe_reduce_grouped_pair past 1024 bins): key ranges, sweep, sum, finish. */
+AQE_API int aqe_reduce_grouped_wide(aqe_ctx* ctx, const aqe_key_filter* filter /* NULL: none */, const aqe_query* q, const int columns[2], int ncols,
+                                    aqe_group_result* out, uint32_t cap, uint32_t* n_groups);
+/* Multi-GPU (extends aqe_grouped_pair_enqueue_bins / aqe_grouped_pair_finish): aqe_group_key_range per column, all-reduce
+ * MIN / MAX, key_min[i] and span[i] = max - min + 1 of column i (a shard with keys outside them: AQE_ERR_INVALID), then
+ *     aqe_grouped_wide_enqueue_bins(ctx, filter, q, columns, ncols, key_min, span, dev_bins, stream)   nbins x 4 doubles
+ *     <ONE all-reduce SUM of nbins * 4 doubles on `stream`>
+ *     aqe_grouped_wide_finish(ctx, q, ncols, key_min, span, dev_bins, stream, out, cap, &n_groups)      synchronises `stream`
+ * Every rank finishes the same bins.  key_min[1] and span[1] are read only with ncols == 2. */
+AQE_API int aqe_grouped_wide_enqueue_bins(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const int columns[2], int ncols,
+                                          const int32_t key_min[2], const uint32_t span[2], double* dev_bins, void* stream);
+AQE_API int aqe_grouped_wide_finish(aqe_ctx* ctx, const aqe_query* q, int ncols, const int32_t key_min[2], const uint32_t span[2], const double* dev_bins,
                                     void* stream, aqe_group_result* out, uint32_t cap, uint32_t* n_groups);
 
 #ifdef __cplusplus
