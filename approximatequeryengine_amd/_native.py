@@ -66,6 +66,7 @@ DISTINCT_VEC_HEAD, DISTINCT_SLOTS = 2, 8192  # [visited, n] for a SUM all-reduce
 SUMMARY_VEC, SUMMARY_VEC_SUM = 12, 10  # the SPREAD_VEC layout + {0, 0} for a SUM all-reduce, then {-min, max} for a MAX all-reduce
 TIME_BIN, TIME_MAX_BUCKETS, TIME_MAX_SPAN = 4, 1024, 2 ** 31 - 1  # {n, P1, P2, visited} per time bucket; the limits of aqe_time_plan
 WIDE_BIN, WIDE_MAX_BINS, WIDE_SLICE_DEFAULT = 4, 65536, 2048  # {n, P1, P2, visited} per bin of the wide GROUP BY; the bound and default slice of aqe_wide_plan
+TOP_MAX = 1024  # the largest LIMIT of the top-N groups (aqe_top_spec.k)
 KEYTERM_NONE, KEYTERM_RANGE, KEYTERM_BITMAP = 0, 1, 2
 KEY_BITMAP_BITS = 1024
 
@@ -107,6 +108,18 @@ class GroupResult(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TopSpec(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("descending", C.c_int32)]
+
+
+class TopInfo(C.Structure):
+    _fields_ = [("groups", C.c_uint32), ("listed", C.c_uint32), ("contenders", C.c_uint32), ("has_next", C.c_int32), ("next", GroupResult)]
+
+    def as_dict(self):
+        return {"groups": self.groups, "listed": self.listed, "contenders": self.contenders, "has_next": bool(self.has_next),
+                "next": self.next.as_dict() if self.has_next else None}
 
 
 class QuantileResult(C.Structure):
@@ -377,6 +390,9 @@ def lib() -> C.CDLL:
         "aqe_reduce_grouped_wide": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), C.c_int, P(GroupResult), u32, P(u32)]),
         "aqe_grouped_wide_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), C.c_int, P(i32), P(u32), vp, vp]),
         "aqe_grouped_wide_finish": (C.c_int, [vp, P(Query), C.c_int, P(i32), P(u32), vp, vp, P(GroupResult), u32, P(u32)]),
+        "aqe_reduce_grouped_top": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), C.c_int, P(TopSpec), P(GroupResult), P(TopInfo)]),
+        "aqe_grouped_top_finish": (C.c_int, [vp, P(Query), C.c_int, P(i32), P(u32), vp, vp, P(TopSpec), P(GroupResult), P(TopInfo)]),
+        "aqe_top_from_results": (C.c_int, [P(GroupResult), u32, P(TopSpec), P(GroupResult), P(TopInfo)]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),

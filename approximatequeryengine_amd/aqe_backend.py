@@ -415,6 +415,26 @@ def _wide_groups_arg(max_groups, combined_with=None) -> bool:
     return max_groups > 1024
 
 
+def _top_arg(top, combined_with=None):
+    """The ``top`` argument of the grouped methods, checked before anything is launched: None, or the limit 1 .. 1024 of
+    ORDER BY the aggregate LIMIT k.  ``combined_with`` names what the top-N form does not combine with."""
+    if top is None:
+        return None
+    if isinstance(top, bool) or not isinstance(top, (int, np.integer)) or not 1 <= top <= nat.TOP_MAX:
+        raise ValueError(f"top must be an integer in 1 .. {nat.TOP_MAX}, got {top!r}")
+    if combined_with is not None:
+        raise ValueError(f"top={top} with {combined_with}: ORDER BY the aggregate LIMIT k orders SUM, AVG and COUNT at one sample "
+                         f"percentage only ({combined_with} has no top-N form)")
+    return int(top)
+
+
+def _top_info_dict(info, pair: bool) -> dict:
+    """aqe_top_info as ``last_top_info`` keeps it: ``next`` is None or (key as the mapping spells it, GroupEstimate)."""
+    spell = (lambda k: "%d,%d" % nat.group_key_unpack(k)) if pair else str
+    nxt = (spell(info.next.key), GroupEstimate(info.next)) if info.has_next else None
+    return {"groups": int(info.groups), "listed": int(info.listed), "contenders": int(info.contenders), "has_next": bool(info.has_next), "next": nxt}
+
+
 def _records(arr: np.ndarray) -> List[Record]:
     """numpy rows -> list[Record], what pybind11's list_caster gives the reference's callers."""
     return [Record(int(i), float(a), int(r), int(p), int(t))
@@ -813,7 +833,8 @@ class CustomBPlusDB:
     def approx_group_by(self, agg: str, group_by: str = "region", sample_percent: Optional[float] = None, method: Optional[str] = None,
                         where: Optional[Tuple[float, float]] = None, block_size: int = 1000,
                         key_where: Optional[dict] = None, error_percent: Optional[float] = None,
-                        max_percent: float = 100.0, max_groups: int = 1024) -> "dict[str, GroupEstimate]":
+                        max_percent: float = 100.0, max_groups: int = 1024, top: Optional[int] = None,
+                        ascending: bool = False) -> "dict[str, GroupEstimate]":
         """APPROX <agg>(amount) ... GROUP BY region | product_id with a 95 % interval per group: the reference's
         execute_query_groupby_with_ci (executor.cpp:202-321; GroupResultWithCI = map<string, {value, ci_lower,
         ci_upper}>) in one sweep.  method "rowid" is that function's own sample (rowid % (100 / sample_percent) == 0);
@@ -832,19 +853,33 @@ class CustomBPlusDB:
 
         ``max_groups`` (default 1024: today's routing and refusals): above 1024, at most 65 536, SUM / AVG / COUNT over key ranges
         that span more than 1024 bins go through the sliced sweep (aqe_reduce_grouped_wide) instead of being refused; it does
-        not combine with ``error_percent``."""
+        not combine with ``error_percent``.
+
+        ``top`` = k (1 .. 1024): ORDER BY the aggregate LIMIT k, selected on the device (aqe_reduce_grouped_top) over key ranges of
+        up to 65 536 bins whatever ``max_groups`` says — the mapping holds the k best groups with n > 0 in RANK order, largest
+        first unless ``ascending``; ties are ordered by ascending key.  ``last_top_info`` keeps the ranked groups, how many are
+        listed, the best unlisted group and ``contenders``: how many unlisted groups' intervals meet the last listed one's.  It
+        does not combine with ``error_percent``."""
         cols = group_columns(group_by)
         col = cols[0]
         wide = _wide_groups_arg(max_groups, "error_percent" if error_percent is not None else None)
+        k = _top_arg(top, "error_percent" if error_percent is not None else None)
         if error_percent is not None:
             return self._group_by_error(agg, cols, sample_percent, method, where, block_size, key_where, error_percent, max_percent)
         sample_percent = 10.0 if sample_percent is None else sample_percent
         method = "rowid" if method is None else method
         m = {"rowid": nat.M_ROWID_MOD, "stride": nat.M_MEMORY_STRIDE, "block": nat.M_BLOCK, "page": nat.M_PAGE, "exact": nat.M_EXACT}[method]
+        if k is not None:
+            self.last_top_info = None
         if self._n == 0:
             return {}
         bs = 4096 if (method == "page" and block_size == 1000) else block_size
         q = make_query(m, sample_percent, agg=_AGG[agg.upper()], where=where, block_size=int(bs))
+        if k is not None:
+            f = None if key_where is None else _key_filter_for(key_where, method)
+            groups, info = _quantile_call(lambda: self._grouped_top(f, q, cols, k, not ascending))
+            self.last_top_info = _top_info_dict(info, len(cols) == 2)
+            return _pair_groups(groups, GroupEstimate) if len(cols) == 2 else {str(r.key): GroupEstimate(r) for r in groups}
         if wide:
             f = None if key_where is None else _key_filter_for(key_where, method)
             groups = _quantile_call(lambda: self._grouped_wide(f, q, cols, int(max_groups)))
@@ -859,6 +894,7 @@ class CustomBPlusDB:
         return {str(r.key): GroupEstimate(r) for r in self._eng().reduce_grouped(q, col)}
 
     last_group_error_info: Optional[dict] = None  # of the most recent approx_group_by(error_percent=...)
+    last_top_info: Optional[dict] = None  # of the most recent approx_group_by(top=...)
 
     def _group_by_error(self, agg, cols, sample_percent, method, where, block_size, key_where, error_percent, max_percent):
         """approx_group_by(error_percent=...): the argument checks (before any table is needed), the call, the info."""
@@ -918,6 +954,9 @@ class CustomBPlusDB:
             return None
         return eng.reduce_grouped_wide(q, cols, f, max_groups)
 
+    def _grouped_top(self, f, q, cols, k, descending):
+        return self._eng().reduce_grouped_top(q, cols, k, descending, f)
+
     def _spread_groups_pair(self, f, q, kind, cols):
         return self._eng().reduce_grouped_pair_spread(q, kind, cols, f)
 
@@ -966,7 +1005,7 @@ class CustomBPlusDB:
     def approx_spread(self, kind: str = "var_samp", method: str = "stride", sample_percent: float = 10.0,
                       where: Optional[Tuple[float, float]] = None, id_between: Optional[Tuple[int, int]] = None, seed: int = 42,
                       confidence_level: float = 0.95, group_by: Optional[str] = None, num_threads: int = 4, block_size: int = 1000,
-                      key_where: Optional[dict] = None, max_groups: int = 1024):
+                      key_where: Optional[dict] = None, max_groups: int = 1024, top: Optional[int] = None):
         """APPROX VARIANCE / STDDEV(amount): ``kind`` is "var_samp" ("variance"), "var_pop", "stddev_samp" ("stddev") or
         "stddev_pop" of the sampled amounts X (WHERE and the key window applied) — numpy.var(X, ddof=1) and its kin, not scaled
         by the sampling fraction — with a large-sample normal interval from the fourth central moment; method "exact" reports
@@ -978,6 +1017,7 @@ class CustomBPlusDB:
         if k not in _SPREAD_KINDS:
             raise ValueError(f"kind must be one of {sorted(_SPREAD_KINDS)}")
         _wide_groups_arg(max_groups, "VARIANCE / STDDEV")
+        _top_arg(top, "VARIANCE / STDDEV")
         if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
             raise ValueError(f"VARIANCE / STDDEV do not take the {method} sampler (single-round family samplers and 'random' only)")
         f = None if key_where is None else _key_filter_for(key_where, method)
@@ -1027,7 +1067,7 @@ class CustomBPlusDB:
     def approx_extremes(self, method: str = "stride", sample_percent: float = 10.0, where: Optional[Tuple[float, float]] = None,
                         id_between: Optional[Tuple[int, int]] = None, seed: int = 42, confidence_level: float = 0.95,
                         group_by: Optional[str] = None, num_threads: int = 4, block_size: int = 1000, key_where: Optional[dict] = None,
-                        max_groups: int = 1024):
+                        max_groups: int = 1024, top: Optional[int] = None):
         """APPROX MIN / MAX(amount): numpy.min(X) and numpy.max(X) of the sampled amounts X (WHERE, the key window and
         ``key_where`` applied, NaN rows left out) from ONE sweep, as an ExtremeEstimate.  A sample's extreme bounds the table's
         from one side only: ``tail_fraction`` says how much of the qualifying rows may lie beyond it at ``confidence_level``
@@ -1036,6 +1076,7 @@ class CustomBPlusDB:
         ("region" | "product_id", or both as approx_group_by takes them) the result is the key -> ExtremeEstimate mapping
         approx_group_by returns.  There is no error-threshold form."""
         _wide_groups_arg(max_groups, "MIN / MAX")
+        _top_arg(top, "MIN / MAX")
         if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
             raise ValueError(f"MIN / MAX do not take the {method} sampler (single-round family samplers and 'random' only)")
         if not 0.0 < float(confidence_level) < 1.0:

@@ -346,6 +346,50 @@ def max_groups_defect(clean: str, args):
     return None
 
 
+_TOP_CLAUSE = re.compile(r"\bORDER\s+BY\s+(SUM|AVG|COUNT)\s*\(\s*(\*|amount)\s*\)\s*(ASC|DESC)?\s*\bLIMIT\s+([+-]?\d+)\s*;?\s*$", re.IGNORECASE)
+
+
+def _top_clause(clean: str):
+    """The match of a claimed ORDER BY <agg> [ASC | DESC] LIMIT k, or None: see top_of."""
+    m = _TOP_CLAUSE.search(clean)
+    if not m:
+        return None
+    head, name = clean[:m.start()], m.group(1).upper()
+    if not re.search(r"\bGROUP\s+BY\b", head, re.IGNORECASE) or (m.group(2) == "*" and name != "COUNT"):
+        return None
+    named = [a for a in ("SUM", "AVG", "COUNT") if re.search(rf"\b{a}\s*\(", head, re.IGNORECASE)]  # (aggregate_of's order of preference)
+    return m if named and named[0] == name else None
+
+
+def top_of(clean: str) -> Optional[Tuple[int, bool]]:
+    """``... GROUP BY ... ORDER BY <agg> [ASC | DESC] LIMIT k`` with <agg> the select list's own aggregate — SUM(amount),
+    AVG(amount), COUNT(*) or COUNT(amount), named literally before the clause; letter case and blanks do not matter on either
+    side — -> (k, descending), SQL's default direction being ASC; None for every other query: ORDER BY a column name, an ordinal
+    or an aggregate the select list does not name, ORDER BY <agg> without LIMIT, no GROUP BY — those clauses stay ignored, as
+    they were."""
+    m = _top_clause(clean)
+    return None if m is None else (int(m.group(4)), (m.group(3) or "ASC").upper() == "DESC")
+
+
+def top_defect(clean: str, args) -> Optional[str]:
+    """What keeps a query with a claimed ORDER BY <agg> LIMIT k from running, found before the table is opened (None: nothing, or
+    no such clause): a LIMIT outside 1 .. 1024, --e, VARIANCE / STDDEV, MIN / MAX or a time bucket — the forms without a top-N."""
+    top = top_of(clean)
+    if top is None:
+        return None
+    if not 1 <= top[0] <= 1024:
+        return f"LIMIT {top[0]}: ORDER BY the aggregate takes a LIMIT of 1 .. 1024"
+    if args.e is not None:
+        return "ORDER BY the aggregate ... LIMIT has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"
+    if re.search(r"\b(VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?)\s*\(", clean, re.IGNORECASE):
+        return "ORDER BY the aggregate ... LIMIT has no VARIANCE / STDDEV form: the top groups are ordered by SUM, AVG or COUNT"
+    if re.search(r"\b(MIN|MAX)\s*\(", clean, re.IGNORECASE):
+        return "ORDER BY the aggregate ... LIMIT has no MIN / MAX form: the top groups are ordered by SUM, AVG or COUNT"
+    if re.search(r"BUCKET\s*\(", clean, flags=re.IGNORECASE):
+        return "ORDER BY the aggregate ... LIMIT has no GROUP BY BUCKET(...) form: time buckets are listed in time order"
+    return None
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV, MIN/MAX, HISTOGRAM, COUNT(DISTINCT), SUMMARY on MI355X "
                                 "(e.g. \"SELECT HISTOGRAM(amount, 20) FROM sales\" --s 10 --ci; \"SELECT SUMMARY(amount) FROM sales\" --s 10 --ci)",
@@ -380,7 +424,7 @@ def run(args, out=sys.stdout) -> int:
         print("error: a query is required unless --explain is given", file=out)
         return 2
     clean, _ = parse_embedded_approx(args.query)
-    why = max_groups_defect(clean, args)
+    why = max_groups_defect(clean, args) or top_defect(clean, args)
     if why is not None:
         print(f"error: {why}", file=out)
         return 2
@@ -565,17 +609,25 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
         pct = args.s if args.s is not None else (100.0 if qtype == QUERY_EXACT else 10.0)
         mg = getattr(args, "max_groups", None)
         gkw = dict(kw) if mg is None else dict(kw, max_groups=mg)  # (passed only when the option is given)
+        top = top_of(clean)
+        if top is not None:  # ORDER BY the aggregate LIMIT k: the k best groups, selected on the device, in rank order
+            gkw.update(top=top[0], ascending=not top[1])
+            agg = _top_clause(clean).group(1).upper()  # (the aggregate the clause and the select list name, blanks or not)
         groups = db.approx_group_by(agg, group_by=", ".join(gb), sample_percent=pct, method="exact" if pct >= 100.0 else "rowid",
                                     where=aqe_backend.parse_where(clean), **gkw)
         ms = (time.perf_counter() - t0) * 1e3
         print(f"\nGROUP BY {', '.join(gb).lower()} ({'exact' if pct >= 100.0 else f'rowid sample {pct:g}%'}):", file=out)
-        shown = len(groups) if (mg is None or getattr(args, "all_groups", False)) else MAX_GROUPS_SHOWN
+        shown = len(groups) if (mg is None or top is not None or getattr(args, "all_groups", False)) else MAX_GROUPS_SHOWN
         for i, (key, g) in enumerate(groups.items()):
             if i >= shown:
                 print(f"   ... and {len(groups) - shown:,} more groups ({len(groups):,} in all; --all-groups prints every one)", file=out)
                 break
             ci = f"   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})" if (args.ci and pct < 100.0) else ""
             print(f"   {key:>6}: {g.value:,.4f}{ci}   n={g.n:,}", file=out)
+        if top is not None:
+            info = db.last_top_info or {"groups": len(groups), "listed": len(groups), "contenders": 0}
+            more = f"; {info['contenders']:,} more within the error of the last listed" if info["contenders"] > 0 else ""
+            print(f"   {info['groups']:,} groups, {info['listed']:,} listed{more}", file=out)
         print(f"   execution time: {ms:.2f} ms", file=out)
         db.close_database()
         return 0

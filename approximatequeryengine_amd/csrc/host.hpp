@@ -353,6 +353,9 @@ int pair_range_ok(aqe_ctx* c, const int* cols, const int32_t* key_min, const uin
 // One column (cols[1] == 0) or the ordered pair {REGION, PRODUCT} in either order.
 int level_columns_ok(aqe_ctx* c, const int* cols);
 
+// top_host.cpp: aqe_top_from_results behind its argument checks
+void top_from_results(const aqe_group_result* all, uint32_t n_all, uint32_t k, bool descending, aqe_group_result* out, aqe_top_info* info);
+
 // extremes.hip
 void extremes_release(aqe_ctx* c);
 

@@ -22,6 +22,7 @@
 #include "host.hpp"
 #include "key_term.hpp"
 #include "sweep_host.hpp"
+#include "top_order.hpp"
 
 namespace aqe {
 namespace {
@@ -229,6 +230,261 @@ __global__ __launch_bounds__(kFinishThreads) void k_wide_finish(const double* __
 
 static_assert(kMaxWideBins / kFinishThreads <= kFinishThreads, "one thread per earlier workgroup's count");
 
+// ---- top-N groups: ORDER BY the aggregate, LIMIT k (aqe_top_spec of include/aqe_hip.h; the order is top_order.hpp's) ----------
+// Three launches over the (all-reduced) bins, no atomics on device memory and none on floating point:
+//   k_top_keys        one thread per bin: wide_result, the 64-bit rank key of its value (smaller = better; unranked: a sentinel)
+//                     and the ranked bins of each workgroup counted (k_wide_count's pattern).
+//   k_top_select      ONE workgroup: radix select of the listed-th smallest composite (rank key, bin) — 80 bits, ten select passes of
+//                     256-bucket LDS histograms (integer ds_add_u32) over the keys, which the L2 serves; composites are unique, so
+//                     the cut is exact and the tie rule needs no case of its own.  The at most 1024 composites at or below the cut
+//                     go to LDS, a bitonic sort orders them, thread i writes wide_result of the bin of rank i; the smallest composite
+//                     above the cut is `next`.
+//   k_top_contenders  one thread per bin against the last listed group's interval, counted per workgroup by ballots; the host adds
+//                     the at most 256 integers.
+constexpr unsigned kTopMax = AQE_TOP_MAX;
+constexpr unsigned kSelectThreads = 1024, kSelectWaves = kSelectThreads / 64;
+constexpr unsigned kSelectUnroll = 8;  // 16-byte loads of rank keys a thread of k_top_select keeps in flight
+constexpr unsigned kTopKeyPasses = 8, kTopPasses = kTopKeyPasses + 2;  // the rank key's bytes, then the bin's two
+constexpr unsigned kTopBlocksMax = kMaxWideBins / kFinishThreads;
+static_assert(kMaxWideBins <= (1u << 16), "a bin is two radix digits");
+static_assert(kTopMax == kSelectThreads, "one thread per listed group, one per item of the sort");
+
+// What k_top_select leaves for k_top_contenders: the cut — the composite of the last listed group — and how many are listed.
+struct TopCut {
+    u64 key;
+    uint32_t bin;
+    uint32_t listed;
+};
+// The device block the host copies back in one piece (the first `listed` entries of out).
+struct TopBlock {
+    aqe_top_info info;
+    TopCut cut;
+    unsigned ccounts[kTopBlocksMax];  // k_top_contenders' per-workgroup counts
+    aqe_group_result out[kTopMax];
+};
+
+__device__ __forceinline__ aqe_group_result top_result(const double* __restrict__ bins, unsigned b, const WideFinish& fin) {
+    const double* const v = bins + static_cast<size_t>(b) * kWideBin;
+    const int64_t key = fin.pair ? pair_key(fin.g, b) : static_cast<int64_t>(fin.g.kmin_a) + b;
+    return wide_result(v[0], v[1], v[2], v[3], key, fin.shift, fin.pct, fin.agg);
+}
+
+__global__ __launch_bounds__(kFinishThreads) void k_top_keys(const double* __restrict__ bins, unsigned nbins, WideFinish fin, int descending,
+                                                             u64* __restrict__ keys, unsigned* __restrict__ counts) {
+    __shared__ unsigned wsum[kFinishThreads / 64];
+    const unsigned b = blockIdx.x * kFinishThreads + threadIdx.x;
+    u64 rk = kTopUnranked;
+    if (b < nbins) {
+        const double* const v = bins + static_cast<size_t>(b) * kWideBin;
+        if (v[3] > 0.0 && v[0] > 0.0) {
+            const double value = top_result(bins, b, fin).value;
+            rk = value != value ? kTopNaN : top_rank_key(okey_of_bits(static_cast<u64>(__double_as_longlong(value))), descending != 0);  // (-0.0 folded into +0.0)
+        }
+        keys[b] = rk;
+    }
+    const u64 m = __ballot(rk != kTopUnranked);
+    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = static_cast<unsigned>(__popcll(m));
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0;
+        for (unsigned w = 0; w < kFinishThreads / 64; ++w) t += wsum[w];
+        counts[blockIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(kSelectThreads) void k_top_select(const double* __restrict__ bins, unsigned nbins, const u64* __restrict__ keys,
+                                                               const unsigned* __restrict__ counts, unsigned nblocks, WideFinish fin, unsigned k,
+                                                               TopBlock* __restrict__ blk) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned wtot[kSelectWaves];
+    __shared__ unsigned s_digit, s_rank, s_fill;
+    __shared__ u64 skey[kTopMax];
+    __shared__ uint32_t sbin[kTopMax];
+    __shared__ u64 wkey[kSelectWaves];
+    __shared__ uint32_t wbin[kSelectWaves];
+    const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    // the ranked groups: integer sums, any order gives the same number
+    unsigned mine = tid < nblocks ? counts[tid] : 0u;
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+    if (lane == 0) wtot[wave] = mine;
+    skey[tid] = kTopUnranked;  // (what the sort pads with: behind every composite)
+    sbin[tid] = ~0u;
+    if (tid == 0) s_fill = 0;
+    __syncthreads();
+    unsigned groups = 0;
+    for (unsigned w = 0; w < kSelectWaves; ++w) groups += wtot[w];
+    const unsigned listed = groups < k ? groups : k;
+    if (listed == 0) {  // (the same on every thread)
+        if (tid == 0) {
+            aqe_top_info z{};
+            z.groups = groups;
+            blk->info = z;
+            blk->cut = TopCut{0, 0, 0};
+        }
+        return;
+    }
+    // Every key, every thread the same number of times (the callers ballot): a thread takes two neighbouring keys per 16-byte
+    // load and kSelectUnroll loads are in flight before the first is used — one workgroup is bound by the L2's latency, not by
+    // its bandwidth.  The keys' buffer is a whole number of pairs long.
+    const ulonglong2* const keys2 = reinterpret_cast<const ulonglong2*>(keys);
+    auto each_key = [&](auto&& fn) {
+        for (unsigned b0 = 0; b0 < nbins; b0 += kSelectThreads * 2 * kSelectUnroll) {
+            ulonglong2 kv[kSelectUnroll];
+#pragma unroll
+            for (unsigned u = 0; u < kSelectUnroll; ++u) {
+                const unsigned b = b0 + (u * kSelectThreads + tid) * 2;
+                kv[u] = b < nbins ? keys2[b >> 1] : ulonglong2{kTopUnranked, kTopUnranked};
+            }
+#pragma unroll
+            for (unsigned u = 0; u < kSelectUnroll; ++u) {
+                const unsigned b = b0 + (u * kSelectThreads + tid) * 2;
+                fn(b < nbins, kv[u].x, b);
+                fn(b + 1 < nbins, kv[u].y, b + 1);
+            }
+        }
+    };
+    // the listed-th smallest composite: its digits from the top, the rank narrowing to the chosen bucket's members
+    u64 pkey = 0;
+    uint32_t pbin = 0;
+    unsigned r = listed - 1;  // zero-based among the candidates
+    for (unsigned pass = 0; pass < kTopPasses; ++pass) {
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        const bool on_key = pass < kTopKeyPasses;
+        const unsigned shift = on_key ? 56u - 8u * pass : (pass == kTopKeyPasses ? 8u : 0u);
+        const u64 key_mask = pass == 0 ? 0ull : (on_key ? ~0ull << (64u - 8u * pass) : ~0ull);  // the key's digits chosen so far
+        const uint32_t bin_mask = pass == kTopPasses - 1 ? 0xff00u : 0u;                          // the bin's
+        each_key([&](bool valid, u64 key, unsigned b) {
+            const bool cand = valid && ((key ^ pkey) & key_mask) == 0 && ((b ^ pbin) & bin_mask) == 0;
+            const unsigned digit = on_key ? static_cast<unsigned>(key >> shift) & 255u : (b >> shift) & 255u;
+            // values of one magnitude share their top digits: a wave whose candidates agree adds once
+            const u64 cm = __ballot(cand);
+            if (cm == 0) return;
+            const unsigned first = __shfl(digit, static_cast<int>(__ffsll(static_cast<long long>(cm)) - 1), 64);
+            if (__ballot(cand && digit != first) == 0) {
+                if (lane == 0) atomicAdd(&hist[first], static_cast<unsigned>(__popcll(cm)));
+            } else if (cand) {
+                atomicAdd(&hist[digit], 1u);
+            }
+        });
+        __syncthreads();
+        unsigned c = 0, incl = 0;
+        if (tid < 256) {
+            c = incl = hist[tid];
+            for (int off = 1; off < 64; off <<= 1) {
+                const unsigned t = __shfl_up(incl, off, 64);
+                if (lane >= static_cast<unsigned>(off)) incl += t;
+            }
+            if (lane == 63) wtot[wave] = incl;
+        }
+        __syncthreads();
+        if (tid < 256) {
+            for (unsigned w = 0; w < wave; ++w) incl += wtot[w];
+            const unsigned excl = incl - c;
+            if (r >= excl && r < incl) {  // one bucket: the counts cover the rank (listed <= groups <= candidates)
+                s_digit = tid;
+                s_rank = r - excl;
+            }
+        }
+        __syncthreads();
+        r = s_rank;
+        if (on_key) pkey |= static_cast<u64>(s_digit) << shift;
+        else pbin |= s_digit << shift;
+    }
+    // at or below the cut: into LDS (any order: the sort follows); above it: the smallest is `next`
+    u64 nkey = kTopUnranked;
+    uint32_t nbin = ~0u;
+    each_key([&](bool valid, u64 key, unsigned b) {
+        if (!valid) return;
+        if (!top_before(pkey, pbin, key, b)) {
+            const unsigned slot = atomicAdd(&s_fill, 1u);
+            if (slot < kTopMax) {
+                skey[slot] = key;
+                sbin[slot] = b;
+            }
+        } else if (top_before(key, b, nkey, nbin)) {
+            nkey = key;
+            nbin = b;
+        }
+    });
+    for (int off = 32; off > 0; off >>= 1) {
+        const u64 ok = __shfl_xor(nkey, off, 64);
+        const uint32_t ob = __shfl_xor(nbin, off, 64);
+        if (top_before(ok, ob, nkey, nbin)) {
+            nkey = ok;
+            nbin = ob;
+        }
+    }
+    if (lane == 0) {
+        wkey[wave] = nkey;
+        wbin[wave] = nbin;
+    }
+    // bitonic sort of the smallest power of two of items that holds the listed ones (the rest is padding)
+    unsigned m = 1;
+    while (m < listed) m <<= 1;
+    for (unsigned size = 2; size <= m; size <<= 1) {
+        for (unsigned stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            const unsigned other = tid ^ stride;
+            if (tid < m && other > tid) {
+                const u64 ka = skey[tid], kb = skey[other];
+                const uint32_t ba = sbin[tid], bb = sbin[other];
+                const bool up = (tid & size) == 0;
+                if (top_before(kb, bb, ka, ba) == up) {
+                    skey[tid] = kb;
+                    sbin[tid] = bb;
+                    skey[other] = ka;
+                    sbin[other] = ba;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < listed) {
+        const uint32_t b = sbin[tid];
+        if (b < nbins) blk->out[tid] = top_result(bins, b, fin);
+    }
+    if (tid == 0) {
+        for (unsigned w = 1; w < kSelectWaves; ++w) {
+            if (top_before(wkey[w], wbin[w], nkey, nbin)) {
+                nkey = wkey[w];
+                nbin = wbin[w];
+            }
+        }
+        aqe_top_info info{};
+        info.groups = groups;
+        info.listed = listed;
+        info.has_next = groups > listed ? 1 : 0;
+        if (info.has_next && nbin < nbins) info.next = top_result(bins, nbin, fin);
+        blk->info = info;
+        blk->cut = TopCut{pkey, pbin, listed};
+    }
+}
+
+__global__ __launch_bounds__(kFinishThreads) void k_top_contenders(const double* __restrict__ bins, unsigned nbins, const u64* __restrict__ keys, WideFinish fin,
+                                                                   int descending, TopBlock* __restrict__ blk) {
+    __shared__ unsigned wsum[kFinishThreads / 64];
+    const unsigned b = blockIdx.x * kFinishThreads + threadIdx.x;
+    const TopCut cut = blk->cut;
+    bool flag = false;
+    if (cut.listed > 0 && cut.listed <= kTopMax && b < nbins) {
+        const u64 key = keys[b];
+        if (key != kTopUnranked && top_before(cut.key, cut.bin, key, b)) {  // ranked and unlisted
+            const aqe_group_result r = top_result(bins, b, fin);
+            const aqe_group_result* const last = blk->out + (cut.listed - 1);
+            flag = descending ? r.ci_upper >= last->ci_lower : r.ci_lower <= last->ci_upper;  // (false with a NaN on either side)
+        }
+    }
+    const u64 m = __ballot(flag);
+    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = static_cast<unsigned>(__popcll(m));
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0;
+        for (unsigned w = 0; w < kFinishThreads / 64; ++w) t += wsum[w];
+        blk->ccounts[blockIdx.x] = t;
+    }
+}
+
 const char* column_name(int column) { return column == AQE_GROUP_REGION ? "region" : "product_id"; }
 
 // The bound and its refusal, in one place: nbins of one column's span (ncols == 1) or of the pair's, and the slices of `slice`
@@ -279,6 +535,12 @@ struct aqe_wide_scratch {
     unsigned* d_counts = nullptr;  // [kMaxWideBins / kFinishThreads + 1]: per finishing workgroup, then the number of groups
     unsigned* h_count = nullptr;   // pinned
     bool lds_opted = false;        // every instantiation of k_group_wide may take kWideMaxSlice bins of dynamic LDS
+    // top-N groups (aqe_grouped_top_finish)
+    unsigned long long* d_tkeys = nullptr;  // [nbins] rank keys
+    size_t tkeys_bytes = 0;
+    unsigned* d_tcounts = nullptr;          // [kTopBlocksMax] ranked bins per workgroup of k_top_keys
+    aqe::TopBlock* d_top = nullptr;         // info, the cut, the contenders' counts, the listed groups
+    aqe::TopBlock* h_top = nullptr;         // its host mirror (pinned)
 };
 
 namespace aqe {
@@ -508,6 +770,83 @@ int sweep_prologue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, aqe_
     return rc;
 }
 
+// The single-GPU entries' sweep: the checks, the table's key ranges (this context holds all of it) and the bins of the whole
+// sample into the context's d_bins on its stream.  *empty: an empty table — no groups, nothing swept.
+int sweep_whole_table(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int* columns, int ncols, GroupCols* g, bool* empty) {
+    *empty = false;
+    int cols[2];
+    int rc = columns_ok(c, columns, ncols, cols);
+    if (rc != AQE_OK) return rc;
+    aqe_plan* p = nullptr;
+    rc = sweep_prologue(c, f, q, &p);
+    if (rc != AQE_OK) return rc;
+    int32_t kmin[2] = {0, 0};
+    uint32_t span[2] = {0, 1};
+    for (int i = 0; i < ncols; ++i) {
+        int32_t lo = 0, hi = -1;
+        rc = aqe_group_key_range(c, cols[i], &lo, &hi);
+        if (rc != AQE_OK) return rc;
+        if (hi < lo) { *empty = true; return AQE_OK; }
+        kmin[i] = lo;
+        span[i] = static_cast<uint32_t>(std::min<int64_t>(static_cast<int64_t>(hi) - lo + 1, 0xffffffffll));  // (2^32 keys: refused as 2^32 - 1 would be)
+    }
+    const uint32_t slice = call_slice();
+    uint32_t nslices = 0;
+    rc = range_ok(c, cols, kmin, span, g, &nslices, slice);
+    if (rc != AQE_OK) return rc;
+    aqe_wide_scratch* sc = c->wide;
+    rc = grow(c, &sc->d_bins, &sc->bins_bytes, static_cast<size_t>(g->nbins()) * kWideBin * sizeof(double));
+    if (rc == AQE_OK) rc = enqueue_bins(c, p, f, *g, slice, sc->d_bins, c->stream);
+    return rc;
+}
+
+// aqe_top_spec's bound, before anything is launched.
+int top_spec_ok(aqe_ctx* c, const aqe_top_spec* spec) {
+    if (!spec) return fail(c, AQE_ERR_INVALID, "null argument");
+    if (spec->k == 0 || spec->k > kTopMax)
+        return fail(c, AQE_ERR_INVALID, "ORDER BY ... LIMIT " + std::to_string(spec->k) + ": the top groups take a limit of 1 .. " + std::to_string(kTopMax));
+    return AQE_OK;
+}
+
+int ensure_top(aqe_ctx* c, uint32_t nbins) {
+    aqe_wide_scratch* s = c->wide;
+    int rc = grow(c, &s->d_tkeys, &s->tkeys_bytes, (static_cast<size_t>(nbins) + 1) / 2 * 2 * sizeof(u64));  // (whole pairs: k_top_select loads two)
+    if (rc != AQE_OK) return rc;
+    if (!s->d_tcounts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_tcounts), sizeof(unsigned) * kTopBlocksMax));
+    if (!s->d_top) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_top), sizeof(TopBlock)));
+    if (!s->h_top) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_top), sizeof(TopBlock), hipHostMallocDefault));
+    return AQE_OK;
+}
+
+// The rank keys, the selection and the contenders over dev_bins on `s`, then info and the listed groups: one copy of the
+// block's head and spec->k entries, 74 856 bytes at most.  The caller has checked spec.
+int top_groups(aqe_ctx* c, const aqe_query* q, const GroupCols& g, const double* dev_bins, hipStream_t s, const aqe_top_spec* spec, aqe_group_result* out,
+               aqe_top_info* info) {
+    const uint32_t nbins = g.nbins();
+    int rc = ensure_top(c, nbins);
+    if (rc != AQE_OK) return rc;
+    aqe_wide_scratch* sc = c->wide;
+    const unsigned blocks = (nbins + kFinishThreads - 1) / kFinishThreads;
+    const WideFinish fin = finish_for(c, q, g);
+    const int desc = spec->descending ? 1 : 0;
+    hipLaunchKernelGGL(k_top_keys, dim3(blocks), dim3(kFinishThreads), 0, s, dev_bins, nbins, fin, desc, sc->d_tkeys, sc->d_tcounts);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_top_select, dim3(1), dim3(kSelectThreads), 0, s, dev_bins, nbins, sc->d_tkeys, sc->d_tcounts, blocks, fin, spec->k, sc->d_top);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_top_contenders, dim3(blocks), dim3(kFinishThreads), 0, s, dev_bins, nbins, sc->d_tkeys, fin, desc, sc->d_top);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(sc->h_top, sc->d_top, offsetof(TopBlock, out) + sizeof(aqe_group_result) * spec->k, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const TopBlock* h = sc->h_top;
+    *info = h->info;
+    if (info->listed > spec->k) return fail(c, AQE_ERR_INTERNAL, "top groups: the selection listed more groups than asked for");
+    uint32_t contenders = 0;
+    for (unsigned b = 0; b < blocks; ++b) contenders += h->ccounts[b];  // integers, in workgroup order
+    info->contenders = contenders;
+    if (info->listed) std::memcpy(out, h->out, sizeof(aqe_group_result) * info->listed);
+    return AQE_OK;
+}
+
 }  // namespace
 
 void wide_release(aqe_ctx* c) {
@@ -521,6 +860,10 @@ void wide_release(aqe_ctx* c) {
     (void)hipFree(s->d_counts);
     if (s->h_groups) (void)hipHostFree(s->h_groups);
     if (s->h_count) (void)hipHostFree(s->h_count);
+    (void)hipFree(s->d_tkeys);
+    (void)hipFree(s->d_tcounts);
+    (void)hipFree(s->d_top);
+    if (s->h_top) (void)hipHostFree(s->h_top);
     delete s;
     c->wide = nullptr;
 }
@@ -543,33 +886,11 @@ int aqe_reduce_grouped_wide(aqe_ctx* c, const aqe_key_filter* f, const aqe_query
     if (!c) return AQE_ERR_INVALID;
     if (!q || !n_groups || (cap && !out)) return fail(c, AQE_ERR_INVALID, "null argument");
     *n_groups = 0;
-    int cols[2];
-    int rc = columns_ok(c, columns, ncols, cols);
-    if (rc != AQE_OK) return rc;
-    aqe_plan* p = nullptr;
-    rc = sweep_prologue(c, f, q, &p);
-    if (rc != AQE_OK) return rc;
-    // the table's key ranges (this context holds all of it)
-    int32_t kmin[2] = {0, 0};
-    uint32_t span[2] = {0, 1};
-    for (int i = 0; i < ncols; ++i) {
-        int32_t lo = 0, hi = -1;
-        rc = aqe_group_key_range(c, cols[i], &lo, &hi);
-        if (rc != AQE_OK) return rc;
-        if (hi < lo) return AQE_OK;  // an empty table: no groups
-        kmin[i] = lo;
-        span[i] = static_cast<uint32_t>(std::min<int64_t>(static_cast<int64_t>(hi) - lo + 1, 0xffffffffll));  // (2^32 keys: refused as 2^32 - 1 would be)
-    }
-    const uint32_t slice = call_slice();
     GroupCols g;
-    uint32_t nslices = 0;
-    rc = range_ok(c, cols, kmin, span, &g, &nslices, slice);
-    if (rc != AQE_OK) return rc;
-    aqe_wide_scratch* sc = c->wide;
-    rc = grow(c, &sc->d_bins, &sc->bins_bytes, static_cast<size_t>(g.nbins()) * kWideBin * sizeof(double));
-    if (rc == AQE_OK) rc = enqueue_bins(c, p, f, g, slice, sc->d_bins, c->stream);
-    if (rc != AQE_OK) return rc;
-    return finish_groups(c, q, g, sc->d_bins, c->stream, out, cap, n_groups);
+    bool empty = false;
+    const int rc = sweep_whole_table(c, f, q, columns, ncols, &g, &empty);
+    if (rc != AQE_OK || empty) return rc;
+    return finish_groups(c, q, g, c->wide->d_bins, c->stream, out, cap, n_groups);
 }
 
 int aqe_grouped_wide_enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int* columns, int ncols, const int32_t* key_min,
@@ -607,6 +928,50 @@ int aqe_grouped_wide_finish(aqe_ctx* c, const aqe_query* q, int ncols, const int
     rc = ensure_scratch(c);
     if (rc != AQE_OK) return rc;
     return finish_groups(c, q, g, dev_bins, stream_of(c, stream), out, cap, n_groups);
+}
+
+int aqe_reduce_grouped_top(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int* columns, int ncols, const aqe_top_spec* spec,
+                           aqe_group_result* out, aqe_top_info* info) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !out || !info) return fail(c, AQE_ERR_INVALID, "null argument");
+    std::memset(info, 0, sizeof *info);
+    int rc = top_spec_ok(c, spec);
+    if (rc != AQE_OK) return rc;
+    GroupCols g;
+    bool empty = false;
+    rc = sweep_whole_table(c, f, q, columns, ncols, &g, &empty);
+    if (rc != AQE_OK || empty) return rc;
+    return top_groups(c, q, g, c->wide->d_bins, c->stream, spec, out, info);
+}
+
+int aqe_grouped_top_finish(aqe_ctx* c, const aqe_query* q, int ncols, const int32_t* key_min, const uint32_t* span, const double* dev_bins, void* stream,
+                           const aqe_top_spec* spec, aqe_group_result* out, aqe_top_info* info) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !out || !info || !dev_bins) return fail(c, AQE_ERR_INVALID, "bad argument");
+    std::memset(info, 0, sizeof *info);
+    int rc = top_spec_ok(c, spec);
+    if (rc != AQE_OK) return rc;
+    if (q->agg != AQE_SUM && q->agg != AQE_AVG && q->agg != AQE_COUNT) return fail(c, AQE_ERR_INVALID, "GROUP BY (wide) takes SUM, AVG or COUNT");
+    if (ncols != 1 && ncols != 2) return fail(c, AQE_ERR_INVALID, "GROUP BY (wide): one group column or a pair of them");
+    const int cols[2] = {AQE_GROUP_REGION, ncols == 2 ? AQE_GROUP_PRODUCT : 0};  // (the finish reads the ranges, not the columns)
+    GroupCols g;
+    uint32_t nslices = 0;
+    rc = range_ok(c, cols, key_min, span, &g, &nslices, 0);
+    if (rc != AQE_OK) return rc;
+    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
+    if (!(q->sample_percent > 0.0)) return fail(c, AQE_ERR_INVALID, "sample_percent must be positive");
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    return top_groups(c, q, g, dev_bins, stream_of(c, stream), spec, out, info);
+}
+
+int aqe_top_from_results(const aqe_group_result* all, uint32_t n_all, const aqe_top_spec* spec, aqe_group_result* out, aqe_top_info* info) {
+    if (!out || !info || (n_all && !all)) return fail(nullptr, AQE_ERR_INVALID, "null argument");
+    const int rc = top_spec_ok(nullptr, spec);  // (no context: aqe_last_error(NULL) has the text)
+    if (rc != AQE_OK) return rc;
+    top_from_results(all, n_all, spec->k, spec->descending != 0, out, info);
+    return AQE_OK;
 }
 
 }  // extern "C"

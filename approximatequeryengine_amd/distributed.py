@@ -428,6 +428,31 @@ def sharded_group_by_pair(engine, query, columns, bins, all_reduce_sum: Callable
         return engine.grouped_pair_spread_finish(query, kind, kmin, span, b.data_ptr(), stream)
 
 
+def _wide_swept_bins(engine, query, columns, bins, all_reduce_sum, all_reduce_max, stream, key_filter):
+    """The collective steps sharded_group_by_wide and sharded_group_by_top share, on ``stream``: ONE MAX all-reduce of
+    [-minA, maxA(, -minB, maxB)], the bins every rank derives from it (engine.wide_plan: more than 65 536 is refused on every rank
+    alike, before the sweep), this rank's part of the sample into them, ONE all-reduce SUM.  (key_min, span, the nbins x WIDE_BIN
+    doubles of ``bins``), or None for an empty table."""
+    from ._native import WIDE_BIN
+    from .engine import wide_plan
+    cols = [int(c) for c in columns]
+    ranges = [engine.group_key_range(c) for c in cols]
+    rng = bins.new_tensor([v for lo, hi in ranges for v in (-float(lo), float(hi))])
+    all_reduce_max(rng)
+    r = [int(v) for v in rng.tolist()]
+    kmin, kmax = [-v for v in r[0::2]], r[1::2]
+    if any(hi < lo for lo, hi in zip(kmin, kmax)):
+        return None
+    span = [hi - lo + 1 for lo, hi in zip(kmin, kmax)]
+    nbins = wide_plan(span)[0]
+    if bins.numel() < WIDE_BIN * nbins:
+        raise ValueError(f"bin buffer holds {bins.numel()} doubles, {WIDE_BIN * nbins} needed")
+    b = bins[: WIDE_BIN * nbins]
+    engine.grouped_wide_enqueue_bins(query, cols, kmin, span, b.data_ptr(), stream, key_filter)
+    all_reduce_sum(b)
+    return kmin, span, b
+
+
 def sharded_group_by_wide(engine, query, columns, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None,
                           max_groups: int = 65536):
     """GROUP BY over wide key ranges across ranks, collective: ``columns`` is one key column or the ordered pair (A, B).  The
@@ -439,26 +464,29 @@ def sharded_group_by_wide(engine, query, columns, bins, all_reduce_sum: Callable
 
     bins    float64 tensor on the engine's device with room for WIDE_BIN * nbins doubles (at most WIDE_BIN * 65 536)
     stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
-    from ._native import WIDE_BIN
-    from .engine import wide_plan
     stream = _stream_for(stream, bins)
-    cols = [int(c) for c in columns]
     with _torch_on(stream, bins):
-        ranges = [engine.group_key_range(c) for c in cols]
-        rng = bins.new_tensor([v for lo, hi in ranges for v in (-float(lo), float(hi))])
-        all_reduce_max(rng)
-        r = [int(v) for v in rng.tolist()]
-        kmin, kmax = [-v for v in r[0::2]], r[1::2]
-        if any(hi < lo for lo, hi in zip(kmin, kmax)):
+        agreed = _wide_swept_bins(engine, query, columns, bins, all_reduce_sum, all_reduce_max, stream, key_filter)
+        if agreed is None:
             return []  # an empty table
-        span = [hi - lo + 1 for lo, hi in zip(kmin, kmax)]
-        nbins = wide_plan(span)[0]
-        if bins.numel() < WIDE_BIN * nbins:
-            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {WIDE_BIN * nbins} needed")
-        b = bins[: WIDE_BIN * nbins]
-        engine.grouped_wide_enqueue_bins(query, cols, kmin, span, b.data_ptr(), stream, key_filter)
-        all_reduce_sum(b)
+        kmin, span, b = agreed
         return engine.grouped_wide_finish(query, kmin, span, b.data_ptr(), stream, max_groups)
+
+
+def sharded_group_by_top(engine, query, columns, bins, all_reduce_sum: Callable, all_reduce_max: Callable, k: int, descending: bool = True,
+                         stream: int = 0, key_filter=None):
+    """ORDER BY the aggregate LIMIT ``k`` over a GROUP BY across ranks, collective: sharded_group_by_wide's steps unchanged — ONE
+    MAX all-reduce of the key ranges, every rank's part of the sample into nbins x WIDE_BIN sums (aqe_grouped_wide_enqueue_bins),
+    ONE all-reduce SUM — then every rank selects the k best groups from the same bins on its device (aqe_grouped_top_finish):
+    an integer selection, so every rank returns the same (list of GroupResult in rank order, TopInfo), bit for bit.  An empty
+    table gives ([], None).  ``bins`` and ``stream`` as sharded_group_by_wide takes them."""
+    stream = _stream_for(stream, bins)
+    with _torch_on(stream, bins):
+        agreed = _wide_swept_bins(engine, query, columns, bins, all_reduce_sum, all_reduce_max, stream, key_filter)
+        if agreed is None:
+            return [], None  # an empty table
+        kmin, span, b = agreed
+        return engine.grouped_top_finish(query, kmin, span, b.data_ptr(), k, descending, stream)
 
 
 def sharded_extremes(engine, query, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):

@@ -612,6 +612,27 @@ class Engine:
                                                     C.c_void_p(dev_bins_ptr), C.c_void_p(stream), out, max_groups, C.byref(n)))
         return list((nat.GroupResult * n.value).from_buffer_copy(out)) if n.value else []
 
+    # -- top-N groups (aqe_reduce_grouped_top / aqe_grouped_top_finish): ORDER BY the aggregate, LIMIT k, selected on the device --
+    def reduce_grouped_top(self, query: Query, columns: Sequence[int], k: int, descending: bool = True, key_filter: "Optional[nat.KeyFilter]" = None):
+        """The ``k`` (1 .. nat.TOP_MAX) best groups of ``columns`` (one column, or the ordered pair; any span up to 65 536 bins) by
+        the query's SUM / AVG / COUNT: (list of GroupResult in rank order, TopInfo).  Only groups with n > 0 are ranked; equal
+        values are ordered by ascending key; ``TopInfo.contenders`` counts the unlisted groups whose interval meets the last
+        listed one's."""
+        cols = [int(c) for c in columns]
+        spec, out, info = _top_spec(k, descending), (nat.GroupResult * _top_room(k))(), nat.TopInfo()
+        self._chk(nat.lib().aqe_reduce_grouped_top(self._h, _filter_ref(key_filter), C.byref(query), _pair(C.c_int, _two(cols, 0)), len(cols),
+                                                   C.byref(spec), out, C.byref(info)))
+        return list(out[: info.listed]), info
+
+    def grouped_top_finish(self, query: Query, key_min: Sequence[int], span: Sequence[int], dev_bins_ptr: int, k: int, descending: bool = True,
+                           stream: int = 0):
+        """The same over the (all-reduced) bins of grouped_wide_enqueue_bins; synchronises ``stream``."""
+        ncols = len(list(span))
+        spec, out, info = _top_spec(k, descending), (nat.GroupResult * _top_room(k))(), nat.TopInfo()
+        self._chk(nat.lib().aqe_grouped_top_finish(self._h, C.byref(query), ncols, _pair(C.c_int32, _two(key_min, 0)), _pair(C.c_uint32, _two(span, 1)),
+                                                   C.c_void_p(dev_bins_ptr), C.c_void_p(stream), C.byref(spec), out, C.byref(info)))
+        return list(out[: info.listed]), info
+
     # -- GROUP BY to an error threshold (aqe_reduce_grouped_error and its stepwise multi-GPU form) --
     def reduce_grouped_error(self, query: Query, columns: Sequence[int], error_percent: float, max_percent: float = 100.0,
                              key_filter: "Optional[nat.KeyFilter]" = None, max_groups: int = 1024):
@@ -900,6 +921,26 @@ def time_plan(spec: "nat.TimeSpec", tmin: int, tmax: int) -> Tuple[int, int]:
     if rc != nat.OK:
         raise nat.AqeError(rc, "BUCKET: the width must be at least 1 and the window must have t_lo <= t_hi")
     return first.value, n.value
+
+
+def _top_spec(k, descending) -> "nat.TopSpec":
+    """aqe_top_spec of a limit as given: a value the 32 bits cannot hold is passed as one the library refuses by name."""
+    k = int(k)
+    return nat.TopSpec(k if 0 <= k <= 0xFFFFFFFF else 0xFFFFFFFF, 1 if descending else 0)
+
+
+def _top_room(k) -> int:
+    return min(max(int(k), 1), nat.TOP_MAX)  # (a k out of range is refused before anything is written)
+
+
+def top_from_results(results, k: int, descending: bool = True):
+    """aqe_top_from_results, host only: the order, cut, ``next`` and ``contenders`` of the top-N groups over a finished list of
+    GroupResult (ascending, as grouped_wide_finish returns it): (list of GroupResult in rank order, TopInfo)."""
+    results = list(results)
+    arr = (nat.GroupResult * max(len(results), 1))(*results)
+    spec, out, info = _top_spec(k, descending), (nat.GroupResult * _top_room(k))(), nat.TopInfo()
+    nat.check(nat.lib().aqe_top_from_results(arr, len(results), C.byref(spec), out, C.byref(info)))
+    return list(out[: info.listed]), info
 
 
 def wide_plan(span: Sequence[int], slice_bins: int = 0) -> Tuple[int, int]:

@@ -1240,6 +1240,54 @@ AQE_API int aqe_grouped_wide_enqueue_bins(aqe_ctx* ctx, const aqe_key_filter* fi
 AQE_API int aqe_grouped_wide_finish(aqe_ctx* ctx, const aqe_query* q, int ncols, const int32_t key_min[2], const uint32_t span[2], const double* dev_bins,
                                     void* stream, aqe_group_result* out, uint32_t cap, uint32_t* n_groups);
 
+/* ---- Top-N groups: ORDER BY the aggregate, LIMIT k, selected on the device (wide_group.hip, top_host.cpp) --------------------
+ * "The ten products with the largest revenue" of a GROUP BY over up to 65 536 bins, without moving every group to the host:
+ * the bins {n, P1, P2, visited} of the wide sweep stay in device memory, the k best groups are selected there and only they
+ * (at most AQE_TOP_MAX entries of 72 bytes) and aqe_top_info are copied.
+ *
+ * Ranked groups.  A group is ranked when visited > 0 and n > 0: a group that is sampled but has no row passing the WHERE does
+ * not exist in SQL's result (and its AVG of 0 must not win an ascending order).
+ *
+ * Order.  By `value`, the figure aqe_grouped_wide_finish reports for q->agg (SUM, AVG or COUNT), compared as IEEE doubles;
+ * -0.0 and +0.0 are equal; a NaN value ranks after every other value in BOTH directions.  Equal values — and NaN among
+ * themselves — are ordered by ascending key (a pair: ascending (a, b), the order aqe_grouped_wide_finish lists in), which also
+ * decides which members of a tie fall on the listed side of the cut.  The selection is on integers: identical bins list
+ * identical groups, run after run and rank after rank.
+ *
+ * Output.  out (room for spec->k entries) gets out[0 .. listed) in rank order, every entry bit-identical to the one
+ * aqe_grouped_wide_finish writes for that key from the same bins.  info->contenders says whether the cut is settled: with L the
+ * last listed group, the number of ranked, unlisted groups with ci_upper >= L.ci_lower (descending) or ci_lower <= L.ci_upper
+ * (ascending); a comparison involving NaN is false; 0 when nothing is unlisted.  COUNT has no margin: its contenders are the
+ * groups tied with L.
+ *
+ * Status.  spec->k == 0 or spec->k > AQE_TOP_MAX: AQE_ERR_INVALID, the message names both numbers, nothing is launched.  No
+ * ranked group (also: nothing sampled, an empty table): AQE_OK with listed == 0.  An aggregate other than SUM / AVG / COUNT, a
+ * refused sampler, spans past 65 536 bins, a refusal of the dynamic LDS: the status and text of aqe_reduce_grouped_wide. */
+#define AQE_TOP_MAX 1024
+typedef struct aqe_top_spec {
+    uint32_t k;         /* 1 .. AQE_TOP_MAX */
+    int32_t descending; /* non-zero: the largest values first (SQL's DESC); 0: the smallest first */
+} aqe_top_spec;
+typedef struct aqe_top_info {
+    uint32_t groups;       /* ranked groups: visited > 0 and n > 0                              */
+    uint32_t listed;       /* min(k, groups): entries written to out                            */
+    uint32_t contenders;   /* unlisted ranked groups whose interval meets the last listed one's */
+    int32_t has_next;      /* groups > listed                                                   */
+    aqe_group_result next; /* the best unlisted group (rank listed + 1) when has_next, else zeros */
+} aqe_top_info;
+/* Single GPU, synchronous: the sweep of aqe_reduce_grouped_wide — unchanged, at ANY span up to 65 536 bins (1024 or fewer are
+ * one slice) — then the selection.  filter, q, columns, ncols: as aqe_reduce_grouped_wide takes them. */
+AQE_API int aqe_reduce_grouped_top(aqe_ctx* ctx, const aqe_key_filter* filter /* NULL: none */, const aqe_query* q, const int columns[2], int ncols,
+                                   const aqe_top_spec* spec, aqe_group_result* out, aqe_top_info* info);
+/* Multi-GPU: over the bins of aqe_grouped_wide_enqueue_bins after the all-reduce SUM, in place of aqe_grouped_wide_finish (or
+ * beside it: the bins are only read).  Synchronises `stream`.  Every rank lists the same groups, bit for bit. */
+AQE_API int aqe_grouped_top_finish(aqe_ctx* ctx, const aqe_query* q, int ncols, const int32_t key_min[2], const uint32_t span[2], const double* dev_bins,
+                                   void* stream, const aqe_top_spec* spec, aqe_group_result* out, aqe_top_info* info);
+/* Host only, no GPU and no context: the same order, cut, `next` and `contenders` over a finished list all[0 .. n_all) as
+ * aqe_grouped_wide_finish writes it (ascending: the position breaks ties).  all may be NULL when n_all == 0.
+ * AQE_ERR_INVALID for a null argument or a k outside 1 .. AQE_TOP_MAX; aqe_last_error(NULL) has the text. */
+AQE_API int aqe_top_from_results(const aqe_group_result* all, uint32_t n_all, const aqe_top_spec* spec, aqe_group_result* out, aqe_top_info* info);
+
 #ifdef __cplusplus
 }
 #endif
