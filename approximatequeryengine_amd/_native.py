@@ -65,6 +65,7 @@ DISTINCT_SKETCH, DISTINCT_EXACT_KEYS = 0, 1
 DISTINCT_VEC_HEAD, DISTINCT_SLOTS = 2, 8192  # [visited, n] for a SUM all-reduce, then slot[0 .. 8192) for a MAX all-reduce
 SUMMARY_VEC, SUMMARY_VEC_SUM = 12, 10  # the SPREAD_VEC layout + {0, 0} for a SUM all-reduce, then {-min, max} for a MAX all-reduce
 TIME_BIN, TIME_MAX_BUCKETS, TIME_MAX_SPAN = 4, 1024, 2 ** 31 - 1  # {n, P1, P2, visited} per time bucket; the limits of aqe_time_plan
+SERIES_BIN, SERIES_MAX_BINS = 4, 65536  # {n, P1, P2, visited} per cell of a per-key time series; the bound of aqe_time_group_plan
 WIDE_BIN, WIDE_MAX_BINS, WIDE_SLICE_DEFAULT = 4, 65536, 2048  # {n, P1, P2, visited} per bin of the wide GROUP BY; the bound and default slice of aqe_wide_plan
 TOP_MAX = 1024  # the largest LIMIT of the top-N groups (aqe_top_spec.k)
 KEYTERM_NONE, KEYTERM_RANGE, KEYTERM_BITMAP = 0, 1, 2
@@ -104,6 +105,15 @@ class Family(C.Structure):
 
 class GroupResult(C.Structure):
     _fields_ = [("key", C.c_int64), ("n", C.c_uint64), ("visited", C.c_uint64), ("sum", C.c_double), ("sumsq", C.c_double),
+                ("mean", C.c_double), ("value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SeriesResult(C.Structure):
+    """aqe_series_result: one cell (key, time bucket) of a per-key time series; ``start`` is the bucket's start."""
+    _fields_ = [("key", C.c_int64), ("start", C.c_int64), ("n", C.c_uint64), ("visited", C.c_uint64), ("sum", C.c_double), ("sumsq", C.c_double),
                 ("mean", C.c_double), ("value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double)]
 
     def as_dict(self):
@@ -393,6 +403,11 @@ def lib() -> C.CDLL:
         "aqe_reduce_grouped_top": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), C.c_int, P(TopSpec), P(GroupResult), P(TopInfo)]),
         "aqe_grouped_top_finish": (C.c_int, [vp, P(Query), C.c_int, P(i32), P(u32), vp, vp, P(TopSpec), P(GroupResult), P(TopInfo)]),
         "aqe_top_from_results": (C.c_int, [P(GroupResult), u32, P(TopSpec), P(GroupResult), P(TopInfo)]),
+        "aqe_time_group_plan": (C.c_int, [P(TimeSpec), C.c_int64, C.c_int64, i32, i32, u32, P(C.c_int64), P(u32), P(u32), P(u32)]),
+        "aqe_reduce_time_groups": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, P(TimeSpec), P(SeriesResult), u32, P(u32)]),
+        "aqe_time_groups_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, P(TimeSpec), C.c_int64, C.c_int64, i32, u32, vp, vp]),
+        "aqe_time_groups_finish": (C.c_int, [vp, P(Query), C.c_int, P(TimeSpec), C.c_int64, C.c_int64, i32, u32, vp, vp, P(SeriesResult), u32, P(u32)]),
+        "aqe_time_groups_from_bins": (C.c_int, [P(dbl), P(Query), dbl, P(TimeSpec), C.c_int64, C.c_int64, i32, u32, P(SeriesResult), u32, P(u32)]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),

@@ -130,7 +130,7 @@ class BucketEstimate(GroupEstimate):
 
     def __init__(self, r):
         super().__init__(r)
-        self.start, self.visited = int(r.key), int(r.visited)
+        self.start, self.visited = int(getattr(r, "start", r.key)), int(r.visited)  # (a cell of a per-key series carries its start beside the key)
 
     def __repr__(self):
         return f"BucketEstimate(start={self.start}, value={self.value:.6g}, ci=[{self.ci_lower:.6g}, {self.ci_upper:.6g}], n={self.n})"
@@ -1142,7 +1142,7 @@ class CustomBPlusDB:
     def approx_time_series(self, agg: str, width: int, origin: int = 0, time_between: Optional[Tuple[int, int]] = None,
                            sample_percent: float = 10.0, method: str = "rowid", where: Optional[Tuple[float, float]] = None,
                            id_between: Optional[Tuple[int, int]] = None, key_where: Optional[dict] = None, seed: int = 42, num_threads: int = 4,
-                           block_size: int = 1000) -> "dict[int, BucketEstimate]":
+                           block_size: int = 1000, group_by: Optional[str] = None) -> "dict[int, BucketEstimate]":
         """APPROX <agg>(amount) ... GROUP BY BUCKET(timestamp, width[, origin]): SUM / AVG / COUNT per time bucket with a 95 %
         interval, from ONE sweep of the sampled rows (aqe_reduce_time_buckets).  bucket(ts) = floor((ts - origin) / width); the
         result is an ordered ``dict`` keyed by the bucket's start, origin + b * width, ascending — only buckets with a sampled row;
@@ -1151,11 +1151,22 @@ class CustomBPlusDB:
         on ONE key column.  Estimates as approx_group_by.  method: "rowid" (default), "exact", "stride", "block", "page",
         "parallel_block", "region", "random" ...; CLT, adaptive, stratified and random_device samplers raise ValueError.  More
         than 1024 buckets, or a table whose timestamps span 2^31 or more, raise ValueError (nothing is truncated); a window
-        that holds no sampled row raises RuntimeError("No samples collected")."""
+        that holds no sampled row raises RuntimeError("No samples collected").
+
+        ``group_by`` = "region" | "product_id": one series per key from ONE sweep (aqe_reduce_time_groups) — an ordered
+        ``dict[key, dict[start, BucketEstimate]]``, keys ascending, each key's buckets ascending; only cells (key, bucket) with a
+        sampled row.  The keys' span times the bucket count may be up to 65 536 (more: ValueError naming the three numbers).
+        ``key_where`` may then name the group column only: the other column is a ValueError before anything is launched."""
         a = str(agg).upper()
         if a not in _AGG:
             raise ValueError(f"time buckets take SUM, AVG or COUNT, not {agg!r}")
         spec = time_spec(width, origin, time_between)
+        column = None
+        if group_by is not None:
+            name = str(group_by).strip().lower()
+            if name not in _GROUP_COLUMNS:
+                raise ValueError(f"a time series is grouped by 'region' or 'product_id', not {group_by!r}")
+            column = _GROUP_COLUMNS[name]
         if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
             raise ValueError(f"time buckets do not take the {method} sampler (single-round family samplers and 'random' only)")
         if not float(sample_percent) > 0.0:
@@ -1163,11 +1174,24 @@ class CustomBPlusDB:
         f = None if key_where is None else _key_filter_for(key_where, method)
         if f is not None and f.term[0].form != nat.KEYTERM_NONE and f.term[1].form != nat.KEYTERM_NONE:
             raise ValueError("time buckets take a key predicate on ONE key column (region or product_id), not on both")
+        if column is not None and f is not None:
+            other = nat.GROUP_PRODUCT if column == nat.GROUP_REGION else nat.GROUP_REGION
+            if f.term[other - 1].form != nat.KEYTERM_NONE:
+                names = {v: k for k, v in _GROUP_COLUMNS.items()}
+                raise ValueError(f"a time series by {names[column]} takes a key predicate on {names[column]} only, not on {names[other]}")
         q = self._approx_query(a, "stride" if method == "rowid" else method, sample_percent, None, where, seed, num_threads, block_size,
                                id_between=id_between)
         if method == "rowid":
             q.method = nat.M_ROWID_MOD
+        if column is not None:
+            series: dict = {}
+            for r in _quantile_call(lambda: self._time_groups(f, q, column, spec)):
+                series.setdefault(int(r.key), {})[int(r.start)] = BucketEstimate(r)
+            return series
         return {int(r.key): BucketEstimate(r) for r in _quantile_call(lambda: self._time_series(f, q, spec))}
+
+    def _time_groups(self, f, q, column, spec):
+        return self._eng().time_groups(q, column, spec, f)
 
     def _time_series(self, f, q, spec):
         return self._eng().time_buckets(q, spec, f)

@@ -291,6 +291,29 @@ def time_bucket_defect(clean: str, args) -> Optional[str]:
     return None
 
 
+_SERIES_COLUMNS = ("region", "product_id")
+
+
+def series_by_defect(clean: str, args, bucket) -> Optional[str]:
+    """What keeps a query given --series-by from running, found before the table is opened (None: nothing, or no --series-by): a
+    query without GROUP BY BUCKET(...), a column other than region / product_id, a key predicate on the other key column."""
+    name = getattr(args, "series_by", None)
+    if name is None:
+        return None
+    if bucket is None:
+        return "--series-by takes a GROUP BY BUCKET(timestamp, W[, origin]) query: it lists the time buckets per key"
+    col = name.strip().lower()
+    if col not in _SERIES_COLUMNS:
+        return f"--series-by {name}: unknown column {name!r} (a time series is listed by region or product_id)"
+    from . import aqe_backend
+    kw = aqe_backend.parse_key_where(clean)  # (time_bucket_defect has refused what does not parse)
+    other = _SERIES_COLUMNS[1 - _SERIES_COLUMNS.index(col)]
+    if kw is not None and other in kw:
+        return (f"the key predicate 'WHERE {where_clause_of(clean)}' names {other}: a time series by {col} takes a key predicate on {col} only "
+                "(the sweep reads one key column beside the timestamps)")
+    return None
+
+
 def group_error_form(clean: str, args) -> bool:
     """SUM / AVG / COUNT ... GROUP BY ... --e E without --s (--s wins, as in determine_query_type) and outside an APPROX(...)
     wrapper: the query the error-threshold form of GROUP BY answers."""
@@ -408,6 +431,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--max-groups", dest="max_groups", type=int, metavar="N", help="SUM / AVG / COUNT ... GROUP BY over key ranges of up to N groups "
                    "(above 1024, at most 65536: the sliced sweep); without it GROUP BY stops at 1024 groups")
     p.add_argument("--all-groups", dest="all_groups", action="store_true", help="with --max-groups: print every group (default: the first 50 and a count of the rest)")
+    p.add_argument("--series-by", dest="series_by", metavar="COLUMN", help="with GROUP BY BUCKET(timestamp, W): one time series per key of COLUMN "
+                   "(region or product_id), from one sweep; at most 65536 cells (keys x buckets)")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="under torchrun (one process per GPU): the torch.distributed backend (nccl = RCCL)")
     p.add_argument("--collective", choices=["torch", "mailbox"], default="torch", help="under torchrun: the all-reduce of the moment vectors "
@@ -433,8 +458,11 @@ def run(args, out=sys.stdout) -> int:
     except ValueError as e:
         print(f"error: {e}", file=out)
         return 2
+    if bucket is None and getattr(args, "series_by", None) is not None:
+        print(f"error: {series_by_defect(clean, args, bucket)}", file=out)
+        return 2
     if bucket is not None:
-        why = time_bucket_defect(clean, args)
+        why = time_bucket_defect(clean, args) or series_by_defect(clean, args, bucket)
         if why is not None:
             print(f"error: {why}", file=out)
             return 2
@@ -921,6 +949,9 @@ def _run_time_series(db, args, out, clean, qtype, agg, bucket, aqe_backend, t0, 
     window = parse_time_where(clean)
     pct = args.s if args.s is not None else (10.0 if qtype == QUERY_EMBEDDED else 100.0)
     method = "exact" if pct >= 100.0 else "rowid"
+    series_by = getattr(args, "series_by", None)
+    if series_by is not None:
+        return _run_time_groups(db, args, out, clean, agg, bucket, window, pct, method, series_by.strip().lower(), aqe_backend, t0, kw)
     try:
         series = db.approx_time_series(agg, width, origin=origin, time_between=window, sample_percent=pct, method=method,
                                        where=aqe_backend.parse_where(clean), **kw)
@@ -935,6 +966,36 @@ def _run_time_series(db, args, out, clean, qtype, agg, bucket, aqe_backend, t0, 
     for start, g in series.items():
         ci = f"   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})" if (args.ci and method != "exact") else ""
         print(f"   {start:>12}: {g.value:,.4f}{ci}   n={g.n:,}", file=out)
+    print(f"   execution time: {ms:.2f} ms", file=out)
+    db.close_database()
+    return 0
+
+
+def _run_time_groups(db, args, out, clean, agg, bucket, window, pct, method, column, aqe_backend, t0, kw) -> int:
+    """... GROUP BY BUCKET(timestamp, W[, origin]) --series-by region | product_id: one line per cell in (key, start) order, in the
+    bucket line's format with the key in front; the first 50 cells unless --all-groups."""
+    width, origin = bucket
+    try:
+        series = db.approx_time_series(agg, width, origin=origin, time_between=window, sample_percent=pct, method=method,
+                                       where=aqe_backend.parse_where(clean), group_by=column, **kw)
+    except ValueError as e:  # (more than 1024 buckets, more than 65 536 cells, a timestamp range of 2^31 or more)
+        print(f"error: {e}", file=out)
+        db.close_database()
+        return 2
+    ms = (time.perf_counter() - t0) * 1e3
+    if window is not None:
+        print(f"window: timestamp {window[0]} .. {window[1]}", file=out)
+    print(f"\n{agg}(amount) GROUP BY BUCKET(timestamp, {width}{f', {origin}' if origin else ''}) per {column} "
+          f"({'exact' if method == 'exact' else f'rowid sample {pct:g}%'}):", file=out)
+    cells = [(key, start, g) for key, buckets in series.items() for start, g in buckets.items()]
+    shown = len(cells) if getattr(args, "all_groups", False) else MAX_GROUPS_SHOWN
+    for key, start, g in cells[:shown]:
+        ci = f"   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})" if (args.ci and method != "exact") else ""
+        print(f"   {key:>6} {start:>12}: {g.value:,.4f}{ci}   n={g.n:,}", file=out)
+    if len(cells) > shown:
+        print(f"   ... and {len(cells) - shown:,} more cells ({len(cells):,} in all; --all-groups prints every one)", file=out)
+    nb = len({start for b in series.values() for start in b})
+    print(f"   {len(series):,} keys, {nb:,} buckets, {len(cells):,} cells", file=out)
     print(f"   execution time: {ms:.2f} ms", file=out)
     db.close_database()
     return 0

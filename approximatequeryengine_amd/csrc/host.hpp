@@ -104,6 +104,7 @@ struct aqe_distinct_scratch;  // distinct.hip
 struct aqe_summary_scratch;  // summary.hip
 struct aqe_time_scratch;  // timeseries.hip
 struct aqe_wide_scratch;  // wide_group.hip
+struct aqe_series_scratch;  // time_group.hip
 
 struct aqe_ctx {
     StageRing ring;
@@ -181,6 +182,8 @@ struct aqe_ctx {
     aqe_time_scratch* timeseries = nullptr;
     // GROUP BY over wide key ranges (wide_group.hip): the slices' partials, the summed bins and the result list, made on first use
     aqe_wide_scratch* wide = nullptr;
+    // per-key time series (time_group.hip): the slices' partials, the summed bins and the cell list, made on first use
+    aqe_series_scratch* series = nullptr;
     // diagnostics (aqe_last_load_policy): the instantiation the most recent launch of a visit_tile kernel was — 1 non-temporal,
     // 0 plain loads, -1 no such launch yet.  Index-list sweeps and the quantile pass have the plain one only.
     int last_nt = -1;
@@ -376,6 +379,9 @@ void timeseries_release(aqe_ctx* c);
 
 // wide_group.hip
 void wide_release(aqe_ctx* c);
+
+// time_group.hip
+void series_release(aqe_ctx* c);
 
 // plans.hip
 void destroy_plan(aqe_plan* p, bool device_idle = false);  // device_idle: the caller has just synchronised the device

@@ -578,6 +578,7 @@ void aqe_destroy(aqe_ctx* c) {
     summary_release(c);
     timeseries_release(c);
     wide_release(c);
+    series_release(c);
     free_table(c);
     free_ring(c);
     if (c->d_stamps) (void)hipFree(c->d_stamps);

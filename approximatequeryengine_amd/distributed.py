@@ -561,6 +561,42 @@ def sharded_time_series(engine, query, spec, bins, all_reduce_sum: Callable, all
         return engine.time_buckets_finish(query, spec, tmin, tmax, b.data_ptr(), stream)
 
 
+def sharded_time_groups(engine, query, group_column, spec, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None,
+                        max_groups: int = 65536):
+    """SUM / AVG / COUNT per cell (key of ``group_column``, time bucket) across the ranks of a process group (engine.Engine
+    interface), collective.  The table's timestamp range AND the group column's key range are agreed in ONE all-reduce MAX of
+    the int64 vector [~tmin, tmax, ~kmin, kmax] (engine.time_range, engine.group_key_range; ~v = -v - 1 reverses the order
+    without overflowing; an empty shard contributes the neutral elements), every rank derives the same grid from it on the
+    host (engine.time_group_plan: time_plan's refusals, and more than 65 536 cells, are raised on every rank alike, before the
+    sweep), bins the part of the sample inside its shard into nbins x SERIES_BIN sums (aqe_time_groups_enqueue_bins, under
+    ``key_filter`` when there is one), ONE all-reduce SUM merges them and every rank finishes the same bins — so every rank
+    returns the same list of SeriesResult, ascending by (key, start).
+
+    bins    float64 tensor on the engine's device with room for SERIES_BIN * nbins doubles (at most SERIES_BIN * 65 536)
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    import torch
+    from ._native import ERR_INVALID, SERIES_BIN, AqeError
+    from .engine import time_group_plan
+    stream = _stream_for(stream, bins)
+    with _torch_on(stream, bins):
+        lo, hi = engine.time_range()
+        klo, khi = engine.group_key_range(int(group_column))
+        rng = torch.tensor([~int(lo), int(hi), ~int(klo), int(khi)], dtype=torch.int64, device=bins.device)
+        all_reduce_max(rng)
+        r = [int(v) for v in rng.tolist()]
+        tmin, tmax, kmin, kmax = ~r[0], r[1], ~r[2], r[3]
+        nbins = time_group_plan(spec, tmin, tmax, kmin, kmax)[2]
+        if nbins == 0:  # an empty table, or a window that holds none of its timestamps
+            raise AqeError(ERR_INVALID, "No samples collected")
+        if bins.numel() < SERIES_BIN * nbins:
+            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {SERIES_BIN * nbins} needed")
+        span = kmax - kmin + 1
+        b = bins[: SERIES_BIN * nbins]
+        engine.time_groups_enqueue_bins(query, group_column, spec, tmin, tmax, kmin, span, b.data_ptr(), stream, key_filter)
+        all_reduce_sum(b)
+        return engine.time_groups_finish(query, group_column, spec, tmin, tmax, kmin, span, b.data_ptr(), stream, max_groups)
+
+
 def sharded_histogram(engine, query, spec, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
     """HISTOGRAM(amount, B) across the ranks of a process group (engine.Engine interface), collective.  When ``spec`` carries no
     range the ranks agree on the table's amount range first — ONE all-reduce MAX of [-min, max] (engine.quantile_amount_range),

@@ -716,6 +716,36 @@ class Engine:
                                                     C.c_void_p(stream), out, max_groups, C.byref(n)))
         return list(out[: n.value])
 
+    # -- per-key time series (aqe_reduce_time_groups and its kin): GROUP BY a key column and BUCKET(timestamp, W) in one sweep --
+    def _series_buf(self, max_groups: int):
+        return (nat.SeriesResult * max(int(max_groups), 1))()
+
+    def time_groups(self, query: Query, group_column: int, spec: "nat.TimeSpec", key_filter: "Optional[nat.KeyFilter]" = None,
+                    max_groups: int = nat.SERIES_MAX_BINS):
+        """SUM / AVG / COUNT per cell (key of ``group_column``, time bucket): list of SeriesResult ascending by (key, start), only cells
+        with a sampled row inside the window (one nothing of which passes with n == 0).  ``key_filter`` may carry a term on the group
+        column only.  More cells than ``max_groups`` is AqeError(ERR_INVALID) with the count; no partial list."""
+        out = self._series_buf(max_groups)
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_reduce_time_groups(self._h, _filter_ref(key_filter), C.byref(query), int(group_column), C.byref(spec), out, int(max_groups),
+                                                   C.byref(n)))
+        return list((nat.SeriesResult * n.value).from_buffer_copy(out)) if n.value else []
+
+    def time_groups_enqueue_bins(self, query: Query, group_column: int, spec: "nat.TimeSpec", tmin: int, tmax: int, key_min: int, span: int,
+                                 dev_bins_ptr: int, stream: int = 0, key_filter: "Optional[nat.KeyFilter]" = None):
+        """This shard's nbins x SERIES_BIN doubles over the agreed timestamp range [tmin, tmax] and keys [key_min, key_min + span) into
+        device memory (all-reduce SUM, then time_groups_finish); nbins is time_group_plan(spec, tmin, tmax, key_min, key_max)[2]."""
+        self._chk(nat.lib().aqe_time_groups_enqueue_bins(self._h, _filter_ref(key_filter), C.byref(query), int(group_column), C.byref(spec), int(tmin),
+                                                         int(tmax), int(key_min), int(span), C.c_void_p(dev_bins_ptr), C.c_void_p(stream)))
+
+    def time_groups_finish(self, query: Query, group_column: int, spec: "nat.TimeSpec", tmin: int, tmax: int, key_min: int, span: int, dev_bins_ptr: int,
+                           stream: int = 0, max_groups: int = nat.SERIES_MAX_BINS):
+        out = self._series_buf(max_groups)
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_time_groups_finish(self._h, C.byref(query), int(group_column), C.byref(spec), int(tmin), int(tmax), int(key_min), int(span),
+                                                   C.c_void_p(dev_bins_ptr), C.c_void_p(stream), out, int(max_groups), C.byref(n)))
+        return list((nat.SeriesResult * n.value).from_buffer_copy(out)) if n.value else []
+
     # -- MIN / MAX (aqe_reduce_extremes and its kin): one sweep answers both; key_filter may be None everywhere --
     def reduce_extremes(self, query: Query, key_filter: "Optional[nat.KeyFilter]" = None) -> "nat.ExtremeResult":
         out = nat.ExtremeResult()
@@ -921,6 +951,33 @@ def time_plan(spec: "nat.TimeSpec", tmin: int, tmax: int) -> Tuple[int, int]:
     if rc != nat.OK:
         raise nat.AqeError(rc, "BUCKET: the width must be at least 1 and the window must have t_lo <= t_hi")
     return first.value, n.value
+
+
+def time_group_plan(spec: "nat.TimeSpec", tmin: int, tmax: int, key_min: int, key_max: int, slice_bins: int = 0) -> Tuple[int, int, int, int]:
+    """aqe_time_group_plan: (first_bucket, nbuckets, nbins, nslices) of the grid of the keys [key_min, key_max] x the buckets of the
+    timestamp range [tmin, tmax] under ``spec``, in slices of ``slice_bins`` bins (0: the default), host only.  nbins == 0: an empty
+    table or a window that leaves nothing.  Raises AqeError with the library's text: time_plan's refusals, ERR_UNSUPPORTED past
+    65 536 cells (the message names the span, the bucket count and their product), ERR_INVALID for a bad slice."""
+    first, nb, nbins, nslices = C.c_int64(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    nat.check(nat.lib().aqe_time_group_plan(C.byref(spec), int(tmin), int(tmax), int(key_min), int(key_max), int(slice_bins), C.byref(first), C.byref(nb),
+                                            C.byref(nbins), C.byref(nslices)))
+    return first.value, nb.value, nbins.value, nslices.value
+
+
+def time_groups_from_bins(bins: Sequence[float], query: Query, shift: float, spec: "nat.TimeSpec", tmin: int, tmax: int, key_min: int, span: int,
+                          max_groups: int = nat.SERIES_MAX_BINS):
+    """aqe_time_groups_from_bins, host only: the finish of a per-key time series over a host copy of its (summed) bins — span x
+    nbuckets x SERIES_BIN doubles {n, P1, P2, visited}, with ``shift`` the c of P1 and P2: list of SeriesResult ascending by
+    (key, start).  Raises AqeError as time_groups_finish does ("No samples collected"; more cells than ``max_groups``)."""
+    v = np.ascontiguousarray(np.asarray(bins, dtype=np.float64).ravel())
+    nbins = time_group_plan(spec, tmin, tmax, key_min, int(key_min) + int(span) - 1)[2]
+    if v.size < nat.SERIES_BIN * nbins:
+        raise ValueError(f"{v.size} doubles given, {nat.SERIES_BIN * nbins} needed")
+    out = (nat.SeriesResult * max(int(max_groups), 1))()
+    n = C.c_uint32()
+    nat.check(nat.lib().aqe_time_groups_from_bins(v.ctypes.data_as(C.POINTER(C.c_double)), C.byref(query), float(shift), C.byref(spec), int(tmin), int(tmax),
+                                                  int(key_min), int(span), out, int(max_groups), C.byref(n)))
+    return list(out[: n.value])
 
 
 def _top_spec(k, descending) -> "nat.TopSpec":

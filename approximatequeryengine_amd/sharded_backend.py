@@ -413,6 +413,16 @@ class ShardedBPlusDB(CustomBPlusDB):
             bins = self._buffer(nat.TIME_BIN * nat.TIME_MAX_BUCKETS)
             return sharded_time_series(self._engine, q, spec, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)
 
+    # ---- per-key time series: one all-reduce MAX of the timestamp and key ranges, one all-reduce SUM of nbins x 4 sums;
+    # approx_time_series(group_by=...) is CustomBPlusDB's own, over this ----
+    def _time_groups(self, f, q, column, spec):
+        import torch
+        from .distributed import sharded_time_groups
+        self._eng()
+        with torch.cuda.stream(self._side):
+            bins = self._buffer(nat.SERIES_BIN * nat.SERIES_MAX_BINS)
+            return sharded_time_groups(self._engine, q, column, spec, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)
+
     # ---- HISTOGRAM: one all-reduce MAX for the range when the caller gives none, one all-reduce SUM of the counts;
     # approx_histogram is CustomBPlusDB's own, over this ----
     def _histogram(self, f, q, spec):

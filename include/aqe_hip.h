@@ -1288,6 +1288,79 @@ AQE_API int aqe_grouped_top_finish(aqe_ctx* ctx, const aqe_query* q, int ncols, 
  * AQE_ERR_INVALID for a null argument or a k outside 1 .. AQE_TOP_MAX; aqe_last_error(NULL) has the text. */
 AQE_API int aqe_top_from_results(const aqe_group_result* all, uint32_t n_all, const aqe_top_spec* spec, aqe_group_result* out, aqe_top_info* info);
 
+/* ---- per-key time series: GROUP BY a key column and BUCKET(timestamp, W) in one sweep (time_group.hip) ------------------------
+ * "Revenue per region per hour": SUM / AVG / COUNT per cell of the grid of ONE key column (AQE_GROUP_REGION or
+ * AQE_GROUP_PRODUCT) x the time buckets of an aqe_time_spec.  Everything not said here is §time buckets' and §wide GROUP BY's.
+ *
+ * Grid.  bucket(ts) = floor((ts - origin) / width); the buckets of [tmin, tmax] intersected with the window are those
+ * aqe_time_plan gives — the same arithmetic, the same two refusals (more than 1024 buckets; a range of 2^31 or more), the same
+ * texts.  With span = key_max - key_min + 1 of the group column (agreed over shards), a row's bin is
+ * (key - key_min) * nbuckets + (bucket - first_bucket) and nbins = span * nbuckets may be up to 65 536: more is
+ * AQE_ERR_UNSUPPORTED with the span, the bucket count and their product in the message; nothing is launched or truncated.
+ *
+ * Rows.  A sampled row outside the timestamp window counts into no cell: neither n nor visited.  A row inside counts into its
+ * cell's `visited`, and into n, P1, P2 when it also passes the inclusive amount range (aqe_query.has_where) and the key term.
+ * `filter` (NULL: none) may carry a term on the GROUP column only — it is judged on the column the sweep reads anyway; a term
+ * on the other key column would need a third column in the row loop and is AQE_ERR_UNSUPPORTED, naming the column, before any
+ * launch.
+ *
+ * Results.  aqe_series_result, ascending by (key, start) — which is bin order — with start = origin + bucket * width.  Only
+ * cells with visited > 0 are listed; a listed cell may have n == 0.  Per cell the estimate and interval are those of
+ * aqe_reduce_grouped: value and half-width scaled by 100 / pct for SUM, no interval for COUNT or when n < 2.  visited == 0 over
+ * all cells is AQE_ERR_INVALID "No samples collected".  cap smaller than the number of cells is AQE_ERR_INVALID with the count
+ * in the message and in *n_groups; no partial list is written.  Samplers, row windows and their refusals are exactly those of
+ * aqe_reduce_time_buckets; SUM / AVG / COUNT only (anything else: AQE_ERR_INVALID).  Needs the rows' timestamps and keys
+ * (AQE_STAGE_KEEP_AOS, or a synthetic table).
+ *
+ * The sweep (k_time_group).  8 + 4 + 4 bytes per sampled row and slice: the time offsets ride in key slot 0, the group column
+ * in slot 1.  The bins {n, P1, P2, visited} are cut into slices as aqe_wide_plan cuts them (default 2048 bins), the grid is
+ * (workgroups, slices); a row of another slice costs its loads and compares only.  While copies x slice_bins fits 2048 bins a
+ * workgroup keeps up to 16 copies of its slice in LDS, lane l adding to copy l mod copies, and adds them in copy order when it
+ * stores the slice — rows of a time-ordered table share a bucket, and a narrow key column would otherwise put a wave's 64
+ * lanes on a handful of words.  The stores are summed per word in workgroup order and one thread per bin finishes and
+ * compacts the list.  Counts are exact; sums are reproducible to rounding.  No floating-point atomics on device memory.
+ * Diagnostics, read per call: AQE_WIDE_SLICE forces the slice as for the wide GROUP BY; AQE_SERIES_COPIES (a power of two not
+ * above what fits) the copies; AQE_SERIES_RUN=1 swaps the LDS adds per row for k_time_buckets' per-lane register run;
+ * AQE_NT=0/1 picks the load flavour, which aqe_last_load_policy reports.  A device that refuses the dynamic LDS is
+ * AQE_ERR_INTERNAL with the byte count; nothing is launched. */
+typedef struct aqe_series_result {
+    int64_t key;     /* the group column's value                               */
+    int64_t start;   /* the bucket's start, origin + bucket * width            */
+    uint64_t n;      /* sampled rows of the cell that pass amount range + term */
+    uint64_t visited; /* sampled rows of the cell inside the window            */
+    double sum, sumsq, mean, value, ci_lower, ci_upper; /* as aqe_group_result */
+} aqe_series_result; /* 80 bytes */
+/* Host only, no GPU and no context; the same answer on every rank.  The buckets of [tmin, tmax] under the spec as aqe_time_plan
+ * gives them, times the keys [key_min, key_max]: *nbins = span * *nbuckets and the slices of slice_bins bins (0: the default).
+ * *nbins == 0: an empty table (tmin > tmax or key_min > key_max) or a window that leaves nothing.  aqe_time_plan's refusals pass
+ * through with their status; AQE_ERR_UNSUPPORTED past 65 536 bins (the outputs then hold the bucket count, *nbins == 0);
+ * AQE_ERR_INVALID for a slice_bins that is no power of two in 64 .. 4096.  aqe_last_error(NULL) has the text. */
+AQE_API int aqe_time_group_plan(const aqe_time_spec* spec, int64_t tmin, int64_t tmax, int32_t key_min, int32_t key_max, uint32_t slice_bins,
+                                int64_t* first_bucket, uint32_t* nbuckets, uint32_t* nbins, uint32_t* nslices);
+/* Single GPU, synchronous: the ranges, the sweep, the sum, the finish. */
+AQE_API int aqe_reduce_time_groups(aqe_ctx* ctx, const aqe_key_filter* filter /* NULL: none */, const aqe_query* q, int group_column,
+                                   const aqe_time_spec* spec, aqe_series_result* out, uint32_t cap, uint32_t* n_groups);
+/* Multi-GPU:
+ *     aqe_time_range(ctx, &tmin, &tmax), aqe_group_key_range(ctx, group_column, &kmin, &kmax)      all-reduce MIN / MAX them
+ *     aqe_time_group_plan(spec, tmin, tmax, kmin, kmax, 0, &first, &nbuckets, &nbins, &nslices)     host only
+ *     aqe_time_groups_enqueue_bins(ctx, filter, q, group_column, spec, tmin, tmax, key_min, span, dev_bins, stream)
+ *                                                  nbins x 4 doubles {n, P1, P2, visited} per bin (zeros from an empty shard)
+ *     <ONE all-reduce SUM of nbins * 4 doubles on `stream`>
+ *     aqe_time_groups_finish(ctx, q, group_column, spec, tmin, tmax, key_min, span, dev_bins, stream, out, cap, &n_groups)
+ *                                                  synchronises `stream`
+ * with span = kmax - kmin + 1.  Every rank finishes the same bins.  A shard with timestamps outside [tmin, tmax] or keys
+ * outside [key_min, key_min + span) is AQE_ERR_INVALID. */
+AQE_API int aqe_time_groups_enqueue_bins(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, int group_column, const aqe_time_spec* spec,
+                                         int64_t tmin, int64_t tmax, int32_t key_min, uint32_t span, double* dev_bins, void* stream);
+AQE_API int aqe_time_groups_finish(aqe_ctx* ctx, const aqe_query* q, int group_column, const aqe_time_spec* spec, int64_t tmin, int64_t tmax,
+                                   int32_t key_min, uint32_t span, const double* dev_bins, void* stream, aqe_series_result* out, uint32_t cap,
+                                   uint32_t* n_groups);
+/* Host only, no GPU and no context: the same finish over a HOST copy of the (summed) bins, bins[nbins * 4], with `shift` the c
+ * of P1 = sum(x - c), P2 = sum (x - c)^2 (the device entries take the table's).  q gives the aggregate and sample_percent.
+ * Status and list as aqe_time_groups_finish; aqe_last_error(NULL) has the text. */
+AQE_API int aqe_time_groups_from_bins(const double* bins, const aqe_query* q, double shift, const aqe_time_spec* spec, int64_t tmin, int64_t tmax,
+                                      int32_t key_min, uint32_t span, aqe_series_result* out, uint32_t cap, uint32_t* n_groups);
+
 #ifdef __cplusplus
 }
 #endif
