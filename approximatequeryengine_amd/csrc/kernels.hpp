@@ -275,6 +275,8 @@ constexpr int kUnionMaxEntries = 768;
 constexpr int kUnionMaxIncidences = 2048;   // (piece, target) pairs: two per thread of the fold
 constexpr int kUnionMaxRows = 256;          // (class, round) rows of totals; targets = 2 x rows (pointer groups a, b)
 constexpr int kUnionWgPieces = 32;          // pieces one workgroup's share may hold (a bit each in the waves' masks)
+constexpr int kUnionJudgeSlots = 32;         // members whose tails the fold stages for the judges: a pass of judging waves
+constexpr int kUnionDenseWaves = 4;         // waves that judge when a member's rounds fit a row of 8 or 16 lanes: one per SIMD
 constexpr int kUnionMaxTilesPerWg = 64 * kPersistWaves;  // lane j of wave w holds tile w + 16 j of the share
 // tile_meta: bits 0..15 the tile's first piece, 16..26 the end of its rows (vhi), 27 their start (vlo: 0 or 1) — see
 // planner.hpp, UnionTile — and this bit: 1024 rows of one piece, no masks

@@ -48,13 +48,15 @@ typedef const AQE_KARG LeanLaunch* LeanKarg;
 // handed to the workgroup, 5 partial out (wave 0), 6 ticket drawn (wave 0);  then [8] of the folding workgroup: 1 rounds
 // summed, 2 judged.  A union group (lean_union) marks 0 entry, 1 tile list in registers, 2 first tile folded, 3 sweep done,
 // 5 partials out, 6 ticket drawn; its fold 3 partial list staged, 4 pieces summed, 5 targets summed, and then per judging
-// wave [wave][8]: 0 first judge done, 1 last result sent.
+// wave [wave][8]: 0 first judge done, 1 last result sent, 2 the wave's hardware id (HW_ID: bits 5:4 its SIMD).
 #ifdef AQE_LEAN_STAMPS
 constexpr size_t kLeanStampWords = (static_cast<size_t>(kMaxPersistGrid) * kPersistWaves + 1 + kPersistWaves) * 8;
 __device__ unsigned long long g_lean_stamps[kLeanStampWords];
 #define LEAN_STAMP(slot) do { if (lane == 0 && blockIdx.x < static_cast<unsigned>(kMaxPersistGrid)) g_lean_stamps[(static_cast<size_t>(blockIdx.x) * kPersistWaves + wave) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #define LEAN_STAMP_FOLD(slot) do { if (threadIdx.x == 0) g_lean_stamps[static_cast<size_t>(kMaxPersistGrid) * kPersistWaves * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #define LEAN_STAMP_JUDGE(slot) do { if (lane == 0) g_lean_stamps[(static_cast<size_t>(kMaxPersistGrid) * kPersistWaves + 1 + wave) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+// (s_getreg_b32 hwreg(HW_REG_HW_ID, 0, 32): a read of the wave's placement)
+#define LEAN_STAMP_HWID(slot) do { if (lane == 0) g_lean_stamps[(static_cast<size_t>(kMaxPersistGrid) * kPersistWaves + 1 + wave) * 8 + (slot)] = __builtin_amdgcn_s_getreg((31 << 11) | 4); } while (0)
 #else
 #define LEAN_STAMP(slot) do { } while (0)
 #define LEAN_STAMP_FOLD(slot) do { } while (0)
@@ -153,14 +155,17 @@ __device__ __forceinline__ void lean_tile(const double* base, unsigned rem, cons
     }
 }
 
+// A tail's words, and a result's with its check word after them, as they lie in a judging wave's LDS
+constexpr unsigned kLeanTailWords = sizeof(LeanTail) / 8u, kLeanResWords = sizeof(aqe_result) / 8u + 1u;
+
 // Wave 0 of the folding workgroup, lane q holding the moments through round q (or a slot's own total where the form
 // asks for that): the decision and the result.  The rules and what follows them are the monitor's (persist.hip,
-// monitor_fold), evaluated once, for every round at the same time.  T: the launch's tail, in LDS.  kLanes = 32: each half
-// of the wave judges a member of its own (lean_union), lane q of the half holding round q, T the half's tail — such
-// members have no top-up slot (plans.hip, union_groups).
+// monitor_fold), evaluated once, for every round at the same time.  T: the launch's tail, in LDS.  kLanes = 32, 16, 8:
+// each aligned row of kLanes lanes judges a member of its own (lean_union), lane q of the row holding round q, T the
+// row's tail, res_words the row's words — such members have no top-up slot (plans.hip, union_groups).
 template <unsigned kLanes = 64>
 __device__ __forceinline__ void lean_judge(const LeanTail& T, const double (&tot)[7], const unsigned wave_lane, unsigned long long t0, unsigned long long epoch, unsigned long long* res_words) {
-    static_assert(kLanes == 64 || kLanes == 32, "a whole wave or a half per member");
+    static_assert(kLanes == 64 || kLanes == 32 || kLanes == 16 || kLanes == 8, "a whole wave per member, or an aligned row of its lanes");
     const unsigned lane = wave_lane & (kLanes - 1u), base = wave_lane & ~(kLanes - 1u) & 63u;  // lane in the member's lanes; their first
     const unsigned rounds = T.rounds;
     const bool tslot = kLanes == 64 && T.topup_slot != 0;  // the last slot is the top-up: summed on its own, never judged
@@ -253,13 +258,28 @@ __device__ __forceinline__ void lean_judge(const LeanTail& T, const double (&tot
 }
 
 // (all lanes of wave 0, after lean_judge: lane i sends word i of the result, lane sizeof/8 the check word; kLanes = 32:
-// lane i of each half, for its member)
+// lane i of each half, for its member; kLanes = 16, 8: T and res_words are the wave's FIRST row's, the other rows' follow
+// them kLeanTailWords / kLeanResWords apart, and the wave sends the words of all its 64 / kLanes rows, 64 per store
+// instruction, a result's check word after its words)
 template <unsigned kLanes = 64>
 __device__ __forceinline__ void lean_send_result(const LeanTail& T, const unsigned long long* res_words, const unsigned wave_lane) {
     const unsigned lane = wave_lane & (kLanes - 1u);
 #if defined(AQE_ABL_NOSTORE) || defined(AQE_ABL_RESDEV)
     return;
 #endif
+    if constexpr (kLanes <= 16) {
+        constexpr unsigned kRows = 64u / kLanes, kAll = kRows * kLeanResWords;
+#pragma unroll
+        for (unsigned x0 = 0; x0 < kAll; x0 += 64u) {
+            const unsigned x = x0 + wave_lane, row = x / kLeanResWords, word = x - row * kLeanResWords;
+            if (x >= kAll) continue;
+            const LeanTail& Tr = *reinterpret_cast<const LeanTail*>(reinterpret_cast<const u64*>(&T) + row * kLeanTailWords);
+            if (Tr.totals_only || !Tr.finalize_here) continue;  // (a row past the last member: a tail of zeros)
+            unsigned long long* const to = word + 1u < kLeanResWords ? reinterpret_cast<unsigned long long*>(Tr.result) + word : Tr.result_seq;
+            __hip_atomic_store(to, res_words[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        return;
+    }
     if (T.totals_only || !T.finalize_here) return;
     constexpr unsigned kWords = sizeof(aqe_result) / 8;
     if (lane < kWords) __hip_atomic_store(reinterpret_cast<unsigned long long*>(T.result) + lane, res_words[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -286,6 +306,81 @@ __device__ __forceinline__ int lean_ticket(unsigned* const counter, const unsign
     return last;
 }
 
+// The judges of a union group's fold (lean_union), kW lanes per member — the smallest of 8, 16 and 32 that holds the rounds
+// of every member of the union: an aligned row of kW lanes judges one member, lane q of it holding the moments through
+// round q, so a wave judges 64 / kW members at once.  Sixteen waves running lean_judge's chain of f64 operations side
+// by side, four to a SIMD, take as long as their SIMD needs for four of them, however few lanes are live: with rows of
+// 8 or 16 lanes only waves 0 .. kUnionDenseWaves - 1 judge — consecutive waves of a workgroup sit on different SIMDs —
+// and with rows of 32 (a member may have kMaxPersistRounds = 32 rounds) all of them do.  Pass k: wave w judges members
+// (waves k + w) 64 / kW and on — the bench's 32 members of 5 rounds in ONE pass of four waves.  `tails`, `results`: a
+// slot per member of a pass (member m: slot m mod kUnionJudgeSlots — always one of its wave's own), the first
+// kUnionJudgeSlots members' tails staged by the fold; a later pass fetches its tails first.  `rows`: the classes' rows of
+// round totals.  The scan over rounds adds in ONE association whatever the width: row_shr by 1, 2, 4 (and 8, and the carry
+// of the first sixteen into the second), a lane that would pull from below its row adding 0.0.
+template <unsigned kW>
+__device__ __forceinline__ void lean_union_judge(const LeanLaunch* const members, const unsigned nmem, const unsigned wave, const int lane,
+                                                 const double* const rows, u64* const tails, unsigned long long* const results,
+                                                 const unsigned long long epoch) {
+    constexpr unsigned kPer = 64u / kW, kWaves = kW == 32 ? static_cast<unsigned>(kPersistWaves) : static_cast<unsigned>(kUnionDenseWaves);
+    constexpr unsigned kPassWords = kPer * kLeanTailWords, kFetch = (kPassWords + 63u) / 64u;
+    static_assert(kUnionJudgeSlots % (kWaves * kPer) == 0, "a wave's members of every pass fall into its own slots");
+    if (wave >= kWaves) return;
+    const unsigned row = static_cast<unsigned>(lane) / kW, q = static_cast<unsigned>(lane) % kW;
+    for (unsigned m0 = wave * kPer; m0 < nmem; m0 += kWaves * kPer) {
+        const unsigned slot0 = m0 % kUnionJudgeSlots;
+        u64* const my_tails = tails + slot0 * kLeanTailWords;
+        if (m0 >= static_cast<unsigned>(kUnionJudgeSlots)) {  // (uniform) a later pass: its tails, one round trip
+            u64 w[kFetch];
+#pragma unroll
+            for (unsigned j = 0; j < kFetch; ++j) {
+                const unsigned x = static_cast<unsigned>(lane) + 64u * j, m = m0 + x / kLeanTailWords;
+                w[j] = x < kPassWords && m < nmem ? reinterpret_cast<const u64*>(&members[m].tail)[x % kLeanTailWords] : 0ull;
+            }
+            wave_lds_handoff();
+#pragma unroll
+            for (unsigned j = 0; j < kFetch; ++j) {
+                const unsigned x = static_cast<unsigned>(lane) + 64u * j;
+                if (x < kPassWords) my_tails[x] = w[j];
+            }
+            wave_lds_handoff();
+        }
+        // (a row past the last member reads a tail of zeros: no rounds, nothing judged, nothing sent)
+        const LeanTail& Tm = *reinterpret_cast<const LeanTail*>(my_tails + row * kLeanTailWords);
+        unsigned long long* const lds_res = results + (slot0 + row) * kLeanResWords;
+        const unsigned rounds = Tm.rounds;
+        const bool mine = q < rounds;
+        const double* const r = rows + static_cast<size_t>(Tm.union_row + (mine ? q : 0u)) * 8u;
+        double tot[7];
+#pragma unroll
+        for (int cc = 0; cc < 6; ++cc) tot[cc] = mine ? r[cc] : 0.0;
+        tot[6] = mine ? r[6] + r[7] : 0.0;
+#pragma unroll
+        for (int cc = 0; cc < 7; ++cc) {  // lane q of a row: the moments through round q (lean_query's scan, one row per round)
+            // (a row of sixteen lanes shifts zeros in by itself; a row of eight that is the upper half of one does not)
+            auto below = [&](double v, unsigned by) { return kW >= 16 || q >= by ? v : 0.0; };
+            double p = tot[cc];
+            p += below(dpp_f64<0x111>(p), 1u);
+            p += below(dpp_f64<0x112>(p), 2u);
+            p += below(dpp_f64<0x114>(p), 4u);
+            if constexpr (kW >= 16) p += dpp_f64<0x118>(p);
+            if constexpr (kW == 32) {
+                const double carry = __shfl(p, static_cast<int>((static_cast<unsigned>(lane) & 32u) | 15u), 64);  // the half's first row's total
+                p += (lane & 16) ? carry : 0.0;
+            }
+            tot[cc] = p;
+        }
+        lean_judge<kW>(Tm, tot, static_cast<unsigned>(lane), 0ull, epoch, lds_res);
+        wave_lds_handoff();
+#ifdef AQE_LEAN_STAMPS
+        if (m0 == wave * kPer) { LEAN_STAMP_JUDGE(0); LEAN_STAMP_HWID(2); }
+#endif
+        // (rows of 8 or 16: the wave's rows are sent together, from its first row's tail and words on)
+        if constexpr (kW == 32) lean_send_result<32>(Tm, lds_res, static_cast<unsigned>(lane));
+        else lean_send_result<kW>(*reinterpret_cast<const LeanTail*>(my_tails), results + slot0 * kLeanResWords, static_cast<unsigned>(lane));
+        LEAN_STAMP_JUDGE(1);
+    }
+}
+
 // A UNION GROUP of a batch (plans.hip, build_union): sweep classes that read the same view with the same shift and WHERE
 // bounds, swept as one.  The union of their runs is cut into PIECES — slot ranges over which one multiset of (class,
 // round, pointer group) targets covers every slot — and tiled in 1024-slot tiles over the covered spans (from an even
@@ -303,7 +398,8 @@ __device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion*
                                            double (&lds_part)[kMaxPersistRounds][kPersistWaves][kVec], double (&lds_round)[kMaxPersistRounds][kVec],
                                            unsigned (&lds_mask)[kPersistWaves], int& s_last) {
     static_assert(kUnionWgPieces <= kMaxPersistRounds && kUnionWgPieces <= 32, "a share's pieces: a row of lds_part and a mask bit each");
-    static_assert(sizeof(LeanUnion) <= sizeof(lds_round), "the union's header is staged in lds_round");
+    static_assert(sizeof(LeanUnion) + sizeof(unsigned) <= sizeof(lds_round), "the union's header is staged in lds_round, the largest round count after it");
+    unsigned* const lds_max_rounds = reinterpret_cast<unsigned*>(&lds_round[0][0]) + sizeof(LeanUnion) / sizeof(unsigned);  // (the fold's)
     const int lane = threadIdx.x & 63;
     const unsigned wave = threadIdx.x >> 6;
     const unsigned t_lo = bid * a.tiles_per_wg;
@@ -411,6 +507,7 @@ __device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion*
     if (cur != ~0u) take(~0u, TileAcc{});  // (flushes the last piece)
     if (lane == 0) lds_mask[wave] = touched;
     if (head_stager && static_cast<unsigned>(lane) < sizeof(LeanUnion) / 8u) reinterpret_cast<u64*>(&lds_round[0][0])[lane] = head_word;
+    if (head_stager && lane == 0) *lds_max_rounds = 0u;
     __syncthreads();
 
     // ---- the share's partial of every piece it holds slots of: data, drain, ticket (as lean_query) ----
@@ -445,18 +542,23 @@ __device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion*
     if (!s_last) return;
 
     // ---- the last workgroup folds.  ONE batch of loads: the partial list (an entry per thread), the pieces' and the
-    //      targets' ranges, the incidence list (two per thread) and the tails of the members the first pass judges (two
-    //      words per lane); staged in lds_part, the tails in registers until the sums are done ----
+    //      targets' ranges, the incidence list (two per thread) and the tails of the first kUnionJudgeSlots members, back
+    //      to back (two words per thread; a member past the last: zeros); staged in lds_part, the tails in registers
+    //      until the sums are done.  Whoever holds a tail's first word — its `rounds` — raises the union's largest round
+    //      count in LDS with it, and so does a thread per member beyond those: what the judges' row width follows ----
     const LeanUnion& H = *reinterpret_cast<const LeanUnion*>(&lds_round[0][0]);
-    constexpr unsigned kTailWords = sizeof(LeanTail) / 8u;
-    static_assert(2 * kTailWords <= 128, "a wave's two members' tails, back to back: two words per lane");
-    // wave w judges members m0 = 32 k + 2 w (lanes 0 .. 31) and m0 + 1 (lanes 32 .. 63) in pass k: word j of the two tails
-    auto tail_word = [&](unsigned m0, unsigned j) -> u64 {
-        const unsigned m = m0 + (j >= kTailWords ? 1u : 0u), w = j >= kTailWords ? j - kTailWords : j;
-        return j < 2u * kTailWords && m < nmem ? reinterpret_cast<const u64*>(&members[m].tail)[w] : 0ull;
-    };
-    const u64 mt0 = tail_word(2u * wave, static_cast<unsigned>(lane)), mt1 = tail_word(2u * wave, static_cast<unsigned>(lane) + 64u);
     const unsigned i = threadIdx.x;
+    static_assert(kUnionJudgeSlots * kLeanTailWords <= 2 * kPersistThreads, "the first members' tails: two words per thread");
+    static_assert(offsetof(LeanTail, rounds) == 0, "a tail's first word holds its rounds (low half)");
+    auto first_tail_word = [&](unsigned x) -> u64 {
+        const unsigned m = x / kLeanTailWords;
+        return m < kUnionJudgeSlots && m < nmem ? reinterpret_cast<const u64*>(&members[m].tail)[x - m * kLeanTailWords] : 0ull;
+    };
+    const u64 mt0 = first_tail_word(i), mt1 = first_tail_word(i + kPersistThreads);
+    unsigned more_rounds = 0;
+    for (unsigned m = kUnionJudgeSlots + i; m < nmem; m += kPersistThreads) more_rounds = max(more_rounds, members[m].tail.rounds);
+    if (i % kLeanTailWords == 0u) more_rounds = max(more_rounds, static_cast<unsigned>(mt0));
+    if ((i + kPersistThreads) % kLeanTailWords == 0u) more_rounds = max(more_rounds, static_cast<unsigned>(mt1));
     const unsigned nent = H.nentries, npc = H.npieces, ntg = H.ntargets, ninc = H.nincidences;
     double e4[4] = {0.0, 0.0, 0.0, 0.0};
     if (i < nent) {
@@ -474,19 +576,23 @@ __device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion*
     if (i < ninc) inc0 = H.target_entry[i];
     if (i + kPersistThreads < ninc) inc1 = H.target_entry[i + kPersistThreads];
     // lds_part as one flat list: [0, 4 kUnionMaxEntries) the entries, then the incidences; later [0, 2048) the judging
-    // waves' words, [2048, 4096) the rows of round totals
+    // waves' words — a tail and a result per slot, member m in slot m mod kUnionJudgeSlots — and [2048, 4096) the rows of
+    // round totals
     double* const F = &lds_part[0][0][0];
     unsigned* const Finc = reinterpret_cast<unsigned*>(F + 4 * kUnionMaxEntries);
     double* const rows = F + 2048;
+    u64* const Ftails = reinterpret_cast<u64*>(F);
+    unsigned long long* const Fres = Ftails + kUnionJudgeSlots * kLeanTailWords;
     static_assert(4 * kUnionMaxEntries * sizeof(double) + kUnionMaxIncidences * sizeof(unsigned) <= sizeof(lds_part), "the fold's staging fits lds_part");
     static_assert(kUnionMaxIncidences <= 2 * kPersistThreads && kUnionMaxEntries <= kPersistThreads && kUnionMaxPieces <= kPersistThreads, "one batch of loads");
-    static_assert(2048 + 8 * kUnionMaxRows <= kMaxPersistRounds * kPersistWaves * kVec && kPersistWaves * 128 <= 2048, "rows beside the judging waves' words");
+    static_assert(2048 + 8 * kUnionMaxRows <= kMaxPersistRounds * kPersistWaves * kVec && kUnionJudgeSlots * (kLeanTailWords + kLeanResWords) <= 2048, "rows beside the judging waves' words");
     if (i < nent) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) F[4u * i + c] = e4[c];
     }
     if (i < ninc) Finc[i] = inc0;
     if (i + kPersistThreads < ninc) Finc[i + kPersistThreads] = inc1;
+    if (more_rounds) atomicMax(lds_max_rounds, more_rounds);  // (after the batch's last load is issued)
     __syncthreads();
     LEAN_STAMP_FOLD(3);
     // (the piece sums read kFoldBatch LDS entries at a time before adding them in order: one LDS round trip per batch)
@@ -515,26 +621,39 @@ __device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion*
     __syncthreads();
     LEAN_STAMP_FOLD(4);
     // A target's pieces, ascending, one component per thread.  A target may add a few hundred pieces: its chain of adds
-    // is fixed (bit-reproducible), so what is cut is the LDS round trips around it — kTargetBatch values per trip, the
-    // next batch's incidences read beside them.
+    // is fixed (bit-reproducible), so what is cut is the LDS round trips around it — kTargetBatch values per trip, and
+    // the trips pipelined: batch k + 1's values are on their way (x1, then x0 again) while batch k is added, the
+    // incidences read a further batch ahead, so that the chain waits for LDS once, at its start.
     auto target_sum = [&](unsigned tb, unsigned te) {
-        constexpr unsigned kTargetBatch = 16;
+        constexpr unsigned kTargetBatch = 8;  // two value buffers and the incidences: 5 words per entry of a batch
         double r = 0.0;
         if (tb >= te) return r;
         unsigned e[kTargetBatch];
+        double x0[kTargetBatch], x1[kTargetBatch];
+        auto incidences = [&](unsigned k) {
 #pragma unroll
-        for (unsigned u = 0; u < kTargetBatch; ++u) e[u] = Finc[tb + u < te ? tb + u : tb];
-        for (unsigned k0 = tb; k0 < te; k0 += kTargetBatch) {
-            double x[kTargetBatch];
+            for (unsigned u = 0; u < kTargetBatch; ++u) e[u] = Finc[k + u < te ? k + u : tb];
+        };
+        auto values = [&](double (&x)[kTargetBatch]) {
 #pragma unroll
             for (unsigned u = 0; u < kTargetBatch; ++u) x[u] = F[4u * e[u] + tc];
-            const unsigned k1 = k0 + kTargetBatch;
-#pragma unroll
-            for (unsigned u = 0; u < kTargetBatch; ++u) e[u] = Finc[k1 + u < te ? k1 + u : tb];
+        };
+        auto add = [&](const double (&x)[kTargetBatch], unsigned k) {  // ascending, each add guarded
 #pragma unroll
             for (unsigned u = 0; u < kTargetBatch; ++u) {
-                if (k0 + u < te) r += x[u];
+                if (k + u < te) r += x[u];
             }
+        };
+        incidences(tb);
+        values(x0);
+        incidences(tb + kTargetBatch);
+        for (unsigned k0 = tb; k0 < te; k0 += 2u * kTargetBatch) {
+            values(x1);
+            incidences(k0 + 2u * kTargetBatch);
+            add(x0, k0);
+            values(x0);
+            incidences(k0 + 3u * kTargetBatch);
+            add(x1, k0 + kTargetBatch);
         }
         return r;
     };
@@ -545,55 +664,17 @@ __device__ __forceinline__ void lean_union(const LeanLaunch& a, const LeanUnion*
     auto put = [&](unsigned t, double r) { rows[static_cast<size_t>(t >> 1) * 8u + (tc < 3u ? 3u * (t & 1u) + tc : 6u + (t & 1u))] = r; };
     if (tt0 < ntg) put(tt0, r0);
     if (tt1 < ntg) put(tt1, r1);
+    if (i < kUnionJudgeSlots * kLeanTailWords) Ftails[i] = mt0;  // (the sums are done: the first members' tails take their slots)
+    if (i + kPersistThreads < kUnionJudgeSlots * kLeanTailWords) Ftails[i + kPersistThreads] = mt1;
     __syncthreads();
     LEAN_STAMP_FOLD(5);
-    // The judges, two members per wave, one per half (a member has at most kMaxPersistRounds = 32 rounds): wave w judges
-    // members 2 w and 2 w + 1 — the bench's 32 members in ONE pass; a union of more members takes further passes, each
-    // fetching its tails first.  A wave's LDS: the two tails back to back, then each half's result words.
+    // The judges (lean_union_judge), rows as wide as the union's largest round count asks for: the bench's members have 5
+    // rounds — eight of them to a wave, one wave per SIMD, ONE pass for its 32.
     static_assert(kMaxPersistRounds <= 32, "a member's rounds fit a half wave");
-    if (2u * wave >= nmem) return;
-    u64* const lds_mine = reinterpret_cast<u64*>(F) + wave * 128u;
-    const unsigned h = static_cast<unsigned>(lane) >> 5, q = static_cast<unsigned>(lane) & 31u;
-    unsigned long long* const lds_res = lds_mine + 80u + 16u * h;
-    static_assert(2 * kTailWords <= 80 && 80 + 2 * 16 <= 128, "a wave's words");
-    lds_mine[lane] = mt0;
-    if (static_cast<unsigned>(lane) + 64u < 2u * kTailWords) lds_mine[lane + 64] = mt1;
-    wave_lds_handoff();
-    for (unsigned m0 = 2u * wave;;) {
-        // (a half past the last member reads a tail of zeros: no rounds, nothing judged, nothing sent)
-        const LeanTail& Tm = *reinterpret_cast<const LeanTail*>(lds_mine + h * kTailWords);
-        const unsigned rounds = Tm.rounds;
-        const bool mine = q < rounds;
-        const double* const r = rows + static_cast<size_t>(Tm.union_row + (mine ? q : 0u)) * 8u;
-        double tot[7];
-#pragma unroll
-        for (int cc = 0; cc < 6; ++cc) tot[cc] = mine ? r[cc] : 0.0;
-        tot[6] = mine ? r[6] + r[7] : 0.0;
-#pragma unroll
-        for (int cc = 0; cc < 7; ++cc) {  // lane q of a half: the moments through round q (lean_query's scan, one row per round)
-            double p = tot[cc];
-            p += dpp_f64<0x111>(p);
-            p += dpp_f64<0x112>(p);
-            p += dpp_f64<0x114>(p);
-            p += dpp_f64<0x118>(p);
-            const double carry = __shfl(p, static_cast<int>((static_cast<unsigned>(lane) & 32u) | 15u), 64);  // the half's first row's total
-            tot[cc] = p + ((lane & 16) ? carry : 0.0);
-        }
-        lean_judge<32>(Tm, tot, static_cast<unsigned>(lane), 0ull, epoch, lds_res);
-        wave_lds_handoff();
-#ifdef AQE_LEAN_STAMPS
-        if (m0 == 2u * wave) LEAN_STAMP_JUDGE(0);
-#endif
-        lean_send_result<32>(Tm, lds_res, static_cast<unsigned>(lane));
-        LEAN_STAMP_JUDGE(1);
-        m0 += 2u * kPersistWaves;
-        if (m0 >= nmem) break;
-        const u64 w0 = tail_word(m0, static_cast<unsigned>(lane)), w1 = tail_word(m0, static_cast<unsigned>(lane) + 64u);
-        wave_lds_handoff();
-        lds_mine[lane] = w0;
-        if (static_cast<unsigned>(lane) + 64u < 2u * kTailWords) lds_mine[lane + 64] = w1;
-        wave_lds_handoff();
-    }
+    const unsigned max_rounds = *lds_max_rounds;  // (uniform)
+    if (max_rounds <= 8u) lean_union_judge<8>(members, nmem, wave, lane, rows, Ftails, Fres, epoch);
+    else if (max_rounds <= 16u) lean_union_judge<16>(members, nmem, wave, lane, rows, Ftails, Fres, epoch);
+    else lean_union_judge<32>(members, nmem, wave, lane, rows, Ftails, Fres, epoch);
 }
 
 // One query on the workgroups bid = 0 .. G-1 (a launch of its own, or one group of a batch's launch).  `a`: the fields

@@ -1,7 +1,7 @@
 """Diagnostics (GPU box): in-kernel timeline of a union group of k_sweep_lean_multi (lean.hip, lean_union) from a library
 built with -DAQE_LEAN_STAMPS: the bench batch (32 queries, T = 4 ... 16, AVG / SUM / COUNT, as bench.headline_queries builds
 them) on the bench table, one launch per iteration, min / max of every mark over the union's workgroups, in us after the
-first wave's entry.
+first wave's entry; then, per judging wave of the fold, its first judge after "targets summed" and the SIMD it ran on.
     tools/ab_libs.sh stamps "-DAQE_LEAN_STAMPS"; AQE_HIP_LIB=tools/lib_stamps.bin python tools/stamp_union.py [rows] [iterations]"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,6 +56,10 @@ for it in range(iters):
     jl = j[:, 1] >= t0
     parts.append("last result %.2f" % us(j[jl, 1].max()) if jl.any() else "last result -")
     print("it %2d: " % it + " | ".join(parts))
+    # per judging wave: first judge done, in us after "targets summed", and the SIMD the wave ran on (HW_ID bits 5:4)
+    jl = j[:, 0] >= t0
+    print("       judge - targets, wave@simd: " + " ".join("%d@%d:%.2f" % (k, (j[k, 2] >> 4) & 3, (j[k, 0] - f[5]) / 100.0) for k in range(WAVES) if jl[k])
+          + " | targets - pieces %.2f" % ((f[5] - f[4]) / 100.0))
 b.close()
 for p in plans:
     p.close()
