@@ -132,6 +132,34 @@ class TopInfo(C.Structure):
                 "next": self.next.as_dict() if self.has_next else None}
 
 
+HAVING_MAX_TERMS = 2
+HAVING_GT, HAVING_GE, HAVING_LT, HAVING_LE, HAVING_BETWEEN, HAVING_NOT_BETWEEN = range(6)
+HAVING_OPS = {">": HAVING_GT, ">=": HAVING_GE, "<": HAVING_LT, "<=": HAVING_LE, "between": HAVING_BETWEEN, "not between": HAVING_NOT_BETWEEN}
+
+
+class HavingTerm(C.Structure):
+    """aqe_having_term: <agg> <op> a, or <agg> [NOT] BETWEEN a AND b."""
+    _fields_ = [("agg", C.c_int32), ("op", C.c_int32), ("a", C.c_double), ("b", C.c_double)]
+
+    def as_tuple(self):
+        return (self.agg, self.op, self.a, self.b)
+
+
+class HavingSpec(C.Structure):
+    _fields_ = [("nterms", C.c_uint32), ("pad", C.c_uint32), ("term", HavingTerm * HAVING_MAX_TERMS)]
+
+    def terms(self):
+        return [self.term[i].as_tuple() for i in range(self.nterms)]
+
+
+class HavingInfo(C.Structure):
+    _fields_ = [("groups", C.c_uint32), ("candidates", C.c_uint32), ("passed", C.c_uint32), ("passed_unsettled", C.c_uint32),
+                ("failed_unsettled", C.c_uint32), ("pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k in ("groups", "candidates", "passed", "passed_unsettled", "failed_unsettled")}
+
+
 class QuantileResult(C.Structure):
     _fields_ = [("p", C.c_double), ("value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double),
                 ("n", C.c_uint64), ("visited", C.c_uint64), ("rank_lo", C.c_uint64), ("rank_hi", C.c_uint64),
@@ -403,6 +431,14 @@ def lib() -> C.CDLL:
         "aqe_reduce_grouped_top": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), C.c_int, P(TopSpec), P(GroupResult), P(TopInfo)]),
         "aqe_grouped_top_finish": (C.c_int, [vp, P(Query), C.c_int, P(i32), P(u32), vp, vp, P(TopSpec), P(GroupResult), P(TopInfo)]),
         "aqe_top_from_results": (C.c_int, [P(GroupResult), u32, P(TopSpec), P(GroupResult), P(TopInfo)]),
+        "aqe_reduce_grouped_having": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), C.c_int, P(HavingSpec), P(TopSpec), P(GroupResult), u32, P(u32),
+                                                P(HavingInfo), P(TopInfo)]),
+        "aqe_grouped_having_finish": (C.c_int, [vp, P(Query), C.c_int, P(i32), P(u32), vp, vp, P(HavingSpec), P(TopSpec), P(GroupResult), u32, P(u32),
+                                                P(HavingInfo), P(TopInfo)]),
+        "aqe_having_from_bins": (C.c_int, [P(C.c_double), u32, C.c_int, P(i32), P(u32), C.c_double, P(Query), P(HavingSpec), P(GroupResult), u32, P(u32),
+                                           P(HavingInfo)]),
+        "aqe_having_test": (C.c_int, [P(HavingTerm), C.c_double, C.c_double, C.c_double, P(C.c_int), P(C.c_int)]),
+        "aqe_parse_having": (C.c_int, [C.c_char_p, P(HavingSpec)]),
         "aqe_time_group_plan": (C.c_int, [P(TimeSpec), C.c_int64, C.c_int64, i32, i32, u32, P(C.c_int64), P(u32), P(u32), P(u32)]),
         "aqe_reduce_time_groups": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, P(TimeSpec), P(SeriesResult), u32, P(u32)]),
         "aqe_time_groups_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, P(TimeSpec), C.c_int64, C.c_int64, i32, u32, vp, vp]),

@@ -428,6 +428,19 @@ def _top_arg(top, combined_with=None):
     return int(top)
 
 
+_LEFT_OUT = object()  # approx_group_by(max_groups=...) not given: told apart from a given 1024 (and from None, which is refused)
+
+
+def _having_arg(having):
+    """The ``having`` argument of approx_group_by, checked before anything is launched: a clause's text or a list of terms into
+    an aqe_having_spec; the library's refusal of a clause becomes a ValueError with its words."""
+    from .engine import having_spec
+    try:
+        return having_spec(having)
+    except nat.AqeError as e:
+        raise ValueError(str(e)) from None
+
+
 def _top_info_dict(info, pair: bool) -> dict:
     """aqe_top_info as ``last_top_info`` keeps it: ``next`` is None or (key as the mapping spells it, GroupEstimate)."""
     spell = (lambda k: "%d,%d" % nat.group_key_unpack(k)) if pair else str
@@ -833,8 +846,8 @@ class CustomBPlusDB:
     def approx_group_by(self, agg: str, group_by: str = "region", sample_percent: Optional[float] = None, method: Optional[str] = None,
                         where: Optional[Tuple[float, float]] = None, block_size: int = 1000,
                         key_where: Optional[dict] = None, error_percent: Optional[float] = None,
-                        max_percent: float = 100.0, max_groups: int = 1024, top: Optional[int] = None,
-                        ascending: bool = False) -> "dict[str, GroupEstimate]":
+                        max_percent: float = 100.0, max_groups=_LEFT_OUT, top: Optional[int] = None,
+                        ascending: bool = False, having=None) -> "dict[str, GroupEstimate]":
         """APPROX <agg>(amount) ... GROUP BY region | product_id with a 95 % interval per group: the reference's
         execute_query_groupby_with_ci (executor.cpp:202-321; GroupResultWithCI = map<string, {value, ci_lower,
         ci_upper}>) in one sweep.  method "rowid" is that function's own sample (rowid % (100 / sample_percent) == 0);
@@ -851,7 +864,7 @@ class CustomBPlusDB:
         sample_percent reached, visited rows, converged, unsettled groups, the widest group's key ("a,b" for a pair) and ratio —
         is kept as the dictionary ``last_group_error_info``.
 
-        ``max_groups`` (default 1024: today's routing and refusals): above 1024, at most 65 536, SUM / AVG / COUNT over key ranges
+        ``max_groups`` (left out: 1024, today's routing and refusals): above 1024, at most 65 536, SUM / AVG / COUNT over key ranges
         that span more than 1024 bins go through the sliced sweep (aqe_reduce_grouped_wide) instead of being refused; it does
         not combine with ``error_percent``.
 
@@ -859,9 +872,23 @@ class CustomBPlusDB:
         up to 65 536 bins whatever ``max_groups`` says — the mapping holds the k best groups with n > 0 in RANK order, largest
         first unless ``ascending``; ties are ordered by ascending key.  ``last_top_info`` keeps the ranked groups, how many are
         listed, the best unlisted group and ``contenders``: how many unlisted groups' intervals meet the last listed one's.  It
-        does not combine with ``error_percent``."""
+        does not combine with ``error_percent``.
+
+        ``having``: a HAVING clause's text ("COUNT(*) >= 30 AND SUM(amount) > 1e6", parsed by aqe_parse_having) or a list of 1 or 2
+        terms (agg, op, a[, b]) joined by AND, judged on the device (aqe_reduce_grouped_having) over key ranges of up to 65 536
+        bins — the mapping holds the groups with n > 0 that pass, ascending, or with ``top`` the k best of them in rank order
+        (``last_top_info`` then counts passing groups only).  Without ``max_groups`` the bound on the passing groups is the
+        65 536 the sweep accepts.  ``last_having_info`` keeps groups, candidates, passed, passed_unsettled (passing groups whose
+        interval reaches across a threshold) and failed_unsettled (groups left out that could pass within their interval); a
+        COUNT term has no interval and is always settled.  It does not combine with ``error_percent``."""
         cols = group_columns(group_by)
         col = cols[0]
+        if having is not None and error_percent is not None:
+            raise ValueError("having with error_percent: HAVING judges SUM, AVG and COUNT at one sample percentage only "
+                             "(the error-threshold form has no HAVING)")
+        hspec = None if having is None else _having_arg(having)
+        if max_groups is _LEFT_OUT:  # 1024, or under having what the wide entry accepts (a given 1024 stays 1024)
+            max_groups = nat.WIDE_MAX_BINS if hspec is not None else 1024
         wide = _wide_groups_arg(max_groups, "error_percent" if error_percent is not None else None)
         k = _top_arg(top, "error_percent" if error_percent is not None else None)
         if error_percent is not None:
@@ -871,10 +898,19 @@ class CustomBPlusDB:
         m = {"rowid": nat.M_ROWID_MOD, "stride": nat.M_MEMORY_STRIDE, "block": nat.M_BLOCK, "page": nat.M_PAGE, "exact": nat.M_EXACT}[method]
         if k is not None:
             self.last_top_info = None
+        if hspec is not None:
+            self.last_having_info = None
         if self._n == 0:
             return {}
         bs = 4096 if (method == "page" and block_size == 1000) else block_size
         q = make_query(m, sample_percent, agg=_AGG[agg.upper()], where=where, block_size=int(bs))
+        if hspec is not None:
+            f = None if key_where is None else _key_filter_for(key_where, method)
+            groups, hinfo, tinfo = _quantile_call(lambda: self._grouped_having(f, q, cols, hspec, k, not ascending, int(max_groups)))
+            self.last_having_info = hinfo.as_dict()
+            if tinfo is not None:
+                self.last_top_info = _top_info_dict(tinfo, len(cols) == 2)
+            return _pair_groups(groups, GroupEstimate) if len(cols) == 2 else {str(r.key): GroupEstimate(r) for r in groups}
         if k is not None:
             f = None if key_where is None else _key_filter_for(key_where, method)
             groups, info = _quantile_call(lambda: self._grouped_top(f, q, cols, k, not ascending))
@@ -956,6 +992,11 @@ class CustomBPlusDB:
 
     def _grouped_top(self, f, q, cols, k, descending):
         return self._eng().reduce_grouped_top(q, cols, k, descending, f)
+
+    last_having_info: Optional[dict] = None  # of the most recent approx_group_by(having=...)
+
+    def _grouped_having(self, f, q, cols, having, k, descending, max_groups):
+        return self._eng().reduce_grouped_having(q, cols, having, k, descending, f, max_groups)
 
     def _spread_groups_pair(self, f, q, kind, cols):
         return self._eng().reduce_grouped_pair_spread(q, kind, cols, f)

@@ -19,6 +19,7 @@
     python -m approximatequeryengine_amd.cli "SELECT SUMMARY(amount) FROM sales WHERE region = 2" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli "SELECT DESCRIBE(amount) FROM sales" --db sales.db --compare
     python -m approximatequeryengine_amd.cli "SELECT SUM(amount) FROM sales WHERE timestamp BETWEEN 0 AND 86399 GROUP BY BUCKET(timestamp, 3600)" --db sales.db --s 10 --ci
+    python -m approximatequeryengine_amd.cli "SELECT product_id, AVG(amount) FROM sales GROUP BY product_id HAVING COUNT(*) >= 30 AND SUM(amount) > 1e6" --db sales.db --s 10
     python -m approximatequeryengine_amd.cli --explain
 
 The reference's own CLI defines `-s/--sample` and `-e/--error` but tests `args.s` / `args.e`
@@ -413,6 +414,50 @@ def top_defect(clean: str, args) -> Optional[str]:
     return None
 
 
+_HAVING_CLAIM = re.compile(r"\bHAVING\s+(?=(?:SUM|AVG|COUNT)\s*\()(.*?)(?=\bORDER\s+BY\b|\bLIMIT\b|;|$)", re.IGNORECASE | re.DOTALL)
+
+
+def having_of(clean: str) -> Optional[str]:
+    """The text of a CLAIMED HAVING clause — what follows HAVING begins with SUM, AVG or COUNT and ``(``; letter case and blanks do
+    not matter — up to ORDER BY, LIMIT, ``;`` or the end, or None: every other ``HAVING ...`` (``having 1``, a column name, an
+    alias) stays ignored, as it was."""
+    m = _HAVING_CLAIM.search(clean)
+    return None if m is None else " ".join(m.group(1).split())
+
+
+def without_having(clean: str) -> str:
+    """The query without its claimed HAVING clause (unchanged when there is none): what the select list, WHERE, GROUP BY and
+    ORDER BY ... LIMIT are read from, so that an aggregate named only by the clause is not taken for the query's own."""
+    m = _HAVING_CLAIM.search(clean)
+    return clean if m is None else clean[:m.start()] + clean[m.end():]
+
+
+def having_defect(clean: str, args) -> Optional[str]:
+    """What keeps a query with a claimed HAVING clause from running, found before the table is opened (None: nothing, or no such
+    clause): a clause outside the grammar (aqe_parse_having's message: OR, a third term, =, arithmetic, another aggregate, an
+    alias), no GROUP BY, --e, VARIANCE / STDDEV, MIN / MAX or a time bucket — the forms without a HAVING."""
+    clause = having_of(clean)
+    if clause is None:
+        return None
+    from . import _native as nat, engine
+    try:
+        engine.parse_having(clause)
+    except nat.AqeError as e:
+        return str(e)
+    rest = without_having(clean)
+    if not re.search(r"\bGROUP\s+BY\b", rest, re.IGNORECASE):
+        return "HAVING takes a GROUP BY query: it judges the groups' SUM, AVG or COUNT"
+    if args.e is not None:
+        return "HAVING has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"
+    if re.search(r"\b(VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?)\s*\(", rest, re.IGNORECASE):
+        return "HAVING has no VARIANCE / STDDEV form: the groups are judged under SUM, AVG or COUNT"
+    if re.search(r"\b(MIN|MAX)\s*\(", rest, re.IGNORECASE):
+        return "HAVING has no MIN / MAX form: the groups are judged under SUM, AVG or COUNT"
+    if re.search(r"BUCKET\s*\(", rest, flags=re.IGNORECASE):
+        return "HAVING has no GROUP BY BUCKET(...) form: time buckets are not judged"
+    return None
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV, MIN/MAX, HISTOGRAM, COUNT(DISTINCT), SUMMARY on MI355X "
                                 "(e.g. \"SELECT HISTOGRAM(amount, 20) FROM sales\" --s 10 --ci; \"SELECT SUMMARY(amount) FROM sales\" --s 10 --ci)",
@@ -449,6 +494,12 @@ def run(args, out=sys.stdout) -> int:
         print("error: a query is required unless --explain is given", file=out)
         return 2
     clean, _ = parse_embedded_approx(args.query)
+    full = clean  # (with a claimed HAVING clause, which _run_on finds again)
+    why = having_defect(clean, args)
+    if why is not None:
+        print(f"error: {why}", file=out)
+        return 2
+    clean = without_having(clean)  # the rest of the query is read without it
     why = max_groups_defect(clean, args) or top_defect(clean, args)
     if why is not None:
         print(f"error: {why}", file=out)
@@ -544,7 +595,7 @@ def run(args, out=sys.stdout) -> int:
         print("error: COUNT ... GROUP BY has no error-threshold (--e) form (a grouped COUNT has no interval to judge): "
               "give a sample percentage (--s) or none (exact)", file=out)
         return 2
-    return _open_and_run(args, out, clean)
+    return _open_and_run(args, out, full)
 
 
 def _open_and_run(args, out, clean) -> int:
@@ -592,10 +643,16 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     db._path = ""  # a read-only session must not rewrite the file on close
     n = db.get_total_records()
     print(f"query: {args.query}\ndatabase: {args.db} ({n:,} records{', ' + sharded_note if sharded_note else ''})\ntype: {qtype}", file=out)
+    having = having_of(clean)
+    if having is not None:  # a claimed HAVING clause: the rest of the query is read without it, its aggregate included
+        clean = without_having(clean)
+        agg = aggregate_of(clean)
     key_where = key_where_of(clean)
     kw = {} if key_where is None else {"key_where": key_where}  # (passed only when there is a key predicate)
     if key_where is not None:
         print(f"predicate: WHERE {where_clause_of(clean)}", file=out)
+    if having is not None:
+        print(f"having: HAVING {having}", file=out)
     t0 = time.perf_counter()
     bucket = time_bucket_of(clean)
     if bucket is not None:
@@ -641,6 +698,8 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
         if top is not None:  # ORDER BY the aggregate LIMIT k: the k best groups, selected on the device, in rank order
             gkw.update(top=top[0], ascending=not top[1])
             agg = _top_clause(clean).group(1).upper()  # (the aggregate the clause and the select list name, blanks or not)
+        if having is not None:  # HAVING: judged on the device, only the passing groups come back
+            gkw.update(having=having)
         groups = db.approx_group_by(agg, group_by=", ".join(gb), sample_percent=pct, method="exact" if pct >= 100.0 else "rowid",
                                     where=aqe_backend.parse_where(clean), **gkw)
         ms = (time.perf_counter() - t0) * 1e3
@@ -656,6 +715,10 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
             info = db.last_top_info or {"groups": len(groups), "listed": len(groups), "contenders": 0}
             more = f"; {info['contenders']:,} more within the error of the last listed" if info["contenders"] > 0 else ""
             print(f"   {info['groups']:,} groups, {info['listed']:,} listed{more}", file=out)
+        if having is not None:
+            h = db.last_having_info or {"groups": len(groups), "passed": len(groups), "passed_unsettled": 0, "failed_unsettled": 0}
+            print(f"   {h['groups']:,} groups, {h['passed']:,} pass HAVING ({h['passed_unsettled']:,} of them within the error of the threshold); "
+                  f"{h['failed_unsettled']:,} more could pass within their error", file=out)
         print(f"   execution time: {ms:.2f} ms", file=out)
         db.close_database()
         return 0

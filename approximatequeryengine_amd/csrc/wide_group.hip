@@ -19,6 +19,7 @@
 #include <string>
 
 #include "device_common.hpp"
+#include "having_core.hpp"
 #include "host.hpp"
 #include "key_term.hpp"
 #include "sweep_host.hpp"
@@ -58,30 +59,7 @@ struct WideLaunch {
 };
 static_assert(sizeof(WideLaunch) <= 4096, "kernel arguments are limited to 4 KB");
 
-// Estimate and interval of one group from its sums: group_result of grouped.hip (executor.cpp:277-296), restated here because
-// that one lives in its translation unit.
-__device__ __forceinline__ aqe_group_result wide_result(double n, double sd, double qd, double visited, int64_t key, double c, double pct, int agg) {
-    aqe_group_result r;
-    r.key = key;
-    r.n = static_cast<uint64_t>(n);
-    r.visited = static_cast<uint64_t>(visited);
-    r.sum = sd + n * c;
-    r.sumsq = qd + 2.0 * c * sd + n * c * c;
-    double mean = 0.0, m2 = 0.0;
-    if (n > 0.0) mean_m2(n, sd, qd, c, mean, m2);
-    r.mean = mean;
-    const double scale = 100.0 / pct;
-    double margin = 0.0;
-    if (n >= 2.0) margin = 1.96 * sqrt((m2 / (n - 1.0)) / n);
-    double value;
-    if (agg == AQE_SUM) { value = r.sum * scale; margin *= scale; }
-    else if (agg == AQE_AVG) { value = mean; }
-    else { value = n * scale; margin = 0.0; }
-    r.value = value;
-    r.ci_lower = value - margin;
-    r.ci_upper = value + margin;
-    return r;
-}
+// (wide_result — estimate and interval of one group from its sums — is having_core.hpp's: the HAVING judge shares it.)
 
 template <bool kNT, int NK>
 __global__ __launch_bounds__(kBlockThreads) void k_group_wide(WideLaunch a) {
@@ -269,14 +247,16 @@ __device__ __forceinline__ aqe_group_result top_result(const double* __restrict_
     return wide_result(v[0], v[1], v[2], v[3], key, fin.shift, fin.pct, fin.agg);
 }
 
+// kMarks: under HAVING (k_having_marks' bytes) only a bin marked passed is ranked; without, `marks` is not read.
+template <bool kMarks>
 __global__ __launch_bounds__(kFinishThreads) void k_top_keys(const double* __restrict__ bins, unsigned nbins, WideFinish fin, int descending,
-                                                             u64* __restrict__ keys, unsigned* __restrict__ counts) {
+                                                             const uint8_t* __restrict__ marks, u64* __restrict__ keys, unsigned* __restrict__ counts) {
     __shared__ unsigned wsum[kFinishThreads / 64];
     const unsigned b = blockIdx.x * kFinishThreads + threadIdx.x;
     u64 rk = kTopUnranked;
     if (b < nbins) {
         const double* const v = bins + static_cast<size_t>(b) * kWideBin;
-        if (v[3] > 0.0 && v[0] > 0.0) {
+        if (v[3] > 0.0 && v[0] > 0.0 && (!kMarks || mark_passed(marks[b]))) {
             const double value = top_result(bins, b, fin).value;
             rk = value != value ? kTopNaN : top_rank_key(okey_of_bits(static_cast<u64>(__double_as_longlong(value))), descending != 0);  // (-0.0 folded into +0.0)
         }
@@ -485,6 +465,70 @@ __global__ __launch_bounds__(kFinishThreads) void k_top_contenders(const double*
     }
 }
 
+// ---- HAVING on the groups (aqe_having_spec of include/aqe_hip.h; the judging is having_core.hpp's) ----------------------------
+// Two launches over the (all-reduced) bins, no atomics:
+//   k_having_marks   one thread per bin: having_mark — wide_result once per distinct aggregate of the terms — into one byte per
+//                    bin, and the five counters of aqe_having_info per workgroup by ballots (k_wide_count's pattern).
+//   k_having_finish  k_wide_finish's rank-by-prefix compaction with the flag `passed`: wide_result for q->agg at the rank, the
+//                    last thread writes the count.
+// Under a top spec k_top_keys<true> ranks the bins marked passed and k_top_select / k_top_contenders run as they are.
+constexpr unsigned kHavingCounters = 5;  // groups, candidates, passed, passed_unsettled, failed_unsettled: aqe_having_info's order
+
+// The device block the host copies back in one piece.
+struct HavingBlock {
+    unsigned counts[kHavingCounters][kTopBlocksMax];  // per workgroup of k_having_marks
+    unsigned listed;                                  // k_having_finish: the passing groups
+};
+
+__global__ __launch_bounds__(kFinishThreads) void k_having_marks(const double* __restrict__ bins, unsigned nbins, aqe_having_spec h, double shift, double pct,
+                                                                 uint8_t* __restrict__ marks, HavingBlock* __restrict__ blk) {
+    __shared__ unsigned wsum[kHavingCounters][kFinishThreads / 64];
+    const unsigned b = blockIdx.x * kFinishThreads + threadIdx.x;
+    unsigned m = 0;
+    if (b < nbins) {
+        const double* const v = bins + static_cast<size_t>(b) * kWideBin;
+        m = having_mark(h, v[0], v[1], v[2], v[3], shift, pct);
+        marks[b] = static_cast<uint8_t>(m);
+    }
+    const u64 bal[kHavingCounters] = {__ballot(mark_group(m)), __ballot(mark_candidate(m)), __ballot(mark_passed(m)), __ballot(mark_passed_unsettled(m)),
+                                      __ballot(mark_failed_unsettled(m))};
+    if ((threadIdx.x & 63u) == 0) {
+#pragma unroll
+        for (unsigned k = 0; k < kHavingCounters; ++k) wsum[k][threadIdx.x >> 6] = static_cast<unsigned>(__popcll(bal[k]));
+    }
+    __syncthreads();
+    if (threadIdx.x < kHavingCounters) {
+        unsigned t = 0;
+        for (unsigned w = 0; w < kFinishThreads / 64; ++w) t += wsum[threadIdx.x][w];
+        blk->counts[threadIdx.x][blockIdx.x] = t;
+    }
+}
+
+// One thread per bin: a passing group's result for q->agg at its rank among the passing bins — the passed counts of the
+// workgroups before this one (at most 256: one per thread), then a prefix over this workgroup's flags by ballots.  cap: nothing
+// past it is written.
+__global__ __launch_bounds__(kFinishThreads) void k_having_finish(const double* __restrict__ bins, unsigned nbins, const uint8_t* __restrict__ marks,
+                                                                  HavingBlock* __restrict__ blk, WideFinish fin, aqe_group_result* __restrict__ out,
+                                                                  unsigned cap) {
+    __shared__ unsigned wsum[kFinishThreads / 64];
+    __shared__ unsigned before[kFinishThreads / 64];
+    const unsigned tid = threadIdx.x, b = blockIdx.x * kFinishThreads + tid;
+    // integer sums: any order gives the same offset
+    unsigned mine = tid < blockIdx.x ? blk->counts[2][tid] : 0u;
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+    if ((tid & 63u) == 0) before[tid >> 6] = mine;
+    const bool flag = b < nbins && mark_passed(marks[b < nbins ? b : 0]);
+    const u64 m = __ballot(flag);
+    if ((tid & 63u) == 0) wsum[tid >> 6] = static_cast<unsigned>(__popcll(m));
+    __syncthreads();
+    unsigned pos = 0;
+    for (unsigned w = 0; w < kFinishThreads / 64; ++w) pos += before[w];
+    for (unsigned w = 0; w < (tid >> 6); ++w) pos += wsum[w];
+    pos += static_cast<unsigned>(__popcll(m & ((1ull << (tid & 63u)) - 1ull)));
+    if (flag && pos < cap) out[pos] = top_result(bins, b, fin);
+    if (blockIdx.x == gridDim.x - 1 && tid == kFinishThreads - 1) blk->listed = pos + (flag ? 1u : 0u);
+}
+
 const char* column_name(int column) { return column == AQE_GROUP_REGION ? "region" : "product_id"; }
 
 // The bound and its refusal, in one place: nbins of one column's span (ncols == 1) or of the pair's, and the slices of `slice`
@@ -541,6 +585,11 @@ struct aqe_wide_scratch {
     unsigned* d_tcounts = nullptr;          // [kTopBlocksMax] ranked bins per workgroup of k_top_keys
     aqe::TopBlock* d_top = nullptr;         // info, the cut, the contenders' counts, the listed groups
     aqe::TopBlock* h_top = nullptr;         // its host mirror (pinned)
+    // HAVING (aqe_grouped_having_finish)
+    uint8_t* d_marks = nullptr;             // [nbins] k_having_marks' bytes
+    size_t marks_bytes = 0;
+    aqe::HavingBlock* d_having = nullptr;   // the counters per workgroup, the number listed
+    aqe::HavingBlock* h_having = nullptr;   // its host mirror (pinned)
 };
 
 namespace aqe {
@@ -819,9 +868,10 @@ int ensure_top(aqe_ctx* c, uint32_t nbins) {
 }
 
 // The rank keys, the selection and the contenders over dev_bins on `s`, then info and the listed groups: one copy of the
-// block's head and spec->k entries, 74 856 bytes at most.  The caller has checked spec.
+// block's head and spec->k entries, 74 856 bytes at most.  The caller has checked spec.  marks (null: none): under HAVING, only
+// the bins marked passed are ranked.
 int top_groups(aqe_ctx* c, const aqe_query* q, const GroupCols& g, const double* dev_bins, hipStream_t s, const aqe_top_spec* spec, aqe_group_result* out,
-               aqe_top_info* info) {
+               aqe_top_info* info, const uint8_t* marks = nullptr, uint32_t cap = kTopMax, bool* cap_too_small = nullptr) {
     const uint32_t nbins = g.nbins();
     int rc = ensure_top(c, nbins);
     if (rc != AQE_OK) return rc;
@@ -829,7 +879,8 @@ int top_groups(aqe_ctx* c, const aqe_query* q, const GroupCols& g, const double*
     const unsigned blocks = (nbins + kFinishThreads - 1) / kFinishThreads;
     const WideFinish fin = finish_for(c, q, g);
     const int desc = spec->descending ? 1 : 0;
-    hipLaunchKernelGGL(k_top_keys, dim3(blocks), dim3(kFinishThreads), 0, s, dev_bins, nbins, fin, desc, sc->d_tkeys, sc->d_tcounts);
+    if (marks) hipLaunchKernelGGL(k_top_keys<true>, dim3(blocks), dim3(kFinishThreads), 0, s, dev_bins, nbins, fin, desc, marks, sc->d_tkeys, sc->d_tcounts);
+    else hipLaunchKernelGGL(k_top_keys<false>, dim3(blocks), dim3(kFinishThreads), 0, s, dev_bins, nbins, fin, desc, marks, sc->d_tkeys, sc->d_tcounts);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(k_top_select, dim3(1), dim3(kSelectThreads), 0, s, dev_bins, nbins, sc->d_tkeys, sc->d_tcounts, blocks, fin, spec->k, sc->d_top);
     HIPCHK(c, hipGetLastError());
@@ -843,7 +894,81 @@ int top_groups(aqe_ctx* c, const aqe_query* q, const GroupCols& g, const double*
     uint32_t contenders = 0;
     for (unsigned b = 0; b < blocks; ++b) contenders += h->ccounts[b];  // integers, in workgroup order
     info->contenders = contenders;
+    if (info->listed > cap) {  // (HAVING's entries take the caller's room; no partial list; *info is whole and the stream idle)
+        if (cap_too_small) *cap_too_small = true;
+        return fail(c, AQE_ERR_INVALID, "HAVING: " + std::to_string(info->listed) + " groups listed, more than the caller's buffer holds (cap " + std::to_string(cap) + ")");
+    }
     if (info->listed) std::memcpy(out, h->out, sizeof(aqe_group_result) * info->listed);
+    return AQE_OK;
+}
+
+// aqe_having_spec's bounds, before anything is launched.
+int having_spec_ok(aqe_ctx* c, const aqe_having_spec* h) {
+    if (!h) return fail(c, AQE_ERR_INVALID, "null argument");
+    const char* why = having_spec_error(*h);
+    return why ? fail(c, AQE_ERR_INVALID, std::string("HAVING: ") + why) : AQE_OK;
+}
+
+int ensure_having(aqe_ctx* c, uint32_t nbins) {
+    aqe_wide_scratch* s = c->wide;
+    int rc = grow(c, &s->d_marks, &s->marks_bytes, nbins);
+    if (rc != AQE_OK) return rc;
+    if (!s->d_having) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_having), sizeof(HavingBlock)));
+    if (!s->h_having) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_having), sizeof(HavingBlock), hipHostMallocDefault));
+    return AQE_OK;
+}
+
+// The marks over dev_bins on `s`, then either the compaction of the passing groups (top == null: ascending, as finish_groups
+// lists) or the selection among them; the counters come back with the block of whichever runs last.  The caller has checked
+// the specs.
+int having_groups(aqe_ctx* c, const aqe_query* q, const GroupCols& g, const double* dev_bins, hipStream_t s, const aqe_having_spec* having,
+                  const aqe_top_spec* top, aqe_group_result* out, uint32_t cap, uint32_t* n_listed, aqe_having_info* hinfo, aqe_top_info* tinfo) {
+    const uint32_t nbins = g.nbins();
+    int rc = ensure_having(c, nbins);
+    if (rc != AQE_OK) return rc;
+    aqe_wide_scratch* sc = c->wide;
+    const unsigned blocks = (nbins + kFinishThreads - 1) / kFinishThreads;
+    const WideFinish fin = finish_for(c, q, g);
+    hipLaunchKernelGGL(k_having_marks, dim3(blocks), dim3(kFinishThreads), 0, s, dev_bins, nbins, *having, fin.shift, fin.pct, sc->d_marks, sc->d_having);
+    HIPCHK(c, hipGetLastError());
+    const uint32_t room = std::min(cap, nbins);
+    if (!top) {
+        rc = ensure_groups(c, std::max<size_t>(room, 1));
+        if (rc != AQE_OK) return rc;
+        hipLaunchKernelGGL(k_having_finish, dim3(blocks), dim3(kFinishThreads), 0, s, dev_bins, nbins, sc->d_marks, sc->d_having, fin, sc->d_groups, room);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipMemcpyAsync(sc->h_having, sc->d_having, sizeof(HavingBlock), hipMemcpyDeviceToHost, s));
+    aqe_top_info ti{};
+    if (top) {
+        bool cap_too_small = false;
+        rc = top_groups(c, q, g, dev_bins, s, top, out, &ti, sc->d_marks, cap, &cap_too_small);  // (synchronises s: the block above has arrived)
+        if (rc != AQE_OK && !cap_too_small) {  // any other failure may have left before the synchronisation: the copy into h_having ends first
+            (void)hipStreamSynchronize(s);
+            return rc;
+        }
+    } else {
+        HIPCHK(c, hipStreamSynchronize(s));
+    }
+    const HavingBlock* h = sc->h_having;
+    uint32_t t[kHavingCounters] = {0, 0, 0, 0, 0};
+    for (unsigned k = 0; k < kHavingCounters; ++k)
+        for (unsigned b = 0; b < blocks; ++b) t[k] += h->counts[k][b];  // integers, in workgroup order
+    *hinfo = aqe_having_info{t[0], t[1], t[2], t[3], t[4], 0};
+    if (top) {
+        if (tinfo) *tinfo = ti;
+        *n_listed = ti.listed;
+        return rc;
+    }
+    const uint32_t count = h->listed;
+    *n_listed = count;
+    if (count != t[2]) return fail(c, AQE_ERR_INTERNAL, "HAVING: the compaction and the counters disagree on the passing groups");
+    if (count > cap)  // no partial list
+        return fail(c, AQE_ERR_INVALID, "HAVING: " + std::to_string(count) + " groups pass, more than the caller's buffer holds (cap " + std::to_string(cap) + ")");
+    if (count == 0) return AQE_OK;
+    HIPCHK(c, hipMemcpyAsync(sc->h_groups, sc->d_groups, sizeof(aqe_group_result) * count, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    std::memcpy(out, sc->h_groups, sizeof(aqe_group_result) * count);
     return AQE_OK;
 }
 
@@ -864,6 +989,9 @@ void wide_release(aqe_ctx* c) {
     (void)hipFree(s->d_tcounts);
     (void)hipFree(s->d_top);
     if (s->h_top) (void)hipHostFree(s->h_top);
+    (void)hipFree(s->d_marks);
+    (void)hipFree(s->d_having);
+    if (s->h_having) (void)hipHostFree(s->h_having);
     delete s;
     c->wide = nullptr;
 }
@@ -964,6 +1092,50 @@ int aqe_grouped_top_finish(aqe_ctx* c, const aqe_query* q, int ncols, const int3
     rc = ensure_scratch(c);
     if (rc != AQE_OK) return rc;
     return top_groups(c, q, g, dev_bins, stream_of(c, stream), spec, out, info);
+}
+
+int aqe_reduce_grouped_having(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const int* columns, int ncols, const aqe_having_spec* having,
+                              const aqe_top_spec* top, aqe_group_result* out, uint32_t cap, uint32_t* n_listed, aqe_having_info* having_info,
+                              aqe_top_info* top_info) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_listed || !having_info || (cap && !out)) return fail(c, AQE_ERR_INVALID, "null argument");
+    *n_listed = 0;
+    std::memset(having_info, 0, sizeof *having_info);
+    if (top_info) std::memset(top_info, 0, sizeof *top_info);
+    int rc = having_spec_ok(c, having);
+    if (rc == AQE_OK && top) rc = top_spec_ok(c, top);
+    if (rc != AQE_OK) return rc;
+    GroupCols g;
+    bool empty = false;
+    rc = sweep_whole_table(c, f, q, columns, ncols, &g, &empty);
+    if (rc != AQE_OK || empty) return rc;
+    return having_groups(c, q, g, c->wide->d_bins, c->stream, having, top, out, cap, n_listed, having_info, top_info);
+}
+
+int aqe_grouped_having_finish(aqe_ctx* c, const aqe_query* q, int ncols, const int32_t* key_min, const uint32_t* span, const double* dev_bins, void* stream,
+                              const aqe_having_spec* having, const aqe_top_spec* top, aqe_group_result* out, uint32_t cap, uint32_t* n_listed,
+                              aqe_having_info* having_info, aqe_top_info* top_info) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_listed || !having_info || (cap && !out) || !dev_bins) return fail(c, AQE_ERR_INVALID, "bad argument");
+    *n_listed = 0;
+    std::memset(having_info, 0, sizeof *having_info);
+    if (top_info) std::memset(top_info, 0, sizeof *top_info);
+    int rc = having_spec_ok(c, having);
+    if (rc == AQE_OK && top) rc = top_spec_ok(c, top);
+    if (rc != AQE_OK) return rc;
+    if (q->agg != AQE_SUM && q->agg != AQE_AVG && q->agg != AQE_COUNT) return fail(c, AQE_ERR_INVALID, "GROUP BY (wide) takes SUM, AVG or COUNT");
+    if (ncols != 1 && ncols != 2) return fail(c, AQE_ERR_INVALID, "GROUP BY (wide): one group column or a pair of them");
+    const int cols[2] = {AQE_GROUP_REGION, ncols == 2 ? AQE_GROUP_PRODUCT : 0};  // (the finish reads the ranges, not the columns)
+    GroupCols g;
+    uint32_t nslices = 0;
+    rc = range_ok(c, cols, key_min, span, &g, &nslices, 0);
+    if (rc != AQE_OK) return rc;
+    if (!c->staged) return fail(c, AQE_ERR_NO_TABLE, "no table staged");
+    if (!(q->sample_percent > 0.0)) return fail(c, AQE_ERR_INVALID, "sample_percent must be positive");
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    return having_groups(c, q, g, dev_bins, stream_of(c, stream), having, top, out, cap, n_listed, having_info, top_info);
 }
 
 int aqe_top_from_results(const aqe_group_result* all, uint32_t n_all, const aqe_top_spec* spec, aqe_group_result* out, aqe_top_info* info) {

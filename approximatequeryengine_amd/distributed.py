@@ -489,6 +489,22 @@ def sharded_group_by_top(engine, query, columns, bins, all_reduce_sum: Callable,
         return engine.grouped_top_finish(query, kmin, span, b.data_ptr(), k, descending, stream)
 
 
+def sharded_group_by_having(engine, query, columns, bins, all_reduce_sum: Callable, all_reduce_max: Callable, having, k: Optional[int] = None,
+                            descending: bool = True, stream: int = 0, key_filter=None, max_groups: int = 65536):
+    """HAVING over a GROUP BY across ranks, collective: sharded_group_by_wide's steps unchanged — ONE MAX all-reduce of the key
+    ranges, every rank's part of the sample into nbins x WIDE_BIN sums, ONE all-reduce SUM — then every rank judges the same bins
+    on its device (aqe_grouped_having_finish; with ``k`` the k best passing groups): integer decisions over identical bins, so
+    every rank returns the same (list of GroupResult, HavingInfo, TopInfo or None), bit for bit.  An empty table gives
+    ([], None, None).  ``having`` as Engine.reduce_grouped_having takes it; ``bins`` and ``stream`` as sharded_group_by_wide."""
+    stream = _stream_for(stream, bins)
+    with _torch_on(stream, bins):
+        agreed = _wide_swept_bins(engine, query, columns, bins, all_reduce_sum, all_reduce_max, stream, key_filter)
+        if agreed is None:
+            return [], None, None  # an empty table
+        kmin, span, b = agreed
+        return engine.grouped_having_finish(query, kmin, span, b.data_ptr(), having, k, descending, stream, max_groups)
+
+
 def sharded_extremes(engine, query, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
     """MIN / MAX across the ranks of a process group (engine.Engine interface), collective: every rank sweeps the part of the
     sample inside its shard into EXTREME_VEC doubles (aqe_extremes_enqueue, under ``key_filter`` when there is one), ONE

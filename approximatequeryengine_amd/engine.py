@@ -633,6 +633,38 @@ class Engine:
                                                    C.c_void_p(dev_bins_ptr), C.c_void_p(stream), C.byref(spec), out, C.byref(info)))
         return list(out[: info.listed]), info
 
+    # -- HAVING on the groups (aqe_reduce_grouped_having / aqe_grouped_having_finish): judged and compacted on the device --
+    def reduce_grouped_having(self, query: Query, columns: Sequence[int], having, k: Optional[int] = None, descending: bool = True,
+                              key_filter: "Optional[nat.KeyFilter]" = None, max_groups: int = nat.WIDE_MAX_BINS):
+        """The groups of ``columns`` (one column, or the ordered pair; any span up to 65 536 bins) that pass ``having`` (a
+        HavingSpec, a clause's text or a list of (agg, op, a[, b]): having_spec): (list of GroupResult, HavingInfo, TopInfo or
+        None).  Without ``k`` the list is ascending by key and more than ``max_groups`` passing groups is AqeError(ERR_INVALID)
+        with the count; with ``k`` it is the k best passing groups in reduce_grouped_top's order."""
+        cols = [int(c) for c in columns]
+        spec, top, out, cap = having_spec(having), (None if k is None else _top_spec(k, descending)), None, int(max_groups)
+        if top is not None:
+            cap = _top_room(k)
+        out = self._group_buf(cap)
+        n, hinfo, tinfo = C.c_uint32(), nat.HavingInfo(), nat.TopInfo()
+        self._chk(nat.lib().aqe_reduce_grouped_having(self._h, _filter_ref(key_filter), C.byref(query), _pair(C.c_int, _two(cols, 0)), len(cols),
+                                                      C.byref(spec), C.byref(top) if top is not None else None, out, cap, C.byref(n), C.byref(hinfo),
+                                                      C.byref(tinfo)))
+        return (list((nat.GroupResult * n.value).from_buffer_copy(out)) if n.value else []), hinfo, (tinfo if top is not None else None)
+
+    def grouped_having_finish(self, query: Query, key_min: Sequence[int], span: Sequence[int], dev_bins_ptr: int, having, k: Optional[int] = None,
+                              descending: bool = True, stream: int = 0, max_groups: int = nat.WIDE_MAX_BINS):
+        """The same over the (all-reduced) bins of grouped_wide_enqueue_bins; synchronises ``stream``."""
+        ncols = len(list(span))
+        spec, top, cap = having_spec(having), (None if k is None else _top_spec(k, descending)), int(max_groups)
+        if top is not None:
+            cap = _top_room(k)
+        out = self._group_buf(cap)
+        n, hinfo, tinfo = C.c_uint32(), nat.HavingInfo(), nat.TopInfo()
+        self._chk(nat.lib().aqe_grouped_having_finish(self._h, C.byref(query), ncols, _pair(C.c_int32, _two(key_min, 0)), _pair(C.c_uint32, _two(span, 1)),
+                                                      C.c_void_p(dev_bins_ptr), C.c_void_p(stream), C.byref(spec),
+                                                      C.byref(top) if top is not None else None, out, cap, C.byref(n), C.byref(hinfo), C.byref(tinfo)))
+        return (list((nat.GroupResult * n.value).from_buffer_copy(out)) if n.value else []), hinfo, (tinfo if top is not None else None)
+
     # -- GROUP BY to an error threshold (aqe_reduce_grouped_error and its stepwise multi-GPU form) --
     def reduce_grouped_error(self, query: Query, columns: Sequence[int], error_percent: float, max_percent: float = 100.0,
                              key_filter: "Optional[nat.KeyFilter]" = None, max_groups: int = 1024):
@@ -998,6 +1030,69 @@ def top_from_results(results, k: int, descending: bool = True):
     spec, out, info = _top_spec(k, descending), (nat.GroupResult * _top_room(k))(), nat.TopInfo()
     nat.check(nat.lib().aqe_top_from_results(arr, len(results), C.byref(spec), out, C.byref(info)))
     return list(out[: info.listed]), info
+
+
+_HAVING_AGGS = {"sum": nat.SUM, "avg": nat.AVG, "count": nat.COUNT}
+
+
+def parse_having(text: str) -> "nat.HavingSpec":
+    """aqe_parse_having, host only: the HavingSpec of a clause's text (or of a query that has a HAVING clause).  Raises AqeError
+    (ERR_INVALID) with the library's reason for OR, a third term, = and <>, arithmetic, another aggregate or an alias."""
+    spec = nat.HavingSpec()
+    nat.check(nat.lib().aqe_parse_having(str(text).encode(), C.byref(spec)))
+    return spec
+
+
+def having_spec(having) -> "nat.HavingSpec":
+    """A HavingSpec as given, parsed from a string, or built from a list of (agg, op, a[, b]) with agg one of nat.SUM / AVG /
+    COUNT or 'sum' / 'avg' / 'count' and op one of nat.HAVING_* or '>', '>=', '<', '<=', 'between', 'not between'."""
+    if isinstance(having, nat.HavingSpec):
+        return having
+    if isinstance(having, str):
+        return parse_having(having)
+    terms = [tuple(t) for t in having]
+    if not 1 <= len(terms) <= nat.HAVING_MAX_TERMS:
+        raise ValueError(f"having: a condition is 1 or {nat.HAVING_MAX_TERMS} terms joined by AND, got {len(terms)}")
+    spec = nat.HavingSpec()
+    spec.nterms = len(terms)
+    for i, t in enumerate(terms):
+        if len(t) not in (3, 4):
+            raise ValueError(f"having: a term is (agg, op, a) or (agg, op, a, b), got {t!r}")
+        agg, op = t[0], t[1]
+        if isinstance(agg, str):
+            if agg.lower() not in _HAVING_AGGS:
+                raise ValueError(f"having: a term judges SUM, AVG or COUNT, not {agg!r}")
+            agg = _HAVING_AGGS[agg.lower()]
+        if isinstance(op, str):
+            name = " ".join(op.lower().split())
+            if name not in nat.HAVING_OPS:
+                raise ValueError(f"having: unknown operator {op!r} (>, >=, <, <=, between, not between)")
+            op = nat.HAVING_OPS[name]
+        spec.term[i] = nat.HavingTerm(int(agg), int(op), float(t[2]), float(t[3]) if len(t) == 4 else 0.0)
+    return spec
+
+
+def having_test(term, value: float, ci_lower: float, ci_upper: float) -> Tuple[bool, bool]:
+    """aqe_having_test, host only: (passes, settled) of one term (agg, op, a[, b]) against one figure and its interval."""
+    spec = having_spec([term])
+    passes, settled = C.c_int(), C.c_int()
+    nat.check(nat.lib().aqe_having_test(C.byref(spec.term[0]), float(value), float(ci_lower), float(ci_upper), C.byref(passes), C.byref(settled)))
+    return bool(passes.value), bool(settled.value)
+
+
+def having_from_bins(bins, query: Query, shift: float, key_min: Sequence[int], span: Sequence[int], having, max_groups: int = nat.WIDE_MAX_BINS):
+    """aqe_having_from_bins, host only: the judging of grouped_having_finish over a host copy of the (all-reduced) bins
+    [nbins][WIDE_BIN] with ``shift`` the table's centring (Engine.info().shift): (list of passing GroupResult ascending,
+    HavingInfo).  The figures are the device's own, bit for bit."""
+    flat = np.ascontiguousarray(np.asarray(bins, dtype=np.float64).reshape(-1))
+    nbins = flat.size // nat.WIDE_BIN
+    ncols = len(list(span))
+    spec, cap = having_spec(having), int(max_groups)
+    out, n, info = (nat.GroupResult * max(cap, 1))(), C.c_uint32(), nat.HavingInfo()
+    nat.check(nat.lib().aqe_having_from_bins(flat.ctypes.data_as(C.POINTER(C.c_double)), nbins, ncols, _pair(C.c_int32, _two(key_min, 0)),
+                                             _pair(C.c_uint32, _two(span, 1)), float(shift), C.byref(query), C.byref(spec), out, cap, C.byref(n),
+                                             C.byref(info)))
+    return list(out[: n.value]), info
 
 
 def wide_plan(span: Sequence[int], slice_bins: int = 0) -> Tuple[int, int]:

@@ -25,7 +25,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import _native as nat
-from .aqe_backend import ApproxResult, CustomBPlusDB, GroupEstimate, _AGG, _key_filter_for, _pair_groups, _quantile_call, _top_arg, _top_info_dict, _wide_groups_arg, group_columns
+from .aqe_backend import ApproxResult, CustomBPlusDB, GroupEstimate, _AGG, _LEFT_OUT, _having_arg, _key_filter_for, _pair_groups, _quantile_call, _top_arg, _top_info_dict, _wide_groups_arg, group_columns
 from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, shard_bounds, sharded_adaptive_plan, sharded_group_by, sharded_filtered, sharded_filtered_group_by, sharded_group_by_pair, sharded_group_by_spread, sharded_quantiles, sharded_spread,
                           sharded_stratified_plan, torch_all_reduce, torch_host_all_reduce)
 from .engine import RECORD_DTYPE, Batch, Engine, make_query
@@ -234,17 +234,25 @@ class ShardedBPlusDB(CustomBPlusDB):
 
     def approx_group_by(self, agg: str, group_by: str = "region", sample_percent=None, method=None,
                         where=None, block_size: int = 1000, key_where=None, error_percent=None, max_percent: float = 100.0,
-                        max_groups: int = 1024, top=None, ascending: bool = False) -> "dict[str, GroupEstimate]":
+                        max_groups=_LEFT_OUT, top=None, ascending: bool = False, having=None) -> "dict[str, GroupEstimate]":
         """GROUP BY over all ranks: the key range is agreed (one MAX all-reduce), every rank bins the part of the sample inside
         its region, ONE all-reduce SUM merges the bins (distributed.sharded_group_by; both columns: sharded_group_by_pair).
         With ``error_percent``: level by level, one all-reduce SUM of the bins per level, every rank judging the same sums
         (distributed.sharded_group_by_error).  With ``max_groups`` above 1024 (at most 65 536): SUM / AVG / COUNT through the
         sliced sweep, the key ranges agreed in one MAX all-reduce and nbins x 4 sums merged in ONE all-reduce SUM
         (distributed.sharded_group_by_wide).  With ``top`` = k: the same two all-reduces, then the k best groups are selected on
-        every rank's device from the same bins (distributed.sharded_group_by_top); ``last_top_info`` as CustomBPlusDB keeps it."""
+        every rank's device from the same bins (distributed.sharded_group_by_top); ``last_top_info`` as CustomBPlusDB keeps it.
+        With ``having``: the same two all-reduces, then every rank judges the same bins on its device
+        (distributed.sharded_group_by_having); ``last_having_info`` as CustomBPlusDB keeps it, the same on every rank."""
         import torch
         cols = group_columns(group_by)
         col = cols[0]
+        if having is not None and error_percent is not None:
+            raise ValueError("having with error_percent: HAVING judges SUM, AVG and COUNT at one sample percentage only "
+                             "(the error-threshold form has no HAVING)")
+        hspec = None if having is None else _having_arg(having)
+        if max_groups is _LEFT_OUT:  # 1024, or under having what the wide entry accepts
+            max_groups = nat.WIDE_MAX_BINS if hspec is not None else 1024
         wide = _wide_groups_arg(max_groups, "error_percent" if error_percent is not None else None)
         k = _top_arg(top, "error_percent" if error_percent is not None else None)
         if error_percent is not None:
@@ -255,6 +263,17 @@ class ShardedBPlusDB(CustomBPlusDB):
         self._eng()
         bs = 4096 if (method == "page" and block_size == 1000) else block_size
         q = make_query(m, sample_percent, agg=_AGG[agg.upper()], where=where, block_size=int(bs))
+        if hspec is not None:
+            self.last_having_info = None
+            if k is not None:
+                self.last_top_info = None
+            f = None if key_where is None else _key_filter_for(key_where, method)
+            groups, hinfo, tinfo = _quantile_call(lambda: self._grouped_having(f, q, cols, hspec, k, not ascending, int(max_groups)))
+            if hinfo is not None:  # (None: an empty table)
+                self.last_having_info = hinfo.as_dict()
+            if tinfo is not None:
+                self.last_top_info = _top_info_dict(tinfo, len(cols) == 2)
+            return _pair_groups(groups, GroupEstimate) if len(cols) == 2 else {str(r.key): GroupEstimate(r) for r in groups}
         if k is not None:
             self.last_top_info = None
             f = None if key_where is None else _key_filter_for(key_where, method)
@@ -367,6 +386,17 @@ class ShardedBPlusDB(CustomBPlusDB):
                 self._wide_bins = torch.zeros(nat.WIDE_BIN * nat.WIDE_MAX_BINS, dtype=torch.float64, device=self._dev)
             return sharded_group_by_top(self._engine, q, cols, self._wide_bins, self._ar_sum, self._ar_max, k, descending,
                                         stream=self._side.cuda_stream, key_filter=f)
+
+    # ---- HAVING: the wide form's two all-reduces, then the judging on every rank's device ----
+    def _grouped_having(self, f, q, cols, having, k, descending, max_groups):
+        import torch
+        from .distributed import sharded_group_by_having
+        self._eng()
+        with torch.cuda.stream(self._side):
+            if self._wide_bins is None:
+                self._wide_bins = torch.zeros(nat.WIDE_BIN * nat.WIDE_MAX_BINS, dtype=torch.float64, device=self._dev)
+            return sharded_group_by_having(self._engine, q, cols, self._wide_bins, self._ar_sum, self._ar_max, having, k, descending,
+                                           stream=self._side.cuda_stream, key_filter=f, max_groups=max_groups)
 
     def _spread_groups_pair(self, f, q, kind, cols):
         import torch

@@ -1288,6 +1288,83 @@ AQE_API int aqe_grouped_top_finish(aqe_ctx* ctx, const aqe_query* q, int ncols, 
  * AQE_ERR_INVALID for a null argument or a k outside 1 .. AQE_TOP_MAX; aqe_last_error(NULL) has the text. */
 AQE_API int aqe_top_from_results(const aqe_group_result* all, uint32_t n_all, const aqe_top_spec* spec, aqe_group_result* out, aqe_top_info* info);
 
+/* ---- HAVING on grouped aggregates: judged and compacted on the device (wide_group.hip, having_core.hpp, having_host.hip) -------
+ * "The products with at least 30 sampled rows and more than 1e6 of revenue" of a GROUP BY over up to 65 536 bins: the bins
+ * {n, P1, P2, visited} of the wide sweep stay in device memory, every group is judged there and only the passing groups and
+ * aqe_having_info are copied.
+ *
+ * Terms.  A condition is 1 .. AQE_HAVING_MAX_TERMS terms joined by AND.  A term {agg, op, a, b} names an aggregate (AQE_SUM,
+ * AQE_AVG or AQE_COUNT, independent of q->agg), an operator and one threshold (a) or, for the BETWEEN forms, two (a <= b, both
+ * ends inclusive; b is not read otherwise).  a and b are finite.  There is no = and no <>: equality on an estimate is
+ * meaningless, and aqe_parse_having refuses both by name.  A spec outside this is AQE_ERR_INVALID before anything is launched.
+ *
+ * What a term judges.  value, ci_lower and ci_upper exactly as aqe_grouped_wide_finish reports them for that bin when asked for
+ * the term's aggregate: the 1.96 margin, SUM scaled by 100 / pct and COUNT's zero margin are those of the wide form.  A NaN
+ * value satisfies no term, NOT BETWEEN included.
+ *
+ * Which groups pass.  A group is a candidate when visited > 0 and n > 0 (the rule of the top-N groups: a group without a
+ * qualifying row does not exist in SQL's result).  A candidate passes when every term holds at `value`.
+ *
+ * Settled.  A term is settled when every point of [ci_lower, ci_upper] has the truth `value` has: for the four comparisons both
+ * ends are tested; BETWEEN is settled-true iff ci_lower >= a and ci_upper <= b and settled-false iff ci_upper < a or
+ * ci_lower > b; NOT BETWEEN mirrors that.  A NaN value fails for certain; a NaN end of the interval settles nothing.  A
+ * passing group is settled when all its terms are, a failing group when at least one term is settled-false.  COUNT has no
+ * interval here (the wide form reports none), so a COUNT term is always settled.
+ *
+ * Status.  As aqe_reduce_grouped_wide for the sweep (same plan, same refusals, nbins <= 65 536), as aqe_reduce_grouped_top for
+ * `top`.  No passing group is AQE_OK with *n_listed == 0. */
+#define AQE_HAVING_MAX_TERMS 2
+enum { AQE_HAVING_GT = 0, AQE_HAVING_GE = 1, AQE_HAVING_LT = 2, AQE_HAVING_LE = 3, AQE_HAVING_BETWEEN = 4, AQE_HAVING_NOT_BETWEEN = 5 };
+typedef struct aqe_having_term {
+    int32_t agg; /* AQE_SUM, AQE_AVG or AQE_COUNT */
+    int32_t op;  /* AQE_HAVING_...                */
+    double a, b; /* the threshold; BETWEEN forms: [a, b] */
+} aqe_having_term;
+typedef struct aqe_having_spec {
+    uint32_t nterms; /* 1 .. AQE_HAVING_MAX_TERMS */
+    uint32_t pad;
+    aqe_having_term term[AQE_HAVING_MAX_TERMS];
+} aqe_having_spec;
+typedef struct aqe_having_info {
+    uint32_t groups;           /* visited > 0, as aqe_grouped_wide_finish counts them                  */
+    uint32_t candidates;       /* visited > 0 and n > 0                                                */
+    uint32_t passed;           /* candidates for which every term holds at `value`                     */
+    uint32_t passed_unsettled; /* of those: some term changes its truth within the interval            */
+    uint32_t failed_unsettled; /* unlisted candidates that could pass within their interval            */
+    uint32_t pad;
+} aqe_having_info;
+/* Single GPU, synchronous: the sweep of aqe_reduce_grouped_wide — unchanged, at ANY span up to 65 536 bins — then the judging.
+ * top == NULL: the passing groups ascending by key into out[0 .. *n_listed), every entry bit-identical to the one
+ * aqe_grouped_wide_finish writes for that key; cap below their number is AQE_ERR_INVALID with the count in the message and in
+ * *n_listed, and no partial list.  top != NULL: the top->k best PASSING groups in aqe_reduce_grouped_top's order with its tie
+ * rule (cap below min(top->k, passing) is AQE_ERR_INVALID with that number, no partial list); failing groups are not ranked;
+ * top_info (may be NULL) is aqe_reduce_grouped_top's over the passing groups only.  having_info is always filled.  The judging adds no atomics: identical bins give identical bytes. */
+AQE_API int aqe_reduce_grouped_having(aqe_ctx* ctx, const aqe_key_filter* filter /* NULL: none */, const aqe_query* q, const int columns[2], int ncols,
+                                      const aqe_having_spec* having, const aqe_top_spec* top /* NULL: every passing group */, aqe_group_result* out,
+                                      uint32_t cap, uint32_t* n_listed, aqe_having_info* having_info, aqe_top_info* top_info /* may be NULL */);
+/* Multi-GPU: over the bins of aqe_grouped_wide_enqueue_bins after the all-reduce SUM, in place of aqe_grouped_wide_finish or
+ * aqe_grouped_top_finish (the bins are only read).  Synchronises `stream`.  Every rank lists the same groups, bit for bit. */
+AQE_API int aqe_grouped_having_finish(aqe_ctx* ctx, const aqe_query* q, int ncols, const int32_t key_min[2], const uint32_t span[2], const double* dev_bins,
+                                      void* stream, const aqe_having_spec* having, const aqe_top_spec* top, aqe_group_result* out, uint32_t cap,
+                                      uint32_t* n_listed, aqe_having_info* having_info, aqe_top_info* top_info);
+/* Host only, no GPU and no context: the same judging over bins[nbins][4] = {n, P1, P2, visited} as
+ * aqe_grouped_wide_enqueue_bins leaves them (after the all-reduce), with `shift` the table's centring (aqe_table_info) and
+ * q->agg, q->sample_percent of the query.  The bins, not a finished list: an entry's sum and sumsq are un-centred, and a margin
+ * worked out from them again can differ from the device's in the last bits (m2 = P2 - P1^2 / n cancels differently), which a
+ * threshold on an interval's end would see.  From the bins every figure is the device's own, bit for bit (the library is
+ * built without contraction).  out gets the passing groups ascending, cap as above; key_min / span as the finish takes them. */
+AQE_API int aqe_having_from_bins(const double* bins, uint32_t nbins, int ncols, const int32_t key_min[2], const uint32_t span[2], double shift,
+                                 const aqe_query* q, const aqe_having_spec* having, aqe_group_result* out, uint32_t cap, uint32_t* n_listed,
+                                 aqe_having_info* info);
+/* Host only: one term against one figure and its interval.  AQE_ERR_INVALID for a term outside the contract. */
+AQE_API int aqe_having_test(const aqe_having_term* term, double value, double ci_lower, double ci_upper, int* passes, int* settled);
+/* Host only: the condition of a query text (the text after HAVING, or a whole query with a HAVING clause), case and blanks free:
+ *     <SUM|AVG|COUNT> ( amount | * ) <op> <number> [AND <term>]        op: > >= < <= BETWEEN x AND y, NOT BETWEEN x AND y
+ * `*` is only for COUNT; BETWEEN binds its own AND.  The clause ends at ORDER BY, LIMIT, a ';', a command-line option (" --")
+ * or the end of the text.  AQE_ERR_INVALID with the reason in aqe_last_error(NULL): OR, a third term, = and <> (by name),
+ * arithmetic, another aggregate (STDDEV ...), an alias, a non-finite or missing number, BETWEEN bounds out of order. */
+AQE_API int aqe_parse_having(const char* text, aqe_having_spec* out);
+
 /* ---- per-key time series: GROUP BY a key column and BUCKET(timestamp, W) in one sweep (time_group.hip) ------------------------
  * "Revenue per region per hour": SUM / AVG / COUNT per cell of the grid of ONE key column (AQE_GROUP_REGION or
  * AQE_GROUP_PRODUCT) x the time buckets of an aqe_time_spec.  Everything not said here is §time buckets' and §wide GROUP BY's.
