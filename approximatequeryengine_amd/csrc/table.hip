@@ -101,8 +101,10 @@ int ensure_keys(aqe_ctx* c, int column) {
     if (c->keycol[k] || c->n_local == 0) return AQE_OK;
     if (!c->aos && !c->synthetic)
         return fail(c, AQE_ERR_UNSUPPORTED, "grouped reduction needs the key columns: stage the table with AQE_STAGE_KEEP_AOS");
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->keycol[k]), c->n_local * sizeof(int32_t)));
-    c->hbm_bytes += c->n_local * sizeof(int32_t);
+    // one spare int32 behind the column: the 8-byte dense key loads park masked lanes on rows 0..1
+    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&c->keycol[k]), (c->n_local + 1) * sizeof(int32_t)));
+    HIPCHK(c, hipMemsetAsync(c->keycol[k] + c->n_local, 0, sizeof(int32_t), c->stream));
+    c->hbm_bytes += (c->n_local + 1) * sizeof(int32_t);
     if (c->aos) HIPCHK(c, launch_extract_key(c->aos, c->keycol[k], c->n_local, column, c->stream));
     else HIPCHK(c, launch_synth_key(c->keycol[k], c->n_local, c->shard_lo, column, c->stream));
     int32_t* d_range = nullptr;
@@ -276,7 +278,7 @@ int ensure_key_view(aqe_ctx* c, int column, uint64_t step, const int32_t** view)
     if (!v.keys[k]) {
         int rc = ensure_keys(c, column);
         if (rc != AQE_OK) return rc;
-        const size_t bytes = (static_cast<size_t>(step) * v.M + 2) * sizeof(int32_t);
+        const size_t bytes = (static_cast<size_t>(step) * v.M + 2) * sizeof(int32_t);  // + the spare slots the 8-byte key loads park on
         int32_t* kv = nullptr;
         HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&kv), bytes));
         hipError_t e = hipMemsetAsync(kv, 0, bytes, c->stream);
