@@ -34,6 +34,7 @@
 #include "host.hpp"
 #include "key_term.hpp"
 #include "spread_core.hpp"
+#include "sweep_host.hpp"
 
 namespace aqe {
 namespace {
@@ -307,13 +308,12 @@ void from_vec(const double* vec, int column, int mode, int32_t key_min, double c
 
 // What the distinct entries keep with the context, apart from every other path's scratch.  Allocated on first use.
 struct aqe_distinct_scratch {
-    unsigned long long* d_head = nullptr;  // [kHead]: every launch leaves it at zero
-    unsigned* d_acc = nullptr;             // [kSlots]: every launch leaves it at zero
-    unsigned* d_ticket = nullptr;          // kCounterWords: every launch leaves them at zero
-    double* d_vec = nullptr;               // [kHead + kSlots]
-    double* h_vec = nullptr;               // pinned, mapped: the fused form's result, and where a finish reads a caller's vector
-    double* d_out = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    aqe::DeviceBuf<unsigned long long> d_head;  // [kHead]: every launch leaves it at zero
+    aqe::DeviceBuf<unsigned> d_acc;             // [kSlots]: every launch leaves it at zero
+    aqe::DeviceBuf<unsigned> d_ticket;          // kCounterWords: every launch leaves them at zero
+    aqe::DeviceBuf<double> d_vec;               // [kHead + kSlots]
+    aqe::PinnedBuf<double> h_vec;               // pinned, mapped: the fused form's result, and where a finish reads a caller's vector
+    aqe::Event ev0, ev1;
     bool ready = false;
 };
 
@@ -323,26 +323,21 @@ namespace {
 constexpr Wording kDistinctWords{"COUNT(DISTINCT) does not take the ", "COUNT(DISTINCT) has no GROUP BY form"};
 
 int ensure_scratch(aqe_ctx* c) {
-    if (c->distinct && c->distinct->ready) return AQE_OK;
-    if (c->distinct) distinct_release(c);  // an allocation that failed part way: start over
-    aqe_distinct_scratch* s = new aqe_distinct_scratch;
-    c->distinct = s;  // (distinct_release frees whatever part of it exists)
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_head), sizeof(unsigned long long) * kHead));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_acc), sizeof(unsigned) * kSlots));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_ticket), sizeof(unsigned) * kCounterWords));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_vec), sizeof(double) * kVecWords));
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_vec), sizeof(double) * kVecWords, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&s->d_out), s->h_vec, 0));
-    HIPCHK(c, hipEventCreate(&s->ev0));
-    HIPCHK(c, hipEventCreate(&s->ev1));
-    hipLaunchKernelGGL(k_distinct_init, dim3(1), dim3(kBlockThreads), 0, c->stream, s->d_head, s->d_acc, s->d_ticket);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // (a caller's stream does not wait for the context's)
-    s->ready = true;
-    return AQE_OK;
+    return ensure_scratch(c, c->distinct, [c](aqe_distinct_scratch& s) -> int {
+        int rc = s.d_head.alloc(c, kHead);
+        if (rc == AQE_OK) rc = s.d_acc.alloc(c, kSlots);
+        if (rc == AQE_OK) rc = s.d_ticket.alloc(c, kCounterWords);
+        if (rc == AQE_OK) rc = s.d_vec.alloc(c, kVecWords);
+        if (rc == AQE_OK) rc = s.h_vec.alloc_mapped(c, kVecWords);
+        if (rc == AQE_OK) rc = s.ev0.create(c);
+        if (rc == AQE_OK) rc = s.ev1.create(c);
+        if (rc != AQE_OK) return rc;
+        hipLaunchKernelGGL(k_distinct_init, dim3(1), dim3(kBlockThreads), 0, c->stream, s.d_head, s.d_acc, s.d_ticket);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // (a caller's stream does not wait for the context's)
+        return AQE_OK;
+    });
 }
-
-inline hipStream_t stream_of(aqe_ctx* c, void* stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
 
 // The entries up to the launch, behind their argument checks.
 int prologue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, int column, int mode, aqe_plan** p) {
@@ -370,7 +365,7 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, int column, 
     a.acc = sc->d_acc;
     a.ticket = sc->d_ticket;
     a.vec = vec;
-    a.out = sc->d_out;
+    a.out = sc->h_vec.dev();
     a.fused = fused;
     a.exact_keys = mode == AQE_DISTINCT_EXACT_KEYS ? 1 : 0;
     a.key_min = key_min;
@@ -379,21 +374,9 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, int column, 
     a.wmax = p->q.has_where ? p->q.where_max : std::numeric_limits<double>::infinity();
     unsigned grid = 1;
     a.sw = SweepCommon{};
-    if (p->host.is_random) {
-        a.sw.amount = c->amount;
-        a.sw.shard_lo = c->shard_lo;
-        a.sw.has_where = p->q.has_where ? 1 : 0;
-        a.sw.wmin = p->q.where_min;
-        a.sw.wmax = p->q.where_max;
-        a.idx = p->d_idx;
-        a.n_idx = a.idx ? p->host.random_idx.size() : 0;
-        grid = grid_for(a.n_idx, static_cast<uint64_t>(kDistThreads) * kTileUnroll);
-    } else if (!p->rounds.empty() && c->n_local) {
-        const LaunchDesc& L = p->rounds[0];
-        a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
-        a.ntiles = L.nfam ? L.ntiles : 0;
-        grid = grid_for(a.ntiles, kDistWaves);
-    }
+    const Source src = sweep_source(c, p, a);
+    if (src == Source::index_list) grid = grid_for(a.n_idx, static_cast<uint64_t>(kDistThreads) * kTileUnroll);
+    else if (src == Source::tiles) grid = grid_for(a.ntiles, kDistWaves);
     // key slots: the column counted first (a column without a term passes every key), then the columns the filter names
     int nk = 0;
     a.flt.t[0] = a.flt.t[1] = pass_all();
@@ -442,21 +425,7 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, int column, 
 
 }  // namespace
 
-void distinct_release(aqe_ctx* c) {
-    aqe_distinct_scratch* s = c->distinct;
-    if (!s) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(s->d_head);
-    (void)hipFree(s->d_acc);
-    (void)hipFree(s->d_ticket);
-    (void)hipFree(s->d_vec);
-    if (s->h_vec) (void)hipHostFree(s->h_vec);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    delete s;
-    c->distinct = nullptr;
-}
+void distinct_release(aqe_ctx* c) { release_scratch(c, c->distinct); }
 
 }  // namespace aqe
 

@@ -25,6 +25,7 @@
 #include "host.hpp"
 #include "key_term.hpp"
 #include "spread_core.hpp"
+#include "sweep_host.hpp"
 
 namespace aqe {
 namespace {
@@ -305,17 +306,15 @@ __global__ __launch_bounds__(64) void k_extremes_groups_finish(const double* __r
 
 // What the extremes entries keep with the context, apart from every other path's scratch.  Allocated on first use.
 struct aqe_extreme_scratch {
-    double* d_partials = nullptr;          // [kSweepGridCap][kExVec]
-    unsigned* d_ticket = nullptr;          // kCounterWords: the ungrouped sweep's; every launch leaves them at zero
-    unsigned* d_gticket = nullptr;         // ... the grouped sweep's
-    double* d_vec = nullptr;               // [kExVec]
-    unsigned long long* d_acc = nullptr;   // [kMaxGroupBins][kAccWords]: every launch leaves it neutral
-    double* d_bins = nullptr;              // [kMaxGroupBins][4]
-    aqe_extreme_result* h_out = nullptr;   // pinned, mapped
-    aqe_extreme_result* d_out = nullptr;
-    aqe_extreme_group_result* h_groups = nullptr;  // pinned, mapped: [kMaxGroupBins]
-    aqe_extreme_group_result* d_groups = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    aqe::DeviceBuf<double> d_partials;          // [kSweepGridCap][kExVec]
+    aqe::DeviceBuf<unsigned> d_ticket;          // kCounterWords: the ungrouped sweep's; every launch leaves them at zero
+    aqe::DeviceBuf<unsigned> d_gticket;         // ... the grouped sweep's
+    aqe::DeviceBuf<double> d_vec;               // [kExVec]
+    aqe::DeviceBuf<unsigned long long> d_acc;   // [kMaxGroupBins][kAccWords]: every launch leaves it neutral
+    aqe::DeviceBuf<double> d_bins;              // [kMaxGroupBins][4]
+    aqe::PinnedBuf<aqe_extreme_result> h_out;   // pinned, mapped
+    aqe::PinnedBuf<aqe_extreme_group_result> h_groups;  // pinned, mapped: [kMaxGroupBins]
+    aqe::Event ev0, ev1;
     bool ready = false;
 };
 
@@ -325,37 +324,25 @@ namespace {
 constexpr Wording kExtremeWords{"MIN / MAX do not take the ",
                                 "grouped MIN / MAX takes a single-round family sampler (exact, stride, rowid-mod, block, page, pointer, region ...)"};
 
-template <typename T>
-int pinned(aqe_ctx* c, T** host, T** dev, size_t count) {
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(host), sizeof(T) * count, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(dev), *host, 0));
-    return AQE_OK;
-}
-
 int ensure_scratch(aqe_ctx* c) {
-    if (c->extremes && c->extremes->ready) return AQE_OK;
-    if (c->extremes) extremes_release(c);  // an allocation that failed part way: start over
-    aqe_extreme_scratch* s = new aqe_extreme_scratch;
-    c->extremes = s;  // (extremes_release frees whatever part of it exists)
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_partials), sizeof(double) * kSweepGridCap * kExVec));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_ticket), sizeof(unsigned) * kCounterWords));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_gticket), sizeof(unsigned) * kCounterWords));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_vec), sizeof(double) * kExVec));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_acc), sizeof(unsigned long long) * kMaxGroupBins * kAccWords));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_bins), sizeof(double) * kMaxGroupBins * 4));
-    int rc = pinned(c, &s->h_out, &s->d_out, 1);
-    if (rc == AQE_OK) rc = pinned(c, &s->h_groups, &s->d_groups, kMaxGroupBins);
-    if (rc != AQE_OK) return rc;
-    HIPCHK(c, hipEventCreate(&s->ev0));
-    HIPCHK(c, hipEventCreate(&s->ev1));
-    hipLaunchKernelGGL(k_extremes_init, dim3(1), dim3(kBlockThreads), 0, c->stream, s->d_acc, static_cast<unsigned>(kMaxGroupBins), s->d_ticket, s->d_gticket);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // (a caller's stream does not wait for the context's)
-    s->ready = true;
-    return AQE_OK;
+    return ensure_scratch(c, c->extremes, [c](aqe_extreme_scratch& s) -> int {
+        int rc = s.d_partials.alloc(c, kSweepGridCap * kExVec);
+        if (rc == AQE_OK) rc = s.d_ticket.alloc(c, kCounterWords);
+        if (rc == AQE_OK) rc = s.d_gticket.alloc(c, kCounterWords);
+        if (rc == AQE_OK) rc = s.d_vec.alloc(c, kExVec);
+        if (rc == AQE_OK) rc = s.d_acc.alloc(c, kMaxGroupBins * kAccWords);
+        if (rc == AQE_OK) rc = s.d_bins.alloc(c, kMaxGroupBins * 4);
+        if (rc == AQE_OK) rc = s.h_out.alloc_mapped(c, 1);
+        if (rc == AQE_OK) rc = s.h_groups.alloc_mapped(c, kMaxGroupBins);
+        if (rc == AQE_OK) rc = s.ev0.create(c);
+        if (rc == AQE_OK) rc = s.ev1.create(c);
+        if (rc != AQE_OK) return rc;
+        hipLaunchKernelGGL(k_extremes_init, dim3(1), dim3(kBlockThreads), 0, c->stream, s.d_acc, static_cast<unsigned>(kMaxGroupBins), s.d_ticket, s.d_gticket);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // (a caller's stream does not wait for the context's)
+        return AQE_OK;
+    });
 }
-
-inline hipStream_t stream_of(aqe_ctx* c, void* stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
 
 // What every entry checks of the query's confidence level: the tail fraction is defined inside (0, 1) only.
 int fin_for(aqe_ctx* c, const aqe_query* q, ExtremeFin* out) {
@@ -386,55 +373,23 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, double* vec,
     a.partials = sc->d_partials;
     a.ticket = sc->d_ticket;
     a.vec = vec;
-    a.out = sc->d_out;
+    a.out = sc->h_out.dev();
     a.fused = fused;
     a.fin = fin;
     unsigned grid = 1;
     a.sw = SweepCommon{};
-    if (p->host.is_random) {
-        a.sw.amount = c->amount;
-        a.sw.shard_lo = c->shard_lo;
-        a.sw.has_where = p->q.has_where ? 1 : 0;
-        a.sw.wmin = p->q.where_min;
-        a.sw.wmax = p->q.where_max;
-        a.idx = p->d_idx;
-        a.n_idx = a.idx ? p->host.random_idx.size() : 0;
-        grid = sweep_grid(a.n_idx, static_cast<uint64_t>(kBlockThreads) * kTileUnroll);
-    } else if (!p->rounds.empty() && c->n_local) {
-        const LaunchDesc& L = p->rounds[0];
-        a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
-        a.ntiles = L.nfam ? L.ntiles : 0;
-        grid = sweep_grid(a.ntiles, kWavesPerBlock);
-    }
-    // the columns the filter names, in column order: a column without a term is not read
+    const Source src = sweep_source(c, p, a);
+    if (src == Source::index_list) grid = sweep_grid(a.n_idx, static_cast<uint64_t>(kBlockThreads) * kTileUnroll);
+    else if (src == Source::tiles) grid = sweep_grid(a.ntiles, kWavesPerBlock);
     int nk = 0;
-    a.flt.t[0] = a.flt.t[1] = pass_all();
     const bool work = a.ntiles > 0 || a.n_idx > 0;
-    for (int col = AQE_GROUP_REGION; f && col <= AQE_GROUP_PRODUCT; ++col) {
-        const aqe_key_term& t = f->term[col - 1];
-        if (t.form == AQE_KEYTERM_NONE) continue;
-        compile_term(t, &a.flt.t[nk], a.flt.map[nk]);
-        if (work) {
-            int rc = p->host.is_random ? ensure_keys(c, col) : key_pointer(c, p, col, &a.keys[nk]);
-            if (rc != AQE_OK) return rc;
-            if (p->host.is_random) a.keys[nk] = c->keycol[col - 1];
-        }
-        ++nk;
-    }
+    const int rc = bind_filter(c, p, f, a, &nk);
+    if (rc != AQE_OK) return rc;
     if (!work) nk = 0;  // nothing is read: the kernel only writes the neutral vector
     const bool nt = a.sw.nt != 0;
     c->last_nt = nt ? 1 : 0;
     const dim3 g(grid), b(kBlockThreads);
-    if (nk == 0) {
-        if (nt) hipLaunchKernelGGL((k_extremes<true, 0>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((k_extremes<false, 0>), g, b, 0, s, a);
-    } else if (nk == 1) {
-        if (nt) hipLaunchKernelGGL((k_extremes<true, 1>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((k_extremes<false, 1>), g, b, 0, s, a);
-    } else {
-        if (nt) hipLaunchKernelGGL((k_extremes<true, 2>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((k_extremes<false, 2>), g, b, 0, s, a);
-    }
+    dispatch_nt_nk(nt, nk, [&](auto NT, auto NK) { hipLaunchKernelGGL((k_extremes<decltype(NT)::value, decltype(NK)::value>), g, b, 0, s, a); });
     HIPCHK(c, hipGetLastError());
     return AQE_OK;
 }
@@ -474,20 +429,9 @@ int enqueue_bins(aqe_ctx* c, const aqe_key_filter* f, aqe_plan* p, const GroupCo
         rc = key_pointer(c, p, g.col[i], &a.keys[i]);
         if (rc != AQE_OK) return rc;
     }
-    a.flt.t[0] = a.flt.t[1] = pass_all();
-    int nk = pair ? 2 : 1;
-    if (f) {
-        compile_term(f->term[g.col[0] - 1], &a.flt.t[0], a.flt.map[0]);
-        const int other = g.col[0] == AQE_GROUP_REGION ? AQE_GROUP_PRODUCT : AQE_GROUP_REGION;  // (column B of a pair)
-        if (pair) {
-            compile_term(f->term[other - 1], &a.flt.t[1], a.flt.map[1]);
-        } else if (f->term[other - 1].form != AQE_KEYTERM_NONE) {
-            compile_term(f->term[other - 1], &a.flt.t[1], a.flt.map[1]);
-            rc = key_pointer(c, p, other, &a.keys[1]);
-            if (rc != AQE_OK) return rc;
-            nk = 2;
-        }
-    }
+    int nk = 0;
+    rc = bind_group_filter(g, f, [&](int col, const int32_t** out) { return key_pointer(c, p, col, out); }, a, &nk);
+    if (rc != AQE_OK) return rc;
     const dim3 gd(grouped_grid(L.ntiles)), bd(kBlockThreads);
     const size_t lds_bytes = static_cast<size_t>(nbins) * kLdsBinBytes;
     c->last_nt = a.sw.nt ? 1 : 0;
@@ -502,7 +446,7 @@ int finish_groups(aqe_ctx* c, const GroupCols& g, const ExtremeFin& fin, const d
                   uint32_t* n_groups) {
     aqe_extreme_scratch* sc = c->extremes;
     const uint32_t nbins = g.nbins();
-    hipLaunchKernelGGL(k_extremes_groups_finish, dim3((nbins + 63) / 64), dim3(64), 0, s, dev_bins, g.range(), g.pair() ? 1 : 0, fin, sc->d_groups);
+    hipLaunchKernelGGL(k_extremes_groups_finish, dim3((nbins + 63) / 64), dim3(64), 0, s, dev_bins, g.range(), g.pair() ? 1 : 0, fin, sc->h_groups.dev());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(s));
     uint32_t k = 0;
@@ -530,24 +474,7 @@ int agreed_range(aqe_ctx* c, const int* columns, const int32_t* key_min, const u
 
 }  // namespace
 
-void extremes_release(aqe_ctx* c) {
-    aqe_extreme_scratch* s = c->extremes;
-    if (!s) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(s->d_partials);
-    (void)hipFree(s->d_ticket);
-    (void)hipFree(s->d_gticket);
-    (void)hipFree(s->d_vec);
-    (void)hipFree(s->d_acc);
-    (void)hipFree(s->d_bins);
-    if (s->h_out) (void)hipHostFree(s->h_out);
-    if (s->h_groups) (void)hipHostFree(s->h_groups);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    delete s;
-    c->extremes = nullptr;
-}
+void extremes_release(aqe_ctx* c) { release_scratch(c, c->extremes); }
 
 }  // namespace aqe
 
@@ -599,7 +526,7 @@ int aqe_extremes_finish(aqe_ctx* c, const aqe_query* q, const double* dev_vec, v
     if (rc != AQE_OK) return rc;
     aqe_extreme_scratch* sc = c->extremes;
     hipStream_t s = stream_of(c, stream);
-    hipLaunchKernelGGL(k_extremes_finish, dim3(1), dim3(64), 0, s, dev_vec, fin, sc->d_out);
+    hipLaunchKernelGGL(k_extremes_finish, dim3(1), dim3(64), 0, s, dev_vec, fin, sc->h_out.dev());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(s));
     std::memcpy(out, sc->h_out, sizeof *out);

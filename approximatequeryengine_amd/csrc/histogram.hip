@@ -29,6 +29,7 @@
 #include "host.hpp"
 #include "key_term.hpp"
 #include "spread_core.hpp"
+#include "sweep_host.hpp"
 
 namespace aqe {
 namespace {
@@ -266,12 +267,11 @@ const char* range_defect(double lo, double hi, uint32_t bins) {
 
 // What the histogram entries keep with the context, apart from every other path's scratch.  Allocated on first use.
 struct aqe_histogram_scratch {
-    unsigned long long* d_acc = nullptr;  // [kHead + kMaxBins]: every launch leaves it at zero
-    unsigned* d_ticket = nullptr;         // kCounterWords: every launch leaves them at zero
-    double* d_vec = nullptr;              // [kHead + kMaxBins]
-    double* h_vec = nullptr;              // pinned, mapped: the fused form's result, and where a finish reads a caller's vector
-    double* d_out = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    aqe::DeviceBuf<unsigned long long> d_acc;  // [kHead + kMaxBins]: every launch leaves it at zero
+    aqe::DeviceBuf<unsigned> d_ticket;         // kCounterWords: every launch leaves them at zero
+    aqe::DeviceBuf<double> d_vec;              // [kHead + kMaxBins]
+    aqe::PinnedBuf<double> h_vec;              // pinned, mapped: the fused form's result, and where a finish reads a caller's vector
+    aqe::Event ev0, ev1;
     bool ready = false;
 };
 
@@ -282,25 +282,20 @@ constexpr Wording kHistogramWords{"HISTOGRAM does not take the ", "HISTOGRAM has
 constexpr size_t kVecWords = kHead + kMaxBins;
 
 int ensure_scratch(aqe_ctx* c) {
-    if (c->histogram && c->histogram->ready) return AQE_OK;
-    if (c->histogram) histogram_release(c);  // an allocation that failed part way: start over
-    aqe_histogram_scratch* s = new aqe_histogram_scratch;
-    c->histogram = s;  // (histogram_release frees whatever part of it exists)
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_acc), sizeof(unsigned long long) * kVecWords));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_ticket), sizeof(unsigned) * kCounterWords));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_vec), sizeof(double) * kVecWords));
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_vec), sizeof(double) * kVecWords, hipHostMallocMapped | hipHostMallocCoherent));
-    HIPCHK(c, hipHostGetDevicePointer(reinterpret_cast<void**>(&s->d_out), s->h_vec, 0));
-    HIPCHK(c, hipEventCreate(&s->ev0));
-    HIPCHK(c, hipEventCreate(&s->ev1));
-    hipLaunchKernelGGL(k_histogram_init, dim3(1), dim3(kBlockThreads), 0, c->stream, s->d_acc, static_cast<unsigned>(kVecWords), s->d_ticket);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // (a caller's stream does not wait for the context's)
-    s->ready = true;
-    return AQE_OK;
+    return ensure_scratch(c, c->histogram, [c](aqe_histogram_scratch& s) -> int {
+        int rc = s.d_acc.alloc(c, kVecWords);
+        if (rc == AQE_OK) rc = s.d_ticket.alloc(c, kCounterWords);
+        if (rc == AQE_OK) rc = s.d_vec.alloc(c, kVecWords);
+        if (rc == AQE_OK) rc = s.h_vec.alloc_mapped(c, kVecWords);
+        if (rc == AQE_OK) rc = s.ev0.create(c);
+        if (rc == AQE_OK) rc = s.ev1.create(c);
+        if (rc != AQE_OK) return rc;
+        hipLaunchKernelGGL(k_histogram_init, dim3(1), dim3(kBlockThreads), 0, c->stream, s.d_acc, static_cast<unsigned>(kVecWords), s.d_ticket);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // (a caller's stream does not wait for the context's)
+        return AQE_OK;
+    });
 }
-
-inline hipStream_t stream_of(aqe_ctx* c, void* stream) { return stream ? static_cast<hipStream_t>(stream) : c->stream; }
 
 // The range a call counts over: the caller's, or — spec->has_range == 0 — the table's non-NaN amount range clipped to the
 // amount WHERE bounds.  Refuses a bucket count outside 1 .. 4096 and a range that is not finite or is empty.
@@ -340,11 +335,6 @@ int prologue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const aqe_
     return rc;
 }
 
-template <bool NT, int NK>
-void launch_as(dim3 g, size_t lds, hipStream_t s, const HistLaunch& a) {
-    hipLaunchKernelGGL((k_histogram<NT, NK>), g, dim3(kHistThreads), lds, s, a);
-}
-
 // One launch: this shard's kHead + bins doubles into `vec`, under the filter `f` (null: none); fused: the last workgroup
 // also writes them to the pinned vector.
 int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, const HistRange& rg, double* vec, int fused, hipStream_t s) {
@@ -353,7 +343,7 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, const HistRa
     a.acc = sc->d_acc;
     a.ticket = sc->d_ticket;
     a.vec = vec;
-    a.out = sc->d_out;
+    a.out = sc->h_vec.dev();
     a.fused = fused;
     a.range = rg;
     a.copies = hist_copies(rg.bins);
@@ -361,51 +351,19 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, const HistRa
     a.wmax = p->q.has_where ? p->q.where_max : std::numeric_limits<double>::infinity();
     unsigned grid = 1;
     a.sw = SweepCommon{};
-    if (p->host.is_random) {
-        a.sw.amount = c->amount;
-        a.sw.shard_lo = c->shard_lo;
-        a.sw.has_where = p->q.has_where ? 1 : 0;
-        a.sw.wmin = p->q.where_min;
-        a.sw.wmax = p->q.where_max;
-        a.idx = p->d_idx;
-        a.n_idx = a.idx ? p->host.random_idx.size() : 0;
-        grid = grid_for(a.n_idx, static_cast<uint64_t>(kHistThreads) * kTileUnroll);
-    } else if (!p->rounds.empty() && c->n_local) {
-        const LaunchDesc& L = p->rounds[0];
-        a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
-        a.ntiles = L.nfam ? L.ntiles : 0;
-        grid = grid_for(a.ntiles, kHistWaves);
-    }
-    // the columns the filter names, in column order: a column without a term is not read
+    const Source src = sweep_source(c, p, a);
+    if (src == Source::index_list) grid = grid_for(a.n_idx, static_cast<uint64_t>(kHistThreads) * kTileUnroll);
+    else if (src == Source::tiles) grid = grid_for(a.ntiles, kHistWaves);
     int nk = 0;
-    a.flt.t[0] = a.flt.t[1] = pass_all();
     const bool work = a.ntiles > 0 || a.n_idx > 0;
-    for (int col = AQE_GROUP_REGION; f && col <= AQE_GROUP_PRODUCT; ++col) {
-        const aqe_key_term& t = f->term[col - 1];
-        if (t.form == AQE_KEYTERM_NONE) continue;
-        compile_term(t, &a.flt.t[nk], a.flt.map[nk]);
-        if (work) {
-            int rc = p->host.is_random ? ensure_keys(c, col) : key_pointer(c, p, col, &a.keys[nk]);
-            if (rc != AQE_OK) return rc;
-            if (p->host.is_random) a.keys[nk] = c->keycol[col - 1];
-        }
-        ++nk;
-    }
+    const int rc = bind_filter(c, p, f, a, &nk);
+    if (rc != AQE_OK) return rc;
     if (!work) nk = 0;  // nothing is read: the kernel only writes the zero vector
     const bool nt = a.sw.nt != 0;
     c->last_nt = nt ? 1 : 0;
     const dim3 g(grid);
     const size_t lds = hist_lds_bytes(rg.bins, a.copies);
-    if (nk == 0) {
-        if (nt) launch_as<true, 0>(g, lds, s, a);
-        else launch_as<false, 0>(g, lds, s, a);
-    } else if (nk == 1) {
-        if (nt) launch_as<true, 1>(g, lds, s, a);
-        else launch_as<false, 1>(g, lds, s, a);
-    } else {
-        if (nt) launch_as<true, 2>(g, lds, s, a);
-        else launch_as<false, 2>(g, lds, s, a);
-    }
+    dispatch_nt_nk(nt, nk, [&](auto NT, auto NK) { hipLaunchKernelGGL((k_histogram<decltype(NT)::value, decltype(NK)::value>), g, dim3(kHistThreads), lds, s, a); });
     HIPCHK(c, hipGetLastError());
     return AQE_OK;
 }
@@ -467,20 +425,7 @@ int finish_host(aqe_ctx* c, const aqe_query* q, const HistRange& rg, const doubl
 
 }  // namespace
 
-void histogram_release(aqe_ctx* c) {
-    aqe_histogram_scratch* s = c->histogram;
-    if (!s) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(s->d_acc);
-    (void)hipFree(s->d_ticket);
-    (void)hipFree(s->d_vec);
-    if (s->h_vec) (void)hipHostFree(s->h_vec);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    delete s;
-    c->histogram = nullptr;
-}
+void histogram_release(aqe_ctx* c) { release_scratch(c, c->histogram); }
 
 }  // namespace aqe
 

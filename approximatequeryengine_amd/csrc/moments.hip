@@ -594,54 +594,48 @@ struct LevelRun {
 // What the spread and the filtered entries keep with the context: partials and tickets of the ungrouped sweep, the pinned
 // results, the grouped form's partials, bins and pinned groups.  Allocated on first use.
 struct aqe_moment_scratch {
-    double* d_partials = nullptr;   // [kSweepGridCap][kSpVec]
-    unsigned* d_ticket = nullptr;   // kCounterWords, zeroed once: every launch leaves them at zero
-    double* d_vec = nullptr;        // [kSpVec]
-    aqe_result* h_out = nullptr;    // pinned, mapped
-    aqe_result* d_out = nullptr;
-    aqe_spread_result* h_sout = nullptr;
-    aqe_spread_result* d_sout = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double* d_gpartial = nullptr;   // grown on demand
-    size_t gpartial_bytes = 0;
-    double* d_bins = nullptr;       // [kMaxGroupBins][kSpBin]
-    aqe_group_result* h_groups = nullptr;  // pinned, mapped: [kMaxGroupBins]
-    aqe_group_result* d_groups = nullptr;
-    aqe_spread_group_result* h_sgroups = nullptr;
-    aqe_spread_group_result* d_sgroups = nullptr;
+    aqe::DeviceBuf<double> d_partials;   // [kSweepGridCap][kSpVec]
+    aqe::DeviceBuf<unsigned> d_ticket;   // kCounterWords, zeroed once: every launch leaves them at zero
+    aqe::DeviceBuf<double> d_vec;        // [kSpVec]
+    aqe::PinnedBuf<aqe_result> h_out;    // pinned, mapped
+    aqe::PinnedBuf<aqe_spread_result> h_sout;
+    aqe::Event ev0, ev1;
+    aqe::DeviceBuf<double> d_gpartial;   // grown on demand
+    aqe::DeviceBuf<double> d_bins;       // [kMaxGroupBins][kSpBin]
+    aqe::PinnedBuf<aqe_group_result> h_groups;  // pinned, mapped: [kMaxGroupBins]
+    aqe::PinnedBuf<aqe_spread_group_result> h_sgroups;
+    bool ready = false;
     // GROUP BY to an error threshold (made on first use): cumulative bins, the judge's tickets, the state and its pinned
     // mirror, the rounds' family tables (pinned staging + device), and the query in progress
-    double* d_cum = nullptr;          // [kMaxGroupBins][kSpBin]
-    unsigned* d_lticket = nullptr;    // kCounterWords
-    aqe::LevelState* d_lstate = nullptr;
-    aqe::LevelState* h_lstate = nullptr;   // pinned, mapped
-    aqe::LevelState* hd_lstate = nullptr;  // the device's address of h_lstate
-    aqe::DevFamily* d_lfams = nullptr;     // [kLevelFams]
-    aqe::DevFamily* h_lfams = nullptr;     // pinned
-    aqe::LevelRun* run = nullptr;
+    aqe::DeviceBuf<double> d_cum;          // [kMaxGroupBins][kSpBin]
+    aqe::DeviceBuf<unsigned> d_lticket;    // kCounterWords
+    aqe::DeviceBuf<aqe::LevelState> d_lstate;
+    aqe::PinnedBuf<aqe::LevelState> h_lstate;   // pinned, mapped
+    aqe::DeviceBuf<aqe::DevFamily> d_lfams;     // [kLevelFams]
+    aqe::PinnedBuf<aqe::DevFamily> h_lfams;     // pinned
+    std::unique_ptr<aqe::LevelRun> run;
 };
 
 namespace aqe {
 namespace {
 
 int ensure_scratch(aqe_ctx* c) {
-    if (c->moments) return AQE_OK;
-    aqe_moment_scratch* s = new aqe_moment_scratch;
-    c->moments = s;  // (moments_release frees whatever part of it exists)
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_partials), sizeof(double) * kSweepGridCap * kSpVec));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_ticket), sizeof(unsigned) * kCounterWords));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_vec), sizeof(double) * kSpVec));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_bins), sizeof(double) * kMaxGroupBins * kSpBin));
-    int rc = pinned(c, &s->h_out, &s->d_out, 1);
-    if (rc == AQE_OK) rc = pinned(c, &s->h_sout, &s->d_sout, 1);
-    if (rc == AQE_OK) rc = pinned(c, &s->h_groups, &s->d_groups, kMaxGroupBins);
-    if (rc == AQE_OK) rc = pinned(c, &s->h_sgroups, &s->d_sgroups, kMaxGroupBins);
-    if (rc != AQE_OK) return rc;
-    HIPCHK(c, hipEventCreate(&s->ev0));
-    HIPCHK(c, hipEventCreate(&s->ev1));
-    HIPCHK(c, hipMemset(s->d_ticket, 0, sizeof(unsigned) * kCounterWords));
-    HIPCHK(c, hipDeviceSynchronize());  // (the memset runs on the null stream, which the context's stream does not wait for)
-    return AQE_OK;
+    return ensure_scratch(c, c->moments, [c](aqe_moment_scratch& s) -> int {
+        int rc = s.d_partials.alloc(c, kSweepGridCap * kSpVec);
+        if (rc == AQE_OK) rc = s.d_ticket.alloc(c, kCounterWords);
+        if (rc == AQE_OK) rc = s.d_vec.alloc(c, kSpVec);
+        if (rc == AQE_OK) rc = s.d_bins.alloc(c, kMaxGroupBins * kSpBin);
+        if (rc == AQE_OK) rc = s.h_out.alloc_mapped(c, 1);
+        if (rc == AQE_OK) rc = s.h_sout.alloc_mapped(c, 1);
+        if (rc == AQE_OK) rc = s.h_groups.alloc_mapped(c, kMaxGroupBins);
+        if (rc == AQE_OK) rc = s.h_sgroups.alloc_mapped(c, kMaxGroupBins);
+        if (rc == AQE_OK) rc = s.ev0.create(c);
+        if (rc == AQE_OK) rc = s.ev1.create(c);
+        if (rc != AQE_OK) return rc;
+        HIPCHK(c, hipMemset(s.d_ticket, 0, sizeof(unsigned) * kCounterWords));
+        HIPCHK(c, hipDeviceSynchronize());  // (the memset runs on the null stream, which the context's stream does not wait for)
+        return AQE_OK;
+    });
 }
 
 int check_kind(aqe_ctx* c, int kind) {
@@ -674,58 +668,25 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, double* vec,
     a.partials = sc->d_partials;
     a.ticket = sc->d_ticket;
     a.vec = vec;
-    a.out = sc->d_out;
-    a.out_spread = sc->d_sout;
+    a.out = sc->h_out.dev();
+    a.out_spread = sc->h_sout.dev();
     a.fused = fused;
     a.fin = finalize_for(c, p->q);
     if (sfin) a.sfin = *sfin;
     unsigned grid = 1;
     a.sw = SweepCommon{};
     a.sw.shift = query_shift(c, p->q);
-    if (p->host.is_random) {
-        a.sw.amount = c->amount;
-        a.sw.shard_lo = c->shard_lo;
-        a.sw.has_where = p->q.has_where ? 1 : 0;
-        a.sw.wmin = p->q.where_min;
-        a.sw.wmax = p->q.where_max;
-        a.idx = p->d_idx;
-        a.n_idx = a.idx ? p->host.random_idx.size() : 0;
-        grid = sweep_grid(a.n_idx, static_cast<uint64_t>(kBlockThreads) * kTileUnroll);
-    } else if (!p->rounds.empty() && c->n_local) {
-        const LaunchDesc& L = p->rounds[0];
-        a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
-        a.ntiles = L.nfam ? L.ntiles : 0;
-        grid = sweep_grid(a.ntiles, kWavesPerBlock);
-    }
-    // the columns the filter names, in column order: a column without a term is not read
+    const Source src = sweep_source(c, p, a);
+    if (src == Source::index_list) grid = sweep_grid(a.n_idx, static_cast<uint64_t>(kBlockThreads) * kTileUnroll);
+    else if (src == Source::tiles) grid = sweep_grid(a.ntiles, kWavesPerBlock);
     int nk = 0;
-    a.flt.t[0] = a.flt.t[1] = pass_all();
-    const bool work = a.ntiles > 0 || a.n_idx > 0;
-    for (int col = AQE_GROUP_REGION; f && col <= AQE_GROUP_PRODUCT; ++col) {
-        const aqe_key_term& t = f->term[col - 1];
-        if (t.form == AQE_KEYTERM_NONE) continue;
-        compile_term(t, &a.flt.t[nk], a.flt.map[nk]);
-        if (work) {
-            int rc = p->host.is_random ? ensure_keys(c, col) : key_pointer(c, p, col, &a.keys[nk]);
-            if (rc != AQE_OK) return rc;
-            if (p->host.is_random) a.keys[nk] = c->keycol[col - 1];
-        }
-        ++nk;
-    }
+    const int rc = bind_filter(c, p, f, a, &nk);
+    if (rc != AQE_OK) return rc;
     a.row_bytes = 8u + 4u * static_cast<unsigned>(nk);
     const bool nt = a.sw.nt != 0;
     c->last_nt = nt ? 1 : 0;
     const dim3 g(grid), b(kBlockThreads);
-    if (nk == 0) {
-        if (nt) hipLaunchKernelGGL((k_moments<true, 0>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((k_moments<false, 0>), g, b, 0, s, a);
-    } else if (nk == 1) {
-        if (nt) hipLaunchKernelGGL((k_moments<true, 1>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((k_moments<false, 1>), g, b, 0, s, a);
-    } else {
-        if (nt) hipLaunchKernelGGL((k_moments<true, 2>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((k_moments<false, 2>), g, b, 0, s, a);
-    }
+    dispatch_nt_nk(nt, nk, [&](auto NT, auto NK) { hipLaunchKernelGGL((k_moments<decltype(NT)::value, decltype(NK)::value>), g, b, 0, s, a); });
     HIPCHK(c, hipGetLastError());
     return AQE_OK;
 }
@@ -769,7 +730,7 @@ int spread_finish(aqe_ctx* c, const aqe_query* q, int kind, const double* dev_ve
     if (rc != AQE_OK) return rc;
     aqe_moment_scratch* sc = c->moments;
     hipStream_t s = stream_of(c, stream);
-    hipLaunchKernelGGL(k_spread_finish, dim3(1), dim3(64), 0, s, dev_vec, query_shift(c, *q), fin_for(q, kind), sc->d_sout);
+    hipLaunchKernelGGL(k_spread_finish, dim3(1), dim3(64), 0, s, dev_vec, query_shift(c, *q), fin_for(q, kind), sc->h_sout.dev());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(s));
     std::memcpy(out, sc->h_sout, sizeof *out);
@@ -780,17 +741,10 @@ inline GroupCols one_column(int column, int32_t key_min, uint32_t nbins) { retur
 
 // The grouped sweep's partial buffer, grown on demand.
 int ensure_gpartial(aqe_ctx* c, size_t need) {
-    aqe_moment_scratch* sc = c->moments;
-    if (sc->gpartial_bytes >= need) return AQE_OK;
-    if (sc->d_gpartial) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier sweep may still be reading the buffer
-        (void)hipFree(sc->d_gpartial);
-    }
-    sc->d_gpartial = nullptr;
-    sc->gpartial_bytes = 0;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_gpartial), need));
-    sc->gpartial_bytes = need;
-    return AQE_OK;
+    aqe::DeviceBuf<double>& b = c->moments->d_gpartial;
+    if (b.bytes() >= need) return AQE_OK;
+    if (b) HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier sweep may still be reading the buffer
+    return b.alloc_bytes(c, need);
 }
 
 template <bool PRIV, bool NT, bool STOP>
@@ -832,20 +786,9 @@ int launch_grouped(aqe_ctx* c, const aqe_key_filter* f, const GroupCols& g, cons
             return fail(c, AQE_ERR_INVALID, pair ? "this shard has keys outside [key_min, key_min + span) of a column of the pair"
                                                  : "this shard has keys outside [key_min, key_min + nbins)");
     }
-    a.flt.t[0] = a.flt.t[1] = pass_all();
-    int nk = pair ? 2 : 1;
-    if (f) {
-        compile_term(f->term[g.col[0] - 1], &a.flt.t[0], a.flt.map[0]);
-        const int other = g.col[0] == AQE_GROUP_REGION ? AQE_GROUP_PRODUCT : AQE_GROUP_REGION;  // (column B of a pair)
-        if (pair) {
-            compile_term(f->term[other - 1], &a.flt.t[1], a.flt.map[1]);
-        } else if (f->term[other - 1].form != AQE_KEYTERM_NONE) {
-            compile_term(f->term[other - 1], &a.flt.t[1], a.flt.map[1]);
-            rc = key_of(other, &a.keys[1]);
-            if (rc != AQE_OK) return rc;
-            nk = 2;
-        }
-    }
+    int nk = 0;
+    rc = bind_group_filter(g, f, key_of, a, &nk);
+    if (rc != AQE_OK) return rc;
     const unsigned grid = grouped_grid(ntiles);
     const size_t bins_bytes = static_cast<size_t>(nbins) * kSpBin * sizeof(double);
     rc = ensure_gpartial(c, static_cast<size_t>(grid) * bins_bytes);
@@ -919,9 +862,9 @@ int finish_groups(aqe_ctx* c, const aqe_query* q, const GroupCols& g, const doub
     aqe_moment_scratch* sc = c->moments;
     const uint32_t nbins = g.nbins();
     const dim3 grid((nbins + 63) / 64), block(64);
-    if (g.pair()) hipLaunchKernelGGL(k_groups_finish_pair, grid, block, 0, s, dev_bins, g.range(), query_shift(c, *q), q->sample_percent, q->agg, sc->d_groups);
-    else hipLaunchKernelGGL(k_groups_finish, grid, block, 0, s, dev_bins, nbins, g.kmin[0], query_shift(c, *q), q->sample_percent, q->agg, sc->d_groups);
-    return collect_groups(c, s, sc->h_groups, nbins, out, cap, n_groups);
+    if (g.pair()) hipLaunchKernelGGL(k_groups_finish_pair, grid, block, 0, s, dev_bins, g.range(), query_shift(c, *q), q->sample_percent, q->agg, sc->h_groups.dev());
+    else hipLaunchKernelGGL(k_groups_finish, grid, block, 0, s, dev_bins, nbins, g.kmin[0], query_shift(c, *q), q->sample_percent, q->agg, sc->h_groups.dev());
+    return collect_groups(c, s, sc->h_groups.get(), nbins, out, cap, n_groups);
 }
 
 int finish_spread_groups(aqe_ctx* c, const aqe_query* q, int kind, const GroupCols& g, const double* dev_bins, hipStream_t s,
@@ -929,9 +872,9 @@ int finish_spread_groups(aqe_ctx* c, const aqe_query* q, int kind, const GroupCo
     aqe_moment_scratch* sc = c->moments;
     const uint32_t nbins = g.nbins();
     const dim3 grid((nbins + 63) / 64), block(64);
-    if (g.pair()) hipLaunchKernelGGL(k_spread_groups_finish_pair, grid, block, 0, s, dev_bins, g.range(), query_shift(c, *q), fin_for(q, kind), sc->d_sgroups);
-    else hipLaunchKernelGGL(k_spread_groups_finish, grid, block, 0, s, dev_bins, nbins, g.kmin[0], query_shift(c, *q), fin_for(q, kind), sc->d_sgroups);
-    return collect_groups(c, s, sc->h_sgroups, nbins, out, cap, n_groups);
+    if (g.pair()) hipLaunchKernelGGL(k_spread_groups_finish_pair, grid, block, 0, s, dev_bins, g.range(), query_shift(c, *q), fin_for(q, kind), sc->h_sgroups.dev());
+    else hipLaunchKernelGGL(k_spread_groups_finish, grid, block, 0, s, dev_bins, nbins, g.kmin[0], query_shift(c, *q), fin_for(q, kind), sc->h_sgroups.dev());
+    return collect_groups(c, s, sc->h_sgroups.get(), nbins, out, cap, n_groups);
 }
 
 const char* column_name(int column) { return column == AQE_GROUP_REGION ? "region" : "product_id"; }
@@ -994,18 +937,14 @@ int ensure_level_scratch(aqe_ctx* c) {
     if (rc != AQE_OK) return rc;
     aqe_moment_scratch* sc = c->moments;
     // (each buffer on its own test: a call that failed part way is taken up where it stopped, nothing is allocated twice)
-    if (!sc->d_cum) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_cum), sizeof(double) * kMaxGroupBins * kSpBin));
-    if (!sc->d_lticket) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_lticket), sizeof(unsigned) * kCounterWords));
-    if (!sc->d_lstate) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_lstate), sizeof(LevelState)));
-    if (!sc->d_lfams) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_lfams), sizeof(DevFamily) * kLevelFams));
-    if (!sc->hd_lstate) {
-        if (sc->h_lstate) (void)hipHostFree(sc->h_lstate);  // (pinned, but its device address was refused)
-        sc->h_lstate = nullptr;
-        rc = pinned(c, &sc->h_lstate, &sc->hd_lstate, 1);
-        if (rc != AQE_OK) return rc;
-    }
-    if (!sc->h_lfams) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&sc->h_lfams), sizeof(DevFamily) * kLevelFams, hipHostMallocDefault));
-    if (!sc->run) sc->run = new LevelRun;
+    if (!sc->d_cum) rc = sc->d_cum.alloc(c, kMaxGroupBins * kSpBin);
+    if (rc == AQE_OK && !sc->d_lticket) rc = sc->d_lticket.alloc(c, kCounterWords);
+    if (rc == AQE_OK && !sc->d_lstate) rc = sc->d_lstate.alloc(c, 1);
+    if (rc == AQE_OK && !sc->d_lfams) rc = sc->d_lfams.alloc(c, kLevelFams);
+    if (rc == AQE_OK && !sc->h_lstate.dev()) rc = sc->h_lstate.alloc_mapped(c, 1);  // (anew when its device address was refused)
+    if (rc == AQE_OK && !sc->h_lfams) rc = sc->h_lfams.alloc(c, kLevelFams);
+    if (rc != AQE_OK) return rc;
+    if (!sc->run) sc->run = std::make_unique<LevelRun>();
     return AQE_OK;
 }
 
@@ -1071,7 +1010,7 @@ int level_begin(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const G
         std::memcpy(sc->h_lfams, fams.data(), fams.size() * sizeof(DevFamily));
         HIPCHK(c, hipMemcpyAsync(sc->d_lfams, sc->h_lfams, fams.size() * sizeof(DevFamily), hipMemcpyHostToDevice, s));
     }
-    hipLaunchKernelGGL(k_level_init, dim3(1), dim3(kBlockThreads), 0, s, sc->d_cum, nbins * static_cast<unsigned>(kSpBin), sc->d_lticket, sc->d_lstate, sc->hd_lstate);
+    hipLaunchKernelGGL(k_level_init, dim3(1), dim3(kBlockThreads), 0, s, sc->d_cum, nbins * static_cast<unsigned>(kSpBin), sc->d_lticket, sc->d_lstate, sc->h_lstate.dev());
     HIPCHK(c, hipGetLastError());
     run.launches = 1;
     run.active = true;
@@ -1090,13 +1029,9 @@ int level_sweep(aqe_ctx* c, uint32_t r, hipStream_t s) {
     const LaunchDesc& d = run.rounds[r];
     if (d.ntiles == 0 || d.nfam == 0 || c->n_local == 0) return AQE_OK;
     SweepCommon sw{};
-    sw.amount = c->amount;
-    sw.shard_lo = c->shard_lo;
+    column_source(c, run.q, sw);
     sw.fams = sc->d_lfams + d.fam_offset;
     sw.nfam = d.nfam;
-    sw.has_where = run.q.has_where ? 1 : 0;
-    sw.wmin = run.q.where_min;
-    sw.wmax = run.q.where_max;
     sw.shift = query_shift(c, run.q);
     sw.dense16 = c->dense16 ? 1 : 0;
     sw.nt = sweeps_non_temporal(d.samples) ? 1 : 0;  // (per level: each is a launch of its own size)
@@ -1119,8 +1054,8 @@ int level_judge(aqe_ctx* c, uint32_t r, const double* src, unsigned nblocks, hip
     a.cum = sc->d_cum;
     a.ticket = sc->d_lticket;
     a.state = sc->d_lstate;
-    a.h_state = sc->hd_lstate;
-    a.groups = sc->d_groups;
+    a.h_state = sc->h_lstate.dev();
+    a.groups = sc->h_groups.dev();
     a.g = g.range();
     a.pair = g.pair() ? 1 : 0;
     a.agg = run.q.agg;
@@ -1262,32 +1197,7 @@ int level_columns_ok(aqe_ctx* c, const int* cols) {
     return pair_columns_ok(c, cols);
 }
 
-void moments_release(aqe_ctx* c) {
-    aqe_moment_scratch* s = c->moments;
-    if (!s) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(s->d_partials);
-    (void)hipFree(s->d_ticket);
-    (void)hipFree(s->d_vec);
-    (void)hipFree(s->d_bins);
-    (void)hipFree(s->d_gpartial);
-    if (s->h_out) (void)hipHostFree(s->h_out);
-    if (s->h_sout) (void)hipHostFree(s->h_sout);
-    if (s->h_groups) (void)hipHostFree(s->h_groups);
-    if (s->h_sgroups) (void)hipHostFree(s->h_sgroups);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    (void)hipFree(s->d_cum);
-    (void)hipFree(s->d_lticket);
-    (void)hipFree(s->d_lstate);
-    (void)hipFree(s->d_lfams);
-    if (s->h_lstate) (void)hipHostFree(s->h_lstate);
-    if (s->h_lfams) (void)hipHostFree(s->h_lfams);
-    delete s->run;
-    delete s;
-    c->moments = nullptr;
-}
+void moments_release(aqe_ctx* c) { release_scratch(c, c->moments); }
 
 }  // namespace aqe
 
@@ -1437,7 +1347,7 @@ int aqe_filtered_finish(aqe_ctx* c, const aqe_query* q, const double* dev_vec, v
     if (rc != AQE_OK) return rc;
     aqe_moment_scratch* sc = c->moments;
     hipStream_t s = stream_of(c, stream);
-    hipLaunchKernelGGL(k_result_finish, dim3(1), dim3(64), 0, s, dev_vec, finalize_for(c, *q), sc->d_out);
+    hipLaunchKernelGGL(k_result_finish, dim3(1), dim3(64), 0, s, dev_vec, finalize_for(c, *q), sc->h_out.dev());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(s));
     std::memcpy(out, sc->h_out, sizeof *out);

@@ -28,6 +28,7 @@
 // same vector, so every rank holds the same state.  Both forms run the same fold on the same integers: equal answers.
 #include "device_common.hpp"
 #include "host.hpp"
+#include "sweep_host.hpp"
 
 namespace aqe {
 namespace {
@@ -474,7 +475,7 @@ inline unsigned grid_for(uint64_t work, uint64_t per_block) {
     return static_cast<unsigned>(g < 1 ? 1 : g > kQGrid ? kQGrid : g);
 }
 
-const char* method_name(int m) {
+const char* sampler_name(int m) {
     switch (m) {
         case AQE_M_OPTIMIZED_CLT: return "optimized_clt";
         case AQE_M_CLT_DUAL_POINTER: return "clt";
@@ -594,7 +595,7 @@ int setup_run(aqe_quantile* r, const aqe_query* q, const double* probs, uint32_t
     if (!(q->sample_percent > 0.0)) return fail(c, AQE_ERR_INVALID, "sample_percent must be positive");
     switch (q->method) {
         case AQE_M_OPTIMIZED_CLT: case AQE_M_CLT_DUAL_POINTER: case AQE_M_ADAPTIVE_BLOCK: case AQE_M_STRATIFIED_BLOCK: case AQE_M_RANDOM_DEVICE:
-            return fail(c, AQE_ERR_UNSUPPORTED, std::string("quantiles do not take the ") + method_name(q->method) +
+            return fail(c, AQE_ERR_UNSUPPORTED, std::string("quantiles do not take the ") + sampler_name(q->method) +
                                                     " sampler (single-round family samplers and the seeded random sampler only)");
         default: break;
     }
@@ -609,7 +610,7 @@ int setup_run(aqe_quantile* r, const aqe_query* q, const double* probs, uint32_t
     bool pair = false;
     for (const DevFamily& f : p->h_fams) pair = pair || (f.flags & AQE_F_PAIR);
     if (p->host.is_perm || p->host.is_clt || p->host.on_sorted || p->rounds.size() > 1 || pair)
-        return fail(c, AQE_ERR_UNSUPPORTED, std::string("quantiles do not take the ") + method_name(q->method) +
+        return fail(c, AQE_ERR_UNSUPPORTED, std::string("quantiles do not take the ") + sampler_name(q->method) +
                                                 " sampler (single-round family samplers and the seeded random sampler only)");
     QSpec& s = r->spec;
     s = QSpec{};
@@ -648,26 +649,10 @@ int enqueue_pass(aqe_quantile* r, double* vec, bool fused, hipStream_t s) {
     a.spec = r->spec;
     a.fused = fused ? 1 : 0;
     unsigned grid = 1;
-    if (p->host.is_random) {
-        a.sw = SweepCommon{};
-        a.sw.amount = c->amount;
-        a.sw.shard_lo = c->shard_lo;
-        a.sw.has_where = p->q.has_where ? 1 : 0;
-        a.sw.wmin = p->q.where_min;
-        a.sw.wmax = p->q.where_max;
-        a.idx = p->d_idx;
-        a.n_idx = p->host.random_idx.size();
-        if (!a.idx) a.n_idx = 0;
-        grid = grid_for(a.n_idx, static_cast<uint64_t>(kBlockThreads) * kTileUnroll);
-    } else if (!p->rounds.empty() && c->n_local) {
-        const LaunchDesc& L = p->rounds[0];
-        a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
-        a.ntiles = L.nfam ? L.ntiles : 0;
-        grid = grid_for(a.ntiles, kWavesPerBlock);
-    } else {
-        a.sw = SweepCommon{};
-        a.ntiles = 0;
-    }
+    a.sw = SweepCommon{};
+    const Source src = sweep_source(c, p, a);
+    if (src == Source::index_list) grid = grid_for(a.n_idx, static_cast<uint64_t>(kBlockThreads) * kTileUnroll);
+    else if (src == Source::tiles) grid = grid_for(a.ntiles, kWavesPerBlock);
     c->last_nt = 0;  // (the pass masks every dense tile and has the plain instantiation only, whatever a.sw.nt says)
     hipLaunchKernelGGL(k_qpass, dim3(grid), dim3(kBlockThreads), 0, s, a);
     HIPCHK(c, hipGetLastError());

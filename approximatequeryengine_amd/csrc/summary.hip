@@ -237,13 +237,12 @@ __global__ __launch_bounds__(64) void k_summary_finish(const double* __restrict_
 
 // What the summary entries keep with the context, apart from every other path's scratch.  Allocated on first use.
 struct aqe_summary_scratch {
-    double* d_partials = nullptr;    // [kSweepGridCap][kSpVec]
-    double* d_xpartials = nullptr;   // [kSweepGridCap][kXWords]
-    unsigned* d_ticket = nullptr;    // kCounterWords, zeroed once: every launch leaves them at zero
-    double* d_vec = nullptr;         // [kSumVec]
-    aqe_summary_result* h_out = nullptr;  // pinned, mapped
-    aqe_summary_result* d_out = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    aqe::DeviceBuf<double> d_partials;    // [kSweepGridCap][kSpVec]
+    aqe::DeviceBuf<double> d_xpartials;   // [kSweepGridCap][kXWords]
+    aqe::DeviceBuf<unsigned> d_ticket;    // kCounterWords, zeroed once: every launch leaves them at zero
+    aqe::DeviceBuf<double> d_vec;         // [kSumVec]
+    aqe::PinnedBuf<aqe_summary_result> h_out;  // pinned, mapped
+    aqe::Event ev0, ev1;
     bool ready = false;
 };
 
@@ -253,22 +252,19 @@ namespace {
 constexpr Wording kSummaryWords{"SUMMARY does not take the ", "SUMMARY has no grouped form"};
 
 int ensure_scratch(aqe_ctx* c) {
-    if (c->summary && c->summary->ready) return AQE_OK;
-    if (c->summary) summary_release(c);  // an allocation that failed part way: start over
-    aqe_summary_scratch* s = new aqe_summary_scratch;
-    c->summary = s;  // (summary_release frees whatever part of it exists)
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_partials), sizeof(double) * kSweepGridCap * kSpVec));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_xpartials), sizeof(double) * kSweepGridCap * kXWords));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_ticket), sizeof(unsigned) * kCounterWords));
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_vec), sizeof(double) * kSumVec));
-    const int rc = pinned(c, &s->h_out, &s->d_out, 1);
-    if (rc != AQE_OK) return rc;
-    HIPCHK(c, hipEventCreate(&s->ev0));
-    HIPCHK(c, hipEventCreate(&s->ev1));
-    HIPCHK(c, hipMemset(s->d_ticket, 0, sizeof(unsigned) * kCounterWords));
-    HIPCHK(c, hipDeviceSynchronize());  // (the memset runs on the null stream, which the context's stream does not wait for)
-    s->ready = true;
-    return AQE_OK;
+    return ensure_scratch(c, c->summary, [c](aqe_summary_scratch& s) -> int {
+        int rc = s.d_partials.alloc(c, kSweepGridCap * kSpVec);
+        if (rc == AQE_OK) rc = s.d_xpartials.alloc(c, kSweepGridCap * kXWords);
+        if (rc == AQE_OK) rc = s.d_ticket.alloc(c, kCounterWords);
+        if (rc == AQE_OK) rc = s.d_vec.alloc(c, kSumVec);
+        if (rc == AQE_OK) rc = s.h_out.alloc_mapped(c, 1);
+        if (rc == AQE_OK) rc = s.ev0.create(c);
+        if (rc == AQE_OK) rc = s.ev1.create(c);
+        if (rc != AQE_OK) return rc;
+        HIPCHK(c, hipMemset(s.d_ticket, 0, sizeof(unsigned) * kCounterWords));
+        HIPCHK(c, hipDeviceSynchronize());  // (the memset runs on the null stream, which the context's stream does not wait for)
+        return AQE_OK;
+    });
 }
 
 // The shift c of the power sums: the query's (query_shift of host.hpp — k_moments' c, so the moment words are k_moments'),
@@ -319,78 +315,32 @@ int enqueue_sweep(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, double* vec,
     a.xpartials = sc->d_xpartials;
     a.ticket = sc->d_ticket;
     a.vec = vec;
-    a.out = sc->d_out;
+    a.out = sc->h_out.dev();
     a.fused = fused;
     unsigned grid = 1;
     a.sw = SweepCommon{};
-    if (p->host.is_random) {
-        a.sw.amount = c->amount;
-        a.sw.shard_lo = c->shard_lo;
-        a.sw.has_where = p->q.has_where ? 1 : 0;
-        a.sw.wmin = p->q.where_min;
-        a.sw.wmax = p->q.where_max;
-        a.idx = p->d_idx;
-        a.n_idx = a.idx ? p->host.random_idx.size() : 0;
-        grid = sweep_grid(a.n_idx, static_cast<uint64_t>(kBlockThreads) * kTileUnroll);
-    } else if (!p->rounds.empty() && c->n_local) {
-        const LaunchDesc& L = p->rounds[0];
-        a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
-        a.ntiles = L.nfam ? L.ntiles : 0;
-        grid = sweep_grid(a.ntiles, kWavesPerBlock);
-    }
+    const Source src = sweep_source(c, p, a);
+    if (src == Source::index_list) grid = sweep_grid(a.n_idx, static_cast<uint64_t>(kBlockThreads) * kTileUnroll);
+    else if (src == Source::tiles) grid = sweep_grid(a.ntiles, kWavesPerBlock);
     a.sw.shift = fin.fin.shift;  // (query_shift, what sweep_common has put there, whenever that is finite)
-    // the columns the filter names, in column order: a column without a term is not read
     int nk = 0;
-    a.flt.t[0] = a.flt.t[1] = pass_all();
     const bool work = a.ntiles > 0 || a.n_idx > 0;
-    for (int col = AQE_GROUP_REGION; f && col <= AQE_GROUP_PRODUCT; ++col) {
-        const aqe_key_term& t = f->term[col - 1];
-        if (t.form == AQE_KEYTERM_NONE) continue;
-        compile_term(t, &a.flt.t[nk], a.flt.map[nk]);
-        if (work) {
-            int rc = p->host.is_random ? ensure_keys(c, col) : key_pointer(c, p, col, &a.keys[nk]);
-            if (rc != AQE_OK) return rc;
-            if (p->host.is_random) a.keys[nk] = c->keycol[col - 1];
-        }
-        ++nk;
-    }
+    const int rc = bind_filter(c, p, f, a, &nk);
+    if (rc != AQE_OK) return rc;
     fin.row_bytes = 8u + 4u * static_cast<unsigned>(nk);
     a.fin = fin;
     if (!work) nk = 0;  // nothing is read: the kernel only writes the neutral vector
     const bool nt = a.sw.nt != 0;
     c->last_nt = nt ? 1 : 0;
     const dim3 g(grid), b(kBlockThreads);
-    if (nk == 0) {
-        if (nt) hipLaunchKernelGGL((k_summary<true, 0>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((k_summary<false, 0>), g, b, 0, s, a);
-    } else if (nk == 1) {
-        if (nt) hipLaunchKernelGGL((k_summary<true, 1>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((k_summary<false, 1>), g, b, 0, s, a);
-    } else {
-        if (nt) hipLaunchKernelGGL((k_summary<true, 2>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((k_summary<false, 2>), g, b, 0, s, a);
-    }
+    dispatch_nt_nk(nt, nk, [&](auto NT, auto NK) { hipLaunchKernelGGL((k_summary<decltype(NT)::value, decltype(NK)::value>), g, b, 0, s, a); });
     HIPCHK(c, hipGetLastError());
     return AQE_OK;
 }
 
 }  // namespace
 
-void summary_release(aqe_ctx* c) {
-    aqe_summary_scratch* s = c->summary;
-    if (!s) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(s->d_partials);
-    (void)hipFree(s->d_xpartials);
-    (void)hipFree(s->d_ticket);
-    (void)hipFree(s->d_vec);
-    if (s->h_out) (void)hipHostFree(s->h_out);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    delete s;
-    c->summary = nullptr;
-}
+void summary_release(aqe_ctx* c) { release_scratch(c, c->summary); }
 
 }  // namespace aqe
 
@@ -442,7 +392,7 @@ int aqe_summary_finish(aqe_ctx* c, const aqe_query* q, const double* dev_vec, vo
     if (rc != AQE_OK) return rc;
     aqe_summary_scratch* sc = c->summary;
     hipStream_t s = stream_of(c, stream);
-    hipLaunchKernelGGL(k_summary_finish, dim3(1), dim3(64), 0, s, dev_vec, fin.fin.shift, fin, sc->d_out);
+    hipLaunchKernelGGL(k_summary_finish, dim3(1), dim3(64), 0, s, dev_vec, fin.fin.shift, fin, sc->h_out.dev());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(s));
     std::memcpy(out, sc->h_out, sizeof *out);

@@ -423,16 +423,13 @@ int column_ok(aqe_ctx* c, int column) {
 // What the time-series entries keep with the context.  Allocated on first use at the size the call needs, grown when a later
 // call needs more, freed with the context.
 struct aqe_series_scratch {
-    double* d_partial = nullptr;  // [nslices][grid][slice_bins][4]
-    size_t partial_bytes = 0;
-    double* d_bins = nullptr;     // [nbins][4]
-    size_t bins_bytes = 0;
-    aqe_series_result* d_cells = nullptr;  // the compacted list
-    aqe_series_result* h_cells = nullptr;  // its host mirror (pinned)
-    size_t cells_cap = 0;
-    unsigned* d_counts = nullptr;  // [kMaxSeriesBins / kSeriesFinishThreads + 1]: per finishing workgroup, then the number of cells
-    unsigned* h_count = nullptr;   // pinned
-    bool lds_opted = false;        // every instantiation of k_time_group may take kSeriesMaxSlice bins of dynamic LDS
+    aqe::DeviceBuf<double> d_partial;  // [nslices][grid][slice_bins][4]
+    aqe::DeviceBuf<double> d_bins;     // [nbins][4]
+    aqe::DeviceBuf<aqe_series_result> d_cells;  // the compacted list
+    aqe::PinnedBuf<aqe_series_result> h_cells;  // its host mirror (pinned)
+    aqe::DeviceBuf<unsigned> d_counts;  // [kMaxSeriesBins / kSeriesFinishThreads + 1]: per finishing workgroup, then the number of cells
+    aqe::PinnedBuf<unsigned> h_count;   // pinned
+    bool lds_opted = false;             // every instantiation of k_time_group may take kSeriesMaxSlice bins of dynamic LDS
 };
 
 namespace aqe {
@@ -440,42 +437,14 @@ namespace {
 
 constexpr Wording kSeriesWords{"time buckets do not take the ", "time buckets have no second GROUP BY column"};  // aqe_reduce_time_buckets' words
 
-template <typename T>
-int grow(aqe_ctx* c, T** p, size_t* have, size_t need) {
-    if (*have >= need) return AQE_OK;
-    if (*p) {
-        HIPCHK(c, hipDeviceSynchronize());  // an earlier sweep (on any stream) may still be using the buffer
-        (void)hipFree(*p);
-    }
-    *p = nullptr;
-    *have = 0;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(p), need));
-    *have = need;
-    return AQE_OK;
-}
-
+// (each member on its own test: a call that failed part way is taken up where it stopped)
 int ensure_scratch(aqe_ctx* c) {
     if (!c->series) c->series = new aqe_series_scratch;  // (series_release frees whatever part of it exists)
     aqe_series_scratch* s = c->series;
-    if (!s->d_counts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_counts), sizeof(unsigned) * (kMaxSeriesBins / kSeriesFinishThreads + 1)));
-    if (!s->h_count) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_count), sizeof(unsigned), hipHostMallocDefault));
-    return AQE_OK;
-}
-
-int ensure_cells(aqe_ctx* c, size_t count) {
-    aqe_series_scratch* s = c->series;
-    if (s->cells_cap >= count) return AQE_OK;
-    if (s->d_cells) {
-        HIPCHK(c, hipDeviceSynchronize());
-        (void)hipFree(s->d_cells);
-    }
-    if (s->h_cells) (void)hipHostFree(s->h_cells);
-    s->d_cells = s->h_cells = nullptr;
-    s->cells_cap = 0;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_cells), sizeof(aqe_series_result) * count));
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_cells), sizeof(aqe_series_result) * count, hipHostMallocDefault));
-    s->cells_cap = count;
-    return AQE_OK;
+    int rc = AQE_OK;
+    if (!s->d_counts) rc = s->d_counts.alloc(c, kMaxSeriesBins / kSeriesFinishThreads + 1);
+    if (rc == AQE_OK && !s->h_count) rc = s->h_count.alloc(c, 1);
+    return rc;
 }
 
 // More than 64 KiB of dynamic LDS needs opting in, once per instantiation; a failure never reaches a launch.
@@ -553,21 +522,9 @@ int enqueue_bins(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, int column, c
     SeriesLaunch a{};
     a.sw = SweepCommon{};
     unsigned cap_x = 1;
-    if (p->host.is_random) {
-        a.sw.amount = c->amount;
-        a.sw.shard_lo = c->shard_lo;
-        a.sw.has_where = p->q.has_where ? 1 : 0;
-        a.sw.wmin = p->q.where_min;
-        a.sw.wmax = p->q.where_max;
-        a.idx = p->d_idx;
-        a.n_idx = a.idx ? p->host.random_idx.size() : 0;
-        cap_x = blocks_for(a.n_idx, static_cast<u64>(kBlockThreads) * kTileUnroll, kGroupedMaxBlocks);
-    } else if (!p->rounds.empty() && c->n_local) {
-        const LaunchDesc& L = p->rounds[0];
-        a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
-        a.ntiles = L.nfam ? L.ntiles : 0;
-        cap_x = grouped_grid(a.ntiles);
-    }
+    const Source src = sweep_source(c, p, a);
+    if (src == Source::index_list) cap_x = blocks_for(a.n_idx, static_cast<u64>(kBlockThreads) * kTileUnroll, kGroupedMaxBlocks);
+    else if (src == Source::tiles) cap_x = grouped_grid(a.ntiles);
     a.sw.shift = query_shift(c, p->q);
     const bool work = (a.ntiles > 0 || a.n_idx > 0) && c->n_local > 0;
     int rc = work ? ensure_time(c) : AQE_OK;
@@ -625,7 +582,7 @@ int enqueue_bins(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, int column, c
     const size_t slice_bytes = static_cast<size_t>(sb) * kSeriesBin * sizeof(double);
     const size_t lds_bytes = slice_bytes * a.copies;
     aqe_series_scratch* sc = c->series;
-    rc = grow(c, &sc->d_partial, &sc->partial_bytes, static_cast<size_t>(nslices) * grid_x * slice_bytes);
+    rc = sc->d_partial.grow(c, static_cast<size_t>(nslices) * grid_x * slice_bytes);
     if (rc == AQE_OK) rc = ensure_lds(c);
     if (rc != AQE_OK) return rc;
     a.partial = sc->d_partial;
@@ -654,7 +611,7 @@ int finish_cells(aqe_ctx* c, const aqe_query* q, const aqe_time_spec* spec, cons
     aqe_series_scratch* sc = c->series;
     const uint32_t nbins = sp.nbins;
     const uint32_t room = std::min(cap, nbins);
-    int rc = ensure_cells(c, std::max<size_t>(room, 1));
+    int rc = grow_mirrored(c, sc->d_cells, sc->h_cells, std::max<size_t>(room, 1));
     if (rc != AQE_OK) return rc;
     const unsigned blocks = (nbins + kSeriesFinishThreads - 1) / kSeriesFinishThreads;
     hipLaunchKernelGGL(k_series_count, dim3(blocks), dim3(kSeriesFinishThreads), 0, s, dev_bins, nbins, sc->d_counts);
@@ -676,20 +633,7 @@ int finish_cells(aqe_ctx* c, const aqe_query* q, const aqe_time_spec* spec, cons
 
 }  // namespace
 
-void series_release(aqe_ctx* c) {
-    aqe_series_scratch* s = c->series;
-    if (!s) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(s->d_partial);
-    (void)hipFree(s->d_bins);
-    (void)hipFree(s->d_cells);
-    (void)hipFree(s->d_counts);
-    if (s->h_cells) (void)hipHostFree(s->h_cells);
-    if (s->h_count) (void)hipHostFree(s->h_count);
-    delete s;
-    c->series = nullptr;
-}
+void series_release(aqe_ctx* c) { release_scratch(c, c->series); }
 
 }  // namespace aqe
 
@@ -729,7 +673,7 @@ int aqe_reduce_time_groups(aqe_ctx* c, const aqe_key_filter* f, const aqe_query*
     if (rc != AQE_OK) return fail(c, rc, sp.why);
     if (sp.nbins == 0) return fail(c, AQE_ERR_INVALID, "No samples collected");
     aqe_series_scratch* sc = c->series;
-    rc = grow(c, &sc->d_bins, &sc->bins_bytes, static_cast<size_t>(sp.nbins) * kSeriesBin * sizeof(double));
+    rc = sc->d_bins.grow(c, static_cast<size_t>(sp.nbins) * kSeriesBin * sizeof(double));
     if (rc == AQE_OK) rc = enqueue_bins(c, p, f, group_column, spec, sp, slice, sc->d_bins, c->stream);
     if (rc != AQE_OK) return rc;
     return finish_cells(c, q, spec, sp, sc->d_bins, c->stream, out, cap, n_groups);

@@ -507,11 +507,10 @@ struct TimeParse {
 
 // What the time-bucket entries keep with the context.  Allocated on first use.
 struct aqe_time_scratch {
-    double* d_partial = nullptr;  // [grid][nbins][4], grown on demand
-    size_t partial_bytes = 0;
-    double* d_bins = nullptr;     // [kMaxGroupBins][4]
-    aqe_group_result* h_groups = nullptr;  // pinned, mapped: [kMaxGroupBins]
-    aqe_group_result* d_groups = nullptr;
+    aqe::DeviceBuf<double> d_partial;  // [grid][nbins][4], grown on demand
+    aqe::DeviceBuf<double> d_bins;     // [kMaxGroupBins][4]
+    aqe::PinnedBuf<aqe_group_result> h_groups;  // pinned, mapped: [kMaxGroupBins]
+    bool ready = false;
 };
 
 namespace aqe {
@@ -520,25 +519,10 @@ namespace {
 constexpr Wording kTimeWords{"time buckets do not take the ", "time buckets have no second GROUP BY column"};
 
 int ensure_scratch(aqe_ctx* c) {
-    if (c->timeseries) return AQE_OK;
-    aqe_time_scratch* s = new aqe_time_scratch;
-    c->timeseries = s;  // (timeseries_release frees whatever part of it exists)
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_bins), sizeof(double) * kMaxGroupBins * kTimeBin));
-    return pinned(c, &s->h_groups, &s->d_groups, kMaxGroupBins);
-}
-
-int ensure_partial(aqe_ctx* c, size_t need) {
-    aqe_time_scratch* sc = c->timeseries;
-    if (sc->partial_bytes >= need) return AQE_OK;
-    if (sc->d_partial) {
-        HIPCHK(c, hipDeviceSynchronize());  // an earlier sweep (on any stream) may still be using the buffer
-        (void)hipFree(sc->d_partial);
-    }
-    sc->d_partial = nullptr;
-    sc->partial_bytes = 0;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&sc->d_partial), need));
-    sc->partial_bytes = need;
-    return AQE_OK;
+    return ensure_scratch(c, c->timeseries, [c](aqe_time_scratch& s) -> int {  // (no neutral-value step: every launch writes what it reads)
+        const int rc = s.d_bins.alloc(c, kMaxGroupBins * kTimeBin);
+        return rc == AQE_OK ? s.h_groups.alloc_mapped(c, kMaxGroupBins) : rc;
+    });
 }
 
 // The one key column a filter may carry a term on (0: none); terms on both are refused.
@@ -586,21 +570,9 @@ int enqueue_bins(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, int column, c
     TimeLaunch a{};
     unsigned grid = 1;
     a.sw = SweepCommon{};
-    if (p->host.is_random) {
-        a.sw.amount = c->amount;
-        a.sw.shard_lo = c->shard_lo;
-        a.sw.has_where = p->q.has_where ? 1 : 0;
-        a.sw.wmin = p->q.where_min;
-        a.sw.wmax = p->q.where_max;
-        a.idx = p->d_idx;
-        a.n_idx = a.idx ? p->host.random_idx.size() : 0;
-        grid = blocks_for(a.n_idx, static_cast<u64>(kBlockThreads) * kTileUnroll, kGroupedMaxBlocks);
-    } else if (!p->rounds.empty() && c->n_local) {
-        const LaunchDesc& L = p->rounds[0];
-        a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
-        a.ntiles = L.nfam ? L.ntiles : 0;
-        grid = grouped_grid(a.ntiles);
-    }
+    const Source src = sweep_source(c, p, a);
+    if (src == Source::index_list) grid = blocks_for(a.n_idx, static_cast<u64>(kBlockThreads) * kTileUnroll, kGroupedMaxBlocks);
+    else if (src == Source::tiles) grid = grouped_grid(a.ntiles);
     a.sw.shift = query_shift(c, p->q);
     const bool work = (a.ntiles > 0 || a.n_idx > 0) && c->n_local > 0;
     int rc = work ? ensure_time(c) : AQE_OK;
@@ -649,7 +621,7 @@ int enqueue_bins(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, int column, c
         if (p->host.is_random) a.keys[1] = c->keycol[column - 1];
         nk = 2;
     }
-    rc = ensure_partial(c, static_cast<size_t>(grid) * bins_bytes);
+    rc = c->timeseries->d_partial.grow(c, static_cast<size_t>(grid) * bins_bytes);
     if (rc != AQE_OK) return rc;
     a.partial = c->timeseries->d_partial;
     const bool nt = a.sw.nt != 0;
@@ -733,17 +705,7 @@ int ensure_time(aqe_ctx* c) {
     return AQE_OK;
 }
 
-void timeseries_release(aqe_ctx* c) {
-    aqe_time_scratch* s = c->timeseries;
-    if (!s) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(s->d_partial);
-    (void)hipFree(s->d_bins);
-    if (s->h_groups) (void)hipHostFree(s->h_groups);
-    delete s;
-    c->timeseries = nullptr;
-}
+void timeseries_release(aqe_ctx* c) { release_scratch(c, c->timeseries); }
 
 }  // namespace aqe
 
@@ -833,7 +795,7 @@ int aqe_reduce_time_buckets(aqe_ctx* c, const aqe_key_filter* f, const aqe_query
     rc = prologue(c, f, q, spec, tmin, tmax, &tp, &column, &p);
     if (rc != AQE_OK) return rc;
     if (tp.nbuckets == 0) return fail(c, AQE_ERR_INVALID, "No samples collected");
-    rc = enqueue_bins(c, p, f, column, q, spec, tp, c->timeseries->d_bins, c->timeseries->d_groups, c->stream);
+    rc = enqueue_bins(c, p, f, column, q, spec, tp, c->timeseries->d_bins, c->timeseries->h_groups.dev(), c->stream);
     if (rc != AQE_OK) return rc;
     return collect(c, c->stream, tp.nbuckets, out, cap, n_groups);
 }
@@ -870,7 +832,7 @@ int aqe_time_buckets_finish(aqe_ctx* c, const aqe_query* q, const aqe_time_spec*
     rc = ensure_scratch(c);
     if (rc != AQE_OK) return rc;
     hipStream_t s = stream_of(c, stream);
-    hipLaunchKernelGGL(k_time_finish, dim3((tp.nbuckets + 63) / 64), dim3(64), 0, s, dev_bins, tp.nbuckets, finish_for(c, q, spec, tp), c->timeseries->d_groups);
+    hipLaunchKernelGGL(k_time_finish, dim3((tp.nbuckets + 63) / 64), dim3(64), 0, s, dev_bins, tp.nbuckets, finish_for(c, q, spec, tp), c->timeseries->h_groups.dev());
     HIPCHK(c, hipGetLastError());
     return collect(c, s, tp.nbuckets, out, cap, n_groups);
 }

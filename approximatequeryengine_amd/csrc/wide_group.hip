@@ -569,27 +569,22 @@ uint32_t call_slice() {
 // What the wide grouped entries keep with the context.  Allocated on first use at the size the call needs, grown when a later
 // call needs more, freed with the context.
 struct aqe_wide_scratch {
-    double* d_partial = nullptr;  // [nslices][grid][slice_bins][4]
-    size_t partial_bytes = 0;
-    double* d_bins = nullptr;     // [nbins][4]
-    size_t bins_bytes = 0;
-    aqe_group_result* d_groups = nullptr;  // the compacted list
-    aqe_group_result* h_groups = nullptr;  // its host mirror (pinned)
-    size_t groups_cap = 0;
-    unsigned* d_counts = nullptr;  // [kMaxWideBins / kFinishThreads + 1]: per finishing workgroup, then the number of groups
-    unsigned* h_count = nullptr;   // pinned
-    bool lds_opted = false;        // every instantiation of k_group_wide may take kWideMaxSlice bins of dynamic LDS
+    aqe::DeviceBuf<double> d_partial;  // [nslices][grid][slice_bins][4]
+    aqe::DeviceBuf<double> d_bins;     // [nbins][4]
+    aqe::DeviceBuf<aqe_group_result> d_groups;  // the compacted list
+    aqe::PinnedBuf<aqe_group_result> h_groups;  // its host mirror (pinned)
+    aqe::DeviceBuf<unsigned> d_counts;  // [kMaxWideBins / kFinishThreads + 1]: per finishing workgroup, then the number of groups
+    aqe::PinnedBuf<unsigned> h_count;   // pinned
+    bool lds_opted = false;             // every instantiation of k_group_wide may take kWideMaxSlice bins of dynamic LDS
     // top-N groups (aqe_grouped_top_finish)
-    unsigned long long* d_tkeys = nullptr;  // [nbins] rank keys
-    size_t tkeys_bytes = 0;
-    unsigned* d_tcounts = nullptr;          // [kTopBlocksMax] ranked bins per workgroup of k_top_keys
-    aqe::TopBlock* d_top = nullptr;         // info, the cut, the contenders' counts, the listed groups
-    aqe::TopBlock* h_top = nullptr;         // its host mirror (pinned)
+    aqe::DeviceBuf<unsigned long long> d_tkeys;  // [nbins] rank keys
+    aqe::DeviceBuf<unsigned> d_tcounts;          // [kTopBlocksMax] ranked bins per workgroup of k_top_keys
+    aqe::DeviceBuf<aqe::TopBlock> d_top;         // info, the cut, the contenders' counts, the listed groups
+    aqe::PinnedBuf<aqe::TopBlock> h_top;         // its host mirror (pinned)
     // HAVING (aqe_grouped_having_finish)
-    uint8_t* d_marks = nullptr;             // [nbins] k_having_marks' bytes
-    size_t marks_bytes = 0;
-    aqe::HavingBlock* d_having = nullptr;   // the counters per workgroup, the number listed
-    aqe::HavingBlock* h_having = nullptr;   // its host mirror (pinned)
+    aqe::DeviceBuf<uint8_t> d_marks;             // [nbins] k_having_marks' bytes
+    aqe::DeviceBuf<aqe::HavingBlock> d_having;   // the counters per workgroup, the number listed
+    aqe::PinnedBuf<aqe::HavingBlock> h_having;   // its host mirror (pinned)
 };
 
 namespace aqe {
@@ -597,42 +592,14 @@ namespace {
 
 constexpr Wording kWideWords{"GROUP BY (wide) does not take the ", "GROUP BY (wide) has no grouped refusal of its own"};
 
-template <typename T>
-int grow(aqe_ctx* c, T** p, size_t* have, size_t need) {
-    if (*have >= need) return AQE_OK;
-    if (*p) {
-        HIPCHK(c, hipDeviceSynchronize());  // an earlier sweep (on any stream) may still be using the buffer
-        (void)hipFree(*p);
-    }
-    *p = nullptr;
-    *have = 0;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(p), need));
-    *have = need;
-    return AQE_OK;
-}
-
+// (each member on its own test: a call that failed part way is taken up where it stopped)
 int ensure_scratch(aqe_ctx* c) {
     if (!c->wide) c->wide = new aqe_wide_scratch;  // (wide_release frees whatever part of it exists)
     aqe_wide_scratch* s = c->wide;
-    if (!s->d_counts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_counts), sizeof(unsigned) * (kMaxWideBins / kFinishThreads + 1)));
-    if (!s->h_count) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_count), sizeof(unsigned), hipHostMallocDefault));
-    return AQE_OK;
-}
-
-int ensure_groups(aqe_ctx* c, size_t count) {
-    aqe_wide_scratch* s = c->wide;
-    if (s->groups_cap >= count) return AQE_OK;
-    if (s->d_groups) {
-        HIPCHK(c, hipDeviceSynchronize());
-        (void)hipFree(s->d_groups);
-    }
-    if (s->h_groups) (void)hipHostFree(s->h_groups);
-    s->d_groups = s->h_groups = nullptr;
-    s->groups_cap = 0;
-    HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_groups), sizeof(aqe_group_result) * count));
-    HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_groups), sizeof(aqe_group_result) * count, hipHostMallocDefault));
-    s->groups_cap = count;
-    return AQE_OK;
+    int rc = AQE_OK;
+    if (!s->d_counts) rc = s->d_counts.alloc(c, kMaxWideBins / kFinishThreads + 1);
+    if (rc == AQE_OK && !s->h_count) rc = s->h_count.alloc(c, 1);
+    return rc;
 }
 
 // More than 64 KiB of dynamic LDS needs opting in, once per instantiation; a failure never reaches a launch.
@@ -693,21 +660,9 @@ int enqueue_bins(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, const GroupCo
     WideLaunch a{};
     a.sw = SweepCommon{};
     unsigned cap_x = 1;
-    if (p->host.is_random) {
-        a.sw.amount = c->amount;
-        a.sw.shard_lo = c->shard_lo;
-        a.sw.has_where = p->q.has_where ? 1 : 0;
-        a.sw.wmin = p->q.where_min;
-        a.sw.wmax = p->q.where_max;
-        a.idx = p->d_idx;
-        a.n_idx = a.idx ? p->host.random_idx.size() : 0;
-        cap_x = blocks_for(a.n_idx, static_cast<u64>(kBlockThreads) * kTileUnroll, kGroupedMaxBlocks);
-    } else if (!p->rounds.empty() && c->n_local) {
-        const LaunchDesc& L = p->rounds[0];
-        a.sw = sweep_common(p, p->d_fams + L.fam_offset, L.nfam);
-        a.ntiles = L.nfam ? L.ntiles : 0;
-        cap_x = grouped_grid(a.ntiles);
-    }
+    const Source src = sweep_source(c, p, a);
+    if (src == Source::index_list) cap_x = blocks_for(a.n_idx, static_cast<u64>(kBlockThreads) * kTileUnroll, kGroupedMaxBlocks);
+    else if (src == Source::tiles) cap_x = grouped_grid(a.ntiles);
     a.sw.shift = query_shift(c, p->q);
     if (!((a.ntiles > 0 || a.n_idx > 0) && c->n_local > 0)) {
         HIPCHK(c, hipMemsetAsync(dev_bins, 0, bins_bytes, s));
@@ -730,20 +685,9 @@ int enqueue_bins(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, const GroupCo
             return fail(c, AQE_ERR_INVALID, pair ? "this shard has keys outside [key_min, key_min + span) of a column of the pair"
                                                  : "this shard has keys outside [key_min, key_min + span)");
     }
-    a.flt.t[0] = a.flt.t[1] = pass_all();
-    int nk = pair ? 2 : 1;
-    if (f) {
-        compile_term(f->term[g.col[0] - 1], &a.flt.t[0], a.flt.map[0]);
-        const int other = g.col[0] == AQE_GROUP_REGION ? AQE_GROUP_PRODUCT : AQE_GROUP_REGION;  // (column B of a pair)
-        if (pair) {
-            compile_term(f->term[other - 1], &a.flt.t[1], a.flt.map[1]);
-        } else if (f->term[other - 1].form != AQE_KEYTERM_NONE) {
-            compile_term(f->term[other - 1], &a.flt.t[1], a.flt.map[1]);
-            rc = key_of(other, &a.keys[1]);
-            if (rc != AQE_OK) return rc;
-            nk = 2;
-        }
-    }
+    int nk = 0;
+    rc = bind_group_filter(g, f, key_of, a, &nk);
+    if (rc != AQE_OK) return rc;
     a.key_min = g.kmin[0];
     a.span_a = g.span[0];
     a.key_min_b = pair ? g.kmin[1] : 0;
@@ -760,7 +704,7 @@ int enqueue_bins(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, const GroupCo
     const unsigned grid_x = std::max(1u, std::min(cap_x, want_x));
     const size_t lds_bytes = static_cast<size_t>(sb) * kWideBin * sizeof(double);
     aqe_wide_scratch* sc = c->wide;
-    rc = grow(c, &sc->d_partial, &sc->partial_bytes, static_cast<size_t>(nslices) * grid_x * lds_bytes);
+    rc = sc->d_partial.grow(c, static_cast<size_t>(nslices) * grid_x * lds_bytes);
     if (rc == AQE_OK) rc = ensure_lds(c);
     if (rc != AQE_OK) return rc;
     a.partial = sc->d_partial;
@@ -786,7 +730,7 @@ int finish_groups(aqe_ctx* c, const aqe_query* q, const GroupCols& g, const doub
     aqe_wide_scratch* sc = c->wide;
     const uint32_t nbins = g.nbins();
     const uint32_t room = std::min(cap, nbins);
-    int rc = ensure_groups(c, std::max<size_t>(room, 1));
+    int rc = grow_mirrored(c, sc->d_groups, sc->h_groups, std::max<size_t>(room, 1));
     if (rc != AQE_OK) return rc;
     const unsigned blocks = (nbins + kFinishThreads - 1) / kFinishThreads;
     hipLaunchKernelGGL(k_wide_count, dim3(blocks), dim3(kFinishThreads), 0, s, dev_bins, nbins, sc->d_counts);
@@ -844,7 +788,7 @@ int sweep_whole_table(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, c
     rc = range_ok(c, cols, kmin, span, g, &nslices, slice);
     if (rc != AQE_OK) return rc;
     aqe_wide_scratch* sc = c->wide;
-    rc = grow(c, &sc->d_bins, &sc->bins_bytes, static_cast<size_t>(g->nbins()) * kWideBin * sizeof(double));
+    rc = sc->d_bins.grow(c, static_cast<size_t>(g->nbins()) * kWideBin * sizeof(double));
     if (rc == AQE_OK) rc = enqueue_bins(c, p, f, *g, slice, sc->d_bins, c->stream);
     return rc;
 }
@@ -859,12 +803,11 @@ int top_spec_ok(aqe_ctx* c, const aqe_top_spec* spec) {
 
 int ensure_top(aqe_ctx* c, uint32_t nbins) {
     aqe_wide_scratch* s = c->wide;
-    int rc = grow(c, &s->d_tkeys, &s->tkeys_bytes, (static_cast<size_t>(nbins) + 1) / 2 * 2 * sizeof(u64));  // (whole pairs: k_top_select loads two)
-    if (rc != AQE_OK) return rc;
-    if (!s->d_tcounts) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_tcounts), sizeof(unsigned) * kTopBlocksMax));
-    if (!s->d_top) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_top), sizeof(TopBlock)));
-    if (!s->h_top) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_top), sizeof(TopBlock), hipHostMallocDefault));
-    return AQE_OK;
+    int rc = s->d_tkeys.grow(c, (static_cast<size_t>(nbins) + 1) / 2 * 2 * sizeof(u64));  // (whole pairs: k_top_select loads two)
+    if (rc == AQE_OK && !s->d_tcounts) rc = s->d_tcounts.alloc(c, kTopBlocksMax);
+    if (rc == AQE_OK && !s->d_top) rc = s->d_top.alloc(c, 1);
+    if (rc == AQE_OK && !s->h_top) rc = s->h_top.alloc(c, 1);
+    return rc;
 }
 
 // The rank keys, the selection and the contenders over dev_bins on `s`, then info and the listed groups: one copy of the
@@ -911,11 +854,10 @@ int having_spec_ok(aqe_ctx* c, const aqe_having_spec* h) {
 
 int ensure_having(aqe_ctx* c, uint32_t nbins) {
     aqe_wide_scratch* s = c->wide;
-    int rc = grow(c, &s->d_marks, &s->marks_bytes, nbins);
-    if (rc != AQE_OK) return rc;
-    if (!s->d_having) HIPCHK(c, hipMalloc(reinterpret_cast<void**>(&s->d_having), sizeof(HavingBlock)));
-    if (!s->h_having) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_having), sizeof(HavingBlock), hipHostMallocDefault));
-    return AQE_OK;
+    int rc = s->d_marks.grow(c, nbins);
+    if (rc == AQE_OK && !s->d_having) rc = s->d_having.alloc(c, 1);
+    if (rc == AQE_OK && !s->h_having) rc = s->h_having.alloc(c, 1);
+    return rc;
 }
 
 // The marks over dev_bins on `s`, then either the compaction of the passing groups (top == null: ascending, as finish_groups
@@ -933,7 +875,7 @@ int having_groups(aqe_ctx* c, const aqe_query* q, const GroupCols& g, const doub
     HIPCHK(c, hipGetLastError());
     const uint32_t room = std::min(cap, nbins);
     if (!top) {
-        rc = ensure_groups(c, std::max<size_t>(room, 1));
+        rc = grow_mirrored(c, sc->d_groups, sc->h_groups, std::max<size_t>(room, 1));
         if (rc != AQE_OK) return rc;
         hipLaunchKernelGGL(k_having_finish, dim3(blocks), dim3(kFinishThreads), 0, s, dev_bins, nbins, sc->d_marks, sc->d_having, fin, sc->d_groups, room);
         HIPCHK(c, hipGetLastError());
@@ -974,27 +916,7 @@ int having_groups(aqe_ctx* c, const aqe_query* q, const GroupCols& g, const doub
 
 }  // namespace
 
-void wide_release(aqe_ctx* c) {
-    aqe_wide_scratch* s = c->wide;
-    if (!s) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(s->d_partial);
-    (void)hipFree(s->d_bins);
-    (void)hipFree(s->d_groups);
-    (void)hipFree(s->d_counts);
-    if (s->h_groups) (void)hipHostFree(s->h_groups);
-    if (s->h_count) (void)hipHostFree(s->h_count);
-    (void)hipFree(s->d_tkeys);
-    (void)hipFree(s->d_tcounts);
-    (void)hipFree(s->d_top);
-    if (s->h_top) (void)hipHostFree(s->h_top);
-    (void)hipFree(s->d_marks);
-    (void)hipFree(s->d_having);
-    if (s->h_having) (void)hipHostFree(s->h_having);
-    delete s;
-    c->wide = nullptr;
-}
+void wide_release(aqe_ctx* c) { release_scratch(c, c->wide); }
 
 }  // namespace aqe
 
