@@ -900,21 +900,23 @@ class CustomBPlusDB:
             self.last_top_info = None
         if hspec is not None:
             self.last_having_info = None
-        if self._n == 0:
+        if self._table_missing():
             return {}
         bs = 4096 if (method == "page" and block_size == 1000) else block_size
         q = make_query(m, sample_percent, agg=_AGG[agg.upper()], where=where, block_size=int(bs))
         if hspec is not None:
             f = None if key_where is None else _key_filter_for(key_where, method)
             groups, hinfo, tinfo = _quantile_call(lambda: self._grouped_having(f, q, cols, hspec, k, not ascending, int(max_groups)))
-            self.last_having_info = hinfo.as_dict()
+            if hinfo is not None:  # (None: an empty table behind a sharded backend)
+                self.last_having_info = hinfo.as_dict()
             if tinfo is not None:
                 self.last_top_info = _top_info_dict(tinfo, len(cols) == 2)
             return _pair_groups(groups, GroupEstimate) if len(cols) == 2 else {str(r.key): GroupEstimate(r) for r in groups}
         if k is not None:
             f = None if key_where is None else _key_filter_for(key_where, method)
             groups, info = _quantile_call(lambda: self._grouped_top(f, q, cols, k, not ascending))
-            self.last_top_info = _top_info_dict(info, len(cols) == 2)
+            if info is not None:  # (None: an empty table behind a sharded backend)
+                self.last_top_info = _top_info_dict(info, len(cols) == 2)
             return _pair_groups(groups, GroupEstimate) if len(cols) == 2 else {str(r.key): GroupEstimate(r) for r in groups}
         if wide:
             f = None if key_where is None else _key_filter_for(key_where, method)
@@ -927,7 +929,14 @@ class CustomBPlusDB:
         if key_where is not None:  # a sampled group nothing of which passes is listed with n == 0
             f = _key_filter_for(key_where, method)
             return {str(r.key): GroupEstimate(r) for r in _quantile_call(lambda: self._grouped_filtered(f, q, col))}
-        return {str(r.key): GroupEstimate(r) for r in self._eng().reduce_grouped(q, col)}
+        return {str(r.key): GroupEstimate(r) for r in self._grouped(q, col)}
+
+    def _table_missing(self) -> bool:
+        """No row to group: approx_group_by then answers {} (a backend for which that is an error raises here instead)."""
+        return self._n == 0
+
+    def _grouped(self, q, col):
+        return self._eng().reduce_grouped(q, col)
 
     last_group_error_info: Optional[dict] = None  # of the most recent approx_group_by(error_percent=...)
     last_top_info: Optional[dict] = None  # of the most recent approx_group_by(top=...)

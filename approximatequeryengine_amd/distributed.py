@@ -14,6 +14,7 @@ fetch), which is how the CPU ``gloo`` tests exercise it with an oracle-backed st
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, Optional, Tuple
 
 MOMENT_VEC = 8
@@ -238,6 +239,100 @@ class PipelinedBatches:
         return [r for b in self.batches for r in b.fetch()]
 
 
+# ---- the sharded aggregates: agree, slice, enqueue, merge, finish -----------------------------------------------------------------
+# Every sharded_* function below is those five steps on one stream, and the helpers here are the steps: a new aggregate's sharded
+# form is written with them, not beside them.
+
+@contextlib.contextmanager
+def _on_stream(given: int, tensor):
+    """The block every sharded_* function runs in: resolves the stream handle the caller gave (``_stream_for``), makes it
+    torch's current stream (``_torch_on``) and yields the resolved handle."""
+    stream = _stream_for(given, tensor)
+    with _torch_on(stream, tensor):
+        yield stream
+
+
+def _agree_ranges(ranges, like, all_reduce_max):
+    """ONE all-reduce MAX of the float64 vector [-lo, hi, ...] of this shard's (lo, hi) ``ranges``: the (lo, hi) of the whole table,
+    as floats, the same on every rank.  ``like``: a tensor on the device the collective runs on."""
+    rng = like.new_tensor([v for lo, hi in ranges for v in (-float(lo), float(hi))])
+    all_reduce_max(rng)
+    r = rng.tolist()
+    return [(-lo, hi) for lo, hi in zip(r[0::2], r[1::2])]
+
+
+def _agree_keys(engine, cols, like, all_reduce_max):
+    """The key ranges of the columns ``cols`` over all ranks, in ONE all-reduce MAX: (key_min, key_max), a list per side with one
+    entry per column, or None for an empty table."""
+    agreed = _agree_ranges([engine.group_key_range(c) for c in cols], like, all_reduce_max)
+    kmin, kmax = [int(lo) for lo, _ in agreed], [int(hi) for _, hi in agreed]
+    return None if any(hi < lo for lo, hi in zip(kmin, kmax)) else (kmin, kmax)
+
+
+def _agree_int64(ranges, like, all_reduce_max):
+    """_agree_ranges for values a double cannot hold (timestamps): ONE all-reduce MAX of the int64 vector [~lo, hi, ...] (~v = -v - 1
+    reverses the order without overflowing), as ints."""
+    import torch
+    rng = torch.tensor([v for lo, hi in ranges for v in (~int(lo), int(hi))], dtype=torch.int64, device=like.device)
+    all_reduce_max(rng)
+    r = [int(v) for v in rng.tolist()]
+    return [(~lo, hi) for lo, hi in zip(r[0::2], r[1::2])]
+
+
+def _take(buf, need: int, vector: bool = False):
+    """The first ``need`` doubles of the caller's buffer; ValueError when it holds fewer."""
+    if buf.numel() < need:
+        raise ValueError(f"vector holds {buf.numel()} doubles, {need} needed" if vector else f"bin buffer holds {buf.numel()} doubles, {need} needed")
+    return buf[:need]
+
+
+def _agree_bins_1024(engine, cols, like, all_reduce_max):
+    """_agree_keys for the binned sweeps that hold at most 1024 bins: (key_min, span, nbins), or None for an empty table; more bins
+    are refused here, on every rank alike, before the sweep."""
+    from ._native import ERR_UNSUPPORTED, AqeError
+    agreed = _agree_keys(engine, cols, like, all_reduce_max)
+    if agreed is None:
+        return None
+    span = [hi - lo + 1 for lo, hi in zip(*agreed)]
+    nbins = span[0] * (span[1] if len(span) == 2 else 1)
+    if nbins > 1024:
+        if len(span) == 2:
+            raise AqeError(ERR_UNSUPPORTED, f"GROUP BY over both key columns: the columns span {span[0]} x {span[1]} keys, more than 1024 bins")
+        raise AqeError(ERR_UNSUPPORTED, "group column spans more than 1024 distinct values")
+    return agreed[0], span, nbins
+
+
+def _sum_then_max(v, k: int, all_reduce_sum, all_reduce_max):
+    """The merge of a vector whose first ``k`` words add up and whose others are maxima: ONE all-reduce SUM, ONE all-reduce MAX."""
+    all_reduce_sum(v[:k])
+    all_reduce_max(v[k:])
+
+
+def _swept_vector(vec, need: int, all_reduce_sum, stream, enqueue, finish):
+    """sharded_spread's and sharded_filtered's body: ``need`` doubles swept by enqueue(ptr, stream), ONE all-reduce SUM,
+    finish(ptr, stream)."""
+    with _on_stream(stream, vec) as stream:
+        v = _take(vec, need, vector=True)
+        enqueue(v.data_ptr(), stream)
+        all_reduce_sum(v)
+        return finish(v.data_ptr(), stream)
+
+
+def _grouped_one(engine, group_column, bins, width: int, all_reduce_sum, all_reduce_max, stream, enqueue, finish):
+    """The body of the three GROUP BYs over one column: the key range agreed, nbins x ``width`` doubles binned by
+    enqueue(key_min, nbins, ptr, stream), ONE all-reduce SUM, finish(key_min, nbins, ptr, stream).  (No refusal here: the entries
+    judge the span themselves.)"""
+    with _on_stream(stream, bins) as stream:
+        agreed = _agree_keys(engine, [group_column], bins, all_reduce_max)
+        if agreed is None:
+            return []  # an empty table
+        kmin, nbins = agreed[0][0], agreed[1][0] - agreed[0][0] + 1
+        b = _take(bins, width * nbins)
+        enqueue(kmin, nbins, b.data_ptr(), stream)
+        all_reduce_sum(b)
+        return finish(kmin, nbins, b.data_ptr(), stream)
+
+
 def sharded_group_by(engine, query, group_column: int, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0):
     """GROUP BY across the ranks of a process group (engine.Engine interface): the per-key bins (n, S - c n, Q,
     visited) are additive, so every rank bins the part of the sample inside its shard over the same key range and
@@ -248,25 +343,8 @@ def sharded_group_by(engine, query, group_column: int, bins, all_reduce_sum: Cal
     stream          raw handle of the stream the collectives are issued on; 0 = torch's current stream (run under
                     ``with torch.cuda.stream(side)``: the legacy default stream is refused, see ``_stream_for``).
     """
-    stream = _stream_for(stream, bins)
-    with _torch_on(stream, bins):
-        return _sharded_group_by(engine, query, group_column, bins, all_reduce_sum, all_reduce_max, stream)
-
-
-def _sharded_group_by(engine, query, group_column, bins, all_reduce_sum, all_reduce_max, stream):
-    lo, hi = engine.group_key_range(group_column)
-    rng = bins.new_tensor([-float(lo), float(hi)])
-    all_reduce_max(rng)
-    kmin, kmax = -int(rng[0].item()), int(rng[1].item())
-    if kmax < kmin:
-        return []  # an empty table
-    nbins = kmax - kmin + 1
-    if bins.numel() < 4 * nbins:
-        raise ValueError(f"bin buffer holds {bins.numel()} doubles, {4 * nbins} needed")
-    b = bins[: 4 * nbins]
-    engine.grouped_enqueue_bins(query, group_column, kmin, nbins, b.data_ptr(), stream)
-    all_reduce_sum(b)
-    return engine.grouped_finish(query, kmin, nbins, b.data_ptr(), stream)
+    return _grouped_one(engine, group_column, bins, 4, all_reduce_sum, all_reduce_max, stream,
+                        lambda *a: engine.grouped_enqueue_bins(query, group_column, *a), lambda *a: engine.grouped_finish(query, *a))
 
 
 def sharded_quantiles(engine, query, probs, interpolation: int, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0):
@@ -277,33 +355,24 @@ def sharded_quantiles(engine, query, probs, interpolation: int, vec, all_reduce_
 
     vec     float64 tensor on the engine's device with room for QUANTILE_VEC_SUM + QUANTILE_VEC_MAX doubles
     stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
-    stream = _stream_for(stream, vec)
-    with _torch_on(stream, vec):
-        return _sharded_quantiles(engine, query, probs, interpolation, vec, all_reduce_sum, all_reduce_max, stream)
-
-
-def _sharded_quantiles(engine, query, probs, interpolation, vec, all_reduce_sum, all_reduce_max, stream):
     from ._native import QUANTILE_VEC_MAX, QUANTILE_VEC_SUM
-    lo, hi = engine.quantile_amount_range()
-    rng = vec.new_tensor([-float(lo), float(hi)])
-    all_reduce_max(rng)
-    amin, amax = -float(rng[0].item()), float(rng[1].item())
-    need = QUANTILE_VEC_SUM + QUANTILE_VEC_MAX
-    if vec.numel() < need:
-        raise ValueError(f"pass vector holds {vec.numel()} doubles, {need} needed")
-    v = vec[:need]
-    run = engine.quantile_begin(query, probs, interpolation, amin, amax, stream)
-    try:
-        while True:
-            run.enqueue_pass(v.data_ptr(), stream)
-            all_reduce_sum(v[:QUANTILE_VEC_SUM])
-            all_reduce_max(v[QUANTILE_VEC_SUM:])
-            run.enqueue_fold(v.data_ptr(), stream)
-            if run.done():  # (the same state on every rank: every rank leaves after the same pass)
-                break
-        return run.finish(stream)
-    finally:
-        run.close()
+    with _on_stream(stream, vec) as stream:
+        (amin, amax), = _agree_ranges([engine.quantile_amount_range()], vec, all_reduce_max)
+        need = QUANTILE_VEC_SUM + QUANTILE_VEC_MAX
+        if vec.numel() < need:
+            raise ValueError(f"pass vector holds {vec.numel()} doubles, {need} needed")
+        v = vec[:need]
+        run = engine.quantile_begin(query, probs, interpolation, amin, amax, stream)
+        try:
+            while True:
+                run.enqueue_pass(v.data_ptr(), stream)
+                _sum_then_max(v, QUANTILE_VEC_SUM, all_reduce_sum, all_reduce_max)
+                run.enqueue_fold(v.data_ptr(), stream)
+                if run.done():  # (the same state on every rank: every rank leaves after the same pass)
+                    break
+            return run.finish(stream)
+        finally:
+            run.close()
 
 
 def sharded_spread(engine, query, kind: int, vec, all_reduce_sum: Callable, stream: int = 0):
@@ -314,14 +383,8 @@ def sharded_spread(engine, query, kind: int, vec, all_reduce_sum: Callable, stre
     vec     float64 tensor on the engine's device with room for SPREAD_VEC doubles
     stream  raw handle of the stream the collective is issued on; 0 = torch's current stream (see ``_stream_for``)."""
     from ._native import SPREAD_VEC
-    stream = _stream_for(stream, vec)
-    if vec.numel() < SPREAD_VEC:
-        raise ValueError(f"vector holds {vec.numel()} doubles, {SPREAD_VEC} needed")
-    with _torch_on(stream, vec):
-        v = vec[:SPREAD_VEC]
-        engine.spread_enqueue(query, v.data_ptr(), stream)
-        all_reduce_sum(v)
-        return engine.spread_finish(query, kind, v.data_ptr(), stream)
+    return _swept_vector(vec, SPREAD_VEC, all_reduce_sum, stream,
+                         lambda *a: engine.spread_enqueue(query, *a), lambda *a: engine.spread_finish(query, kind, *a))
 
 
 def sharded_group_by_spread(engine, query, kind: int, group_column: int, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0):
@@ -330,21 +393,9 @@ def sharded_group_by_spread(engine, query, kind: int, group_column: int, bins, a
 
     bins    float64 tensor on the engine's device with room for SPREAD_BIN * (number of distinct keys) doubles"""
     from ._native import SPREAD_BIN
-    stream = _stream_for(stream, bins)
-    with _torch_on(stream, bins):
-        lo, hi = engine.group_key_range(group_column)
-        rng = bins.new_tensor([-float(lo), float(hi)])
-        all_reduce_max(rng)
-        kmin, kmax = -int(rng[0].item()), int(rng[1].item())
-        if kmax < kmin:
-            return []  # an empty table
-        nbins = kmax - kmin + 1
-        if bins.numel() < SPREAD_BIN * nbins:
-            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {SPREAD_BIN * nbins} needed")
-        b = bins[: SPREAD_BIN * nbins]
-        engine.grouped_spread_enqueue_bins(query, group_column, kmin, nbins, b.data_ptr(), stream)
-        all_reduce_sum(b)
-        return engine.grouped_spread_finish(query, kind, kmin, nbins, b.data_ptr(), stream)
+    return _grouped_one(engine, group_column, bins, SPREAD_BIN, all_reduce_sum, all_reduce_max, stream,
+                        lambda *a: engine.grouped_spread_enqueue_bins(query, group_column, *a),
+                        lambda *a: engine.grouped_spread_finish(query, kind, *a))
 
 
 def sharded_filtered(engine, key_filter, query, vec, all_reduce_sum: Callable, stream: int = 0, kind=None):
@@ -355,16 +406,11 @@ def sharded_filtered(engine, key_filter, query, vec, all_reduce_sum: Callable, s
     vec     float64 tensor on the engine's device with room for SPREAD_VEC doubles
     stream  raw handle of the stream the collective is issued on; 0 = torch's current stream (see ``_stream_for``)."""
     from ._native import SPREAD_VEC
-    stream = _stream_for(stream, vec)
-    if vec.numel() < SPREAD_VEC:
-        raise ValueError(f"vector holds {vec.numel()} doubles, {SPREAD_VEC} needed")
-    with _torch_on(stream, vec):
-        v = vec[:SPREAD_VEC]
-        engine.filtered_enqueue(key_filter, query, v.data_ptr(), stream)
-        all_reduce_sum(v)
-        if kind is None:
-            return engine.filtered_finish(query, v.data_ptr(), stream)
-        return engine.filtered_spread_finish(query, kind, v.data_ptr(), stream)
+    if kind is None:
+        finish = lambda *a: engine.filtered_finish(query, *a)
+    else:
+        finish = lambda *a: engine.filtered_spread_finish(query, kind, *a)
+    return _swept_vector(vec, SPREAD_VEC, all_reduce_sum, stream, lambda *a: engine.filtered_enqueue(key_filter, query, *a), finish)
 
 
 def sharded_filtered_group_by(engine, key_filter, query, group_column: int, bins, all_reduce_sum: Callable, all_reduce_max: Callable,
@@ -375,23 +421,12 @@ def sharded_filtered_group_by(engine, key_filter, query, group_column: int, bins
 
     bins    float64 tensor on the engine's device with room for SPREAD_BIN * (number of distinct keys) doubles"""
     from ._native import SPREAD_BIN
-    stream = _stream_for(stream, bins)
-    with _torch_on(stream, bins):
-        lo, hi = engine.group_key_range(group_column)
-        rng = bins.new_tensor([-float(lo), float(hi)])
-        all_reduce_max(rng)
-        kmin, kmax = -int(rng[0].item()), int(rng[1].item())
-        if kmax < kmin:
-            return []  # an empty table
-        nbins = kmax - kmin + 1
-        if bins.numel() < SPREAD_BIN * nbins:
-            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {SPREAD_BIN * nbins} needed")
-        b = bins[: SPREAD_BIN * nbins]
-        engine.filtered_grouped_enqueue_bins(key_filter, query, group_column, kmin, nbins, b.data_ptr(), stream)
-        all_reduce_sum(b)
-        if kind is None:
-            return engine.filtered_grouped_finish(query, kmin, nbins, b.data_ptr(), stream)
-        return engine.grouped_spread_finish(query, kind, kmin, nbins, b.data_ptr(), stream)
+    if kind is None:
+        finish = lambda *a: engine.filtered_grouped_finish(query, *a)
+    else:
+        finish = lambda *a: engine.grouped_spread_finish(query, kind, *a)
+    return _grouped_one(engine, group_column, bins, SPREAD_BIN, all_reduce_sum, all_reduce_max, stream,
+                        lambda *a: engine.filtered_grouped_enqueue_bins(key_filter, query, group_column, *a), finish)
 
 
 def sharded_group_by_pair(engine, query, columns, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None,
@@ -403,24 +438,14 @@ def sharded_group_by_pair(engine, query, columns, bins, all_reduce_sum: Callable
     returns the same bits.  More than 1024 bins is refused on every rank alike, before the sweep.
 
     bins    float64 tensor on the engine's device with room for SPREAD_BIN * spanA * spanB doubles (at most SPREAD_BIN * 1024)"""
-    from ._native import ERR_UNSUPPORTED, SPREAD_BIN, AqeError
-    stream = _stream_for(stream, bins)
+    from ._native import SPREAD_BIN
     cols = [int(c) for c in columns]
-    with _torch_on(stream, bins):
-        (lo_a, hi_a), (lo_b, hi_b) = engine.group_key_range(cols[0]), engine.group_key_range(cols[1])
-        rng = bins.new_tensor([-float(lo_a), float(hi_a), -float(lo_b), float(hi_b)])
-        all_reduce_max(rng)
-        r = [int(v) for v in rng.tolist()]
-        kmin, kmax = (-r[0], -r[2]), (r[1], r[3])
-        if kmax[0] < kmin[0] or kmax[1] < kmin[1]:
+    with _on_stream(stream, bins) as stream:
+        agreed = _agree_bins_1024(engine, cols, bins, all_reduce_max)
+        if agreed is None:
             return []  # an empty table
-        span = (kmax[0] - kmin[0] + 1, kmax[1] - kmin[1] + 1)
-        nbins = span[0] * span[1]
-        if nbins > 1024:
-            raise AqeError(ERR_UNSUPPORTED, f"GROUP BY over both key columns: the columns span {span[0]} x {span[1]} keys, more than 1024 bins")
-        if bins.numel() < SPREAD_BIN * nbins:
-            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {SPREAD_BIN * nbins} needed")
-        b = bins[: SPREAD_BIN * nbins]
+        kmin, span, nbins = agreed
+        b = _take(bins, SPREAD_BIN * nbins)
         engine.grouped_pair_enqueue_bins(query, cols, kmin, span, b.data_ptr(), stream, key_filter)
         all_reduce_sum(b)
         if kind is None:
@@ -436,18 +461,12 @@ def _wide_swept_bins(engine, query, columns, bins, all_reduce_sum, all_reduce_ma
     from ._native import WIDE_BIN
     from .engine import wide_plan
     cols = [int(c) for c in columns]
-    ranges = [engine.group_key_range(c) for c in cols]
-    rng = bins.new_tensor([v for lo, hi in ranges for v in (-float(lo), float(hi))])
-    all_reduce_max(rng)
-    r = [int(v) for v in rng.tolist()]
-    kmin, kmax = [-v for v in r[0::2]], r[1::2]
-    if any(hi < lo for lo, hi in zip(kmin, kmax)):
+    agreed = _agree_keys(engine, cols, bins, all_reduce_max)
+    if agreed is None:
         return None
-    span = [hi - lo + 1 for lo, hi in zip(kmin, kmax)]
-    nbins = wide_plan(span)[0]
-    if bins.numel() < WIDE_BIN * nbins:
-        raise ValueError(f"bin buffer holds {bins.numel()} doubles, {WIDE_BIN * nbins} needed")
-    b = bins[: WIDE_BIN * nbins]
+    kmin = agreed[0]
+    span = [hi - lo + 1 for lo, hi in zip(*agreed)]
+    b = _take(bins, WIDE_BIN * wide_plan(span)[0])
     engine.grouped_wide_enqueue_bins(query, cols, kmin, span, b.data_ptr(), stream, key_filter)
     all_reduce_sum(b)
     return kmin, span, b
@@ -464,8 +483,7 @@ def sharded_group_by_wide(engine, query, columns, bins, all_reduce_sum: Callable
 
     bins    float64 tensor on the engine's device with room for WIDE_BIN * nbins doubles (at most WIDE_BIN * 65 536)
     stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
-    stream = _stream_for(stream, bins)
-    with _torch_on(stream, bins):
+    with _on_stream(stream, bins) as stream:
         agreed = _wide_swept_bins(engine, query, columns, bins, all_reduce_sum, all_reduce_max, stream, key_filter)
         if agreed is None:
             return []  # an empty table
@@ -480,8 +498,7 @@ def sharded_group_by_top(engine, query, columns, bins, all_reduce_sum: Callable,
     ONE all-reduce SUM — then every rank selects the k best groups from the same bins on its device (aqe_grouped_top_finish):
     an integer selection, so every rank returns the same (list of GroupResult in rank order, TopInfo), bit for bit.  An empty
     table gives ([], None).  ``bins`` and ``stream`` as sharded_group_by_wide takes them."""
-    stream = _stream_for(stream, bins)
-    with _torch_on(stream, bins):
+    with _on_stream(stream, bins) as stream:
         agreed = _wide_swept_bins(engine, query, columns, bins, all_reduce_sum, all_reduce_max, stream, key_filter)
         if agreed is None:
             return [], None  # an empty table
@@ -496,8 +513,7 @@ def sharded_group_by_having(engine, query, columns, bins, all_reduce_sum: Callab
     on its device (aqe_grouped_having_finish; with ``k`` the k best passing groups): integer decisions over identical bins, so
     every rank returns the same (list of GroupResult, HavingInfo, TopInfo or None), bit for bit.  An empty table gives
     ([], None, None).  ``having`` as Engine.reduce_grouped_having takes it; ``bins`` and ``stream`` as sharded_group_by_wide."""
-    stream = _stream_for(stream, bins)
-    with _torch_on(stream, bins):
+    with _on_stream(stream, bins) as stream:
         agreed = _wide_swept_bins(engine, query, columns, bins, all_reduce_sum, all_reduce_max, stream, key_filter)
         if agreed is None:
             return [], None, None  # an empty table
@@ -514,14 +530,10 @@ def sharded_extremes(engine, query, vec, all_reduce_sum: Callable, all_reduce_ma
     vec     float64 tensor on the engine's device with room for EXTREME_VEC doubles
     stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
     from ._native import EXTREME_VEC
-    stream = _stream_for(stream, vec)
-    if vec.numel() < EXTREME_VEC:
-        raise ValueError(f"vector holds {vec.numel()} doubles, {EXTREME_VEC} needed")
-    with _torch_on(stream, vec):
-        v = vec[:EXTREME_VEC]
+    with _on_stream(stream, vec) as stream:
+        v = _take(vec, EXTREME_VEC, vector=True)
         engine.extremes_enqueue(query, v.data_ptr(), stream, key_filter)
-        all_reduce_sum(v[:2])
-        all_reduce_max(v[2:])
+        _sum_then_max(v, 2, all_reduce_sum, all_reduce_max)
         return engine.extremes_finish(query, v.data_ptr(), stream)
 
 
@@ -535,14 +547,10 @@ def sharded_summary(engine, query, vec, all_reduce_sum: Callable, all_reduce_max
     vec     float64 tensor on the engine's device with room for SUMMARY_VEC doubles
     stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
     from ._native import SUMMARY_VEC, SUMMARY_VEC_SUM
-    stream = _stream_for(stream, vec)
-    if vec.numel() < SUMMARY_VEC:
-        raise ValueError(f"vector holds {vec.numel()} doubles, {SUMMARY_VEC} needed")
-    with _torch_on(stream, vec):
-        v = vec[:SUMMARY_VEC]
+    with _on_stream(stream, vec) as stream:
+        v = _take(vec, SUMMARY_VEC, vector=True)
         engine.summary_enqueue(query, v.data_ptr(), stream, key_filter)
-        all_reduce_sum(v[:SUMMARY_VEC_SUM])
-        all_reduce_max(v[SUMMARY_VEC_SUM:])
+        _sum_then_max(v, SUMMARY_VEC_SUM, all_reduce_sum, all_reduce_max)
         return engine.summary_finish(query, v.data_ptr(), stream)
 
 
@@ -557,21 +565,14 @@ def sharded_time_series(engine, query, spec, bins, all_reduce_sum: Callable, all
 
     bins    float64 tensor on the engine's device with room for TIME_BIN * nbuckets doubles (at most TIME_BIN * 1024)
     stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
-    import torch
     from ._native import ERR_INVALID, TIME_BIN, AqeError
     from .engine import time_plan
-    stream = _stream_for(stream, bins)
-    with _torch_on(stream, bins):
-        lo, hi = engine.time_range()
-        rng = torch.tensor([~int(lo), int(hi)], dtype=torch.int64, device=bins.device)
-        all_reduce_max(rng)
-        tmin, tmax = ~int(rng[0].item()), int(rng[1].item())
+    with _on_stream(stream, bins) as stream:
+        (tmin, tmax), = _agree_int64([engine.time_range()], bins, all_reduce_max)
         nbuckets = time_plan(spec, tmin, tmax)[1]
         if nbuckets == 0:  # an empty table, or a window that holds none of its timestamps
             raise AqeError(ERR_INVALID, "No samples collected")
-        if bins.numel() < TIME_BIN * nbuckets:
-            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {TIME_BIN * nbuckets} needed")
-        b = bins[: TIME_BIN * nbuckets]
+        b = _take(bins, TIME_BIN * nbuckets)
         engine.time_buckets_enqueue_bins(query, spec, tmin, tmax, b.data_ptr(), stream, key_filter)
         all_reduce_sum(b)
         return engine.time_buckets_finish(query, spec, tmin, tmax, b.data_ptr(), stream)
@@ -590,24 +591,15 @@ def sharded_time_groups(engine, query, group_column, spec, bins, all_reduce_sum:
 
     bins    float64 tensor on the engine's device with room for SERIES_BIN * nbins doubles (at most SERIES_BIN * 65 536)
     stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
-    import torch
     from ._native import ERR_INVALID, SERIES_BIN, AqeError
     from .engine import time_group_plan
-    stream = _stream_for(stream, bins)
-    with _torch_on(stream, bins):
-        lo, hi = engine.time_range()
-        klo, khi = engine.group_key_range(int(group_column))
-        rng = torch.tensor([~int(lo), int(hi), ~int(klo), int(khi)], dtype=torch.int64, device=bins.device)
-        all_reduce_max(rng)
-        r = [int(v) for v in rng.tolist()]
-        tmin, tmax, kmin, kmax = ~r[0], r[1], ~r[2], r[3]
+    with _on_stream(stream, bins) as stream:
+        (tmin, tmax), (kmin, kmax) = _agree_int64([engine.time_range(), engine.group_key_range(int(group_column))], bins, all_reduce_max)
         nbins = time_group_plan(spec, tmin, tmax, kmin, kmax)[2]
         if nbins == 0:  # an empty table, or a window that holds none of its timestamps
             raise AqeError(ERR_INVALID, "No samples collected")
-        if bins.numel() < SERIES_BIN * nbins:
-            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {SERIES_BIN * nbins} needed")
+        b = _take(bins, SERIES_BIN * nbins)
         span = kmax - kmin + 1
-        b = bins[: SERIES_BIN * nbins]
         engine.time_groups_enqueue_bins(query, group_column, spec, tmin, tmax, kmin, span, b.data_ptr(), stream, key_filter)
         all_reduce_sum(b)
         return engine.time_groups_finish(query, group_column, spec, tmin, tmax, kmin, span, b.data_ptr(), stream, max_groups)
@@ -623,25 +615,18 @@ def sharded_histogram(engine, query, spec, vec, all_reduce_sum: Callable, all_re
     vec     float64 tensor on the engine's device with room for HISTOGRAM_VEC_HEAD + spec.bins doubles
     stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
     from ._native import ERR_INVALID, HISTOGRAM_MAX_BINS, HISTOGRAM_VEC_HEAD, AqeError, HistogramSpec
-    stream = _stream_for(stream, vec)
-    bins = int(spec.bins)
-    if not 1 <= bins <= HISTOGRAM_MAX_BINS:
-        raise AqeError(ERR_INVALID, "HISTOGRAM: the number of buckets must lie in 1 .. 4096")
-    need = HISTOGRAM_VEC_HEAD + bins
-    if vec.numel() < need:
-        raise ValueError(f"vector holds {vec.numel()} doubles, {need} needed")
-    with _torch_on(stream, vec):
+    with _on_stream(stream, vec) as stream:
+        bins = int(spec.bins)
+        if not 1 <= bins <= HISTOGRAM_MAX_BINS:
+            raise AqeError(ERR_INVALID, "HISTOGRAM: the number of buckets must lie in 1 .. 4096")
+        v = _take(vec, HISTOGRAM_VEC_HEAD + bins, vector=True)
         if not spec.has_range:
-            lo, hi = engine.quantile_amount_range()
-            rng = vec.new_tensor([-float(lo), float(hi)])
-            all_reduce_max(rng)
-            lo, hi = -float(rng[0].item()), float(rng[1].item())
+            (lo, hi), = _agree_ranges([engine.quantile_amount_range()], vec, all_reduce_max)
             if query.has_where:
                 lo, hi = max(lo, float(query.where_min)), min(hi, float(query.where_max))
             if not (lo < hi and hi - lo < float("inf") and lo > float("-inf")):
                 raise AqeError(ERR_INVALID, "HISTOGRAM: the table's amounts leave no finite range with lo < hi (a constant or empty column): give a range")
             spec = HistogramSpec(lo, hi, bins, 1)
-        v = vec[:need]
         engine.histogram_enqueue(query, spec, v.data_ptr(), stream, key_filter)
         all_reduce_sum(v)
         return engine.histogram_finish(query, spec, v.data_ptr(), stream)
@@ -659,22 +644,15 @@ def sharded_distinct(engine, query, column: int, vec, all_reduce_sum: Callable, 
     stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
     from ._native import DISTINCT_AMOUNT, DISTINCT_SKETCH, DISTINCT_SLOTS, DISTINCT_VEC_HEAD
     from .engine import distinct_mode
-    stream = _stream_for(stream, vec)
-    need = DISTINCT_VEC_HEAD + DISTINCT_SLOTS
-    if vec.numel() < need:
-        raise ValueError(f"vector holds {vec.numel()} doubles, {need} needed")
-    column = int(column)
-    with _torch_on(stream, vec):
+    with _on_stream(stream, vec) as stream:
+        v = _take(vec, DISTINCT_VEC_HEAD + DISTINCT_SLOTS, vector=True)
+        column = int(column)
         mode, kmin = DISTINCT_SKETCH, 0
-        if column != DISTINCT_AMOUNT:
-            lo, hi = engine.group_key_range(column)
-            rng = vec.new_tensor([-float(lo), float(hi)])
-            all_reduce_max(rng)
-            mode, kmin = distinct_mode(column, -int(rng[0].item()), int(rng[1].item()))
-        v = vec[:need]
+        if column != DISTINCT_AMOUNT:  # (an empty range is distinct_mode's to judge, not an early return: _agree_ranges, not _agree_keys)
+            (lo, hi), = _agree_ranges([engine.group_key_range(column)], vec, all_reduce_max)
+            mode, kmin = distinct_mode(column, int(lo), int(hi))
         engine.distinct_enqueue(query, column, mode, kmin, v.data_ptr(), stream, key_filter)
-        all_reduce_sum(v[:DISTINCT_VEC_HEAD])
-        all_reduce_max(v[DISTINCT_VEC_HEAD:])
+        _sum_then_max(v, DISTINCT_VEC_HEAD, all_reduce_sum, all_reduce_max)
         return engine.distinct_finish(query, column, mode, kmin, v.data_ptr(), stream)
 
 
@@ -686,32 +664,15 @@ def sharded_group_extremes(engine, query, columns, bins, all_reduce_sum: Callabl
     alike, before the sweep.
 
     bins    float64 tensor on the engine's device with room for 4 * (number of bins) doubles (at most 4 * 1024)"""
-    from ._native import ERR_UNSUPPORTED, AqeError
-    stream = _stream_for(stream, bins)
     cols = [int(c) for c in columns]
-    with _torch_on(stream, bins):
-        flat = []
-        for col in cols:
-            lo, hi = engine.group_key_range(col)
-            flat += [-float(lo), float(hi)]
-        rng = bins.new_tensor(flat)
-        all_reduce_max(rng)
-        r = [int(v) for v in rng.tolist()]
-        kmin, kmax = [-r[2 * i] for i in range(len(cols))], [r[2 * i + 1] for i in range(len(cols))]
-        if any(hi < lo for lo, hi in zip(kmin, kmax)):
+    with _on_stream(stream, bins) as stream:
+        agreed = _agree_bins_1024(engine, cols, bins, all_reduce_max)
+        if agreed is None:
             return []  # an empty table
-        span = [hi - lo + 1 for lo, hi in zip(kmin, kmax)]
-        nbins = span[0] * (span[1] if len(cols) == 2 else 1)
-        if nbins > 1024:
-            if len(cols) == 2:
-                raise AqeError(ERR_UNSUPPORTED, f"GROUP BY over both key columns: the columns span {span[0]} x {span[1]} keys, more than 1024 bins")
-            raise AqeError(ERR_UNSUPPORTED, "group column spans more than 1024 distinct values")
-        if bins.numel() < 4 * nbins:
-            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {4 * nbins} needed")
-        b = bins[: 4 * nbins]
+        kmin, span, nbins = agreed
+        b = _take(bins, 4 * nbins)
         engine.grouped_extremes_enqueue_bins(query, cols, kmin, span, b.data_ptr(), stream, key_filter)
-        all_reduce_sum(b[: 2 * nbins])
-        all_reduce_max(b[2 * nbins:])
+        _sum_then_max(b, 2 * nbins, all_reduce_sum, all_reduce_max)
         return engine.grouped_extremes_finish(query, cols, kmin, span, b.data_ptr(), stream)
 
 
@@ -724,29 +685,14 @@ def sharded_group_by_error(engine, query, columns, error_percent: float, max_per
     stop word is read once per level.  Returns (groups, GroupErrorInfo).
 
     bins    float64 tensor on the engine's device with room for SPREAD_BIN * (number of bins) doubles (at most SPREAD_BIN * 1024)"""
-    from ._native import ERR_UNSUPPORTED, SPREAD_BIN, AqeError, GroupErrorInfo
-    stream = _stream_for(stream, bins)
+    from ._native import SPREAD_BIN, GroupErrorInfo
     cols = [int(c) for c in columns]
-    with _torch_on(stream, bins):
-        flat = []
-        for col in cols:
-            lo, hi = engine.group_key_range(col)
-            flat += [-float(lo), float(hi)]
-        rng = bins.new_tensor(flat)
-        all_reduce_max(rng)
-        r = [int(v) for v in rng.tolist()]
-        kmin, kmax = [-r[2 * i] for i in range(len(cols))], [r[2 * i + 1] for i in range(len(cols))]
-        if any(hi < lo for lo, hi in zip(kmin, kmax)):
+    with _on_stream(stream, bins) as stream:
+        agreed = _agree_bins_1024(engine, cols, bins, all_reduce_max)
+        if agreed is None:
             return [], GroupErrorInfo()  # an empty table
-        span = [hi - lo + 1 for lo, hi in zip(kmin, kmax)]
-        nbins = span[0] * (span[1] if len(cols) == 2 else 1)
-        if nbins > 1024:
-            if len(cols) == 2:
-                raise AqeError(ERR_UNSUPPORTED, f"GROUP BY over both key columns: the columns span {span[0]} x {span[1]} keys, more than 1024 bins")
-            raise AqeError(ERR_UNSUPPORTED, "group column spans more than 1024 distinct values")
-        if bins.numel() < SPREAD_BIN * nbins:
-            raise ValueError(f"bin buffer holds {bins.numel()} doubles, {SPREAD_BIN * nbins} needed")
-        b = bins[: SPREAD_BIN * nbins]
+        kmin, span, nbins = agreed
+        b = _take(bins, SPREAD_BIN * nbins)
         levels = engine.grouped_error_begin(query, cols, kmin, span, error_percent, max_percent, stream, key_filter)
         for level in range(levels):
             engine.grouped_error_enqueue_round(level, b.data_ptr(), stream)

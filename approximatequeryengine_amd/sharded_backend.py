@@ -23,21 +23,36 @@ import os
 from typing import List, Optional
 
 import numpy as np
+import torch
+import torch.distributed as dist
 
 from . import _native as nat
-from .aqe_backend import ApproxResult, CustomBPlusDB, GroupEstimate, _AGG, _LEFT_OUT, _having_arg, _key_filter_for, _pair_groups, _quantile_call, _top_arg, _top_info_dict, _wide_groups_arg, group_columns
-from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, shard_bounds, sharded_adaptive_plan, sharded_group_by, sharded_filtered, sharded_filtered_group_by, sharded_group_by_pair, sharded_group_by_spread, sharded_quantiles, sharded_spread,
-                          sharded_stratified_plan, torch_all_reduce, torch_host_all_reduce)
-from .engine import RECORD_DTYPE, Batch, Engine, make_query
+from .aqe_backend import ApproxResult, CustomBPlusDB
+from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, mailbox_all_reduce, mailbox_from_torch_group, shard_bounds, sharded_adaptive_plan,
+                          sharded_distinct, sharded_extremes, sharded_filtered, sharded_filtered_group_by, sharded_group_by, sharded_group_by_error,
+                          sharded_group_by_having, sharded_group_by_pair, sharded_group_by_spread, sharded_group_by_top, sharded_group_by_wide,
+                          sharded_group_extremes, sharded_histogram, sharded_quantiles, sharded_spread, sharded_stratified_plan, sharded_summary,
+                          sharded_time_groups, sharded_time_series, torch_all_reduce, torch_host_all_reduce)
+from .engine import RECORD_DTYPE, Batch, Engine
 
 
 class ShardedBPlusDB(CustomBPlusDB):
     """CustomBPlusDB over the ranks of a process group.  Every method below is COLLECTIVE: every rank calls it with the same
-    arguments, in the same order."""
+    arguments, in the same order.  The query methods are CustomBPlusDB's own; what they call to reach the table is overridden
+    here, hook by hook, with the collective function of distributed.py that gives every rank the single GPU's answer.
+
+    approx_group_by over all ranks: the key range is agreed (one MAX all-reduce), every rank bins the part of the sample inside
+    its region, ONE all-reduce SUM merges the bins (distributed.sharded_group_by; both columns: sharded_group_by_pair).
+    With ``error_percent``: level by level, one all-reduce SUM of the bins per level, every rank judging the same sums
+    (distributed.sharded_group_by_error).  With ``max_groups`` above 1024 (at most 65 536): SUM / AVG / COUNT through the
+    sliced sweep, the key ranges agreed in one MAX all-reduce and nbins x 4 sums merged in ONE all-reduce SUM
+    (distributed.sharded_group_by_wide).  With ``top`` = k: the same two all-reduces, then the k best groups are selected on
+    every rank's device from the same bins (distributed.sharded_group_by_top); ``last_top_info`` as CustomBPlusDB keeps it.
+    With ``having``: the same two all-reduces, then every rank judges the same bins on its device
+    (distributed.sharded_group_by_having); ``last_having_info`` as CustomBPlusDB keeps it, the same on every rank.  With no
+    table loaded it raises RuntimeError where CustomBPlusDB answers {}."""
 
     def __init__(self, *, device_id: Optional[int] = None, group=None, keep_rows_on_device: bool = True, collective: str = "torch"):
-        import torch
-        import torch.distributed as dist
         if not dist.is_initialized():
             raise RuntimeError("ShardedBPlusDB needs an initialised torch.distributed process group (one process per GPU)")
         super().__init__(device_id=int(os.environ.get("LOCAL_RANK", "0")) if device_id is None else device_id, keep_rows_on_device=keep_rows_on_device)
@@ -56,8 +71,7 @@ class ShardedBPlusDB(CustomBPlusDB):
             raise ValueError("collective must be 'torch' or 'mailbox'")
         self._plans = {}
         self._vec = None
-        self._bins = None
-        self._wide_bins = None  # the wide GROUP BY's bins (2 MiB), made when that form is first asked for
+        self._wide_bins = None  # the wide GROUP BY's bins (2 MiB), made when that form is first asked for (_sharded)
         self._lo = self._hi = 0
 
     # ---- the table: every rank stages its own region ----
@@ -114,7 +128,6 @@ class ShardedBPlusDB(CustomBPlusDB):
     def close_database(self) -> None:
         self._drop_plans()
         if self._mailbox is not None:
-            import torch.distributed as dist
             dist.barrier(group=self._group)  # nobody is still writing into a mailbox that is about to go
             self._mailbox.close()
             self._mailbox = None
@@ -125,7 +138,6 @@ class ShardedBPlusDB(CustomBPlusDB):
     def _finish_staging(self):
         self._dirty = False
         if self._want_mailbox and self._mailbox is None:
-            from .distributed import mailbox_from_torch_group
             self._mailbox = mailbox_from_torch_group(self._engine, self._group)
 
     def _drop_plans(self):
@@ -145,7 +157,6 @@ class ShardedBPlusDB(CustomBPlusDB):
     # ---- one query over all ranks ----
     def _collective(self, numel: int):
         if self._mailbox is not None and numel <= nat.MAILBOX_MAX_DOUBLES:
-            from .distributed import mailbox_all_reduce
             return mailbox_all_reduce(self._mailbox, self._side.cuda_stream)
         return self._ar_sum
 
@@ -165,13 +176,11 @@ class ShardedBPlusDB(CustomBPlusDB):
         return p
 
     def _buffer(self, need: int):
-        import torch
         if self._vec is None or self._vec.numel() < need:
             self._vec = torch.zeros(max(need, 1024), dtype=torch.float64, device=self._dev)
         return self._vec
 
     def _reduce(self, q) -> nat.Result:
-        import torch
         self._eng()
         plan = self._plan_for(q)
         need = max(MOMENT_VEC, plan.totals_len)
@@ -193,7 +202,6 @@ class ShardedBPlusDB(CustomBPlusDB):
     def _random_cpp(self, agg, sample_percent, seed, where=None) -> nat.Result:
         # (the reference draws from std::random_device; here every rank must draw the SAME sample: rank 0's seed)
         if seed is None:
-            import torch.distributed as dist
             box = [int.from_bytes(os.urandom(8), "little") if self._rank == 0 else None]
             dist.broadcast_object_list(box, src=dist.get_global_rank(self._group, 0) if self._group is not None else 0, group=self._group)
             seed = box[0]
@@ -202,7 +210,6 @@ class ShardedBPlusDB(CustomBPlusDB):
     def approx_batch(self, queries: "List[dict]") -> "List[ApproxResult]":
         """Several APPROX queries with ONE collective for all those that have the batched form (multi-round CLT queries: their
         sweeps are one launch, their round totals one all-reduce, their replays one launch); the others one after another."""
-        import torch
         self._eng()
         specs = [dict(kw) for kw in queries]
         keyed = {i for i, kw in enumerate(specs) if kw.get("key_where") is not None}  # entries with a key predicate run on their own
@@ -232,243 +239,98 @@ class ShardedBPlusDB(CustomBPlusDB):
                 raise RuntimeError("No samples collected")
         return out
 
-    def approx_group_by(self, agg: str, group_by: str = "region", sample_percent=None, method=None,
-                        where=None, block_size: int = 1000, key_where=None, error_percent=None, max_percent: float = 100.0,
-                        max_groups=_LEFT_OUT, top=None, ascending: bool = False, having=None) -> "dict[str, GroupEstimate]":
-        """GROUP BY over all ranks: the key range is agreed (one MAX all-reduce), every rank bins the part of the sample inside
-        its region, ONE all-reduce SUM merges the bins (distributed.sharded_group_by; both columns: sharded_group_by_pair).
-        With ``error_percent``: level by level, one all-reduce SUM of the bins per level, every rank judging the same sums
-        (distributed.sharded_group_by_error).  With ``max_groups`` above 1024 (at most 65 536): SUM / AVG / COUNT through the
-        sliced sweep, the key ranges agreed in one MAX all-reduce and nbins x 4 sums merged in ONE all-reduce SUM
-        (distributed.sharded_group_by_wide).  With ``top`` = k: the same two all-reduces, then the k best groups are selected on
-        every rank's device from the same bins (distributed.sharded_group_by_top); ``last_top_info`` as CustomBPlusDB keeps it.
-        With ``having``: the same two all-reduces, then every rank judges the same bins on its device
-        (distributed.sharded_group_by_having); ``last_having_info`` as CustomBPlusDB keeps it, the same on every rank."""
-        import torch
-        cols = group_columns(group_by)
-        col = cols[0]
-        if having is not None and error_percent is not None:
-            raise ValueError("having with error_percent: HAVING judges SUM, AVG and COUNT at one sample percentage only "
-                             "(the error-threshold form has no HAVING)")
-        hspec = None if having is None else _having_arg(having)
-        if max_groups is _LEFT_OUT:  # 1024, or under having what the wide entry accepts
-            max_groups = nat.WIDE_MAX_BINS if hspec is not None else 1024
-        wide = _wide_groups_arg(max_groups, "error_percent" if error_percent is not None else None)
-        k = _top_arg(top, "error_percent" if error_percent is not None else None)
-        if error_percent is not None:
-            return self._group_by_error(agg, cols, sample_percent, method, where, block_size, key_where, error_percent, max_percent)
-        sample_percent = 10.0 if sample_percent is None else sample_percent
-        method = "rowid" if method is None else method
-        m = {"rowid": nat.M_ROWID_MOD, "stride": nat.M_MEMORY_STRIDE, "block": nat.M_BLOCK, "page": nat.M_PAGE, "exact": nat.M_EXACT}[method]
+    # ---- the hooks of CustomBPlusDB's query methods, each ONE collective function of distributed.py on the side stream ----
+    def _sharded(self, fn, need, *lead, sum_only: bool = False, **kw):
+        """fn(engine, *lead, buffer, all-reduce SUM(, all-reduce MAX), stream=the side stream, **kw) under the side stream: ``fn``
+        is a distributed.sharded_* function, ``need`` the doubles its buffer must hold (None: the wide GROUP BY's bins, 2 MiB,
+        made when one of its three forms is first asked for)."""
         self._eng()
-        bs = 4096 if (method == "page" and block_size == 1000) else block_size
-        q = make_query(m, sample_percent, agg=_AGG[agg.upper()], where=where, block_size=int(bs))
-        if hspec is not None:
-            self.last_having_info = None
-            if k is not None:
-                self.last_top_info = None
-            f = None if key_where is None else _key_filter_for(key_where, method)
-            groups, hinfo, tinfo = _quantile_call(lambda: self._grouped_having(f, q, cols, hspec, k, not ascending, int(max_groups)))
-            if hinfo is not None:  # (None: an empty table)
-                self.last_having_info = hinfo.as_dict()
-            if tinfo is not None:
-                self.last_top_info = _top_info_dict(tinfo, len(cols) == 2)
-            return _pair_groups(groups, GroupEstimate) if len(cols) == 2 else {str(r.key): GroupEstimate(r) for r in groups}
-        if k is not None:
-            self.last_top_info = None
-            f = None if key_where is None else _key_filter_for(key_where, method)
-            groups, info = _quantile_call(lambda: self._grouped_top(f, q, cols, k, not ascending))
-            if info is not None:  # (None: an empty table)
-                self.last_top_info = _top_info_dict(info, len(cols) == 2)
-            return _pair_groups(groups, GroupEstimate) if len(cols) == 2 else {str(r.key): GroupEstimate(r) for r in groups}
-        if wide:
-            f = None if key_where is None else _key_filter_for(key_where, method)
-            groups = _quantile_call(lambda: self._grouped_wide(f, q, cols, int(max_groups)))
-            return _pair_groups(groups, GroupEstimate) if len(cols) == 2 else {str(r.key): GroupEstimate(r) for r in groups}
-        if len(cols) == 2:
-            f = None if key_where is None else _key_filter_for(key_where, method)
-            return _pair_groups(_quantile_call(lambda: self._grouped_pair(f, q, cols)), GroupEstimate)
-        if key_where is not None:
-            f = _key_filter_for(key_where, method)
-            return {str(r.key): GroupEstimate(r) for r in _quantile_call(lambda: self._grouped_filtered(f, q, col))}
         with torch.cuda.stream(self._side):
-            if self._bins is None:
-                self._bins = torch.zeros(4 * 4096, dtype=torch.float64, device=self._dev)
-            groups = sharded_group_by(self._engine, q, col, self._bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream)
-        return {str(r.key): GroupEstimate(r) for r in groups}
+            if need is not None:
+                buf = self._buffer(need)
+            else:
+                if self._wide_bins is None:
+                    self._wide_bins = torch.zeros(nat.WIDE_BIN * nat.WIDE_MAX_BINS, dtype=torch.float64, device=self._dev)
+                buf = self._wide_bins
+            ars = (self._ar_sum,) if sum_only else (self._ar_sum, self._ar_max)
+            return fn(self._engine, *lead, buf, *ars, stream=self._side.cuda_stream, **kw)
+
+    def _table_missing(self) -> bool:
+        self._eng()  # (raises: a sharded query with no table is an error on every rank alike, not an empty answer)
+        return False
+
+    def _grouped(self, q, col):
+        return self._sharded(sharded_group_by, 4 * 4096, q, col)
 
     def _quantiles(self, q, probs, interp):
         """approx_quantile over all ranks (collective): the amount range is agreed, then per pass one all-reduce SUM of the
         counts and one MAX of the range extremes (distributed.sharded_quantiles).  Every rank gets the same answer."""
-        import torch
-        self._eng()
-        with torch.cuda.stream(self._side):
-            vec = self._buffer(nat.QUANTILE_VEC_SUM + nat.QUANTILE_VEC_MAX)
-            return sharded_quantiles(self._engine, q, probs, interp, vec, self._ar_sum, self._ar_max, stream=self._side.cuda_stream)
+        return self._sharded(sharded_quantiles, nat.QUANTILE_VEC_SUM + nat.QUANTILE_VEC_MAX, q, probs, interp)
 
     def _spread(self, q, kind):
         """approx_spread over all ranks (collective): ONE all-reduce SUM of the 8 shifted power sums (distributed.sharded_spread)."""
-        import torch
-        self._eng()
-        with torch.cuda.stream(self._side):
-            return sharded_spread(self._engine, q, kind, self._buffer(nat.SPREAD_VEC), self._ar_sum, stream=self._side.cuda_stream)
+        return self._sharded(sharded_spread, nat.SPREAD_VEC, q, kind, sum_only=True)
 
     def _spread_groups(self, q, kind, col):
         """approx_spread(group_by=...) over all ranks: the key range is agreed, then ONE all-reduce SUM of nbins x 6 sums."""
-        import torch
-        self._eng()
-        with torch.cuda.stream(self._side):
-            bins = self._buffer(nat.SPREAD_BIN * 1024)
-            return sharded_group_by_spread(self._engine, q, kind, col, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream)
+        return self._sharded(sharded_group_by_spread, nat.SPREAD_BIN * 1024, q, kind, col)
 
-    # ---- key predicates (WHERE on region / product_id): the filtered sweeps over all ranks, one all-reduce SUM each ----
+    # key predicates (WHERE on region / product_id): the filtered sweeps over all ranks, one all-reduce SUM each
     def _reduce_filtered(self, f, q):
-        import torch
-        self._eng()
-        with torch.cuda.stream(self._side):
-            return sharded_filtered(self._engine, f, q, self._buffer(nat.SPREAD_VEC), self._ar_sum, stream=self._side.cuda_stream)
+        return self._sharded(sharded_filtered, nat.SPREAD_VEC, f, q, sum_only=True)
 
     def _spread_filtered(self, f, q, kind):
-        import torch
-        self._eng()
-        with torch.cuda.stream(self._side):
-            return sharded_filtered(self._engine, f, q, self._buffer(nat.SPREAD_VEC), self._ar_sum, stream=self._side.cuda_stream, kind=kind)
+        return self._sharded(sharded_filtered, nat.SPREAD_VEC, f, q, sum_only=True, kind=kind)
 
     def _grouped_filtered(self, f, q, col):
-        import torch
-        self._eng()
-        with torch.cuda.stream(self._side):
-            bins = self._buffer(nat.SPREAD_BIN * 1024)
-            return sharded_filtered_group_by(self._engine, f, q, col, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream)
+        return self._sharded(sharded_filtered_group_by, nat.SPREAD_BIN * 1024, f, q, col)
 
     def _spread_groups_filtered(self, f, q, kind, col):
-        import torch
-        self._eng()
-        with torch.cuda.stream(self._side):
-            bins = self._buffer(nat.SPREAD_BIN * 1024)
-            return sharded_filtered_group_by(self._engine, f, q, col, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, kind=kind)
+        return self._sharded(sharded_filtered_group_by, nat.SPREAD_BIN * 1024, f, q, col, kind=kind)
 
     def _grouped_error(self, f, q, cols, error_percent, max_percent):
-        import torch
-        from .distributed import sharded_group_by_error
-        self._eng()
-        with torch.cuda.stream(self._side):
-            bins = self._buffer(nat.SPREAD_BIN * 1024)
-            return sharded_group_by_error(self._engine, q, cols, error_percent, max_percent, bins, self._ar_sum, self._ar_max,
-                                          stream=self._side.cuda_stream, key_filter=f)
+        return self._sharded(sharded_group_by_error, nat.SPREAD_BIN * 1024, q, cols, error_percent, max_percent, key_filter=f)
 
-    # ---- GROUP BY both key columns: one MAX all-reduce of both key ranges, one all-reduce SUM of the bins ----
+    # GROUP BY both key columns: one MAX all-reduce of both key ranges, one all-reduce SUM of the bins
     def _grouped_pair(self, f, q, cols):
-        import torch
-        self._eng()
-        with torch.cuda.stream(self._side):
-            bins = self._buffer(nat.SPREAD_BIN * 1024)
-            return sharded_group_by_pair(self._engine, q, cols, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)
-
-    # ---- GROUP BY over wide key ranges: one MAX all-reduce of the key ranges, one all-reduce SUM of nbins x 4 sums ----
-    def _grouped_wide(self, f, q, cols, max_groups):
-        import torch
-        from .distributed import sharded_group_by_wide
-        self._eng()
-        with torch.cuda.stream(self._side):
-            if self._wide_bins is None:
-                self._wide_bins = torch.zeros(nat.WIDE_BIN * nat.WIDE_MAX_BINS, dtype=torch.float64, device=self._dev)
-            return sharded_group_by_wide(self._engine, q, cols, self._wide_bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream,
-                                         key_filter=f, max_groups=max_groups)
-
-    # ---- top-N groups: the wide form's two all-reduces, then the selection on every rank's device ----
-    def _grouped_top(self, f, q, cols, k, descending):
-        import torch
-        from .distributed import sharded_group_by_top
-        self._eng()
-        with torch.cuda.stream(self._side):
-            if self._wide_bins is None:
-                self._wide_bins = torch.zeros(nat.WIDE_BIN * nat.WIDE_MAX_BINS, dtype=torch.float64, device=self._dev)
-            return sharded_group_by_top(self._engine, q, cols, self._wide_bins, self._ar_sum, self._ar_max, k, descending,
-                                        stream=self._side.cuda_stream, key_filter=f)
-
-    # ---- HAVING: the wide form's two all-reduces, then the judging on every rank's device ----
-    def _grouped_having(self, f, q, cols, having, k, descending, max_groups):
-        import torch
-        from .distributed import sharded_group_by_having
-        self._eng()
-        with torch.cuda.stream(self._side):
-            if self._wide_bins is None:
-                self._wide_bins = torch.zeros(nat.WIDE_BIN * nat.WIDE_MAX_BINS, dtype=torch.float64, device=self._dev)
-            return sharded_group_by_having(self._engine, q, cols, self._wide_bins, self._ar_sum, self._ar_max, having, k, descending,
-                                           stream=self._side.cuda_stream, key_filter=f, max_groups=max_groups)
+        return self._sharded(sharded_group_by_pair, nat.SPREAD_BIN * 1024, q, cols, key_filter=f)
 
     def _spread_groups_pair(self, f, q, kind, cols):
-        import torch
-        self._eng()
-        with torch.cuda.stream(self._side):
-            bins = self._buffer(nat.SPREAD_BIN * 1024)
-            return sharded_group_by_pair(self._engine, q, cols, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f, kind=kind)
+        return self._sharded(sharded_group_by_pair, nat.SPREAD_BIN * 1024, q, cols, key_filter=f, kind=kind)
 
-    # ---- MIN / MAX: one all-reduce SUM of the counts, one all-reduce MAX of {-min, max}; approx_extremes / approx_min /
-    # approx_max are CustomBPlusDB's own, over these ----
+    # GROUP BY over wide key ranges, its top-N and HAVING forms: one MAX all-reduce of the key ranges, one all-reduce SUM of
+    # nbins x 4 sums, then the finish, the selection or the judging on every rank's device.  (Never None: no narrow path after it.)
+    def _grouped_wide(self, f, q, cols, max_groups):
+        return self._sharded(sharded_group_by_wide, None, q, cols, key_filter=f, max_groups=max_groups)
+
+    def _grouped_top(self, f, q, cols, k, descending):
+        return self._sharded(sharded_group_by_top, None, q, cols, k=k, descending=descending, key_filter=f)
+
+    def _grouped_having(self, f, q, cols, having, k, descending, max_groups):
+        return self._sharded(sharded_group_by_having, None, q, cols, having=having, k=k, descending=descending, key_filter=f, max_groups=max_groups)
+
+    # MIN / MAX: one all-reduce SUM of the counts, one all-reduce MAX of {-min, max} (grouped: of each half of the bins)
     def _extremes(self, f, q):
-        import torch
-        from .distributed import sharded_extremes
-        self._eng()
-        with torch.cuda.stream(self._side):
-            return sharded_extremes(self._engine, q, self._buffer(nat.EXTREME_VEC), self._ar_sum, self._ar_max, stream=self._side.cuda_stream,
-                                    key_filter=f)
+        return self._sharded(sharded_extremes, nat.EXTREME_VEC, q, key_filter=f)
 
     def _extremes_groups(self, f, q, cols):
-        import torch
-        from .distributed import sharded_group_extremes
-        self._eng()
-        with torch.cuda.stream(self._side):
-            bins = self._buffer(4 * 1024)
-            return sharded_group_extremes(self._engine, q, cols, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)
+        return self._sharded(sharded_group_extremes, 4 * 1024, q, cols, key_filter=f)
 
-    # ---- SUMMARY: one all-reduce SUM of the power sums and counts, one all-reduce MAX of {-min, max}; approx_summary is
-    # CustomBPlusDB's own, over this ----
+    # SUMMARY: one all-reduce SUM of the power sums and counts, one all-reduce MAX of {-min, max}
     def _summary(self, f, q):
-        import torch
-        from .distributed import sharded_summary
-        self._eng()
-        with torch.cuda.stream(self._side):
-            return sharded_summary(self._engine, q, self._buffer(nat.SUMMARY_VEC), self._ar_sum, self._ar_max, stream=self._side.cuda_stream,
-                                   key_filter=f)
+        return self._sharded(sharded_summary, nat.SUMMARY_VEC, q, key_filter=f)
 
-    # ---- time buckets: one all-reduce MAX of the timestamp range, one all-reduce SUM of nbuckets x 4 sums; approx_time_series is
-    # CustomBPlusDB's own, over this ----
+    # time buckets: one all-reduce MAX of the timestamp range (per key: and the key range), one all-reduce SUM of the bins
     def _time_series(self, f, q, spec):
-        import torch
-        from .distributed import sharded_time_series
-        self._eng()
-        with torch.cuda.stream(self._side):
-            bins = self._buffer(nat.TIME_BIN * nat.TIME_MAX_BUCKETS)
-            return sharded_time_series(self._engine, q, spec, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)
+        return self._sharded(sharded_time_series, nat.TIME_BIN * nat.TIME_MAX_BUCKETS, q, spec, key_filter=f)
 
-    # ---- per-key time series: one all-reduce MAX of the timestamp and key ranges, one all-reduce SUM of nbins x 4 sums;
-    # approx_time_series(group_by=...) is CustomBPlusDB's own, over this ----
     def _time_groups(self, f, q, column, spec):
-        import torch
-        from .distributed import sharded_time_groups
-        self._eng()
-        with torch.cuda.stream(self._side):
-            bins = self._buffer(nat.SERIES_BIN * nat.SERIES_MAX_BINS)
-            return sharded_time_groups(self._engine, q, column, spec, bins, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)
+        return self._sharded(sharded_time_groups, nat.SERIES_BIN * nat.SERIES_MAX_BINS, q, column, spec, key_filter=f)
 
-    # ---- HISTOGRAM: one all-reduce MAX for the range when the caller gives none, one all-reduce SUM of the counts;
-    # approx_histogram is CustomBPlusDB's own, over this ----
+    # HISTOGRAM: one all-reduce MAX for the range when the caller gives none, one all-reduce SUM of the counts
     def _histogram(self, f, q, spec):
-        import torch
-        from .distributed import sharded_histogram
-        self._eng()
-        with torch.cuda.stream(self._side):
-            vec = self._buffer(nat.HISTOGRAM_VEC_HEAD + nat.HISTOGRAM_MAX_BINS)
-            return sharded_histogram(self._engine, q, spec, vec, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)
+        return self._sharded(sharded_histogram, nat.HISTOGRAM_VEC_HEAD + nat.HISTOGRAM_MAX_BINS, q, spec, key_filter=f)
 
-    # ---- COUNT(DISTINCT): one all-reduce MAX for a key column's range, one all-reduce SUM of the counts, one all-reduce MAX of
-    # the slots; approx_distinct is CustomBPlusDB's own, over this ----
+    # COUNT(DISTINCT): one all-reduce MAX for a key column's range, one all-reduce SUM of the counts, one MAX of the slots
     def _distinct(self, f, q, col):
-        import torch
-        from .distributed import sharded_distinct
-        self._eng()
-        with torch.cuda.stream(self._side):
-            vec = self._buffer(nat.DISTINCT_VEC_HEAD + nat.DISTINCT_SLOTS)
-            return sharded_distinct(self._engine, q, col, vec, self._ar_sum, self._ar_max, stream=self._side.cuda_stream, key_filter=f)
+        return self._sharded(sharded_distinct, nat.DISTINCT_VEC_HEAD + nat.DISTINCT_SLOTS, q, col, key_filter=f)
