@@ -63,6 +63,8 @@ HISTOGRAM_VEC_HEAD = 4  # [visited, n, below, above], then count[0 .. bins): one
 DISTINCT_AMOUNT = 0  # the column of a distinct count: this, GROUP_REGION or GROUP_PRODUCT
 DISTINCT_SKETCH, DISTINCT_EXACT_KEYS = 0, 1
 DISTINCT_VEC_HEAD, DISTINCT_SLOTS = 2, 8192  # [visited, n] for a SUM all-reduce, then slot[0 .. 8192) for a MAX all-reduce
+# COUNT(DISTINCT) per group: the bounds of aqe_gdistinct_plan, the head of its vector, the words of a group's rank histogram
+GDISTINCT_MAX_GROUPS, GDISTINCT_MAX_CELLS, GDISTINCT_SLICE_CELLS, GDISTINCT_VEC_HEAD, GDISTINCT_RANKS = 1024, 262144, 16384, 2, 58
 SUMMARY_VEC, SUMMARY_VEC_SUM = 12, 10  # the SPREAD_VEC layout + {0, 0} for a SUM all-reduce, then {-min, max} for a MAX all-reduce
 TIME_BIN, TIME_MAX_BUCKETS, TIME_MAX_SPAN = 4, 1024, 2 ** 31 - 1  # {n, P1, P2, visited} per time bucket; the limits of aqe_time_plan
 SERIES_BIN, SERIES_MAX_BINS = 4, 65536  # {n, P1, P2, visited} per cell of a per-key time series; the bound of aqe_time_group_plan
@@ -251,6 +253,36 @@ class DistinctResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class GDistinctShape(C.Structure):
+    """aqe_gdistinct_shape: the plan of a COUNT(DISTINCT) per group (aqe_gdistinct_plan)."""
+    _fields_ = [("column", C.c_int32), ("by", C.c_int32), ("mode", C.c_int32), ("precision", C.c_int32), ("key_min", C.c_int32), ("groups", C.c_uint32),
+                ("cell_min", C.c_int32), ("cells_per_group", C.c_uint32), ("groups_per_slice", C.c_uint32), ("nslices", C.c_uint32),
+                ("total_cells", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class GDistinctResult(C.Structure):
+    """aqe_gdistinct_result: COUNT(DISTINCT column) of one group's sampled rows that qualify."""
+    _fields_ = [("value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double), ("key", C.c_int64), ("empty_slots", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class GDistinctInfo(C.Structure):
+    """aqe_gdistinct_info: the plan a grouped distinct count ran under and its counts over all groups."""
+    _fields_ = [("shape", GDistinctShape), ("n", C.c_uint64), ("visited", C.c_uint64), ("listed", C.c_uint32), ("lower_bound", C.c_int32),
+                ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "shape"}
+        d["shape"] = self.shape.as_dict()
+        return d
+
+
 class GroupErrorInfo(C.Structure):
     """aqe_group_error_info: where a GROUP BY to an error threshold stopped."""
     _fields_ = [("level", C.c_uint32), ("levels", C.c_uint32), ("sample_percent", C.c_double), ("visited", C.c_uint64),
@@ -413,6 +445,12 @@ def lib() -> C.CDLL:
         "aqe_distinct_mode": (C.c_int, [C.c_int, i32, i32, P(C.c_int), P(i32)]),
         "aqe_distinct_slot": (C.c_int, [C.c_int, C.c_int, i32, u64, P(u32), P(u32)]),
         "aqe_distinct_from_vec": (C.c_int, [P(dbl), C.c_int, C.c_int, i32, dbl, C.c_int, P(DistinctResult)]),
+        "aqe_gdistinct_plan": (C.c_int, [C.c_int, C.c_int, i32, i32, i32, i32, u32, P(GDistinctShape)]),
+        "aqe_gdistinct_slot": (C.c_int, [C.c_int, C.c_int, u64, P(u32), P(u32)]),
+        "aqe_gdistinct_from_cells": (C.c_int, [P(dbl), P(GDistinctShape), C.c_int64, dbl, P(GDistinctResult)]),
+        "aqe_reduce_grouped_distinct": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, C.c_int, P(GDistinctResult), u32, P(GDistinctInfo), P(u32)]),
+        "aqe_grouped_distinct_enqueue_cells": (C.c_int, [vp, P(KeyFilter), P(Query), P(GDistinctShape), vp, vp]),
+        "aqe_grouped_distinct_finish": (C.c_int, [vp, P(Query), P(GDistinctShape), vp, vp, P(GDistinctResult), u32, P(GDistinctInfo), P(u32)]),
         "aqe_reduce_summary": (C.c_int, [vp, P(KeyFilter), P(Query), P(SummaryResult)]),
         "aqe_summary_enqueue": (C.c_int, [vp, P(KeyFilter), P(Query), vp, vp]),
         "aqe_summary_finish": (C.c_int, [vp, P(Query), vp, vp, P(SummaryResult)]),

@@ -458,6 +458,29 @@ def having_defect(clean: str, args) -> Optional[str]:
     return None
 
 
+def distinct_by_defect(clean: str, args) -> Optional[str]:
+    """What is wrong with --distinct-by beside this query (None: nothing, or the flag is absent): it goes with a query
+    distinct_of() claims, names region or product_id — not the counted column — and has no --e form.  (A GROUP BY clause is left
+    to the refusal every distinct count gives it.)"""
+    by = getattr(args, "distinct_by", None)
+    if by is None:
+        return None
+    name = str(by).strip().lower()
+    if name not in ("region", "product_id"):
+        return f"--distinct-by {by}: the groups are the keys of region or product_id"
+    try:
+        col = distinct_of(clean)
+    except ValueError as e:
+        return str(e)
+    if col is None:
+        return "--distinct-by goes with a distinct count, e.g. \"SELECT COUNT(DISTINCT product_id) FROM sales\" --distinct-by region"
+    if args.e is not None:
+        return "--distinct-by has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"
+    if col == name and not re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
+        return f"--distinct-by {name}: COUNT(DISTINCT {col}) is counted per key of the other key column (every {name} holds one {name})"
+    return None
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV, MIN/MAX, HISTOGRAM, COUNT(DISTINCT), SUMMARY on MI355X "
                                 "(e.g. \"SELECT HISTOGRAM(amount, 20) FROM sales\" --s 10 --ci; \"SELECT SUMMARY(amount) FROM sales\" --s 10 --ci)",
@@ -478,6 +501,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--all-groups", dest="all_groups", action="store_true", help="with --max-groups: print every group (default: the first 50 and a count of the rest)")
     p.add_argument("--series-by", dest="series_by", metavar="COLUMN", help="with GROUP BY BUCKET(timestamp, W): one time series per key of COLUMN "
                    "(region or product_id), from one sweep; at most 65536 cells (keys x buckets)")
+    p.add_argument("--distinct-by", dest="distinct_by", metavar="COLUMN", help="with COUNT(DISTINCT col): one count per key of COLUMN (region or product_id), "
+                   "from one sweep; at most 1024 groups")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="under torchrun (one process per GPU): the torch.distributed backend (nccl = RCCL)")
     p.add_argument("--collective", choices=["torch", "mailbox"], default="torch", help="under torchrun: the all-reduce of the moment vectors "
@@ -494,6 +519,10 @@ def run(args, out=sys.stdout) -> int:
         print("error: a query is required unless --explain is given", file=out)
         return 2
     clean, _ = parse_embedded_approx(args.query)
+    why = distinct_by_defect(clean, args)
+    if why is not None:
+        print(f"error: {why}", file=out)
+        return 2
     full = clean  # (with a claimed HAVING clause, which _run_on finds again)
     why = having_defect(clean, args)
     if why is not None:
@@ -558,7 +587,7 @@ def run(args, out=sys.stdout) -> int:
             print("error: COUNT(DISTINCT) has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
             return 2
         if re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
-            print("error: GROUP BY is not supported with COUNT(DISTINCT)", file=out)
+            print("error: GROUP BY is not supported with COUNT(DISTINCT) (a count per group: leave the GROUP BY clause out and give --distinct-by region|product_id)", file=out)
             return 2
     try:
         summary = summary_of(clean)
@@ -938,6 +967,29 @@ def _run_distinct(db, args, out, clean, qtype, column, aqe_backend, t0, kw=None)
         pct = args.s if args.s is not None else 10.0
         method = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", "stride")
         name = f"{method} sampling ({pct}%)"
+    by = getattr(args, "distinct_by", None)
+    if by is not None:  # one count per key of `by`: a line per group, then the summary
+        by = str(by).strip().lower()
+        groups = db.approx_distinct_by(column, by, method=method, sample_percent=pct, where=where, confidence_level=args.confidence, seed=args.seed,
+                                       num_threads=args.threads, **kw)
+        ms = (time.perf_counter() - t0) * 1e3
+        info = db.last_distinct_by_info
+        shape = info["shape"]
+        sketch = shape["precision"] > 0  # (exact keys carry no precision)
+        fmt = (lambda v: f"{v:,.1f}") if sketch else (lambda v: f"{int(v):,}")
+        print(f"\n{name} COUNT(DISTINCT {column}) by {by} result:", file=out)
+        for key, g in groups.items():
+            ci = f"   ({fmt(g.ci_lower)} - {fmt(g.ci_upper)})" if args.ci else ""
+            print(f"   {by} {key}: {fmt(g.value)}{ci}", file=out)
+        se = 1.04 / shape["cells_per_group"] ** 0.5 * 100 if sketch else 0.0
+        mode = f"sketch (HyperLogLog, p = {shape['precision']})" if sketch else "exact keys"
+        print(f"   {len(groups)} groups; {mode}, {shape['cells_per_group']:,} slots per group, standard error {se:.2f}%; "
+              f"{info['n']:,} rows qualified of {info['visited']:,} sampled", file=out)
+        if method != "exact":
+            print("   note: the figures count the distinct values among the sampled rows: lower bounds for the table", file=out)
+        print(f"   execution time: {ms:.2f} ms (kernels {info['kernel_ms'] * 1e3:.1f} us)", file=out)
+        db.close_database()
+        return 0
     res = db.approx_distinct(column=column, method=method, sample_percent=pct, where=where, confidence_level=args.confidence, seed=args.seed,
                              num_threads=args.threads, **kw)
     ms = (time.perf_counter() - t0) * 1e3

@@ -31,6 +31,7 @@
 #include <limits>
 
 #include "device_common.hpp"
+#include "distinct_core.hpp"
 #include "host.hpp"
 #include "key_term.hpp"
 #include "spread_core.hpp"
@@ -44,28 +45,16 @@ constexpr int kDistWaves = kDistThreads / 64;
 constexpr unsigned kDistGridCap = 256;  // one workgroup per CU, all resident at once
 constexpr unsigned kSlots = AQE_DISTINCT_SLOTS;
 constexpr unsigned kHead = AQE_DISTINCT_VEC_HEAD;
-constexpr unsigned kPrecision = 13;     // slot = the hash's top 13 bits
+constexpr unsigned kPrecision = kSketchMaxPrecision;  // slot = the hash's top 13 bits
 constexpr unsigned kMaxRank = 64 - kPrecision + 1;  // 52: the 51 bits below them all zero
 constexpr size_t kVecWords = kHead + kSlots;
 static_assert(kHead == 2 && kSlots == (1u << kPrecision) && kMaxRank == 52, "vector layout and sketch of include/aqe_hip.h");
 static_assert(sizeof(aqe_distinct_result) == 72, "layout of include/aqe_hip.h");
 static_assert(kMapWords == 16, "two maps are staged by 32 threads");
 
-// splitmix64's finaliser.
-__host__ __device__ inline uint64_t distinct_hash(uint64_t u) {
-    uint64_t z = u + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// The sketch's slot and rank of a hash.
-__host__ __device__ inline void sketch_slot(uint64_t h, unsigned* slot, unsigned* rank) {
-    const uint64_t w = h << kPrecision;
-    *slot = static_cast<unsigned>(h >> (64 - kPrecision));
-    *rank = w ? static_cast<unsigned>(__builtin_clzll(w)) + 1u : kMaxRank;
-}
-// The value bits of an amount (NaN aside): -0.0 and +0.0 are one value.
-__host__ __device__ inline uint64_t amount_bits(uint64_t bits) { return bits == 0x8000000000000000ull ? 0ull : bits; }
+// (distinct_hash, amount_bits, the slot and rank at a precision and Ertl's estimator are distinct_core.hpp's: the grouped form
+// shares them.)  The sketch's slot and rank of a hash at p = 13.
+__host__ __device__ inline void sketch_slot(uint64_t h, unsigned* slot, unsigned* rank) { sketch_slot_at(h, kPrecision, slot, rank); }
 
 struct DistLaunch {
     SweepCommon sw;
@@ -226,30 +215,6 @@ inline unsigned grid_for(uint64_t work, uint64_t per_block) {
     return static_cast<unsigned>(g < 1 ? 1 : g > kDistGridCap ? kDistGridCap : g);
 }
 
-// Ertl's two helper series (include/aqe_hip.h).
-inline double hll_sigma(double x) {
-    if (x == 1.0) return std::numeric_limits<double>::infinity();
-    double y = 1.0, z = x, before;
-    do {
-        x *= x;
-        before = z;
-        z += x * y;
-        y += y;
-    } while (before != z);
-    return z;
-}
-inline double hll_tau(double x) {
-    if (x == 0.0 || x == 1.0) return 0.0;
-    double y = 1.0, z = 1.0 - x, before;
-    do {
-        x = std::sqrt(x);
-        before = z;
-        y *= 0.5;
-        z -= (1.0 - x) * (1.0 - x) * y;
-    } while (before != z);
-    return z / 3.0;
-}
-
 inline bool column_ok(int column) { return column == AQE_DISTINCT_AMOUNT || column == AQE_GROUP_REGION || column == AQE_GROUP_PRODUCT; }
 // What is wrong with a (column, mode) pair (nullptr: nothing).
 const char* mode_defect(int column, int mode) {
@@ -292,12 +257,8 @@ void from_vec(const double* vec, int column, int mode, int32_t key_min, double c
         r->value = r->ci_lower = r->ci_upper = static_cast<double>(set);
         return;
     }
-    const double m = static_cast<double>(kSlots);
-    double z = m * hll_tau(1.0 - C[kMaxRank] / m);
-    for (unsigned k = kMaxRank - 1; k >= 1; --k) z = 0.5 * (z + C[k]);
-    z += m * hll_sigma(C[0] / m);
-    const double value = m * m / (2.0 * std::log(2.0)) / z;
-    const double half = z_for(confidence) * (1.04 / std::sqrt(m));
+    const double value = hll_estimate(C, kPrecision);
+    const double half = hll_half_width(z_for(confidence), kPrecision);
     r->value = value;
     r->ci_lower = std::max(0.0, value * (1.0 - half));
     r->ci_upper = value * (1.0 + half);

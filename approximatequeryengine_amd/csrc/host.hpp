@@ -101,6 +101,7 @@ struct aqe_moment_scratch;  // moments.hip
 struct aqe_extreme_scratch;  // extremes.hip
 struct aqe_histogram_scratch;  // histogram.hip
 struct aqe_distinct_scratch;  // distinct.hip
+struct aqe_gdistinct_scratch;  // grouped_distinct.hip
 struct aqe_summary_scratch;  // summary.hip
 struct aqe_time_scratch;  // timeseries.hip
 struct aqe_wide_scratch;  // wide_group.hip
@@ -176,6 +177,8 @@ struct aqe_ctx {
     aqe_histogram_scratch* histogram = nullptr;
     // COUNT(DISTINCT) (distinct.hip): accumulator, tickets and the pinned vector of the sketch sweep, made on first use
     aqe_distinct_scratch* distinct = nullptr;
+    // COUNT(DISTINCT) per group (grouped_distinct.hip): accumulator, tickets, the cell vector and the rank counts, made on first use
+    aqe_gdistinct_scratch* gdistinct = nullptr;
     // SUMMARY (summary.hip): partials, tickets and the pinned result of the fused moments-and-extremes sweep, made on first use
     aqe_summary_scratch* summary = nullptr;
     // time buckets (timeseries.hip): the workgroups' bins, the summed bins and the pinned groups, made on first use
@@ -367,6 +370,9 @@ void histogram_release(aqe_ctx* c);
 
 // distinct.hip
 void distinct_release(aqe_ctx* c);
+
+// grouped_distinct.hip
+void gdistinct_release(aqe_ctx* c);
 
 // summary.hip
 void summary_release(aqe_ctx* c);

@@ -656,6 +656,34 @@ def sharded_distinct(engine, query, column: int, vec, all_reduce_sum: Callable, 
         return engine.distinct_finish(query, column, mode, kmin, v.data_ptr(), stream)
 
 
+def sharded_distinct_groups(engine, query, column: int, by: int, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
+    """COUNT(DISTINCT column) per key of ``by`` across the ranks of a process group (engine.Engine interface), collective.  The
+    key ranges of the group column and of the counted column (a counted amount: the other key column's, unused) are agreed in
+    ONE all-reduce MAX of [-min, max] pairs, as sharded_group_by_pair; every rank makes the same plan from them on the host
+    (engine.gdistinct_plan: more than 1024 groups, or the same column on both sides, is refused on every rank alike, before the
+    sweep).  Then every rank sweeps the part of the sample inside its shard into GDISTINCT_VEC_HEAD + total_cells doubles
+    (aqe_grouped_distinct_enqueue_cells; an empty shard contributes zeros), ONE all-reduce SUM merges [visited, n], ONE
+    all-reduce MAX the cells, and every rank finishes the same vector: the same (groups, info, rank histograms) on every rank,
+    bit for bit.  An empty table gives ([], None, None).
+
+    vec     float64 tensor on the engine's device with room for GDISTINCT_VEC_HEAD + total_cells doubles (at most 2 + 262 144)
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    from ._native import DISTINCT_AMOUNT, GDISTINCT_VEC_HEAD, GROUP_PRODUCT, GROUP_REGION
+    from .engine import gdistinct_plan
+    column, by = int(column), int(by)
+    gdistinct_plan(column, by, (0, 0))  # the columns' own refusals, before any collective
+    with _on_stream(stream, vec) as stream:
+        second = column if column != DISTINCT_AMOUNT else (GROUP_PRODUCT if by == GROUP_REGION else GROUP_REGION)
+        (by_lo, by_hi), (c_lo, c_hi) = _agree_ranges([engine.group_key_range(by), engine.group_key_range(second)], vec, all_reduce_max)
+        if by_hi < by_lo:
+            return [], None, None  # an empty table
+        shape = gdistinct_plan(column, by, (int(by_lo), int(by_hi)), (int(c_lo), int(c_hi)))
+        v = _take(vec, GDISTINCT_VEC_HEAD + shape.total_cells, vector=True)
+        engine.distinct_groups_enqueue_cells(query, shape, v.data_ptr(), stream, key_filter)
+        _sum_then_max(v, GDISTINCT_VEC_HEAD, all_reduce_sum, all_reduce_max)
+        return engine.distinct_groups_finish(query, shape, v.data_ptr(), stream)
+
+
 def sharded_group_extremes(engine, query, columns, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
     """GROUP BY MIN / MAX across ranks, collective: ``columns`` is one column or the ordered pair (A, B).  The key ranges are
     agreed in ONE MAX all-reduce (as sharded_group_by_pair); every rank bins its part of the sample into

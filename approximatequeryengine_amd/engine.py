@@ -855,6 +855,32 @@ class Engine:
                                                 C.byref(out)))
         return out
 
+    # -- COUNT(DISTINCT column) per group (aqe_reduce_grouped_distinct and its kin): one sliced sketch sweep --
+    def distinct_groups(self, query: Query, column: int, by: int, key_filter: "Optional[nat.KeyFilter]" = None):
+        """The distinct values of ``column`` per key of ``by`` (GROUP_REGION, GROUP_PRODUCT) among the sampled rows that qualify:
+        (list of GDistinctResult ascending by key, GDistinctInfo, the listed groups' rank histograms as a uint32 array
+        [listed, GDISTINCT_RANKS])."""
+        cap = nat.GDISTINCT_MAX_GROUPS
+        out, info, ranks = (nat.GDistinctResult * cap)(), nat.GDistinctInfo(), np.zeros((cap, nat.GDISTINCT_RANKS), dtype=np.uint32)
+        self._chk(nat.lib().aqe_reduce_grouped_distinct(self._h, _filter_ref(key_filter), C.byref(query), int(column), int(by), out, cap, C.byref(info),
+                                                        ranks.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return list(out[: info.listed]), info, ranks[: info.listed].copy()
+
+    def distinct_groups_enqueue_cells(self, query: Query, shape: "nat.GDistinctShape", dev_vec_ptr: int, stream: int = 0,
+                                      key_filter: "Optional[nat.KeyFilter]" = None):
+        """This shard's GDISTINCT_VEC_HEAD + shape.total_cells doubles into device memory: all-reduce SUM of [0, 2), MAX of the rest,
+        then distinct_groups_finish.  ``shape`` is the plan every rank makes from the agreed key ranges (gdistinct_plan)."""
+        self._chk(nat.lib().aqe_grouped_distinct_enqueue_cells(self._h, _filter_ref(key_filter), C.byref(query), C.byref(shape), C.c_void_p(dev_vec_ptr),
+                                                               C.c_void_p(stream)))
+
+    def distinct_groups_finish(self, query: Query, shape: "nat.GDistinctShape", dev_vec_ptr: int, stream: int = 0):
+        """(groups, info, rank histograms) as distinct_groups returns them, from the (all-reduced) cell vector."""
+        cap = nat.GDISTINCT_MAX_GROUPS
+        out, info, ranks = (nat.GDistinctResult * cap)(), nat.GDistinctInfo(), np.zeros((cap, nat.GDISTINCT_RANKS), dtype=np.uint32)
+        self._chk(nat.lib().aqe_grouped_distinct_finish(self._h, C.byref(query), C.byref(shape), C.c_void_p(dev_vec_ptr), C.c_void_p(stream), out, cap,
+                                                        C.byref(info), ranks.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return list(out[: info.listed]), info, ranks[: info.listed].copy()
+
     def gather(self, query: Query) -> np.ndarray:
         """Rows of the record-returning sampler, as a RECORD_DTYPE array."""
         n = C.c_uint64()
@@ -1204,6 +1230,39 @@ def distinct_from_vec(vec: Sequence[float], column: int, mode: int, key_min: int
                                          int(bool(exact)), C.byref(out))
     if rc != nat.OK:
         raise nat.AqeError(rc, "COUNT(DISTINCT): bad column or mode (the amount column takes the sketch only)")
+    return out
+
+
+def gdistinct_plan(column: int, by: int, by_range: Tuple[int, int], column_range: Tuple[int, int] = (0, -1), slice_cells: int = 0) -> "nat.GDistinctShape":
+    """aqe_gdistinct_plan: the plan of COUNT(DISTINCT column) per key of ``by`` over the group column's key range ``by_range`` and,
+    for a counted key column, its ``column_range`` — mode, cells per group, precision, groups per slice, slices — host only.
+    ``slice_cells`` 0: AQE_GDISTINCT_SLICE from the environment, or the default.  Raises AqeError with the library's text:
+    ERR_INVALID for the same column on both sides, ERR_UNSUPPORTED past GDISTINCT_MAX_GROUPS groups (the message names the span)."""
+    out = nat.GDistinctShape()
+    nat.check(nat.lib().aqe_gdistinct_plan(int(column), int(by), int(by_range[0]), int(by_range[1]), int(column_range[0]), int(column_range[1]),
+                                           int(slice_cells), C.byref(out)))
+    return out
+
+
+def gdistinct_slot(column: int, precision: int, value_bits: int):
+    """aqe_gdistinct_slot: (register, rank) the grouped sweep writes for the 64 value bits at ``precision`` 8 .. 13 — no GPU.
+    AqeError (ERR_INVALID) for a NaN amount or a precision outside that range."""
+    slot, rank = C.c_uint32(), C.c_uint32()
+    rc = nat.lib().aqe_gdistinct_slot(int(column), int(precision), int(value_bits) & 0xFFFFFFFFFFFFFFFF, C.byref(slot), C.byref(rank))
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "COUNT(DISTINCT) by group: no register for this column, precision and value (a NaN amount, a precision outside 8 .. 13)")
+    return slot.value, rank.value
+
+
+def gdistinct_from_cells(cells: Sequence[float], shape: "nat.GDistinctShape", key: int = 0, confidence_level: float = 0.95) -> "nat.GDistinctResult":
+    """aqe_gdistinct_from_cells: one group's value and interval from its ``shape.cells_per_group`` cells, on the host — no GPU."""
+    v = np.ascontiguousarray(cells, dtype=np.float64)
+    if len(v) != shape.cells_per_group:
+        raise ValueError(f"{shape.cells_per_group} cells expected, got {len(v)}")
+    out = nat.GDistinctResult()
+    rc = nat.lib().aqe_gdistinct_from_cells(v.ctypes.data_as(C.POINTER(C.c_double)), C.byref(shape), int(key), float(confidence_level), C.byref(out))
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "COUNT(DISTINCT) by group: not a plan of gdistinct_plan")
     return out
 
 

@@ -29,7 +29,7 @@ import torch.distributed as dist
 from . import _native as nat
 from .aqe_backend import ApproxResult, CustomBPlusDB
 from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, mailbox_all_reduce, mailbox_from_torch_group, shard_bounds, sharded_adaptive_plan,
-                          sharded_distinct, sharded_extremes, sharded_filtered, sharded_filtered_group_by, sharded_group_by, sharded_group_by_error,
+                          sharded_distinct, sharded_distinct_groups, sharded_extremes, sharded_filtered, sharded_filtered_group_by, sharded_group_by, sharded_group_by_error,
                           sharded_group_by_having, sharded_group_by_pair, sharded_group_by_spread, sharded_group_by_top, sharded_group_by_wide,
                           sharded_group_extremes, sharded_histogram, sharded_quantiles, sharded_spread, sharded_stratified_plan, sharded_summary,
                           sharded_time_groups, sharded_time_series, torch_all_reduce, torch_host_all_reduce)
@@ -334,3 +334,11 @@ class ShardedBPlusDB(CustomBPlusDB):
     # COUNT(DISTINCT): one all-reduce MAX for a key column's range, one all-reduce SUM of the counts, one MAX of the slots
     def _distinct(self, f, q, col):
         return self._sharded(sharded_distinct, nat.DISTINCT_VEC_HEAD + nat.DISTINCT_SLOTS, q, col, key_filter=f)
+
+    # COUNT(DISTINCT) per group: one all-reduce MAX of both columns' key ranges, one all-reduce SUM of the counts, one MAX of the cells
+    def _distinct_groups(self, f, q, col, by):
+        groups, info, ranks = self._sharded(sharded_distinct_groups, nat.GDISTINCT_VEC_HEAD + nat.GDISTINCT_MAX_CELLS, q, col, by, key_filter=f)
+        if info is None:  # an empty table
+            info = nat.GDistinctInfo()
+            info.shape.column, info.shape.by = col, by
+        return groups, info, ranks

@@ -1084,6 +1084,86 @@ AQE_API int aqe_distinct_slot(int column, int mode, int32_t key_min, uint64_t va
 AQE_API int aqe_distinct_from_vec(const double* vec, int column, int mode, int32_t key_min, double confidence_level, int exact,
                                   aqe_distinct_result* out);
 
+/* ---- grouped distinct: COUNT(DISTINCT column) per key of a group column from ONE sliced sweep (grouped_distinct.hip) ----------
+ * `column` as above; `by` is AQE_GROUP_REGION or AQE_GROUP_PRODUCT and differs from `column` (the same column on both sides is
+ * AQE_ERR_INVALID naming it).  Which rows qualify, the value bits and the hash: exactly as for aqe_reduce_distinct, with both key
+ * terms of `filter` in force.  A group is LISTED when at least one of its sampled rows qualified; the list ascends by key.
+ *
+ * The plan (aqe_gdistinct_plan, host only).  G = the group column's span by_hi - by_lo + 1, at most AQE_GDISTINCT_MAX_GROUPS
+ * (more: AQE_ERR_UNSUPPORTED naming G and the limit; nothing is truncated); total cells G x cells_per_group at most
+ * AQE_GDISTINCT_MAX_CELLS.
+ *   AQE_DISTINCT_EXACT_KEYS  a counted key column of span S <= 8192 with G x S <= AQE_GDISTINCT_MAX_CELLS: cells_per_group = S,
+ *                            cell key - cell_min of the row's group is set to 1, the count is exact and its interval has no width.
+ *   AQE_DISTINCT_SKETCH      otherwise: HyperLogLog with m = 2^p registers per group, p = min(13, floor(log2(MAX_CELLS / G))) —
+ *                            13 up to 32 groups, 11 at 100, 8 at 1024; relative standard error 1.04 / sqrt(m).  Register = the hash's
+ *                            top p bits; with w = h << p the rank is w ? clz(w) + 1 : 64 - p + 1 (aqe_gdistinct_slot).  At p = 13
+ *                            a group's registers are those aqe_reduce_distinct holds for that group's rows.
+ * Slices: a slice holds whole groups and at most AQE_GDISTINCT_SLICE_CELLS cells (64 KiB of LDS); every slice's workgroups sweep
+ * the sampled rows again.  slice_cells != 0, or else the environment variable AQE_GDISTINCT_SLICE (read when the plan is made),
+ * forces a smaller slice; a value that fits no whole group, or above the default, is ignored.  The answer does not depend on it.
+ *
+ * Vector: [visited, n, cell[group 0][0 .. cells_per_group), cell[group 1][...], ...] as doubles, AQE_GDISTINCT_VEC_HEAD +
+ * total_cells of them; shards merge by SUM over the head and MAX over the cells — integers both: bit-identical from run to run.
+ * Result per listed group.  Sketch: Ertl's estimator as above with m = 2^p, q = 64 - p, from the histogram C[0 .. 64 - p + 1] of
+ * the group's register values, which k_gdistinct_counts makes on the device (AQE_GDISTINCT_RANKS integers per listed group are
+ * copied back, not the cells); ci = value (1 -+ z 1.04 / sqrt(m)), the lower end never below 0.  Exact keys: the number of cells
+ * set, [value, value].  empty_slots: cells still 0.  THE INTERVAL COVERS THE SKETCH'S ERROR, NOT THE SAMPLING (lower_bound).
+ * Samplers: those of aqe_reduce_distinct, refused by name alike; there is no error-threshold form. */
+#define AQE_GDISTINCT_MAX_GROUPS 1024
+#define AQE_GDISTINCT_MAX_CELLS 262144
+#define AQE_GDISTINCT_SLICE_CELLS 16384
+#define AQE_GDISTINCT_VEC_HEAD 2
+#define AQE_GDISTINCT_RANKS 58 /* C[0 .. 57]: the histogram of register values at the smallest precision, 8 */
+typedef struct aqe_gdistinct_shape {
+    int32_t column, by;
+    int32_t mode;              /* AQE_DISTINCT_SKETCH or AQE_DISTINCT_EXACT_KEYS */
+    int32_t precision;         /* sketch: p; exact keys: 0 */
+    int32_t key_min;           /* the group column's smallest key: group g is key_min + g */
+    uint32_t groups;           /* G; 0: an empty table */
+    int32_t cell_min;          /* exact keys: the counted key of cell 0 (else 0) */
+    uint32_t cells_per_group;
+    uint32_t groups_per_slice, nslices;
+    uint32_t total_cells;      /* groups x cells_per_group */
+    uint32_t reserved;
+} aqe_gdistinct_shape;
+typedef struct aqe_gdistinct_result {
+    double value, ci_lower, ci_upper;
+    int64_t key;               /* of the group column */
+    uint32_t empty_slots;      /* cells still 0, of cells_per_group */
+    uint32_t reserved;
+} aqe_gdistinct_result;
+typedef struct aqe_gdistinct_info {
+    aqe_gdistinct_shape shape;
+    uint64_t n, visited;       /* rows qualifying, rows sampled: over all groups */
+    uint32_t listed;           /* groups with a qualifying sampled row (also when cap is too small) */
+    int32_t lower_bound;       /* 1: the rows swept are a sample */
+    double kernel_ms;          /* aqe_reduce_grouped_distinct: the sweep, the counts, the compaction */
+} aqe_gdistinct_info;
+/* Host only, no GPU.  aqe_gdistinct_plan: the plan over the group column's key range [by_lo, by_hi] (empty: groups == 0) and,
+ * for a counted key column, its range [col_lo, col_hi]; a refusal's text is aqe_last_error(NULL)'s.  aqe_gdistinct_slot: the
+ * register and rank the sweep writes for `value_bits` at precision 8 .. 13 (an amount's NaN: AQE_ERR_INVALID).
+ * aqe_gdistinct_from_cells: one group's result from its cells_per_group cells (doubles, as the vector holds them) — at p = 13
+ * value, interval and empty_slots are aqe_distinct_from_vec's for the same registers, to the bit. */
+AQE_API int aqe_gdistinct_plan(int column, int by, int32_t by_lo, int32_t by_hi, int32_t col_lo, int32_t col_hi, uint32_t slice_cells,
+                               aqe_gdistinct_shape* out);
+AQE_API int aqe_gdistinct_slot(int column, int precision, uint64_t value_bits, uint32_t* slot, uint32_t* rank);
+AQE_API int aqe_gdistinct_from_cells(const double* cells, const aqe_gdistinct_shape* shape, int64_t key, double confidence_level,
+                                     aqe_gdistinct_result* out);
+/* Single GPU, synchronous: the plan from the table's own key ranges, the sweep, the counts, the estimates.  out: room for `cap`
+ * groups (fewer than listed: AQE_ERR_INVALID with the number, info->listed set, no partial list).  rank_counts (NULL: not
+ * wanted): [cap][AQE_GDISTINCT_RANKS], the histogram C of every listed group as it came back from the device. */
+AQE_API int aqe_reduce_grouped_distinct(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, int column, int by, aqe_gdistinct_result* out,
+                                        uint32_t cap, aqe_gdistinct_info* info, uint32_t* rank_counts);
+/* Multi-GPU.  The ranks agree on both columns' key ranges (aqe_group_key_range, ONE all-reduce MAX of [-min, max] pairs) and
+ * every rank makes the same plan from them; dev_vec: AQE_GDISTINCT_VEC_HEAD + shape->total_cells doubles:
+ *     aqe_grouped_distinct_enqueue_cells(ctx, filter, q, &shape, dev_vec, stream)     (an empty shard: zeros)
+ *     all-reduce SUM of dev_vec[0 .. 2), all-reduce MAX of dev_vec[2 .. 2 + total_cells)
+ *     aqe_grouped_distinct_finish(ctx, q, &shape, dev_vec, stream, out, cap, &info, rank_counts)     synchronises `stream` */
+AQE_API int aqe_grouped_distinct_enqueue_cells(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const aqe_gdistinct_shape* shape,
+                                               double* dev_vec, void* stream);
+AQE_API int aqe_grouped_distinct_finish(aqe_ctx* ctx, const aqe_query* q, const aqe_gdistinct_shape* shape, const double* dev_vec, void* stream,
+                                        aqe_gdistinct_result* out, uint32_t cap, aqe_gdistinct_info* info, uint32_t* rank_counts);
+
 /* ---- summary: SUMMARY(amount) — count, sum, mean, spread, smallest and largest from ONE fused sweep (summary.hip) ----------
  * X = the sampled amounts: rows of q's sampler inside its row window that pass the inclusive amount WHERE range and the
  * key filter (`filter`, NULL: none — in every entry), NaN rows left out: the set aqe_reduce_extremes sees.  n = |X|;
