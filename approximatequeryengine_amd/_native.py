@@ -69,6 +69,8 @@ SUMMARY_VEC, SUMMARY_VEC_SUM = 12, 10  # the SPREAD_VEC layout + {0, 0} for a SU
 TIME_BIN, TIME_MAX_BUCKETS, TIME_MAX_SPAN = 4, 1024, 2 ** 31 - 1  # {n, P1, P2, visited} per time bucket; the limits of aqe_time_plan
 SERIES_BIN, SERIES_MAX_BINS = 4, 65536  # {n, P1, P2, visited} per cell of a per-key time series; the bound of aqe_time_group_plan
 WIDE_BIN, WIDE_MAX_BINS, WIDE_SLICE_DEFAULT = 4, 65536, 2048  # {n, P1, P2, visited} per bin of the wide GROUP BY; the bound and default slice of aqe_wide_plan
+BUDGET_MIN, BUDGET_MAX, BUDGET_MAX_GROUPS = 2, 1 << 20, 65536  # the bounds of aqe_budget_plan (the budgeted GROUP BY)
+BUDGET_SUMS, BUDGET_VARS = 5, 3  # {N, v, n, N S / v, N n / v} and {VarT, VarC, VarD} per key of the sharded budgeted GROUP BY
 TOP_MAX = 1024  # the largest LIMIT of the top-N groups (aqe_top_spec.k)
 KEYTERM_NONE, KEYTERM_RANGE, KEYTERM_BITMAP = 0, 1, 2
 KEY_BITMAP_BITS = 1024
@@ -302,6 +304,27 @@ class KeyFilter(C.Structure):
     _fields_ = [("term", KeyTerm * 2)]
 
 
+class BudgetFilter(C.Structure):
+    """aqe_budget_filter: the key terms and the amount range of a budgeted GROUP BY."""
+    _fields_ = [("keys", KeyFilter), ("has_where", C.c_int32), ("reserved0", C.c_int32), ("where_min", C.c_double), ("where_max", C.c_double)]
+
+
+class BudgetGroupResult(C.Structure):
+    """aqe_budget_group_result: ``rows`` is the group's exact size, ``visited`` the rows read, ``n`` those that pass."""
+    _fields_ = [("key", C.c_int64), ("rows", C.c_uint64), ("visited", C.c_uint64), ("n", C.c_uint64), ("sum", C.c_double), ("sumsq", C.c_double),
+                ("mean", C.c_double), ("value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class BudgetLaunchInfo(C.Structure):
+    _fields_ = [("chunk", C.c_uint32), ("blocks", C.c_uint32), ("max_range", C.c_uint32), ("fully_read", C.c_uint32), ("sampled_rows", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class TableInfo(C.Structure):
     _fields_ = [("global_rows", C.c_uint64), ("shard_lo", C.c_uint64), ("local_rows", C.c_uint64),
                 ("shift", C.c_double), ("has_aos", C.c_int32), ("device_id", C.c_int32), ("hbm_bytes", C.c_uint64),
@@ -482,6 +505,16 @@ def lib() -> C.CDLL:
         "aqe_time_groups_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, P(TimeSpec), C.c_int64, C.c_int64, i32, u32, vp, vp]),
         "aqe_time_groups_finish": (C.c_int, [vp, P(Query), C.c_int, P(TimeSpec), C.c_int64, C.c_int64, i32, u32, vp, vp, P(SeriesResult), u32, P(u32)]),
         "aqe_time_groups_from_bins": (C.c_int, [P(dbl), P(Query), dbl, P(TimeSpec), C.c_int64, C.c_int64, i32, u32, P(SeriesResult), u32, P(u32)]),
+        "aqe_group_index_build": (C.c_int, [vp, C.c_int]),
+        "aqe_group_index_info": (C.c_int, [vp, C.c_int, P(u32), P(u64), P(i32)]),
+        "aqe_reduce_grouped_budget": (C.c_int, [vp, P(BudgetFilter), C.c_int, C.c_int, C.c_int64, u64, P(BudgetGroupResult), u32, P(u32)]),
+        "aqe_grouped_budget_enqueue_sums": (C.c_int, [vp, P(BudgetFilter), C.c_int, C.c_int64, u64, i32, u32, vp, vp]),
+        "aqe_grouped_budget_variances": (C.c_int, [vp, C.c_int, i32, u32, vp, vp, vp]),
+        "aqe_grouped_budget_finish": (C.c_int, [vp, C.c_int, i32, u32, vp, vp, vp, P(BudgetGroupResult), u32, P(u32)]),
+        "aqe_budget_last_launch": (C.c_int, [vp, P(BudgetLaunchInfo)]),
+        "aqe_budget_position": (C.c_int, [u64, i32, u64, u64, u64, P(u64)]),
+        "aqe_budget_from_sums": (C.c_int, [C.c_int, P(dbl), u32, C.c_int64, P(BudgetGroupResult)]),
+        "aqe_budget_plan": (C.c_int, [u64, u64, C.c_int64]),
         "aqe_mailbox_create": (C.c_int, [vp, C.c_int, C.c_int, P(vp)]),
         "aqe_mailbox_handle": (C.c_int, [vp, vp]),
         "aqe_mailbox_connect": (C.c_int, [vp, vp]),

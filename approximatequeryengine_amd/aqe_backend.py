@@ -31,10 +31,10 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as nat
-from .engine import RECORD_DTYPE, Engine, histogram_spec, key_filter_terms, make_key_filter, make_query, time_spec, wide_plan
+from .engine import RECORD_DTYPE, Engine, histogram_spec, key_filter_terms, make_budget_filter, make_key_filter, make_query, time_spec, wide_plan
 
 __all__ = ["Record", "CustomBPlusDB", "CustomApproximateScheduler", "CustomValidationResult",
-           "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate", "SpreadEstimate", "SummaryEstimate", "BucketEstimate"]
+           "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate", "SpreadEstimate", "SummaryEstimate", "BucketEstimate", "BudgetGroupEstimate"]
 
 
 class Record:
@@ -122,6 +122,24 @@ class GroupEstimate:
 
     def __iter__(self):  # unpacks like the reference's (value, ci_lower, ci_upper)
         return iter((self.value, self.ci_lower, self.ci_upper))
+
+
+class BudgetGroupEstimate(GroupEstimate):
+    """One group of approx_group_by(per_group=K): a GroupEstimate plus ``rows``, the group's exact size in the table, and
+    ``visited``, the rows read (min(rows, K) on one GPU); ``n`` of those pass the filter.  A group read completely
+    (visited == rows) reports its exact value: ci_lower == value == ci_upper."""
+    __slots__ = ("rows", "visited")
+
+    def __init__(self, r):
+        super().__init__(r)
+        self.rows, self.visited = int(r.rows), int(r.visited)
+
+    @property
+    def fully_read(self) -> bool:
+        return self.visited == self.rows
+
+    def __repr__(self):
+        return f"BudgetGroupEstimate(value={self.value:.6g}, ci=[{self.ci_lower:.6g}, {self.ci_upper:.6g}], n={self.n}, rows={self.rows})"
 
 
 class BucketEstimate(GroupEstimate):
@@ -426,6 +444,12 @@ def group_columns(group_by) -> Tuple[int, ...]:
 def _pair_groups(results, make):
     """The mapping of a pair's results: "a,b" in the order the columns were named -> estimate, ascending by (a, b)."""
     return {"%d,%d" % nat.group_key_unpack(r.key): make(r) for r in results}
+
+
+def _budget_info(groups, index_built: bool) -> dict:
+    """last_budget_info from the listed groups: how many, the rows read over all of them, the groups read completely."""
+    return {"groups": len(groups), "sampled_rows": int(sum(int(r.visited) for r in groups)),
+            "fully_read_groups": int(sum(1 for r in groups if r.visited == r.rows)), "index_built": bool(index_built)}
 
 
 def _wide_groups_arg(max_groups, combined_with=None) -> bool:
@@ -873,7 +897,7 @@ class CustomBPlusDB:
                         where: Optional[Tuple[float, float]] = None, block_size: int = 1000,
                         key_where: Optional[dict] = None, error_percent: Optional[float] = None,
                         max_percent: float = 100.0, max_groups=_LEFT_OUT, top: Optional[int] = None,
-                        ascending: bool = False, having=None) -> "dict[str, GroupEstimate]":
+                        ascending: bool = False, having=None, per_group: Optional[int] = None, seed: int = 42) -> "dict[str, GroupEstimate]":
         """APPROX <agg>(amount) ... GROUP BY region | product_id with a 95 % interval per group: the reference's
         execute_query_groupby_with_ci (executor.cpp:202-321; GroupResultWithCI = map<string, {value, ci_lower,
         ci_upper}>) in one sweep.  method "rowid" is that function's own sample (rowid % (100 / sample_percent) == 0);
@@ -906,7 +930,20 @@ class CustomBPlusDB:
         (``last_top_info`` then counts passing groups only).  Without ``max_groups`` the bound on the passing groups is the
         65 536 the sweep accepts.  ``last_having_info`` keeps groups, candidates, passed, passed_unsettled (passing groups whose
         interval reaches across a threshold) and failed_unsettled (groups left out that could pass within their interval); a
-        COUNT term has no interval and is always settled.  It does not combine with ``error_percent``."""
+        COUNT term has no interval and is always settled.  It does not combine with ``error_percent``.
+
+        ``per_group`` = K (2 .. 2^20): the budgeted GROUP BY (aqe_reduce_grouped_budget) — a sample stratified on the key
+        column instead of a uniform one: every occurring key is listed, a group of at most K rows is read completely and
+        reports its exact value, a larger one is sampled K times from the seeded start ``seed``.  SUM / AVG / COUNT over one
+        column, with ``where`` and ``key_where`` (a term on the grouped column included); the mapping holds
+        BudgetGroupEstimate, whose ``rows`` is the group's exact size.  ``last_budget_info`` keeps {groups, sampled_rows,
+        fully_read_groups, index_built}.  It does not combine with ``sample_percent``, ``method``, ``error_percent``,
+        ``max_groups``, ``top``, ``having`` or a column pair."""
+        if per_group is not None:
+            return self._group_by_budget(agg, group_by, per_group, seed, where, key_where,
+                                         {"sample_percent": sample_percent is not None, "method": method is not None,
+                                          "error_percent": error_percent is not None, "max_groups": max_groups is not _LEFT_OUT,
+                                          "top": top is not None, "having": having is not None})
         cols = group_columns(group_by)
         col = cols[0]
         if having is not None and error_percent is not None:
@@ -956,6 +993,37 @@ class CustomBPlusDB:
             f = _key_filter_for(key_where, method)
             return {str(r.key): GroupEstimate(r) for r in _quantile_call(lambda: self._grouped_filtered(f, q, col))}
         return {str(r.key): GroupEstimate(r) for r in self._grouped(q, col)}
+
+    last_budget_info: Optional[dict] = None  # of the most recent approx_group_by(per_group=...)
+
+    def _group_by_budget(self, agg, group_by, per_group, seed, where, key_where, given):
+        """approx_group_by(per_group=...): the argument checks (before any table is needed), the call, the info."""
+        for name, is_given in given.items():
+            if is_given:
+                raise ValueError(f"per_group with {name}: the budgeted GROUP BY reads a fixed number of rows per group from its own "
+                                 f"stratified sample (leave {name} out)")
+        cols = group_columns(group_by)
+        if len(cols) == 2:
+            raise ValueError("per_group with a column pair: the budgeted GROUP BY takes one key column (region or product_id)")
+        a = agg.upper()
+        if a not in _AGG:
+            raise ValueError(f"GROUP BY with per_group takes SUM, AVG or COUNT, not {agg!r}")
+        if isinstance(per_group, bool) or not isinstance(per_group, (int, np.integer)) or not nat.BUDGET_MIN <= int(per_group) <= nat.BUDGET_MAX:
+            raise ValueError(f"per_group={per_group!r} is not an integer in {nat.BUDGET_MIN} .. {nat.BUDGET_MAX}")
+        kf = None if key_where is None else make_key_filter(key_where)
+        bf = make_budget_filter(where, kf)
+        self.last_budget_info = None
+        if self._table_missing():
+            return {}
+        groups, info = _quantile_call(lambda: self._grouped_budget(bf, _AGG[a], cols[0], int(per_group), int(seed)))
+        self.last_budget_info = info
+        return {str(r.key): BudgetGroupEstimate(r) for r in groups}
+
+    def _grouped_budget(self, bf, agg, col, per_group, seed):
+        """(list of BudgetGroupResult ascending, the info dictionary) of one budgeted GROUP BY."""
+        eng = self._eng()
+        groups = eng.reduce_grouped_budget(agg, col, per_group, seed, bf)
+        return groups, _budget_info(groups, eng.group_index_info(col)["built_now"])
 
     def _table_missing(self) -> bool:
         """No row to group: approx_group_by then answers {} (a backend for which that is an error raises here instead)."""

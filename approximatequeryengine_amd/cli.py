@@ -370,6 +370,38 @@ def max_groups_defect(clean: str, args):
     return None
 
 
+def per_group_defect(full: str, args) -> Optional[str]:
+    """What keeps a query given --per-group from running, found before the table is opened (None: nothing, or no --per-group): a
+    budget outside 2 .. 1048576, --s, --e, --max-groups, an aggregate other than SUM / AVG / COUNT, a time bucket, HAVING,
+    ORDER BY ... LIMIT, no GROUP BY or two columns — the budgeted GROUP BY reads its own stratified sample of one key column."""
+    k = getattr(args, "per_group", None)
+    if k is None:
+        return None
+    if not 2 <= k <= 1 << 20:
+        return f"--per-group {k}: the budget is an integer in 2 .. 1048576 rows per group"
+    for opt, given in (("--s", args.s is not None), ("--e", args.e is not None), ("--max-groups", getattr(args, "max_groups", None) is not None)):
+        if given:
+            return f"--per-group with {opt}: the budgeted GROUP BY reads a fixed number of rows per group from its own stratified sample (leave {opt} out)"
+    if re.search(r"\b(VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?)\s*\(", full, re.IGNORECASE):
+        return "--per-group has no VARIANCE / STDDEV form: the budgeted GROUP BY takes SUM, AVG or COUNT"
+    if re.search(r"\b(MIN|MAX)\s*\(", full, re.IGNORECASE):
+        return "--per-group has no MIN / MAX form: the budgeted GROUP BY takes SUM, AVG or COUNT"
+    if re.search(r"BUCKET\s*\(", full, flags=re.IGNORECASE):
+        return "--per-group has no GROUP BY BUCKET(...) form: the budget is per key of region or product_id"
+    if re.search(r"\bHAVING\b", full, re.IGNORECASE):
+        return "--per-group has no HAVING form"
+    if re.search(r"\bORDER\s+BY\b.*\bLIMIT\b", full, re.IGNORECASE | re.DOTALL):
+        return "--per-group has no ORDER BY ... LIMIT form"
+    if not re.search(r"\b(SUM|AVG|COUNT)\s*\(", full, re.IGNORECASE):
+        return "--per-group takes SUM, AVG or COUNT ... GROUP BY region | product_id"
+    gb = group_by_of(full)
+    if not gb:
+        return "--per-group needs GROUP BY region | product_id"
+    if len(gb) != 1:
+        return "--per-group with two columns: the budgeted GROUP BY takes one key column (region or product_id)"
+    return None
+
+
 _TOP_CLAUSE = re.compile(r"\bORDER\s+BY\s+(SUM|AVG|COUNT)\s*\(\s*(\*|amount)\s*\)\s*(ASC|DESC)?\s*\bLIMIT\s+([+-]?\d+)\s*;?\s*$", re.IGNORECASE)
 
 
@@ -498,6 +530,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--max-groups", dest="max_groups", type=int, metavar="N", help="SUM / AVG / COUNT ... GROUP BY over key ranges of up to N groups "
                    "(above 1024, at most 65536: the sliced sweep); without it GROUP BY stops at 1024 groups")
+    p.add_argument("--per-group", dest="per_group", type=int, metavar="K", help="SUM / AVG / COUNT ... GROUP BY region | product_id from at most K rows "
+                   "of every group (2 .. 1048576): every key is listed, a group of at most K rows exactly")
     p.add_argument("--all-groups", dest="all_groups", action="store_true", help="with --max-groups: print every group (default: the first 50 and a count of the rest)")
     p.add_argument("--series-by", dest="series_by", metavar="COLUMN", help="with GROUP BY BUCKET(timestamp, W): one time series per key of COLUMN "
                    "(region or product_id), from one sweep; at most 65536 cells (keys x buckets)")
@@ -519,7 +553,7 @@ def run(args, out=sys.stdout) -> int:
         print("error: a query is required unless --explain is given", file=out)
         return 2
     clean, _ = parse_embedded_approx(args.query)
-    why = distinct_by_defect(clean, args)
+    why = per_group_defect(clean, args) or distinct_by_defect(clean, args)
     if why is not None:
         print(f"error: {why}", file=out)
         return 2
@@ -704,6 +738,22 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     if summary_of(clean) is not None:
         return _run_summary(db, args, out, clean, qtype, aqe_backend, t0, kw)
     gb = group_by_of(clean)
+    if gb and getattr(args, "per_group", None) is not None:
+        # --per-group K: a sample stratified on the key column, at most K rows of every group (aqe_reduce_grouped_budget)
+        groups = db.approx_group_by(agg, group_by=gb[0], per_group=int(args.per_group), seed=args.seed, where=aqe_backend.parse_where(clean), **kw)
+        ms = (time.perf_counter() - t0) * 1e3
+        info = db.last_budget_info or {"groups": len(groups), "fully_read_groups": 0, "sampled_rows": 0}
+        print(f"\nGROUP BY {gb[0].lower()} (at most {args.per_group:,} rows per group):", file=out)
+        shown = len(groups) if getattr(args, "all_groups", False) else MAX_GROUPS_SHOWN
+        for i, (key, g) in enumerate(groups.items()):
+            if i >= shown:
+                print(f"   ... and {len(groups) - shown:,} more groups ({len(groups):,} in all; --all-groups prints every one)", file=out)
+                break
+            print(f"   {key:>6}: {g.value:,.4f}   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})   n={g.n:,}   rows={g.rows:,}", file=out)
+        print(f"   {info['groups']:,} groups, {info['fully_read_groups']:,} read completely, {info['sampled_rows']:,} rows sampled", file=out)
+        print(f"   execution time: {ms:.2f} ms", file=out)
+        db.close_database()
+        return 0
     if gb and group_error_form(clean, args):
         # --e with GROUP BY: nested block levels until every group's interval is within the threshold (aqe_reduce_grouped_error)
         groups = db.approx_group_by(agg, group_by=", ".join(gb), where=aqe_backend.parse_where(clean), error_percent=float(args.e), **kw)

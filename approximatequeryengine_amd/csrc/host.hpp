@@ -106,6 +106,18 @@ struct aqe_summary_scratch;  // summary.hip
 struct aqe_time_scratch;  // timeseries.hip
 struct aqe_wide_scratch;  // wide_group.hip
 struct aqe_series_scratch;  // time_group.hip
+struct aqe_budget_scratch;  // budget_group.hip
+
+// The rows of one key column sorted by key (group_index.hip): what the budgeted GROUP BY sweeps.  The host mirrors of the
+// listed keys and segment offsets (at most 65 536 + 1 entries) are what a call plans its launch from.
+struct aqe_group_index {
+    uint32_t* perm = nullptr;     // [n_local] rows, by key then ascending
+    int32_t* keys = nullptr;      // [L] the occurring keys, ascending
+    uint32_t* seg_off = nullptr;  // [L + 1]
+    std::vector<int32_t> h_keys;
+    std::vector<uint32_t> h_seg;
+    uint64_t bytes = 0;           // HBM held, part of hbm_bytes
+};
 
 struct aqe_ctx {
     StageRing ring;
@@ -187,6 +199,11 @@ struct aqe_ctx {
     aqe_wide_scratch* wide = nullptr;
     // per-key time series (time_group.hip): the slices' partials, the summed bins and the cell list, made on first use
     aqe_series_scratch* series = nullptr;
+    // budgeted GROUP BY: the group index per key column (group_index.hip; goes with the table) and the sweep's scratch
+    // (budget_group.hip; goes with the context)
+    aqe_group_index* gindex[2] = {nullptr, nullptr};  // [AQE_GROUP_REGION - 1], [AQE_GROUP_PRODUCT - 1]
+    bool gindex_built_now[2] = {false, false};        // the most recent call that needed the index built it
+    aqe_budget_scratch* budget = nullptr;
     // diagnostics (aqe_last_load_policy): the instantiation the most recent launch of a visit_tile kernel was — 1 non-temporal,
     // 0 plain loads, -1 no such launch yet.  Index-list sweeps and the quantile pass have the plain one only.
     int last_nt = -1;
@@ -388,6 +405,13 @@ void wide_release(aqe_ctx* c);
 
 // time_group.hip
 void series_release(aqe_ctx* c);
+
+// group_index.hip
+int ensure_group_index(aqe_ctx* c, int column);  // builds c->gindex[column - 1] on first use; sets gindex_built_now
+void group_index_release(aqe_ctx* c);            // both columns' indexes (the table changed)
+
+// budget_group.hip
+void budget_release(aqe_ctx* c);
 
 // plans.hip
 void destroy_plan(aqe_plan* p, bool device_idle = false);  // device_idle: the caller has just synchronised the device

@@ -43,6 +43,7 @@ void destroy_plan(aqe_plan* p, bool device_idle) {
 void drop_cache(aqe_ctx* c) {
     for (auto& kv : c->cache) destroy_plan(kv.second);
     c->cache.clear();
+    group_index_release(c);  // (whatever invalidates the plans may have changed what the index was built from)
 }
 
 namespace {

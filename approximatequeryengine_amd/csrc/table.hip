@@ -48,6 +48,7 @@ void free_table(aqe_ctx* c) {
     }
     if (c->sorted_amount) (void)hipFree(c->sorted_amount);
     if (c->sorted_row) (void)hipFree(c->sorted_row);
+    group_index_release(c);
     for (int k = 0; k < 3; ++k) {
         if (c->keycol[k]) (void)hipFree(c->keycol[k]);
         c->keycol[k] = nullptr;
@@ -582,6 +583,7 @@ void aqe_destroy(aqe_ctx* c) {
     timeseries_release(c);
     wide_release(c);
     series_release(c);
+    budget_release(c);
     free_table(c);
     free_ring(c);
     if (c->d_stamps) (void)hipFree(c->d_stamps);

@@ -491,6 +491,35 @@ def sharded_group_by_wide(engine, query, columns, bins, all_reduce_sum: Callable
         return engine.grouped_wide_finish(query, kmin, span, b.data_ptr(), stream, max_groups)
 
 
+def sharded_group_by_budget(engine, agg: int, column: int, budget: int, seed: int, buf, all_reduce_sum: Callable, all_reduce_max: Callable,
+                            stream: int = 0, budget_filter=None, max_groups: int = 65536):
+    """The budgeted GROUP BY across ranks, collective: a shard's segment of a group is a stratum of its own, with the budget
+    ``budget`` per (group, shard).  ONE MAX all-reduce of [-min, max] of the key column; every rank's strata as
+    span x BUDGET_SUMS doubles {N, v, n, N S / v, N n / v} (aqe_grouped_budget_enqueue_sums), ONE all-reduce SUM — which gives
+    every rank the totals T̂ and Ĉ of every key; every rank's share of the variances, AVG's around R = T̂ / Ĉ, as
+    span x BUDGET_VARS doubles (aqe_grouped_budget_variances), ONE all-reduce SUM; then every rank finishes the same vectors
+    and returns the same list of BudgetGroupResult.  A span of more than 65 536 keys is refused on every rank alike, before
+    the sweep; an empty table gives [].
+
+    buf     float64 tensor on the engine's device with room for (BUDGET_SUMS + BUDGET_VARS) * span doubles
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    from ._native import BUDGET_MAX_GROUPS, BUDGET_SUMS, BUDGET_VARS, ERR_UNSUPPORTED, AqeError
+    with _on_stream(stream, buf) as stream:
+        agreed = _agree_keys(engine, [int(column)], buf, all_reduce_max)
+        if agreed is None:
+            return []  # an empty table
+        kmin, span = agreed[0][0], agreed[1][0] - agreed[0][0] + 1
+        if span > BUDGET_MAX_GROUPS:
+            raise AqeError(ERR_UNSUPPORTED, f"GROUP BY (budgeted): the group column spans {span} keys over the shards, more than {BUDGET_MAX_GROUPS} bins")
+        b = _take(buf, (BUDGET_SUMS + BUDGET_VARS) * span)
+        sums, var = b[: BUDGET_SUMS * span], b[BUDGET_SUMS * span:]
+        engine.grouped_budget_enqueue_sums(column, budget, seed, kmin, span, sums.data_ptr(), stream, budget_filter)
+        all_reduce_sum(sums)
+        engine.grouped_budget_variances(column, kmin, span, sums.data_ptr(), var.data_ptr(), stream)
+        all_reduce_sum(var)
+        return engine.grouped_budget_finish(agg, kmin, span, sums.data_ptr(), var.data_ptr(), stream, max_groups)
+
+
 def sharded_group_by_top(engine, query, columns, bins, all_reduce_sum: Callable, all_reduce_max: Callable, k: int, descending: bool = True,
                          stream: int = 0, key_filter=None):
     """ORDER BY the aggregate LIMIT ``k`` over a GROUP BY across ranks, collective: sharded_group_by_wide's steps unchanged — ONE

@@ -612,6 +612,51 @@ class Engine:
                                                     C.c_void_p(dev_bins_ptr), C.c_void_p(stream), out, max_groups, C.byref(n)))
         return list((nat.GroupResult * n.value).from_buffer_copy(out)) if n.value else []
 
+    # -- budgeted GROUP BY (aqe_reduce_grouped_budget and its kin): a per-group row budget over the group index --
+    def group_index_build(self, column: int):
+        self._chk(nat.lib().aqe_group_index_build(self._h, int(column)))
+
+    def group_index_info(self, column: int) -> dict:
+        """{groups, bytes, built_now} of the group index of ``column`` (zeros before it exists)."""
+        n, b, now = C.c_uint32(), C.c_uint64(), C.c_int32()
+        self._chk(nat.lib().aqe_group_index_info(self._h, int(column), C.byref(n), C.byref(b), C.byref(now)))
+        return {"groups": n.value, "bytes": b.value, "built_now": bool(now.value)}
+
+    def reduce_grouped_budget(self, agg: int, column: int, budget: int, seed: int = 42, budget_filter: "Optional[nat.BudgetFilter]" = None,
+                              max_groups: int = nat.BUDGET_MAX_GROUPS):
+        """SUM / AVG / COUNT per occurring key of ``column`` from at most ``budget`` rows of every group: list of
+        BudgetGroupResult ascending by key.  More groups than ``max_groups`` is AqeError(ERR_INVALID) with the count."""
+        out = (nat.BudgetGroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_reduce_grouped_budget(self._h, _filter_ref(budget_filter), int(agg), int(column), _budget_int(budget), int(seed) & _U64, out,
+                                                      max_groups, C.byref(n)))
+        return list((nat.BudgetGroupResult * n.value).from_buffer_copy(out)) if n.value else []
+
+    def grouped_budget_enqueue_sums(self, column: int, budget: int, seed: int, key_min: int, span: int, dev_vec_ptr: int, stream: int = 0,
+                                    budget_filter: "Optional[nat.BudgetFilter]" = None):
+        """This shard's span x BUDGET_SUMS doubles {N, v, n, N S / v, N n / v} into device memory (all-reduce SUM next)."""
+        self._chk(nat.lib().aqe_grouped_budget_enqueue_sums(self._h, _filter_ref(budget_filter), int(column), _budget_int(budget), int(seed) & _U64,
+                                                            int(key_min), int(span), C.c_void_p(dev_vec_ptr), C.c_void_p(stream)))
+
+    def grouped_budget_variances(self, column: int, key_min: int, span: int, dev_vec_ptr: int, dev_var_ptr: int, stream: int = 0):
+        """This shard's span x BUDGET_VARS doubles {VarT, VarC, VarD} from the all-reduced sums (all-reduce SUM next)."""
+        self._chk(nat.lib().aqe_grouped_budget_variances(self._h, int(column), int(key_min), int(span), C.c_void_p(dev_vec_ptr), C.c_void_p(dev_var_ptr),
+                                                         C.c_void_p(stream)))
+
+    def grouped_budget_finish(self, agg: int, key_min: int, span: int, dev_vec_ptr: int, dev_var_ptr: int, stream: int = 0,
+                              max_groups: int = nat.BUDGET_MAX_GROUPS):
+        out = (nat.BudgetGroupResult * max_groups)()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_grouped_budget_finish(self._h, int(agg), int(key_min), int(span), C.c_void_p(dev_vec_ptr), C.c_void_p(dev_var_ptr),
+                                                      C.c_void_p(stream), out, max_groups, C.byref(n)))
+        return list((nat.BudgetGroupResult * n.value).from_buffer_copy(out)) if n.value else []
+
+    def budget_last_launch(self) -> dict:
+        """Diagnostics of the most recent budgeted sweep: chunk, blocks, max_range, fully_read, sampled_rows."""
+        info = nat.BudgetLaunchInfo()
+        self._chk(nat.lib().aqe_budget_last_launch(self._h, C.byref(info)))
+        return info.as_dict()
+
     # -- top-N groups (aqe_reduce_grouped_top / aqe_grouped_top_finish): ORDER BY the aggregate, LIMIT k, selected on the device --
     def reduce_grouped_top(self, query: Query, columns: Sequence[int], k: int, descending: bool = True, key_filter: "Optional[nat.KeyFilter]" = None):
         """The ``k`` (1 .. nat.TOP_MAX) best groups of ``columns`` (one column, or the ordered pair; any span up to 65 536 bins) by
@@ -1402,6 +1447,49 @@ def _two(values, fill):
 
 def _filter_ref(key_filter):
     return None if key_filter is None else C.byref(key_filter)
+
+
+_U64 = (1 << 64) - 1
+
+
+def _budget_int(budget) -> int:
+    """The per-group budget as the C ABI takes it (an int64, so that a value out of range reaches the library's refusal)."""
+    b = int(budget)
+    if b != budget:
+        raise ValueError(f"per_group={budget!r} is not an integer")
+    return max(-(1 << 63), min(b, (1 << 63) - 1))
+
+
+def make_budget_filter(where: Optional[Tuple[float, float]] = None, key_filter: "Optional[nat.KeyFilter]" = None) -> "Optional[nat.BudgetFilter]":
+    """aqe_budget_filter from an amount range and a compiled key filter; None when there is neither."""
+    if where is None and key_filter is None:
+        return None
+    f = nat.BudgetFilter()
+    if key_filter is not None:
+        C.memmove(C.byref(f.keys), C.byref(key_filter), C.sizeof(nat.KeyFilter))
+    if where is not None:
+        f.has_where, f.where_min, f.where_max = 1, float(where[0]), float(where[1])
+    return f
+
+
+def budget_position(seed: int, key: int, rows: int, take: int, j: int) -> int:
+    """aqe_budget_position (host only): pos_j of a group of ``rows`` rows under (seed, key) that takes ``take`` of them."""
+    pos = C.c_uint64()
+    nat.check(nat.lib().aqe_budget_position(int(seed) & _U64, int(key), int(rows), int(take), int(j), C.byref(pos)))
+    return pos.value
+
+
+def budget_from_sums(agg: int, strata, key: int = 0) -> "nat.BudgetGroupResult":
+    """aqe_budget_from_sums (host only): one group from its strata, rows of {N, v, n, S, Q}."""
+    v = np.ascontiguousarray(np.asarray(strata, dtype=np.float64).reshape(-1, 5))
+    out = nat.BudgetGroupResult()
+    nat.check(nat.lib().aqe_budget_from_sums(int(agg), v.ctypes.data_as(C.POINTER(C.c_double)), len(v), int(key), C.byref(out)))
+    return out
+
+
+def budget_plan(local_rows: int, ngroups: int, budget: int) -> None:
+    """aqe_budget_plan (host only): raises AqeError with the library's text for a table or budget out of bounds."""
+    nat.check(nat.lib().aqe_budget_plan(int(local_rows), int(ngroups), _budget_int(budget)))
 
 
 def make_query(method: int, sample_percent: float = 10.0, agg: int = nat.SUM, convention: int = nat.EST_CLI,

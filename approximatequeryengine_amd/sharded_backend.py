@@ -29,7 +29,7 @@ import torch.distributed as dist
 from . import _native as nat
 from .aqe_backend import ApproxResult, CustomBPlusDB
 from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, mailbox_all_reduce, mailbox_from_torch_group, shard_bounds, sharded_adaptive_plan,
-                          sharded_distinct, sharded_distinct_groups, sharded_extremes, sharded_filtered, sharded_filtered_group_by, sharded_group_by, sharded_group_by_error,
+                          sharded_distinct, sharded_distinct_groups, sharded_extremes, sharded_filtered, sharded_filtered_group_by, sharded_group_by, sharded_group_by_budget, sharded_group_by_error,
                           sharded_group_by_having, sharded_group_by_pair, sharded_group_by_spread, sharded_group_by_top, sharded_group_by_wide,
                           sharded_group_extremes, sharded_histogram, sharded_quantiles, sharded_spread, sharded_stratified_plan, sharded_summary,
                           sharded_time_groups, sharded_time_series, torch_all_reduce, torch_host_all_reduce)
@@ -308,6 +308,14 @@ class ShardedBPlusDB(CustomBPlusDB):
 
     def _grouped_having(self, f, q, cols, having, k, descending, max_groups):
         return self._sharded(sharded_group_by_having, None, q, cols, having=having, k=k, descending=descending, key_filter=f, max_groups=max_groups)
+
+    # budgeted GROUP BY (per_group=K): one MAX all-reduce of the key range, one all-reduce SUM of span x 5 sums, one of span x 3
+    # variances; a shard's segment of a group is a stratum with the budget K of its own
+    def _grouped_budget(self, bf, agg, col, per_group, seed):
+        from .aqe_backend import _budget_info
+        need = (nat.BUDGET_SUMS + nat.BUDGET_VARS) * nat.BUDGET_MAX_GROUPS
+        groups = self._sharded(sharded_group_by_budget, need, agg, col, per_group, seed, budget_filter=bf)
+        return groups, _budget_info(groups, self._engine.group_index_info(col)["built_now"])
 
     # MIN / MAX: one all-reduce SUM of the counts, one all-reduce MAX of {-min, max} (grouped: of each half of the bins)
     def _extremes(self, f, q):

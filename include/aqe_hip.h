@@ -1518,6 +1518,86 @@ AQE_API int aqe_time_groups_finish(aqe_ctx* ctx, const aqe_query* q, int group_c
 AQE_API int aqe_time_groups_from_bins(const double* bins, const aqe_query* q, double shift, const aqe_time_spec* spec, int64_t tmin, int64_t tmax,
                                       int32_t key_min, uint32_t span, aqe_series_result* out, uint32_t cap, uint32_t* n_groups);
 
+/* ---- Budgeted GROUP BY: a per-group row budget, a sample stratified on the key (group_index.hip, budget_group.hip,
+ * budget_core.hpp) ------------------------------------------------------------------------------------------------
+ * Every occurring key of `column` (AQE_GROUP_REGION or AQE_GROUP_PRODUCT) is a stratum with the same budget K: a group of
+ * N <= K rows is read completely and its figures are exact (ci_lower == value == ci_upper); a larger one is sampled K times.
+ * COUNT per group is Ĉ = N n / v — without a filter exactly N — and every aggregate carries an interval.
+ *
+ * Group index.  Per table and key column, built on first use (or by aqe_group_index_build) and kept until the table
+ * changes: the rows sorted by key (stable: ascending inside a group) as perm[local_rows] (uint32), the occurring keys
+ * ascending and seg_off[L + 1].  Refused by name before any launch: more than 2^32 - 1 local rows, more than 65 536 occurring
+ * keys (AQE_ERR_UNSUPPORTED with the count), a table without key columns (ensure_keys' message).  Counted in hbm_bytes.
+ *
+ * Design.  Group g takes n_g = min(N_g, K) rows at positions pos_j = (j N_g + r_g) / n_g of its segment (64-bit integer
+ * division), r_g = mix64(seed, key) mod N_g; aqe_budget_position restates it.  K is an integer in 2 .. 2^20, anything else
+ * AQE_ERR_INVALID naming the value.
+ *
+ * Filter.  The amount range (inclusive both ends; a NaN amount never passes, with or without a range) and the key terms of
+ * an aqe_key_filter; a term on the grouped column is allowed.  Filtered rows count in `visited`, not in `n`.
+ *
+ * Finish.  One formula, single GPU and sharded; a stratum is (group, shard) with N rows, v visited, n passing, S and Q the
+ * sum and sum of squares of the passing amounts: T̂ = Σ N S / v, Ĉ = Σ N n / v; SUM = T̂, COUNT = Ĉ, AVG = R = T̂ / Ĉ.
+ * Variance by linearisation over a stratum's visited rows, d = y pass (SUM), pass (COUNT), (y - R) pass (AVG):
+ * s² = (Σd² - (Σd)² / v) / (v - 1), Var = Σ N² (1 - v / N) s² / v, AVG's divided by Ĉ²; margin 1.96 √Var.  A stratum with
+ * v == N adds zero.  AVG with Ĉ == 0 is NaN (interval ends included); AVG with one passing row in all and some v < N has the
+ * interval (-inf, +inf).  These intervals are NOT those of aqe_reduce_grouped (which follows the reference's executor).
+ *
+ * Results: every occurring key, ascending.  cap below their number is AQE_ERR_INVALID with the count in the message and in
+ * *n_out; no partial list.  visited and n are exact integers, the same on every run of the same query. */
+typedef struct aqe_budget_filter {
+    aqe_key_filter keys;   /* forms AQE_KEYTERM_NONE: no key term */
+    int32_t has_where;     /* 1: keep where_min <= amount <= where_max */
+    int32_t reserved0;
+    double where_min, where_max;
+} aqe_budget_filter;
+typedef struct aqe_budget_group_result {
+    int64_t key;
+    uint64_t rows;    /* N: the group's rows in the table — exact                              */
+    uint64_t visited; /* rows read: min(N, K) (sharded: summed over the shards)                */
+    uint64_t n;       /* ... of which pass the filter                                          */
+    double sum, sumsq; /* S, Q over the passing rows read (sharded entries: NaN — the shards' raw sums are not merged) */
+    double mean;      /* R = T̂ / Ĉ (NaN when Ĉ == 0)                                          */
+    double value, ci_lower, ci_upper;
+} aqe_budget_group_result;
+AQE_API int aqe_group_index_build(aqe_ctx* ctx, int column);
+/* ngroups: occurring keys; bytes: HBM the index holds; built_now: 1 when the most recent call that needed the index
+ * (aqe_group_index_build or a budgeted entry) built it, 0 when it found it.  No index yet: AQE_OK with zeros. */
+AQE_API int aqe_group_index_info(aqe_ctx* ctx, int column, uint32_t* ngroups, uint64_t* bytes, int32_t* built_now);
+AQE_API int aqe_reduce_grouped_budget(aqe_ctx* ctx, const aqe_budget_filter* filter /* NULL: none */, int agg, int column, int64_t budget, uint64_t seed,
+                                      aqe_budget_group_result* out, uint32_t cap, uint32_t* n_out);
+/* Multi-GPU.  A shard's segment of a group is a stratum of its own, so the all-reduced vector must carry T̂ and Ĉ themselves:
+ *     aqe_group_key_range(ctx, column, &kmin, &kmax)                       all-reduce MIN / MAX; span = kmax - kmin + 1 <= 65 536
+ *     aqe_grouped_budget_enqueue_sums(ctx, filter, column, budget, seed, key_min, span, dev_vec, stream)
+ *                                                  [span][5] doubles {N, v, n, N S / v, N n / v} of this shard (zeros: key not here)
+ *     <ONE all-reduce SUM of span * 5 doubles on `stream`>                 -> {rows, visited, n, T̂, Ĉ} per key
+ *     aqe_grouped_budget_variances(ctx, column, key_min, span, dev_vec, dev_var, stream)
+ *                                                  [span][3] doubles {VarT, VarC, VarD} of this shard's strata, VarD with R = T̂ / Ĉ
+ *     <ONE all-reduce SUM of span * 3 doubles on `stream`>
+ *     aqe_grouped_budget_finish(ctx, agg, key_min, span, dev_vec, dev_var, stream, out, cap, &n_out)     synchronises `stream`
+ * Every rank lists the same groups.  aqe_grouped_budget_variances uses the sums its context kept from the enqueue_sums call
+ * before it (same column, same stream).  A span above 65 536 or keys outside it: AQE_ERR_UNSUPPORTED / AQE_ERR_INVALID. */
+AQE_API int aqe_grouped_budget_enqueue_sums(aqe_ctx* ctx, const aqe_budget_filter* filter, int column, int64_t budget, uint64_t seed, int32_t key_min,
+                                            uint32_t span, double* dev_vec, void* stream);
+AQE_API int aqe_grouped_budget_variances(aqe_ctx* ctx, int column, int32_t key_min, uint32_t span, const double* dev_vec, double* dev_var, void* stream);
+AQE_API int aqe_grouped_budget_finish(aqe_ctx* ctx, int agg, int32_t key_min, uint32_t span, const double* dev_vec, const double* dev_var, void* stream,
+                                      aqe_budget_group_result* out, uint32_t cap, uint32_t* n_out);
+/* Diagnostics: the most recent budgeted sweep of this context — sample ordinals per workgroup, workgroups, the most groups one
+ * workgroup touched, groups read completely, sampled rows. */
+typedef struct aqe_budget_launch_info {
+    uint32_t chunk, blocks, max_range, fully_read;
+    uint64_t sampled_rows;
+} aqe_budget_launch_info;
+AQE_API int aqe_budget_last_launch(const aqe_ctx* ctx, aqe_budget_launch_info* out);
+/* Host only, no GPU and no context (aqe_last_error(NULL) has a refusal's text).
+ * aqe_budget_position: pos_j of a group of `rows` rows under (seed, key) that takes `take` = min(rows, K) of them.
+ * aqe_budget_from_sums: one group from its strata, strata[nstrata][5] = {N, v, n, S, Q} with the RAW sums; rows, visited, n,
+ * sum and sumsq of `out` are the totals over the strata.
+ * aqe_budget_plan: the bounds — local_rows <= 2^32 - 1, ngroups <= 65 536 (AQE_ERR_UNSUPPORTED), budget in 2 .. 2^20 (AQE_ERR_INVALID). */
+AQE_API int aqe_budget_position(uint64_t seed, int32_t key, uint64_t rows, uint64_t take, uint64_t j, uint64_t* pos);
+AQE_API int aqe_budget_from_sums(int agg, const double* strata, uint32_t nstrata, int64_t key, aqe_budget_group_result* out);
+AQE_API int aqe_budget_plan(uint64_t local_rows, uint64_t ngroups, int64_t budget);
+
 #ifdef __cplusplus
 }
 #endif
