@@ -325,6 +325,19 @@ class BudgetLaunchInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+UNION_FORMED, UNION_MAX_ROWS, UNION_MAX_PIECES, UNION_MAX_INCIDENCES, UNION_MAX_TILES_PER_WG, UNION_WG_PIECES, UNION_MAX_ENTRIES = range(7)
+
+
+class UnionShape(C.Structure):
+    _fields_ = [("declined_by", C.c_uint32), ("candidates", C.c_uint32), ("classes", C.c_uint32), ("workgroups", C.c_uint32),
+                ("rows", C.c_uint32), ("pieces", C.c_uint32), ("incidences", C.c_uint32), ("tiles", C.c_uint32),
+                ("tiles_per_wg", C.c_uint32), ("whole_tiles", C.c_uint32), ("masked_tiles", C.c_uint32), ("two_piece_tiles", C.c_uint32),
+                ("max_share_pieces", C.c_uint32), ("entries", C.c_uint32), ("slots", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class TableInfo(C.Structure):
     _fields_ = [("global_rows", C.c_uint64), ("shard_lo", C.c_uint64), ("local_rows", C.c_uint64),
                 ("shift", C.c_double), ("has_aos", C.c_int32), ("device_id", C.c_int32), ("hbm_bytes", C.c_uint64),
@@ -549,6 +562,7 @@ def lib() -> C.CDLL:
         "aqe_batch_launch_info": (C.c_int, [vp, P(C.c_float), P(u64), P(u32)]),
         "aqe_batch_share_info": (C.c_int, [vp, P(u32), P(u64)]),
         "aqe_batch_union_info": (C.c_int, [vp, P(u32), P(u64)]),
+        "aqe_batch_union_shape": (C.c_int, [vp, u32, P(UnionShape)]),
         "aqe_comm_unique_id": (C.c_int, [vp]),
         "aqe_comm_create": (C.c_int, [vp, vp, C.c_int, C.c_int, P(vp)]),
         "aqe_comm_create_all": (C.c_int, [P(vp), C.c_int, P(vp)]),

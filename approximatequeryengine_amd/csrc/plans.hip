@@ -1126,6 +1126,7 @@ struct BatchMulti {
     uint64_t rows_loaded = 0;              // rows the classes sweep (each class's rows once)
     std::vector<void*> unions;             // lean: the union groups' device blocks (build_union)
     uint64_t union_rows = 0;               // rows the launch loads (a union group's slots once, every other class's rows)
+    std::vector<aqe_union_shape> union_shapes;  // what build_union counted: the union groups in launch order, then the declined sets
     bool nt = false;                       // the launch's loads go past the caches (build_multi)
     const double* totals = nullptr;        // kind 1: the buffer the descriptors were written for
     uint64_t stride = 0;
@@ -1157,6 +1158,7 @@ void free_multi(BatchMulti& m) {
     if (m.d_wgmap) (void)hipFree(m.d_wgmap);
     for (void* u : m.unions) (void)hipFree(u);
     m.unions.clear();
+    m.union_shapes.clear();
     m.d_ltable = nullptr;
     m.lean = false;
     m.d_table = nullptr;
@@ -1254,13 +1256,15 @@ int sweep_classes(aqe_batch* b, int kind, const std::vector<char>& head, const s
 // form of each sweep class of the group (full forms of plain runs, one view, one shift and WHERE); `G`: the group's
 // workgroups.  Classes whose runs are the same (AQE_BATCH_SHARE=0 leaves one class per plan) share their rows of round
 // totals: `class_row` gets each class's first row.  Leaves `d_block` null (and returns AQE_OK) when the group exceeds a
-// bound of the kernel's fold — it then does not form, and its classes run as they are.
+// bound of the kernel's fold — it then does not form, and its classes run as they are.  `shape` (aqe_batch_union_shape):
+// what was counted on the way, and the bound that declined the group if one did.
 struct UnionBuilt {
     void* d_block = nullptr;
     uint32_t ntiles = 0, tiles_per_wg = 0;
     double* d_partials = nullptr;
     uint64_t slots = 0;
     std::vector<uint32_t> class_row;
+    aqe_union_shape shape{};
 };
 
 int build_union(aqe_ctx* c, const std::vector<const SweepForm*>& forms, uint32_t G, UnionBuilt& out) {
@@ -1282,15 +1286,31 @@ int build_union(aqe_ctx* c, const std::vector<const SweepForm*>& forms, uint32_t
         }
         nrows += F->slots;
     }
-    if (nrows > static_cast<uint32_t>(kUnionMaxRows)) return AQE_OK;
+    aqe_union_shape& sh = out.shape;
+    auto declined = [&](uint32_t bound) { sh.declined_by = bound; return AQE_OK; };
+    sh.classes = static_cast<uint32_t>(forms.size());
+    sh.workgroups = G;
+    sh.rows = nrows;
+    if (nrows > static_cast<uint32_t>(kUnionMaxRows)) return declined(AQE_UNION_MAX_ROWS);
     UnionCover cv;
     if (!build_union_cover(runs, 2u * nrows, cv)) return fail(c, AQE_ERR_INVALID, "internal: a union run names no row");
     const size_t np = cv.piece_lo.size(), ninc = cv.target_piece.size();
-    if (np == 0 || np > static_cast<size_t>(kUnionMaxPieces) || ninc > static_cast<size_t>(kUnionMaxIncidences)) return AQE_OK;
+    sh.pieces = static_cast<uint32_t>(np);
+    sh.incidences = static_cast<uint32_t>(ninc);
+    sh.slots = cv.slots;
+    if (np == 0 || np > static_cast<size_t>(kUnionMaxPieces)) return declined(AQE_UNION_MAX_PIECES);
+    if (ninc > static_cast<size_t>(kUnionMaxIncidences)) return declined(AQE_UNION_MAX_INCIDENCES);
     std::vector<UnionTile> tl;
     union_tiles(cv, tl);
     const uint64_t T = tl.size(), K = (T + G - 1) / G;
-    if (K > static_cast<uint64_t>(kUnionMaxTilesPerWg) || T >= 0xffffffffull) return AQE_OK;
+    sh.tiles = static_cast<uint32_t>(std::min<uint64_t>(T, 0xffffffffull));
+    sh.tiles_per_wg = static_cast<uint32_t>(std::min<uint64_t>(K, 0xffffffffull));
+    for (const UnionTile& u : tl) {
+        sh.whole_tiles += u.whole ? 1u : 0u;
+        sh.two_piece_tiles += u.last_piece != u.piece ? 1u : 0u;
+    }
+    sh.masked_tiles = sh.tiles - sh.whole_tiles;
+    if (K > static_cast<uint64_t>(kUnionMaxTilesPerWg) || T >= 0xffffffffull) return declined(AQE_UNION_MAX_TILES_PER_WG);
     // every workgroup's share holds slots of the pieces pf .. pl (consecutive: the tiles of a share are); their partials
     // go piece-major, the workgroups of a piece ascending
     std::vector<std::vector<uint32_t>> piece_wgs(np);
@@ -1299,7 +1319,8 @@ int build_union(aqe_ctx* c, const std::vector<const SweepForm*>& forms, uint32_t
         const uint64_t t0 = b * K, t1 = std::min<uint64_t>(t0 + K, T);
         if (t0 >= t1) continue;
         const uint32_t pf = tl[t0].piece, pl = tl[t1 - 1].last_piece;
-        if (pl - pf + 1u > static_cast<uint32_t>(kUnionWgPieces)) return AQE_OK;
+        sh.max_share_pieces = std::max(sh.max_share_pieces, pl - pf + 1u);
+        if (pl - pf + 1u > static_cast<uint32_t>(kUnionWgPieces)) return declined(AQE_UNION_WG_PIECES);
         wg_first[b] = pf;
         wg_count[b] = pl - pf + 1u;
         for (uint32_t p = pf; p <= pl; ++p) piece_wgs[p].push_back(b);
@@ -1307,7 +1328,8 @@ int build_union(aqe_ctx* c, const std::vector<const SweepForm*>& forms, uint32_t
     std::vector<uint32_t> piece_entry(np + 1, 0);
     for (size_t p = 0; p < np; ++p) piece_entry[p + 1] = piece_entry[p] + static_cast<uint32_t>(piece_wgs[p].size());
     const uint32_t nent = piece_entry[np];
-    if (nent > static_cast<uint32_t>(kUnionMaxEntries)) return AQE_OK;
+    sh.entries = nent;
+    if (nent > static_cast<uint32_t>(kUnionMaxEntries)) return declined(AQE_UNION_MAX_ENTRIES);
     // the block: header, tile_row, tile_meta, workgroup records, piece_lo, piece_hi, piece_entry,
     // target_begin, target_entry, then the partial list
     auto up8 = [](size_t x) { return (x + 7) & ~static_cast<size_t>(7); };
@@ -1373,6 +1395,9 @@ int union_groups(aqe_batch* b, int kind, const std::vector<char>& head, const st
     static const bool union_off = [] { const char* e = std::getenv("AQE_BATCH_UNION"); return e && e[0] == '0'; }();  // diagnostics: A/B in one build
     groups.clear();
     blocks.clear();
+    std::vector<aqe_union_shape>& shapes = b->multi[kind].union_shapes;  // the formed groups (their order is the launch's), then the declined sets
+    std::vector<aqe_union_shape> declined;
+    shapes.clear();
     const size_t nc = classes.size();
     std::vector<int> taken(nc, -1);  // class -> its union group
     if (kind == 0 && !union_off) {
@@ -1403,11 +1428,14 @@ int union_groups(aqe_batch* b, int kind, const std::vector<char>& head, const st
             UnionBuilt u;
             int rc = build_union(b->ctx, forms, static_cast<uint32_t>(std::min<uint64_t>(g, kMaxPersistGrid)), u);
             if (rc != AQE_OK) { for (UnionBuilt& x : blocks) (void)hipFree(x.d_block); blocks.clear(); return rc; }
-            if (!u.d_block) continue;
+            if (!u.d_block) { declined.push_back(u.shape); continue; }
             for (size_t k : ks) taken[k] = static_cast<int>(blocks.size());
+            shapes.push_back(u.shape);
             blocks.push_back(std::move(u));
         }
     }
+    shapes.insert(shapes.end(), declined.begin(), declined.end());
+    for (aqe_union_shape& x : shapes) x.candidates = static_cast<uint32_t>(shapes.size());
     std::vector<int> placed(blocks.size(), 0);
     std::vector<UnionBuilt> ordered;  // blocks in the order their groups take in the launch
     for (size_t k = 0; k < nc; ++k) {
@@ -1918,6 +1946,15 @@ int aqe_batch_union_info(aqe_batch* b, uint32_t* groups, uint64_t* rows_loaded) 
     const BatchMulti& m = b->multi[b->last_kind];
     if (groups) *groups = static_cast<uint32_t>(m.unions.size());
     if (rows_loaded) *rows_loaded = m.lean ? m.union_rows : m.rows_loaded;
+    return AQE_OK;
+}
+
+int aqe_batch_union_shape(aqe_batch* b, uint32_t index, aqe_union_shape* out) {
+    if (!b || !out) return AQE_ERR_INVALID;
+    if (b->last_kind < 0) return fail(b->ctx, AQE_ERR_INVALID, "no one-launch execution yet");
+    const BatchMulti& m = b->multi[b->last_kind];
+    if (index >= m.union_shapes.size()) return fail(b->ctx, AQE_ERR_INVALID, "no union candidate set of that index in the most recent build");
+    *out = m.union_shapes[index];
     return AQE_OK;
 }
 

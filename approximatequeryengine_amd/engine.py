@@ -181,6 +181,14 @@ class Batch:
         nat.check(nat.lib().aqe_batch_union_info(self._h, C.byref(g), C.byref(r)), self.engine._h)
         return g.value, r.value
 
+    def union_shape(self, index: int = 0):
+        """What the most recent build made of union candidate set `index` (nat.UnionShape; aqe_batch_union_shape): indices below
+        union_info()'s group count are the union groups in launch order, the ones after them the sets a bound of the union
+        kernel declined (`declined_by`, nat.UNION_*).  `candidates` counts both."""
+        s = nat.UnionShape()
+        nat.check(nat.lib().aqe_batch_union_shape(self._h, index, C.byref(s)), self.engine._h)
+        return s
+
 
 class Comm:
     """RCCL communicator behind the C ABI (aqe_comm): in-place f64 all-reduce on the engine's GPU.

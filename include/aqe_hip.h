@@ -775,6 +775,38 @@ AQE_API int aqe_batch_share_info(aqe_batch* batch, uint32_t* classes, uint64_t* 
  * it.  `groups`: union groups of the launch; `rows_loaded`: rows the launch loads (the union groups' slots once, every
  * other class's rows once).  AQE_BATCH_UNION=0 in the environment: no union groups.  Either output may be NULL. */
 AQE_API int aqe_batch_union_info(aqe_batch* batch, uint32_t* groups, uint64_t* rows_loaded);
+/* What the most recent build of the one-launch form made of its union candidates (read-only: tests and reports; nothing
+ * of it is on the launch path).  A CANDIDATE SET is two or more sweep classes that read the same view with the same
+ * shift and WHERE bounds.  Index 0 .. groups - 1 (aqe_batch_union_info's `groups`): the union groups, in launch order.
+ * From `groups` on: the candidate sets that did not form a union because a bound of the union kernel's fold declined
+ * them, in the order of their first class; their classes run as they are.  `candidates` is the number of both kinds;
+ * an index at or beyond it is AQE_ERR_INVALID.  A declined set reports what had been counted when the bound declined
+ * it (the bounds are tried in the order of the codes below); everything after that is 0. */
+#define AQE_UNION_FORMED 0
+#define AQE_UNION_MAX_ROWS 1          /* more than 256 (class, round) rows of totals */
+#define AQE_UNION_MAX_PIECES 2        /* more than 512 pieces in the cover; also a cover of no piece at all (only empty runs) */
+#define AQE_UNION_MAX_INCIDENCES 3    /* more than 2048 (piece, target) pairs */
+#define AQE_UNION_MAX_TILES_PER_WG 4  /* more than 1024 tiles in a workgroup's share; also 2^32 - 1 tiles or more in all */
+#define AQE_UNION_WG_PIECES 5         /* a share that holds slots of more than 32 pieces */
+#define AQE_UNION_MAX_ENTRIES 6       /* more than 768 (piece, workgroup) partials */
+typedef struct aqe_union_shape {
+    uint32_t declined_by;      /* AQE_UNION_FORMED, or the bound that declined the set */
+    uint32_t candidates;       /* candidate sets of the build: union groups + declined sets */
+    uint32_t classes;          /* sweep classes of the set */
+    uint32_t workgroups;       /* workgroups of the group */
+    uint32_t rows;             /* (class, round) rows of totals; targets = 2 x rows */
+    uint32_t pieces;           /* pieces of the cover */
+    uint32_t incidences;       /* (piece, target) pairs */
+    uint32_t tiles;
+    uint32_t tiles_per_wg;     /* a workgroup's share: workgroup b sweeps the tiles [b x tiles_per_wg, ...) */
+    uint32_t whole_tiles;      /* tiles of 1024 slots of one piece (no masks) */
+    uint32_t masked_tiles;     /* every other tile */
+    uint32_t two_piece_tiles;  /* masked tiles that hold slots of two pieces */
+    uint32_t max_share_pieces; /* the most pieces one workgroup's share holds slots of */
+    uint32_t entries;          /* (piece, workgroup) partials the fold adds */
+    uint64_t slots;            /* slots of the union: the rows the group loads */
+} aqe_union_shape;
+AQE_API int aqe_batch_union_shape(aqe_batch* batch, uint32_t index, aqe_union_shape* out);
 /* ---- the collective behind the C ABI: RCCL over xGMI ---------------------------------------------
  * One all-reduce SUM of the moment vectors replaces the reference's in-process merges (mutex-guarded vector, CAS on
  * atomic<double>, DB.cpp:948-951, 966-967, 2031-2036).  librccl is opened on first use (no link-time dependency; a
