@@ -342,7 +342,7 @@ class TableInfo(C.Structure):
     _fields_ = [("global_rows", C.c_uint64), ("shard_lo", C.c_uint64), ("local_rows", C.c_uint64),
                 ("shift", C.c_double), ("has_aos", C.c_int32), ("device_id", C.c_int32), ("hbm_bytes", C.c_uint64),
                 ("view_bytes", C.c_uint64), ("n_views", C.c_uint32), ("view_evictions", C.c_uint32), ("view_fallbacks", C.c_uint32),
-                ("reserved", C.c_uint32)]
+                ("side_streams", C.c_uint32)]
 
 
 class StageStats(C.Structure):

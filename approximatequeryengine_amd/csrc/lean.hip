@@ -50,13 +50,22 @@ typedef const AQE_KARG LeanLaunch* LeanKarg;
 // 5 partials out, 6 ticket drawn; its fold 3 partial list staged, 4 pieces summed, 5 targets summed, and then per judging
 // wave [wave][8]: 0 first judge done, 1 last result sent, 2 the wave's hardware id (HW_ID: bits 5:4 its SIMD).
 #ifdef AQE_LEAN_STAMPS
+// (-DAQE_LEAN_STAMPS=2, tools/stamp_overlap.py: two blocks of marks, a launch writes block `epoch & 1` — consecutive launches of a
+// context keep their marks apart, on one clock)
+#if AQE_LEAN_STAMPS + 0 >= 2
+#define LEAN_STAMP_BLOCKS 2
+#define LEAN_STAMP_BASE (static_cast<size_t>(epoch & 1ull) * kLeanStampWords)
+#else
+#define LEAN_STAMP_BLOCKS 1
+#define LEAN_STAMP_BASE static_cast<size_t>(0)
+#endif
 constexpr size_t kLeanStampWords = (static_cast<size_t>(kMaxPersistGrid) * kPersistWaves + 1 + kPersistWaves) * 8;
-__device__ unsigned long long g_lean_stamps[kLeanStampWords];
-#define LEAN_STAMP(slot) do { if (lane == 0 && blockIdx.x < static_cast<unsigned>(kMaxPersistGrid)) g_lean_stamps[(static_cast<size_t>(blockIdx.x) * kPersistWaves + wave) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define LEAN_STAMP_FOLD(slot) do { if (threadIdx.x == 0) g_lean_stamps[static_cast<size_t>(kMaxPersistGrid) * kPersistWaves * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define LEAN_STAMP_JUDGE(slot) do { if (lane == 0) g_lean_stamps[(static_cast<size_t>(kMaxPersistGrid) * kPersistWaves + 1 + wave) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+__device__ unsigned long long g_lean_stamps[LEAN_STAMP_BLOCKS * kLeanStampWords];
+#define LEAN_STAMP(slot) do { if (lane == 0 && blockIdx.x < static_cast<unsigned>(kMaxPersistGrid)) g_lean_stamps[LEAN_STAMP_BASE + (static_cast<size_t>(blockIdx.x) * kPersistWaves + wave) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define LEAN_STAMP_FOLD(slot) do { if (threadIdx.x == 0) g_lean_stamps[LEAN_STAMP_BASE + static_cast<size_t>(kMaxPersistGrid) * kPersistWaves * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define LEAN_STAMP_JUDGE(slot) do { if (lane == 0) g_lean_stamps[LEAN_STAMP_BASE + (static_cast<size_t>(kMaxPersistGrid) * kPersistWaves + 1 + wave) * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 // (s_getreg_b32 hwreg(HW_REG_HW_ID, 0, 32): a read of the wave's placement)
-#define LEAN_STAMP_HWID(slot) do { if (lane == 0) g_lean_stamps[(static_cast<size_t>(kMaxPersistGrid) * kPersistWaves + 1 + wave) * 8 + (slot)] = __builtin_amdgcn_s_getreg((31 << 11) | 4); } while (0)
+#define LEAN_STAMP_HWID(slot) do { if (lane == 0) g_lean_stamps[LEAN_STAMP_BASE + (static_cast<size_t>(kMaxPersistGrid) * kPersistWaves + 1 + wave) * 8 + (slot)] = __builtin_amdgcn_s_getreg((31 << 11) | 4); } while (0)
 #else
 #define LEAN_STAMP(slot) do { } while (0)
 #define LEAN_STAMP_FOLD(slot) do { } while (0)
@@ -253,7 +262,7 @@ __device__ __forceinline__ void lean_judge(const LeanTail& T, const double (&tot
         res_words[sizeof(aqe_result) / 8] = result_check(res, epoch);
     }
 #ifdef AQE_LEAN_STAMPS
-    g_lean_stamps[static_cast<size_t>(kMaxPersistGrid) * kPersistWaves * 8 + 2] = __builtin_amdgcn_s_memrealtime();
+    g_lean_stamps[LEAN_STAMP_BASE + static_cast<size_t>(kMaxPersistGrid) * kPersistWaves * 8 + 2] = __builtin_amdgcn_s_memrealtime();
 #endif
 }
 
@@ -1024,7 +1033,7 @@ hipError_t launch_sweep_lean(const LeanLaunch& a, unsigned grid, bool nt, hipStr
 
 #ifdef AQE_LEAN_STAMPS
 extern "C" __attribute__((visibility("default"))) int aqe_debug_lean_stamps(unsigned long long* out, size_t words) {
-    const size_t all = kLeanStampWords;
+    const size_t all = LEAN_STAMP_BLOCKS * kLeanStampWords;  // (AQE_LEAN_STAMPS=2: the block of the even epochs, then the odd ones)
     return static_cast<int>(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_lean_stamps), 8 * (words < all ? words : all), 0, hipMemcpyDeviceToHost));
 }
 #endif

@@ -1098,6 +1098,10 @@ namespace {
 // runtime multiplexes streams onto a handful of hardware queues, and a stream that waits on an event blocks every
 // other stream sharing its queue.  Three lanes plus the caller's stream each get a queue of their own, and two
 // kernels in flight are already enough for one query's hand-off tail to overlap the next query's sweep.
+// Made by the calls that launch on them (aqe_batch_enqueue_sweeps, aqe_batch_enqueue_replays), not with the batch: a
+// stream takes its place in the runtime's rotation over the hardware queues (four to a process) when it is created,
+// and three streams created between a caller's two put those two on ONE queue — the launches of the one-launch form
+// (aqe_batch_enqueue_all), which never touches a side stream, then ran strictly one after the other.
 int ensure_lanes(aqe_ctx* c) {
     while (c->lanes.size() < kBatchLanes) {
         hipStream_t s = nullptr;
@@ -1827,8 +1831,6 @@ int aqe_batch_create(aqe_plan* const* plans, uint32_t n, aqe_batch** out) {
     }
     aqe_ctx* c = plans[0]->ctx;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensure_lanes(c);
-    if (rc != AQE_OK) return rc;
     std::unique_ptr<aqe_batch, void (*)(aqe_batch*)> b(new aqe_batch, aqe_batch_destroy);
     b->ctx = c;
     b->plans.assign(plans, plans + n);
@@ -1860,14 +1862,16 @@ int aqe_batch_enqueue_sweeps(aqe_batch* b, double* dev_totals, uint64_t row_stri
         if (p->rounds.size() < 2) return fail(c, AQE_ERR_UNSUPPORTED, "a plan of the batch has no batched (totals) form (single round: use the per-round calls)");
         if (row_stride < static_cast<uint64_t>(p->rounds.size()) * kVec) return fail(c, AQE_ERR_INVALID, "row_stride shorter than a plan's totals");
     }
+    int rc = ensure_lanes(c);
+    if (rc != AQE_OK) return rc;
     BatchMulti& m = b->multi[1];
     if (!m.built || m.totals != dev_totals || m.stride != row_stride) {
-        int rc = build_multi(b, 1, dev_totals, row_stride);
+        rc = build_multi(b, 1, dev_totals, row_stride);
         if (rc != AQE_OK) return rc;
     }
     // ONE launch sweeps every plan's rounds (a group of workgroups per plan) on the first side stream; the plans'
     // previous replay precedes it there (aqe_batch_enqueue_replays makes the side streams wait for it)
-    int rc = launch_multi(b, 1, c->lanes[0]);
+    rc = launch_multi(b, 1, c->lanes[0]);
     if (rc != AQE_OK) return rc;
     HIPCHK(c, hipEventRecord(b->swept[0], c->lanes[0]));  // (one launch on one side stream: one event)
     return AQE_OK;
@@ -1976,6 +1980,8 @@ int aqe_batch_enqueue_replays(aqe_batch* b, const double* dev_totals, uint64_t r
         int rc = plan_is_current(p);
         if (rc != AQE_OK) return rc;
     }
+    int rc = ensure_lanes(c);
+    if (rc != AQE_OK) return rc;
     // ONE launch replays every plan of the batch on the caller's stream, right behind the collective; the side
     // streams then wait for it before they sweep again (their plans' state, result and buffer row are read here)
     HIPCHK(c, launch_replay_batch(b->d_items, static_cast<uint32_t>(b->plans.size()), dev_totals, row_stride, main_s));
@@ -1996,7 +2002,7 @@ int aqe_batch_fetch(aqe_batch* b, aqe_result* out_n) {
     if (totals) HIPCHK(b->ctx, hipEventSynchronize(b->reduced));
     for (size_t i = 0; i < b->plans.size(); ++i) {
         int rc = plan_is_current(b->plans[i]);
-        hipStream_t s = totals ? b->ctx->lanes[0] : b->last_stream;
+        hipStream_t s = totals && !b->ctx->lanes.empty() ? b->ctx->lanes[0] : b->last_stream;  // (no side stream yet: nothing swept totals)
         if (rc == AQE_OK) rc = fetch(b->plans[i], out_n + i, s, totals);
         if (rc != AQE_OK) return rc;
     }

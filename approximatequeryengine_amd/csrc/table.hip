@@ -737,7 +737,7 @@ int aqe_table_info_get(const aqe_ctx* c, aqe_table_info* out) {
     out->n_views = static_cast<uint32_t>(c->stride_views.size());
     out->view_evictions = static_cast<uint32_t>(c->view_evictions);
     out->view_fallbacks = static_cast<uint32_t>(c->view_fallbacks);
-    out->reserved = 0;
+    out->side_streams = static_cast<uint32_t>(c->lanes.size());
     return AQE_OK;
 }
 

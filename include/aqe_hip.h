@@ -208,7 +208,9 @@ typedef struct aqe_table_info {
     uint32_t n_views;
     uint32_t view_evictions; /* views dropped to make room since the table was staged                        */
     uint32_t view_fallbacks; /* plans that wanted a view while all 8 were held by live plans: swept in place  */
-    uint32_t reserved;
+    uint32_t side_streams;   /* streams of its own the context holds beside its default one: 0 until a batch sweeps
+                                totals (aqe_batch_enqueue_sweeps, the sharded form) — the one-launch form runs on the
+                                caller's streams alone and takes no hardware queue away from them                    */
 } aqe_table_info;
 
 /* ---- lifecycle ------------------------------------------------------------------------------ */
