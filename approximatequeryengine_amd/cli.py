@@ -34,7 +34,9 @@ import os
 import re
 import sys
 import time
-from typing import Optional, Tuple
+from dataclasses import dataclass
+from functools import cached_property
+from typing import Callable, NamedTuple, Optional, Tuple
 
 QUERY_EXACT, QUERY_RANDOM, QUERY_CLT, QUERY_EMBEDDED = "exact", "random_sample", "clt_approximation", "embedded_approx"
 
@@ -57,27 +59,43 @@ def parse_embedded_approx(query: str) -> Tuple[str, bool]:
     return query, False
 
 
+# ---- the aggregate families: which one a query belongs to, and what its runner needs of the query ----
+
+_PLAIN = ("SUM", "AVG", "COUNT")  # the plain aggregates, in aggregate_of's order of preference
+_PLAIN_NAMES = "|".join(_PLAIN)
+_PLAIN_CALL = rf"(?:{_PLAIN_NAMES})\("  # read in the query's upper case, WITHOUT blanks: "SUM (amount)" is not a plain aggregate's call
+
+
 def aggregate_of(query: str) -> str:
     up = query.upper()
-    for a in ("SUM", "AVG", "COUNT"):
+    for a in _PLAIN:
         if a + "(" in up:
             return a
     return "AVG"  # enhanced_aqe_cli.py:198-200: default to average
 
 
 _QUANTILE_FUNCS = {"PERCENTILE_CONT": "linear", "PERCENTILE_DISC": "inverted_cdf", "PERCENTILE": "linear"}
+_SPREAD_FUNCS = {"VARIANCE": "var_samp", "VAR_SAMP": "var_samp", "VAR_POP": "var_pop", "STDDEV": "stddev_samp",
+                 "STDDEV_SAMP": "stddev_samp", "STDDEV_POP": "stddev_pop"}
+_DISTINCT_COLUMNS = ("amount", "region", "product_id")
+# every family's function names, as an alternation: written here and nowhere else
+_PERCENTILES = "PERCENTILE(?:_CONT|_DISC)?"
+_SPREADS = "VARIANCE|VAR_SAMP|VAR_POP|STDDEV(?:_SAMP|_POP)?"
+_EXTREMES = "MIN|MAX"
+_SUMMARIES = "SUMMARY|DESCRIBE"
+_APPROX_DISTINCT = "APPROX_COUNT_DISTINCT"
+_COUNT_DISTINCT = r"COUNT\s*\(\s*DISTINCT\b"
 
 
 def quantile_of(query: str) -> Optional[Tuple[float, str, str]]:
     """MEDIAN(amount) / PERCENTILE(amount, p) / PERCENTILE_CONT(amount, p) -> (p, "linear", name); PERCENTILE_DISC(amount, p)
-    -> (p, "inverted_cdf", name); None for any other query — and for every query that names SUM(, AVG( or COUNT(, whose
-    routing stays as it was.  A p that is not a number in [0, 1] raises ValueError."""
-    up = query.upper()
-    if any(a + "(" in up for a in ("SUM", "AVG", "COUNT")):
+    -> (p, "inverted_cdf", name); None for a query that is not the family's (see _FAMILIES).  A p that is not a number in [0, 1]
+    raises ValueError."""
+    if _shut_out("quantile", query):
         return None
     if re.search(r"\bMEDIAN\s*\(\s*amount\s*\)", query, re.IGNORECASE):
         return 0.5, "linear", "MEDIAN"
-    m = re.search(r"\b(PERCENTILE_CONT|PERCENTILE_DISC|PERCENTILE)\s*\(\s*amount\s*,\s*([^)]*?)\s*\)", query, re.IGNORECASE)
+    m = re.search(rf"\b({_PERCENTILES})\s*\(\s*amount\s*,\s*([^)]*?)\s*\)", query, re.IGNORECASE)
     if not m:
         return None
     try:
@@ -89,50 +107,32 @@ def quantile_of(query: str) -> Optional[Tuple[float, str, str]]:
     return p, _QUANTILE_FUNCS[m.group(1).upper()], m.group(1).upper()
 
 
-_SPREAD_FUNCS = {"VARIANCE": "var_samp", "VAR_SAMP": "var_samp", "VAR_POP": "var_pop", "STDDEV": "stddev_samp",
-                 "STDDEV_SAMP": "stddev_samp", "STDDEV_POP": "stddev_pop"}
-
-
 def spread_of(query: str) -> Optional[Tuple[str, str]]:
     """VARIANCE | VAR_SAMP | VAR_POP | STDDEV | STDDEV_SAMP | STDDEV_POP (amount) -> (kind of approx_spread, name as typed, in
-    upper case); None for any other query — and for every query that names SUM(, AVG(, COUNT( or a quantile function, whose
-    routing stays as it was."""
-    up = query.upper()
-    if any(a + "(" in up for a in ("SUM", "AVG", "COUNT")):
+    upper case); None for a query that is not the family's."""
+    if _shut_out("spread", query):
         return None
-    if re.search(r"\b(MEDIAN|PERCENTILE(_CONT|_DISC)?)\s*\(", query, re.IGNORECASE):
-        return None
-    m = re.search(r"\b(VARIANCE|VAR_SAMP|VAR_POP|STDDEV_SAMP|STDDEV_POP|STDDEV)\s*\(\s*amount\s*\)", query, re.IGNORECASE)
-    if not m:
-        return None
-    return _SPREAD_FUNCS[m.group(1).upper()], m.group(1).upper()
+    m = re.search(rf"\b({_SPREADS})\s*\(\s*amount\s*\)", query, re.IGNORECASE)
+    return (_SPREAD_FUNCS[m.group(1).upper()], m.group(1).upper()) if m else None
 
 
 def extreme_of(query: str) -> Optional[Tuple[str, ...]]:
-    """MIN(amount) and / or MAX(amount) -> the names typed, in upper case and in the order typed (each once); None for any
-    other query — and for every query that names SUM(, AVG(, COUNT(, a quantile function or a spread function, whose routing
-    stays as it was."""
-    up = query.upper()
-    if any(a + "(" in up for a in ("SUM", "AVG", "COUNT")):
+    """MIN(amount) and / or MAX(amount) -> the names typed, in upper case and in the order typed (each once); None for a query
+    that is not the family's."""
+    if _shut_out("extreme", query):
         return None
-    if re.search(r"\b(MEDIAN|PERCENTILE(_CONT|_DISC)?|VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?)\s*\(", query, re.IGNORECASE):
-        return None
-    names = []
-    for m in re.finditer(r"\b(MIN|MAX)\s*\(\s*amount\s*\)", query, re.IGNORECASE):
-        if m.group(1).upper() not in names:
-            names.append(m.group(1).upper())
-    return tuple(names) or None
+    found = []
+    for m in re.finditer(rf"\b({_EXTREMES})\s*\(\s*amount\s*\)", query, re.IGNORECASE):
+        if m.group(1).upper() not in found:
+            found.append(m.group(1).upper())
+    return tuple(found) or None
 
 
 def histogram_of(query: str) -> Optional[Tuple[int, Optional[Tuple[float, float]]]]:
-    """HISTOGRAM(amount, B) -> (B, None); HISTOGRAM(amount, B, lo, hi) -> (B, (lo, hi)); None for any other query — and for
-    every query that also names SUM(, AVG(, COUNT(, a quantile, spread or extreme function, whose routing stays as it was.
+    """HISTOGRAM(amount, B) -> (B, None); HISTOGRAM(amount, B, lo, hi) -> (B, (lo, hi)); None for a query that is not the family's.
     ValueError, quoting the offending text, for a B that is not an integer in 1 .. 4096, a range that is not two finite numbers
     with lo < hi, or another number of arguments."""
-    up = query.upper()
-    if any(a + "(" in up for a in ("SUM", "AVG", "COUNT")):
-        return None
-    if re.search(r"\b(MEDIAN|PERCENTILE(_CONT|_DISC)?|VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?|MIN|MAX)\s*\(", query, re.IGNORECASE):
+    if _shut_out("histogram", query):
         return None
     m = re.search(r"\bHISTOGRAM\s*\(\s*amount\s*(?:,([^)]*))?\)", query, re.IGNORECASE)
     if not m:
@@ -156,21 +156,14 @@ def histogram_of(query: str) -> Optional[Tuple[int, Optional[Tuple[float, float]
     return int(parts[0]), (lo, hi)
 
 
-_DISTINCT_COLUMNS = ("amount", "region", "product_id")
-
-
 def distinct_of(query: str) -> Optional[str]:
     """COUNT(DISTINCT col) / APPROX_COUNT_DISTINCT(col), in any letter case -> col in lower case (amount, region or product_id);
-    None for any other query — and for every query that names another aggregate beside it (SUM(, AVG(, a COUNT( not followed by
-    DISTINCT, a quantile, spread, extreme or histogram function), whose routing stays as it was.  ValueError, quoting the
-    offending text, for a column that cannot be counted and for more than one distinct count in a query."""
-    found = list(re.finditer(r"\b(?:COUNT\s*\(\s*DISTINCT\b|APPROX_COUNT_DISTINCT\s*\()([^)]*)\)", query, re.IGNORECASE))
+    None for a query that is not the family's.  ValueError, quoting the offending text, for a column that cannot be counted and
+    for more than one distinct count in a query."""
+    if _shut_out("distinct", query):
+        return None
+    found = list(re.finditer(rf"\b(?:{_COUNT_DISTINCT}|{_APPROX_DISTINCT}\s*\()([^)]*)\)", query, re.IGNORECASE))
     if not found:
-        return None
-    up = query.upper()
-    if "SUM(" in up or "AVG(" in up or re.search(r"COUNT\((?!\s*DISTINCT\b)", up):
-        return None
-    if re.search(r"\b(MEDIAN|PERCENTILE(_CONT|_DISC)?|VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?|MIN|MAX|HISTOGRAM)\s*\(", query, re.IGNORECASE):
         return None
     shown = " ".join(found[0].group(0).split())
     if len(found) > 1:
@@ -182,22 +175,54 @@ def distinct_of(query: str) -> Optional[str]:
 
 
 def summary_of(query: str) -> Optional[bool]:
-    """SUMMARY(amount) / DESCRIBE(amount), in any letter case -> True; None for any other query — and for every query that
-    names another aggregate beside it (SUM(, AVG(, COUNT(, a distinct count, a quantile, spread, extreme or histogram
-    function), whose routing stays as it was.  ValueError, quoting the offending text, for a column other than amount."""
-    m = re.search(r"\b(SUMMARY|DESCRIBE)\s*\(([^)]*)\)", query, re.IGNORECASE)
+    """SUMMARY(amount) / DESCRIBE(amount), in any letter case -> True; None for a query that is not the family's.  ValueError, quoting the
+    offending text, for a column other than amount."""
+    if _shut_out("summary", query):
+        return None
+    m = re.search(rf"\b({_SUMMARIES})\s*\(([^)]*)\)", query, re.IGNORECASE)
     if not m:
-        return None
-    up = query.upper()
-    if any(a + "(" in up for a in ("SUM", "AVG", "COUNT")):
-        return None
-    if re.search(r"\b(MEDIAN|PERCENTILE(_CONT|_DISC)?|VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?|MIN|MAX|HISTOGRAM|COUNT|APPROX_COUNT_DISTINCT)\s*\(",
-                 query, re.IGNORECASE):
         return None
     col = m.group(2).strip()
     if col.lower() != "amount":
         raise ValueError(f"'{' '.join(m.group(0).split())}': unknown column {col!r} ({m.group(1).upper()} takes amount)")
     return True
+
+
+class _Family(NamedTuple):
+    name: str
+    names: str  # the function names that are the family's, as an alternation
+    read: Callable  # query -> what the family's runner needs of the query, None for a query that is not the family's
+    plain: str = _PLAIN_CALL  # the plain aggregates' calls (in the query's upper case) that shut the family out
+
+
+# In order of precedence.  A query is a family's when it holds a call of the family's own, none of the plain calls in `plain` and
+# no NAME( of a family above it — whatever that name's arguments are, and whether or not that family takes the query itself: such
+# a query keeps the routing it had before the family existed (SELECT MEDIAN(amount), COUNT(DISTINCT region) is a plain COUNT).
+_FAMILIES = (
+    _Family("quantile", f"MEDIAN|{_PERCENTILES}", quantile_of),
+    _Family("spread", _SPREADS, spread_of),
+    _Family("extreme", _EXTREMES, extreme_of),
+    _Family("histogram", "HISTOGRAM", histogram_of),
+    _Family("distinct", f"COUNT|{_APPROX_DISTINCT}", distinct_of, plain=r"(?:SUM|AVG)\(|COUNT\((?!\s*DISTINCT\b)"),
+    _Family("summary", _SUMMARIES, summary_of),
+)
+
+
+def _called(*families: str) -> str:
+    """The pattern of NAME( for every name of the given families, blanks before the parenthesis allowed."""
+    return rf"\b(?:{'|'.join(f.names for f in _FAMILIES if f.name in families)})\s*\("
+
+
+def _shut_out(family: str, query: str) -> bool:
+    """Whether a plain aggregate's call or the name of a family above `family` keeps the query from being the family's."""
+    at = [f.name for f in _FAMILIES].index(family)
+    above = [f.name for f in _FAMILIES[:at]]
+    return bool(re.search(_FAMILIES[at].plain, query.upper()) or (above and re.search(_called(*above), query, re.IGNORECASE)))
+
+
+# ---- the clauses ----
+
+_CLAUSE_END = r"\bORDER\s+BY\b|\bLIMIT\b|;|$"
 
 
 def where_clause_of(query: str) -> Optional[str]:
@@ -220,14 +245,19 @@ def key_where_of(query: str) -> Optional[dict]:
 _GROUP_COLUMNS = ("region", "product_id")
 
 
+def _group_by_clause(query: str) -> Optional[str]:
+    """The text between GROUP BY and HAVING / ORDER BY / LIMIT / ``;`` / the end, blanks squeezed, or None."""
+    m = re.search(rf"\bGROUP\s+BY\b(.*?)(?=\bHAVING\b|{_CLAUSE_END})", query, re.IGNORECASE | re.DOTALL)
+    return " ".join(m.group(1).split()) if m else None
+
+
 def group_by_of(query: str) -> Optional[Tuple[str, ...]]:
     """The columns of the query's GROUP BY clause as typed — one of region / product_id, or both in either order — or None
     for a query without the clause.  ValueError, quoting the clause, for an unknown column, a column named twice or more than
     two columns: a column the engine cannot group by is never dropped."""
-    m = re.search(r"\bGROUP\s+BY\b(.*?)(?=\bHAVING\b|\bORDER\s+BY\b|\bLIMIT\b|;|$)", query, re.IGNORECASE | re.DOTALL)
-    if not m:
+    clause = _group_by_clause(query)
+    if clause is None:
         return None
-    clause = " ".join(m.group(1).split())
     names = [re.sub(r"\s+(ASC|DESC)$", "", c.strip(), flags=re.IGNORECASE) for c in clause.split(",")]
     low = [c.lower() for c in names]
     for c, l in zip(names, low):
@@ -243,10 +273,9 @@ def time_bucket_of(query: str) -> Optional[Tuple[int, int]]:
     None for a query whose GROUP BY clause has no ``BUCKET(`` — whose routing stays as it was.  ValueError, quoting the clause, for a
     column other than timestamp, a W that is not an integer of at least 1, an origin that is not an integer, another number of
     arguments, or a second GROUP BY column beside the bucket."""
-    m = re.search(r"\bGROUP\s+BY\b(.*?)(?=\bHAVING\b|\bORDER\s+BY\b|\bLIMIT\b|;|$)", query, re.IGNORECASE | re.DOTALL)
-    if not m or not re.search(r"BUCKET\s*\(", m.group(1), re.IGNORECASE):
+    clause = _group_by_clause(query)
+    if clause is None or not re.search(r"BUCKET\s*\(", clause, re.IGNORECASE):
         return None
-    clause = " ".join(m.group(1).split())
     shown = f"'GROUP BY {clause}'"
     b = re.fullmatch(r"(TIME_BUCKET|BUCKET)\s*\(([^()]*)\)\s*(.*)", clause, re.IGNORECASE)
     if not b:
@@ -270,15 +299,183 @@ def time_bucket_of(query: str) -> Optional[Tuple[int, int]]:
     return int(parts[1]), origin
 
 
-_NO_BUCKET_FORM = r"\b(MEDIAN|PERCENTILE(_CONT|_DISC)?|VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?|MIN|MAX|HISTOGRAM|APPROX_COUNT_DISTINCT|SUMMARY|DESCRIBE)\s*\("
+_TOP_CLAUSE = re.compile(rf"\bORDER\s+BY\s+({_PLAIN_NAMES})\s*\(\s*(\*|amount)\s*\)\s*(ASC|DESC)?\s*\bLIMIT\s+([+-]?\d+)\s*;?\s*$", re.IGNORECASE)
+
+
+def _top(clean: str) -> Optional[Tuple[int, bool, str]]:
+    """(k, descending, aggregate) of a claimed ORDER BY <agg> [ASC | DESC] LIMIT k, or None: see top_of."""
+    m = _TOP_CLAUSE.search(clean)
+    if not m:
+        return None
+    head, name = clean[:m.start()], m.group(1).upper()
+    if not re.search(r"\bGROUP\s+BY\b", head, re.IGNORECASE) or (m.group(2) == "*" and name != "COUNT"):
+        return None
+    named = [a for a in _PLAIN if re.search(rf"\b{a}\s*\(", head, re.IGNORECASE)]
+    if not named or named[0] != name:
+        return None
+    return int(m.group(4)), (m.group(3) or "ASC").upper() == "DESC", name
+
+
+def top_of(clean: str) -> Optional[Tuple[int, bool]]:
+    """``... GROUP BY ... ORDER BY <agg> [ASC | DESC] LIMIT k`` with <agg> the select list's own aggregate — SUM(amount),
+    AVG(amount), COUNT(*) or COUNT(amount), named literally before the clause; letter case and blanks do not matter on either
+    side — -> (k, descending), SQL's default direction being ASC; None for every other query: ORDER BY a column name, an ordinal
+    or an aggregate the select list does not name, ORDER BY <agg> without LIMIT, no GROUP BY — those clauses stay ignored, as
+    they were."""
+    top = _top(clean)
+    return None if top is None else top[:2]
+
+
+_HAVING_CLAIM = re.compile(rf"\bHAVING\s+(?=(?:{_PLAIN_NAMES})\s*\()(.*?)(?={_CLAUSE_END})", re.IGNORECASE | re.DOTALL)
+
+
+def having_of(clean: str) -> Optional[str]:
+    """The text of a CLAIMED HAVING clause — what follows HAVING begins with SUM, AVG or COUNT and ``(``; letter case and blanks do
+    not matter — up to ORDER BY, LIMIT, ``;`` or the end, or None: every other ``HAVING ...`` (``having 1``, a column name, an
+    alias) stays ignored, as it was."""
+    m = _HAVING_CLAIM.search(clean)
+    return None if m is None else " ".join(m.group(1).split())
+
+
+def without_having(clean: str) -> str:
+    """The query without its claimed HAVING clause (unchanged when there is none): what the select list, WHERE, GROUP BY and
+    ORDER BY ... LIMIT are read from, so that an aggregate named only by the clause is not taken for the query's own."""
+    m = _HAVING_CLAIM.search(clean)
+    return clean if m is None else clean[:m.start()] + clean[m.end():]
+
+
+# ---- one reading of the query ----
+
+@dataclass(frozen=True)
+class ParsedQuery:
+    """An unwrapped query (no APPROX(...)) and what the command line reads in it.  Every part is read on first use and kept, and a
+    part that cannot be read raises its ValueError there, not before: run() reports the first thing wrong in ITS order of checks,
+    and a query that never reaches a part is never refused for it."""
+    text: str  # as given, a claimed HAVING clause included
+
+    @cached_property
+    def having(self) -> Optional[str]:
+        return having_of(self.text)
+
+    @cached_property
+    def rest(self) -> str:  # the query without its claimed HAVING clause: what every part below is read from
+        return without_having(self.text)
+
+    @cached_property
+    def family(self) -> Tuple[str, object]:
+        """(the family that claims the query, its payload), or ("plain", None): SUM / AVG / COUNT, see `aggregate`."""
+        for f in _FAMILIES:
+            payload = f.read(self.rest)
+            if payload is not None:
+                return f.name, payload
+        return "plain", None
+
+    @cached_property
+    def aggregate(self) -> str:
+        return aggregate_of(self.rest)
+
+    @cached_property
+    def group_by(self) -> Optional[Tuple[str, ...]]:
+        return group_by_of(self.rest)
+
+    @cached_property
+    def bucket(self) -> Optional[Tuple[int, int]]:
+        return time_bucket_of(self.rest)
+
+    @cached_property
+    def top(self) -> Optional[Tuple[int, bool, str]]:  # (k, descending, the aggregate the clause and the select list name)
+        return _top(self.rest)
+
+    @cached_property
+    def where(self) -> Optional[str]:
+        return where_clause_of(self.rest)
+
+    @cached_property
+    def key_where(self) -> Optional[dict]:
+        return key_where_of(self.rest)
+
+    @cached_property
+    def amount_where(self) -> Optional[Tuple[float, float]]:
+        # `WHERE amount BETWEEN a AND b` / `>= a AND <= b` / `> a` (the façade's extraction, custom_scheduler.cpp:277-294) is
+        # honoured by every sampler that has a WHERE form; the reference CLI ignores it for scalar queries altogether
+        from . import aqe_backend
+        return aqe_backend.parse_where(self.rest)
+
+
+def read_query(clean: str) -> ParsedQuery:
+    return ParsedQuery(clean)
+
+
+# ---- the refusals: what a feature or a family has no form for, found before the table is opened ----
+
+_has_e = lambda q, args: args.e is not None
+_grouped = lambda q, args: re.search(r"GROUP\s+BY", q, re.IGNORECASE)
+_bucketed = lambda q, args: re.search(r"BUCKET\s*\(", q, re.IGNORECASE)
+_names = lambda family: (lambda q, args: re.search(_called(family), q, re.IGNORECASE))  # the name is in the query, claimed or not
+_grouped_count = lambda q, args: group_error_form(q, args) and aggregate_of(q) == "COUNT"
+
+# who refuses -> (what of the query and the options it refuses, its message), in the order the defects are reported
+_REFUSALS = {
+    "--max-groups": (
+        (_has_e, "--max-groups has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
+        (lambda q, args: spread_of(q) is not None, "--max-groups has no VARIANCE / STDDEV form: GROUP BY over more than 1024 groups takes SUM, AVG or COUNT"),
+        (lambda q, args: extreme_of(q) is not None, "--max-groups has no MIN / MAX form: GROUP BY over more than 1024 groups takes SUM, AVG or COUNT"),
+        (_bucketed, "--max-groups has no GROUP BY BUCKET(...) form: time buckets stop at 1024 buckets")),
+    "--per-group": (
+        (_names("spread"), "--per-group has no VARIANCE / STDDEV form: the budgeted GROUP BY takes SUM, AVG or COUNT"),
+        (_names("extreme"), "--per-group has no MIN / MAX form: the budgeted GROUP BY takes SUM, AVG or COUNT"),
+        (_bucketed, "--per-group has no GROUP BY BUCKET(...) form: the budget is per key of region or product_id"),
+        (lambda q, args: re.search(r"\bHAVING\b", q, re.IGNORECASE), "--per-group has no HAVING form"),
+        (lambda q, args: re.search(r"\bORDER\s+BY\b.*\bLIMIT\b", q, re.IGNORECASE | re.DOTALL), "--per-group has no ORDER BY ... LIMIT form"),
+        (lambda q, args: not re.search(rf"\b({_PLAIN_NAMES})\s*\(", q, re.IGNORECASE), "--per-group takes SUM, AVG or COUNT ... GROUP BY region | product_id")),
+    "top": (
+        (_has_e, "ORDER BY the aggregate ... LIMIT has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
+        (_names("spread"), "ORDER BY the aggregate ... LIMIT has no VARIANCE / STDDEV form: the top groups are ordered by SUM, AVG or COUNT"),
+        (_names("extreme"), "ORDER BY the aggregate ... LIMIT has no MIN / MAX form: the top groups are ordered by SUM, AVG or COUNT"),
+        (_bucketed, "ORDER BY the aggregate ... LIMIT has no GROUP BY BUCKET(...) form: time buckets are listed in time order")),
+    "HAVING": (
+        (_has_e, "HAVING has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
+        (_names("spread"), "HAVING has no VARIANCE / STDDEV form: the groups are judged under SUM, AVG or COUNT"),
+        (_names("extreme"), "HAVING has no MIN / MAX form: the groups are judged under SUM, AVG or COUNT"),
+        (_bucketed, "HAVING has no GROUP BY BUCKET(...) form: time buckets are not judged")),
+    "BUCKET": ((_has_e, "GROUP BY BUCKET(...) has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),),
+    "--distinct-by": ((_has_e, "--distinct-by has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),),
+    "quantile": (
+        (_has_e, "quantiles have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
+        (_grouped, "GROUP BY is not supported with MEDIAN / PERCENTILE")),
+    "spread": ((_has_e, "VARIANCE / STDDEV have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),),
+    "extreme": ((_has_e, "MIN / MAX have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),),
+    "histogram": (
+        (_has_e, "HISTOGRAM has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
+        (_grouped, "GROUP BY is not supported with HISTOGRAM")),
+    "distinct": (
+        (_has_e, "COUNT(DISTINCT) has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
+        (_grouped, "GROUP BY is not supported with COUNT(DISTINCT) (a count per group: leave the GROUP BY clause out and give --distinct-by region|product_id)")),
+    "summary": (
+        (_has_e, "SUMMARY has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
+        (_grouped, "GROUP BY is not supported with SUMMARY")),
+    "GROUP BY": (
+        (_grouped_count, "COUNT ... GROUP BY has no error-threshold (--e) form (a grouped COUNT has no interval to judge): "
+                         "give a sample percentage (--s) or none (exact)"),),
+}
+
+
+def _refusal(who: str, query: str, args) -> Optional[str]:
+    """The first of `who`'s refusals that the query and the options meet, or None."""
+    for meets, message in _REFUSALS.get(who, ()):
+        if meets(query, args):
+            return message
+    return None
 
 
 def time_bucket_defect(clean: str, args) -> Optional[str]:
     """What keeps a GROUP BY BUCKET(...) query from running, found before the table is opened (None: nothing): --e, an aggregate
     without a bucketed form, a timestamp or key predicate outside the supported forms, key terms on both columns."""
-    if args.e is not None:
-        return "GROUP BY BUCKET(...) has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"
-    m = re.search(_NO_BUCKET_FORM, clean, re.IGNORECASE) or re.search(r"\bCOUNT\s*\(\s*DISTINCT\b", clean, re.IGNORECASE)
+    why = _refusal("BUCKET", clean, args)
+    if why is not None:
+        return why
+    no_form = rf"{_called('quantile', 'spread', 'extreme', 'histogram', 'summary')}|\b{_APPROX_DISTINCT}\s*\("
+    m = re.search(no_form, clean, re.IGNORECASE) or re.search(rf"\b{_COUNT_DISTINCT}", clean, re.IGNORECASE)
     if m:
         return f"{' '.join(m.group(0).split()).rstrip('(').strip().upper()} has no GROUP BY BUCKET(...) form: time buckets take SUM, AVG or COUNT"
     from . import aqe_backend, engine
@@ -315,12 +512,15 @@ def series_by_defect(clean: str, args, bucket) -> Optional[str]:
     return None
 
 
+def _error_form_asked(args) -> bool:
+    """--e without --s (--s wins, as in determine_query_type) and outside an APPROX(...) wrapper."""
+    return args.e is not None and args.s is None and not parse_embedded_approx(args.query)[1]
+
+
 def group_error_form(clean: str, args) -> bool:
-    """SUM / AVG / COUNT ... GROUP BY ... --e E without --s (--s wins, as in determine_query_type) and outside an APPROX(...)
-    wrapper: the query the error-threshold form of GROUP BY answers."""
-    if args.e is None or args.s is not None or parse_embedded_approx(args.query)[1]:
-        return False
-    if quantile_of(clean) is not None or spread_of(clean) is not None or extreme_of(clean) is not None:
+    """SUM / AVG / COUNT ... GROUP BY ... --e E without --s and outside an APPROX(...) wrapper: the query the error-threshold form
+    of GROUP BY answers."""
+    if not _error_form_asked(args) or any(of(clean) is not None for of in (quantile_of, spread_of, extreme_of)):
         return False
     return bool(group_by_of(clean))
 
@@ -359,15 +559,7 @@ def max_groups_defect(clean: str, args):
         return None
     if not 1 <= mg <= 65536:
         return f"--max-groups {mg}: a GROUP BY holds 1 .. 65536 groups"
-    if args.e is not None:
-        return "--max-groups has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"
-    if spread_of(clean) is not None:
-        return "--max-groups has no VARIANCE / STDDEV form: GROUP BY over more than 1024 groups takes SUM, AVG or COUNT"
-    if extreme_of(clean) is not None:
-        return "--max-groups has no MIN / MAX form: GROUP BY over more than 1024 groups takes SUM, AVG or COUNT"
-    if re.search(r"BUCKET\s*\(", clean, flags=re.IGNORECASE):
-        return "--max-groups has no GROUP BY BUCKET(...) form: time buckets stop at 1024 buckets"
-    return None
+    return _refusal("--max-groups", clean, args)
 
 
 def per_group_defect(full: str, args) -> Optional[str]:
@@ -382,49 +574,15 @@ def per_group_defect(full: str, args) -> Optional[str]:
     for opt, given in (("--s", args.s is not None), ("--e", args.e is not None), ("--max-groups", getattr(args, "max_groups", None) is not None)):
         if given:
             return f"--per-group with {opt}: the budgeted GROUP BY reads a fixed number of rows per group from its own stratified sample (leave {opt} out)"
-    if re.search(r"\b(VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?)\s*\(", full, re.IGNORECASE):
-        return "--per-group has no VARIANCE / STDDEV form: the budgeted GROUP BY takes SUM, AVG or COUNT"
-    if re.search(r"\b(MIN|MAX)\s*\(", full, re.IGNORECASE):
-        return "--per-group has no MIN / MAX form: the budgeted GROUP BY takes SUM, AVG or COUNT"
-    if re.search(r"BUCKET\s*\(", full, flags=re.IGNORECASE):
-        return "--per-group has no GROUP BY BUCKET(...) form: the budget is per key of region or product_id"
-    if re.search(r"\bHAVING\b", full, re.IGNORECASE):
-        return "--per-group has no HAVING form"
-    if re.search(r"\bORDER\s+BY\b.*\bLIMIT\b", full, re.IGNORECASE | re.DOTALL):
-        return "--per-group has no ORDER BY ... LIMIT form"
-    if not re.search(r"\b(SUM|AVG|COUNT)\s*\(", full, re.IGNORECASE):
-        return "--per-group takes SUM, AVG or COUNT ... GROUP BY region | product_id"
+    why = _refusal("--per-group", full, args)
+    if why is not None:
+        return why
     gb = group_by_of(full)
     if not gb:
         return "--per-group needs GROUP BY region | product_id"
     if len(gb) != 1:
         return "--per-group with two columns: the budgeted GROUP BY takes one key column (region or product_id)"
     return None
-
-
-_TOP_CLAUSE = re.compile(r"\bORDER\s+BY\s+(SUM|AVG|COUNT)\s*\(\s*(\*|amount)\s*\)\s*(ASC|DESC)?\s*\bLIMIT\s+([+-]?\d+)\s*;?\s*$", re.IGNORECASE)
-
-
-def _top_clause(clean: str):
-    """The match of a claimed ORDER BY <agg> [ASC | DESC] LIMIT k, or None: see top_of."""
-    m = _TOP_CLAUSE.search(clean)
-    if not m:
-        return None
-    head, name = clean[:m.start()], m.group(1).upper()
-    if not re.search(r"\bGROUP\s+BY\b", head, re.IGNORECASE) or (m.group(2) == "*" and name != "COUNT"):
-        return None
-    named = [a for a in ("SUM", "AVG", "COUNT") if re.search(rf"\b{a}\s*\(", head, re.IGNORECASE)]  # (aggregate_of's order of preference)
-    return m if named and named[0] == name else None
-
-
-def top_of(clean: str) -> Optional[Tuple[int, bool]]:
-    """``... GROUP BY ... ORDER BY <agg> [ASC | DESC] LIMIT k`` with <agg> the select list's own aggregate — SUM(amount),
-    AVG(amount), COUNT(*) or COUNT(amount), named literally before the clause; letter case and blanks do not matter on either
-    side — -> (k, descending), SQL's default direction being ASC; None for every other query: ORDER BY a column name, an ordinal
-    or an aggregate the select list does not name, ORDER BY <agg> without LIMIT, no GROUP BY — those clauses stay ignored, as
-    they were."""
-    m = _top_clause(clean)
-    return None if m is None else (int(m.group(4)), (m.group(3) or "ASC").upper() == "DESC")
 
 
 def top_defect(clean: str, args) -> Optional[str]:
@@ -435,33 +593,7 @@ def top_defect(clean: str, args) -> Optional[str]:
         return None
     if not 1 <= top[0] <= 1024:
         return f"LIMIT {top[0]}: ORDER BY the aggregate takes a LIMIT of 1 .. 1024"
-    if args.e is not None:
-        return "ORDER BY the aggregate ... LIMIT has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"
-    if re.search(r"\b(VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?)\s*\(", clean, re.IGNORECASE):
-        return "ORDER BY the aggregate ... LIMIT has no VARIANCE / STDDEV form: the top groups are ordered by SUM, AVG or COUNT"
-    if re.search(r"\b(MIN|MAX)\s*\(", clean, re.IGNORECASE):
-        return "ORDER BY the aggregate ... LIMIT has no MIN / MAX form: the top groups are ordered by SUM, AVG or COUNT"
-    if re.search(r"BUCKET\s*\(", clean, flags=re.IGNORECASE):
-        return "ORDER BY the aggregate ... LIMIT has no GROUP BY BUCKET(...) form: time buckets are listed in time order"
-    return None
-
-
-_HAVING_CLAIM = re.compile(r"\bHAVING\s+(?=(?:SUM|AVG|COUNT)\s*\()(.*?)(?=\bORDER\s+BY\b|\bLIMIT\b|;|$)", re.IGNORECASE | re.DOTALL)
-
-
-def having_of(clean: str) -> Optional[str]:
-    """The text of a CLAIMED HAVING clause — what follows HAVING begins with SUM, AVG or COUNT and ``(``; letter case and blanks do
-    not matter — up to ORDER BY, LIMIT, ``;`` or the end, or None: every other ``HAVING ...`` (``having 1``, a column name, an
-    alias) stays ignored, as it was."""
-    m = _HAVING_CLAIM.search(clean)
-    return None if m is None else " ".join(m.group(1).split())
-
-
-def without_having(clean: str) -> str:
-    """The query without its claimed HAVING clause (unchanged when there is none): what the select list, WHERE, GROUP BY and
-    ORDER BY ... LIMIT are read from, so that an aggregate named only by the clause is not taken for the query's own."""
-    m = _HAVING_CLAIM.search(clean)
-    return clean if m is None else clean[:m.start()] + clean[m.end():]
+    return _refusal("top", clean, args)
 
 
 def having_defect(clean: str, args) -> Optional[str]:
@@ -479,15 +611,7 @@ def having_defect(clean: str, args) -> Optional[str]:
     rest = without_having(clean)
     if not re.search(r"\bGROUP\s+BY\b", rest, re.IGNORECASE):
         return "HAVING takes a GROUP BY query: it judges the groups' SUM, AVG or COUNT"
-    if args.e is not None:
-        return "HAVING has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"
-    if re.search(r"\b(VARIANCE|VAR_SAMP|VAR_POP|STDDEV(_SAMP|_POP)?)\s*\(", rest, re.IGNORECASE):
-        return "HAVING has no VARIANCE / STDDEV form: the groups are judged under SUM, AVG or COUNT"
-    if re.search(r"\b(MIN|MAX)\s*\(", rest, re.IGNORECASE):
-        return "HAVING has no MIN / MAX form: the groups are judged under SUM, AVG or COUNT"
-    if re.search(r"BUCKET\s*\(", rest, flags=re.IGNORECASE):
-        return "HAVING has no GROUP BY BUCKET(...) form: time buckets are not judged"
-    return None
+    return _refusal("HAVING", rest, args)
 
 
 def distinct_by_defect(clean: str, args) -> Optional[str]:
@@ -506,9 +630,10 @@ def distinct_by_defect(clean: str, args) -> Optional[str]:
         return str(e)
     if col is None:
         return "--distinct-by goes with a distinct count, e.g. \"SELECT COUNT(DISTINCT product_id) FROM sales\" --distinct-by region"
-    if args.e is not None:
-        return "--distinct-by has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"
-    if col == name and not re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
+    why = _refusal("--distinct-by", clean, args)
+    if why is not None:
+        return why
+    if col == name and not _grouped(clean, args):
         return f"--distinct-by {name}: COUNT(DISTINCT {col}) is counted per key of the other key column (every {name} holds one {name})"
     return None
 
@@ -544,6 +669,29 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def _query_defect(pq: ParsedQuery, args) -> Optional[str]:
+    """What keeps the query from running once its options have passed, found before the table is opened (None: nothing): the
+    bucket's own syntax, --series-by, the bucket's defects; else the family's arguments and refusals, the GROUP BY clause, the
+    key predicate, a grouped COUNT under --e.  A part of the query that cannot be read raises its ValueError."""
+    clean = pq.rest
+    bucket = pq.bucket  # before group_by: the comma inside the parentheses never reaches that property's split
+    why = (time_bucket_defect(clean, args) if bucket is not None else None) or series_by_defect(clean, args, bucket)
+    if why is not None or bucket is not None:
+        return why
+    family = pq.family[0]
+    why = _refusal(family, clean, args)
+    if why is not None:
+        return why
+    pq.group_by  # (read for its ValueError)
+    if pq.key_where is not None:
+        if args.e is not None:
+            return (f"the CLT sampler (--e) samples the whole table and has no form for the key predicate 'WHERE {pq.where}': "
+                    "give a sample percentage (--s) or none (exact)")
+        if family == "quantile":
+            return f"MEDIAN / PERCENTILE under the key predicate 'WHERE {pq.where}' are not supported yet"
+    return _refusal("GROUP BY", clean, args)
+
+
 def run(args, out=sys.stdout) -> int:
     if args.explain:
         for k, v in METHODS.items():
@@ -552,123 +700,27 @@ def run(args, out=sys.stdout) -> int:
     if not args.query:
         print("error: a query is required unless --explain is given", file=out)
         return 2
-    clean, _ = parse_embedded_approx(args.query)
-    why = per_group_defect(clean, args) or distinct_by_defect(clean, args)
+    pq = read_query(parse_embedded_approx(args.query)[0])
+    why = (per_group_defect(pq.text, args) or distinct_by_defect(pq.text, args) or having_defect(pq.text, args)
+           or max_groups_defect(pq.rest, args) or top_defect(pq.rest, args))  # (the first three read the query with its HAVING clause)
+    if why is None:
+        try:
+            why = _query_defect(pq, args)
+        except ValueError as e:
+            why = str(e)
     if why is not None:
         print(f"error: {why}", file=out)
         return 2
-    full = clean  # (with a claimed HAVING clause, which _run_on finds again)
-    why = having_defect(clean, args)
-    if why is not None:
-        print(f"error: {why}", file=out)
-        return 2
-    clean = without_having(clean)  # the rest of the query is read without it
-    why = max_groups_defect(clean, args) or top_defect(clean, args)
-    if why is not None:
-        print(f"error: {why}", file=out)
-        return 2
-    try:
-        bucket = time_bucket_of(clean)  # before group_by_of: the comma inside the parentheses never reaches that function's split
-    except ValueError as e:
-        print(f"error: {e}", file=out)
-        return 2
-    if bucket is None and getattr(args, "series_by", None) is not None:
-        print(f"error: {series_by_defect(clean, args, bucket)}", file=out)
-        return 2
-    if bucket is not None:
-        why = time_bucket_defect(clean, args) or series_by_defect(clean, args, bucket)
-        if why is not None:
-            print(f"error: {why}", file=out)
-            return 2
-        return _open_and_run(args, out, clean)
-    try:
-        quant = quantile_of(clean)
-    except ValueError as e:
-        print(f"error: {e}", file=out)
-        return 2
-    if quant is not None:
-        if args.e is not None:
-            print("error: quantiles have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
-            return 2
-        if re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
-            print("error: GROUP BY is not supported with MEDIAN / PERCENTILE", file=out)
-            return 2
-    if spread_of(clean) is not None and args.e is not None:
-        print("error: VARIANCE / STDDEV have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
-        return 2
-    if extreme_of(clean) is not None and args.e is not None:
-        print("error: MIN / MAX have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
-        return 2
-    try:
-        hist = histogram_of(clean)
-    except ValueError as e:
-        print(f"error: {e}", file=out)
-        return 2
-    if hist is not None:
-        if args.e is not None:
-            print("error: HISTOGRAM has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
-            return 2
-        if re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
-            print("error: GROUP BY is not supported with HISTOGRAM", file=out)
-            return 2
-    try:
-        distinct = distinct_of(clean)
-    except ValueError as e:
-        print(f"error: {e}", file=out)
-        return 2
-    if distinct is not None:
-        if args.e is not None:
-            print("error: COUNT(DISTINCT) has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
-            return 2
-        if re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
-            print("error: GROUP BY is not supported with COUNT(DISTINCT) (a count per group: leave the GROUP BY clause out and give --distinct-by region|product_id)", file=out)
-            return 2
-    try:
-        summary = summary_of(clean)
-    except ValueError as e:
-        print(f"error: {e}", file=out)
-        return 2
-    if summary is not None:
-        if args.e is not None:
-            print("error: SUMMARY has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)", file=out)
-            return 2
-        if re.search(r"GROUP\s+BY", clean, flags=re.IGNORECASE):
-            print("error: GROUP BY is not supported with SUMMARY", file=out)
-            return 2
-    try:
-        group_by_of(clean)
-    except ValueError as e:
-        print(f"error: {e}", file=out)
-        return 2
-    try:
-        key_where = key_where_of(clean)
-    except ValueError as e:
-        print(f"error: {e}", file=out)
-        return 2
-    if key_where is not None:
-        clause = where_clause_of(clean)
-        if args.e is not None:
-            print(f"error: the CLT sampler (--e) samples the whole table and has no form for the key predicate 'WHERE {clause}': "
-                  "give a sample percentage (--s) or none (exact)", file=out)
-            return 2
-        if quant is not None:
-            print(f"error: MEDIAN / PERCENTILE under the key predicate 'WHERE {clause}' are not supported yet", file=out)
-            return 2
-    if group_error_form(clean, args) and aggregate_of(clean) == "COUNT":
-        print("error: COUNT ... GROUP BY has no error-threshold (--e) form (a grouped COUNT has no interval to judge): "
-              "give a sample percentage (--s) or none (exact)", file=out)
-        return 2
-    return _open_and_run(args, out, full)
+    return _open_and_run(args, out, pq)
 
 
-def _open_and_run(args, out, clean) -> int:
+def _open_and_run(args, out, pq: ParsedQuery) -> int:
     """The query has passed the checks that need no table: open it — sharded over the ranks under torchrun — and run."""
     if not os.path.exists(args.db):
         print(f"error: database file '{args.db}' not found", file=out)
         return 1
     from . import aqe_backend
     qtype = determine_query_type(args.query, args)
-    agg = aggregate_of(clean)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "torch.distributed" in sys.modules and sys.modules["torch.distributed"].is_initialized():  # called from a program that has its group
         world = sys.modules["torch.distributed"].get_world_size()
@@ -690,134 +742,106 @@ def _open_and_run(args, out, clean) -> int:
             out = open(os.devnull, "w")
         try:
             db = ShardedBPlusDB(device_id=args.device if args.backend != "nccl" else None, collective=args.collective)
-            return _run_on(db, args, out, clean, qtype, agg, aqe_backend, f"{world} GPUs, sharded by row region")
+            return _run_on(db, args, out, pq.text, qtype, pq.aggregate, aqe_backend, f"{world} GPUs, sharded by row region", pq)
         finally:
             if own_group:
                 dist.barrier()
                 dist.destroy_process_group()
     db = aqe_backend.CustomBPlusDB(device_id=args.device)
-    return _run_on(db, args, out, clean, qtype, agg, aqe_backend, None)
+    return _run_on(db, args, out, pq.text, qtype, pq.aggregate, aqe_backend, None, pq)
 
 
-def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
+def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note, parsed: Optional[ParsedQuery] = None) -> int:
+    """Open the table, print the heading, run the query's runner, close the table.  `parsed` is the reading of `clean` when the
+    caller has one; `aqe_backend` is kept for the callers that pass it (the reading imports what it needs).  An exception leaves
+    the table open."""
     if not db.open_database(args.db):
         print(f"error: cannot open database: {args.db}", file=out)
         return 1
     db._path = ""  # a read-only session must not rewrite the file on close
     n = db.get_total_records()
     print(f"query: {args.query}\ndatabase: {args.db} ({n:,} records{', ' + sharded_note if sharded_note else ''})\ntype: {qtype}", file=out)
-    having = having_of(clean)
-    if having is not None:  # a claimed HAVING clause: the rest of the query is read without it, its aggregate included
-        clean = without_having(clean)
-        agg = aggregate_of(clean)
-    key_where = key_where_of(clean)
-    kw = {} if key_where is None else {"key_where": key_where}  # (passed only when there is a key predicate)
-    if key_where is not None:
-        print(f"predicate: WHERE {where_clause_of(clean)}", file=out)
-    if having is not None:
-        print(f"having: HAVING {having}", file=out)
+    pq = parsed if parsed is not None else read_query(clean)
+    if pq.having is not None:  # a claimed HAVING clause: the rest of the query is read without it, its aggregate included
+        agg = pq.aggregate
+    kw = {} if pq.key_where is None else {"key_where": pq.key_where}  # (passed only when there is a key predicate)
+    if pq.key_where is not None:
+        print(f"predicate: WHERE {pq.where}", file=out)
+    if pq.having is not None:
+        print(f"having: HAVING {pq.having}", file=out)
     t0 = time.perf_counter()
-    bucket = time_bucket_of(clean)
-    if bucket is not None:
-        return _run_time_series(db, args, out, clean, qtype, agg, bucket, aqe_backend, t0, kw)
-    quant = quantile_of(clean)
-    if quant is not None:
-        return _run_quantile(db, args, out, clean, qtype, quant, aqe_backend, t0)
-    spread = spread_of(clean)
-    if spread is not None:
-        return _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0, kw)
-    extreme = extreme_of(clean)
-    if extreme is not None:
-        return _run_extremes(db, args, out, clean, qtype, extreme, aqe_backend, t0, kw)
-    hist = histogram_of(clean)
-    if hist is not None:
-        return _run_histogram(db, args, out, clean, qtype, hist, aqe_backend, t0, kw)
-    distinct = distinct_of(clean)
-    if distinct is not None:
-        return _run_distinct(db, args, out, clean, qtype, distinct, aqe_backend, t0, kw)
-    if summary_of(clean) is not None:
-        return _run_summary(db, args, out, clean, qtype, aqe_backend, t0, kw)
-    gb = group_by_of(clean)
-    if gb and getattr(args, "per_group", None) is not None:
-        # --per-group K: a sample stratified on the key column, at most K rows of every group (aqe_reduce_grouped_budget)
-        groups = db.approx_group_by(agg, group_by=gb[0], per_group=int(args.per_group), seed=args.seed, where=aqe_backend.parse_where(clean), **kw)
-        ms = (time.perf_counter() - t0) * 1e3
-        info = db.last_budget_info or {"groups": len(groups), "fully_read_groups": 0, "sampled_rows": 0}
-        print(f"\nGROUP BY {gb[0].lower()} (at most {args.per_group:,} rows per group):", file=out)
-        shown = len(groups) if getattr(args, "all_groups", False) else MAX_GROUPS_SHOWN
-        for i, (key, g) in enumerate(groups.items()):
-            if i >= shown:
-                print(f"   ... and {len(groups) - shown:,} more groups ({len(groups):,} in all; --all-groups prints every one)", file=out)
-                break
-            print(f"   {key:>6}: {g.value:,.4f}   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})   n={g.n:,}   rows={g.rows:,}", file=out)
-        print(f"   {info['groups']:,} groups, {info['fully_read_groups']:,} read completely, {info['sampled_rows']:,} rows sampled", file=out)
-        print(f"   execution time: {ms:.2f} ms", file=out)
-        db.close_database()
-        return 0
-    if gb and group_error_form(clean, args):
-        # --e with GROUP BY: nested block levels until every group's interval is within the threshold (aqe_reduce_grouped_error)
-        groups = db.approx_group_by(agg, group_by=", ".join(gb), where=aqe_backend.parse_where(clean), error_percent=float(args.e), **kw)
-        ms = (time.perf_counter() - t0) * 1e3
-        info = db.last_group_error_info or {}
-        print(f"\nGROUP BY {', '.join(gb).lower()} (every group within ±{args.e:g}%, nested block sample):", file=out)
-        for key, g in groups.items():
-            print(f"   {key:>6}: {g.value:,.4f}   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})   n={g.n:,}", file=out)
-        if info:
-            how = "yes" if info["converged"] else f"no ({info['unsettled']} groups unsettled)"
-            print(f"   stopped at level {info['level']} of {info['levels'] - 1} ({info['sample_percent']:g}% of rows), converged: {how}, "
-                  f"widest: key {info['worst_key']} ±{info['worst_rel'] * 100.0:.4g}%", file=out)
-        print(f"   execution time: {ms:.2f} ms", file=out)
-        db.close_database()
-        return 0
-    if gb:  # one sweep, one bin per key (or per pair of keys), an interval per group (executor.cpp:202-321 semantics)
-        pct = args.s if args.s is not None else (100.0 if qtype == QUERY_EXACT else 10.0)
-        mg = getattr(args, "max_groups", None)
-        gkw = dict(kw) if mg is None else dict(kw, max_groups=mg)  # (passed only when the option is given)
-        top = top_of(clean)
-        if top is not None:  # ORDER BY the aggregate LIMIT k: the k best groups, selected on the device, in rank order
-            gkw.update(top=top[0], ascending=not top[1])
-            agg = _top_clause(clean).group(1).upper()  # (the aggregate the clause and the select list name, blanks or not)
-        if having is not None:  # HAVING: judged on the device, only the passing groups come back
-            gkw.update(having=having)
-        groups = db.approx_group_by(agg, group_by=", ".join(gb), sample_percent=pct, method="exact" if pct >= 100.0 else "rowid",
-                                    where=aqe_backend.parse_where(clean), **gkw)
-        ms = (time.perf_counter() - t0) * 1e3
-        print(f"\nGROUP BY {', '.join(gb).lower()} ({'exact' if pct >= 100.0 else f'rowid sample {pct:g}%'}):", file=out)
-        shown = len(groups) if (mg is None or top is not None or getattr(args, "all_groups", False)) else MAX_GROUPS_SHOWN
-        for i, (key, g) in enumerate(groups.items()):
-            if i >= shown:
-                print(f"   ... and {len(groups) - shown:,} more groups ({len(groups):,} in all; --all-groups prints every one)", file=out)
-                break
-            ci = f"   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})" if (args.ci and pct < 100.0) else ""
-            print(f"   {key:>6}: {g.value:,.4f}{ci}   n={g.n:,}", file=out)
-        if top is not None:
-            info = db.last_top_info or {"groups": len(groups), "listed": len(groups), "contenders": 0}
-            more = f"; {info['contenders']:,} more within the error of the last listed" if info["contenders"] > 0 else ""
-            print(f"   {info['groups']:,} groups, {info['listed']:,} listed{more}", file=out)
-        if having is not None:
-            h = db.last_having_info or {"groups": len(groups), "passed": len(groups), "passed_unsettled": 0, "failed_unsettled": 0}
-            print(f"   {h['groups']:,} groups, {h['passed']:,} pass HAVING ({h['passed_unsettled']:,} of them within the error of the threshold); "
-                  f"{h['failed_unsettled']:,} more could pass within their error", file=out)
-        print(f"   execution time: {ms:.2f} ms", file=out)
-        db.close_database()
-        return 0
+    if pq.bucket is not None:
+        rc = _run_time_series(db, args, out, pq, qtype, agg, t0, kw)
+    elif pq.family[0] == "plain":
+        rc = _run_plain(db, args, out, pq, qtype, agg, n, t0, kw)
+    else:
+        rc = _RUNNERS[pq.family[0]](db, args, out, pq, qtype, t0, kw)
+    db.close_database()
+    return rc
+
+
+# ---- what the runners share ----
+
+_METHOD_SAMPLERS = {"block": "block", "parallel": "region", "random": "random"}  # --method -> the sampler; any other: the runner's default
+
+
+def _sampling(args, qtype, grouped: bool = False) -> Tuple[str, float, str]:
+    """(method, sample percentage, label): exact without --s; with --s (or an APPROX(...) wrapper, at 10%) a sample — --method
+    block / parallel / random honoured, stride otherwise; a grouped form samples by rowid (exact at 100%)."""
+    if args.s is None and qtype != QUERY_EMBEDDED:
+        return "exact", 100.0, "exact"
+    pct = args.s if args.s is not None else 10.0
+    if grouped:
+        method = "exact" if pct >= 100.0 else "rowid"
+    else:
+        method = _METHOD_SAMPLERS.get(args.method or "", "stride")
+    return method, pct, "exact" if method == "exact" else f"{method} sampling ({pct}%)"
+
+
+def _num(v) -> str:
+    return "n/a" if v != v else f"{v:,.4f}"
+
+
+def _print_comparison(out, approx, exact, fmt="{:,.4f}".format) -> None:
+    print(f"\ncomparison:\n   approximate: {fmt(approx)}\n   exact:       {fmt(exact)}", file=out)
+    if exact != 0:
+        print(f"   actual error: {abs(approx - exact) / abs(exact) * 100:.4f}%", file=out)
+
+
+def _actual_error(a, x) -> str:
+    """One figure of several (MIN and MAX, a summary's lines): the error against a finite, non-zero exact figure, or nothing."""
+    return f"   actual error: {abs(a - x) / abs(x) * 100:.4f}%" if (x == x and a == a and x != 0 and abs(x) != float("inf")) else ""
+
+
+def _print_first(out, items, shown: int, line: Callable, what: str = "groups") -> None:
+    """One line per item for the first `shown` of them, then a count of the rest."""
+    items = list(items)
+    for item in items[:shown]:
+        print(line(item), file=out)
+    if len(items) > shown:
+        print(f"   ... and {len(items) - shown:,} more {what} ({len(items):,} in all; --all-groups prints every one)", file=out)
+
+
+# ---- the runners: (db, args, out, the parsed query, ...) -> the exit code; _run_on closes the table ----
+
+def _run_plain(db, args, out, pq, qtype, agg, n, t0, kw) -> int:
+    """SUM / AVG / COUNT, grouped or scalar."""
+    if pq.group_by:
+        return _run_grouped(db, args, out, pq, qtype, agg, t0, kw)
     if qtype == QUERY_EMBEDDED:
-        method = args.method or get_optimal_method_for_query(clean, n)
+        method = args.method or get_optimal_method_for_query(pq.rest, n)
         qtype = QUERY_CLT if method == "clt" else QUERY_RANDOM  # enhanced_aqe_cli.py:489-494
         e, s = 2.0, 10.0
-        if qtype == QUERY_CLT and key_where is not None:
+        if qtype == QUERY_CLT and pq.key_where is not None:
             print("note: the CLT sampler has no form for a key predicate (it samples the whole table): the query takes the sampled path (10%)", file=out)
             qtype = QUERY_RANDOM
     else:
         e, s = args.e if args.e is not None else 5.0, args.s if args.s is not None else 10.0
-    # `WHERE amount BETWEEN a AND b` / `>= a AND <= b` / `> a` (the façade's extraction, custom_scheduler.cpp:277-294) is
-    # honoured by every sampler that has a WHERE form; the reference CLI ignores it for scalar queries altogether
-    where = aqe_backend.parse_where(clean)
+    where = pq.amount_where
     if qtype == QUERY_RANDOM:
         # the reference CLI's own routing by table size when no method is named (enhanced_aqe_cli.py:178-186): memory stride
         # above 50 k rows, direct access above 10 k, the sequential sampler below
-        auto = "stride" if n > 50_000 else "direct_access" if n > 10_000 else "sequential"
-        m = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", auto)
+        m = _METHOD_SAMPLERS.get(args.method or "", "stride" if n > 50_000 else "direct_access" if n > 10_000 else "sequential")
         res = db.approx(agg, method=m, sample_percent=s, seed=args.seed, num_threads=args.threads, where=where, **kw)
         name = f"{m} sampling ({s}%)"
     elif qtype == QUERY_CLT:
@@ -836,25 +860,70 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note) -> int:
     print(f"   samples used: {res.n:,}   rounds: {res.rounds}   converged: {bool(res.converged)}", file=out)
     print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us, {res.achieved_GBps:.0f} GB/s algorithmic)", file=out)
     if args.compare and qtype != QUERY_EXACT:
-        exact = db.approx(agg, method="exact", where=where, **kw)
-        print(f"\ncomparison:\n   approximate: {res.value:,.4f}\n   exact:       {exact.value:,.4f}", file=out)
-        if exact.value != 0:
-            print(f"   actual error: {abs(res.value - exact.value) / abs(exact.value) * 100:.4f}%", file=out)
-    db.close_database()
+        _print_comparison(out, res.value, db.approx(agg, method="exact", where=where, **kw).value)
     return 0
 
 
-def _run_quantile(db, args, out, clean, qtype, quant, aqe_backend, t0) -> int:
-    """MEDIAN / PERCENTILE(_CONT, _DISC): exact without --s; with --s (or an APPROX(...) wrapper) a sample, --method block /
-    parallel / random honoured, stride otherwise."""
-    p, interp, fname = quant
-    where = aqe_backend.parse_where(clean)
-    if args.s is None and qtype != QUERY_EMBEDDED:
-        method, pct, name = "exact", 100.0, "exact"
-    else:
-        pct = args.s if args.s is not None else 10.0
-        method = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", "stride")
-        name = f"{method} sampling ({pct}%)"
+def _run_grouped(db, args, out, pq, qtype, agg, t0, kw) -> int:
+    """SUM / AVG / COUNT ... GROUP BY region | product_id | both: under a per-group row budget, under --e, or from one sweep."""
+    gb, where = pq.group_by, pq.amount_where
+    if getattr(args, "per_group", None) is not None:
+        # --per-group K: a sample stratified on the key column, at most K rows of every group (aqe_reduce_grouped_budget)
+        groups = db.approx_group_by(agg, group_by=gb[0], per_group=int(args.per_group), seed=args.seed, where=where, **kw)
+        ms = (time.perf_counter() - t0) * 1e3
+        info = db.last_budget_info or {"groups": len(groups), "fully_read_groups": 0, "sampled_rows": 0}
+        print(f"\nGROUP BY {gb[0].lower()} (at most {args.per_group:,} rows per group):", file=out)
+        _print_first(out, groups.items(), len(groups) if getattr(args, "all_groups", False) else MAX_GROUPS_SHOWN,
+                     lambda kg: f"   {kg[0]:>6}: {kg[1].value:,.4f}   ({kg[1].ci_lower:,.4f} - {kg[1].ci_upper:,.4f})   n={kg[1].n:,}   rows={kg[1].rows:,}")
+        print(f"   {info['groups']:,} groups, {info['fully_read_groups']:,} read completely, {info['sampled_rows']:,} rows sampled", file=out)
+        print(f"   execution time: {ms:.2f} ms", file=out)
+        return 0
+    if _error_form_asked(args):
+        # --e with GROUP BY: nested block levels until every group's interval is within the threshold (aqe_reduce_grouped_error)
+        groups = db.approx_group_by(agg, group_by=", ".join(gb), where=where, error_percent=float(args.e), **kw)
+        ms = (time.perf_counter() - t0) * 1e3
+        info = db.last_group_error_info or {}
+        print(f"\nGROUP BY {', '.join(gb).lower()} (every group within ±{args.e:g}%, nested block sample):", file=out)
+        for key, g in groups.items():
+            print(f"   {key:>6}: {g.value:,.4f}   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})   n={g.n:,}", file=out)
+        if info:
+            how = "yes" if info["converged"] else f"no ({info['unsettled']} groups unsettled)"
+            print(f"   stopped at level {info['level']} of {info['levels'] - 1} ({info['sample_percent']:g}% of rows), converged: {how}, "
+                  f"widest: key {info['worst_key']} ±{info['worst_rel'] * 100.0:.4g}%", file=out)
+        print(f"   execution time: {ms:.2f} ms", file=out)
+        return 0
+    # one sweep, one bin per key (or per pair of keys), an interval per group (executor.cpp:202-321 semantics)
+    pct = args.s if args.s is not None else (100.0 if qtype == QUERY_EXACT else 10.0)
+    mg, top, having = getattr(args, "max_groups", None), pq.top, pq.having
+    gkw = dict(kw) if mg is None else dict(kw, max_groups=mg)  # (passed only when the option is given)
+    if top is not None:  # ORDER BY the aggregate LIMIT k: the k best groups, selected on the device, in rank order
+        gkw.update(top=top[0], ascending=not top[1])
+        agg = top[2]
+    if having is not None:  # HAVING: judged on the device, only the passing groups come back
+        gkw.update(having=having)
+    groups = db.approx_group_by(agg, group_by=", ".join(gb), sample_percent=pct, method="exact" if pct >= 100.0 else "rowid", where=where, **gkw)
+    ms = (time.perf_counter() - t0) * 1e3
+    print(f"\nGROUP BY {', '.join(gb).lower()} ({'exact' if pct >= 100.0 else f'rowid sample {pct:g}%'}):", file=out)
+    ci = (lambda g: f"   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})") if (args.ci and pct < 100.0) else (lambda g: "")
+    _print_first(out, groups.items(), len(groups) if (mg is None or top is not None or getattr(args, "all_groups", False)) else MAX_GROUPS_SHOWN,
+                 lambda kg: f"   {kg[0]:>6}: {kg[1].value:,.4f}{ci(kg[1])}   n={kg[1].n:,}")
+    if top is not None:
+        info = db.last_top_info or {"groups": len(groups), "listed": len(groups), "contenders": 0}
+        more = f"; {info['contenders']:,} more within the error of the last listed" if info["contenders"] > 0 else ""
+        print(f"   {info['groups']:,} groups, {info['listed']:,} listed{more}", file=out)
+    if having is not None:
+        h = db.last_having_info or {"groups": len(groups), "passed": len(groups), "passed_unsettled": 0, "failed_unsettled": 0}
+        print(f"   {h['groups']:,} groups, {h['passed']:,} pass HAVING ({h['passed_unsettled']:,} of them within the error of the threshold); "
+              f"{h['failed_unsettled']:,} more could pass within their error", file=out)
+    print(f"   execution time: {ms:.2f} ms", file=out)
+    return 0
+
+
+def _run_quantile(db, args, out, pq, qtype, t0, kw) -> int:
+    """MEDIAN / PERCENTILE(_CONT, _DISC).  (No key-predicate form: `kw` is not passed on, run() refuses the query.)"""
+    p, interp, fname = pq.family[1]
+    where = pq.amount_where
+    method, pct, name = _sampling(args, qtype)
     res = db.approx_quantile(p, method=method, sample_percent=pct, where=where, interpolation=interp,
                              confidence_level=args.confidence, seed=args.seed, num_threads=args.threads)
     ms = (time.perf_counter() - t0) * 1e3
@@ -865,93 +934,58 @@ def _run_quantile(db, args, out, clean, qtype, quant, aqe_backend, t0) -> int:
     print(f"   samples used: {res.n:,}   passes: {res.passes}", file=out)
     print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
     if args.compare and method != "exact":
-        exact = db.approx_quantile(p, method="exact", where=where, interpolation=interp)
-        print(f"\ncomparison:\n   approximate: {res.value:,.4f}\n   exact:       {exact.value:,.4f}", file=out)
-        if exact.value != 0:
-            print(f"   actual error: {abs(res.value - exact.value) / abs(exact.value) * 100:.4f}%", file=out)
-    db.close_database()
+        _print_comparison(out, res.value, db.approx_quantile(p, method="exact", where=where, interpolation=interp).value)
     return 0
 
 
-def _run_spread(db, args, out, clean, qtype, spread, aqe_backend, t0, kw=None) -> int:
-    """VARIANCE / VAR_SAMP / VAR_POP / STDDEV / STDDEV_SAMP / STDDEV_POP: exact without --s; with --s (or an APPROX(...)
-    wrapper) a sample — --method block / parallel / random honoured, stride otherwise; GROUP BY region | product_id | both
-    samples by rowid, as the SUM / AVG / COUNT form does."""
-    kind, fname = spread
-    kw = kw or {}  # {"key_where": ...} when the WHERE clause names region / product_id
-    where = aqe_backend.parse_where(clean)
-    gb = group_by_of(clean)
-    if args.s is None and qtype != QUERY_EMBEDDED:
-        method, pct, name = "exact", 100.0, "exact"
-    else:
-        pct = args.s if args.s is not None else 10.0
-        if gb:
-            method = "exact" if pct >= 100.0 else "rowid"
-        else:
-            method = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", "stride")
-        name = "exact" if method == "exact" else f"{method} sampling ({pct}%)"
-    fmt = lambda v: "n/a" if v != v else f"{v:,.4f}"
+def _run_spread(db, args, out, pq, qtype, t0, kw) -> int:
+    """VARIANCE / VAR_SAMP / VAR_POP / STDDEV / STDDEV_SAMP / STDDEV_POP, scalar or GROUP BY region | product_id | both."""
+    kind, fname = pq.family[1]
+    where, gb = pq.amount_where, pq.group_by
+    method, pct, name = _sampling(args, qtype, grouped=bool(gb))
     if gb:
         groups = db.approx_spread(kind, method=method, sample_percent=pct, where=where, confidence_level=args.confidence,
                                   group_by=", ".join(gb), **kw)
         ms = (time.perf_counter() - t0) * 1e3
         print(f"\n{fname}(amount) GROUP BY {', '.join(gb).lower()} ({name}):", file=out)
         for key, g in groups.items():
-            ci = f"   ({fmt(g.ci_lower)} - {fmt(g.ci_upper)})" if (args.ci and method != "exact") else ""
-            print(f"   {key:>6}: {fmt(g.value)}{ci}   n={g.n:,}", file=out)
+            ci = f"   ({_num(g.ci_lower)} - {_num(g.ci_upper)})" if (args.ci and method != "exact") else ""
+            print(f"   {key:>6}: {_num(g.value)}{ci}   n={g.n:,}", file=out)
         print(f"   execution time: {ms:.2f} ms", file=out)
-        db.close_database()
         return 0
     res = db.approx_spread(kind, method=method, sample_percent=pct, where=where, confidence_level=args.confidence, seed=args.seed,
                            num_threads=args.threads, **kw)
     ms = (time.perf_counter() - t0) * 1e3
-    print(f"\n{name} {fname}(amount) result:\n   value: {fmt(res.value)}", file=out)
+    print(f"\n{name} {fname}(amount) result:\n   value: {_num(res.value)}", file=out)
     if args.ci and method != "exact":
-        print(f"   confidence interval ({args.confidence:g}, fourth moment): ({fmt(res.ci_lower)} - {fmt(res.ci_upper)})", file=out)
+        print(f"   confidence interval ({args.confidence:g}, fourth moment): ({_num(res.ci_lower)} - {_num(res.ci_upper)})", file=out)
     print(f"   samples used: {res.n:,}   mean: {res.mean:,.4f}", file=out)
     print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
     if args.compare and method != "exact":
-        exact = db.approx_spread(kind, method="exact", where=where, **kw)
-        print(f"\ncomparison:\n   approximate: {fmt(res.value)}\n   exact:       {fmt(exact.value)}", file=out)
-        if exact.value != 0:
-            print(f"   actual error: {abs(res.value - exact.value) / abs(exact.value) * 100:.4f}%", file=out)
-    db.close_database()
+        _print_comparison(out, res.value, db.approx_spread(kind, method="exact", where=where, **kw).value, _num)
     return 0
 
 
-def _run_extremes(db, args, out, clean, qtype, names, aqe_backend, t0, kw=None) -> int:
-    """MIN / MAX (either or both, from one call): exact without --s; with --s (or an APPROX(...) wrapper) a sample — --method
-    block / parallel / random honoured, stride otherwise; GROUP BY region | product_id | both samples by rowid, as the other
-    grouped forms do."""
-    kw = kw or {}  # {"key_where": ...} when the WHERE clause names region / product_id
-    where = aqe_backend.parse_where(clean)
-    gb = group_by_of(clean)
-    if args.s is None and qtype != QUERY_EMBEDDED:
-        method, pct, name = "exact", 100.0, "exact"
-    else:
-        pct = args.s if args.s is not None else 10.0
-        if gb:
-            method = "exact" if pct >= 100.0 else "rowid"
-        else:
-            method = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", "stride")
-        name = "exact" if method == "exact" else f"{method} sampling ({pct}%)"
-    fmt = lambda v: "n/a" if v != v else f"{v:,.4f}"
+def _run_extremes(db, args, out, pq, qtype, t0, kw) -> int:
+    """MIN / MAX (either or both, from one call), scalar or GROUP BY region | product_id | both."""
+    names = pq.family[1]
+    where, gb = pq.amount_where, pq.group_by
+    method, pct, name = _sampling(args, qtype, grouped=bool(gb))
     if gb:
         groups = db.approx_extremes(method=method, sample_percent=pct, where=where, confidence_level=args.confidence, group_by=", ".join(gb), **kw)
         ms = (time.perf_counter() - t0) * 1e3
         print(f"\n{', '.join(f'{fn}(amount)' for fn in names)} GROUP BY {', '.join(gb).lower()} ({name}):", file=out)
         for key, g in groups.items():
-            vals = "   ".join(f"{fn.lower()} {fmt(getattr(g, fn.lower()))}" for fn in names) if len(names) > 1 else fmt(getattr(g, names[0].lower()))
+            vals = "   ".join(f"{fn.lower()} {_num(getattr(g, fn.lower()))}" for fn in names) if len(names) > 1 else _num(getattr(g, names[0].lower()))
             tail = f"   (beyond: at most {g.tail_fraction * 100:.4g}%)" if (args.ci and method != "exact" and g.n) else ""
             print(f"   {key:>6}: {vals}{tail}   n={g.n:,}", file=out)
         print(f"   execution time: {ms:.2f} ms", file=out)
-        db.close_database()
         return 0
     res = db.approx_extremes(method=method, sample_percent=pct, where=where, confidence_level=args.confidence, seed=args.seed,
                              num_threads=args.threads, **kw)
     ms = (time.perf_counter() - t0) * 1e3
     for fn in names:
-        print(f"\n{name} {fn}(amount) result:\n   value: {fmt(getattr(res, fn.lower()))}", file=out)
+        print(f"\n{name} {fn}(amount) result:\n   value: {_num(getattr(res, fn.lower()))}", file=out)
         if args.ci and method != "exact" and res.n:
             print(f"   with confidence {args.confidence:g}, at most {res.tail_fraction * 100:.4g}% of qualifying rows lie "
                   f"{'below' if fn == 'MIN' else 'above'} it", file=out)
@@ -961,31 +995,22 @@ def _run_extremes(db, args, out, clean, qtype, names, aqe_backend, t0, kw=None) 
         exact = db.approx_extremes(method="exact", where=where, **kw)
         for fn in names:
             a, x = getattr(res, fn.lower()), getattr(exact, fn.lower())
-            print(f"\ncomparison ({fn}):\n   approximate: {fmt(a)}\n   exact:       {fmt(x)}", file=out)
-            if x == x and a == a and x != 0 and abs(x) != float("inf"):
-                print(f"   actual error: {abs(a - x) / abs(x) * 100:.4f}%", file=out)
-    db.close_database()
+            print(f"\ncomparison ({fn}):\n   approximate: {_num(a)}\n   exact:       {_num(x)}", file=out)
+            if _actual_error(a, x):
+                print(_actual_error(a, x), file=out)
     return 0
 
 
-def _run_histogram(db, args, out, clean, qtype, hist, aqe_backend, t0, kw=None) -> int:
-    """HISTOGRAM(amount, B [, lo, hi]): exact without --s; with --s (or an APPROX(...) wrapper) a sample — --method block /
-    parallel / random honoured, stride otherwise.  One line per bucket: [e_i, e_{i+1})  estimate  (interval with --ci)  count."""
-    kw = kw or {}  # {"key_where": ...} when the WHERE clause names region / product_id
-    bins, rng = hist
-    where = aqe_backend.parse_where(clean)
-    if args.s is None and qtype != QUERY_EMBEDDED:
-        method, pct, name = "exact", 100.0, "exact"
-    else:
-        pct = args.s if args.s is not None else 10.0
-        method = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", "stride")
-        name = f"{method} sampling ({pct}%)"
+def _run_histogram(db, args, out, pq, qtype, t0, kw) -> int:
+    """HISTOGRAM(amount, B [, lo, hi]).  One line per bucket: [e_i, e_{i+1})  estimate  (interval with --ci)  count."""
+    bins, rng = pq.family[1]
+    where = pq.amount_where
+    method, pct, name = _sampling(args, qtype)
     try:
         res = db.approx_histogram(bins=bins, range=rng, method=method, sample_percent=pct, where=where, confidence_level=args.confidence,
                                   seed=args.seed, num_threads=args.threads, **kw)
     except ValueError as e:  # (a constant column without a range)
         print(f"error: {e}", file=out)
-        db.close_database()
         return 2
     ms = (time.perf_counter() - t0) * 1e3
     exact = None
@@ -1002,21 +1027,15 @@ def _run_histogram(db, args, out, clean, qtype, hist, aqe_backend, t0, kw=None) 
         print(f"   exact below: {exact.below:,}   exact above: {exact.above:,}", file=out)
     print(f"   samples used: {res.n:,}", file=out)
     print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
-    db.close_database()
     return 0
 
 
-def _run_distinct(db, args, out, clean, qtype, column, aqe_backend, t0, kw=None) -> int:
-    """COUNT(DISTINCT col) / APPROX_COUNT_DISTINCT(col): exact without --s; with --s (or an APPROX(...) wrapper) a sample —
-    --method block / parallel / random honoured, stride otherwise.  A sample's figure counts the sampled rows' values."""
-    kw = kw or {}  # {"key_where": ...} when the WHERE clause names region / product_id
-    where = aqe_backend.parse_where(clean)
-    if args.s is None and qtype != QUERY_EMBEDDED:
-        method, pct, name = "exact", 100.0, "exact"
-    else:
-        pct = args.s if args.s is not None else 10.0
-        method = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", "stride")
-        name = f"{method} sampling ({pct}%)"
+def _run_distinct(db, args, out, pq, qtype, t0, kw) -> int:
+    """COUNT(DISTINCT col) / APPROX_COUNT_DISTINCT(col), in all or per key of --distinct-by.  A sample's figure counts the sampled
+    rows' values."""
+    column = pq.family[1]
+    where = pq.amount_where
+    method, pct, name = _sampling(args, qtype)
     by = getattr(args, "distinct_by", None)
     if by is not None:  # one count per key of `by`: a line per group, then the summary
         by = str(by).strip().lower()
@@ -1038,7 +1057,6 @@ def _run_distinct(db, args, out, clean, qtype, column, aqe_backend, t0, kw=None)
         if method != "exact":
             print("   note: the figures count the distinct values among the sampled rows: lower bounds for the table", file=out)
         print(f"   execution time: {ms:.2f} ms (kernels {info['kernel_ms'] * 1e3:.1f} us)", file=out)
-        db.close_database()
         return 0
     res = db.approx_distinct(column=column, method=method, sample_percent=pct, where=where, confidence_level=args.confidence, seed=args.seed,
                              num_threads=args.threads, **kw)
@@ -1054,42 +1072,30 @@ def _run_distinct(db, args, out, clean, qtype, column, aqe_backend, t0, kw=None)
     print(f"   samples used: {res.n:,}", file=out)
     print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
     if args.compare and method != "exact":
-        exact = db.approx_distinct(column=column, method="exact", where=where, **kw)
-        print(f"\ncomparison:\n   approximate: {fmt(res.value)}\n   exact:       {fmt(exact.value)}", file=out)
-        if exact.value != 0:
-            print(f"   actual error: {abs(res.value - exact.value) / abs(exact.value) * 100:.4f}%", file=out)
-    db.close_database()
+        _print_comparison(out, res.value, db.approx_distinct(column=column, method="exact", where=where, **kw).value, fmt)
     return 0
 
 
-def _run_summary(db, args, out, clean, qtype, aqe_backend, t0, kw=None) -> int:
-    """SUMMARY(amount) / DESCRIBE(amount): exact without --s; with --s (or an APPROX(...) wrapper) a sample — --method block /
-    parallel / random honoured, stride otherwise.  One fused sweep; one line per figure, in a fixed order: count, sum, mean,
-    stddev, min, max, skewness, kurtosis."""
-    kw = kw or {}  # {"key_where": ...} when the WHERE clause names region / product_id
-    where = aqe_backend.parse_where(clean)
-    if args.s is None and qtype != QUERY_EMBEDDED:
-        method, pct, name = "exact", 100.0, "exact"
-    else:
-        pct = args.s if args.s is not None else 10.0
-        method = {"block": "block", "parallel": "region", "random": "random"}.get(args.method or "", "stride")
-        name = f"{method} sampling ({pct}%)"
+def _run_summary(db, args, out, pq, qtype, t0, kw) -> int:
+    """SUMMARY(amount) / DESCRIBE(amount).  One fused sweep; one line per figure, in a fixed order: count, sum, mean, stddev, min,
+    max, skewness, kurtosis."""
+    where = pq.amount_where
+    method, pct, name = _sampling(args, qtype)
     res = db.approx_summary(method=method, sample_percent=pct, where=where, confidence_level=args.confidence, seed=args.seed,
                             num_threads=args.threads, **kw)
     ms = (time.perf_counter() - t0) * 1e3
-    fmt = lambda v: "n/a" if v != v else f"{v:,.4f}"
     ci = args.ci and method != "exact"
-    between = lambda r: f"   ({fmt(r.ci_lower)} - {fmt(r.ci_upper)})" if ci else ""
+    between = lambda r: f"   ({_num(r.ci_lower)} - {_num(r.ci_upper)})" if ci else ""
     tail = lambda side: f"   (with confidence {args.confidence:g}, at most {res.tail_fraction * 100:.4g}% of qualifying rows lie {side} it)" if (ci and res.n) else ""
     print(f"\n{name} SUMMARY(amount) result:", file=out)
-    print(f"   count:    {fmt(res.count.value)}", file=out)
-    print(f"   sum:      {fmt(res.sum.value)}{between(res.sum)}", file=out)
-    print(f"   mean:     {fmt(res.mean.value)}{between(res.mean)}", file=out)
-    print(f"   stddev:   {fmt(res.stddev.value)}{between(res.stddev)}", file=out)
-    print(f"   min:      {fmt(res.min)}{tail('below')}", file=out)
-    print(f"   max:      {fmt(res.max)}{tail('above')}", file=out)
-    print(f"   skewness: {fmt(res.skewness)}", file=out)
-    print(f"   kurtosis: {fmt(res.excess_kurtosis)}   (excess)", file=out)
+    print(f"   count:    {_num(res.count.value)}", file=out)
+    print(f"   sum:      {_num(res.sum.value)}{between(res.sum)}", file=out)
+    print(f"   mean:     {_num(res.mean.value)}{between(res.mean)}", file=out)
+    print(f"   stddev:   {_num(res.stddev.value)}{between(res.stddev)}", file=out)
+    print(f"   min:      {_num(res.min)}{tail('below')}", file=out)
+    print(f"   max:      {_num(res.max)}{tail('above')}", file=out)
+    print(f"   skewness: {_num(res.skewness)}", file=out)
+    print(f"   kurtosis: {_num(res.excess_kurtosis)}   (excess)", file=out)
     print(f"   samples used: {res.n:,}", file=out)
     print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
     if args.compare and method != "exact":
@@ -1098,72 +1104,47 @@ def _run_summary(db, args, out, clean, qtype, aqe_backend, t0, kw=None) -> int:
         for label, a, x in (("count", res.count.value, exact.count.value), ("sum", res.sum.value, exact.sum.value),
                             ("mean", res.mean.value, exact.mean.value), ("stddev", res.stddev.value, exact.stddev.value),
                             ("min", res.min, exact.min), ("max", res.max, exact.max)):
-            err = f"   actual error: {abs(a - x) / abs(x) * 100:.4f}%" if (x == x and a == a and x != 0 and abs(x) != float("inf")) else ""
-            print(f"   {label + ':':<8} {fmt(a)} / {fmt(x)}{err}", file=out)
-    db.close_database()
+            print(f"   {label + ':':<8} {_num(a)} / {_num(x)}{_actual_error(a, x)}", file=out)
     return 0
 
 
-def _run_time_series(db, args, out, clean, qtype, agg, bucket, aqe_backend, t0, kw=None) -> int:
-    """SUM / AVG / COUNT ... GROUP BY BUCKET(timestamp, W[, origin]): exact without --s; with --s (or an APPROX(...) wrapper) the
-    rowid sample the other grouped forms take.  The query's WHERE timestamp terms are the window, its amount and key terms keep
-    their meaning.  One line per bucket: start, value, interval (with --ci), n."""
+def _run_time_series(db, args, out, pq, qtype, agg, t0, kw) -> int:
+    """SUM / AVG / COUNT ... GROUP BY BUCKET(timestamp, W[, origin]), in all or per key of --series-by.  The query's WHERE timestamp
+    terms are the window, its amount and key terms keep their meaning.  One line per bucket: start, value, interval (with --ci),
+    n; with --series-by one line per cell in (key, start) order, the key in front, the first 50 cells unless --all-groups."""
     from .engine import parse_time_where
-    kw = kw or {}  # {"key_where": ...} when the WHERE clause names region / product_id
-    width, origin = bucket
-    window = parse_time_where(clean)
-    pct = args.s if args.s is not None else (10.0 if qtype == QUERY_EMBEDDED else 100.0)
-    method = "exact" if pct >= 100.0 else "rowid"
+    width, origin = pq.bucket
+    window = parse_time_where(pq.rest)
+    method, pct, _ = _sampling(args, qtype, grouped=True)
     series_by = getattr(args, "series_by", None)
-    if series_by is not None:
-        return _run_time_groups(db, args, out, clean, agg, bucket, window, pct, method, series_by.strip().lower(), aqe_backend, t0, kw)
+    by = {} if series_by is None else {"group_by": series_by.strip().lower()}
     try:
         series = db.approx_time_series(agg, width, origin=origin, time_between=window, sample_percent=pct, method=method,
-                                       where=aqe_backend.parse_where(clean), **kw)
-    except ValueError as e:  # (more than 1024 buckets, a timestamp range of 2^31 or more)
-        print(f"error: {e}", file=out)
-        db.close_database()
-        return 2
-    ms = (time.perf_counter() - t0) * 1e3
-    if window is not None:
-        print(f"window: timestamp {window[0]} .. {window[1]}", file=out)
-    print(f"\n{agg}(amount) GROUP BY BUCKET(timestamp, {width}{f', {origin}' if origin else ''}) ({'exact' if method == 'exact' else f'rowid sample {pct:g}%'}):", file=out)
-    for start, g in series.items():
-        ci = f"   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})" if (args.ci and method != "exact") else ""
-        print(f"   {start:>12}: {g.value:,.4f}{ci}   n={g.n:,}", file=out)
-    print(f"   execution time: {ms:.2f} ms", file=out)
-    db.close_database()
-    return 0
-
-
-def _run_time_groups(db, args, out, clean, agg, bucket, window, pct, method, column, aqe_backend, t0, kw) -> int:
-    """... GROUP BY BUCKET(timestamp, W[, origin]) --series-by region | product_id: one line per cell in (key, start) order, in the
-    bucket line's format with the key in front; the first 50 cells unless --all-groups."""
-    width, origin = bucket
-    try:
-        series = db.approx_time_series(agg, width, origin=origin, time_between=window, sample_percent=pct, method=method,
-                                       where=aqe_backend.parse_where(clean), group_by=column, **kw)
+                                       where=pq.amount_where, **by, **kw)
     except ValueError as e:  # (more than 1024 buckets, more than 65 536 cells, a timestamp range of 2^31 or more)
         print(f"error: {e}", file=out)
-        db.close_database()
         return 2
     ms = (time.perf_counter() - t0) * 1e3
     if window is not None:
         print(f"window: timestamp {window[0]} .. {window[1]}", file=out)
-    print(f"\n{agg}(amount) GROUP BY BUCKET(timestamp, {width}{f', {origin}' if origin else ''}) per {column} "
+    print(f"\n{agg}(amount) GROUP BY BUCKET(timestamp, {width}{f', {origin}' if origin else ''}){' per ' + by['group_by'] if by else ''} "
           f"({'exact' if method == 'exact' else f'rowid sample {pct:g}%'}):", file=out)
-    cells = [(key, start, g) for key, buckets in series.items() for start, g in buckets.items()]
-    shown = len(cells) if getattr(args, "all_groups", False) else MAX_GROUPS_SHOWN
-    for key, start, g in cells[:shown]:
-        ci = f"   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})" if (args.ci and method != "exact") else ""
-        print(f"   {key:>6} {start:>12}: {g.value:,.4f}{ci}   n={g.n:,}", file=out)
-    if len(cells) > shown:
-        print(f"   ... and {len(cells) - shown:,} more cells ({len(cells):,} in all; --all-groups prints every one)", file=out)
-    nb = len({start for b in series.values() for start in b})
-    print(f"   {len(series):,} keys, {nb:,} buckets, {len(cells):,} cells", file=out)
+    ci = (lambda g: f"   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})") if (args.ci and method != "exact") else (lambda g: "")
+    if not by:
+        for start, g in series.items():
+            print(f"   {start:>12}: {g.value:,.4f}{ci(g)}   n={g.n:,}", file=out)
+    else:
+        cells = [(key, start, g) for key, buckets in series.items() for start, g in buckets.items()]
+        _print_first(out, cells, len(cells) if getattr(args, "all_groups", False) else MAX_GROUPS_SHOWN,
+                     lambda c: f"   {c[0]:>6} {c[1]:>12}: {c[2].value:,.4f}{ci(c[2])}   n={c[2].n:,}", what="cells")
+        nb = len({start for b in series.values() for start in b})
+        print(f"   {len(series):,} keys, {nb:,} buckets, {len(cells):,} cells", file=out)
     print(f"   execution time: {ms:.2f} ms", file=out)
-    db.close_database()
     return 0
+
+
+_RUNNERS = {"quantile": _run_quantile, "spread": _run_spread, "extreme": _run_extremes, "histogram": _run_histogram,
+            "distinct": _run_distinct, "summary": _run_summary}
 
 
 def main(argv=None) -> int:
