@@ -448,6 +448,11 @@ def lib() -> C.CDLL:
         "aqe_filtered_grouped_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, C.c_int32, u32, vp, vp]),
         "aqe_filtered_grouped_finish": (C.c_int, [vp, P(Query), C.c_int32, u32, vp, vp, P(GroupResult), u32, P(u32)]),
         "aqe_filtered_from_sums": (C.c_int, [P(dbl), P(Query), u64, P(Result)]),
+        "aqe_reduce_windowed": (C.c_int, [vp, P(Query), P(KeyFilter), C.c_int64, C.c_int64, P(Result)]),
+        "aqe_reduce_windowed_spread": (C.c_int, [vp, P(Query), P(KeyFilter), C.c_int64, C.c_int64, C.c_int, P(SpreadResult)]),
+        "aqe_windowed_enqueue": (C.c_int, [vp, P(Query), P(KeyFilter), C.c_int64, C.c_int64, vp, vp]),
+        "aqe_last_window_tiles": (C.c_int, [vp, P(u64), P(u64)]),
+        "aqe_time_window_offsets": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, P(C.c_int32), P(C.c_int32)]),
         "aqe_reduce_grouped_pair": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), P(GroupResult), u32, P(u32)]),
         "aqe_reduce_grouped_pair_spread": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, P(C.c_int), P(SpreadGroupResult), u32, P(u32)]),
         "aqe_grouped_pair_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), P(i32), P(u32), vp, vp]),

@@ -31,7 +31,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as nat
-from .engine import RECORD_DTYPE, Engine, histogram_spec, key_filter_terms, make_budget_filter, make_key_filter, make_query, time_spec, wide_plan
+from .engine import RECORD_DTYPE, Engine, histogram_spec, key_filter_terms, make_budget_filter, make_key_filter, make_query, time_spec, time_window, wide_plan
 
 __all__ = ["Record", "CustomBPlusDB", "CustomApproximateScheduler", "CustomValidationResult",
            "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate", "SpreadEstimate", "SummaryEstimate", "BucketEstimate", "BudgetGroupEstimate"]
@@ -421,6 +421,25 @@ def _key_filter_for(key_where, method):
     return make_key_filter(key_where)
 
 
+def _time_window_for(time_between, key_where, method, error_percent=None, what="aggregates"):
+    """(t_lo, t_hi) and the compiled key filter (or None) of a ``time_between`` argument, checked before anything is launched:
+    the samplers without a windowed sweep, an error threshold, terms on both key columns, bounds that are not int64 integers
+    and an empty window are errors, not no-ops."""
+    if method in _NO_KEY_WHERE:
+        raise ValueError(f"method={method!r} has no WHERE timestamp form (time windows on {what} take the single-round family "
+                         "samplers and 'random')")
+    if error_percent is not None:
+        raise ValueError("a time window (time_between) samples a fixed percentage: error_percent= belongs to the CLT sampler, which has no WHERE timestamp form")
+    window = time_window(time_between)
+    f = None
+    if key_where is not None:
+        if sum(1 for c in ("region", "product_id") if key_where.get(c) is not None) > 1:
+            raise ValueError("a time window (time_between) takes a key predicate on region or on product_id, not on both: the time offsets "
+                             "take one of the sweep's two key slots")
+        f = make_key_filter(key_where)
+    return window, f
+
+
 _GROUP_COLUMNS = {"region": nat.GROUP_REGION, "product_id": nat.GROUP_PRODUCT}
 
 
@@ -796,13 +815,27 @@ class CustomBPlusDB:
     def approx(self, agg: str, method: str = "stride", sample_percent: float = 10.0, error_percent: Optional[float] = None,
                where: Optional[Tuple[float, float]] = None, seed: int = 42, num_threads: int = 4, block_size: int = 1000,
                confidence_level: float = 0.95, check_interval: int = 10, round0: int = 4096, growth: int = 4,
-               convention: str = "cli", id_between: Optional[Tuple[int, int]] = None, key_where: Optional[dict] = None) -> ApproxResult:
+               convention: str = "cli", id_between: Optional[Tuple[int, int]] = None, key_where: Optional[dict] = None,
+               time_between: Optional[Tuple[int, int]] = None) -> ApproxResult:
         """APPROX <agg>(amount): method in {"stride","random","random_device","block","page","parallel_block","region","clt",
         "exact","adaptive_block","stratified_block"}.  "random" is random_pointer_sample(seed) bit for bit (host mt19937 +
         Lemire index list, DB.cpp:856-882); "random_device" draws a simple random sample on the device (no index list).
         ``error_percent`` (CLT) is in percent, as the reference CLI's --e (enhanced_aqe_cli.py:414-415); the
         sample percentage then follows enhanced_aqe_cli.py:243-250.  ``key_where`` (parse_key_where's dictionary) keeps the
-        sampled rows whose region / product_id pass, exactly as ``where`` keeps an amount range."""
+        sampled rows whose region / product_id pass, exactly as ``where`` keeps an amount range.  ``time_between`` = (t_lo, t_hi)
+        keeps the sampled rows with t_lo <= timestamp <= t_hi, both inclusive, the same way — every sampled row counts in
+        ``visited``, the rows that pass in ``n``, and the estimators scale by N / visited (NOT approx_time_series' window, which
+        drops the rows outside it) — beside ``where`` and at most ONE key column of ``key_where``; tiles of the table whose
+        timestamps miss the window are not read.  CLT and the other samplers without a WHERE form, ``error_percent=``, terms
+        on both key columns, bounds that are not integers and t_lo > t_hi raise ValueError before anything is launched."""
+        if time_between is not None:
+            window, f = _time_window_for(time_between, key_where, method, error_percent)
+            q = self._approx_query(agg, method, sample_percent, None, where, seed, num_threads, block_size, confidence_level,
+                                   check_interval, round0, growth, convention, id_between)
+            res = _quantile_call(lambda: self._reduce_windowed(f, q, window))
+            if res.visited == 0:
+                raise RuntimeError("No samples collected")
+            return ApproxResult(res, method)
         if key_where is not None:
             f = _key_filter_for(key_where, method)
             q = self._approx_query(agg, method, sample_percent, error_percent, where, seed, num_threads, block_size, confidence_level,
@@ -1071,6 +1104,12 @@ class CustomBPlusDB:
     def _reduce_filtered(self, f, q):
         return self._eng().reduce_filtered(f, q)
 
+    def _reduce_windowed(self, f, q, window):
+        return self._eng().windowed(q, window, f)
+
+    def _spread_windowed(self, f, q, kind, window):
+        return self._eng().windowed_spread(q, window, kind, f)
+
     def _grouped_filtered(self, f, q, col):
         return self._eng().reduce_filtered_grouped(f, q, col)
 
@@ -1149,19 +1188,32 @@ class CustomBPlusDB:
     def approx_spread(self, kind: str = "var_samp", method: str = "stride", sample_percent: float = 10.0,
                       where: Optional[Tuple[float, float]] = None, id_between: Optional[Tuple[int, int]] = None, seed: int = 42,
                       confidence_level: float = 0.95, group_by: Optional[str] = None, num_threads: int = 4, block_size: int = 1000,
-                      key_where: Optional[dict] = None, max_groups: int = 1024, top: Optional[int] = None):
+                      key_where: Optional[dict] = None, max_groups: int = 1024, top: Optional[int] = None,
+                      time_between: Optional[Tuple[int, int]] = None):
         """APPROX VARIANCE / STDDEV(amount): ``kind`` is "var_samp" ("variance"), "var_pop", "stddev_samp" ("stddev") or
         "stddev_pop" of the sampled amounts X (WHERE and the key window applied) — numpy.var(X, ddof=1) and its kin, not scaled
         by the sampling fraction — with a large-sample normal interval from the fourth central moment; method "exact" reports
         [value, value].  method as approx_quantile ("exact", "stride", "block", "page", "parallel_block", "region", "random" ...;
         CLT, adaptive, stratified and random_device samplers raise ValueError), and "rowid" (approx_group_by's sample).  With
         ``group_by`` ("region" | "product_id", or both as approx_group_by takes them) the result is the key -> SpreadEstimate
-        mapping approx_group_by returns."""
+        mapping approx_group_by returns.  ``time_between`` = (t_lo, t_hi) keeps the sampled rows with t_lo <= timestamp <= t_hi
+        as approx() does (ungrouped, beside ``where`` and at most one key column of ``key_where``; ``group_by`` and "rowid" are a
+        ValueError)."""
         k = str(kind).strip().lower()
         if k not in _SPREAD_KINDS:
             raise ValueError(f"kind must be one of {sorted(_SPREAD_KINDS)}")
         _wide_groups_arg(max_groups, "VARIANCE / STDDEV")
         _top_arg(top, "VARIANCE / STDDEV")
+        if time_between is not None:
+            if group_by is not None:
+                raise ValueError("VARIANCE / STDDEV under a time window (time_between) has no GROUP BY form")
+            if method == "rowid":
+                raise ValueError("VARIANCE / STDDEV under a time window (time_between) takes approx()'s samplers, not 'rowid'")
+            window, f = _time_window_for(time_between, key_where, method, what="VARIANCE / STDDEV")
+            q = self._approx_query("SUM", method, sample_percent, None, where, seed, num_threads, block_size, confidence_level,
+                                   id_between=id_between)
+            q.confidence_level = float(confidence_level)
+            return SpreadEstimate(_quantile_call(lambda: self._spread_windowed(f, q, _SPREAD_KINDS[k], window)), k, method)
         if method in ("clt", "adaptive_block", "stratified_block", "random_device"):
             raise ValueError(f"VARIANCE / STDDEV do not take the {method} sampler (single-round family samplers and 'random' only)")
         f = None if key_where is None else _key_filter_for(key_where, method)

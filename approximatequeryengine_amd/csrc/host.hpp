@@ -107,6 +107,7 @@ struct aqe_time_scratch;  // timeseries.hip
 struct aqe_wide_scratch;  // wide_group.hip
 struct aqe_series_scratch;  // time_group.hip
 struct aqe_budget_scratch;  // budget_group.hip
+struct aqe_window_scratch;  // time_window.hip
 
 // The rows of one key column sorted by key (group_index.hip): what the budgeted GROUP BY sweeps.  The host mirrors of the
 // listed keys and segment offsets (at most 65 536 + 1 entries) are what a call plans its launch from.
@@ -204,6 +205,9 @@ struct aqe_ctx {
     aqe_group_index* gindex[2] = {nullptr, nullptr};  // [AQE_GROUP_REGION - 1], [AQE_GROUP_PRODUCT - 1]
     bool gindex_built_now[2] = {false, false};        // the most recent call that needed the index built it
     aqe_budget_scratch* budget = nullptr;
+    // WHERE timestamp windows on the ungrouped aggregates (time_window.hip): the sweep's scratch and the zone maps of the time
+    // arrays (the row-order column, its stride-major views), by array pointer; made on first use
+    aqe_window_scratch* window = nullptr;
     // diagnostics (aqe_last_load_policy): the instantiation the most recent launch of a visit_tile kernel was — 1 non-temporal,
     // 0 plain loads, -1 no such launch yet.  Index-list sweeps and the quantile pass have the plain one only.
     int last_nt = -1;
@@ -405,6 +409,10 @@ void wide_release(aqe_ctx* c);
 
 // time_group.hip
 void series_release(aqe_ctx* c);
+
+// time_window.hip
+void window_release(aqe_ctx* c);
+void window_forget(aqe_ctx* c, const int32_t* time_array);  // the array is about to be freed (null: all of them): its zone map goes
 
 // group_index.hip
 int ensure_group_index(aqe_ctx* c, int column);  // builds c->gindex[column - 1] on first use; sets gindex_built_now

@@ -49,6 +49,7 @@ void free_table(aqe_ctx* c) {
     if (c->sorted_amount) (void)hipFree(c->sorted_amount);
     if (c->sorted_row) (void)hipFree(c->sorted_row);
     group_index_release(c);
+    window_forget(c, nullptr);  // (the zone maps of the time column and of its views)
     for (int k = 0; k < 3; ++k) {
         if (c->keycol[k]) (void)hipFree(c->keycol[k]);
         c->keycol[k] = nullptr;
@@ -188,6 +189,7 @@ int ensure_sorted(aqe_ctx* c) {
 namespace {
 
 void free_view(aqe_ctx* c, StrideView& v) {
+    window_forget(c, v.keys[kTimeColumn - 1]);
     (void)hipFree(v.amount);
     for (int32_t* k : v.keys)
         if (k) (void)hipFree(k);
@@ -584,6 +586,7 @@ void aqe_destroy(aqe_ctx* c) {
     wide_release(c);
     series_release(c);
     budget_release(c);
+    window_release(c);
     free_table(c);
     free_ring(c);
     if (c->d_stamps) (void)hipFree(c->d_stamps);

@@ -413,6 +413,23 @@ def sharded_filtered(engine, key_filter, query, vec, all_reduce_sum: Callable, s
     return _swept_vector(vec, SPREAD_VEC, all_reduce_sum, stream, lambda *a: engine.filtered_enqueue(key_filter, query, *a), finish)
 
 
+def sharded_windowed(engine, query, time_between, vec, all_reduce_sum: Callable, stream: int = 0, kind=None, key_filter=None):
+    """SUM / AVG / COUNT (kind None) or VARIANCE / STDDEV (kind = SPREAD_*) under a time window ``time_between`` = (t_lo, t_hi)
+    across the ranks of a process group, collective: every rank converts the window against its own shard's time_min and sweeps
+    the part of the sample inside its shard into SPREAD_VEC shifted power sums of the rows that pass (aqe_windowed_enqueue; a
+    rank the window misses skips its tiles and contributes its visited count), ONE all-reduce SUM merges them and every rank
+    finishes the same vector with the filtered finishes.
+
+    vec     float64 tensor on the engine's device with room for SPREAD_VEC doubles
+    stream  raw handle of the stream the collective is issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    from ._native import SPREAD_VEC
+    if kind is None:
+        finish = lambda *a: engine.filtered_finish(query, *a)
+    else:
+        finish = lambda *a: engine.filtered_spread_finish(query, kind, *a)
+    return _swept_vector(vec, SPREAD_VEC, all_reduce_sum, stream, lambda *a: engine.windowed_enqueue(query, time_between, *a, key_filter=key_filter), finish)
+
+
 def sharded_filtered_group_by(engine, key_filter, query, group_column: int, bins, all_reduce_sum: Callable, all_reduce_max: Callable,
                               stream: int = 0, kind=None):
     """GROUP BY under a key filter across ranks: the key range is agreed (one MAX all-reduce of [-min, max], as sharded_group_by),

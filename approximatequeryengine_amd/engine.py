@@ -553,6 +553,35 @@ class Engine:
                                                         C.c_void_p(stream), out, max_groups, C.byref(n)))
         return list(out[: n.value])
 
+    # -- WHERE timestamp windows on the ungrouped aggregates (aqe_reduce_windowed and its kin; time_window.hip): key_filter may be None --
+    def windowed(self, query: Query, time_between, key_filter: "Optional[nat.KeyFilter]" = None) -> Result:
+        """SUM / AVG / COUNT over the sampled rows with t_lo <= timestamp <= t_hi (``time_between`` = (t_lo, t_hi), inclusive) that
+        also pass the key filter and the query's amount range: reduce_filtered's arithmetic — visited counts every sampled row, n
+        the rows that pass.  Tiles whose zone-map entries miss the window are not read (last_window_tiles)."""
+        lo, hi = time_window(time_between)
+        res = Result()
+        self._chk(nat.lib().aqe_reduce_windowed(self._h, C.byref(query), _filter_ref(key_filter), lo, hi, C.byref(res)))
+        return res
+
+    def windowed_spread(self, query: Query, time_between, kind: int = nat.SPREAD_VAR_SAMP, key_filter: "Optional[nat.KeyFilter]" = None) -> "nat.SpreadResult":
+        """VARIANCE / STDDEV under a time window: reduce_filtered_spread's arithmetic on the rows that pass."""
+        lo, hi = time_window(time_between)
+        out = nat.SpreadResult()
+        self._chk(nat.lib().aqe_reduce_windowed_spread(self._h, C.byref(query), _filter_ref(key_filter), lo, hi, int(kind), C.byref(out)))
+        return out
+
+    def windowed_enqueue(self, query: Query, time_between, dev_vec_ptr: int, stream: int = 0, key_filter: "Optional[nat.KeyFilter]" = None):
+        """This shard's SPREAD_VEC power sums of the rows that pass, into device memory (all-reduce SUM, then filtered_finish or
+        filtered_spread_finish); the window is converted against this shard's own time_min."""
+        lo, hi = time_window(time_between)
+        self._chk(nat.lib().aqe_windowed_enqueue(self._h, C.byref(query), _filter_ref(key_filter), lo, hi, C.c_void_p(dev_vec_ptr), C.c_void_p(stream)))
+
+    def last_window_tiles(self) -> Tuple[int, int]:
+        """Diagnostics: (tiles, skipped) of the most recent windowed sweep (aqe_last_window_tiles); (0, 0) before any."""
+        tiles, skipped = C.c_uint64(), C.c_uint64()
+        self._chk(nat.lib().aqe_last_window_tiles(self._h, C.byref(tiles), C.byref(skipped)))
+        return tiles.value, skipped.value
+
     # -- GROUP BY both key columns (aqe_reduce_grouped_pair and its kin): `columns` is the ordered pair (A, B), key_filter may be None --
     def reduce_grouped_pair(self, query: Query, columns: Sequence[int], key_filter: "Optional[nat.KeyFilter]" = None, max_groups: int = 1024):
         """SUM / AVG / COUNT per (a, b): list of GroupResult ascending by (a, b); ``key`` packs both (nat.group_key_unpack)."""
@@ -1042,6 +1071,38 @@ def time_spec(width: int, origin: int = 0, time_between=None) -> "nat.TimeSpec":
             raise ValueError(f"BUCKET: the timestamp window is empty (t_lo {lo} > t_hi {hi})")
         spec.t_lo, spec.t_hi, spec.has_window = lo, hi, 1
     return spec
+
+
+def time_window(time_between) -> Tuple[int, int]:
+    """The inclusive int64 pair (t_lo, t_hi) of a ``time_between`` argument.  ValueError for anything but two int64 integers with
+    t_lo <= t_hi."""
+    if time_between is None or isinstance(time_between, (str, bytes)) or not hasattr(time_between, "__len__") or len(time_between) != 2:
+        raise ValueError(f"time window: time_between takes (t_lo, t_hi), got {time_between!r}")
+    out = []
+    for v, what in zip(time_between, ("t_lo", "t_hi")):
+        try:
+            whole = not isinstance(v, bool) and int(v) == v
+        except (TypeError, ValueError):
+            whole = False
+        if not whole:
+            raise ValueError(f"time window: {what} must be an integer, got {v!r}")
+        if not _I64_MIN <= int(v) <= _I64_MAX:
+            raise ValueError(f"time window: {what} {v!r} does not fit int64")
+        out.append(int(v))
+    if out[0] > out[1]:
+        raise ValueError(f"time window: the window is empty (t_lo {out[0]} > t_hi {out[1]})")
+    return out[0], out[1]
+
+
+def time_window_offsets(time_min: int, time_max: int, t_lo: int, t_hi: int) -> Tuple[int, int]:
+    """aqe_time_window_offsets, host only: the window as inclusive int32 offsets relative to a shard's ``time_min``, clamped to
+    [0, time_max - time_min]; lo > hi when the window misses the shard.  Raises AqeError: ERR_INVALID for t_lo > t_hi,
+    ERR_UNSUPPORTED for a shard whose timestamps span 2^31 or more."""
+    lo, hi = C.c_int32(), C.c_int32()
+    rc = nat.lib().aqe_time_window_offsets(int(time_min), int(time_max), int(t_lo), int(t_hi), C.byref(lo), C.byref(hi))
+    if rc != nat.OK:
+        raise nat.AqeError(rc, (nat.lib().aqe_last_error(None) or b"").decode() or "time window: refused")
+    return lo.value, hi.value
 
 
 def time_bucket(ts: int, spec: "nat.TimeSpec") -> int:

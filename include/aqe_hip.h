@@ -1632,6 +1632,48 @@ AQE_API int aqe_budget_position(uint64_t seed, int32_t key, uint64_t rows, uint6
 AQE_API int aqe_budget_from_sums(int agg, const double* strata, uint32_t nstrata, int64_t key, aqe_budget_group_result* out);
 AQE_API int aqe_budget_plan(uint64_t local_rows, uint64_t ngroups, int64_t budget);
 
+/* ---- WHERE timestamp windows on the ungrouped aggregates, zone-map tile skipping (time_window.hip) --------------------------
+ * A time window is an inclusive int64 pair [t_lo, t_hi] and one more conjunct of `pass`, treated exactly as a key term is:
+ *     pass = sampled && amount range (aqe_query.has_where) && timestamp in [t_lo, t_hi] && (at most ONE key term)
+ * `visited` counts every sampled row and `n` the rows that pass.  SUM / AVG / COUNT are aqe_reduce_filtered's on those
+ * (N / visited scaling under q.convention), VARIANCE / STDDEV aqe_reduce_filtered_spread's.  This is NOT the window of
+ * aqe_time_spec: GROUP BY BUCKET(timestamp, W) drops the rows outside its window (they are in neither n nor visited) and
+ * scales by 100 / pct.  A sample none of whose rows pass — or a window that misses the table — is an answer with n == 0;
+ * only visited == 0 is "No samples collected".  t_lo > t_hi is AQE_ERR_INVALID.
+ * Samplers, row windows and refusals are aqe_reduce_filtered's: the single-round family samplers and the seeded
+ * AQE_M_RANDOM_POINTER (through its index list); CLT, adaptive, stratified, AQE_M_RANDOM_DEVICE and pair-family samplers are
+ * AQE_ERR_UNSUPPORTED by name.  `filter` may be NULL; terms on both key columns are AQE_ERR_UNSUPPORTED (the time offsets take
+ * key slot 0 of the row loop and one key column slot 1, as in k_time_buckets).  Needs the rows' timestamps
+ * (AQE_STAGE_KEEP_AOS, or a synthetic table, whose timestamp is the row number); a shard whose timestamps span 2^31 or more
+ * is refused as aqe_reduce_time_buckets refuses it (the time column is kept as int32 offsets).
+ *
+ * The sweep (k_window) reads 8 + 4 bytes per sampled row (+ 4 under a key term) of the tiles it reads, and its reduction is
+ * aqe_reduce_filtered's, so its answer is bit-identical from run to run.  Per time array (the row-order column, or a
+ * stride-major view of it) a zone map keeps {min, max} of every 1024 consecutive offsets — 8 bytes per 1024 rows, built on
+ * first use, dropped with the array.  Before a tile's loads the wave tests the zones the tile can touch (at most 64, else it
+ * reads) and SKIPS the tile when none meets the window: the sampled slots still count into visited, nothing is loaded, and
+ * every word of the answer is what reading the tile would have given.  The seeded random sampler's index list is read with
+ * no skip.  AQE_NT=0/1 picks the load flavour, which aqe_last_load_policy reports; AQE_ZONE_SKIP=0 (diagnostics, read per
+ * launch) reads every tile. */
+AQE_API int aqe_reduce_windowed(aqe_ctx* ctx, const aqe_query* q, const aqe_key_filter* filter /* may be NULL */, int64_t t_lo, int64_t t_hi,
+                                aqe_result* out);
+AQE_API int aqe_reduce_windowed_spread(aqe_ctx* ctx, const aqe_query* q, const aqe_key_filter* filter /* may be NULL */, int64_t t_lo, int64_t t_hi,
+                                       int kind, aqe_spread_result* out);
+/* Multi-GPU form: every rank sweeps its shard (the window is converted against the rank's own time_min),
+ *     aqe_windowed_enqueue(ctx, q, filter, t_lo, t_hi, dev_vec, stream)      this shard's AQE_SPREAD_VEC doubles
+ *                                                                            {n, P1, P2, P3, P4, visited, n c, 0}
+ *     <ONE all-reduce SUM of AQE_SPREAD_VEC doubles on `stream`>
+ *     aqe_filtered_finish / aqe_filtered_spread_finish                       as they are */
+AQE_API int aqe_windowed_enqueue(aqe_ctx* ctx, const aqe_query* q, const aqe_key_filter* filter /* may be NULL */, int64_t t_lo, int64_t t_hi,
+                                 double* dev_vec, void* stream);
+/* Diagnostics: the tiles of the most recent windowed sweep of this context and how many of them were skipped (the index
+ * list: its chunks, none skipped; before any such sweep: 0, 0).  Waits for the stream that sweep ran on. */
+AQE_API int aqe_last_window_tiles(aqe_ctx* ctx, uint64_t* tiles, uint64_t* skipped);
+/* Host only, no GPU and no context (aqe_last_error(NULL) has a refusal's text): the window as inclusive int32 offsets relative
+ * to a shard's time_min, clamped to [0, time_max - time_min]; *lo > *hi when the window misses the shard (or the shard is
+ * empty, time_min > time_max).  AQE_ERR_INVALID: t_lo > t_hi.  AQE_ERR_UNSUPPORTED: time_max - time_min >= 2^31. */
+AQE_API int aqe_time_window_offsets(int64_t time_min, int64_t time_max, int64_t t_lo, int64_t t_hi, int32_t* lo, int32_t* hi);
+
 #ifdef __cplusplus
 }
 #endif
