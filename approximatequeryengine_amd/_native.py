@@ -20,6 +20,7 @@ M_RANDOM_DEVICE = 18
 M_DIRECT_ACCESS = 19
 M_OPTIMIZED_SEQUENTIAL = 20
 GROUP_REGION, GROUP_PRODUCT = 1, 2
+GROUP_PAIR = 3  # both key columns at once: named only to be refused by the windowed GROUP BY
 
 
 def group_key_pack(a: int, b: int) -> int:
@@ -453,6 +454,8 @@ def lib() -> C.CDLL:
         "aqe_windowed_enqueue": (C.c_int, [vp, P(Query), P(KeyFilter), C.c_int64, C.c_int64, vp, vp]),
         "aqe_last_window_tiles": (C.c_int, [vp, P(u64), P(u64)]),
         "aqe_time_window_offsets": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, P(C.c_int32), P(C.c_int32)]),
+        "aqe_reduce_window_groups": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, C.c_int64, C.c_int64, P(GroupResult), u32, P(u32)]),
+        "aqe_window_groups_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, C.c_int64, C.c_int64, i32, u32, vp, vp]),
         "aqe_reduce_grouped_pair": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), P(GroupResult), u32, P(u32)]),
         "aqe_reduce_grouped_pair_spread": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, P(C.c_int), P(SpreadGroupResult), u32, P(u32)]),
         "aqe_grouped_pair_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), P(i32), P(u32), vp, vp]),

@@ -930,7 +930,8 @@ class CustomBPlusDB:
                         where: Optional[Tuple[float, float]] = None, block_size: int = 1000,
                         key_where: Optional[dict] = None, error_percent: Optional[float] = None,
                         max_percent: float = 100.0, max_groups=_LEFT_OUT, top: Optional[int] = None,
-                        ascending: bool = False, having=None, per_group: Optional[int] = None, seed: int = 42) -> "dict[str, GroupEstimate]":
+                        ascending: bool = False, having=None, per_group: Optional[int] = None, seed: int = 42,
+                        time_between: Optional[Tuple[int, int]] = None) -> "dict[str, GroupEstimate]":
         """APPROX <agg>(amount) ... GROUP BY region | product_id with a 95 % interval per group: the reference's
         execute_query_groupby_with_ci (executor.cpp:202-321; GroupResultWithCI = map<string, {value, ci_lower,
         ci_upper}>) in one sweep.  method "rowid" is that function's own sample (rowid % (100 / sample_percent) == 0);
@@ -971,7 +972,19 @@ class CustomBPlusDB:
         column, with ``where`` and ``key_where`` (a term on the grouped column included); the mapping holds
         BudgetGroupEstimate, whose ``rows`` is the group's exact size.  ``last_budget_info`` keeps {groups, sampled_rows,
         fully_read_groups, index_built}.  It does not combine with ``sample_percent``, ``method``, ``error_percent``,
-        ``max_groups``, ``top``, ``having`` or a column pair."""
+        ``max_groups``, ``top``, ``having`` or a column pair.
+
+        ``time_between`` = (t_lo, t_hi): GROUP BY one key column under WHERE timestamp BETWEEN t_lo AND t_hi, inclusive
+        (aqe_reduce_window_groups) — SUM / AVG / COUNT per group over the sampled rows inside the window, with the row rule of the
+        bucketed forms (approx_time_series), not approx()'s: a sampled row outside the window is in no group's ``visited``, a group
+        without a sampled row inside it is not listed, and the estimate is what one bucket covering the window would give.  Tiles
+        of a time-ordered table that the window misses are not read.  It combines with ``where``, ``key_where`` on the grouped
+        column, ``max_groups``, ``top`` / ``ascending`` and ``having`` (``last_top_info`` and ``last_having_info`` as without it);
+        a column pair, ``error_percent``, ``per_group``, a term on the other key column, a sampler without a windowed sweep and a
+        bad window raise ValueError before anything is launched."""
+        if time_between is not None:
+            return self._group_by_window(agg, group_by, sample_percent, method, where, block_size, key_where, error_percent, max_groups, top,
+                                         ascending, having, per_group, time_between)
         if per_group is not None:
             return self._group_by_budget(agg, group_by, per_group, seed, where, key_where,
                                          {"sample_percent": sample_percent is not None, "method": method is not None,
@@ -1026,6 +1039,77 @@ class CustomBPlusDB:
             f = _key_filter_for(key_where, method)
             return {str(r.key): GroupEstimate(r) for r in _quantile_call(lambda: self._grouped_filtered(f, q, col))}
         return {str(r.key): GroupEstimate(r) for r in self._grouped(q, col)}
+
+    _WINDOW_GROUP_METHODS = {"rowid": nat.M_ROWID_MOD, "stride": nat.M_MEMORY_STRIDE, "block": nat.M_BLOCK, "page": nat.M_PAGE, "exact": nat.M_EXACT}
+
+    def _group_by_window(self, agg, group_by, sample_percent, method, where, block_size, key_where, error_percent, max_groups, top, ascending,
+                         having, per_group, time_between):
+        """approx_group_by(time_between=...): the argument checks (before any table is needed), the call, the infos."""
+        if per_group is not None:
+            raise ValueError("per_group with time_between: the budgeted GROUP BY reads its own stratified sample, which has no WHERE timestamp form")
+        cols = group_columns(group_by)
+        if len(cols) == 2:
+            raise ValueError("GROUP BY region, product_id under a time window (time_between): the time offsets take one of the sweep's two key "
+                             "slots and one group column the other; a second group column would need a third key slot")
+        col = cols[0]
+        a = agg.upper()
+        if a not in _AGG:
+            raise ValueError(f"GROUP BY under a time window (time_between) takes SUM, AVG or COUNT, not {agg!r}")
+        method = "rowid" if method is None else method
+        if method not in self._WINDOW_GROUP_METHODS:
+            raise ValueError(f"method={method!r} has no WHERE timestamp form under GROUP BY (time windows on groups take 'rowid', 'stride', "
+                             "'block', 'page' and 'exact')")
+        window, _ = _time_window_for(time_between, None, method, error_percent, what="groups")
+        name = {nat.GROUP_REGION: "region", nat.GROUP_PRODUCT: "product_id"}
+        other = nat.GROUP_PRODUCT if col == nat.GROUP_REGION else nat.GROUP_REGION
+        f = None
+        if key_where is not None:
+            if key_where.get(name[other]) is not None:
+                raise ValueError(f"GROUP BY {name[col]} under a time window (time_between) takes a key predicate on {name[col]} only: a term on "
+                                 f"{name[other]} would need a third key slot")
+            f = make_key_filter(key_where)
+        hspec = None if having is None else _having_arg(having)
+        if max_groups is _LEFT_OUT:  # 1024, or under having what the wide entry accepts (a given 1024 stays 1024)
+            max_groups = nat.WIDE_MAX_BINS if hspec is not None else 1024
+        wide = _wide_groups_arg(max_groups)
+        k = _top_arg(top)
+        sample_percent = 10.0 if sample_percent is None else sample_percent
+        if k is not None:
+            self.last_top_info = None
+        if hspec is not None:
+            self.last_having_info = None
+        if self._table_missing():
+            return {}
+        bs = 4096 if (method == "page" and block_size == 1000) else block_size
+        q = make_query(self._WINDOW_GROUP_METHODS[method], sample_percent, agg=_AGG[a], where=where, block_size=int(bs))
+        groups, hinfo, tinfo = _quantile_call(lambda: self._grouped_window(f, q, col, window, int(max_groups), wide, hspec, k, not ascending))
+        if hinfo is not None:
+            self.last_having_info = hinfo.as_dict()
+        if tinfo is not None:
+            self.last_top_info = _top_info_dict(tinfo, False)
+        return {str(r.key): GroupEstimate(r) for r in groups}
+
+    def _grouped_window(self, f, q, col, window, max_groups, wide, hspec, k, descending):
+        """(list of GroupResult, HavingInfo or None, TopInfo or None) of one GROUP BY under a time window.  The plain list is the
+        single-GPU entry; top-N and HAVING sweep the bins (window_groups_enqueue_bins) and go through the existing finishes, a
+        world of one."""
+        eng = self._eng()
+        lo, hi = eng.group_key_range(col)
+        if hi < lo:
+            return [], None, None  # an empty table
+        span = hi - lo + 1
+        if hspec is None and k is None:
+            if not wide and span > 1024:
+                raise nat.AqeError(nat.ERR_UNSUPPORTED, "group column spans more than 1024 distinct values")
+            return eng.window_groups(q, col, window, f, max_groups), None, None
+        if span > nat.WIDE_MAX_BINS:
+            raise nat.AqeError(nat.ERR_UNSUPPORTED, f"GROUP BY under a time window: the group column spans {span} distinct values, more than 65536 bins")
+        with eng.device_doubles(nat.WIDE_BIN * span) as bins:
+            eng.window_groups_enqueue_bins(q, col, window, lo, span, bins, 0, f)
+            if hspec is not None:
+                return eng.grouped_having_finish(q, [lo], [span], bins, hspec, k, descending, 0, max_groups)
+            groups, info = eng.grouped_top_finish(q, [lo], [span], bins, k, descending, 0)
+            return groups, None, info
 
     last_budget_info: Optional[dict] = None  # of the most recent approx_group_by(per_group=...)
 

@@ -470,6 +470,22 @@ _REFUSALS = {
          "--time-where has no COUNT(DISTINCT) form: a WHERE timestamp window is honoured by SUM, AVG, COUNT, VARIANCE and STDDEV"),
         (_names("summary"), "--time-where has no SUMMARY form: a WHERE timestamp window is honoured by SUM, AVG, COUNT, VARIANCE and STDDEV"),
         (lambda q, args: len(key_where_of(q) or ()) > 1, "--time-where takes a key predicate on ONE of region / product_id: the time offsets take one of the sweep's two key slots")),
+    "--group-time-where": (
+        (lambda q, args: not _grouped(q, args), "--group-time-where takes a GROUP BY region | product_id query: it makes the WHERE clause's timestamp terms count "
+                                                "per group (the ungrouped aggregates take --time-where)"),
+        (lambda q, args: len(group_by_of(q) or ()) > 1, "--group-time-where has no form for a pair of group columns: the time offsets take one of the sweep's "
+                                                                 "two key slots and one group column the other; a second one would need a third key slot"),
+        (_has_e, "--group-time-where has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
+        (lambda q, args: getattr(args, "per_group", None) is not None, "--group-time-where has no --per-group form: the budgeted GROUP BY reads its own stratified sample"),
+        (_names("spread"), "--group-time-where has no VARIANCE / STDDEV form: GROUP BY under a timestamp window takes SUM, AVG or COUNT"),
+        (_names("extreme"), "--group-time-where has no MIN / MAX form: GROUP BY under a timestamp window takes SUM, AVG or COUNT"),
+        (_names("quantile"), "--group-time-where has no MEDIAN / PERCENTILE form: GROUP BY under a timestamp window takes SUM, AVG or COUNT"),
+        (_names("histogram"), "--group-time-where has no HISTOGRAM form: GROUP BY under a timestamp window takes SUM, AVG or COUNT"),
+        (lambda q, args: distinct_of(q) is not None or re.search(rf"\b{_COUNT_DISTINCT}|\b{_APPROX_DISTINCT}\s*\(", q, re.IGNORECASE),
+         "--group-time-where has no COUNT(DISTINCT) form: GROUP BY under a timestamp window takes SUM, AVG or COUNT"),
+        (_names("summary"), "--group-time-where has no SUMMARY form: GROUP BY under a timestamp window takes SUM, AVG or COUNT"),
+        (lambda q, args: any(c != group_by_of(q)[0].lower() for c in (key_where_of(q) or ())),
+         "--group-time-where takes a key predicate on the group column only: a term on the other key column would need a third key slot")),
     "GROUP BY": (
         (_grouped_count, "COUNT ... GROUP BY has no error-threshold (--e) form (a grouped COUNT has no interval to judge): "
                          "give a sample percentage (--s) or none (exact)"),),
@@ -546,6 +562,25 @@ def time_where_defect(pq: "ParsedQuery", args) -> Optional[str]:
     if window is None:
         return None
     return _refusal("--time-where", pq.rest, args)
+
+
+def group_time_where_of(pq: "ParsedQuery", args) -> Optional[Tuple[int, int]]:
+    """The inclusive window (t_lo, t_hi) that --group-time-where makes count per group: the timestamp terms of the WHERE clause of a
+    query without BUCKET( — or None: no flag, a bucketed query, or no timestamp term, which all run as they always did.
+    ValueError, quoting the term, for what parse_time_where refuses."""
+    if not getattr(args, "group_time_where", False) or pq.bucket is not None:
+        return None
+    from .engine import parse_time_where
+    return parse_time_where(pq.rest)
+
+
+def group_time_where_defect(pq: "ParsedQuery", args) -> Optional[str]:
+    """What keeps a query under --group-time-where from running, found before the table is opened (None: nothing, or the flag
+    changes nothing): no GROUP BY, a pair of group columns, --e, --per-group, an aggregate family without a windowed grouped form,
+    a key term on the other key column."""
+    if group_time_where_of(pq, args) is None:
+        return None
+    return _refusal("--group-time-where", pq.rest, args)
 
 
 def _error_form_asked(args) -> bool:
@@ -698,6 +733,9 @@ def build_parser() -> argparse.ArgumentParser:
                    "(region or product_id), from one sweep; at most 65536 cells (keys x buckets)")
     p.add_argument("--time-where", dest="time_where", action="store_true", help="honour the WHERE clause's timestamp terms in a query without BUCKET(: "
                    "SUM / AVG / COUNT / VARIANCE / STDDEV of the rows with t_lo <= timestamp <= t_hi (without the flag such a term is ignored)")
+    p.add_argument("--group-time-where", dest="group_time_where", action="store_true", help="honour the WHERE clause's timestamp terms in a GROUP BY region | "
+                   "product_id query without BUCKET(: SUM / AVG / COUNT per group of the rows with t_lo <= timestamp <= t_hi, also under HAVING, "
+                   "ORDER BY ... LIMIT and --max-groups (without the flag such a term is ignored)")
     p.add_argument("--distinct-by", dest="distinct_by", metavar="COLUMN", help="with COUNT(DISTINCT col): one count per key of COLUMN (region or product_id), "
                    "from one sweep; at most 1024 groups")
     p.add_argument("--device", type=int, default=0)
@@ -740,7 +778,7 @@ def run(args, out=sys.stdout) -> int:
         return 2
     pq = read_query(parse_embedded_approx(args.query)[0])
     try:
-        why = time_where_defect(pq, args)  # (None without --time-where: nothing below changes)
+        why = time_where_defect(pq, args) or group_time_where_defect(pq, args)  # (None without the flags: nothing below changes)
     except ValueError as e:
         why = str(e)
     if why is not None:
@@ -816,6 +854,10 @@ def _run_on(db, args, out, clean, qtype, agg, aqe_backend, sharded_note, parsed:
         print(f"having: HAVING {pq.having}", file=out)
     window = time_where_of(pq, args)
     if window is not None:  # (passed only under --time-where with a timestamp term)
+        kw = dict(kw, time_between=window)
+        print(f"window: timestamp {window[0]} .. {window[1]}", file=out)
+    window = group_time_where_of(pq, args)
+    if window is not None:  # (passed only under --group-time-where with a timestamp term)
         kw = dict(kw, time_between=window)
         print(f"window: timestamp {window[0]} .. {window[1]}", file=out)
     t0 = time.perf_counter()

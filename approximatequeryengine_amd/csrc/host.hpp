@@ -108,6 +108,7 @@ struct aqe_wide_scratch;  // wide_group.hip
 struct aqe_series_scratch;  // time_group.hip
 struct aqe_budget_scratch;  // budget_group.hip
 struct aqe_window_scratch;  // time_window.hip
+struct aqe_wgroup_scratch;  // window_group.hip
 
 // The rows of one key column sorted by key (group_index.hip): what the budgeted GROUP BY sweeps.  The host mirrors of the
 // listed keys and segment offsets (at most 65 536 + 1 entries) are what a call plans its launch from.
@@ -208,6 +209,8 @@ struct aqe_ctx {
     // WHERE timestamp windows on the ungrouped aggregates (time_window.hip): the sweep's scratch and the zone maps of the time
     // arrays (the row-order column, its stride-major views), by array pointer; made on first use
     aqe_window_scratch* window = nullptr;
+    // GROUP BY under a timestamp window (window_group.hip): the slices' partials, the summed bins and the tile words, made on first use
+    aqe_wgroup_scratch* wgroup = nullptr;
     // diagnostics (aqe_last_load_policy): the instantiation the most recent launch of a visit_tile kernel was — 1 non-temporal,
     // 0 plain loads, -1 no such launch yet.  Index-list sweeps and the quantile pass have the plain one only.
     int last_nt = -1;
@@ -413,6 +416,14 @@ void series_release(aqe_ctx* c);
 // time_window.hip
 void window_release(aqe_ctx* c);
 void window_forget(aqe_ctx* c, const int32_t* time_array);  // the array is about to be freed (null: all of them): its zone map goes
+struct Zone;  // zone_probe.hpp: {min, max} of 1024 consecutive time offsets
+// The zone map of the time array `t` of `n` elements (the row-order column or a stride-major view of it), built on first use.
+int ensure_zones(aqe_ctx* c, const int32_t* t, uint64_t n, const Zone** out);
+// The pinned pair {tiles, skipped} of aqe_last_window_tiles, as the device sees it; the launch on `s` becomes the most recent one.
+int window_counts(aqe_ctx* c, hipStream_t s, unsigned long long** dev_counts);
+
+// window_group.hip
+void window_group_release(aqe_ctx* c);
 
 // group_index.hip
 int ensure_group_index(aqe_ctx* c, int column);  // builds c->gindex[column - 1] on first use; sets gindex_built_now

@@ -33,19 +33,14 @@
 #include "key_term.hpp"
 #include "spread_core.hpp"
 #include "sweep_host.hpp"
+#include "zone_probe.hpp"
 
 namespace aqe {
 namespace {
 
-constexpr unsigned kZoneShift = 10, kZoneRows = 1u << kZoneShift;  // elements of the time array per zone
 constexpr int64_t kMaxWindowSpan = (1ll << 31) - 1;                 // ensure_time's bound
 constexpr int kFuseNone = 0, kFuseResult = 1, kFuseSpread = 2;
 static_assert(kSpVec == 8, "vector layout of include/aqe_hip.h");
-static_assert(kZoneRows == 64 * 16, "one wave per zone, 16 elements per lane");
-
-struct Zone {
-    int32_t min, max;
-};
 
 // ---- the zone map -------------------------------------------------------------------------------------------------------------
 
@@ -114,77 +109,7 @@ struct WindowLaunch {
 };
 static_assert(sizeof(WindowLaunch) <= 4096, "kernel arguments are limited to 4 KB");
 
-// A tile's place in its family, as visit_tile decodes it.
-struct TileGeom {
-    u64 j, seg_len, step, seg_ord0, ord_lo, ord_hi, row_base, col0, pitch;
-    int form;  // 0 dense (two ordinals per lane and load), 1 linear (pages), 2 strided
-};
-template <typename FamPtr>
-__device__ __forceinline__ TileGeom tile_geom(const SweepCommon& sw, FamPtr fams, u64 t) {
-    const auto& F = fams[find_family(fams, sw.nfam, t)];
-    const u64 lt = t - F.tile_begin;
-    u64 seg, j;
-    if (F.tiles_per_seg == 0) { seg = F.seg_lo; j = F.j_lo + lt; }
-    else { seg = F.seg_lo + lt / F.tiles_per_seg; j = lt % F.tiles_per_seg; }
-    TileGeom g;
-    g.j = j;
-    g.seg_len = F.seg_len;
-    g.step = F.step;
-    g.seg_ord0 = seg * F.seg_len;
-    g.ord_lo = F.ord_lo;
-    g.ord_hi = F.ord_hi;
-    g.row_base = F.row0 + seg * F.pitch - sw.shard_lo;
-    g.col0 = F.row0 - sw.shard_lo;
-    g.pitch = F.pitch;
-    g.form = (sw.dense16 && is_dense16(F.step, F.flags, F.seg_len)) ? 0 : (F.flags & kFamLinear) ? 1 : 2;
-    return g;
-}
-
-// The verdict on a tile, in flight: the lane's zone of the tile's element range (when the range is one the map can judge).
-struct Probe {
-    bool can;     // wave-uniform: the range is valid and spans at most 64 zones
-    bool active;  // this lane holds a zone of it
-    Zone z;
-};
-
-// The inclusive element range [e_lo, e_hi] of the time array that holds every slot of the tile with ok == true (a superset),
-// then lane i's load of zone e_lo / 1024 + i.  A range the arithmetic cannot vouch for — empty, past the array, wider than 64
-// zones — is read and tested per row.
-template <typename FamPtr>
-__device__ __forceinline__ Probe probe_tile(const WindowLaunch& a, FamPtr fams, u64 t, int lane) {
-    Probe p;
-    p.can = p.active = false;
-    p.z = Zone{0, 0};
-    const TileGeom g = tile_geom(a.sw, fams, t);
-    u64 e_lo, e_hi;
-    bool valid = g.seg_len > 0;
-    if (g.form == 0) {  // dense: ordinals [j 1024, (j + 1) 1024) of the segment, cut at its end — an unaligned tile touches two zones
-        const u64 o0 = g.j * kDenseTileOrdinals, o1 = o0 + kDenseTileOrdinals < g.seg_len ? o0 + kDenseTileOrdinals : g.seg_len;
-        valid = valid && o0 < o1;
-        e_lo = g.row_base + o0;
-        e_hi = g.row_base + o1 - 1;
-    } else if (g.form == 1) {  // linear: ordinals [T0, T0 + 512) cut at ord_hi, over the segments they fall into
-        const u64 T0 = g.j * kTileOrdinals, last = T0 + kTileOrdinals < g.ord_hi ? T0 + kTileOrdinals : g.ord_hi;
-        valid = valid && T0 < last;
-        const u64 sl = valid ? g.seg_len : 1;
-        const u64 seg0 = T0 / sl, seg1 = (valid ? last - 1 : 0) / sl;
-        e_lo = g.col0 + seg0 * g.pitch;
-        e_hi = g.col0 + seg1 * g.pitch + (g.seg_len - 1) * g.step;
-    } else {  // strided: ordinals [j 512, (j + 1) 512) of the segment, cut at its end, `step` elements apart
-        const u64 o0 = g.j * kTileOrdinals, o1 = o0 + kTileOrdinals < g.seg_len ? o0 + kTileOrdinals : g.seg_len;
-        valid = valid && o0 < o1;
-        e_lo = g.row_base + o0 * g.step;
-        e_hi = g.row_base + (o1 - 1) * g.step;
-    }
-    e_lo = uniform64(e_lo);
-    e_hi = uniform64(e_hi);
-    valid = __builtin_amdgcn_readfirstlane(valid ? 1 : 0) != 0 && e_lo <= e_hi && e_hi < a.n_elems;
-    const u64 z_lo = e_lo >> kZoneShift, z_hi = e_hi >> kZoneShift;
-    p.can = valid && z_hi - z_lo < 64;
-    p.active = p.can && z_lo + static_cast<u64>(lane) <= z_hi;
-    if (p.active) p.z = a.zones[z_lo + static_cast<u64>(lane)];  // (z_hi < nzones: e_hi < n_elems)
-    return p;
-}
+// (Zone, TileGeom, tile_geom, Probe and probe_tile are zone_probe.hpp's: k_window_groups shares them.)
 
 // How many of the lane's slots of the tile are sampled rows: the `ok` predicates of visit_tile's paths, which need no load.
 template <typename FamPtr>
@@ -282,14 +207,14 @@ __global__ __launch_bounds__(kBlockThreads) void k_window(WindowLaunch a) {
         Probe cur;
         cur.can = cur.active = false;
         cur.z = Zone{0, 0};
-        if (judge && wave_id < a.ntiles) cur = probe_tile(a, fams, wave_id, lane);
+        if (judge && wave_id < a.ntiles) cur = probe_tile(a.sw, a.zones, a.n_elems, fams, wave_id, lane);
         for (u64 t = wave_id; t < a.ntiles; t += wave_stride) {
             // the next tile's zones are on their way while this tile is visited
             const u64 tn = t + wave_stride;
             Probe nxt;
             nxt.can = nxt.active = false;
             nxt.z = Zone{0, 0};
-            if (judge && tn < a.ntiles) nxt = probe_tile(a, fams, tn, lane);
+            if (judge && tn < a.ntiles) nxt = probe_tile(a.sw, a.zones, a.n_elems, fams, tn, lane);
             const bool meets = cur.active && !empty && cur.z.min <= whi && cur.z.max >= wlo;
             if (cur.can && __ballot(meets) == 0ull) {
                 nv += count_tile(a.sw, fams, t, lane);  // no load of amount, time or key
@@ -405,11 +330,15 @@ int ensure_scratch(aqe_ctx* c) {
     });
 }
 
+}  // namespace
+
 // The zone map of the time array `t` of `n` elements: built on the context's stream on first use, and waited for (the sweep may
-// run on another stream).
+// run on another stream).  (host.hpp: the grouped sweep of window_group.hip asks too; the scratch is made when it is not there.)
 int ensure_zones(aqe_ctx* c, const int32_t* t, uint64_t n, const Zone** out) {
     *out = nullptr;
     if (!t || n == 0) return AQE_OK;
+    const int have = ensure_scratch(c);
+    if (have != AQE_OK) return have;
     auto& maps = c->window->maps;
     auto it = maps.find(t);
     if (it != maps.end() && it->second.n_elems == n) {
@@ -430,6 +359,20 @@ int ensure_zones(aqe_ctx* c, const int32_t* t, uint64_t n, const Zone** out) {
     maps.emplace(t, std::move(m));
     return AQE_OK;
 }
+
+// The pinned pair {tiles, skipped} aqe_last_window_tiles reads, as the device sees it, for a windowed launch of another unit on
+// the stream `s`: that launch becomes the most recent one.
+int window_counts(aqe_ctx* c, hipStream_t s, unsigned long long** dev_counts) {
+    const int rc = ensure_scratch(c);
+    if (rc != AQE_OK) return rc;
+    aqe_window_scratch* sc = c->window;
+    sc->last_stream = s;
+    sc->launched = true;
+    *dev_counts = sc->h_counts.dev();
+    return AQE_OK;
+}
+
+namespace {
 
 constexpr Wording kWindowWords{"time windows do not take the ", "a time window has no GROUP BY form"};
 

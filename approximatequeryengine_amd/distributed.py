@@ -567,6 +567,44 @@ def sharded_group_by_having(engine, query, columns, bins, all_reduce_sum: Callab
         return engine.grouped_having_finish(query, kmin, span, b.data_ptr(), having, k, descending, stream, max_groups)
 
 
+def sharded_group_by_window(engine, query, group_column: int, time_between, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0,
+                            key_filter=None, max_groups: int = 65536, k: Optional[int] = None, descending: bool = True, having=None, narrow: bool = False):
+    """GROUP BY one key column under a time window ``time_between`` = (t_lo, t_hi) across ranks, collective: ONE MAX all-reduce
+    of the key range [-min, max] as sharded_group_by_wide does (more than 65 536 bins is refused on every rank alike, before
+    the sweep; ``narrow``: more than 1024, in the narrow GROUP BY's words); every rank converts the window against its own shard's
+    time_min and bins the part of the sample inside its shard and inside the window into span x WIDE_BIN sums
+    (aqe_window_groups_enqueue_bins; a rank the window misses skips its tiles and contributes zeros, as an empty shard does), ONE
+    all-reduce SUM merges them and every rank finishes the same bins with the EXISTING finishes: the list ascending by key
+    (aqe_grouped_wide_finish), with ``k`` the k best groups (sharded_group_by_top's), with ``having`` the passing groups or the k
+    best of them (sharded_group_by_having's).  Returns (list of GroupResult, HavingInfo or None, TopInfo or None), the same on every
+    rank; an empty table gives ([], None, None), and a plain list without a group is AqeError "No samples collected", as at the
+    single-GPU entry.
+
+    bins    float64 tensor on the engine's device with room for WIDE_BIN * span doubles (at most WIDE_BIN * 65 536)
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    from ._native import ERR_INVALID, ERR_UNSUPPORTED, WIDE_BIN, AqeError
+    from .engine import wide_plan
+    with _on_stream(stream, bins) as stream:
+        agreed = _agree_keys(engine, [int(group_column)], bins, all_reduce_max)
+        if agreed is None:
+            return [], None, None  # an empty table
+        kmin, span = agreed[0][0], agreed[1][0] - agreed[0][0] + 1
+        if narrow and having is None and k is None and span > 1024:
+            raise AqeError(ERR_UNSUPPORTED, "group column spans more than 1024 distinct values")
+        b = _take(bins, WIDE_BIN * wide_plan([span])[0])
+        engine.window_groups_enqueue_bins(query, group_column, time_between, kmin, span, b.data_ptr(), stream, key_filter)
+        all_reduce_sum(b)
+        if having is not None:
+            return engine.grouped_having_finish(query, [kmin], [span], b.data_ptr(), having, k, descending, stream, max_groups)
+        if k is not None:
+            groups, info = engine.grouped_top_finish(query, [kmin], [span], b.data_ptr(), k, descending, stream)
+            return groups, None, info
+        groups = engine.grouped_wide_finish(query, [kmin], [span], b.data_ptr(), stream, max_groups)
+        if len(groups) == 0:  # no bin has a sampled row inside the window: the single-GPU entry's status, on every rank alike
+            raise AqeError(ERR_INVALID, "No samples collected")
+        return groups, None, None
+
+
 def sharded_extremes(engine, query, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
     """MIN / MAX across the ranks of a process group (engine.Engine interface), collective: every rank sweeps the part of the
     sample inside its shard into EXTREME_VEC doubles (aqe_extremes_enqueue, under ``key_filter`` when there is one), ONE

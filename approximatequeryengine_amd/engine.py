@@ -5,6 +5,7 @@ The Engine owns an ``aqe_ctx``; every number it returns was computed by the HIP 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import weakref
 from typing import Optional, Sequence, Tuple
@@ -576,11 +577,44 @@ class Engine:
         lo, hi = time_window(time_between)
         self._chk(nat.lib().aqe_windowed_enqueue(self._h, C.byref(query), _filter_ref(key_filter), lo, hi, C.c_void_p(dev_vec_ptr), C.c_void_p(stream)))
 
+    @contextlib.contextmanager
+    def device_doubles(self, count: int):
+        """``count`` doubles of device memory for the length of a ``with`` block (aqe_device_malloc / aqe_device_free): the raw
+        device pointer, as the enqueue and finish entries take it."""
+        dev = C.c_void_p()
+        self._chk(nat.lib().aqe_device_malloc(self._h, 8 * max(int(count), 1), C.byref(dev)))
+        try:
+            yield dev.value
+        finally:
+            nat.lib().aqe_device_free(self._h, dev)
+
     def last_window_tiles(self) -> Tuple[int, int]:
         """Diagnostics: (tiles, skipped) of the most recent windowed sweep (aqe_last_window_tiles); (0, 0) before any."""
         tiles, skipped = C.c_uint64(), C.c_uint64()
         self._chk(nat.lib().aqe_last_window_tiles(self._h, C.byref(tiles), C.byref(skipped)))
         return tiles.value, skipped.value
+
+    # -- GROUP BY one key column under a time window (aqe_reduce_window_groups and its kin; window_group.hip): key_filter may be None --
+    def window_groups(self, query: Query, group_column, time_between, key_filter: "Optional[nat.KeyFilter]" = None, max_groups: int = nat.WIDE_MAX_BINS):
+        """SUM / AVG / COUNT per group of ``group_column`` over the sampled rows with t_lo <= timestamp <= t_hi (``time_between`` =
+        (t_lo, t_hi), inclusive): list of GroupResult ascending by key.  The bucketed forms' row rule, not windowed()'s: a sampled
+        row outside the window is in no group's visited; a group without a sampled row inside the window is not listed.  Tiles
+        whose zone-map entries miss the window are not read (last_window_tiles).  Both columns at once is AqeError(ERR_UNSUPPORTED)."""
+        lo, hi = time_window(time_between)
+        out = self._group_buf(max_groups)
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_reduce_window_groups(self._h, _filter_ref(key_filter), C.byref(query), _window_group_column(group_column), lo, hi, out,
+                                                     max_groups, C.byref(n)))
+        return list((nat.GroupResult * n.value).from_buffer_copy(out)) if n.value else []
+
+    def window_groups_enqueue_bins(self, query: Query, group_column, time_between, key_min: int, span: int, dev_bins_ptr: int, stream: int = 0,
+                                   key_filter: "Optional[nat.KeyFilter]" = None):
+        """This shard's span x WIDE_BIN sums under the window into device memory, in grouped_wide_enqueue_bins' layout (all-reduce
+        SUM, then grouped_wide_finish, grouped_top_finish or grouped_having_finish with one column); the window is converted
+        against this shard's own time_min."""
+        lo, hi = time_window(time_between)
+        self._chk(nat.lib().aqe_window_groups_enqueue_bins(self._h, _filter_ref(key_filter), C.byref(query), _window_group_column(group_column), lo, hi,
+                                                           int(key_min), int(span), C.c_void_p(dev_bins_ptr), C.c_void_p(stream)))
 
     # -- GROUP BY both key columns (aqe_reduce_grouped_pair and its kin): `columns` is the ordered pair (A, B), key_filter may be None --
     def reduce_grouped_pair(self, query: Query, columns: Sequence[int], key_filter: "Optional[nat.KeyFilter]" = None, max_groups: int = 1024):
@@ -1516,6 +1550,17 @@ def _two(values, fill):
 
 def _filter_ref(key_filter):
     return None if key_filter is None else C.byref(key_filter)
+
+
+def _window_group_column(group_column) -> int:
+    """The group column of a windowed GROUP BY as the C ABI takes it: one column code, or a sequence of them — both columns
+    travel as GROUP_PAIR, which the library refuses by name."""
+    if isinstance(group_column, (int, np.integer)):
+        return int(group_column)
+    cols = [int(c) for c in group_column]
+    if len(cols) == 1:
+        return cols[0]
+    return nat.GROUP_PAIR if sorted(cols) == [nat.GROUP_REGION, nat.GROUP_PRODUCT] else 0
 
 
 _U64 = (1 << 64) - 1

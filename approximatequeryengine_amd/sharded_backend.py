@@ -30,7 +30,7 @@ from . import _native as nat
 from .aqe_backend import ApproxResult, CustomBPlusDB
 from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, mailbox_all_reduce, mailbox_from_torch_group, shard_bounds, sharded_adaptive_plan,
                           sharded_distinct, sharded_distinct_groups, sharded_extremes, sharded_filtered, sharded_filtered_group_by, sharded_group_by, sharded_group_by_budget, sharded_group_by_error,
-                          sharded_group_by_having, sharded_group_by_pair, sharded_group_by_spread, sharded_group_by_top, sharded_group_by_wide,
+                          sharded_group_by_having, sharded_group_by_pair, sharded_group_by_spread, sharded_group_by_top, sharded_group_by_wide, sharded_group_by_window,
                           sharded_group_extremes, sharded_histogram, sharded_quantiles, sharded_spread, sharded_stratified_plan, sharded_summary,
                           sharded_time_groups, sharded_time_series, sharded_windowed, torch_all_reduce, torch_host_all_reduce)
 from .engine import RECORD_DTYPE, Batch, Engine
@@ -315,6 +315,12 @@ class ShardedBPlusDB(CustomBPlusDB):
 
     def _grouped_having(self, f, q, cols, having, k, descending, max_groups):
         return self._sharded(sharded_group_by_having, None, q, cols, having=having, k=k, descending=descending, key_filter=f, max_groups=max_groups)
+
+    # GROUP BY under a time window (time_between=): one MAX all-reduce of the key range, one all-reduce SUM of span x 4 sums, every
+    # rank's window converted against its own time_min, then the wide finish, the selection or the judging on every rank's device
+    def _grouped_window(self, f, q, col, window, max_groups, wide, hspec, k, descending):
+        return self._sharded(sharded_group_by_window, None, q, col, window, key_filter=f, max_groups=max_groups, k=k, descending=descending,
+                             having=hspec, narrow=not wide)
 
     # budgeted GROUP BY (per_group=K): one MAX all-reduce of the key range, one all-reduce SUM of span x 5 sums, one of span x 3
     # variances; a shard's segment of a group is a stratum with the budget K of its own

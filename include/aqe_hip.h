@@ -1674,6 +1674,52 @@ AQE_API int aqe_last_window_tiles(aqe_ctx* ctx, uint64_t* tiles, uint64_t* skipp
  * empty, time_min > time_max).  AQE_ERR_INVALID: t_lo > t_hi.  AQE_ERR_UNSUPPORTED: time_max - time_min >= 2^31. */
 AQE_API int aqe_time_window_offsets(int64_t time_min, int64_t time_max, int64_t t_lo, int64_t t_hi, int32_t* lo, int32_t* hi);
 
+/* ---- GROUP BY one key column under a WHERE timestamp window, zone-map tile skipping (window_group.hip) ----------------------
+ * Extends the windowed sweep above (its int32 time offsets, its zone map, its tile verdict) to GROUP BY region | product_id,
+ * with the sliced LDS bins of aqe_reduce_grouped_wide and the LDS copies of aqe_reduce_time_groups.
+ *
+ * Rows.  Under the inclusive int64 window [t_lo, t_hi] the rows have the semantics of the BUCKETED forms
+ * (aqe_reduce_time_buckets, aqe_reduce_time_groups), NOT those of aqe_reduce_windowed above, where visited counts every
+ * sampled row:
+ *     a sampled row outside the window counts into no bin: neither n nor visited;
+ *     a sampled row inside the window counts into its group's visited;
+ *     it counts into n, P1, P2 when it also passes the amount range (aqe_query.has_where) and the key term.
+ * Per group the estimate and interval are aqe_reduce_grouped's, exactly as aqe_grouped_wide_finish reports them (100 / pct
+ * scaling, which never reads visited): bin for bin what aqe_reduce_time_groups gives for ONE bucket that covers the window.  A
+ * group with no sampled row inside the window is not listed; a listed group may have n == 0.  Because a tile the zone map rules
+ * out contributes to no bin, it is skipped with no load at all — counting outside rows into visited per group would force the
+ * key column to be read in every cold tile.
+ *
+ * Limits.  One group column, AQE_GROUP_REGION or AQE_GROUP_PRODUCT, spanning up to 65 536 bins (more: AQE_ERR_UNSUPPORTED with
+ * the span).  The time offsets ride in key slot 0 of the row loop and the group column in slot 1, as in k_time_group, so each
+ * of these is AQE_ERR_UNSUPPORTED by name before any launch ("would need a third key slot"): both group columns at once
+ * (group_column == AQE_GROUP_PAIR), and a key term on the OTHER key column; a term on the group column itself is allowed.
+ * Samplers, row windows and refusals are aqe_reduce_windowed's, in the words "GROUP BY under a time window does not take the
+ * ... sampler"; the seeded random sampler goes through its index list, read and tested per row with no skip.  t_lo > t_hi is
+ * AQE_ERR_INVALID; a shard whose timestamps span 2^31 or more is refused as aqe_reduce_time_buckets refuses it; a window that
+ * misses the shard yields zero bins.  SUM / AVG / COUNT only.
+ *
+ * aqe_reduce_window_groups: single GPU, synchronous — key range, sweep, bins sum, k_wide_finish: the groups ascending by key.
+ * A cap that is too small behaves as in aqe_reduce_grouped_wide (AQE_ERR_INVALID with the count, no partial list); when no bin
+ * has a sampled row inside the window the status is AQE_ERR_INVALID "No samples collected".
+ * Multi-GPU form: every rank sweeps its shard over the agreed key range (the window is converted against the rank's own
+ * time_min, aqe_time_window_offsets),
+ *     aqe_window_groups_enqueue_bins(ctx, filter, q, group_column, t_lo, t_hi, key_min, span, dev_bins, stream)
+ *                                                              this shard's span x AQE_WIDE_BIN doubles {n, P1, P2, visited}
+ *                                                              in exactly aqe_grouped_wide_enqueue_bins' layout (an empty
+ *                                                              shard writes zeros)
+ *     <ONE all-reduce SUM of span x AQE_WIDE_BIN doubles on `stream`>
+ *     aqe_grouped_wide_finish / aqe_grouped_top_finish / aqe_grouped_having_finish with ncols = 1, as they are.
+ * After either entry aqe_last_window_tiles reports the grouped launch: the tiles of the sample (not times the slices) and how
+ * many of them were skipped.  AQE_ZONE_SKIP=0 reads every tile; AQE_WIDE_SLICE and AQE_SERIES_COPIES (diagnostics) force the
+ * slice and the LDS copies as they do for the parents.  No floating-point atomics on device memory: counts are exact, sums
+ * reproducible to rounding. */
+#define AQE_GROUP_PAIR 3 /* both key columns at once: named only to be refused, see above */
+AQE_API int aqe_reduce_window_groups(aqe_ctx* ctx, const aqe_key_filter* filter /* may be NULL */, const aqe_query* q, int group_column, int64_t t_lo,
+                                     int64_t t_hi, aqe_group_result* out, uint32_t cap, uint32_t* n_groups);
+AQE_API int aqe_window_groups_enqueue_bins(aqe_ctx* ctx, const aqe_key_filter* filter /* may be NULL */, const aqe_query* q, int group_column, int64_t t_lo,
+                                           int64_t t_hi, int32_t key_min, uint32_t span, double* dev_bins, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
