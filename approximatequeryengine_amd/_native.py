@@ -66,6 +66,7 @@ DISTINCT_SKETCH, DISTINCT_EXACT_KEYS = 0, 1
 DISTINCT_VEC_HEAD, DISTINCT_SLOTS = 2, 8192  # [visited, n] for a SUM all-reduce, then slot[0 .. 8192) for a MAX all-reduce
 # COUNT(DISTINCT) per group: the bounds of aqe_gdistinct_plan, the head of its vector, the words of a group's rank histogram
 GDISTINCT_MAX_GROUPS, GDISTINCT_MAX_CELLS, GDISTINCT_SLICE_CELLS, GDISTINCT_VEC_HEAD, GDISTINCT_RANKS = 1024, 262144, 16384, 2, 58
+GQUANTILE_MAX_GROUPS, GQUANTILE_MAX_ROWS = 1024, 1 << 28  # the bounds of aqe_reduce_grouped_quantiles (MEDIAN / PERCENTILE per group)
 SUMMARY_VEC, SUMMARY_VEC_SUM = 12, 10  # the SPREAD_VEC layout + {0, 0} for a SUM all-reduce, then {-min, max} for a MAX all-reduce
 TIME_BIN, TIME_MAX_BUCKETS, TIME_MAX_SPAN = 4, 1024, 2 ** 31 - 1  # {n, P1, P2, visited} per time bucket; the limits of aqe_time_plan
 SERIES_BIN, SERIES_MAX_BINS = 4, 65536  # {n, P1, P2, visited} per cell of a per-key time series; the bound of aqe_time_group_plan
@@ -173,6 +174,18 @@ class QuantileResult(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class GroupQuantileResult(C.Structure):
+    """aqe_group_quantile_result: one probability of one group of a MEDIAN / PERCENTILE per group."""
+    _fields_ = [("key", C.c_int32), ("reserved", C.c_int32), ("p", C.c_double), ("value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double),
+                ("n", C.c_uint64), ("visited", C.c_uint64), ("rank_lo", C.c_uint64), ("rank_hi", C.c_uint64), ("ci_rank_lo", C.c_uint64),
+                ("ci_rank_hi", C.c_uint64), ("device_status", C.c_int32), ("reserved2", C.c_int32), ("kernel_ms", C.c_double)]
+
+    passes = 1  # one collecting sweep, whatever the data (a QuantileResult counts its narrowing passes here)
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
 class SpreadResult(C.Structure):
@@ -590,6 +603,12 @@ def lib() -> C.CDLL:
         "aqe_plan_launch_samples": (C.c_int, [vp, P(u64), u32, P(u32)]),
         "aqe_plan_last_kernel": (C.c_int, [vp, P(C.c_int)]),
         "aqe_last_load_policy": (C.c_int, [vp, P(C.c_int)]),
+        "aqe_reduce_grouped_quantiles": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, P(dbl), u32, C.c_int, P(GroupQuantileResult), u32, P(u32)]),
+        "aqe_last_grouped_quantile_times": (C.c_int, [vp, P(dbl)]),
+        "aqe_gquantile_from_sorted": (C.c_int, [P(dbl), u64, P(dbl), u32, C.c_int, C.c_int, dbl, i32, u64, P(GroupQuantileResult)]),
+        "aqe_grouped_quantile_enqueue_collect": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, i32, u32, vp, vp, vp]),
+        "aqe_grouped_quantile_enqueue_place": (C.c_int, [vp, vp, u64, u64, vp]),
+        "aqe_grouped_quantile_finish": (C.c_int, [vp, P(Query), i32, u32, vp, u64, vp, P(dbl), u32, C.c_int, vp, P(GroupQuantileResult), u32, P(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -1269,6 +1269,45 @@ class CustomBPlusDB:
         """APPROX MEDIAN(amount): approx_quantile(0.5, **kw)."""
         return self.approx_quantile(0.5, **kw)
 
+    def approx_quantile_by(self, p, by: str, method: str = "stride", sample_percent: float = 10.0, where: Optional[Tuple[float, float]] = None,
+                           id_between: Optional[Tuple[int, int]] = None, interpolation: str = "linear", confidence_level: float = 0.95,
+                           seed: int = 42, num_threads: int = 4, block_size: int = 1000, key_where: Optional[dict] = None, time_between=None):
+        """APPROX PERCENTILE(amount, p) per key of ``by`` ("region" | "product_id"): for every key with a sampled row that qualifies
+        (WHERE, the key window and ``key_where`` on either key column applied, NaN rows left out), numpy.quantile of that group's
+        sampled amounts and the distribution-free interval from its own order statistics — approx_quantile's definitions with
+        the group's n — from ONE collecting sweep, a sort and a selection (aqe_reduce_grouped_quantiles).  Returns an ordered
+        ``dict`` keyed by the group's key, ascending: a QuantileEstimate per key, or a list of them when ``p`` is a list (up to
+        8).  An ungrouped quantile under a key predicate is the one listed group of ``by="region", key_where={"region": ("in",
+        [2])}``.  More than 1024 keys, more than 2^28 sampled rows and the CLT, adaptive, stratified and random_device samplers
+        raise ValueError; there is no error-threshold form, no pair of group columns and no timestamp window."""
+        if time_between is not None:
+            raise ValueError("quantiles by group have no timestamp-window (time_between) form")
+        if not isinstance(by, str) or "," in by:
+            raise ValueError(f"quantiles by {by!r}: a pair of group columns is not supported (one of 'region' or 'product_id')")
+        by_name = by.strip().lower()
+        if by_name not in _GROUP_COLUMNS:
+            raise ValueError(f"quantiles by {by.strip()!r}: groups are keys of 'region' or 'product_id'")
+        single = not isinstance(p, (list, tuple, np.ndarray))
+        probs = [float(p)] if single else [float(v) for v in p]
+        if not probs or len(probs) > nat.MAX_QUANTILES or any(not (0.0 <= v <= 1.0) for v in probs):
+            raise ValueError(f"1 .. {nat.MAX_QUANTILES} probabilities, each in [0, 1]")
+        q, interp = self._quantile_query(method, sample_percent, where, id_between, interpolation, confidence_level, seed,
+                                         num_threads, block_size)
+        f = None if key_where is None else _key_filter_for(key_where, method)
+        groups = _quantile_call(lambda: self._quantile_groups(f, q, _GROUP_COLUMNS[by_name], probs, interp))
+        out = {}
+        for entries in groups:
+            est = [QuantileEstimate(r, method) for r in entries]
+            out[int(entries[0].key)] = est[0] if single else est
+        return out
+
+    def _quantile_groups(self, f, q, by, probs, interp):
+        return self._eng().reduce_grouped_quantiles(q, by, probs, interp, f)
+
+    def approx_median_by(self, by: str, **kw):
+        """APPROX MEDIAN(amount) per key of ``by``: approx_quantile_by(0.5, by, **kw)."""
+        return self.approx_quantile_by(0.5, by, **kw)
+
     def approx_spread(self, kind: str = "var_samp", method: str = "stride", sample_percent: float = 10.0,
                       where: Optional[Tuple[float, float]] = None, id_between: Optional[Tuple[int, int]] = None, seed: int = 42,
                       confidence_level: float = 0.95, group_by: Optional[str] = None, num_threads: int = 4, block_size: int = 1000,

@@ -443,6 +443,11 @@ _REFUSALS = {
         (_bucketed, "HAVING has no GROUP BY BUCKET(...) form: time buckets are not judged")),
     "BUCKET": ((_has_e, "GROUP BY BUCKET(...) has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),),
     "--distinct-by": ((_has_e, "--distinct-by has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),),
+    "--quantile-by": (
+        (_has_e, "--quantile-by has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
+        (lambda q, args: quantile_of(q) is None, "--quantile-by goes with MEDIAN / PERCENTILE, e.g. \"SELECT MEDIAN(amount) FROM sales\" --quantile-by region"),
+        (lambda q, args: str(getattr(args, "quantile_by", "")).strip().lower() not in ("region", "product_id"),
+         "--quantile-by takes region or product_id: the groups are the keys of one of the two key columns")),
     "quantile": (
         (_has_e, "quantiles have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
         (_grouped, "GROUP BY is not supported with MEDIAN / PERCENTILE")),
@@ -709,6 +714,18 @@ def distinct_by_defect(clean: str, args) -> Optional[str]:
     return None
 
 
+def quantile_by_defect(clean: str, args) -> Optional[str]:
+    """What is wrong with --quantile-by beside this query (None: nothing, or the flag is absent): it has no --e form, goes with a
+    query quantile_of() claims and names region or product_id.  (A GROUP BY clause is left to the refusal every quantile gives
+    it.)"""
+    if getattr(args, "quantile_by", None) is None:
+        return None
+    try:
+        return _refusal("--quantile-by", clean, args)
+    except ValueError as e:  # (a probability outside [0, 1])
+        return str(e)
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV, MIN/MAX, HISTOGRAM, COUNT(DISTINCT), SUMMARY on MI355X "
                                 "(e.g. \"SELECT HISTOGRAM(amount, 20) FROM sales\" --s 10 --ci; \"SELECT SUMMARY(amount) FROM sales\" --s 10 --ci)",
@@ -738,6 +755,8 @@ def build_parser() -> argparse.ArgumentParser:
                    "ORDER BY ... LIMIT and --max-groups (without the flag such a term is ignored)")
     p.add_argument("--distinct-by", dest="distinct_by", metavar="COLUMN", help="with COUNT(DISTINCT col): one count per key of COLUMN (region or product_id), "
                    "from one sweep; at most 1024 groups")
+    p.add_argument("--quantile-by", dest="quantile_by", metavar="COLUMN", help="with MEDIAN / PERCENTILE: one value per key of COLUMN (region or product_id), "
+                   "from one collecting sweep and a sort; at most 1024 groups; a key predicate in WHERE is honoured")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="under torchrun (one process per GPU): the torch.distributed backend (nccl = RCCL)")
     p.add_argument("--collective", choices=["torch", "mailbox"], default="torch", help="under torchrun: the all-reduce of the moment vectors "
@@ -763,7 +782,7 @@ def _query_defect(pq: ParsedQuery, args) -> Optional[str]:
         if args.e is not None:
             return (f"the CLT sampler (--e) samples the whole table and has no form for the key predicate 'WHERE {pq.where}': "
                     "give a sample percentage (--s) or none (exact)")
-        if family == "quantile":
+        if family == "quantile" and getattr(args, "quantile_by", None) is None:
             return f"MEDIAN / PERCENTILE under the key predicate 'WHERE {pq.where}' are not supported yet"
     return _refusal("GROUP BY", clean, args)
 
@@ -784,7 +803,7 @@ def run(args, out=sys.stdout) -> int:
     if why is not None:
         print(f"error: {why}", file=out)
         return 2
-    why = (per_group_defect(pq.text, args) or distinct_by_defect(pq.text, args) or having_defect(pq.text, args)
+    why = (per_group_defect(pq.text, args) or distinct_by_defect(pq.text, args) or quantile_by_defect(pq.text, args) or having_defect(pq.text, args)
            or max_groups_defect(pq.rest, args) or top_defect(pq.rest, args))  # (the first three read the query with its HAVING clause)
     if why is None:
         try:
@@ -1014,10 +1033,26 @@ def _run_grouped(db, args, out, pq, qtype, agg, t0, kw) -> int:
 
 
 def _run_quantile(db, args, out, pq, qtype, t0, kw) -> int:
-    """MEDIAN / PERCENTILE(_CONT, _DISC).  (No key-predicate form: `kw` is not passed on, run() refuses the query.)"""
+    """MEDIAN / PERCENTILE(_CONT, _DISC), in all or per key of --quantile-by.  (The ungrouped form has no key-predicate form: `kw`
+    is not passed on, run() refuses the query.)"""
     p, interp, fname = pq.family[1]
     where = pq.amount_where
     method, pct, name = _sampling(args, qtype)
+    by = getattr(args, "quantile_by", None)
+    if by is not None:  # one value per key of `by`: a line per group, then their number
+        by = str(by).strip().lower()
+        groups = db.approx_quantile_by(p, by, method=method, sample_percent=pct, where=where, interpolation=interp, confidence_level=args.confidence,
+                                       seed=args.seed, num_threads=args.threads, **kw)
+        ms = (time.perf_counter() - t0) * 1e3
+        print(f"\n{name} {fname}(amount{'' if fname == 'MEDIAN' else f', {p:g}'}) by {by} result:", file=out)
+        kernel_ms = 0.0
+        for key, g in groups.items():
+            ci = f"   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})" if (args.ci and method != "exact") else ""
+            print(f"   {by} {key}: {g.value:,.4f}{ci}   n={g.n:,}", file=out)
+            kernel_ms = g.kernel_ms
+        print(f"   {len(groups)} groups", file=out)
+        print(f"   execution time: {ms:.2f} ms (kernels {kernel_ms * 1e3:.1f} us)", file=out)
+        return 0
     res = db.approx_quantile(p, method=method, sample_percent=pct, where=where, interpolation=interp,
                              confidence_level=args.confidence, seed=args.seed, num_threads=args.threads)
     ms = (time.perf_counter() - t0) * 1e3

@@ -102,6 +102,7 @@ struct aqe_extreme_scratch;  // extremes.hip
 struct aqe_histogram_scratch;  // histogram.hip
 struct aqe_distinct_scratch;  // distinct.hip
 struct aqe_gdistinct_scratch;  // grouped_distinct.hip
+struct aqe_gquantile_scratch;  // group_quantile.hip
 struct aqe_summary_scratch;  // summary.hip
 struct aqe_time_scratch;  // timeseries.hip
 struct aqe_wide_scratch;  // wide_group.hip
@@ -193,6 +194,9 @@ struct aqe_ctx {
     aqe_distinct_scratch* distinct = nullptr;
     // COUNT(DISTINCT) per group (grouped_distinct.hip): accumulator, tickets, the cell vector and the rank counts, made on first use
     aqe_gdistinct_scratch* gdistinct = nullptr;
+    // MEDIAN / PERCENTILE per group (group_quantile.hip): the collected pairs, the sort's second buffer and temporaries, the
+    // counters and the pinned results, made on first use and grown on demand
+    aqe_gquantile_scratch* gquantile = nullptr;
     // SUMMARY (summary.hip): partials, tickets and the pinned result of the fused moments-and-extremes sweep, made on first use
     aqe_summary_scratch* summary = nullptr;
     // time buckets (timeseries.hip): the workgroups' bins, the summed bins and the pinned groups, made on first use
@@ -397,6 +401,9 @@ void distinct_release(aqe_ctx* c);
 
 // grouped_distinct.hip
 void gdistinct_release(aqe_ctx* c);
+
+// group_quantile.hip
+void gquantile_release(aqe_ctx* c);
 
 // summary.hip
 void summary_release(aqe_ctx* c);

@@ -28,6 +28,7 @@
 // same vector, so every rank holds the same state.  Both forms run the same fold on the same integers: equal answers.
 #include "device_common.hpp"
 #include "host.hpp"
+#include "quantile_core.hpp"
 #include "sweep_host.hpp"
 
 namespace aqe {
@@ -136,17 +137,7 @@ __device__ void q_write_results(const QState& st, const QTarget* T, const QSpec&
             r.rank_lo = r.rank_hi = r.ci_rank_lo = r.ci_rank_hi = 0;
         } else {
             const QTarget* t = T + 4 * i;
-            const double a = okey_inv(t[0].key), b = okey_inv(t[1].key);
-            double value;
-            if (spec.interp == AQE_QUANTILE_LINEAR) {
-                // numpy _lerp: gamma = virtual index - previous index (the clamped index -1 above the last element)
-                const double v = static_cast<double>(n - 1) * p;
-                const double gamma = v >= static_cast<double>(n - 1) ? v - (-1.0) : v - floor(v);
-                const double diff = b - a;
-                value = gamma >= 0.5 ? b - diff * (1.0 - gamma) : a + diff * gamma;
-            } else {
-                value = a;
-            }
+            const double value = quantile_value(okey_inv(t[0].key), okey_inv(t[1].key), n, p, spec.interp);  // (quantile_core.hpp)
             r.value = value;
             r.rank_lo = st.rank0[4 * i] + 1;
             r.rank_hi = st.rank0[4 * i + 1] + 1;
@@ -185,31 +176,9 @@ __device__ void q_fold(const double* vec, QState* st, const QSpec& spec, QOut* o
                 q_write_results(*st, T, spec, out, 1, 0);
                 s_done = 1;
             } else {
-                const double nd = static_cast<double>(n);
                 for (u32 i = 0; i < spec.nprobs; ++i) {
-                    const double p = spec.p[i];
-                    u64 ra, rb;
-                    if (spec.interp == AQE_QUANTILE_LINEAR) {
-                        const double v = static_cast<double>(n - 1) * p;
-                        if (v >= static_cast<double>(n - 1)) { ra = rb = n - 1; }
-                        else { ra = static_cast<u64>(floor(v)); rb = ra + 1; }
-                    } else {  // inverted_cdf: index n p - 1, its floor when that is exact, the next one else; >= 0
-                        const double idx = nd * p - 1.0;
-                        const double f = floor(idx);
-                        const double r = (idx - f) == 0.0 ? f : f + 1.0;
-                        ra = rb = r < 0.0 ? 0 : static_cast<u64>(r);
-                    }
-                    u64 cl = ra, ch = rb;  // the exact scan's interval is the value itself
-                    if (!spec.exact) {
-                        const double np_ = nd * p;
-                        const double s = spec.z * sqrt(np_ * (1.0 - p));
-                        double lo = floor(np_ - s), hi = ceil(np_ + s);
-                        lo = lo < 1.0 ? 1.0 : lo > nd ? nd : lo;
-                        hi = hi < 1.0 ? 1.0 : hi > nd ? nd : hi;
-                        cl = static_cast<u64>(lo) - 1;
-                        ch = static_cast<u64>(hi) - 1;
-                    }
-                    const u64 rk[4] = {ra, rb, cl, ch};
+                    const QuantileRanks qr = quantile_ranks(n, spec.p[i], spec.interp, spec.exact != 0, spec.z);  // (quantile_core.hpp)
+                    const u64 rk[4] = {qr.a, qr.b, qr.ci_lo, qr.ci_hi};
                     for (int k = 0; k < 4; ++k) {
                         QTarget& t = T[4 * i + k];
                         t.lo = spec.kmin; t.hi = spec.kmax; t.rank = rk[k]; t.key = 0; t.resolved = 0; t.group = 0;
@@ -622,7 +591,7 @@ int setup_run(aqe_quantile* r, const aqe_query* q, const double* probs, uint32_t
     s.nprobs = n_probs;
     s.interp = interpolation;
     s.exact = q->method == AQE_M_EXACT ? 1 : 0;
-    s.z = q->confidence_level >= 0.99 ? 2.576 : q->confidence_level >= 0.95 ? 1.96 : 1.645;  // as the CLT path, DB.cpp:911-912
+    s.z = quantile_z(q->confidence_level);  // as the CLT path, DB.cpp:911-912
     r->passes = 0;
     return AQE_OK;
 }

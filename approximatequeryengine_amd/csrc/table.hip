@@ -581,6 +581,7 @@ void aqe_destroy(aqe_ctx* c) {
     histogram_release(c);
     distinct_release(c);
     gdistinct_release(c);
+    gquantile_release(c);
     summary_release(c);
     timeseries_release(c);
     wide_release(c);

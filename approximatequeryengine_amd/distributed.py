@@ -375,6 +375,47 @@ def sharded_quantiles(engine, query, probs, interpolation: int, vec, all_reduce_
             run.close()
 
 
+def sharded_quantile_groups(engine, query, by: int, probs, interpolation: int, vec, all_reduce_sum: Callable, all_reduce_max: Callable, rank: int, world: int,
+                            stream: int = 0, key_filter=None):
+    """MEDIAN / PERCENTILE per key of ``by`` across the ranks of a process group (engine.Engine interface), collective: every rank
+    gets the same answer.  The group column's key range is agreed first (ONE all-reduce MAX, ``_agree_keys``); every rank collects
+    the (amount, bin) pairs of the part of the sample inside its shard (aqe_grouped_quantile_enqueue_collect); ONE all-reduce SUM
+    of world + nbins doubles — each rank's pair count in its own slot, visited per bin — tells every rank the total and its own
+    offset; every rank writes its pairs as doubles into a zero-filled union of 2 x total doubles at its offset
+    (aqe_grouped_quantile_enqueue_place) and ONE all-reduce SUM fills the union on every rank (x + 0.0 is x for every amount
+    that is no NaN, bins are small integers: ``_key_to_double``'s precedent); every rank then sorts the same union and selects
+    (aqe_grouped_quantile_finish).  The union is ``world`` times what an all-gather would move; the collective kit has SUM and
+    MAX only, in all three of its forms.  More than GQUANTILE_MAX_ROWS pairs in total is refused on every rank alike.
+
+    vec     float64 tensor on the engine's device with room for world + nbins doubles (at most world + 1024); the union is
+            allocated here, sized by the total
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    import torch
+    from ._native import ERR_INVALID, ERR_UNSUPPORTED, GQUANTILE_MAX_GROUPS, GQUANTILE_MAX_ROWS, GROUP_REGION, AqeError
+    by, rank, world = int(by), int(rank), int(world)
+    with _on_stream(stream, vec) as stream:
+        agreed = _agree_keys(engine, [by], vec, all_reduce_max)
+        if agreed is None:
+            raise AqeError(ERR_INVALID, "No samples collected")  # an empty table
+        kmin, nbins = agreed[0][0], agreed[1][0] - agreed[0][0] + 1
+        if nbins > GQUANTILE_MAX_GROUPS:
+            name = "region" if by == GROUP_REGION else "product_id"
+            raise AqeError(ERR_UNSUPPORTED, f"MEDIAN / PERCENTILE by {name}: the group column spans {nbins} keys, more than {GQUANTILE_MAX_GROUPS} groups")
+        head = _take(vec, world + nbins, vector=True)
+        head.zero_()
+        engine.grouped_quantile_enqueue_collect(query, by, kmin, nbins, head[rank:].data_ptr(), head[world:].data_ptr(), stream, key_filter)
+        all_reduce_sum(head)
+        counts = [int(v) for v in head[:world].tolist()]
+        total, offset = sum(counts), sum(counts[:rank])
+        if total > GQUANTILE_MAX_ROWS:
+            raise AqeError(ERR_UNSUPPORTED, f"MEDIAN / PERCENTILE by group: the sample holds {total} rows over all ranks, more than {GQUANTILE_MAX_ROWS}")
+        union = torch.zeros(max(2 * total, 1), dtype=torch.float64, device=vec.device)
+        engine.grouped_quantile_enqueue_place(union.data_ptr(), total, offset, stream)
+        if total:
+            all_reduce_sum(union[: 2 * total])
+        return engine.grouped_quantile_finish(query, kmin, nbins, union.data_ptr(), total, head[world:].data_ptr(), probs, interpolation, stream)
+
+
 def sharded_spread(engine, query, kind: int, vec, all_reduce_sum: Callable, stream: int = 0):
     """VARIANCE / STDDEV across the ranks of a process group (engine.Engine interface), collective: every rank sweeps the part
     of the sample inside its shard into SPREAD_VEC shifted power sums, ONE all-reduce SUM merges them and every rank finishes

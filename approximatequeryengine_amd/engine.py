@@ -468,6 +468,47 @@ class Engine:
                        stream: int = 0) -> "QuantileRun":
         return QuantileRun(self, query, probs, interpolation, amount_min, amount_max, stream)
 
+    # -- MEDIAN / PERCENTILE per group (aqe_reduce_grouped_quantiles and its stepwise sharded form): collect, sort, select --
+    def reduce_grouped_quantiles(self, query: Query, by: int, probs: Sequence[float], interpolation: int = nat.QUANTILE_LINEAR,
+                                 key_filter: Optional["nat.KeyFilter"] = None, max_groups: int = nat.GQUANTILE_MAX_GROUPS):
+        """Order statistics of the sampled amounts per key of ``by`` (GROUP_REGION / GROUP_PRODUCT): a list over the groups with a
+        qualifying sampled row, ascending by key, of lists of GroupQuantileResult, one per probability."""
+        ps = _probs(probs)
+        arr = (C.c_double * len(ps))(*ps)
+        out = (nat.GroupQuantileResult * (max_groups * len(ps)))()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_reduce_grouped_quantiles(self._h, _filter_ref(key_filter), C.byref(query), int(by), arr, len(ps), int(interpolation), out,
+                                                         max_groups, C.byref(n)))
+        return _by_group(out, n.value, len(ps))
+
+    def last_grouped_quantile_times(self) -> Tuple[float, float, float]:
+        """Diagnostics: device ms of the most recent reduce_grouped_quantiles as (collect, sorts, select)."""
+        ms = (C.c_double * 3)()
+        self._chk(nat.lib().aqe_last_grouped_quantile_times(self._h, ms))
+        return ms[0], ms[1], ms[2]
+
+    def grouped_quantile_enqueue_collect(self, query: Query, by: int, key_min: int, nbins: int, dev_count_ptr: int, dev_visited_ptr: int, stream: int = 0,
+                                         key_filter: Optional["nat.KeyFilter"] = None):
+        """This shard's pairs into the engine's scratch; their number to ``dev_count_ptr`` (one double), visited per bin to
+        ``dev_visited_ptr`` (nbins doubles): to be all-reduced with SUM, then grouped_quantile_enqueue_place."""
+        self._chk(nat.lib().aqe_grouped_quantile_enqueue_collect(self._h, _filter_ref(key_filter), C.byref(query), int(by), int(key_min), int(nbins),
+                                                                 C.c_void_p(dev_count_ptr), C.c_void_p(dev_visited_ptr), C.c_void_p(stream)))
+
+    def grouped_quantile_enqueue_place(self, dev_union_ptr: int, total: int, offset: int, stream: int = 0):
+        """The shard's pairs as doubles into the zero-filled union of 2 x total doubles, at ``offset``: to be all-reduced with SUM."""
+        self._chk(nat.lib().aqe_grouped_quantile_enqueue_place(self._h, C.c_void_p(dev_union_ptr), int(total), int(offset), C.c_void_p(stream)))
+
+    def grouped_quantile_finish(self, query: Query, key_min: int, nbins: int, dev_union_ptr: int, total: int, dev_visited_ptr: int, probs: Sequence[float],
+                                interpolation: int = nat.QUANTILE_LINEAR, stream: int = 0, max_groups: int = nat.GQUANTILE_MAX_GROUPS):
+        ps = _probs(probs)
+        arr = (C.c_double * len(ps))(*ps)
+        out = (nat.GroupQuantileResult * (max_groups * len(ps)))()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_grouped_quantile_finish(self._h, C.byref(query), int(key_min), int(nbins), C.c_void_p(dev_union_ptr), int(total),
+                                                        C.c_void_p(dev_visited_ptr), arr, len(ps), int(interpolation), C.c_void_p(stream), out, max_groups,
+                                                        C.byref(n)))
+        return _by_group(out, n.value, len(ps))
+
     # -- spread: VARIANCE / STDDEV (aqe_reduce_spread, its additive multi-GPU split, the GROUP BY form) --
     def reduce_spread(self, query: Query, kind: int = nat.SPREAD_VAR_SAMP) -> "nat.SpreadResult":
         """Variance / standard deviation of the sampled amounts with the fourth-moment interval (include/aqe_hip.h)."""
@@ -1491,6 +1532,26 @@ def _probs(probs) -> list:
     if not 1 <= len(ps) <= nat.MAX_QUANTILES:
         raise ValueError(f"1 .. {nat.MAX_QUANTILES} probabilities per call")
     return ps
+
+
+def _by_group(entries, n_groups: int, n_probs: int) -> list:
+    """The group-major entries of a grouped quantile call as one list of n_probs entries per listed group."""
+    return [[entries[g * n_probs + j] for j in range(n_probs)] for g in range(n_groups)]
+
+
+def gquantile_from_sorted(sorted_amounts, probs, interpolation: int = nat.QUANTILE_LINEAR, exact: bool = False, confidence_level: float = 0.95,
+                          key: int = 0, visited: int = 0) -> list:
+    """aqe_gquantile_from_sorted: one group's GroupQuantileResult per probability from its amounts sorted ascending, on the host —
+    no GPU; the arithmetic (quantile_core.hpp) is the device selection's."""
+    x = np.ascontiguousarray(sorted_amounts, dtype=np.float64)
+    ps = _probs(probs)
+    arr = (C.c_double * len(ps))(*ps)
+    out = (nat.GroupQuantileResult * len(ps))()
+    rc = nat.lib().aqe_gquantile_from_sorted(x.ctypes.data_as(C.POINTER(C.c_double)), len(x), arr, len(ps), int(interpolation), int(bool(exact)),
+                                             float(confidence_level), int(key), int(visited), out)
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "MEDIAN / PERCENTILE by group: a group of no rows, a probability outside [0, 1] or an unknown interpolation")
+    return list(out)
 
 
 class QuantileRun:

@@ -1198,6 +1198,78 @@ AQE_API int aqe_grouped_distinct_enqueue_cells(aqe_ctx* ctx, const aqe_key_filte
 AQE_API int aqe_grouped_distinct_finish(aqe_ctx* ctx, const aqe_query* q, const aqe_gdistinct_shape* shape, const double* dev_vec, void* stream,
                                         aqe_gdistinct_result* out, uint32_t cap, aqe_gdistinct_info* info, uint32_t* rank_counts);
 
+/* ---- grouped quantiles: MEDIAN / PERCENTILE per key of a group column — one collecting sweep, sort, select (group_quantile.hip) --
+ * `by` is AQE_GROUP_REGION or AQE_GROUP_PRODUCT.  For each key g occurring in the sample:
+ *   X_g        the amounts of the sampled rows (q's sampler, inside its row window) with that key that pass `filter` (NULL: none;
+ *              terms on either key column) and the inclusive amount WHERE range; NaN rows left out.  n_g = |X_g|.
+ *   visited_g  the sampled rows with that key that pass `filter`, before the amount range and NaN.
+ * Per probability the entry reports what aqe_reduce_quantiles reports for the whole sample, with n_g in place of n: value =
+ * numpy.quantile(X_g, p, method=M) to the bit, the value's own ranks, and the distribution-free interval (same z, same rank
+ * formulas, same clamping; [value, value] for AQE_M_EXACT).  -0.0 reads as +0.0; +-inf are values.  The arithmetic is ONE copy,
+ * quantile_core.hpp, shared with quantile.hip and with the host restatement aqe_gquantile_from_sorted.
+ * Groups are listed in ascending key order, n_probs entries per group (group-major); a group with n_g == 0 is not listed; no
+ * listed group at all is AQE_ERR_INVALID "No samples collected".
+ * How.  k_gq_collect sweeps the sample once and appends (order-preserving amount key, key bin) of every row of some X_g to two
+ * device arrays — positions from a device counter advanced once per wave per tile, the stores of a wave contiguous — and counts
+ * {n_g, visited_g} in LDS, flushed with integer atomics.  It never stores past the capacity it was given (the plan's host-side
+ * sample count): a wave whose reservation would pass it stores nothing and raises a status word: AQE_ERR_INTERNAL.  Two stable
+ * radix sorts (rocPRIM): by amount key, then by bin over ceil(log2(nbins)) bits.  k_gq_select reads the order statistics off
+ * the sorted array, one thread per (group, probability).  Exact, no narrowing state, bit-identical from run to run: the pairs'
+ * arrival order cannot reach the answer, because equal pairs are indistinguishable after the sort.
+ * Limits, each refused by name with the offending number before any launch: more than AQE_GQUANTILE_MAX_GROUPS bins
+ * (key_max - key_min + 1; AQE_ERR_UNSUPPORTED), n_probs outside 1 .. AQE_MAX_QUANTILES (AQE_ERR_INVALID), more than
+ * AQE_GQUANTILE_MAX_ROWS sampled rows by the plan's count (AQE_ERR_UNSUPPORTED; 3 GiB of pairs plus the sort's second buffer;
+ * on a sharded table the cap applies to the ranks' total; the environment variable AQE_GQUANTILE_MAX_ROWS, read per call, lowers
+ * it: diagnostics and tests).  Samplers: those of aqe_reduce_quantiles, refused by name alike.  No error-threshold form, no pair
+ * of group columns, no timestamp window.  AQE_NT=0/1 picks the load flavour, which aqe_last_load_policy reports. */
+#define AQE_GQUANTILE_MAX_GROUPS 1024
+#define AQE_GQUANTILE_MAX_ROWS (1ull << 28)
+typedef struct aqe_group_quantile_result {
+    int32_t key;                   /* of the group column */
+    int32_t reserved;
+    double p;
+    double value;
+    double ci_lower, ci_upper;
+    uint64_t n;                    /* n_g */
+    uint64_t visited;              /* visited_g */
+    uint64_t rank_lo, rank_hi;     /* 1-based, within the group: the order statistics `value` is made of */
+    uint64_t ci_rank_lo, ci_rank_hi;
+    int32_t device_status;         /* 0 ok */
+    int32_t reserved2;
+    double kernel_ms;              /* aqe_reduce_grouped_quantiles: device time of the call (events around its launches) */
+} aqe_group_quantile_result;
+/* Single GPU, synchronous.  out: room for cap_groups x n_probs entries; *n_groups: the groups listed (more than cap_groups:
+ * AQE_ERR_INVALID with the number, *n_groups set, no partial list). */
+AQE_API int aqe_reduce_grouped_quantiles(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, int by, const double* probs,
+                                         uint32_t n_probs, int interpolation, aqe_group_quantile_result* out, uint32_t cap_groups,
+                                         uint32_t* n_groups);
+/* The device times of the most recent aqe_reduce_grouped_quantiles, in ms: [collect, sorts, select] (diagnostics). */
+AQE_API int aqe_last_grouped_quantile_times(aqe_ctx* ctx, double* ms3);
+/* Host only, no GPU and no context: one group's entries from its amounts sorted ascending (no NaN; n >= 1), by the same header the
+ * device selection runs.  exact != 0: as AQE_M_EXACT.  out: n_probs entries with kernel_ms 0. */
+AQE_API int aqe_gquantile_from_sorted(const double* sorted, uint64_t n, const double* probs, uint32_t n_probs, int interpolation, int exact,
+                                      double confidence_level, int32_t key, uint64_t visited, aqe_group_quantile_result* out);
+/* Multi-GPU.  The ranks agree on the group column's key range (aqe_group_key_range, ONE all-reduce MAX of [-min, max]); then
+ *     aqe_grouped_quantile_enqueue_collect(ctx, filter, q, by, key_min, nbins, dev_count, dev_visited, stream)
+ *         collects this shard's pairs into the context's scratch and writes their number to *dev_count (one double: the rank's
+ *         own slot of a vector of `world` zeros) and visited per bin to dev_visited[0 .. nbins)
+ *     ONE all-reduce SUM of the world + nbins doubles; total = the sum of the counts (more than AQE_GQUANTILE_MAX_ROWS: refuse),
+ *         offset = the sum of the counts of the ranks before this one
+ *     aqe_grouped_quantile_enqueue_place(ctx, dev_union, total, offset, stream)
+ *         writes the shard's pairs as doubles into a zero-filled union vector of 2 x total doubles: amounts at [offset ..),
+ *         bins at [total + offset ..); nothing past either half
+ *     ONE all-reduce SUM of the 2 x total doubles (x + 0.0 is x for every amount that is no NaN)
+ *     aqe_grouped_quantile_finish(ctx, q, key_min, nbins, dev_union, total, dev_visited, probs, n_probs, interpolation, stream, out,
+ *                                 cap_groups, &n_groups)     sorts and selects over the union; synchronises `stream`
+ * Every rank sorts the same union and holds the same answer.  aqe_reduce_grouped_quantiles is this at a world of one, without
+ * the detour through doubles. */
+AQE_API int aqe_grouped_quantile_enqueue_collect(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, int by, int32_t key_min, uint32_t nbins,
+                                                 double* dev_count, double* dev_visited, void* stream);
+AQE_API int aqe_grouped_quantile_enqueue_place(aqe_ctx* ctx, double* dev_union, uint64_t total, uint64_t offset, void* stream);
+AQE_API int aqe_grouped_quantile_finish(aqe_ctx* ctx, const aqe_query* q, int32_t key_min, uint32_t nbins, const double* dev_union, uint64_t total,
+                                        const double* dev_visited, const double* probs, uint32_t n_probs, int interpolation, void* stream,
+                                        aqe_group_quantile_result* out, uint32_t cap_groups, uint32_t* n_groups);
+
 /* ---- summary: SUMMARY(amount) — count, sum, mean, spread, smallest and largest from ONE fused sweep (summary.hip) ----------
  * X = the sampled amounts: rows of q's sampler inside its row window that pass the inclusive amount WHERE range and the
  * key filter (`filter`, NULL: none — in every entry), NaN rows left out: the set aqe_reduce_extremes sees.  n = |X|;
