@@ -188,6 +188,17 @@ class GroupQuantileResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
+class TimeQuantileResult(C.Structure):
+    """aqe_time_quantile_result: one probability of one time bucket of a MEDIAN / PERCENTILE per bucket: the bucket's start, then the
+    fields of GroupQuantileResult (``key`` is the bucket's number counted from the plan's first bucket)."""
+    _fields_ = [("start", C.c_int64)] + list(GroupQuantileResult._fields_)
+
+    passes = 1
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 class SpreadResult(C.Structure):
     _fields_ = [("value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double), ("mean", C.c_double), ("m2", C.c_double),
                 ("m3", C.c_double), ("m4", C.c_double), ("n", C.c_uint64), ("visited", C.c_uint64), ("has_interval", C.c_int32),
@@ -607,6 +618,9 @@ def lib() -> C.CDLL:
         "aqe_last_grouped_quantile_times": (C.c_int, [vp, P(dbl)]),
         "aqe_gquantile_from_sorted": (C.c_int, [P(dbl), u64, P(dbl), u32, C.c_int, C.c_int, dbl, i32, u64, P(GroupQuantileResult)]),
         "aqe_grouped_quantile_enqueue_collect": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, i32, u32, vp, vp, vp]),
+        "aqe_reduce_time_quantiles": (C.c_int, [vp, P(KeyFilter), P(Query), P(TimeSpec), P(dbl), u32, C.c_int, P(TimeQuantileResult), u32, P(u32)]),
+        "aqe_time_quantiles_from_sorted": (C.c_int, [P(dbl), u64, P(dbl), u32, C.c_int, C.c_int, dbl, P(TimeSpec), C.c_int64, u32, u64, P(TimeQuantileResult)]),
+        "aqe_time_quantiles_enqueue_collect": (C.c_int, [vp, P(KeyFilter), P(Query), P(TimeSpec), C.c_int64, C.c_int64, vp, vp, vp]),
         "aqe_grouped_quantile_enqueue_place": (C.c_int, [vp, vp, u64, u64, vp]),
         "aqe_grouped_quantile_finish": (C.c_int, [vp, P(Query), i32, u32, vp, u64, vp, P(dbl), u32, C.c_int, vp, P(GroupQuantileResult), u32, P(u32)]),
     }

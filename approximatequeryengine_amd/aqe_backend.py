@@ -1308,6 +1308,47 @@ class CustomBPlusDB:
         """APPROX MEDIAN(amount) per key of ``by``: approx_quantile_by(0.5, by, **kw)."""
         return self.approx_quantile_by(0.5, by, **kw)
 
+    def approx_quantile_series(self, p, width: int, origin: int = 0, time_between: Optional[Tuple[int, int]] = None, method: str = "stride",
+                               sample_percent: float = 10.0, where: Optional[Tuple[float, float]] = None, id_between: Optional[Tuple[int, int]] = None,
+                               key_where: Optional[dict] = None, interpolation: str = "linear", confidence_level: float = 0.95, seed: int = 42,
+                               num_threads: int = 4, block_size: int = 1000):
+        """APPROX PERCENTILE(amount, p) per time bucket, BUCKET(timestamp, width[, origin]): for every bucket with a sampled row that
+        qualifies, numpy.quantile of that bucket's sampled amounts and the distribution-free interval from its own order
+        statistics — approx_quantile_by's definitions with the bucket's n — from ONE collecting sweep, a sort and a selection
+        (aqe_reduce_time_quantiles).  bucket(ts) = floor((ts - origin) / width); the result is an ordered ``dict`` keyed by the
+        bucket's start, ascending: a QuantileEstimate per bucket, or a list of them when ``p`` is a list (up to 8).
+        ``time_between`` = (t_lo, t_hi) keeps the rows with t_lo <= timestamp <= t_hi: a row outside is in no bucket, neither in
+        n nor in visited; a row inside counts in visited, and in n when it also passes ``where`` and ``key_where`` (a term on ONE
+        key column) and is no NaN.  method: as approx_quantile_by, and "rowid".  More than 1024 buckets, a table whose timestamps
+        span 2^31 or more, more than 2^28 sampled rows and the CLT, adaptive, stratified and random_device samplers raise
+        ValueError; there is no error-threshold form and no buckets x key column form."""
+        spec = time_spec(width, origin, time_between)
+        single = not isinstance(p, (list, tuple, np.ndarray))
+        probs = [float(p)] if single else [float(v) for v in p]
+        if not probs or len(probs) > nat.MAX_QUANTILES or any(not (0.0 <= v <= 1.0) for v in probs):
+            raise ValueError(f"1 .. {nat.MAX_QUANTILES} probabilities, each in [0, 1]")
+        if not float(sample_percent) > 0.0:
+            raise ValueError(f"sample_percent must be positive, got {sample_percent!r}")
+        q, interp = self._quantile_query("stride" if method == "rowid" else method, sample_percent, where, id_between, interpolation, confidence_level,
+                                         seed, num_threads, block_size)
+        if method == "rowid":
+            q.method = nat.M_ROWID_MOD
+        f = None if key_where is None else _key_filter_for(key_where, method)
+        if f is not None and f.term[0].form != nat.KEYTERM_NONE and f.term[1].form != nat.KEYTERM_NONE:
+            raise ValueError("time buckets take a key predicate on ONE key column (region or product_id), not on both")
+        out = {}
+        for entries in _quantile_call(lambda: self._quantile_series(f, q, spec, probs, interp)):
+            est = [QuantileEstimate(r, method) for r in entries]
+            out[int(entries[0].start)] = est[0] if single else est
+        return out
+
+    def _quantile_series(self, f, q, spec, probs, interp):
+        return self._eng().time_quantiles(q, spec, probs, interp, f)
+
+    def approx_median_series(self, width: int, **kw):
+        """APPROX MEDIAN(amount) per time bucket: approx_quantile_series(0.5, width, **kw)."""
+        return self.approx_quantile_series(0.5, width, **kw)
+
     def approx_spread(self, kind: str = "var_samp", method: str = "stride", sample_percent: float = 10.0,
                       where: Optional[Tuple[float, float]] = None, id_between: Optional[Tuple[int, int]] = None, seed: int = 42,
                       confidence_level: float = 0.95, group_by: Optional[str] = None, num_threads: int = 4, block_size: int = 1000,

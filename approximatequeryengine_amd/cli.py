@@ -448,6 +448,17 @@ _REFUSALS = {
         (lambda q, args: quantile_of(q) is None, "--quantile-by goes with MEDIAN / PERCENTILE, e.g. \"SELECT MEDIAN(amount) FROM sales\" --quantile-by region"),
         (lambda q, args: str(getattr(args, "quantile_by", "")).strip().lower() not in ("region", "product_id"),
          "--quantile-by takes region or product_id: the groups are the keys of one of the two key columns")),
+    "--quantile-bucket": (
+        (_has_e, "--quantile-bucket has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
+        (lambda q, args: getattr(args, "quantile_by", None) is not None, "--quantile-bucket has no --quantile-by form: buckets x key column is not supported "
+                                                                        "(a key predicate in WHERE picks one key)"),
+        (_bucketed, "--quantile-bucket goes with a query without a BUCKET(...) clause: MEDIAN / PERCENTILE have no GROUP BY BUCKET(...) form, the flag names "
+                    "the buckets"),
+        (lambda q, args: quantile_of(q) is None, "--quantile-bucket goes with MEDIAN / PERCENTILE, e.g. \"SELECT MEDIAN(amount) FROM sales\" --quantile-bucket 3600"),
+        (lambda q, args: len(key_where_of(q) or ()) > 1, "--quantile-bucket takes a key predicate on ONE of region / product_id: the time offsets take one of the "
+                                                         "sweep's two key slots"),
+        (lambda q, args: quantile_bucket_of(args) is None, "--quantile-bucket takes W[,origin]: an integer width of at least 1 and an optional integer origin, "
+                                                           "e.g. --quantile-bucket 3600 or --quantile-bucket 86400,-3600")),
     "quantile": (
         (_has_e, "quantiles have no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
         (_grouped, "GROUP BY is not supported with MEDIAN / PERCENTILE")),
@@ -726,6 +737,30 @@ def quantile_by_defect(clean: str, args) -> Optional[str]:
         return str(e)
 
 
+def quantile_bucket_of(args) -> Optional[Tuple[int, int]]:
+    """(width, origin) of --quantile-bucket W[,origin]; None when the text is not that (or the flag is absent)."""
+    text = getattr(args, "quantile_bucket", None)
+    m = re.fullmatch(r"\s*([+-]?\d+)\s*(?:,\s*([+-]?\d+)\s*)?", str(text)) if text is not None else None
+    if m is None or int(m.group(1)) < 1:
+        return None
+    return int(m.group(1)), int(m.group(2) or 0)
+
+
+def quantile_bucket_defect(pq: "ParsedQuery", args) -> Optional[str]:
+    """What is wrong with --quantile-bucket beside this query (None: nothing, or the flag is absent), found before the table is
+    opened: the routing table's refusals, then what parse_time_where refuses of the WHERE clause's timestamp terms."""
+    if getattr(args, "quantile_bucket", None) is None:
+        return None
+    try:
+        why = _refusal("--quantile-bucket", pq.text, args)
+        if why is None:
+            from .engine import parse_time_where
+            parse_time_where(pq.rest)
+        return why
+    except ValueError as e:  # (a probability outside [0, 1]; a timestamp term that cannot be read)
+        return str(e)
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="aqe", description="Approximate SUM/AVG/COUNT, MEDIAN/PERCENTILE, VARIANCE/STDDEV, MIN/MAX, HISTOGRAM, COUNT(DISTINCT), SUMMARY on MI355X "
                                 "(e.g. \"SELECT HISTOGRAM(amount, 20) FROM sales\" --s 10 --ci; \"SELECT SUMMARY(amount) FROM sales\" --s 10 --ci)",
@@ -757,6 +792,9 @@ def build_parser() -> argparse.ArgumentParser:
                    "from one sweep; at most 1024 groups")
     p.add_argument("--quantile-by", dest="quantile_by", metavar="COLUMN", help="with MEDIAN / PERCENTILE: one value per key of COLUMN (region or product_id), "
                    "from one collecting sweep and a sort; at most 1024 groups; a key predicate in WHERE is honoured")
+    p.add_argument("--quantile-bucket", dest="quantile_bucket", metavar="W[,ORIGIN]", help="with MEDIAN / PERCENTILE: one value per time bucket of width W "
+                   "(from ORIGIN, default 0), from one collecting sweep and a sort; at most 1024 buckets; the WHERE clause's timestamp terms are the "
+                   "window, a key predicate on one key column is honoured")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="under torchrun (one process per GPU): the torch.distributed backend (nccl = RCCL)")
     p.add_argument("--collective", choices=["torch", "mailbox"], default="torch", help="under torchrun: the all-reduce of the moment vectors "
@@ -782,7 +820,7 @@ def _query_defect(pq: ParsedQuery, args) -> Optional[str]:
         if args.e is not None:
             return (f"the CLT sampler (--e) samples the whole table and has no form for the key predicate 'WHERE {pq.where}': "
                     "give a sample percentage (--s) or none (exact)")
-        if family == "quantile" and getattr(args, "quantile_by", None) is None:
+        if family == "quantile" and getattr(args, "quantile_by", None) is None and getattr(args, "quantile_bucket", None) is None:
             return f"MEDIAN / PERCENTILE under the key predicate 'WHERE {pq.where}' are not supported yet"
     return _refusal("GROUP BY", clean, args)
 
@@ -803,7 +841,8 @@ def run(args, out=sys.stdout) -> int:
     if why is not None:
         print(f"error: {why}", file=out)
         return 2
-    why = (per_group_defect(pq.text, args) or distinct_by_defect(pq.text, args) or quantile_by_defect(pq.text, args) or having_defect(pq.text, args)
+    why = (per_group_defect(pq.text, args) or distinct_by_defect(pq.text, args) or quantile_bucket_defect(pq, args) or quantile_by_defect(pq.text, args)
+           or having_defect(pq.text, args)
            or max_groups_defect(pq.rest, args) or top_defect(pq.rest, args))  # (the first three read the query with its HAVING clause)
     if why is None:
         try:
@@ -1051,6 +1090,24 @@ def _run_quantile(db, args, out, pq, qtype, t0, kw) -> int:
             print(f"   {by} {key}: {g.value:,.4f}{ci}   n={g.n:,}", file=out)
             kernel_ms = g.kernel_ms
         print(f"   {len(groups)} groups", file=out)
+        print(f"   execution time: {ms:.2f} ms (kernels {kernel_ms * 1e3:.1f} us)", file=out)
+        return 0
+    if getattr(args, "quantile_bucket", None) is not None:  # one value per time bucket: a line per bucket start, then their number
+        from .engine import parse_time_where
+        width, origin = quantile_bucket_of(args)
+        window = parse_time_where(pq.rest)  # the WHERE clause's timestamp terms are the bucketed window (None: none)
+        if window is not None:
+            print(f"window: timestamp {window[0]} .. {window[1]}", file=out)
+        series = db.approx_quantile_series(p, width, origin=origin, time_between=window, method=method, sample_percent=pct, where=where, interpolation=interp,
+                                           confidence_level=args.confidence, seed=args.seed, num_threads=args.threads, **kw)
+        ms = (time.perf_counter() - t0) * 1e3
+        print(f"\n{name} {fname}(amount{'' if fname == 'MEDIAN' else f', {p:g}'}) per bucket of {width}{f' from {origin}' if origin else ''} result:", file=out)
+        kernel_ms = 0.0
+        for start, g in series.items():
+            ci = f"   ({g.ci_lower:,.4f} - {g.ci_upper:,.4f})" if (args.ci and method != "exact") else ""
+            print(f"   {start}: {g.value:,.4f}{ci}   n={g.n:,}", file=out)
+            kernel_ms = g.kernel_ms
+        print(f"   {len(series)} buckets", file=out)
         print(f"   execution time: {ms:.2f} ms (kernels {kernel_ms * 1e3:.1f} us)", file=out)
         return 0
     res = db.approx_quantile(p, method=method, sample_percent=pct, where=where, interpolation=interp,

@@ -32,11 +32,25 @@
 // n_g >= 1 in ascending key order by a prefix over ballots, no atomics; then one thread per (listed group, probability) places
 // the ranks (quantile_core.hpp: the ONE copy quantile.hip and the host restatement share), reads their elements and writes the
 // entry.  Single GPU: the segments are checked against the sweep's own n_g counters (device status 3 on a mismatch).
+//
+// k_tq_collect.  MEDIAN / PERCENTILE per TIME BUCKET (aqe_reduce_time_quantiles and its sharded collect): the same collecting
+// sweep with the bin a time bucket.  Slot 0 carries the int32 time offsets, slot 1 the ONE key column under a term (NK = 2);
+// bin = bin0 + floor((u + add) / div) by time_bucket_core.hpp's exact multiply-high division, the window the inclusive offset
+// range [ulo, uhi].  The rows follow the bucketed forms (timeseries.hip): a sampled row outside the window is in no bucket,
+// neither n nor visited; one inside counts in its bucket's visited, and in n with its pair collected when it passes the amount
+// range and the key term and is no NaN.  On a time-ordered table every lane of a wave holds the same bucket, the worst case for
+// two LDS atomics per row on one address: when all in-window lanes of a visit hold one bucket (a ballot against the first such
+// lane's bin) one lane adds the two popcounts, otherwise the lanes add for themselves — integers either way, the same counts
+// (AQE_TQ_WAVE=0, read per launch, turns the wave step off).  Under a window on the tile source the zone map is probed one tile
+// ahead (zone_probe.hpp) and a tile none of whose zones meets the window is skipped with no load: outside rows are in no
+// visited, so nothing needs accounting.  Everything behind the sweep — sorts, offsets, selection, place / union / finish — is
+// the grouped form's, on opaque bins.
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
 #include <limits>
 #include <string>
+#include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -45,6 +59,8 @@
 #include "key_term.hpp"
 #include "quantile_core.hpp"
 #include "sweep_host.hpp"
+#include "time_bucket_core.hpp"
+#include "zone_probe.hpp"
 
 namespace aqe {
 namespace {
@@ -206,6 +222,179 @@ __global__ __launch_bounds__(kGqSelectThreads) void k_gq_unplace(const double* _
     }
 }
 
+// ---- the collecting sweep per time bucket ---------------------------------------------------------------------------------------
+
+struct TqLaunch {
+    SweepCommon sw;
+    u64 ntiles;
+    const uint64_t* idx;  // the seeded random sampler: global rows (else null)
+    u64 n_idx;
+    const int32_t* keys[2];      // [0] the time offsets, [1] the key column under the term (or their stride-major views)
+    unsigned long long* counts;  // [nbins][2] {n, visited}, zero before the launch
+    unsigned long long* cursor;  // [0] entries reserved, [1] status; zero before the launch
+    unsigned long long* skipped; // tiles skipped; zero before the launch
+    u64* out_keys;               // [capacity]
+    unsigned* out_bins;          // [capacity]
+    u64 capacity;
+    double wmin, wmax;       // the inclusive amount range; -inf / +inf without one
+    uint32_t nbins;
+    uint32_t ulo, uhi;       // the window as inclusive offsets (ulo > uhi: no row)
+    uint32_t add, div;       // bin = bin0 + floor((u + add) / div); u + add < 2^32
+    uint32_t m_hi, m_lo;     // ceil(2^64 / div), div >= 2
+    int32_t bin0;
+    uint32_t wave;           // the wave-level counting step (AQE_TQ_WAVE)
+    DevFilter flt;           // t[1] / map[1]: the key term (NK == 2)
+    const Zone* zones;       // of keys[0]; null: every tile is read (no window, AQE_ZONE_SKIP=0, the index list)
+    u64 n_elems;             // elements of keys[0] the zones cover
+};
+static_assert(sizeof(TqLaunch) <= 4096, "kernel arguments are limited to 4 KB");
+
+template <bool kNT, int NK>
+__global__ __launch_bounds__(kGqThreads) void k_tq_collect(TqLaunch a) {
+    static_assert(NK == 1 || NK == 2, "the time column, and the key column under a term");
+    __shared__ u64 st_key[kGqWaves][kGqStage];
+    __shared__ unsigned short st_bin[kGqWaves][kGqStage];
+    __shared__ unsigned cnt[kGqMaxBins][2];
+    __shared__ DevFamily lds_fams[kMaxLdsFams];
+    __shared__ u64 s_map[2][kMapWords];
+    const unsigned tid = threadIdx.x;
+    const int lane = tid & 63;
+    const unsigned nbins = a.nbins;  // (<= kGqMaxBins: time_plan's refusal)
+    for (unsigned i = tid; i < 2 * nbins; i += kGqThreads) (&cnt[0][0])[i] = 0u;
+    stage_maps<TqLaunch>(s_map);  // (ends with a barrier)
+    u64* const mk = st_key[tid >> 6];
+    unsigned short* const mb = st_bin[tid >> 6];
+    const double wmin = a.wmin, wmax = a.wmax;
+    const unsigned ulo = a.ulo, uhi = a.uhi, add = a.add, m_hi = a.m_hi, m_lo = a.m_lo;
+    const bool div_one = a.div == 1u, wave_step = a.wave != 0u;
+    const int bin0 = a.bin0;
+    const DevTerm T1 = a.flt.t[1];
+    const u64 capacity = a.capacity;
+    unsigned staged = 0;  // wave-uniform: entries parked since the last flush
+    bool stage_full = false;
+    // (wave-uniform control flow, every lane active: the ballots see the whole wave)
+    auto visit = [&](double x, int k0, int k1, bool ok) {
+        const unsigned u = static_cast<unsigned>(k0), s = u + add;
+        const unsigned q = div_one ? s : div_magic(s, m_hi, m_lo);
+        const unsigned bin = static_cast<unsigned>(bin0) + q;  // (modulo 2^32: a row far outside the window wraps, and fails `in`)
+        const bool in = ok && u >= ulo && u <= uhi && bin < nbins;  // (the host checked the shard's range: a row in the window has bin < nbins)
+        bool pass = in && x >= wmin && x <= wmax;                   // inclusive both ends; a NaN fails both
+        if (NK >= 2) pass = pass && term_pass(T1, s_map[1], k1);
+        const u64 m_in = __ballot(in), m = __ballot(pass);
+        if (m_in != 0ull) {
+            bool one = false;
+            unsigned first = 0;
+            if (wave_step) {
+                first = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(bin), static_cast<int>(__ffsll(static_cast<long long>(m_in))) - 1));
+                one = __ballot(in && bin != first) == 0ull;
+            }
+            if (one) {  // every in-window lane holds bucket `first` (< nbins: that lane is in): one lane adds the popcounts
+                if (lane == 0) {
+                    __hip_atomic_fetch_add(&cnt[first][1], static_cast<unsigned>(__popcll(m_in)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (m != 0ull) __hip_atomic_fetch_add(&cnt[first][0], static_cast<unsigned>(__popcll(m)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            } else {
+                if (in) __hip_atomic_fetch_add(&cnt[bin][1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (pass) __hip_atomic_fetch_add(&cnt[bin][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+        const unsigned below = __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(m), 0u));
+        const unsigned pos = staged + below;
+        if (pass) {
+            if (pos < kGqStage) { mk[pos] = okey(x); mb[pos] = static_cast<unsigned short>(bin); }
+            else stage_full = true;  // (never: a tile has at most kGqStage slots)
+        }
+        staged += static_cast<unsigned>(__popcll(m));
+    };
+    // the wave's parked entries out to the device arrays: one reservation, contiguous stores (k_gq_collect's)
+    auto flush = [&]() {
+        const unsigned count = staged < kGqStage ? staged : kGqStage;
+        staged = 0;
+        if (count == 0) return;
+        unsigned long long base = 0;
+        if (lane == 0) base = __hip_atomic_fetch_add(a.cursor, static_cast<unsigned long long>(count), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        base = uniform64(base);
+        if (base + count > capacity) {  // would end past the arrays: nothing is stored
+            if (lane == 0) __hip_atomic_fetch_or(a.cursor + 1, static_cast<unsigned long long>(kGqStatusOverrun), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
+        wave_lds_handoff();  // the lanes' parked entries, before other lanes read them
+        for (unsigned i = lane; i < count; i += 64u) {
+            a.out_keys[base + i] = mk[i];
+            a.out_bins[base + i] = mb[i];
+        }
+        wave_lds_handoff();  // ... and the reads, before the next tile parks over them
+    };
+    unsigned skipped = 0;  // wave-uniform
+    if (a.idx) {           // the index list: read and tested per row, no skip
+        constexpr u64 kChunk = static_cast<u64>(kGqThreads) * kTileUnroll;
+        for (u64 c0 = static_cast<u64>(blockIdx.x) * kChunk; c0 < a.n_idx; c0 += static_cast<u64>(gridDim.x) * kChunk) {
+            u64 off[kTileUnroll];
+            bool ok[kTileUnroll];
+#pragma unroll
+            for (int k = 0; k < kTileUnroll; ++k) {
+                const u64 i = c0 + tid + static_cast<u64>(k) * kGqThreads;
+                ok[k] = i < a.n_idx;
+                const u64 row = a.idx[ok[k] ? i : 0];
+                off[k] = ok[k] ? row - a.sw.shard_lo : 0;
+            }
+            double v[kTileUnroll];
+            int ka[kTileUnroll], kb[kTileUnroll];
+#pragma unroll
+            for (int k = 0; k < kTileUnroll; ++k) {
+                v[k] = a.sw.amount[off[k]];
+                ka[k] = a.keys[0][off[k]];
+                kb[k] = NK >= 2 ? a.keys[1][off[k]] : 0;
+            }
+#pragma unroll
+            for (int k = 0; k < kTileUnroll; ++k) visit(v[k], ka[k], kb[k], ok[k]);
+            flush();
+        }
+    } else {
+        const DevFamily* fams = stage_families(a.sw, lds_fams);
+        const u64 wave_id = uniform64(static_cast<u64>(blockIdx.x) * kGqWaves + (tid >> 6));
+        const u64 wave_stride = static_cast<u64>(gridDim.x) * kGqWaves;
+        const bool judge = a.zones != nullptr;
+        const bool empty = ulo > uhi;
+        const int wlo = static_cast<int>(ulo), whi = static_cast<int>(uhi);  // (offsets are below 2^31)
+        Probe cur;
+        cur.can = cur.active = false;
+        cur.z = Zone{0, 0};
+        if (judge && wave_id < a.ntiles) cur = probe_tile(a.sw, a.zones, a.n_elems, fams, wave_id, lane);
+        for (u64 t = wave_id; t < a.ntiles; t += wave_stride) {
+            // the next tile's zones are on their way while this tile is visited
+            const u64 tn = t + wave_stride;
+            Probe nxt;
+            nxt.can = nxt.active = false;
+            nxt.z = Zone{0, 0};
+            if (judge && tn < a.ntiles) nxt = probe_tile(a.sw, a.zones, a.n_elems, fams, tn, lane);
+            const bool meets = cur.active && !empty && cur.z.min <= whi && cur.z.max >= wlo;
+            if (cur.can && __ballot(meets) == 0ull) ++skipped;  // no row of the tile lies in the window: no bucket, no load
+            else {
+                visit_tile<kNT, NK>(a.sw, fams, a.keys[0], a.keys[1], t, lane, visit);
+                flush();
+            }
+            cur = nxt;
+        }
+    }
+    if (__any(stage_full) && lane == 0) __hip_atomic_fetch_or(a.cursor + 1, static_cast<unsigned long long>(kGqStatusStage), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (skipped && lane == 0) __hip_atomic_fetch_add(a.skipped, static_cast<unsigned long long>(skipped), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();  // every wave's counts are in
+    // this workgroup's counts into the device counters: integer atomics, exact in any order
+    for (unsigned i = tid; i < 2 * nbins; i += kGqThreads) {
+        const unsigned v = (&cnt[0][0])[i];
+        if (v) __hip_atomic_fetch_add(a.counts + i, static_cast<unsigned long long>(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// After the sweep, on its stream: {tiles of the sample, tiles skipped} into the pinned pair aqe_last_window_tiles reads.
+__global__ __launch_bounds__(64) void k_tq_tiles(const unsigned long long* __restrict__ skipped, unsigned long long tiles, unsigned long long* __restrict__ counts) {
+    if (threadIdx.x == 0) {
+        counts[0] = tiles;
+        counts[1] = *skipped;
+    }
+}
+
 struct GqMeta {
     unsigned listed, status;
 };
@@ -296,6 +485,7 @@ struct aqe_gquantile_scratch {
     aqe::DeviceBuf<char> d_tmp;                   // rocPRIM's temporary storage
     aqe::DeviceBuf<unsigned long long> d_counts;  // [kGqMaxBins][2]
     aqe::DeviceBuf<unsigned long long> d_cursor;  // [2]
+    aqe::DeviceBuf<unsigned long long> d_tiles;   // [1]: tiles k_tq_collect skipped
     aqe::DeviceBuf<double> d_visited;             // [kGqMaxBins]: the single-GPU form's visited per bin
     aqe::DeviceBuf<aqe::u64> d_off;               // [kGqMaxBins + 1]
     aqe::DeviceBuf<unsigned> d_list;              // [kGqMaxBins]
@@ -321,6 +511,7 @@ int ensure_scratch(aqe_ctx* c) {
     return ensure_scratch(c, c->gquantile, [c](aqe_gquantile_scratch& s) -> int {
         int rc = s.d_counts.alloc(c, 2 * static_cast<size_t>(kGqMaxBins));
         if (rc == AQE_OK) rc = s.d_cursor.alloc(c, 2);
+        if (rc == AQE_OK) rc = s.d_tiles.alloc(c, 1);
         if (rc == AQE_OK) rc = s.d_visited.alloc(c, kGqMaxBins);
         if (rc == AQE_OK) rc = s.d_off.alloc(c, kGqMaxBins + 1);
         if (rc == AQE_OK) rc = s.d_list.alloc(c, kGqMaxBins);
@@ -539,6 +730,123 @@ int sort_select(aqe_ctx* c, const aqe_query* q, int32_t key_min, uint32_t nbins,
     return AQE_OK;
 }
 
+// ---- per time bucket ------------------------------------------------------------------------------------------------------------
+
+constexpr Wording kTqWords{"MEDIAN / PERCENTILE per time bucket do not take the ", "MEDIAN / PERCENTILE per time bucket have no grouped refusal of their own"};
+static_assert(kMaxTimeBuckets == static_cast<int64_t>(kGqMaxBins), "time_plan's refusal keeps a bucket inside the counters and the u16 of the staging area");
+static_assert(sizeof(aqe_time_quantile_result) == 112 && offsetof(aqe_time_quantile_result, key) == 8 && offsetof(aqe_time_quantile_result, kernel_ms) == 104,
+              "layout of include/aqe_hip.h: a start, then aqe_group_quantile_result");
+
+template <bool NT, int NK>
+void tq_launch_as(unsigned grid, hipStream_t s, const TqLaunch& a) {
+    hipLaunchKernelGGL((k_tq_collect<NT, NK>), dim3(grid), dim3(kGqThreads), 0, s, a);
+}
+
+// The entries up to the launch, behind their argument checks: the buckets of [tmin, tmax], the one key column under a term,
+// the plan, the scratch.
+int tq_prologue(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const aqe_time_spec* spec, int64_t tmin, int64_t tmax, TimePlan* tp, int* column, aqe_plan** p) {
+    if (!q) return fail(c, AQE_ERR_INVALID, "null query");
+    int rc = time_plan(spec, tmin, tmax, tp);
+    if (rc != AQE_OK) return fail(c, rc, tp->why);
+    rc = term_column(c, f, column);
+    if (rc != AQE_OK) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = moment_plan(c, q, false, kTqWords, p);
+    if (rc == AQE_OK) rc = ensure_scratch(c);
+    return rc;
+}
+
+// The collecting sweep on `s`: this shard's pairs into the scratch (none when nothing of the sample lies in this shard or in
+// the window), the counters, the cursor, and the launch's tile counts into the pinned pair of aqe_last_window_tiles.  Refuses
+// a sample past the row cap by the plan's own count, before any launch.
+int tq_enqueue_collect(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, int column, const aqe_time_spec* spec, const TimePlan& tp, hipStream_t s) {
+    aqe_gquantile_scratch* sc = c->gquantile;
+    TqLaunch a{};
+    a.sw = SweepCommon{};
+    unsigned grid = 1;
+    uint64_t rows = 0;
+    const Source src = sweep_source(c, p, a);
+    if (src == Source::index_list) { grid = blocks_for(a.n_idx, static_cast<u64>(kGqThreads) * kTileUnroll, kGqGrid); rows = a.n_idx; }
+    else if (src == Source::tiles) { grid = blocks_for(a.ntiles, kGqWaves, kGqGrid); rows = a.ntiles ? p->rounds[0].samples : 0; }
+    int rc = rows_ok(c, rows);
+    if (rc == AQE_OK) rc = grow_for(c, rows, bits_for(tp.nbuckets));
+    if (rc != AQE_OK) return rc;
+    unsigned long long* pinned = nullptr;
+    rc = window_counts(c, s, &pinned);
+    if (rc != AQE_OK) return rc;
+    HIPCHK(c, hipMemsetAsync(sc->d_counts, 0, 2 * sizeof(unsigned long long) * kGqMaxBins, s));
+    HIPCHK(c, hipMemsetAsync(sc->d_cursor, 0, 2 * sizeof(unsigned long long), s));
+    HIPCHK(c, hipMemsetAsync(sc->d_tiles, 0, sizeof(unsigned long long), s));
+    const bool work = (a.ntiles > 0 || a.n_idx > 0) && c->n_local > 0;
+    if (!work) {  // nothing of the sample lies in this shard: no pairs, no tiles
+        hipLaunchKernelGGL(k_tq_tiles, dim3(1), dim3(64), 0, s, sc->d_tiles.get(), 0ull, pinned);
+        HIPCHK(c, hipGetLastError());
+        return AQE_OK;
+    }
+    rc = ensure_time(c);  // (carries the refusal of a shard whose span is 2^31 or more)
+    if (rc != AQE_OK) return rc;
+    // some row of this shard may lie in [lo, hi]: the constants of its offsets; else the empty window, which reads no row
+    if (tp.nbuckets > 0 && c->time_min <= tp.hi && c->time_max >= tp.lo) {
+        const BucketConsts k = bucket_consts(spec, tp, c->time_min, c->time_max);
+        a.ulo = k.ulo; a.uhi = k.uhi; a.add = k.add; a.div = k.div; a.m_hi = k.m_hi; a.m_lo = k.m_lo; a.bin0 = k.bin0;
+    } else {
+        a.ulo = 1u; a.uhi = 0u; a.div = 1u;
+    }
+    a.nbins = tp.nbuckets;
+    // the columns: the time offsets in key slot 0, the key column under the term in slot 1; the zone map of slot 0's array
+    int nk = 1;
+    a.flt.t[0] = a.flt.t[1] = pass_all();
+    if (p->host.is_random) a.keys[0] = c->keycol[kTimeColumn - 1];
+    else if ((rc = key_pointer(c, p, kTimeColumn, &a.keys[0])) != AQE_OK) return rc;
+    if (column) {
+        compile_term(f->term[column - 1], &a.flt.t[1], a.flt.map[1]);
+        rc = p->host.is_random ? ensure_keys(c, column) : key_pointer(c, p, column, &a.keys[1]);
+        if (rc != AQE_OK) return rc;
+        if (p->host.is_random) a.keys[1] = c->keycol[column - 1];
+        nk = 2;
+    }
+    if (!p->host.is_random && spec->has_window) {
+        bool skip = true;
+        if (const char* e = std::getenv("AQE_ZONE_SKIP")) skip = e[0] != '0';  // diagnostics, read per launch: 0 reads every tile
+        if (skip) {
+            uint64_t n_elems = c->n_local;
+            if (p->view_rounds) {  // the rows index a stride-major view: its slots
+                auto it = c->stride_views.find(p->view_step_rounds);
+                if (it == c->stride_views.end()) return fail(c, AQE_ERR_INVALID, "internal: a plan over a view that is gone");
+                n_elems = p->view_step_rounds * it->second.M;
+            }
+            rc = ensure_zones(c, a.keys[0], n_elems, &a.zones);
+            if (rc != AQE_OK) return rc;
+            a.n_elems = n_elems;
+        }
+    }
+    a.counts = sc->d_counts;
+    a.cursor = sc->d_cursor;
+    a.skipped = sc->d_tiles;
+    a.out_keys = sc->d_keys[0];
+    a.out_bins = sc->d_bins[0];
+    a.capacity = std::min<uint64_t>(rows, sc->capacity);  // (what the plan counted; the arrays hold at least that)
+    a.wmin = p->q.has_where ? p->q.where_min : -std::numeric_limits<double>::infinity();
+    a.wmax = p->q.has_where ? p->q.where_max : std::numeric_limits<double>::infinity();
+    a.wave = 1u;
+    if (const char* e = std::getenv("AQE_TQ_WAVE")) a.wave = e[0] != '0' ? 1u : 0u;  // diagnostics (tools/time_quantile_time.py): the wave-level step off
+    const bool nt = a.sw.nt != 0;
+    c->last_nt = nt ? 1 : 0;
+    if (nk == 1) {
+        if (nt) tq_launch_as<true, 1>(grid, s, a);
+        else tq_launch_as<false, 1>(grid, s, a);
+    } else {
+        if (nt) tq_launch_as<true, 2>(grid, s, a);
+        else tq_launch_as<false, 2>(grid, s, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    constexpr u64 kChunk = static_cast<u64>(kGqThreads) * kTileUnroll;
+    const unsigned long long tiles = a.idx ? (a.n_idx + kChunk - 1) / kChunk : a.ntiles;  // (the index list: its chunks, none skipped)
+    hipLaunchKernelGGL(k_tq_tiles, dim3(1), dim3(64), 0, s, sc->d_tiles.get(), tiles, pinned);
+    HIPCHK(c, hipGetLastError());
+    return AQE_OK;
+}
+
 }  // namespace
 
 void gquantile_release(aqe_ctx* c) { release_scratch(c, c->gquantile); }
@@ -666,6 +974,89 @@ int aqe_grouped_quantile_finish(aqe_ctx* c, const aqe_query* q, int32_t key_min,
                        sc->d_keys[0].get(), sc->d_bins[0].get());
     HIPCHK(c, hipGetLastError());
     return sort_select(c, q, key_min, nbins, total, dev_visited, false, probs, n_probs, interpolation, s, out, cap, n_groups, nullptr, nullptr);
+}
+
+int aqe_reduce_time_quantiles(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const aqe_time_spec* spec, const double* probs, uint32_t n_probs, int interpolation,
+                              aqe_time_quantile_result* out, uint32_t cap, uint32_t* n_buckets) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!q || !n_buckets || (cap && !out)) return fail(c, AQE_ERR_INVALID, "null argument");
+    *n_buckets = 0;
+    int rc = probs_ok(c, probs, n_probs, interpolation);
+    if (rc != AQE_OK) return rc;
+    if (const char* d = spec_defect(spec)) return fail(c, AQE_ERR_INVALID, d);
+    int64_t tmin = 0, tmax = 0;
+    rc = aqe_time_range(c, &tmin, &tmax);
+    if (rc != AQE_OK) return rc;
+    TimePlan tp;
+    int column = 0;
+    aqe_plan* p = nullptr;
+    rc = tq_prologue(c, f, q, spec, tmin, tmax, &tp, &column, &p);
+    if (rc != AQE_OK) return rc;
+    const uint32_t nbins = tp.nbuckets;
+    aqe_gquantile_scratch* sc = c->gquantile;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipEventRecord(sc->ev[0], s));
+    rc = tq_enqueue_collect(c, p, f, column, spec, tp, s);  // (a window that leaves nothing: the sweep runs, and skips what the zone map rules out)
+    if (rc != AQE_OK) return rc;
+    if (nbins == 0) return fail(c, AQE_ERR_INVALID, "No samples collected");
+    hipLaunchKernelGGL(k_gq_publish, dim3((nbins + kGqSelectThreads - 1) / kGqSelectThreads), dim3(kGqSelectThreads), 0, s, sc->d_counts.get(), sc->d_cursor.get(), nbins,
+                       static_cast<double*>(nullptr), sc->d_visited.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(sc->ev[1], s));
+    // the number of pairs sizes the sorts: one round trip
+    HIPCHK(c, hipMemcpyAsync(sc->h_words, sc->d_cursor.get(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const unsigned long long total = sc->h_words[0], status = sc->h_words[1];
+    if (status || total > sc->capacity)
+        return fail(c, AQE_ERR_INTERNAL, "MEDIAN / PERCENTILE per time bucket: the collecting sweep met more rows than the plan counted (device status " + std::to_string(status) +
+                                             ", " + std::to_string(total) + " pairs, room for " + std::to_string(sc->capacity) + "); nothing was stored past the arrays");
+    std::vector<aqe_group_quantile_result> bins(static_cast<size_t>(nbins) * n_probs);
+    uint32_t listed = 0;
+    rc = sort_select(c, q, 0, nbins, total, sc->d_visited.get(), true, probs, n_probs, interpolation, s, bins.data(), nbins, &listed, sc->ev[2], sc->ev[3]);
+    if (rc != AQE_OK) return rc;
+    *n_buckets = listed;
+    if (listed > cap)  // no partial list
+        return fail(c, AQE_ERR_INVALID, "MEDIAN / PERCENTILE per time bucket: " + std::to_string(listed) + " buckets, more than the caller's buffer holds (cap " + std::to_string(cap) + ")");
+    float t01 = 0.0f, t12 = 0.0f, t23 = 0.0f;
+    if (hipEventElapsedTime(&t01, sc->ev[0], sc->ev[1]) == hipSuccess && hipEventElapsedTime(&t12, sc->ev[1], sc->ev[2]) == hipSuccess &&
+        hipEventElapsedTime(&t23, sc->ev[2], sc->ev[3]) == hipSuccess) {
+        sc->ms[0] = t01; sc->ms[1] = t12; sc->ms[2] = t23;
+    }
+    const double ms = sc->ms[0] + sc->ms[1] + sc->ms[2];
+    for (size_t i = 0; i < static_cast<size_t>(listed) * n_probs; ++i) {
+        aqe_time_quantile_result& e = out[i];
+        e.start = bucket_start(spec, tp.first, static_cast<uint32_t>(bins[i].key));  // (key: the bucket's bin, the sweep's key_min being 0)
+        std::memcpy(&e.key, &bins[i], sizeof(aqe_group_quantile_result));
+        e.kernel_ms = ms;
+    }
+    return AQE_OK;
+}
+
+int aqe_time_quantiles_enqueue_collect(aqe_ctx* c, const aqe_key_filter* f, const aqe_query* q, const aqe_time_spec* spec, int64_t tmin, int64_t tmax, double* dev_count,
+                                       double* dev_visited, void* stream) {
+    if (!c) return AQE_ERR_INVALID;
+    if (!dev_count || !dev_visited) return fail(c, AQE_ERR_INVALID, "null argument");
+    TimePlan tp;
+    int column = 0;
+    aqe_plan* p = nullptr;
+    int rc = tq_prologue(c, f, q, spec, tmin, tmax, &tp, &column, &p);
+    if (rc != AQE_OK) return rc;
+    if (c->n_local) {
+        rc = ensure_time(c);
+        if (rc != AQE_OK) return rc;
+        if (c->time_min < tmin || c->time_max > tmax) return fail(c, AQE_ERR_INVALID, "this shard has timestamps outside [tmin, tmax]");
+    }
+    hipStream_t s = stream_of(c, stream);
+    rc = tq_enqueue_collect(c, p, f, column, spec, tp, s);
+    if (rc != AQE_OK) return rc;
+    if (tp.nbuckets == 0) {  // no bucket: no pair, and no word of dev_visited
+        HIPCHK(c, hipMemsetAsync(dev_count, 0, sizeof(double), s));
+        return AQE_OK;
+    }
+    hipLaunchKernelGGL(k_gq_publish, dim3((tp.nbuckets + kGqSelectThreads - 1) / kGqSelectThreads), dim3(kGqSelectThreads), 0, s, c->gquantile->d_counts.get(),
+                       c->gquantile->d_cursor.get(), tp.nbuckets, dev_count, dev_visited);
+    HIPCHK(c, hipGetLastError());
+    return AQE_OK;
 }
 
 }  // extern "C"

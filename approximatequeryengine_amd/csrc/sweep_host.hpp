@@ -257,6 +257,20 @@ int bind_group_filter(const GroupCols& g, const aqe_key_filter* f, KeyOf&& key_o
     return s.fetch_second ? key_of(s.col[1], &a.keys[1]) : AQE_OK;
 }
 
+// The one key column a filter may carry a term on (0: none); terms on both are refused (the time-bucketed
+// sweeps: timeseries.hip, k_tq_collect of group_quantile.hip).
+inline int term_column(aqe_ctx* c, const aqe_key_filter* f, int* column) {
+    *column = 0;
+    if (!f) return AQE_OK;
+    const int rc = check_filter(c, f);
+    if (rc != AQE_OK) return rc;
+    const bool r = f->term[0].form != AQE_KEYTERM_NONE, p = f->term[1].form != AQE_KEYTERM_NONE;
+    if (r && p)
+        return fail(c, AQE_ERR_UNSUPPORTED, "time buckets take a key predicate on ONE key column (region or product_id), not on both: the sweep has one key slot beside the time column");
+    *column = r ? AQE_GROUP_REGION : p ? AQE_GROUP_PRODUCT : 0;
+    return AQE_OK;
+}
+
 // f(NT, NK) with std::integral_constant arguments for the load policy and the number of key slots 0 .. 2.
 template <typename F>
 void dispatch_nt_nk(bool nt, int nk, F&& f) {

@@ -27,6 +27,7 @@
 #include "host.hpp"
 #include "key_term.hpp"
 #include "sweep_host.hpp"
+#include "time_bucket_core.hpp"
 
 static_assert(sizeof(aqe_series_result) == 80, "layout of include/aqe_hip.h");
 
@@ -40,7 +41,6 @@ constexpr unsigned kSeriesTargetBlocks = 1024;  // workgroups of a launch over a
 constexpr unsigned kSeriesMaxCopies = 16;
 constexpr unsigned kSeriesCopyBins = 2048;      // copies x slice_bins stays within 64 KiB of LDS
 constexpr unsigned kSeriesFinishThreads = 256;
-constexpr int64_t kMaxTimeSpan = (1ll << 31) - 1;
 static_assert(kSeriesMaxSlice * kSeriesBin * 8 == 128 * 1024, "the largest slice is 128 KiB of LDS");
 static_assert(kSeriesMinSlice % 16 == 0, "64 consecutive words of the bins lie in one slice");
 static_assert(kMaxSeriesBins / kSeriesFinishThreads <= kSeriesFinishThreads, "one thread per earlier workgroup's count");
@@ -64,13 +64,6 @@ struct SeriesLaunch {
     DevFilter flt;           // t[1] / map[1]: the term on the group column (pass-all without one)
 };
 static_assert(sizeof(SeriesLaunch) <= 4096, "kernel arguments are limited to 4 KB");
-
-// floor(n / d) for d >= 2 from M = ceil(2^64 / d) = m_hi 2^32 + m_lo: the top word of the 96-bit product n M (timeseries.hip has
-// the proof; restated here because that one lives in its translation unit).
-__host__ __device__ __forceinline__ unsigned div_magic(unsigned n, unsigned m_hi, unsigned m_lo) {
-    const u64 low = static_cast<u64>(n) * m_lo;
-    return static_cast<unsigned>((static_cast<u64>(n) * m_hi + (low >> 32)) >> 32);
-}
 
 // What a cell's key and start follow from, and the estimator's parameters.
 struct SeriesFinish {
@@ -288,67 +281,9 @@ __global__ __launch_bounds__(kSeriesFinishThreads) void k_series_finish(const do
     if (blockIdx.x == gridDim.x - 1 && tid == kSeriesFinishThreads - 1) counts[gridDim.x] = pos + (flag ? 1u : 0u);
 }
 
-// ---- the plan: aqe_time_plan's buckets (restated: that code lives in timeseries.hip's translation unit), times the keys ------
+// ---- the plan: aqe_time_plan's buckets (time_bucket_core.hpp), times the keys ----------------------------------------------------
 
-typedef __int128 i128;
-
-inline i128 floor_div(i128 a, i128 b) {  // b > 0
-    i128 q = a / b;
-    if (a % b != 0 && a < 0) --q;
-    return q;
-}
-inline int64_t saturate(i128 v) {
-    const i128 lo = std::numeric_limits<int64_t>::min(), hi = std::numeric_limits<int64_t>::max();
-    return static_cast<int64_t>(v < lo ? lo : v > hi ? hi : v);
-}
-
-const char* spec_defect(const aqe_time_spec* s) {
-    if (!s) return "null time spec";
-    if (s->width < 1) return "BUCKET: the width must be at least 1";
-    if (s->has_window && s->t_lo > s->t_hi) return "BUCKET: the timestamp window is empty (t_lo > t_hi)";
-    return nullptr;
-}
-
-struct TimePlan {
-    int64_t lo = 0, hi = -1;  // [tmin, tmax] intersected with the window (lo > hi: nothing)
-    int64_t first = 0;        // bucket(lo)
-    uint32_t nbuckets = 0;
-    std::string why;
-};
-// time_plan of timeseries.hip: the same arithmetic, the same two refusals, the same texts.
-int time_plan(const aqe_time_spec* s, int64_t tmin, int64_t tmax, TimePlan* out) {
-    *out = TimePlan{};
-    if (const char* d = spec_defect(s)) { out->why = d; return AQE_ERR_INVALID; }
-    if (tmin > tmax) return AQE_OK;  // an empty table
-    const i128 span = static_cast<i128>(tmax) - tmin;
-    if (span > kMaxTimeSpan) {
-        out->why = "BUCKET: the table's timestamps span " + std::to_string(static_cast<unsigned long long>(span)) + " (tmax - tmin = " + std::to_string(tmax) + " - " +
-                   std::to_string(tmin) + "), 2^31 or more: the time column is kept as int32 offsets";
-        return AQE_ERR_UNSUPPORTED;
-    }
-    int64_t lo = tmin, hi = tmax;
-    if (s->has_window) {
-        lo = std::max(lo, s->t_lo);
-        hi = std::min(hi, s->t_hi);
-    }
-    out->lo = lo;
-    out->hi = hi;
-    if (lo > hi) return AQE_OK;  // the window leaves nothing
-    const i128 b0 = floor_div(static_cast<i128>(lo) - s->origin, s->width), b1 = floor_div(static_cast<i128>(hi) - s->origin, s->width);
-    const i128 count = b1 - b0 + 1;  // <= 2^31: the span is below 2^31 and the width at least 1
-    out->first = saturate(b0);
-    out->nbuckets = static_cast<uint32_t>(count);
-    if (count > kMaxGroupBins) {
-        out->why = "BUCKET: " + std::to_string(static_cast<long long>(count)) + " buckets of width " + std::to_string(s->width) + " over timestamps " + std::to_string(lo) +
-                   " .. " + std::to_string(hi) + ", more than 1024: take a wider bucket or a narrower window";
-        return AQE_ERR_UNSUPPORTED;
-    }
-    return AQE_OK;
-}
-
-inline int64_t bucket_start(const aqe_time_spec* s, int64_t first, uint32_t b) {
-    return saturate(static_cast<i128>(s->origin) + (static_cast<i128>(first) + b) * s->width);
-}
+static_assert(kMaxTimeBuckets == kMaxGroupBins, "time_plan's refusal is the LDS bins' bound");
 
 const char* column_name(int column) { return column == AQE_GROUP_REGION ? "region" : "product_id"; }
 
@@ -537,28 +472,8 @@ int enqueue_bins(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, int column, c
     }
     if (c->key_min[column - 1] < sp.key_min || static_cast<int64_t>(c->key_max[column - 1]) - sp.key_min >= static_cast<int64_t>(sp.span))
         return fail(c, AQE_ERR_INVALID, "this shard has keys outside [key_min, key_min + span)");
-    // the buckets relative to this shard's offsets u = timestamp - time_min (enqueue_bins of timeseries.hip)
-    const i128 tmin_s = c->time_min, rel = tmin_s - spec->origin;
-    const i128 q0 = floor_div(rel, spec->width), r0 = rel - q0 * spec->width;  // 0 <= r0 < width
-    a.ulo = static_cast<uint32_t>(std::max<i128>(static_cast<i128>(tp.lo) - tmin_s, 0));
-    a.uhi = static_cast<uint32_t>(std::min<i128>(static_cast<i128>(tp.hi) - tmin_s, static_cast<i128>(c->time_max) - tmin_s));
-    a.bin0 = static_cast<int32_t>(q0 - tp.first);  // |bucket(time_min) - bucket(lo)| < 2^31: both lie in one table's range
-    const i128 two31 = static_cast<i128>(1) << 31;
-    if (spec->width <= two31) {
-        a.div = static_cast<uint32_t>(spec->width);
-        a.add = static_cast<uint32_t>(r0);
-    } else {  // at most one bucket edge inside the offsets, at u = width - r0: the same form with d = 2^31
-        const i128 edge = static_cast<i128>(spec->width) - r0;
-        a.div = static_cast<uint32_t>(two31);
-        a.add = edge <= kMaxTimeSpan ? static_cast<uint32_t>(two31 - edge) : 0u;
-    }
-    if (a.div >= 2u) {
-        const unsigned __int128 one64 = static_cast<unsigned __int128>(1) << 64;
-        unsigned __int128 m = one64 / a.div;
-        if (m * a.div != one64) ++m;
-        a.m_hi = static_cast<uint32_t>(static_cast<uint64_t>(m) >> 32);
-        a.m_lo = static_cast<uint32_t>(static_cast<uint64_t>(m));
-    }
+    const BucketConsts k = bucket_consts(spec, tp, c->time_min, c->time_max);  // relative to this shard's offsets u = timestamp - time_min
+    a.ulo = k.ulo; a.uhi = k.uhi; a.add = k.add; a.div = k.div; a.m_hi = k.m_hi; a.m_lo = k.m_lo; a.bin0 = k.bin0;
     a.nbuckets = tp.nbuckets;
     a.key_min = sp.key_min;
     a.span = sp.span;

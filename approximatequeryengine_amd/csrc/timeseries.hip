@@ -32,15 +32,16 @@
 #include "host.hpp"
 #include "key_term.hpp"
 #include "sweep_host.hpp"
+#include "time_bucket_core.hpp"
 
 namespace aqe {
 namespace {
 
 constexpr unsigned kNoBucket = 0xffffffffu;
 constexpr unsigned kTimeBin = 4;  // {n, P1, P2, visited}: aqe_grouped_enqueue_bins' layout
-constexpr int64_t kMaxTimeSpan = (1ll << 31) - 1;
 static_assert(sizeof(aqe_time_spec) == 40, "layout of include/aqe_hip.h");
 static_assert(kMaxGroupBins * kTimeBin * 8 <= 32 * 1024, "the bins of the widest bucket range fit a launch's LDS");
+static_assert(kMaxTimeBuckets == kMaxGroupBins, "time_plan's refusal is the LDS bins' bound");
 
 struct TimeLaunch {
     SweepCommon sw;
@@ -57,12 +58,6 @@ struct TimeLaunch {
     DevFilter flt;           // t[0] / map[0]: the key term (NK == 2)
 };
 static_assert(sizeof(TimeLaunch) <= 4096, "kernel arguments are limited to 4 KB");
-
-// floor(n / d) for d >= 2 from M = ceil(2^64 / d) = m_hi 2^32 + m_lo: the top word of the 96-bit product n M.
-__host__ __device__ __forceinline__ unsigned div_magic(unsigned n, unsigned m_hi, unsigned m_lo) {
-    const u64 low = static_cast<u64>(n) * m_lo;
-    return static_cast<unsigned>((static_cast<u64>(n) * m_hi + (low >> 32)) >> 32);
-}
 
 // Estimate and interval of one bucket from its sums: group_result of grouped.hip (executor.cpp:277-296), restated here
 // because that one lives in its translation unit.
@@ -270,66 +265,6 @@ inline unsigned blocks_for(u64 work, u64 per_block, unsigned cap) {
     return static_cast<unsigned>(g > cap ? cap : g);
 }
 
-typedef __int128 i128;
-
-inline i128 floor_div(i128 a, i128 b) {  // b > 0
-    i128 q = a / b;
-    if (a % b != 0 && a < 0) --q;
-    return q;
-}
-inline int64_t saturate(i128 v) {
-    const i128 lo = std::numeric_limits<int64_t>::min(), hi = std::numeric_limits<int64_t>::max();
-    return static_cast<int64_t>(v < lo ? lo : v > hi ? hi : v);
-}
-
-const char* spec_defect(const aqe_time_spec* s) {
-    if (!s) return "null time spec";
-    if (s->width < 1) return "BUCKET: the width must be at least 1";
-    if (s->has_window && s->t_lo > s->t_hi) return "BUCKET: the timestamp window is empty (t_lo > t_hi)";
-    return nullptr;
-}
-
-// The buckets of [tmin, tmax] under the spec; what aqe_time_plan returns, and the message of its refusals.
-struct TimePlan {
-    int64_t lo = 0, hi = -1;  // [tmin, tmax] intersected with the window (lo > hi: nothing)
-    int64_t first = 0;        // bucket(lo)
-    uint32_t nbuckets = 0;
-    std::string why;
-};
-int time_plan(const aqe_time_spec* s, int64_t tmin, int64_t tmax, TimePlan* out) {
-    *out = TimePlan{};
-    if (const char* d = spec_defect(s)) { out->why = d; return AQE_ERR_INVALID; }
-    if (tmin > tmax) return AQE_OK;  // an empty table
-    const i128 span = static_cast<i128>(tmax) - tmin;
-    if (span > kMaxTimeSpan) {
-        out->why = "BUCKET: the table's timestamps span " + std::to_string(static_cast<unsigned long long>(span)) + " (tmax - tmin = " + std::to_string(tmax) + " - " +
-                   std::to_string(tmin) + "), 2^31 or more: the time column is kept as int32 offsets";
-        return AQE_ERR_UNSUPPORTED;
-    }
-    int64_t lo = tmin, hi = tmax;
-    if (s->has_window) {
-        lo = std::max(lo, s->t_lo);
-        hi = std::min(hi, s->t_hi);
-    }
-    out->lo = lo;
-    out->hi = hi;
-    if (lo > hi) return AQE_OK;  // the window leaves nothing
-    const i128 b0 = floor_div(static_cast<i128>(lo) - s->origin, s->width), b1 = floor_div(static_cast<i128>(hi) - s->origin, s->width);
-    const i128 count = b1 - b0 + 1;  // <= 2^31: the span is below 2^31 and the width at least 1
-    out->first = saturate(b0);
-    out->nbuckets = static_cast<uint32_t>(count);
-    if (count > kMaxGroupBins) {
-        out->why = "BUCKET: " + std::to_string(static_cast<long long>(count)) + " buckets of width " + std::to_string(s->width) + " over timestamps " + std::to_string(lo) +
-                   " .. " + std::to_string(hi) + ", more than 1024: take a wider bucket or a narrower window";
-        return AQE_ERR_UNSUPPORTED;
-    }
-    return AQE_OK;
-}
-
-inline int64_t bucket_start(const aqe_time_spec* s, int64_t first, uint32_t b) {
-    return saturate(static_cast<i128>(s->origin) + (static_cast<i128>(first) + b) * s->width);
-}
-
 // ---- the timestamp terms of a WHERE clause --------------------------------------------------------------------------------------
 
 struct TimeTok {
@@ -525,19 +460,6 @@ int ensure_scratch(aqe_ctx* c) {
     });
 }
 
-// The one key column a filter may carry a term on (0: none); terms on both are refused.
-int term_column(aqe_ctx* c, const aqe_key_filter* f, int* column) {
-    *column = 0;
-    if (!f) return AQE_OK;
-    const int rc = check_filter(c, f);
-    if (rc != AQE_OK) return rc;
-    const bool r = f->term[0].form != AQE_KEYTERM_NONE, p = f->term[1].form != AQE_KEYTERM_NONE;
-    if (r && p)
-        return fail(c, AQE_ERR_UNSUPPORTED, "time buckets take a key predicate on ONE key column (region or product_id), not on both: the sweep has one key slot beside the time column");
-    *column = r ? AQE_GROUP_REGION : p ? AQE_GROUP_PRODUCT : 0;
-    return AQE_OK;
-}
-
 template <bool NT, bool WAVE>
 void launch_as(int nk, dim3 g, size_t lds, hipStream_t s, const TimeLaunch& a) {
     if (nk == 1) hipLaunchKernelGGL((k_time_buckets<NT, 1, WAVE>), g, dim3(kBlockThreads), lds, s, a);
@@ -586,28 +508,8 @@ int enqueue_bins(aqe_ctx* c, aqe_plan* p, const aqe_key_filter* f, int column, c
         }
         return AQE_OK;
     }
-    // everything relative to this shard's offsets u = timestamp - time_min
-    const i128 tmin_s = c->time_min, rel = tmin_s - spec->origin;
-    const i128 q0 = floor_div(rel, spec->width), r0 = rel - q0 * spec->width;  // 0 <= r0 < width
-    a.ulo = static_cast<uint32_t>(std::max<i128>(static_cast<i128>(tp.lo) - tmin_s, 0));
-    a.uhi = static_cast<uint32_t>(std::min<i128>(static_cast<i128>(tp.hi) - tmin_s, static_cast<i128>(c->time_max) - tmin_s));
-    a.bin0 = static_cast<int32_t>(q0 - tp.first);  // |bucket(time_min) - bucket(lo)| < 2^31: both lie in one table's range
-    const i128 two31 = static_cast<i128>(1) << 31;
-    if (spec->width <= two31) {
-        a.div = static_cast<uint32_t>(spec->width);
-        a.add = static_cast<uint32_t>(r0);
-    } else {  // at most one bucket edge inside the offsets, at u = width - r0: the same form with d = 2^31
-        const i128 edge = static_cast<i128>(spec->width) - r0;
-        a.div = static_cast<uint32_t>(two31);
-        a.add = edge <= kMaxTimeSpan ? static_cast<uint32_t>(two31 - edge) : 0u;
-    }
-    if (a.div >= 2u) {
-        const unsigned __int128 one64 = static_cast<unsigned __int128>(1) << 64;
-        unsigned __int128 m = one64 / a.div;
-        if (m * a.div != one64) ++m;
-        a.m_hi = static_cast<uint32_t>(static_cast<uint64_t>(m) >> 32);
-        a.m_lo = static_cast<uint32_t>(static_cast<uint64_t>(m));
-    }
+    const BucketConsts k = bucket_consts(spec, tp, c->time_min, c->time_max);  // relative to this shard's offsets u = timestamp - time_min
+    a.ulo = k.ulo; a.uhi = k.uhi; a.add = k.add; a.div = k.div; a.m_hi = k.m_hi; a.m_lo = k.m_lo; a.bin0 = k.bin0;
     a.nbins = nb;
     // the columns: the time offsets in key slot 0, the key column under the term in slot 1
     int nk = 1;

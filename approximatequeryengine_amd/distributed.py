@@ -703,6 +703,47 @@ def sharded_time_series(engine, query, spec, bins, all_reduce_sum: Callable, all
         return engine.time_buckets_finish(query, spec, tmin, tmax, b.data_ptr(), stream)
 
 
+def sharded_quantile_series(engine, query, spec, probs, interpolation: int, vec, all_reduce_sum: Callable, all_reduce_max: Callable, rank: int, world: int,
+                            stream: int = 0, key_filter=None):
+    """MEDIAN / PERCENTILE per time bucket across the ranks of a process group (engine.Engine interface), collective: every rank
+    gets the same answer.  The table's timestamp range is agreed in ONE all-reduce MAX (``_agree_int64``, as sharded_time_series),
+    so every rank derives the same buckets on the host (engine.time_plan, with its two refusals, before the sweep); every rank
+    collects the (amount, bucket) pairs of the part of the sample inside its shard and the window
+    (aqe_time_quantiles_enqueue_collect: a shard the window misses collects nothing); then sharded_quantile_groups' two SUM
+    all-reduces — the pair counts and visited per bucket, then the union — and the grouped form's place and finish with key_min 0
+    and nbins = nbuckets.  Returns a list over the listed buckets, ascending by start, of lists of TimeQuantileResult.
+
+    vec     float64 tensor on the engine's device with room for world + nbuckets doubles (at most world + 1024)
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    import torch
+    from ._native import ERR_INVALID, ERR_UNSUPPORTED, GQUANTILE_MAX_ROWS, AqeError, TimeQuantileResult
+    from .engine import time_plan
+    rank, world = int(rank), int(world)
+    with _on_stream(stream, vec) as stream:
+        (tmin, tmax), = _agree_int64([engine.time_range()], vec, all_reduce_max)
+        first, nbuckets = time_plan(spec, tmin, tmax)
+        if nbuckets == 0:  # an empty table, or a window that holds none of its timestamps
+            raise AqeError(ERR_INVALID, "No samples collected")
+        head = _take(vec, world + nbuckets, vector=True)
+        head.zero_()
+        engine.time_quantiles_enqueue_collect(query, spec, tmin, tmax, head[rank:].data_ptr(), head[world:].data_ptr(), stream, key_filter)
+        all_reduce_sum(head)
+        counts = [int(v) for v in head[:world].tolist()]
+        total, offset = sum(counts), sum(counts[:rank])
+        if total > GQUANTILE_MAX_ROWS:
+            raise AqeError(ERR_UNSUPPORTED, f"MEDIAN / PERCENTILE per time bucket: the sample holds {total} rows over all ranks, more than {GQUANTILE_MAX_ROWS}")
+        union = torch.zeros(max(2 * total, 1), dtype=torch.float64, device=vec.device)
+        engine.grouped_quantile_enqueue_place(union.data_ptr(), total, offset, stream)
+        if total:
+            all_reduce_sum(union[: 2 * total])
+        groups = engine.grouped_quantile_finish(query, 0, nbuckets, union.data_ptr(), total, head[world:].data_ptr(), probs, interpolation, stream)
+    out = []
+    for entries in groups:  # an entry's key is its bucket's bin: the start follows from the plan's first bucket
+        start = min(max(int(spec.origin) + (first + int(entries[0].key)) * int(spec.width), -2 ** 63), 2 ** 63 - 1)
+        out.append([TimeQuantileResult(start, *[getattr(e, f) for f, _ in type(e)._fields_]) for e in entries])
+    return out
+
+
 def sharded_time_groups(engine, query, group_column, spec, bins, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None,
                         max_groups: int = 65536):
     """SUM / AVG / COUNT per cell (key of ``group_column``, time bucket) across the ranks of a process group (engine.Engine

@@ -509,6 +509,26 @@ class Engine:
                                                         C.byref(n)))
         return _by_group(out, n.value, len(ps))
 
+    # -- MEDIAN / PERCENTILE per time bucket (aqe_reduce_time_quantiles and its sharded collect): the grouped form, the bin a bucket --
+    def time_quantiles(self, query: Query, spec: "nat.TimeSpec", probs: Sequence[float], interpolation: int = nat.QUANTILE_LINEAR,
+                       key_filter: Optional["nat.KeyFilter"] = None, max_buckets: int = nat.TIME_MAX_BUCKETS):
+        """Order statistics of the sampled amounts per time bucket of ``spec``: a list over the buckets with a qualifying sampled row
+        inside the window, ascending by start, of lists of TimeQuantileResult, one per probability."""
+        ps = _probs(probs)
+        arr = (C.c_double * len(ps))(*ps)
+        out = (nat.TimeQuantileResult * (max(int(max_buckets), 1) * len(ps)))()
+        n = C.c_uint32()
+        self._chk(nat.lib().aqe_reduce_time_quantiles(self._h, _filter_ref(key_filter), C.byref(query), C.byref(spec), arr, len(ps), int(interpolation), out,
+                                                      int(max_buckets), C.byref(n)))
+        return _by_group(out, n.value, len(ps))
+
+    def time_quantiles_enqueue_collect(self, query: Query, spec: "nat.TimeSpec", tmin: int, tmax: int, dev_count_ptr: int, dev_visited_ptr: int,
+                                       stream: int = 0, key_filter: Optional["nat.KeyFilter"] = None):
+        """grouped_quantile_enqueue_collect with the bins the buckets of time_plan(spec, tmin, tmax) over the agreed range: then the
+        grouped form's place and finish with key_min 0 and nbins = nbuckets."""
+        self._chk(nat.lib().aqe_time_quantiles_enqueue_collect(self._h, _filter_ref(key_filter), C.byref(query), C.byref(spec), int(tmin), int(tmax),
+                                                               C.c_void_p(dev_count_ptr), C.c_void_p(dev_visited_ptr), C.c_void_p(stream)))
+
     # -- spread: VARIANCE / STDDEV (aqe_reduce_spread, its additive multi-GPU split, the GROUP BY form) --
     def reduce_spread(self, query: Query, kind: int = nat.SPREAD_VAR_SAMP) -> "nat.SpreadResult":
         """Variance / standard deviation of the sampled amounts with the fourth-moment interval (include/aqe_hip.h)."""
@@ -1551,6 +1571,21 @@ def gquantile_from_sorted(sorted_amounts, probs, interpolation: int = nat.QUANTI
                                              float(confidence_level), int(key), int(visited), out)
     if rc != nat.OK:
         raise nat.AqeError(rc, "MEDIAN / PERCENTILE by group: a group of no rows, a probability outside [0, 1] or an unknown interpolation")
+    return list(out)
+
+
+def time_quantiles_from_sorted(sorted_amounts, probs, spec: "nat.TimeSpec", first_bucket: int, bin: int, interpolation: int = nat.QUANTILE_LINEAR,
+                               exact: bool = False, confidence_level: float = 0.95, visited: int = 0) -> list:
+    """aqe_time_quantiles_from_sorted: one bucket's TimeQuantileResult per probability from its amounts sorted ascending, on the host;
+    ``bin`` counts from ``first_bucket`` (time_plan)."""
+    x = np.ascontiguousarray(sorted_amounts, dtype=np.float64)
+    ps = _probs(probs)
+    arr = (C.c_double * len(ps))(*ps)
+    out = (nat.TimeQuantileResult * len(ps))()
+    rc = nat.lib().aqe_time_quantiles_from_sorted(x.ctypes.data_as(C.POINTER(C.c_double)), len(x), arr, len(ps), int(interpolation), int(bool(exact)),
+                                                  float(confidence_level), C.byref(spec), int(first_bucket), int(bin), int(visited), out)
+    if rc != nat.OK:
+        raise nat.AqeError(rc, "MEDIAN / PERCENTILE per time bucket: a bucket of no rows, a probability outside [0, 1], an unknown interpolation or a malformed spec")
     return list(out)
 
 

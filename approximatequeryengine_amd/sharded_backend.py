@@ -31,7 +31,7 @@ from .aqe_backend import ApproxResult, CustomBPlusDB
 from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, mailbox_all_reduce, mailbox_from_torch_group, shard_bounds, sharded_adaptive_plan,
                           sharded_distinct, sharded_distinct_groups, sharded_extremes, sharded_filtered, sharded_filtered_group_by, sharded_group_by, sharded_group_by_budget, sharded_group_by_error,
                           sharded_group_by_having, sharded_group_by_pair, sharded_group_by_spread, sharded_group_by_top, sharded_group_by_wide, sharded_group_by_window,
-                          sharded_group_extremes, sharded_histogram, sharded_quantile_groups, sharded_quantiles, sharded_spread, sharded_stratified_plan, sharded_summary,
+                          sharded_group_extremes, sharded_histogram, sharded_quantile_groups, sharded_quantile_series, sharded_quantiles, sharded_spread, sharded_stratified_plan, sharded_summary,
                           sharded_time_groups, sharded_time_series, sharded_windowed, torch_all_reduce, torch_host_all_reduce)
 from .engine import RECORD_DTYPE, Batch, Engine
 
@@ -340,6 +340,10 @@ class ShardedBPlusDB(CustomBPlusDB):
     # MEDIAN / PERCENTILE per group: one all-reduce MAX of the key range, one SUM of the pair counts and visited, one SUM of the union
     def _quantile_groups(self, f, q, by, probs, interp):
         return self._sharded(sharded_quantile_groups, self._world + nat.GQUANTILE_MAX_GROUPS, q, by, probs, interp, rank=self._rank, world=self._world, key_filter=f)
+
+    # MEDIAN / PERCENTILE per time bucket: one all-reduce MAX of the timestamp range, then the grouped form's two SUMs
+    def _quantile_series(self, f, q, spec, probs, interp):
+        return self._sharded(sharded_quantile_series, self._world + nat.TIME_MAX_BUCKETS, q, spec, probs, interp, rank=self._rank, world=self._world, key_filter=f)
 
     # SUMMARY: one all-reduce SUM of the power sums and counts, one all-reduce MAX of {-min, max}
     def _summary(self, f, q):

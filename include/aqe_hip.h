@@ -1381,6 +1381,66 @@ AQE_API int aqe_time_buckets_enqueue_bins(aqe_ctx* ctx, const aqe_key_filter* fi
 AQE_API int aqe_time_buckets_finish(aqe_ctx* ctx, const aqe_query* q, const aqe_time_spec* spec, int64_t tmin, int64_t tmax, const double* dev_bins,
                                     void* stream, aqe_group_result* out, uint32_t cap, uint32_t* n_groups);
 
+/* ---- quantiles per time bucket: MEDIAN / PERCENTILE over BUCKET(timestamp, W) — collect, sort, select (group_quantile.hip) --------
+ * The grouped quantile form with a time bucket as the bin.  `spec` is an aqe_time_spec of §time buckets: bucket(ts) =
+ * floor((ts - origin) / width), the buckets those of aqe_time_plan over the table's timestamp range intersected with the window,
+ * the same two refusals (more than 1024 buckets, by count; a span of 2^31 or more, by span).
+ * Rows — the bucketed forms' rule.  A sampled row outside the window is in no bucket: it counts in neither n nor visited.  A row
+ * inside the window counts in its bucket's `visited`; it also counts in `n`, and its amount belongs to X_b, when it passes the
+ * inclusive amount WHERE range and the key term and is no NaN.  `filter` (NULL: none) may carry a term on ONE key column; terms
+ * on both are AQE_ERR_UNSUPPORTED.  Per probability and bucket the entry is what aqe_reduce_grouped_quantiles reports for a group
+ * with these rows: numpy.quantile(X_b, p, method=M) to the bit, ranks, the distribution-free interval ([value, value] for
+ * AQE_M_EXACT).  Buckets are listed ascending by start, n_probs entries per bucket; only buckets with n >= 1 are listed; none
+ * listed is AQE_ERR_INVALID "No samples collected".
+ * How.  k_tq_collect is k_gq_collect's collecting sweep — per-wave LDS staging, one returning atomic per wave per tile,
+ * contiguous copy-out, never a store past the capacity given (AQE_ERR_INTERNAL on a raised status word) — with the time offsets
+ * in key slot 0 and the bucket by an exact multiply-high division.  On time-ordered rows a wave holds one bucket: one lane adds
+ * the wave's two popcounts to the LDS counters (AQE_TQ_WAVE=0, read per launch, turns that step off; the counts are the same).
+ * Under a window, on the tile source, the zone map of §time windows is probed one tile ahead and a tile that cannot meet the
+ * window is skipped with no load (AQE_ZONE_SKIP=0 reads every tile); aqe_last_window_tiles reports {tiles, skipped} of the
+ * launch.  The sorts, the selection and the sharded place / union / finish are the grouped form's, unchanged.
+ * Limits, each refused by name with the offending number before any launch: more than 1024 buckets, a span of 2^31 or more,
+ * more than AQE_GQUANTILE_MAX_ROWS sampled rows (the environment override holds), n_probs outside 1 .. AQE_MAX_QUANTILES, terms
+ * on both key columns, the samplers the grouped quantile form refuses.  No error-threshold form, no buckets x key column.
+ * AQE_NT=0/1 picks the load flavour, which aqe_last_load_policy reports. */
+typedef struct aqe_time_quantile_result {
+    int64_t start;                 /* the bucket's start: origin + (first_bucket + key) * width */
+    int32_t key;                   /* the bucket's bin: its number counted from the plan's first bucket */
+    int32_t reserved;
+    double p;
+    double value;
+    double ci_lower, ci_upper;
+    uint64_t n;
+    uint64_t visited;
+    uint64_t rank_lo, rank_hi;     /* 1-based, within the bucket */
+    uint64_t ci_rank_lo, ci_rank_hi;
+    int32_t device_status;         /* 0 ok */
+    int32_t reserved2;
+    double kernel_ms;              /* aqe_reduce_time_quantiles: device time of the call */
+} aqe_time_quantile_result;
+#ifdef __cplusplus
+static_assert(sizeof(aqe_time_quantile_result) == sizeof(aqe_group_quantile_result) + 8, "a start, then the fields of aqe_group_quantile_result");
+#endif
+/* Single GPU, synchronous.  out: room for cap_buckets x n_probs entries; *n_buckets: the buckets listed (more than cap_buckets:
+ * AQE_ERR_INVALID with the number, *n_buckets set, no partial list).  aqe_last_grouped_quantile_times then holds this call's
+ * [collect, sorts, select]. */
+AQE_API int aqe_reduce_time_quantiles(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const aqe_time_spec* spec, const double* probs,
+                                      uint32_t n_probs, int interpolation, aqe_time_quantile_result* out, uint32_t cap_buckets, uint32_t* n_buckets);
+/* Host only, no GPU and no context: one bucket's entries from its amounts sorted ascending, as aqe_gquantile_from_sorted, with
+ * the start of bin `bin` of a plan whose first bucket is first_bucket. */
+AQE_API int aqe_time_quantiles_from_sorted(const double* sorted, uint64_t n, const double* probs, uint32_t n_probs, int interpolation, int exact,
+                                           double confidence_level, const aqe_time_spec* spec, int64_t first_bucket, uint32_t bin, uint64_t visited,
+                                           aqe_time_quantile_result* out);
+/* Multi-GPU.  The ranks agree on the timestamp range (aqe_time_range, all-reduced MIN / MAX), so aqe_time_plan(spec, tmin, tmax)
+ * gives the same first bucket and nbuckets on every rank; then
+ *     aqe_time_quantiles_enqueue_collect(ctx, filter, q, spec, tmin, tmax, dev_count, dev_visited, stream)
+ *         as aqe_grouped_quantile_enqueue_collect with nbins = nbuckets: a shard with timestamps outside [tmin, tmax] is
+ *         AQE_ERR_INVALID; a shard that does not meet the window collects nothing and publishes zeros
+ *     the SUM all-reduce, aqe_grouped_quantile_enqueue_place, the SUM all-reduce of the union and aqe_grouped_quantile_finish with
+ *         key_min 0 and nbins = nbuckets, unchanged; the caller turns an entry's key b into origin + (first + b) * width. */
+AQE_API int aqe_time_quantiles_enqueue_collect(aqe_ctx* ctx, const aqe_key_filter* filter, const aqe_query* q, const aqe_time_spec* spec, int64_t tmin,
+                                               int64_t tmax, double* dev_count, double* dev_visited, void* stream);
+
 /* ---- GROUP BY over wide key ranges: up to 65 536 groups, sliced sweep (wide_group.hip) --------------------------------------
  * aqe_reduce_grouped and aqe_reduce_grouped_pair bin into one workgroup's LDS and stop at 1024 bins; they keep that bound and
  * their refusals.  These entries answer SUM / AVG / COUNT per group — per group the estimate and interval of
