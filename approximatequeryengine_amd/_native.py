@@ -58,6 +58,7 @@ QUANTILE_LINEAR, QUANTILE_INVERTED_CDF = 0, 1
 QUANTILE_VEC_SUM, QUANTILE_VEC_MAX = 8194, 64
 SPREAD_VAR_SAMP, SPREAD_VAR_POP, SPREAD_STDDEV_SAMP, SPREAD_STDDEV_POP = 0, 1, 2, 3
 SPREAD_VEC, SPREAD_BIN = 8, 6
+TREND_VEC = 16  # {n, su, su2, su3, su4, visited, sd, n c, sd2, sud, su2d, su3d, sud2, su2d2, 0, 0}: one SUM all-reduce
 EXTREME_VEC = 4  # {n, visited} for a SUM all-reduce, then {-min, max} for a MAX all-reduce
 HISTOGRAM_MAX_BINS = 4096
 HISTOGRAM_VEC_HEAD = 4  # [visited, n, below, above], then count[0 .. bins): one SUM all-reduce
@@ -203,6 +204,17 @@ class SpreadResult(C.Structure):
     _fields_ = [("value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double), ("mean", C.c_double), ("m2", C.c_double),
                 ("m3", C.c_double), ("m4", C.c_double), ("n", C.c_uint64), ("visited", C.c_uint64), ("has_interval", C.c_int32),
                 ("device_status", C.c_int32), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class TrendResult(C.Structure):
+    """aqe_trend_result: TREND(amount), the slope and the correlation of amount over timestamp."""
+    _fields_ = [("slope", C.c_double), ("slope_lo", C.c_double), ("slope_hi", C.c_double), ("intercept", C.c_double), ("mean_time", C.c_double),
+                ("mean_amount", C.c_double), ("r", C.c_double), ("r2", C.c_double), ("r_lo", C.c_double), ("r_hi", C.c_double), ("n", C.c_uint64),
+                ("visited", C.c_uint64), ("has_slope", C.c_int32), ("has_interval", C.c_int32), ("has_r_interval", C.c_int32), ("settled", C.c_int32),
+                ("device_status", C.c_int32), ("reserved", C.c_int32), ("kernel_ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -480,6 +492,11 @@ def lib() -> C.CDLL:
         "aqe_time_window_offsets": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, P(C.c_int32), P(C.c_int32)]),
         "aqe_reduce_window_groups": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, C.c_int64, C.c_int64, P(GroupResult), u32, P(u32)]),
         "aqe_window_groups_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, C.c_int64, C.c_int64, i32, u32, vp, vp]),
+        "aqe_trend_frame": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, P(dbl), P(dbl)]),
+        "aqe_trend_from_vec": (C.c_int, [P(dbl), dbl, dbl, dbl, dbl, dbl, C.c_int, P(TrendResult)]),
+        "aqe_reduce_trend": (C.c_int, [vp, P(Query), P(KeyFilter), C.c_int, C.c_int64, C.c_int64, dbl, P(TrendResult)]),
+        "aqe_trend_enqueue": (C.c_int, [vp, P(Query), P(KeyFilter), C.c_int, C.c_int64, C.c_int64, dbl, dbl, vp, vp]),
+        "aqe_trend_finish": (C.c_int, [vp, P(Query), vp, vp, dbl, dbl, dbl, P(TrendResult)]),
         "aqe_reduce_grouped_pair": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), P(GroupResult), u32, P(u32)]),
         "aqe_reduce_grouped_pair_spread": (C.c_int, [vp, P(KeyFilter), P(Query), C.c_int, P(C.c_int), P(SpreadGroupResult), u32, P(u32)]),
         "aqe_grouped_pair_enqueue_bins": (C.c_int, [vp, P(KeyFilter), P(Query), P(C.c_int), P(i32), P(u32), vp, vp]),

@@ -21,6 +21,7 @@ reference builds from ascending inserts).
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import enum
 import math
 import os
@@ -34,7 +35,7 @@ from . import _native as nat
 from .engine import RECORD_DTYPE, Engine, histogram_spec, key_filter_terms, make_budget_filter, make_key_filter, make_query, time_spec, time_window, wide_plan
 
 __all__ = ["Record", "CustomBPlusDB", "CustomApproximateScheduler", "CustomValidationResult",
-           "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate", "SpreadEstimate", "SummaryEstimate", "BucketEstimate", "BudgetGroupEstimate"]
+           "CustomApproximationStatus", "ApproxResult", "BenchmarkResults", "GroupEstimate", "QuantileEstimate", "SpreadEstimate", "SummaryEstimate", "TrendEstimate", "BucketEstimate", "BudgetGroupEstimate"]
 
 
 class Record:
@@ -210,6 +211,43 @@ class SpreadEstimate:
 
     def __iter__(self):  # unpacks like a GroupEstimate: (value, ci_lower, ci_upper)
         return iter((self.value, self.ci_lower, self.ci_upper))
+
+
+@dataclasses.dataclass(frozen=True)
+class TrendEstimate:
+    """Result of approx_trend: the least-squares slope of amount over timestamp among the sampled rows that pass, in amount per
+    ``per`` timestamp units, with the linearisation (sandwich) interval of that slope under sampling; the correlation ``r`` with
+    Fisher's normal-theory interval; the means (include/aqe_hip.h, aqe_trend_result).  ``has_slope`` is False for fewer than two
+    rows or one distinct timestamp (NaN figures); ``has_interval`` needs n >= 3, ``has_r_interval`` n >= 4.  ``settled``: the
+    slope interval excludes 0.  ``intercept`` loses digits for epoch-sized timestamps that the slope keeps: use ``predict``."""
+    slope: float
+    slope_lo: float
+    slope_hi: float
+    intercept: float
+    mean_time: float
+    mean_amount: float
+    r: float
+    r2: float
+    r_lo: float
+    r_hi: float
+    n: int
+    visited: int
+    has_slope: bool
+    has_interval: bool
+    has_r_interval: bool
+    settled: bool
+    per: float
+    kernel_ms: float
+    method: str
+
+    @classmethod
+    def from_result(cls, r, per: float, method: str) -> "TrendEstimate":
+        return cls(r.slope, r.slope_lo, r.slope_hi, r.intercept, r.mean_time, r.mean_amount, r.r, r.r2, r.r_lo, r.r_hi, int(r.n), int(r.visited),
+                   bool(r.has_slope), bool(r.has_interval), bool(r.has_r_interval), bool(r.settled), float(per), getattr(r, "kernel_ms", 0.0), method)
+
+    def predict(self, t) -> float:
+        """The fitted amount at timestamp ``t``: mean_amount + slope / per * (t - mean_time)."""
+        return self.mean_amount + self.slope / self.per * (t - self.mean_time)
 
 
 class ExtremeEstimate:
@@ -1412,6 +1450,40 @@ class CustomBPlusDB:
 
     def _spread(self, q, kind):
         return self._eng().reduce_spread(q, kind)
+
+    def approx_trend(self, method: str = "stride", sample_percent: float = 10.0, where: Optional[Tuple[float, float]] = None,
+                     key_where: Optional[dict] = None, time_between: Optional[Tuple[int, int]] = None, per: float = 1.0,
+                     confidence_level: float = 0.95, seed: int = 42, id_between: Optional[Tuple[int, int]] = None, num_threads: int = 4,
+                     block_size: int = 1000) -> "TrendEstimate":
+        """APPROX TREND(amount): how amount moves with timestamp among the sampled rows that pass ``where`` (inclusive amount
+        range), ``key_where`` (a term on ONE of region / product_id) and ``time_between`` = (t_lo, t_hi), NaN amounts left out —
+        the least-squares slope in amount per ``per`` timestamp units (86400: per day of a table in seconds) with the
+        sandwich interval of the table's own slope under sampling, the correlation with Fisher's normal-theory interval, and
+        the means, from ONE sweep (aqe_reduce_trend).  ``visited`` counts every sampled row, ``n`` those that pass; nothing is
+        scaled by the sampling fraction.  method as approx_spread ("exact", "stride", "block", "page", "parallel_block",
+        "region", "random" ...; "exact" collapses the intervals onto the values); the CLT, adaptive, stratified and
+        random_device samplers, key terms on both columns, an empty window, ``per`` not positive and finite and a table whose
+        timestamps span 2^31 or more raise ValueError.  A sample with one distinct timestamp has no slope (has_slope False)."""
+        per = float(per)
+        if not (per > 0.0 and per < math.inf):
+            raise ValueError(f"per must be positive and finite, got {per!r}")
+        if method in _NO_KEY_WHERE:
+            raise ValueError(f"TREND does not take the {method} sampler (single-round family samplers and 'random' only)")
+        if method == "rowid":
+            raise ValueError("TREND takes approx()'s samplers, not 'rowid'")
+        window = None if time_between is None else time_window(time_between)
+        f = None
+        if key_where is not None:
+            if sum(1 for c in ("region", "product_id") if key_where.get(c) is not None) > 1:
+                raise ValueError("TREND takes a key predicate on region or on product_id, not on both: the time offsets take one of the "
+                                 "sweep's two key slots")
+            f = make_key_filter(key_where)
+        q = self._approx_query("SUM", method, sample_percent, None, where, seed, num_threads, block_size, confidence_level, id_between=id_between)
+        q.confidence_level = float(confidence_level)
+        return TrendEstimate.from_result(_quantile_call(lambda: self._trend(f, q, window, per)), per, method)
+
+    def _trend(self, f, q, window, per):
+        return self._eng().reduce_trend(q, window, per, f)
 
     def _spread_groups(self, q, kind, col):
         return self._eng().reduce_grouped_spread(q, kind, col)

@@ -16,8 +16,8 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "lib" / "libaqe_hip.so"
-SOURCES = [CSRC / "capi.hip", CSRC / "table.hip", CSRC / "plans.hip", CSRC / "kernels.hip", CSRC / "persist.hip", CSRC / "lean.hip", CSRC / "grouped.hip", CSRC / "quantile.hip", CSRC / "moments.hip", CSRC / "extremes.hip", CSRC / "histogram.hip", CSRC / "distinct.hip", CSRC / "grouped_distinct.hip", CSRC / "group_quantile.hip", CSRC / "summary.hip", CSRC / "timeseries.hip", CSRC / "wide_group.hip", CSRC / "time_group.hip", CSRC / "time_window.hip", CSRC / "window_group.hip", CSRC / "group_index.hip", CSRC / "budget_group.hip", CSRC / "having_host.hip", CSRC / "filter.hip", CSRC / "sort.hip", CSRC / "comm.hip", CSRC / "mailbox.hip", CSRC / "planner.cpp", CSRC / "top_host.cpp", CSRC / "group_quantile_host.cpp"]
-HEADERS = [CSRC / "host.hpp", CSRC / "kernels.hpp", CSRC / "device_common.hpp", CSRC / "spread_core.hpp", CSRC / "extreme_core.hpp", CSRC / "sweep_host.hpp", CSRC / "key_term.hpp", CSRC / "planner.hpp", CSRC / "top_order.hpp", CSRC / "having_core.hpp", CSRC / "distinct_core.hpp", CSRC / "quantile_core.hpp", CSRC / "budget_core.hpp", CSRC / "zone_probe.hpp", CSRC / "time_bucket_core.hpp", ROOT / "include" / "aqe_hip.h"]
+SOURCES = [CSRC / "capi.hip", CSRC / "table.hip", CSRC / "plans.hip", CSRC / "kernels.hip", CSRC / "persist.hip", CSRC / "lean.hip", CSRC / "grouped.hip", CSRC / "quantile.hip", CSRC / "moments.hip", CSRC / "extremes.hip", CSRC / "histogram.hip", CSRC / "distinct.hip", CSRC / "grouped_distinct.hip", CSRC / "group_quantile.hip", CSRC / "summary.hip", CSRC / "timeseries.hip", CSRC / "wide_group.hip", CSRC / "time_group.hip", CSRC / "time_window.hip", CSRC / "window_group.hip", CSRC / "trend.hip", CSRC / "group_index.hip", CSRC / "budget_group.hip", CSRC / "having_host.hip", CSRC / "filter.hip", CSRC / "sort.hip", CSRC / "comm.hip", CSRC / "mailbox.hip", CSRC / "planner.cpp", CSRC / "top_host.cpp", CSRC / "group_quantile_host.cpp"]
+HEADERS = [CSRC / "host.hpp", CSRC / "kernels.hpp", CSRC / "device_common.hpp", CSRC / "spread_core.hpp", CSRC / "extreme_core.hpp", CSRC / "sweep_host.hpp", CSRC / "key_term.hpp", CSRC / "planner.hpp", CSRC / "top_order.hpp", CSRC / "having_core.hpp", CSRC / "distinct_core.hpp", CSRC / "quantile_core.hpp", CSRC / "budget_core.hpp", CSRC / "zone_probe.hpp", CSRC / "time_bucket_core.hpp", CSRC / "trend_core.hpp", ROOT / "include" / "aqe_hip.h"]
 ARCH = "gfx950"
 
 

@@ -21,6 +21,7 @@
     python -m approximatequeryengine_amd.cli "SELECT SUM(amount) FROM sales WHERE timestamp BETWEEN 0 AND 86399 GROUP BY BUCKET(timestamp, 3600)" --db sales.db --s 10 --ci
     python -m approximatequeryengine_amd.cli "SELECT product_id, AVG(amount) FROM sales GROUP BY product_id HAVING COUNT(*) >= 30 AND SUM(amount) > 1e6" --db sales.db --s 10
     python -m approximatequeryengine_amd.cli "SELECT STDDEV(amount) FROM sales WHERE timestamp BETWEEN 86400 AND 172799 AND region = 2" --db sales.db --s 10 --time-where
+    python -m approximatequeryengine_amd.cli "SELECT TREND(amount) FROM sales WHERE timestamp BETWEEN 0 AND 2591999 AND region = 2" --db sales.db --s 10 --ci --trend-per 86400
     python -m approximatequeryengine_amd.cli --explain
 
 The reference's own CLI defines `-s/--sample` and `-e/--error` but tests `args.s` / `args.e`
@@ -86,6 +87,7 @@ _PERCENTILES = "PERCENTILE(?:_CONT|_DISC)?"
 _SPREADS = "VARIANCE|VAR_SAMP|VAR_POP|STDDEV(?:_SAMP|_POP)?"
 _EXTREMES = "MIN|MAX"
 _SUMMARIES = "SUMMARY|DESCRIBE"
+_TRENDS = "TREND|REGR_SLOPE|CORR"
 _APPROX_DISTINCT = "APPROX_COUNT_DISTINCT"
 _COUNT_DISTINCT = r"COUNT\s*\(\s*DISTINCT\b"
 
@@ -191,6 +193,26 @@ def summary_of(query: str) -> Optional[bool]:
     return True
 
 
+def trend_of(query: str) -> Optional[str]:
+    """TREND(amount) / REGR_SLOPE(amount, timestamp) / CORR(amount, timestamp), in any letter case -> the name typed, in upper
+    case (the three print the same block); None for a query that is not the family's.  ValueError, quoting the offending text, for
+    other columns: the trend is that of amount over timestamp."""
+    if _shut_out("trend", query):
+        return None
+    m = re.search(rf"\b({_TRENDS})\s*\(([^)]*)\)", query, re.IGNORECASE)
+    if not m:
+        return None
+    name, cols = m.group(1).upper(), [c.strip().lower() for c in m.group(2).split(",")]
+    want = ["amount"] if name == "TREND" else ["amount", "timestamp"]
+    if cols != want:
+        bad = next((c for c, w in zip(cols, want) if c != w), None)
+        shown = " ".join(m.group(0).split())
+        if bad is not None:
+            raise ValueError(f"'{shown}': unknown column {bad!r} ({name} takes ({', '.join(want)}))")
+        raise ValueError(f"'{shown}': {name} takes ({', '.join(want)})")
+    return name
+
+
 class _Family(NamedTuple):
     name: str
     names: str  # the function names that are the family's, as an alternation
@@ -208,6 +230,7 @@ _FAMILIES = (
     _Family("histogram", "HISTOGRAM", histogram_of),
     _Family("distinct", f"COUNT|{_APPROX_DISTINCT}", distinct_of, plain=r"(?:SUM|AVG)\(|COUNT\((?!\s*DISTINCT\b)"),
     _Family("summary", _SUMMARIES, summary_of),
+    _Family("trend", _TRENDS, trend_of),
 )
 
 
@@ -473,6 +496,18 @@ _REFUSALS = {
     "summary": (
         (_has_e, "SUMMARY has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
         (_grouped, "GROUP BY is not supported with SUMMARY")),
+    "trend": (
+        (_has_e, "TREND has no error-threshold (--e) form: give a sample percentage (--s) or none (exact)"),
+        (_grouped, "GROUP BY is not supported with TREND (a trend per group or per bucket is not built)"),
+        (lambda q, args: getattr(args, "quantile_by", None) is not None, "TREND has no --quantile-by form: the flag goes with MEDIAN / PERCENTILE"),
+        (lambda q, args: getattr(args, "quantile_bucket", None) is not None, "TREND has no --quantile-bucket form: the flag goes with MEDIAN / PERCENTILE"),
+        (lambda q, args: getattr(args, "series_by", None) is not None, "TREND has no --series-by form: the flag goes with GROUP BY BUCKET(timestamp, W)"),
+        (lambda q, args: getattr(args, "distinct_by", None) is not None, "TREND has no --distinct-by form: the flag goes with COUNT(DISTINCT col)"),
+        (lambda q, args: getattr(args, "max_groups", None) is not None, "TREND has no --max-groups form: the flag goes with GROUP BY"),
+        (lambda q, args: getattr(args, "per_group", None) is not None, "TREND has no --per-group form: the flag goes with GROUP BY"),
+        (lambda q, args: getattr(args, "time_where", False), "TREND reads the WHERE clause's timestamp terms as its window by itself: leave --time-where out"),
+        (lambda q, args: getattr(args, "group_time_where", False), "TREND has no --group-time-where form: the flag goes with GROUP BY region | product_id"),
+        (lambda q, args: len(key_where_of(q) or ()) > 1, "TREND takes a key predicate on ONE of region / product_id: the time offsets take one of the sweep's two key slots")),
     "--time-where": (
         (_has_e, "--time-where has no error-threshold (--e) form: the CLT sampler samples the whole table; give a sample percentage (--s) or none (exact)"),
         (_grouped, "--time-where has no GROUP BY form: a WHERE timestamp window is honoured by the ungrouped SUM / AVG / COUNT / VARIANCE / STDDEV "
@@ -485,6 +520,7 @@ _REFUSALS = {
         (lambda q, args: distinct_of(q) is not None or re.search(rf"\b{_COUNT_DISTINCT}|\b{_APPROX_DISTINCT}\s*\(", q, re.IGNORECASE),
          "--time-where has no COUNT(DISTINCT) form: a WHERE timestamp window is honoured by SUM, AVG, COUNT, VARIANCE and STDDEV"),
         (_names("summary"), "--time-where has no SUMMARY form: a WHERE timestamp window is honoured by SUM, AVG, COUNT, VARIANCE and STDDEV"),
+        (_names("trend"), "--time-where has no TREND form: TREND reads the WHERE clause's timestamp terms as its window by itself (leave the flag out)"),
         (lambda q, args: len(key_where_of(q) or ()) > 1, "--time-where takes a key predicate on ONE of region / product_id: the time offsets take one of the sweep's two key slots")),
     "--group-time-where": (
         (lambda q, args: not _grouped(q, args), "--group-time-where takes a GROUP BY region | product_id query: it makes the WHERE clause's timestamp terms count "
@@ -500,6 +536,7 @@ _REFUSALS = {
         (lambda q, args: distinct_of(q) is not None or re.search(rf"\b{_COUNT_DISTINCT}|\b{_APPROX_DISTINCT}\s*\(", q, re.IGNORECASE),
          "--group-time-where has no COUNT(DISTINCT) form: GROUP BY under a timestamp window takes SUM, AVG or COUNT"),
         (_names("summary"), "--group-time-where has no SUMMARY form: GROUP BY under a timestamp window takes SUM, AVG or COUNT"),
+        (_names("trend"), "--group-time-where has no TREND form: GROUP BY under a timestamp window takes SUM, AVG or COUNT"),
         (lambda q, args: any(c != group_by_of(q)[0].lower() for c in (key_where_of(q) or ())),
          "--group-time-where takes a key predicate on the group column only: a term on the other key column would need a third key slot")),
     "GROUP BY": (
@@ -522,7 +559,7 @@ def time_bucket_defect(clean: str, args) -> Optional[str]:
     why = _refusal("BUCKET", clean, args)
     if why is not None:
         return why
-    no_form = rf"{_called('quantile', 'spread', 'extreme', 'histogram', 'summary')}|\b{_APPROX_DISTINCT}\s*\("
+    no_form = rf"{_called('quantile', 'spread', 'extreme', 'histogram', 'summary', 'trend')}|\b{_APPROX_DISTINCT}\s*\("
     m = re.search(no_form, clean, re.IGNORECASE) or re.search(rf"\b{_COUNT_DISTINCT}", clean, re.IGNORECASE)
     if m:
         return f"{' '.join(m.group(0).split()).rstrip('(').strip().upper()} has no GROUP BY BUCKET(...) form: time buckets take SUM, AVG or COUNT"
@@ -795,6 +832,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--quantile-bucket", dest="quantile_bucket", metavar="W[,ORIGIN]", help="with MEDIAN / PERCENTILE: one value per time bucket of width W "
                    "(from ORIGIN, default 0), from one collecting sweep and a sort; at most 1024 buckets; the WHERE clause's timestamp terms are the "
                    "window, a key predicate on one key column is honoured")
+    p.add_argument("--trend-per", dest="trend_per", type=float, metavar="SECONDS", help="with TREND(amount): report the slope per SECONDS timestamp units "
+                   "(default 1; 86400: per day of a table in seconds)")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="under torchrun (one process per GPU): the torch.distributed backend (nccl = RCCL)")
     p.add_argument("--collective", choices=["torch", "mailbox"], default="torch", help="under torchrun: the all-reduce of the moment vectors "
@@ -815,6 +854,9 @@ def _query_defect(pq: ParsedQuery, args) -> Optional[str]:
     why = _refusal(family, clean, args)
     if why is not None:
         return why
+    if family == "trend":  # the WHERE clause's timestamp terms are this family's window: read for their ValueError
+        from .engine import parse_time_where
+        parse_time_where(clean)
     pq.group_by  # (read for its ValueError)
     if pq.key_where is not None:
         if args.e is not None:
@@ -1329,8 +1371,50 @@ def _run_time_series(db, args, out, pq, qtype, agg, t0, kw) -> int:
     return 0
 
 
+def trend_verdict(res) -> str:
+    """The one verdict line of a TREND block: the sign of the slope when its interval excludes 0."""
+    if res.has_slope and res.settled:
+        return "rising" if res.slope > 0 else "falling"
+    return "no trend beyond the sampling error"
+
+
+def _run_trend(db, args, out, pq, qtype, t0, kw) -> int:
+    """TREND(amount) / REGR_SLOPE(amount, timestamp) / CORR(amount, timestamp): one sweep, one block whichever name was typed.
+    The WHERE clause's timestamp terms are the window (no --time-where), its amount and key terms keep their meaning.  Lines in a
+    fixed order: slope (interval under --ci), correlation, r2, mean time and amount, n / visited, the verdict."""
+    from .engine import parse_time_where
+    window = parse_time_where(pq.rest)
+    per = getattr(args, "trend_per", None)
+    per = 1.0 if per is None else per
+    method, pct, name = _sampling(args, qtype)
+    try:
+        res = db.approx_trend(method=method, sample_percent=pct, where=pq.amount_where, time_between=window, per=per,
+                              confidence_level=args.confidence, seed=args.seed, num_threads=args.threads, **kw)
+    except ValueError as e:  # (--trend-per not positive, a timestamp range of 2^31 or more)
+        print(f"error: {e}", file=out)
+        return 2
+    ms = (time.perf_counter() - t0) * 1e3
+    ci = args.ci and method != "exact"
+    if window is not None:
+        print(f"window: timestamp {window[0]} .. {window[1]}", file=out)
+    print(f"\n{name} TREND(amount) result:", file=out)
+    between = f"   ({_num(res.slope_lo)} - {_num(res.slope_hi)})" if (ci and res.has_interval) else ""
+    print(f"   slope:       {_num(res.slope)} per {per:g} timestamp unit{'s' if per != 1 else ''}{between}", file=out)
+    between = f"   ({_num(res.r_lo)} - {_num(res.r_hi)}; Fisher, normal theory)" if (ci and res.has_r_interval) else ""
+    print(f"   correlation: {_num(res.r)}{between}", file=out)
+    print(f"   r2:          {_num(res.r2)}", file=out)
+    print(f"   mean time:   {_num(res.mean_time)}   mean amount: {_num(res.mean_amount)}", file=out)
+    print(f"   samples used: {res.n:,} of {res.visited:,} visited", file=out)
+    print(f"   verdict: {trend_verdict(res)}", file=out)
+    print(f"   execution time: {ms:.2f} ms (kernels {res.kernel_ms * 1e3:.1f} us)", file=out)
+    if args.compare and method != "exact":
+        exact = db.approx_trend(method="exact", where=pq.amount_where, time_between=window, per=per, **kw)
+        _print_comparison(out, res.slope, exact.slope, _num)
+    return 0
+
+
 _RUNNERS = {"quantile": _run_quantile, "spread": _run_spread, "extreme": _run_extremes, "histogram": _run_histogram,
-            "distinct": _run_distinct, "summary": _run_summary}
+            "distinct": _run_distinct, "summary": _run_summary, "trend": _run_trend}
 
 
 def main(argv=None) -> int:

@@ -110,6 +110,7 @@ struct aqe_series_scratch;  // time_group.hip
 struct aqe_budget_scratch;  // budget_group.hip
 struct aqe_window_scratch;  // time_window.hip
 struct aqe_wgroup_scratch;  // window_group.hip
+struct aqe_trend_scratch;  // trend.hip
 
 // The rows of one key column sorted by key (group_index.hip): what the budgeted GROUP BY sweeps.  The host mirrors of the
 // listed keys and segment offsets (at most 65 536 + 1 entries) are what a call plans its launch from.
@@ -215,6 +216,8 @@ struct aqe_ctx {
     aqe_window_scratch* window = nullptr;
     // GROUP BY under a timestamp window (window_group.hip): the slices' partials, the summed bins and the tile words, made on first use
     aqe_wgroup_scratch* wgroup = nullptr;
+    // TREND(amount) (trend.hip): partials, tickets, skip words and the pinned result of the co-moment sweep, made on first use
+    aqe_trend_scratch* trend = nullptr;
     // diagnostics (aqe_last_load_policy): the instantiation the most recent launch of a visit_tile kernel was — 1 non-temporal,
     // 0 plain loads, -1 no such launch yet.  Index-list sweeps and the quantile pass have the plain one only.
     int last_nt = -1;
@@ -431,6 +434,9 @@ int window_counts(aqe_ctx* c, hipStream_t s, unsigned long long** dev_counts);
 
 // window_group.hip
 void window_group_release(aqe_ctx* c);
+
+// trend.hip
+void trend_release(aqe_ctx* c);
 
 // group_index.hip
 int ensure_group_index(aqe_ctx* c, int column);  // builds c->gindex[column - 1] on first use; sets gindex_built_now

@@ -587,6 +587,7 @@ void aqe_destroy(aqe_ctx* c) {
     wide_release(c);
     series_release(c);
     budget_release(c);
+    trend_release(c);
     window_group_release(c);
     window_release(c);
     free_table(c);

@@ -471,6 +471,28 @@ def sharded_windowed(engine, query, time_between, vec, all_reduce_sum: Callable,
     return _swept_vector(vec, SPREAD_VEC, all_reduce_sum, stream, lambda *a: engine.windowed_enqueue(query, time_between, *a, key_filter=key_filter), finish)
 
 
+def sharded_trend(engine, query, time_between, per: float, vec, all_reduce_sum: Callable, all_reduce_max: Callable, stream: int = 0, key_filter=None):
+    """TREND(amount) — slope and correlation of amount over timestamp — across the ranks of a process group (engine.Engine
+    interface), collective.  The table's timestamp range is agreed in ONE all-reduce MAX (``_agree_int64``, as
+    sharded_time_series), every rank derives the same frame (centre, half) from it on the host (engine.trend_frame: a range of
+    2^31 or more is refused on every rank alike, before the sweep), sweeps the part of the sample inside its shard into
+    TREND_VEC sums in that frame (aqe_trend_enqueue; the frame and the window are converted against the rank's own time_min, a
+    shard the window misses publishes its visited count and zeros), ONE all-reduce SUM merges them and every rank finishes the
+    same vector on the host — so every rank returns the same bits.  ``time_between``: (t_lo, t_hi) or None.
+
+    vec     float64 tensor on the engine's device with room for TREND_VEC doubles
+    stream  raw handle of the stream the collectives are issued on; 0 = torch's current stream (see ``_stream_for``)."""
+    from ._native import TREND_VEC
+    from .engine import trend_frame
+    with _on_stream(stream, vec) as stream:
+        v = _take(vec, TREND_VEC, vector=True)
+        (tmin, tmax), = _agree_int64([engine.time_range()], v, all_reduce_max)
+        centre, half = trend_frame(tmin, tmax, time_between)
+        engine.trend_enqueue(query, time_between, centre, half, v.data_ptr(), stream, key_filter)
+        all_reduce_sum(v)
+        return engine.trend_finish(query, v.data_ptr(), centre, half, per, stream)
+
+
 def sharded_filtered_group_by(engine, key_filter, query, group_column: int, bins, all_reduce_sum: Callable, all_reduce_max: Callable,
                               stream: int = 0, kind=None):
     """GROUP BY under a key filter across ranks: the key range is agreed (one MAX all-reduce of [-min, max], as sharded_group_by),

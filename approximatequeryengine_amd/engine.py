@@ -638,6 +638,32 @@ class Engine:
         lo, hi = time_window(time_between)
         self._chk(nat.lib().aqe_windowed_enqueue(self._h, C.byref(query), _filter_ref(key_filter), lo, hi, C.c_void_p(dev_vec_ptr), C.c_void_p(stream)))
 
+    # -- TREND(amount): slope and correlation of amount over timestamp (aqe_reduce_trend and its kin; trend.hip): key_filter may be None --
+    def reduce_trend(self, query: Query, time_between=None, per: float = 1.0, key_filter: "Optional[nat.KeyFilter]" = None) -> "nat.TrendResult":
+        """The least-squares slope of amount over timestamp (times ``per``), its sandwich interval, the correlation with Fisher's
+        interval and the means, over the sampled rows that pass the query's amount range, the key filter and the optional
+        inclusive window ``time_between`` = (t_lo, t_hi): one fused sweep.  visited counts every sampled row, n the rows that
+        pass (NaN amounts are left out)."""
+        has, lo, hi = _trend_window(time_between)
+        out = nat.TrendResult()
+        self._chk(nat.lib().aqe_reduce_trend(self._h, C.byref(query), _filter_ref(key_filter), has, lo, hi, float(per), C.byref(out)))
+        return out
+
+    def trend_enqueue(self, query: Query, time_between, centre: float, half: float, dev_vec_ptr: int, stream: int = 0,
+                      key_filter: "Optional[nat.KeyFilter]" = None):
+        """This shard's TREND_VEC sums in the frame (centre, half) of trend_frame, into device memory (all-reduce SUM, then
+        trend_finish); the frame and the window are converted against this shard's own time_min."""
+        has, lo, hi = _trend_window(time_between)
+        self._chk(nat.lib().aqe_trend_enqueue(self._h, C.byref(query), _filter_ref(key_filter), has, lo, hi, float(centre), float(half),
+                                              C.c_void_p(dev_vec_ptr), C.c_void_p(stream)))
+
+    def trend_finish(self, query: Query, dev_vec_ptr: int, centre: float, half: float, per: float = 1.0, stream: int = 0) -> "nat.TrendResult":
+        """The figures from a summed TREND_VEC vector in device memory: waits for ``stream``, then host arithmetic."""
+        out = nat.TrendResult()
+        self._chk(nat.lib().aqe_trend_finish(self._h, C.byref(query), C.c_void_p(dev_vec_ptr), C.c_void_p(stream), float(centre), float(half), float(per),
+                                             C.byref(out)))
+        return out
+
     @contextlib.contextmanager
     def device_doubles(self, count: int):
         """``count`` doubles of device memory for the length of a ``with`` block (aqe_device_malloc / aqe_device_free): the raw
@@ -1187,6 +1213,40 @@ def time_window(time_between) -> Tuple[int, int]:
     if out[0] > out[1]:
         raise ValueError(f"time window: the window is empty (t_lo {out[0]} > t_hi {out[1]})")
     return out[0], out[1]
+
+
+def _trend_window(time_between) -> Tuple[int, int, int]:
+    """(has_window, t_lo, t_hi) of a ``time_between`` argument that may be None."""
+    if time_between is None:
+        return 0, 0, 0
+    lo, hi = time_window(time_between)
+    return 1, lo, hi
+
+
+def trend_frame(time_min: int, time_max: int, time_between=None) -> Tuple[float, float]:
+    """aqe_trend_frame, host only: (centre, half) of the frame TREND(amount) conditions its time sums in — the midpoint and half the
+    width (at least 1) of the window clipped to [time_min, time_max], of the whole range without a window.  AqeError for a range
+    of 2^31 or more."""
+    has, lo, hi = _trend_window(time_between)
+    centre, half = C.c_double(), C.c_double()
+    rc = nat.lib().aqe_trend_frame(int(time_min), int(time_max), has, lo, hi, C.byref(centre), C.byref(half))
+    if rc != nat.OK:
+        nat.check(rc)
+    return centre.value, half.value
+
+
+def trend_from_vec(vec, shift: float, centre: float, half: float, per: float = 1.0, confidence_level: float = 0.95, exact: bool = False) -> "nat.TrendResult":
+    """aqe_trend_from_vec, host only: the figures of TREND(amount) from TREND_VEC summed doubles swept with the shift ``shift`` in the
+    frame (centre, half)."""
+    v = np.ascontiguousarray(vec, dtype=np.float64)
+    if v.size != nat.TREND_VEC:
+        raise ValueError(f"the vector holds {v.size} doubles, TREND_VEC = {nat.TREND_VEC} needed")
+    out = nat.TrendResult()
+    rc = nat.lib().aqe_trend_from_vec(v.ctypes.data_as(C.POINTER(C.c_double)), float(shift), float(centre), float(half), float(per),
+                                      float(confidence_level), 1 if exact else 0, C.byref(out))
+    if rc != nat.OK:
+        nat.check(rc)
+    return out
 
 
 def time_window_offsets(time_min: int, time_max: int, t_lo: int, t_hi: int) -> Tuple[int, int]:

@@ -32,7 +32,7 @@ from .distributed import (MOMENT_VEC, ShardedBatch, ShardedQuery, mailbox_all_re
                           sharded_distinct, sharded_distinct_groups, sharded_extremes, sharded_filtered, sharded_filtered_group_by, sharded_group_by, sharded_group_by_budget, sharded_group_by_error,
                           sharded_group_by_having, sharded_group_by_pair, sharded_group_by_spread, sharded_group_by_top, sharded_group_by_wide, sharded_group_by_window,
                           sharded_group_extremes, sharded_histogram, sharded_quantile_groups, sharded_quantile_series, sharded_quantiles, sharded_spread, sharded_stratified_plan, sharded_summary,
-                          sharded_time_groups, sharded_time_series, sharded_windowed, torch_all_reduce, torch_host_all_reduce)
+                          sharded_time_groups, sharded_time_series, sharded_trend, sharded_windowed, torch_all_reduce, torch_host_all_reduce)
 from .engine import RECORD_DTYPE, Batch, Engine
 
 
@@ -288,6 +288,10 @@ class ShardedBPlusDB(CustomBPlusDB):
 
     def _spread_windowed(self, f, q, kind, window):
         return self._sharded(sharded_windowed, nat.SPREAD_VEC, q, window, sum_only=True, kind=kind, key_filter=f)
+
+    # TREND(amount): one MAX all-reduce of the timestamp range, the same frame on every rank, one all-reduce SUM of 16 sums
+    def _trend(self, f, q, window, per):
+        return self._sharded(sharded_trend, nat.TREND_VEC, q, window, per, key_filter=f)
 
     def _grouped_filtered(self, f, q, col):
         return self._sharded(sharded_filtered_group_by, nat.SPREAD_BIN * 1024, f, q, col)

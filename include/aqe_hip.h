@@ -1852,6 +1852,95 @@ AQE_API int aqe_reduce_window_groups(aqe_ctx* ctx, const aqe_key_filter* filter 
 AQE_API int aqe_window_groups_enqueue_bins(aqe_ctx* ctx, const aqe_key_filter* filter /* may be NULL */, const aqe_query* q, int group_column, int64_t t_lo,
                                            int64_t t_hi, int32_t key_min, uint32_t span, double* dev_bins, void* stream);
 
+/* ---- TREND(amount): least-squares slope and correlation of amount over timestamp, one sweep (trend.hip, trend_core.hpp) ----------
+ * Rows.  The sampled rows that pass are (t_i, x_i), i = 1 .. n.  A row passes when it meets the inclusive amount range
+ * (aqe_query.has_where), the key term (`filter`, NULL: none; a term on ONE of region / product_id), the optional inclusive
+ * window t_lo <= timestamp <= t_hi (has_window), and x is no NaN (a NaN would poison every sum, so it is left out of n as
+ * aqe_reduce_summary leaves it out).  The row rule is aqe_reduce_windowed's, not the bucketed forms': `visited` counts every
+ * sampled row, `n` the rows that pass, and no N / visited scaling enters any figure.
+ *
+ * Figures.  With T = t - mean(t), X = x - mean(x), sums over the passing rows:
+ *     slope        b = sum TX / sum T^2, the least-squares slope of the sampled rows in amount per timestamp unit, times `per`
+ *                  (1: per unit; 86400: "per day" of a table in seconds)
+ *     mean_time, mean_amount    mean(t), mean(x)
+ *     intercept    mean(x) - b mean(t), a plain double: for epoch-sized timestamps it loses the digits b mean(t) cancels, which
+ *                  the slope keeps — predict from (mean_time, mean_amount, slope), not from the intercept
+ *     slope_lo, slope_hi        b -+ z se, se = sqrt(sum T^2 e^2) / sum T^2, e = X - b T: the linearisation (sandwich, HC0)
+ *                  standard error of the table's own least-squares slope under sampling; it assumes neither a linear model nor
+ *                  equal variances.  z = 2.576 / 1.96 / 1.645 from q.confidence_level as everywhere.  Needs n >= 3
+ *                  (has_interval); AQE_M_EXACT reports [b, b].
+ *     r, r2        sum TX / sqrt(sum T^2 sum X^2) and its square
+ *     r_lo, r_hi   tanh(atanh r -+ z / sqrt(n - 3)), n >= 4 (has_r_interval): FISHER'S NORMAL-THEORY interval — exact in
+ *                  distribution only for bivariate normal rows, a rough guide otherwise; |r| = 1 gives [r, r], as AQE_M_EXACT does
+ *     settled      1 when the slope interval excludes 0, else 0
+ * Degenerate inputs are answers, not errors (AQE_OK, NaN figures, flags 0): n < 2 or sum T^2 == 0 (one distinct timestamp) has
+ * no slope (has_slope 0; the means are reported from n >= 1); sum X^2 == 0 has slope 0 (interval [0, 0]) and r NaN.
+ * visited == 0 is AQE_ERR_INVALID "No samples collected".
+ *
+ * Conditioning.  The kernel never forms powers of raw time offsets.  The host picks a frame (aqe_trend_frame): the centre T_c is
+ * the midpoint of the window clipped to the table's [time_min, time_max] (of the whole range without a window, or when the window
+ * misses it), the half-width h = max(half that range, 1), both doubles in absolute timestamp units.  A shard converts the frame
+ * against its own time_min: u = (double(offset) - a) (1 / h), a = T_c - time_min, so |u| <= 1 for every row inside the window.
+ * Amounts are shifted as everywhere else, d = x - c (the query's shift).  A row that fails contributes u = d = 0.0 to sums that
+ * start at +0.0, so a tile the zone map skips leaves every word bit-identical to reading it.
+ * The vector, AQE_TREND_VEC doubles, all additive over shards that use the same frame and shift:
+ *     [0] n  [1] sum u  [2] sum u^2  [3] sum u^3  [4] sum u^4  [5] visited  [6] sum d  [7] n c
+ *     [8] sum d^2  [9] sum u d  [10] sum u^2 d  [11] sum u^3 d  [12] sum u d^2  [13] sum u^2 d^2  [14] 0  [15] 0
+ * trend_core centres them by binomial expansion (sum U^2, sum UD, sum D^2, sum U^4, sum U^3 D, sum U^2 D^2 with U = u - mean u,
+ * D = d - mean d), forms sum U^2 e^2 = sum U^2 D^2 - 2 b sum U^3 D + b^2 sum U^4, clamps the even sums at 0, and scales b by
+ * per / h; mean_time = T_c + h mean(u), mean_amount = c + mean(d).  One copy of that arithmetic runs in the last workgroup,
+ * in aqe_trend_finish and in aqe_trend_from_vec: the three agree to the bit (the interval of r uses a tanh built from + - * /
+ * only, so that host and device round alike).
+ *
+ * The sweep (k_trend) is k_window's: time offsets in key slot 0, one key column under a term in slot 1, the seeded random
+ * sampler through its index list (no skip), on tiles the zone map probed one tile ahead and a tile that cannot meet the window
+ * skipped with no load (AQE_ZONE_SKIP=0 reads every tile); without a window no zone map is consulted.  aqe_last_window_tiles
+ * reports {tiles, skipped} of the launch.  Per lane eleven double sums and two counters; wave butterflies, LDS in wave order,
+ * two [grid][8] partial arrays, sharded arrival tickets, the last workgroup adds in a fixed order: no floating-point atomics, the
+ * answer is bit-identical from run to run.  AQE_NT=0/1 picks the load flavour, which aqe_last_load_policy reports.
+ *
+ * Refusals, each by name before any launch: key terms on both key columns (AQE_ERR_UNSUPPORTED: a third key slot), t_lo > t_hi
+ * under has_window (AQE_ERR_INVALID), timestamps that span 2^31 or more (AQE_ERR_UNSUPPORTED), the CLT (error-threshold),
+ * adaptive, stratified, AQE_M_RANDOM_DEVICE and pair-family samplers ("TREND does not take the ... sampler"), `per` not finite
+ * or <= 0, a half-width not finite or <= 0 (AQE_ERR_INVALID). */
+#define AQE_TREND_VEC 16
+typedef struct aqe_trend_result {
+    double slope;                  /* amount per `per` timestamp units; NaN without has_slope */
+    double slope_lo, slope_hi;     /* NaN without has_interval */
+    double intercept;              /* mean_amount - (slope / per) mean_time */
+    double mean_time, mean_amount; /* NaN when n == 0 */
+    double r, r2;                  /* NaN without has_slope, or when the amounts that pass are all equal */
+    double r_lo, r_hi;             /* Fisher's normal-theory interval; NaN without has_r_interval */
+    uint64_t n;                    /* rows that pass */
+    uint64_t visited;              /* sampled rows */
+    int32_t has_slope, has_interval, has_r_interval;
+    int32_t settled;               /* the slope interval excludes 0 */
+    int32_t device_status;         /* 0 ok */
+    int32_t reserved;
+    double kernel_ms;              /* aqe_reduce_trend: device time of the launch */
+} aqe_trend_result;
+/* Host only, no GPU and no context (aqe_last_error(NULL) has a refusal's text): the one copy of the frame rule.  has_window == 0:
+ * t_lo, t_hi are not read.  time_min > time_max (no rows): centre 0, half 1.  AQE_ERR_INVALID: t_lo > t_hi.
+ * AQE_ERR_UNSUPPORTED: time_max - time_min >= 2^31. */
+AQE_API int aqe_trend_frame(int64_t time_min, int64_t time_max, int has_window, int64_t t_lo, int64_t t_hi, double* centre, double* half);
+/* Host only: trend_core on a summed vector.  shift: the c of d = x - c the vector was swept with; exact != 0: the intervals
+ * collapse onto the values. */
+AQE_API int aqe_trend_from_vec(const double* vec16, double shift, double centre, double half, double per, double confidence_level, int exact,
+                               aqe_trend_result* out);
+/* Single GPU, synchronous: the frame from this table's timestamp range, one fused launch, timed by events. */
+AQE_API int aqe_reduce_trend(aqe_ctx* ctx, const aqe_query* q, const aqe_key_filter* filter /* may be NULL */, int has_window, int64_t t_lo, int64_t t_hi,
+                             double per, aqe_trend_result* out);
+/* Multi-GPU form: the ranks agree on the table's timestamp range (aqe_time_range, all-reduced MIN / MAX), every rank calls
+ * aqe_trend_frame on the same numbers, then
+ *     aqe_trend_enqueue(ctx, q, filter, has_window, t_lo, t_hi, centre, half, dev_vec, stream)   this shard's AQE_TREND_VEC doubles
+ *                                                    (a shard the window misses publishes its visited count and zeros)
+ *     <ONE all-reduce SUM of AQE_TREND_VEC doubles on `stream`>
+ *     aqe_trend_finish(ctx, q, dev_vec, stream, centre, half, per, out)      waits for `stream`, host arithmetic on the summed vector */
+AQE_API int aqe_trend_enqueue(aqe_ctx* ctx, const aqe_query* q, const aqe_key_filter* filter /* may be NULL */, int has_window, int64_t t_lo, int64_t t_hi,
+                              double centre, double half, double* dev_vec, void* stream);
+AQE_API int aqe_trend_finish(aqe_ctx* ctx, const aqe_query* q, const double* dev_vec, void* stream, double centre, double half, double per,
+                             aqe_trend_result* out);
+
 #ifdef __cplusplus
 }
 #endif
